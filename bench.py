@@ -11,6 +11,11 @@
 One "step" = one env.step() of all envs of a rank = ONE launch of the step kernel (4 physics substeps, observation,
 reward, termination, in-kernel auto-reset), inputs resident in HBM.
 
+A plain run sets up, pre-rolls and warms up, times the K steps and prints the JSON line.  Everything else it can measure runs
+only with --full: the CPU baselines (`cpu_baseline`, with its `pybullet` leg) and, N = 1 only, the two untimed brackets
+(`sensitivity`, `workload_sensitivity`).  --dump-outputs DIR writes what the last timed step returned (obs, reward, done, info)
+as .npy files; the inputs depend only on the arguments, so two builds can be compared output for output.
+
 Multi-GPU: env batches are independent shards (each env is its own world in the reference, env_base.py:55): one
 process per GPU, env_offset = rank x envs, NO data-path collective and no RCCL -- the start/stop barrier and the MAX of
 the per-rank times go over a gloo (CPU) group.  Two ways in:
@@ -365,6 +370,31 @@ def workload_bracket(args, local_rank, lo, tape, steps=200, preroll=800):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, env, rank=0):
+    """--dump-outputs: the arrays the last timed env.step() handed its caller -- obs [N, obs_dim], reward [N], done [N] (bit 0 terminated,
+    bit 1 TimeLimit) and info [N] -- as DIR/<name>.npy in float32 (done, exact) or float64 (info, exact).  A batch whose arrays exceed
+    64 MB in all is written for a fixed seeded sample of its env rows, the sorted row ids as env_rows.npy."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    arrays = {"obs": env.obs.float().cpu().numpy(), "reward": env.rew.float().cpu().numpy(),
+              "done": env.done.float().cpu().numpy(), "info": env.info.double().cpu().numpy()}
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096          # the .npy headers
+    if env.n_envs * row_bytes > budget:
+        k = budget // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(env.n_envs, k, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["env_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -372,6 +402,12 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--envs", type=int, default=ENVS_PER_GPU, help="envs per GPU (4096 = the metric's config; 8192 = configs[4])")
     ap.add_argument("--env-id", default=ENV_ID)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baselines and (N = 1) the physics and workload brackets; "
+                         "--no-cpu-baseline / --no-physics-bracket / --no-workload-bracket drop one of them again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (obs, reward, done, info) to DIR/<name>.npy "
+                         "(float32 / float64; rank r > 0: <name>.rank<r>.npy; beyond 64 MB a fixed seeded sample of env rows, ids in env_rows.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--preroll", type=int, default=1000,
                     help="data preparation, before the W warm-up steps: env-steps that age the freshly reset batch into the steady-state mix of "
@@ -426,6 +462,8 @@ def parse_args(argv=None):
         args.no_physics_bracket = args.no_workload_bracket = True
     if args.host_io and args.stagger > 1:
         ap.error("--host-io times the synchronous host loop of ONE handle; it does not combine with --stagger")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU run; --dry-run computes nothing")
     return args
 
 
@@ -583,6 +621,12 @@ def main():
             # ranks reach the start barrier of the timed window within ~1 ms of each other.  A rank that waits there with an idle GPU for
             # 5 ms runs its whole 20-launch window 4 % slow, for >= 10 ms 9 % slow (profiles/archive/r04_idle_gap.txt),
             # and the job's time is the slowest rank's.
+            # How many launches fit into preroll_seconds varies from run to run: the batch is snapshotted before them and restored after
+            # (state, task record and, Stepper, terrain: what workload_bracket's exact replays restore), so the warm-up and the timed
+            # steps start from where the fixed --preroll left it and compute the same outputs on every run with the same arguments.
+            stepper = "Stepper" in args.env_id
+            handles = env.parts if subs else [env]
+            snaps = [(h.get_state(), h.get_task(), h.get_terrain() if stepper else None) for h in handles]
             torch.cuda.synchronize()
             barrier()
             t_pre = time.perf_counter()
@@ -592,6 +636,10 @@ def main():
                 preroll_steps += 8
                 torch.cuda.synchronize()
                 preroll_s = time.perf_counter() - t_pre
+            for h, (st, tk, tr) in zip(handles, snaps):
+                h.set_state(st); h.set_task(tk)
+                if tr is not None:
+                    h.set_terrain(tr)
         n_done = torch.zeros((), device=dev)
         for i in range(args.warmup):
             done = step_all(i, ordered=True)
@@ -622,16 +670,18 @@ def main():
         barrier()
         torch.cuda.synchronize()
         kern_ms = ev0.elapsed_time(ev1) / args.steps  # back-to-back launches: average launch duration incl. launch gaps
+        if args.dump_outputs:      # before anything below steps the batch again (--host-io)
+            dump_outputs(args.dump_outputs, env, rank)
         kinfo = env.kernel_info()
         bracket = None
-        if world == 1 and not args.no_physics_bracket and not subs and args.max_rows is None:
+        if args.full and world == 1 and not args.no_physics_bracket and not subs and args.max_rows is None:
             try:      # (untimed extra: a failure here must not cost the line its headline)
                 cassie = "Cassie" in args.env_id     # 50 physics steps per env.step: a shorter window
                 bracket = physics_bracket(args, local_rank, lo, tape, steps=40 if cassie else 200, preroll=150 if cassie else 800)
             except Exception as e:      # noqa: BLE001
                 bracket = {"error": f"{type(e).__name__}: {e}"}
         workloads = None
-        if world == 1 and not args.no_workload_bracket and not subs and args.max_rows is None:
+        if args.full and world == 1 and not args.no_workload_bracket and not subs and args.max_rows is None:
             try:
                 cassie = "Cassie" in args.env_id
                 workloads = workload_bracket(args, local_rank, lo, tape, steps=40 if cassie else 200, preroll=150 if cassie else 800)
@@ -748,7 +798,7 @@ def main():
             out["dry_run"] = True
         if args.oversubscribe:
             out["oversubscribed"] = True
-        if world == 1 and not args.no_cpu_baseline and not args.dry_run:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dry_run:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.env_id)
             except Exception as e:      # noqa: BLE001  (the reported baseline must not cost the line its GPU numbers)

@@ -104,11 +104,11 @@ def test_sub_batches_on_their_own_streams_reproduce_the_single_batch():
 
 @pytest.mark.gpu
 def test_default_bench_line_carries_both_brackets_and_the_baselines():
-    """`python bench.py` as the driver runs it (smaller batch here): ONE JSON line with `roofline`, `cpu_baseline` (incl. the `pybullet` leg's
+    """`python bench.py --full` (smaller batch here): ONE JSON line with `roofline`, `cpu_baseline` (incl. the `pybullet` leg's
     answer), the physics-law `sensitivity` bracket and the behaviour `workload_sensitivity` bracket, whose closed-loop workloads must replay
     exactly from their snapshots."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--envs", "512", "--steps", "10", "--warmup", "3", "--preroll", "50",
-                        "--preroll-seconds", "0"], capture_output=True, text=True, timeout=900)
+                        "--preroll-seconds", "0", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1
@@ -124,3 +124,29 @@ def test_default_bench_line_carries_both_brackets_and_the_baselines():
         assert w["replay_exact"] and w["value"] > 0 and 0 <= w["reset_fraction_per_step"] < 0.2, name
     assert ws["workloads"]["pd_to_t_pose"]["reset_fraction_per_step"] < ws["headline"]["reset_fraction_per_step"]      # the controller keeps robots up longer
     assert out["per_rank"]["device"][0]["name"] and out["per_rank"]["distinct_devices"] == 1
+
+
+@pytest.mark.parametrize("env_id", ["Walker3DCustomEnv-v0", "Walker3DStepperEnv-v0"])
+def test_plain_bench_line_is_lean_and_its_outputs_repeat(tmp_path, env_id):
+    """`python bench.py` without --full: the headline line alone (no CPU baseline, no bracket), and --dump-outputs writes what the last
+    timed step returned.  Two runs whose time-bound pre-rolls differ in length dump the same bits: the batch is restored after that
+    pre-roll, so the timed steps start from where the fixed --preroll left it."""
+    outs, dumps = [], []
+    for k, seconds in enumerate(("0.2", "0.5")):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--env-id", env_id, "--envs", "512", "--steps", "20", "--warmup", "5",
+                            "--preroll", "100", "--preroll-seconds", seconds, "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(line) == 1
+        outs.append(json.loads(line[0]))
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("obs", "reward", "done", "info")})
+    for out in outs:
+        assert out["steps"] == 20 and out["ms_per_step"] > 0 and out["value"] > 0 and out["higher_is_better"] and out["dtype"] == "f32"
+        assert not {"cpu_baseline", "sensitivity", "workload_sensitivity"} & set(out)
+    assert outs[0]["config"]["preroll_steps"] != outs[1]["config"]["preroll_steps"]
+    a, b = dumps
+    assert a["obs"].shape[0] == 512 and a["obs"].dtype == np.float32 and a["reward"].shape == (512,) and a["info"].dtype == np.float64
+    for n in a:
+        np.testing.assert_array_equal(a[n], b[n], err_msg=n)
+    assert np.isfinite(a["obs"]).all() and set(np.unique(a["done"])) <= {0.0, 1.0, 2.0, 3.0}

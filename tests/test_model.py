@@ -1,15 +1,15 @@
-"""Model compiler: the Walker3D table vs the reference XML (when present) and structural invariants."""
+"""Model compiler: the Walker3D table vs the reference XML (stored as a fixture) and structural invariants."""
+import json
 import math
 import os
-import xml.etree.ElementTree as ET
 
 import numpy as np
 import pytest
 
 from mocca_envs_amd import model as M
 
-REF_XML = "/root/reference/mocca_envs/data/robots/walker3d.xml"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF_XML = os.path.join(ROOT, "tests", "golden", "walker3d_xml.json")   # the reference's walker3d.xml numbers (tests/golden/make_walker3d_xml.py)
 
 
 def test_totals():
@@ -71,17 +71,11 @@ def test_topology_header_is_current():
     assert hdr == M.topology_header(M.compile_walker3d(), "Walker3D"), "run python -m mocca_envs_amd.model"
 
 
-@pytest.mark.skipif(not os.path.exists(REF_XML), reason="reference not mounted (GPU box)")
 def test_table_matches_reference_xml():
-    """Every number of data/robots/walker3d.xml that the compiler uses, re-read from the reference."""
-    root = ET.parse(REF_XML).getroot()
-    ref_bodies = {}
-
-    def rec(b, parent):
-        ref_bodies[b.get("name")] = (b, parent)
-        for ch in b.findall("body"):
-            rec(ch, b.get("name"))
-    rec(root.find("worldbody").find("body"), None)
+    """Every number of data/robots/walker3d.xml that the compiler uses, as the fixture tests/golden/walker3d_xml.json holds it."""
+    with open(REF_XML) as f:
+        ref = json.load(f)
+    ref_bodies = {b["name"]: (b, b["parent"]) for b in ref["bodies"]}
 
     def mine(b, parent, acc):
         acc[b.name] = (b, parent)
@@ -90,35 +84,33 @@ def test_table_matches_reference_xml():
         return acc
     my = mine(M.walker3d_description(), None, {})
     assert set(my) == set(ref_bodies)
-    f = lambda s: [float(x) for x in s.split()]
     for name, (rb, rparent) in ref_bodies.items():
         mb, mparent = my[name]
         assert mparent == rparent
-        np.testing.assert_allclose(mb.pos, f(rb.get("pos")), atol=1e-12)
-        if rb.get("quat"):
-            np.testing.assert_allclose(mb.quat_wxyz, f(rb.get("quat")), atol=1e-12)
-        rj = rb.findall("joint")
-        assert [j.get("name") for j in rj] == [h.name for h in mb.hinges]
+        np.testing.assert_allclose(mb.pos, rb["pos"], atol=1e-12)
+        if rb["quat"]:
+            np.testing.assert_allclose(mb.quat_wxyz, rb["quat"], atol=1e-12)
+        rj = rb["joints"]
+        assert [j["name"] for j in rj] == [h.name for h in mb.hinges]
         for j, h in zip(rj, mb.hinges):
-            np.testing.assert_allclose(h.axis, f(j.get("axis")), atol=1e-12)
-            np.testing.assert_allclose([h.lo_deg, h.hi_deg], f(j.get("range")), atol=1e-12)
-            np.testing.assert_allclose(mb.anchor, f(j.get("pos")), atol=1e-12)
-        rg = rb.findall("geom")
-        assert [g.get("name") for g in rg] == [g.name for g in mb.geoms]
+            np.testing.assert_allclose(h.axis, j["axis"], atol=1e-12)
+            np.testing.assert_allclose([h.lo_deg, h.hi_deg], j["range"], atol=1e-12)
+            np.testing.assert_allclose(mb.anchor, j["pos"], atol=1e-12)
+        rg = rb["geoms"]
+        assert [g["name"] for g in rg] == [g.name for g in mb.geoms]
         for g, mg in zip(rg, mb.geoms):
-            assert abs(mg.radius - f(g.get("size"))[0]) < 1e-12
-            if g.get("type") == "capsule":
-                ft = f(g.get("fromto"))
-                np.testing.assert_allclose(list(mg.p1) + list(mg.p2), ft, atol=1e-12)
+            assert abs(mg.radius - g["size"][0]) < 1e-12
+            if g["type"] == "capsule":
+                np.testing.assert_allclose(list(mg.p1) + list(mg.p2), g["fromto"], atol=1e-12)
                 assert mg.kind == M.GEOM_CAPSULE
             else:
-                np.testing.assert_allclose(mg.p1, f(g.get("pos")), atol=1e-12)
-            assert mg.group == int(g.get("contype", 3)) and mg.mask == int(g.get("conaffinity", 3))
-    d = root.find("default")
-    assert float(d.find("joint").get("armature")) == 0.01 and float(d.find("joint").get("damping")) == 0.1
+                np.testing.assert_allclose(mg.p1, g["pos"], atol=1e-12)
+            assert mg.group == g["contype"] and mg.mask == g["conaffinity"]
+    d = ref["default_joint"]
+    assert d["armature"] == 0.01 and d["damping"] == 0.1
     m = M.compile_walker3d()
     assert abs(m.jarm[1] - 0.01) < 1e-7 and abs(m.jdamp[1] - 0.1) < 1e-7  # fp32 blob
-    assert f(d.find("geom").get("friction"))[0] == pytest.approx(m.g_friction[0])
+    assert ref["default_geom"]["friction"][0] == pytest.approx(m.g_friction[0])
 
 
 def test_bullet_fidelity_switches_the_accuracy_instance_fields():

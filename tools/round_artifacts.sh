@@ -12,23 +12,23 @@ tools/profile_round.sh ${tag} Walker3DCustomEnv-v0 4096 > /dev/null 2>&1
 [ -s $O/${tag}_traffic.json ] && cp $O/${tag}_traffic.json profiles/traffic.json
 # 1. the driver's own invocation (what BENCH_rNN.json records) + a long steady-state line (with the CPU baselines)
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/${tag}_bench_driver_protocol.json 2> /dev/null
-python bench.py --steps 1000 --warmup 200 > $O/${tag}_bench_full.json 2> $O/${tag}_bench_full.err
+python bench.py --steps 1000 --warmup 200 --full > $O/${tag}_bench_full.json 2> $O/${tag}_bench_full.err
 # 2. batch-size sweep of the headline env (1 / 2 / 4 waves per SIMD resident, then 2 and 4 rounds of waves)
 for n in 512 1024 2048 4096 8192 16384; do
   python bench.py --envs $n --steps 400 --warmup 200 --no-cpu-baseline 2>/dev/null | tail -1 | \
     python -c "import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps({'envs': $n, 'kernel_us': round(1000*d['roofline']['kernel_ms'],1), 'env_steps_per_s': round(d['value'])}))"
 done > $O/${tag}_batch_sweep.jsonl
 # 3. the other configs / env ids (untraced bench lines)
-python bench.py --envs 8192 --steps 400 --warmup 200 --no-cpu-baseline --no-physics-bracket > $O/${tag}_custom8192_untraced_bench.json 2>/dev/null
-python bench.py --env-id Walker3DStepperEnv-v0 --curriculum 0 --steps 400 --warmup 200 --no-cpu-baseline > $O/${tag}_stepper_c0_bench.json 2>/dev/null
-python bench.py --env-id Walker3DStepperEnv-v0 --curriculum 9 --steps 400 --warmup 200 --no-cpu-baseline > $O/${tag}_stepper_c9_bench.json 2>/dev/null
-python bench.py --env-id CassieEnv-v0 --envs 2048 --steps 100 --warmup 30 --no-cpu-baseline > $O/${tag}_cassie_bench.json 2>/dev/null
+python bench.py --envs 8192 --steps 400 --warmup 200 --no-cpu-baseline --no-physics-bracket --full > $O/${tag}_custom8192_untraced_bench.json 2>/dev/null
+python bench.py --env-id Walker3DStepperEnv-v0 --curriculum 0 --steps 400 --warmup 200 --no-cpu-baseline --full > $O/${tag}_stepper_c0_bench.json 2>/dev/null
+python bench.py --env-id Walker3DStepperEnv-v0 --curriculum 9 --steps 400 --warmup 200 --no-cpu-baseline --full > $O/${tag}_stepper_c9_bench.json 2>/dev/null
+python bench.py --env-id CassieEnv-v0 --envs 2048 --steps 100 --warmup 30 --no-cpu-baseline --full > $O/${tag}_cassie_bench.json 2>/dev/null
 for e in Child3DCustomEnv-v0 MikeStepperEnv-v0 Walker2DCustomEnv-v0 Crab2DCustomEnv-v0 LaikagoCustomEnv-v0 LaikagoStepperEnv-v0 Walker3DPlannerEnv-v0 MikePlannerEnv-v0; do
-  python bench.py --env-id $e --steps 300 --warmup 100 --no-cpu-baseline > $O/${tag}_$(echo $e | tr 'A-Z' 'a-z' | sed 's/env-v0//')_bench.json 2>/dev/null
+  python bench.py --env-id $e --steps 300 --warmup 100 --no-cpu-baseline --full > $O/${tag}_$(echo $e | tr 'A-Z' 'a-z' | sed 's/env-v0//')_bench.json 2>/dev/null
 done
-python bench.py --env-id Cassie2DEnv-v0 --envs 2048 --steps 100 --warmup 30 --no-cpu-baseline > $O/${tag}_cassie2d_bench.json 2>/dev/null
-python bench.py --env-id CassiePhaseMocca2DEnv-v0 --envs 2048 --steps 100 --warmup 30 --no-cpu-baseline > $O/${tag}_cassiephasemocca2d_bench.json 2>/dev/null
-python bench.py --env-id CassiePhaseMirror2DEnv-v0 --envs 2048 --steps 100 --warmup 30 --no-cpu-baseline > $O/${tag}_cassiephasemirror2d_bench.json 2>/dev/null
+python bench.py --env-id Cassie2DEnv-v0 --envs 2048 --steps 100 --warmup 30 --no-cpu-baseline --full > $O/${tag}_cassie2d_bench.json 2>/dev/null
+python bench.py --env-id CassiePhaseMocca2DEnv-v0 --envs 2048 --steps 100 --warmup 30 --no-cpu-baseline --full > $O/${tag}_cassiephasemocca2d_bench.json 2>/dev/null
+python bench.py --env-id CassiePhaseMirror2DEnv-v0 --envs 2048 --steps 100 --warmup 30 --no-cpu-baseline --full > $O/${tag}_cassiephasemirror2d_bench.json 2>/dev/null
 # 3b. the trainer-facing surface (mocca_envs_amd.trainer_api): PPO collection loops at the metric's batch and at config 5's shard
 python tools/trainer_loop_bench.py --envs 4096 > $O/${tag}_trainer_loop_4096.json 2>/dev/null
 python tools/trainer_loop_bench.py --envs 8192 > $O/${tag}_trainer_loop_8192.json 2>/dev/null
