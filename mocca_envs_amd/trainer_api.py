@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import gym_shim
+from . import lib as _lib
 from .multi import make_vec_env
 
 
@@ -59,7 +60,8 @@ class _StepRecords:
         done = np.zeros(env.num_envs, dtype=bool)
         done[self._idx] = True
         if env._want_terminal and self._idx.size:            # owned copies of the finished envs' terminal observations, gathered once
-            self._term = env.venv.terminal_obs.index_select(0, torch.from_numpy(self._idx).to(env.device))
+            # from THIS step's own buffer (its slot's rows): the live buffer of later launches holds other episodes' ends by now
+            self._term = env._term_bufs[self.serial % env._slots].index_select(0, torch.from_numpy(self._idx).to(env.device))
         self._done = done
         self._env = None
 
@@ -184,11 +186,13 @@ class TorchVecEnv:
     `record_slots`: how many steps' episode records the pinned ring holds; a step's `done` / `infos` that are still referenced when
     their slot comes up for rewriting are fetched then, so they stay correct however late they are read.  `eager_done=True` returns
     `done` as a real numpy array (one synchronise per step -- for code that insists on `isinstance(done, np.ndarray)`); `record_events=False`
-    drops the per-step event (for loops that read `masks` / `episode_totals` only)."""
+    drops the per-step event (for loops that read `masks` / `episode_totals` only).  `terminal_observation=True` gives every record slot
+    terminal-observation rows of its own (launch k writes slot k % record_slots), so `infos[i]["terminal_observation"]` is the final
+    observation of THAT step's episode however late it is read."""
 
     def __init__(self, env_id: str, num_envs: int, seed: int = 0, device: Optional[int] = None, sub_batches: int = 1,
                  terminal_observation: bool = False, record_slots: int = 8, eager_done: bool = False, record_events: bool = True, **kw):
-        self.venv = make_vec_env(env_id, num_envs, sub_batches=sub_batches, seed=seed, auto_reset=True, terminal_obs=terminal_observation,
+        self.venv = make_vec_env(env_id, num_envs, sub_batches=sub_batches, seed=seed, auto_reset=True,
                                  **({"device": device} if device is not None else {}), **kw)
         self.env_id, self.num_envs = env_id, int(num_envs)
         self.device = self.venv.device
@@ -208,9 +212,33 @@ class TorchVecEnv:
         self._events = [torch.cuda.Event() for _ in range(self._slots)] if record_events else None
         self._rew2 = self.venv.rew.unsqueeze(1)
         self._want_terminal = bool(terminal_observation)
+        self._term_bufs = self._term_attach = self.rollout_terminal_obs = None
+        if self._want_terminal:
+            # one terminal-observation buffer per record slot: launch k writes its finished envs' final observations into slot k % slots,
+            # which no launch touches again before k + slots -- and step() materialises record k before that launch, so a record's
+            # terminal observations are its own however late they are read.  Attaching a buffer is a host-side pointer swap (no kernel)
+            self._term_bufs = torch.zeros(self._slots, self.num_envs, self.venv.obs_dim, dtype=torch.float32, device=self.device)
+            self._term_attach = [self._attach_terminal(self._term_bufs[s]) for s in range(self._slots)]
         self._eager = bool(eager_done)
         from . import model as M
         self._stepper = self.venv.task_id == M.TASK_WALKER3D_STEPPER
+
+    def _attach_terminal(self, buf: torch.Tensor):
+        """Attach `buf` [N, obs_dim] as the terminal-observation buffer of the handle(s) (each sub-batch its rows) and return the
+        (function, handle, pointer) calls that attach it again -- what step() replays before its launch."""
+        venv = self.venv
+        parts = [(venv, buf)] if hasattr(venv, "lib") else [(e, buf[sl]) for e, sl in zip(venv.parts, venv.slices)]
+        calls = []
+        for e, b in parts:
+            e.keep_terminal_obs(True, buffer=b)     # (checks shape, dtype and device once)
+            calls.append((e.lib.mocca_set_terminal_obs_buffer, e.h, b.data_ptr()))
+        venv.terminal_obs = buf
+        return calls
+
+    def _use_terminal(self, slot: int):
+        for fn, h, ptr in self._term_attach[slot]:
+            _lib.check(fn(h, ptr), h)
+        self.venv.terminal_obs = self._term_bufs[slot]
 
     def synchronize(self):
         """Wait for every launch issued so far (the streams the env steps on)."""
@@ -236,6 +264,8 @@ class TorchVecEnv:
                 old.materialise()      # its slot is about to be rewritten: fetch it now (its launch finished long ago)
         if actions.device != self.device or actions.dtype != torch.float32 or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        if self._term_attach is not None:
+            self._use_terminal(slot)
         rew = self._rew2
         if into:
             if not hasattr(self.venv, "lib"):
@@ -265,10 +295,17 @@ class TorchVecEnv:
         capture: they advance the envs too.  `into`: a callable t -> the `into` dict of `step()`, each with an "obs" entry -- launch t of the
         graph writes its observations / rewards / masks straight into those tensors (row t + 1 of the trainer's storage) and `policy` reads
         `into(t - 1)["obs"]`; `into(-1)["obs"]` is the storage's row 0, which must hold the current observation before every replay (PPO's
-        `rollouts.after_update()` copies the last row there; this call leaves it filled): the rollout needs no copy kernels at all."""
+        `rollouts.after_update()` copies the last row there; this call leaves it filled): the rollout needs no copy kernels at all.
+        `terminal_observation=True`: the graph's launches all write their finished envs' final observations into ONE buffer of their own,
+        `envs.rollout_terminal_obs` [N, obs_dim] (apart from the record slots of `step()`; rows of envs that did not finish keep older
+        content), which is also `envs.venv.terminal_obs` while `sink` runs -- a sink that wants them copies them at step t."""
         if not hasattr(self.venv, "lib"):
             raise NotImplementedError("capture_rollout needs one handle (sub_batches=1): sub-batches step on streams of their own")
         venv, dev = self.venv, self.device
+        if self._want_terminal:          # the graph bakes the buffer's address into its launches: a fixed one, not a record slot of step()
+            if self.rollout_terminal_obs is None:
+                self.rollout_terminal_obs = torch.zeros_like(self._term_bufs[0])
+            self._attach_terminal(self.rollout_terminal_obs)
         obs, rew = venv.obs, self._rew2
         if len(inspect.signature(policy).parameters) >= 2:        # policy(obs, t): e.g. to write its action into the storage's row t
             act_of = policy

@@ -1502,8 +1502,13 @@ static void reset_env(Oracle *o, int env, float *obs) {
   real stale_fc[MOCCA_MAX_FEET];
   for (int k = 0; k < MOCCA_MAX_FEET; ++k) stale_fc[k] = tk->feet_contact[k];
   int stale_nsi = tk->next_step_index, stale_cover = tk->cover;
+  /* the random-reward weights are drawn by step() (env_locomotion.py:533-547), not by reset(): a reset leaves the last step's weights in
+   * the record, as the kernel's reset does (it rebuilds the task registers only) */
+  real keep_rw[8];
+  memcpy(keep_rw, tk->rw, sizeof(keep_rw));
   memset(tk, 0, sizeof(*tk));
   tk->episode = ep; tk->curriculum = keep_cur;
+  memcpy(tk->rw, keep_rw, sizeof(keep_rw));
 
   tk->applied_gain = 1;
   if (o->task_id == MOCCA_TASK_WALKER3D_CUSTOM) {

@@ -101,6 +101,48 @@ def test_records_read_late_are_still_the_right_ones(events):
     lazy.close(); eager.close()
 
 
+@pytest.mark.parametrize("sub_batches", [1, 2])
+def test_terminal_observations_read_late_are_still_the_right_ones(sub_batches):
+    """`infos[i]["terminal_observation"]` kept for 30 steps (the ring holds 4) and read afterwards must be, bit for bit, what an eager twin
+    handed out at that step (read and cloned at once).  With max_episode_steps = 3 every env ends at least every third step, so a late
+    read of ONE live terminal-observation buffer would hand out a later episode's end."""
+    import torch
+    from mocca_envs_amd.trainer_api import make_vec_envs
+    from mocca_envs_amd.vec_env import compile_model_for
+    n, steps = 64, 90
+    m = compile_model_for("Walker3DCustomEnv-v0")
+    m.max_episode_steps = 3
+    blob = m.to_bytes()
+    kw = dict(seed=7, num_processes=n, sub_batches=sub_batches, terminal_observation=True, model_blob=blob)
+    lazy = make_vec_envs("Walker3DCustomEnv-v0", record_slots=4, **kw)
+    eager = make_vec_envs("Walker3DCustomEnv-v0", eager_done=True, **kw)
+    assert torch.equal(lazy.reset(), eager.reset())
+    g = torch.Generator(device="cuda").manual_seed(11)
+    kept, seen = [], []
+    n_term = n_rows_rewritten = 0
+    for t in range(steps):
+        a = torch.rand(n, 21, device="cuda", generator=g) * 2 - 1
+        _, _, d1, i1 = lazy.step(a)
+        _, _, d2, i2 = eager.step(a)
+        seen.append((d2.copy(), {k: v["terminal_observation"].clone() for k, v in i2.finished()}))
+        kept.append((d1, i1))
+        if len(kept) == 30:
+            for j, ((dl, il), (de, te)) in enumerate(zip(kept, seen)):
+                assert (np.asarray(dl) == de).all()
+                got = {k: v["terminal_observation"] for k, v in il.finished()}
+                assert sorted(got) == sorted(te), (t, j)
+                for k in te:
+                    assert torch.equal(got[k], te[k]), (t, j, k)
+                    # an env that ended again within the next 3 steps: its row of a single live buffer was rewritten before this look
+                    n_rows_rewritten += any(seen[jj][0][k] for jj in range(j + 1, min(j + 4, len(seen))))
+                n_term += len(te)
+            kept, seen = [], []
+    print(f"\nsub_batches={sub_batches}: {n_term} terminal observations read 0..29 steps late; {n_rows_rewritten} of them had their env end "
+          f"again within 3 steps")
+    assert n_term > 4 * n and n_rows_rewritten > n         # the sample exercises what is checked
+    lazy.close(); eager.close()
+
+
 def test_policy_and_step_replay_from_a_cuda_graph():
     """The collection loop without the host: `policy -> mocca_step` captured once in a torch.cuda.CUDAGraph (default parameters: the pace
     calibrates itself on the device since ABI 7) and replayed; observations, rewards, done bytes, masks, episode totals and the
