@@ -1329,9 +1329,14 @@ static real cassie_state(Oracle *o, const Dyn *s, const Task *tk, float *rs) {
     rs[6 + k] = cassie_nrm(m, k, s->q[m->ordered_body[k]]);
     rs[6 + no + k] = (float)s->qd[m->ordered_body[k]];
   }
+  /* the feet as the walkers read them (robot_state above): the blob's foot point on the foot link -- the link's centre of mass in the
+   * compiled blob (model.compile_cassie), a field of its own in any blob, and the one the kernel reads */
   real minz = 1e30;
   for (int k = 0; k < m->n_feet; ++k) {
-    real z = s->pos[2] + w->comw[m->foot_body[k]][2];
+    int b = m->foot_body[k];
+    real fp[3] = {m->foot_point[k][0], m->foot_point[k][1], m->foot_point[k][2]}, fw[3];
+    matvec3(w->R[b], fp, fw);
+    real z = s->pos[2] + w->r[b][2] + fw[2];
     if (z < minz) minz = z;
   }
   return s->pos[2] - minz;

@@ -88,8 +88,10 @@ class Model:
         self.closures = [dict(a=m.cl_body_a[c], b=m.cl_body_b[c], pa=np.array(list(m.cl_point_a[c]), float),
                               pb=np.array(list(m.cl_point_b[c]), float)) for c in range(m.n_closures)]
         for k in ("gravity", "dt", "n_iters", "erp", "erp_noncontact", "friction_cone", "limit_at_violation", "contact_margin", "lin_damp", "ang_damp", "max_qd", "warmstart", "ground_friction",
-                  "plank_friction", "plank_stiffness", "plank_damping", "limit_slack", "plank_com_z", "max_contacts", "max_rows", "n_slots", "manifold_max", "linear_slop", "sweep_alternate"):
+                  "plank_friction", "plank_stiffness", "plank_damping", "limit_slack", "plank_com_z", "max_contacts", "max_rows", "n_slots", "manifold_max", "linear_slop", "sweep_alternate",
+                  "planar"):
             setattr(self, k, getattr(m, k))
+        self.init_y = float(m.init_pos[1])
         self.gravity, self.dt = float(np.float32(self.gravity)), float(np.float32(self.dt))
         self.plank_half = np.array(list(m.plank_half), float)
 
@@ -444,6 +446,18 @@ def substep(mdl: Model, st: State, tau, planks=None, heightfield=None):
                 break
             rows.append(dict(J=Jp[ip + 2 * ci][ax] - Jp[ip + 2 * ci + 1][ax], bias=mdl.erp_noncontact * (Pb[ax] - Pa[ax]) / dt, cfm=0.0, lo=-1e30, hi=1e30,
                              lam=0.0, kind=3, slot=-1))
+    if mdl.planar:
+        # CassieEnv(planar=True): the base's y axis R e_y is held on the world's y axis and the base on the plane y = init_y.  With
+        # dR/dt = [omega]x R at R e_y = e_y:  d(R e_y)_z / dt = omega_x  and  d(-(R e_y)_x) / dt = omega_z; the third row is v_y itself.
+        # Each row drives its error to zero at the non-contact ERP, in the order omega_x, omega_z, v_y.  NOT independent of the oracle in
+        # what the constraint IS: this is the oracle's small-angle error and row order (env_cassie.py:326-341 as the oracle reads it); what
+        # the dense comparison checks here is the rows' Jacobians, their place among the other rows and the solve.
+        R0 = _quat_mat(st.quat)
+        for comp, err in ((0, R0[2, 1]), (2, -R0[0, 1]), (4, st.pos[1] - mdl.init_y)):
+            if len(rows) >= mdl.max_rows:
+                break
+            J = np.zeros(mdl.nd); J[comp] = 1.0
+            rows.append(dict(J=J, bias=-mdl.erp_noncontact * err / dt, cfm=0.0, lo=-1e30, hi=1e30, lam=0.0, kind=3, slot=-1, planar=True))
     nc = min(len(contacts), (mdl.max_rows - len(rows)) // 3)
     first_normal = len(rows)
     cj = []
@@ -517,7 +531,7 @@ def substep(mdl: Model, st: State, tau, planks=None, heightfield=None):
     pos = st.pos + dt * vel
     Rn = _expm_so3(omg * dt) @ _quat_mat(st.quat)
     new = State(pos, _mat_quat(Rn), vel, omg, q, qd, warm)
-    return new, dict(rows=nr, n_limit=n_limit, nc=nc, lam=lam, kinds=[r["kind"] for r in rows], contacts=contacts, nu_star=nus,
+    return new, dict(rows=nr, n_limit=n_limit, n_planar=sum(1 for r in rows if r.get("planar")), nc=nc, lam=lam, kinds=[r["kind"] for r in rows], contacts=contacts, nu_star=nus,
                      slot_mask=slot_mask, n_self=n_self, Rn=Rn)
 
 

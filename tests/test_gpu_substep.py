@@ -136,6 +136,8 @@ def _one_substep_blob(env_id, **kw):
     return m
 
 
+# tests/substep_compare.py (SubstepStats) restates the bars of this test for tests/test_gpu_fuzz.py, as a verdict a negative control can
+# inspect: a change to a threshold here must be made there too
 @pytest.mark.parametrize("env_id,task,kw", CASES)
 def test_single_substep_parity_with_matching_active_sets(env_id, task, kw):
     import torch

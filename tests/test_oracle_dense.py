@@ -241,6 +241,31 @@ def test_substep_with_loop_closures(alternate):
         assert info["kinds"].count(3) == 6
 
 
+def test_substep_with_planar_base_rows():
+    """Cassie2D (CassieEnv(planar=True), env_cassie.py:326-341): three bilateral rows hold the base in the x-z plane (omega_x, omega_z, v_y),
+    after the closures and before the contacts.  Adversarial states: the base rolled, yawed and shifted off the plane, spinning and sliding
+    out of it, loops open, toes in the ground -- the rows must be present in every sample and agree with the dense reference."""
+    m = M.compile_cassie(planar=True)
+    assert m.planar == 1
+    mdl = D.Model(m)
+    orc = Oracle(m.to_bytes(), M.TASK_CASSIE, 1, "f64")
+    orc.reset(seed=0)
+    base = orc.get_state()[0]
+    rng = np.random.default_rng(13)
+    nj = m.n_joints
+    for k in range(6):
+        row = base.copy()
+        row[1] += rng.normal(0, 0.05)                                   # off the plane
+        qt = np.concatenate([rng.normal(0, 0.15, 3), [1.0]]) * (1 if k % 2 else -1)   # rolled / yawed; w < 0 on every other sample
+        row[3:7] = qt / np.linalg.norm(qt)
+        row[2] -= 0.04 * rng.random()                                   # toes into the ground
+        row[13:13 + nj] += rng.normal(0, 0.03, nj)                      # loops slightly open
+        row[7:13] = rng.normal(0, 0.5, 6)                               # out-of-plane v_y, omega_x, omega_z too
+        row[13 + nj:13 + 2 * nj] = rng.normal(0, 0.5, nj)
+        info = _compare(orc, m, mdl, row, rng.uniform(-20, 20, nj), tol=1e-7)
+        assert info["n_planar"] == 3 and info["kinds"].count(3) == 9, (info["n_planar"], info["kinds"])
+
+
 def _random_tree(rng, n_links):
     """A random branching mechanism in the model compiler's own description format: random parents, hinge axes, offsets,
     capsule / sphere geoms (hence random masses and inertias)."""
