@@ -196,19 +196,14 @@ class MoccaModel(C.Structure):
         def bits(i: int) -> float:
             return float(np.array([i & 0xFFFFFFFF], dtype=np.uint32).view(np.float32)[0])
         # joint record 0 is the identity: the kinematics walk composes it for the path positions past a body's depth
-        for k in range(9):
-            self.jrot[0][k] = 1.0 if k in (0, 4, 8) else 0.0
-        for k in range(3):
-            self.jpos[0][k] = 0.0
-            self.jaxis[0][k] = 1.0 if k == 2 else 0.0
+        _put(self.jrot[0], np.eye(3).reshape(-1))
+        _put(self.jpos[0], (0.0, 0.0, 0.0))
+        _put(self.jaxis[0], (0.0, 0.0, 1.0))
         for g in range(self.n_geoms):
             ne = 2 if self.g_type[g] == GEOM_CAPSULE else 1
             b = self.g_body[g]
             for e in range(2):
-                p = self.g_p2[g] if e else self.g_p1[g]
-                for k in range(3):
-                    self.gp_tab[2 * g + e][k] = p[k]
-                self.gp_tab[2 * g + e][3] = bits(b)
+                _put(self.gp_tab[2 * g + e], [*(self.g_p2[g] if e else self.g_p1[g]), bits(b)])
             mq = self.margin_code(g)
             for e in range(ne):
                 sl = self.g_slot[g] + e
@@ -246,6 +241,52 @@ def bullet_fidelity(m: "MoccaModel") -> "MoccaModel":
     m.sweep_alternate = 1
     m.linear_slop = 1e-5
     return m
+
+
+# Bullet defaults the reference never touches (bullet_utils.py:338-350 sets the time step, 5 iterations, 4 substeps and the CONTACT erp only),
+# restated from the published source as recalled  [UNVERIFIED-BULLET]:
+#  * rows that are not contacts (joint limits, point-to-point closures) take infoGlobal.m_erp = 0.2, not the contact ERP (m_erp2) that
+#    setDefaultContactERP(0.9) sets: btMultiBodyConstraint::fillMultiBodyConstraint ("split impulse is not implemented yet for
+#    btMultiBody*": erp = infoGlobal.m_erp), btMultiBodyJointLimitConstraint::createConstraintRows;
+#  * multibody contact rows do NOT warm start: btMultiBodyConstraintSolver::setupMultiBodyContactConstraint, "disable warmstarting for
+#    btMultiBody, it has issues gaining energy (==explosion)", `if (0)`; later versions gate it behind SOLVER_USE_ARTICULATED_WARMSTARTING,
+#    which pybullet's default solver mode does not contain.  (Rounds 1-3 early used 0.85, btContactSolverInfo's rigid-body factor.)
+#  * the two friction rows of a contact are coupled ("implicit cone friction", Bullet >= 2.87): both candidate impulses from the same
+#    velocity state, the pair clipped to the circle of radius mu * lambda_n (btMultiBodyConstraintSolver::resolveConeFrictionConstraintRows);
+#    pybullet: setPhysicsEngineParameter(enableConeFriction=0) selects the pyramid, "cone is default".  (Pyramid until round 3 late.)
+#  * a joint-limit row exists only while the joint is at or past its limit: btMultiBodyJointLimitConstraint::createConstraintRows,
+#    "//todo: consider adding some safety threshold here / if (penetration > 0) continue;" -- the joint crosses the limit by up to
+#    speed x dt and is pushed back with the non-contact ERP.  (Until round 3 late: a row from a predicted gap of 0.05 rad on, which stops the
+#    joint AT the limit -- the older form of that file, whose positive-gap branch `velocityError = -penetration / dt` is still in the source.)
+#  * contacts open within the RELATIVE breaking threshold 0.02 x getAngularMotionDisc() of the smaller of the two collision objects
+#    (btCollisionDispatcher::getNewManifold, CD_USE_RELATIVE_CONTACT_BREAKING_THRESHOLD on by default; MoccaModel.g_margin): 3 - 6 mm for a
+#    walker's links.  (Until round 3 late: 20 mm for every pair.)
+CONTACT_BREAKING_THRESHOLD = 0.02
+MARGIN_UNIT = 2.0 ** -13      # slot_tab carries a geom's margin as an 8-bit multiple of this (0.122 mm; up to 31 mm)
+ERP_NONCONTACT = 0.2
+WARMSTART = 0.0
+FRICTION_CONE = 1
+LIMIT_AT_VIOLATION = 1
+
+
+def _set_engine_defaults(m: "MoccaModel") -> None:
+    """The Bullet engine constants every robot shares: what bullet_utils.py:338-371 sets and the defaults above."""
+    m.magic, m.version = MAGIC, VERSION
+    m.gravity = 9.8                 # env_base.py:80
+    m.n_iters = 5                   # bullet_utils.py:340
+    m.erp = 0.9                     # bullet_utils.py:345: setDefaultContactERP = infoGlobal.m_erp2, the contact rows' ERP
+    m.erp_noncontact = ERP_NONCONTACT   # limits, point-to-point closures (btMultiBodyPoint2Point -> fillMultiBodyConstraint)
+    m.friction_cone = FRICTION_CONE
+    m.limit_at_violation = LIMIT_AT_VIOLATION
+    m.contact_margin = CONTACT_BREAKING_THRESHOLD   # gContactBreakingThreshold: the FACTOR of the relative thresholds in g_margin
+    m.lin_damp = 0.04               # [UNVERIFIED-BULLET] btMultiBody default; applies to the base and to every link, with the quadratic term
+    m.ang_damp = 0.04
+    m.max_qd = 100.0                # [UNVERIFIED-BULLET] maxCoordinateVelocity
+    m.warmstart = WARMSTART
+    m.ground_friction = 0.8         # bullet_utils.py:371
+    m.limit_slack = 0.05
+    m.max_contacts = 12
+    m.max_rows = 48
 
 
 def relative_margins(factor: float, groups) -> dict:
@@ -418,10 +459,10 @@ def _geom_inertial(g: Geom) -> Tuple[float, np.ndarray, np.ndarray]:
 
 
 def _compose_inertial(parts: List[Tuple[float, np.ndarray, np.ndarray]]):
+    """(mass, com, inertia about the com) of rigidly joined parts (mass, com, inertia about its own com); without mass the com is the
+    origin and the inertia the sum of the parts' own."""
     m = sum(p[0] for p in parts)
-    if m == 0.0:
-        return 0.0, np.zeros(3), np.zeros((3, 3))
-    c = sum(p[0] * p[1] for p in parts) / m
+    c = sum(p[0] * p[1] for p in parts) / m if m > 0 else np.zeros(3)
     I = np.zeros((3, 3))
     for mi, ci, Ii in parts:
         d = ci - c
@@ -430,46 +471,65 @@ def _compose_inertial(parts: List[Tuple[float, np.ndarray, np.ndarray]]):
 
 
 @dataclass
-class _FlatBody:
+class _FlatGeom:
+    """A contact geom in the frame of the flat link that carries it."""
+    kind: int
+    radius: float
+    p1: np.ndarray
+    p2: np.ndarray
+    friction: float
+    terrain: bool = True
+    foot: int = -1                       # index of the foot it belongs to
+    torso: bool = False
+    margin_key: object = None            # geoms of one key are one Bullet collision object (relative contact margin); None: the link
+    margin_weight: Optional[Tuple[float, np.ndarray]] = None   # (mass, com) of the geom in that object; None: 1 at the link's COM
+    src: Optional[Geom] = None           # MJCF only: the description's geom ...
+    bl: int = 0                          # ... and the Bullet link it sits on
+
+
+@dataclass
+class _Link:
+    """One body of the blob: the hinge that moves it (radians, axis in the link frame) and what it carries."""
     name: str
     parent: int
-    jpos: np.ndarray
-    jrot: np.ndarray
-    hinge: Optional[Hinge]
-    geoms: List[Tuple[Geom, np.ndarray, np.ndarray, int]]  # geom, p1, p2 (flat body frame), bullet link id
-    bullet_link: int
+    jpos: np.ndarray = field(default_factory=lambda: np.zeros(3))
+    jrot: np.ndarray = field(default_factory=lambda: np.eye(3))
+    axis: Optional[np.ndarray] = None
+    lo: float = 0.0
+    hi: float = 0.0
+    gain: float = 0.0
+    parts: List[Tuple[float, np.ndarray, np.ndarray]] = field(default_factory=list)   # inertial parts (mass, com, inertia about com)
+    geoms: List[_FlatGeom] = field(default_factory=list)
+    mass: Optional[float] = None         # changeDynamics(mass=...): the composed inertia scaled to this mass
 
 
-def _flatten(root: Body, base_ref: str):
-    """Expand multi-hinge bodies into chains, merge hinge-less children into their parent.
+def _flatten(root: Body, foot_names: Sequence[str] = (), torso_name: Optional[str] = None):
+    """MJCF front end: expand multi-hinge bodies into chains, merge hinge-less children into their parent.
 
-    Returns flat bodies plus, for the self-collision filter, the Bullet-style
-    link tree in which hinge-less children stay separate links attached by fixed
-    joints ("jointfix", robots.py:167).
+    Returns the flat links, the link of each body in `foot_names`, and the self-collision candidate pairs
+    (URDF_USE_SELF_COLLISION | URDF_USE_SELF_COLLISION_EXCLUDE_ALL_PARENTS, robots.py:259-264, + group/mask filter) in the
+    Bullet-style link tree, in which hinge-less children stay separate links attached by fixed joints ("jointfix", robots.py:167).
     """
-    flat: List[_FlatBody] = []
+    links: List[_Link] = []
     bl_parent: List[int] = []  # Bullet-style link parents (index = bullet link id)
+    carrier: Dict[str, int] = {}  # MJCF body name -> the link that carries it (its last hinge)
 
-    # base reference point: origin of the base frame inside the root body frame
-    own = [_geom_inertial(g) for g in root.geoms]
-    if base_ref == "own_com":
-        base_origin = _compose_inertial(own)[1]
-    elif base_ref == "body_frame":
-        base_origin = np.zeros(3)
-    else:
-        raise ValueError(base_ref)
-
-    def add_geoms(fb: _FlatBody, body: Body, R: np.ndarray, t: np.ndarray, bl: int):
+    def add_geoms(b: int, body: Body, R: np.ndarray, t: np.ndarray, bl: int):
         for g in body.geoms:
             p1 = R @ np.asarray(g.p1, float) + t
             p2 = R @ np.asarray(g.p2 if g.p2 is not None else g.p1, float) + t
-            fb.geoms.append((g, p1, p2, bl))
+            fg = _FlatGeom(g.kind, g.radius, p1, p2, g.friction, filters_collide(g.group, g.mask, TERRAIN_GROUP, TERRAIN_MASK),
+                           torso=body.name == torso_name, margin_key=(b, bl), src=g, bl=bl)
+            gm, gc, gI = _geom_inertial(fg)
+            fg.margin_weight = (gm, gc)
+            links[b].parts.append((gm, gc, gI))
+            links[b].geoms.append(fg)
 
     def merge_fixed(fi: int, body: Body, R: np.ndarray, t: np.ndarray, bl_par: int):
-        """hinge-less child `body` rigidly attached to flat body `fi`: x_fi = R x + t."""
+        """hinge-less child `body` rigidly attached to flat link `fi`: x_fi = R x + t."""
         bl_parent.append(bl_par)
         bl = len(bl_parent) - 1
-        add_geoms(flat[fi], body, R, t, bl)
+        add_geoms(fi, body, R, t, bl)
         for ch in body.children:
             Rc = R @ quat_wxyz_to_mat(ch.quat_wxyz)
             tc = R @ np.asarray(ch.pos, float) + t
@@ -479,23 +539,19 @@ def _flatten(root: Body, base_ref: str):
                 merge_fixed(fi, ch, Rc, tc, bl)
 
     def add_hinged(body: Body, parent_flat: int, R: np.ndarray, t: np.ndarray, bl_par: int):
-        """`body` frame expressed in the parent flat-body frame: x_par = R x + t (at q = 0)."""
+        """`body` frame expressed in the parent flat-link frame: x_par = R x + t (at q = 0)."""
         anchor = np.asarray(body.anchor, float)
         last = parent_flat
         bl = bl_par
         for k, h in enumerate(body.hinges):
-            if k == 0:
-                jpos, jrot = R @ anchor + t, R
-            else:
-                jpos, jrot = np.zeros(3), np.eye(3)
             bl_parent.append(bl)
             bl = len(bl_parent) - 1
-            fb = _FlatBody(h.name, last, jpos, jrot, h, [], bl)
-            flat.append(fb)
-            last = len(flat) - 1
-        fb = flat[last]
+            jpos, jrot = (R @ anchor + t, R) if k == 0 else (np.zeros(3), np.eye(3))
+            links.append(_Link(h.name, last, jpos, jrot, np.asarray(h.axis, float), h.lo_deg * DEG, h.hi_deg * DEG, h.gain))
+            last = len(links) - 1
+        carrier[body.name] = last
         # the last link of the chain carries the MJCF body: body coords -> link coords = x - anchor
-        add_geoms(fb, body, np.eye(3), -anchor, bl)
+        add_geoms(last, body, np.eye(3), -anchor, bl)
         for ch in body.children:
             Rc = quat_wxyz_to_mat(ch.quat_wxyz)
             tc = np.asarray(ch.pos, float) - anchor
@@ -505,17 +561,34 @@ def _flatten(root: Body, base_ref: str):
                 merge_fixed(last, ch, Rc, tc, bl)
 
     bl_parent.append(-1)
-    base = _FlatBody(root.name, -1, np.zeros(3), np.eye(3), None, [], 0)
-    flat.append(base)
-    add_geoms(base, root, np.eye(3), -base_origin, 0)
+    links.append(_Link(root.name, -1))
+    add_geoms(0, root, np.eye(3), np.zeros(3), 0)
     for ch in root.children:
         Rc = quat_wxyz_to_mat(ch.quat_wxyz)
-        tc = np.asarray(ch.pos, float) - base_origin
+        tc = np.asarray(ch.pos, float)
         if ch.hinges:
             add_hinged(ch, 0, Rc, tc, 0)
         else:
             merge_fixed(0, ch, Rc, tc, 0)
-    return flat, bl_parent, base_origin
+
+    feet = [carrier[n] for n in foot_names]
+    for k, b in enumerate(feet):   # every geom of the foot link belongs to the foot
+        for g in links[b].geoms:
+            if g.foot < 0:
+                g.foot = k
+    geoms = [(b, g) for b, link in enumerate(links) for g in link.geoms]
+    pairs = []
+    for i, (bi, gi) in enumerate(geoms):
+        for j in range(i + 1, len(geoms)):
+            bj, gj = geoms[j]
+            if gi.bl == gj.bl or gi.bl in _bullet_ancestors(bl_parent, gj.bl) or gj.bl in _bullet_ancestors(bl_parent, gi.bl):
+                continue
+            if not filters_collide(gi.src.group, gi.src.mask, gj.src.group, gj.src.mask):
+                continue
+            if bi == bj:
+                continue  # rigidly attached in our tree (e.g. head vs torso): cannot move relative
+            pairs.append((i, j))
+    return links, feet, pairs
 
 
 def _bullet_ancestors(bl_parent: List[int], a: int) -> set:
@@ -562,13 +635,99 @@ def set_stepper_params(m: "MoccaModel", *, quadruped: bool = False, plank_class:
     shape, half, com_z, per_radius = PLANK_CLASSES[plank_class]
     scale = per_radius * m.step_radius
     m.plank_shape = shape
-    for k in range(3):
-        m.plank_half[k] = half[k] * scale
+    _put(m.plank_half, [h * scale for h in half])
     m.plank_com_z = com_z * scale                  # BaseStep._pos_offset (bullet_objects.py:62)
     m.plank_friction, m.plank_stiffness, m.plank_damping = 1.0, 30000.0, 1000.0      # bullet_objects.py:64-72
     # reset() -> calc_feet_state() on the manifolds of the episode before (env_locomotion.py:484-499); only the Stepper task reads the flag
     m.task_flags |= TASKF_STALE_RESET_CONTACTS
     return m
+
+
+def _put(dst, values) -> None:
+    """Write a vector (or a flattened matrix, a list of indices) into a ctypes array field."""
+    for k, v in enumerate(values):
+        dst[k] = v
+
+
+def _set_inertial(m: "MoccaModel", b: int, mass: float, com, I: np.ndarray) -> None:
+    m.mass[b] = mass
+    _put(m.com[b], com)
+    _put(m.inertia[b], [I[i, j] for i, j in ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))])
+
+
+def _set_mirror(m: "MoccaModel", right: Sequence[int], left: Sequence[int], neg: Sequence[int] = ()) -> None:
+    m.n_mirror_side, m.n_mirror_neg = len(right), len(neg)
+    _put(m.mirror_right, right)
+    _put(m.mirror_left, left)
+    _put(m.mirror_neg, neg)
+
+
+def _assemble(links: List[_Link], feet: Sequence[Tuple[int, Optional[Sequence[float]]]], pairs: Sequence[Tuple[int, int]] = ()) -> "MoccaModel":
+    """The blob's tree, inertia, geom / slot / margin, pair and foot fields from flat links, on top of the engine defaults.
+    `feet`: (link, point) per foot, point None = the link's COM (what getLinkState reports for the foot link)."""
+    nb = len(links)
+    assert nb <= MAX_BODIES
+    m = MoccaModel()
+    _set_engine_defaults(m)
+    m.n_bodies, m.n_joints = nb, nb - 1
+    coms = []
+    for b, link in enumerate(links):
+        m.parent[b] = link.parent
+        if b:
+            m.anc_mask[b] = m.anc_mask[link.parent] | (1 << b)
+            m.depth[b] = m.depth[link.parent] + 1
+            _put(m.jpos[b], link.jpos)
+            _put(m.jrot[b], link.jrot.reshape(-1))
+            _put(m.jaxis[b], link.axis)
+            m.jlo[b], m.jhi[b] = link.lo, link.hi
+        mass, com, I = _compose_inertial(link.parts)
+        coms.append(com)
+        if link.mass is not None:
+            # changeDynamics(mass=...) on a link (robots.py:507-510): Bullet re-derives the link's local inertia from its
+            # collision shape at the new mass, i.e. scales it with the mass.                    [UNVERIFIED-BULLET]
+            I, mass = I * (link.mass / mass), link.mass
+        _set_inertial(m, b, mass, com, I)
+
+    geoms = [(b, g) for b, link in enumerate(links) for g in link.geoms]
+    assert len(geoms) <= MAX_GEOMS
+    m.n_geoms = len(geoms)
+    slot = 0
+    for gi, (b, g) in enumerate(geoms):
+        m.g_body[gi], m.g_type[gi], m.g_radius[gi], m.g_friction[gi] = b, g.kind, g.radius, g.friction
+        _put(m.g_p1[gi], g.p1)
+        _put(m.g_p2[gi], g.p2)
+        m.g_slot[gi] = slot
+        slot += 1 if g.kind == GEOM_SPHERE else 2
+        m.g_terrain[gi], m.g_foot[gi], m.g_torso[gi] = int(g.terrain), g.foot, int(g.torso)
+    assert slot <= MAX_SLOTS
+    m.n_slots = slot
+    # Bullet's relative contact breaking threshold, per collision object
+    keys = [b if g.margin_key is None else g.margin_key for b, g in geoms]
+    groups = {}
+    for key, (b, g) in zip(keys, geoms):
+        gm, gc = g.margin_weight or (1.0, coms[b])
+        groups.setdefault(key, []).append((g.kind, g.radius, g.p1, g.p2, gm, gc))
+    rel = relative_margins(CONTACT_BREAKING_THRESHOLD, groups)
+    for gi, key in enumerate(keys):
+        m.g_margin[gi] = rel[key]
+
+    assert len(pairs) <= MAX_PAIRS, len(pairs)
+    m.n_pairs = len(pairs)
+    for k, (i, j) in enumerate(pairs):
+        m.pair_a[k], m.pair_b[k] = i, j
+    m.n_feet = len(feet)
+    for k, (b, point) in enumerate(feet):
+        m.foot_body[k] = b
+        _put(m.foot_point[k], coms[b] if point is None else point)
+    return m
+
+
+def _set_walker_task(m: "MoccaModel", termination_height: float) -> None:
+    """WalkerBaseEnv's control step, termination height and costs (env_locomotion.py:39-56) and the 1000-step limit (__init__.py:55)."""
+    m.control_dt = 1.0 / 60.0
+    m.termination_height = termination_height
+    m.electricity_cost, m.stall_torque_cost, m.joints_at_limit_cost = 4.5, 0.225, 0.1
+    m.max_episode_steps = 1000
 
 
 def compile_model(
@@ -580,7 +739,6 @@ def compile_model(
     mirror_left: Sequence[int],
     mirror_neg: Sequence[int],
     *,
-    base_ref: str = "body_frame",
     joint_damping: float = 0.0,
     joint_armature: float = 0.0,
     self_collision: bool = True,
@@ -589,157 +747,22 @@ def compile_model(
     plank_class: str = "LargePlank",
     torso_name: Optional[str] = None,
 ) -> MoccaModel:
-    flat, bl_parent, _ = _flatten(root, base_ref)
-    nb = len(flat)
-    assert nb <= MAX_BODIES
-    m = MoccaModel()
-    m.magic, m.version = MAGIC, VERSION
-    m.n_bodies, m.n_joints = nb, nb - 1
-
-    geoms = []
-    for b, fb in enumerate(flat):
-        m.parent[b] = fb.parent
-        if b == 0:
-            m.anc_mask[0], m.depth[0] = 0, 0
-        else:
-            m.anc_mask[b] = m.anc_mask[fb.parent] | (1 << b)
-            m.depth[b] = m.depth[fb.parent] + 1
-            for k in range(3):
-                m.jpos[b][k] = fb.jpos[k]
-                m.jaxis[b][k] = fb.hinge.axis[k]
-            for k in range(9):
-                m.jrot[b][k] = fb.jrot.reshape(-1)[k]
-            m.jlo[b] = fb.hinge.lo_deg * DEG
-            m.jhi[b] = fb.hinge.hi_deg * DEG
-            m.jdamp[b] = joint_damping
-            m.jarm[b] = joint_armature
-            m.gain[b] = fb.hinge.gain
-            m.init_q[b] = init_q_by_name.get(fb.hinge.name, 0.0)
-        parts = []
-        for g, p1, p2, bl in fb.geoms:
-            gg = Geom(g.name, g.kind, g.radius, tuple(p1), tuple(p2), g.group, g.mask, g.friction)
-            parts.append(_geom_inertial(gg))
-            geoms.append((b, gg, bl))
-        mass, com, I = _compose_inertial(parts)
-        if link_mass and fb.name in link_mass:
-            # changeDynamics(mass=...) on a link (robots.py:507-510): Bullet re-derives the link's local inertia from its
-            # collision shape at the new mass, i.e. scales it with the mass.                    [UNVERIFIED-BULLET]
-            I, mass = I * (link_mass[fb.name] / mass), link_mass[fb.name]
-        m.mass[b] = mass
-        for k in range(3):
-            m.com[b][k] = com[k]
-        for k, (i, j) in enumerate([(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]):
-            m.inertia[b][k] = I[i, j]
-
-    assert len(geoms) <= MAX_GEOMS
-    m.n_geoms = len(geoms)
-    slot = 0
-    for gi, (b, g, bl) in enumerate(geoms):
-        m.g_body[gi], m.g_type[gi], m.g_radius[gi] = b, g.kind, g.radius
-        m.g_friction[gi] = g.friction
-        for k in range(3):
-            m.g_p1[gi][k] = g.p1[k]
-            m.g_p2[gi][k] = g.p2[k]
-        m.g_slot[gi] = slot
-        slot += 1 if g.kind == GEOM_SPHERE else 2
-        m.g_terrain[gi] = int(filters_collide(g.group, g.mask, TERRAIN_GROUP, TERRAIN_MASK))
-    assert slot <= MAX_SLOTS
-    m.n_slots = slot
-    # Bullet's relative contact breaking threshold, per Bullet link (a hinge-less child body is a link of its own there)
-    groups = {}
-    for gi, (b, g, bl) in enumerate(geoms):
-        gm, gc, _ = _geom_inertial(g)
-        groups.setdefault((b, bl), []).append((g.kind, g.radius, g.p1, g.p2, gm, gc))
-    rel = relative_margins(CONTACT_BREAKING_THRESHOLD, groups)
-    for gi, (b, g, bl) in enumerate(geoms):
-        m.g_margin[gi] = rel[(b, bl)]
-
-    # self-collision candidate pairs: URDF_USE_SELF_COLLISION |
-    # URDF_USE_SELF_COLLISION_EXCLUDE_ALL_PARENTS (robots.py:259-264) + group/mask filter
-    pairs = []
-    if self_collision:
-        for i in range(len(geoms)):
-            for j in range(i + 1, len(geoms)):
-                bi, gi_, li = geoms[i]
-                bj, gj_, lj = geoms[j]
-                if li == lj:
-                    continue
-                if li in _bullet_ancestors(bl_parent, lj) or lj in _bullet_ancestors(bl_parent, li):
-                    continue
-                if not filters_collide(gi_.group, gi_.mask, gj_.group, gj_.mask):
-                    continue
-                if bi == bj:
-                    continue  # rigidly attached in our tree (e.g. head vs torso): cannot move relative
-                pairs.append((i, j))
-    assert len(pairs) <= MAX_PAIRS, len(pairs)
-    m.n_pairs = len(pairs)
-    for k, (i, j) in enumerate(pairs):
-        m.pair_a[k], m.pair_b[k] = i, j
-
-    names = [fb.name for fb in flat]
-    last_link_of_body = {}
-    # foot_names are MJCF body names; the link carrying the body is its last hinge
-    def find_body(b: Body, nm: str) -> Optional[Body]:
-        if b.name == nm:
-            return b
-        for ch in b.children:
-            r = find_body(ch, nm)
-            if r is not None:
-                return r
-        return None
-
-    m.n_feet = len(foot_names)
-    for k, fn in enumerate(foot_names):
-        fbdy = find_body(root, fn)
-        m.foot_body[k] = names.index(fbdy.hinges[-1].name)
-    for gi in range(m.n_geoms):   # MJCF feet: every geom of the foot body belongs to the foot link
-        m.g_foot[gi] = next((k for k in range(m.n_feet) if m.foot_body[k] == m.g_body[gi]), -1)
-    if torso_name is not None:    # robot_torso_name (env_locomotion.py:992): the link that carries the MJCF body of that name
-        tb = names.index(find_body(root, torso_name).hinges[-1].name)
-        for gi, (b, g, bl) in enumerate(geoms):
-            m.g_torso[gi] = int(b == tb and bl == flat[tb].bullet_link)
+    """Blob of an MJCF walker.  `torso_name`: robot_torso_name (env_locomotion.py:992), the body whose geoms are the torso's."""
+    links, feet, pairs = _flatten(root, foot_names, torso_name)
+    for link in links:
+        link.mass = (link_mass or {}).get(link.name)
+    m = _assemble(links, [(b, None) for b in feet], pairs if self_collision else ())
+    for b in range(1, m.n_bodies):
+        m.jdamp[b], m.jarm[b], m.gain[b] = joint_damping, joint_armature, links[b].gain
+        m.init_q[b] = init_q_by_name.get(links[b].name, 0.0)
     m.target_range, m.fall_z = 16.0, -5.0     # env_locomotion.py:1060, :1108
-    for k in range(m.n_feet):     # ... and the foot link is the body itself: its COM is what getLinkState reports
-        for i in range(3):
-            m.foot_point[k][i] = m.com[m.foot_body[k]][i]
-
-    # physics parameters
-    m.gravity = 9.8                 # env_base.py:80
     m.dt = 1.0 / 240.0              # env_base.py:81 with env_locomotion.py:39-41
     m.n_substeps = 4                # env_locomotion.py:41
-    m.n_iters = 5                   # bullet_utils.py:340
-    m.erp = 0.9                     # bullet_utils.py:345: setDefaultContactERP = infoGlobal.m_erp2, the contact rows' ERP
-    m.erp_noncontact = ERP_NONCONTACT
-    m.friction_cone = FRICTION_CONE
-    m.limit_at_violation = LIMIT_AT_VIOLATION
-    m.contact_margin = CONTACT_BREAKING_THRESHOLD   # gContactBreakingThreshold: the FACTOR of the relative thresholds in g_margin (above)
-    m.lin_damp = 0.04               # [UNVERIFIED-BULLET] btMultiBody default; applies to the base and to every link, with the quadratic term
-    m.ang_damp = 0.04
-    m.max_qd = 100.0                # [UNVERIFIED-BULLET] maxCoordinateVelocity
-    m.warmstart = WARMSTART
-    m.ground_friction = 0.8         # bullet_utils.py:371
     set_stepper_params(m, plank_class=plank_class)   # plank geometry, terrain ranges, curricula (LargePlank: 0.5 x 10 x 0.25 m slab)
-    m.limit_slack = 0.05
-    m.max_contacts = 12
-    m.max_rows = 48
-
-    for k in range(3):
-        m.init_pos[k] = init_pos[k]
-    for k in range(4):
-        m.init_quat[k] = init_quat_xyzw[k]
-    m.control_dt = 1.0 / 60.0       # env_locomotion.py:39
-    m.termination_height = 0.7      # env_locomotion.py:44
-    m.electricity_cost = 4.5        # env_locomotion.py:54
-    m.stall_torque_cost = 0.225     # env_locomotion.py:55
-    m.joints_at_limit_cost = 0.1    # env_locomotion.py:56
-    m.max_episode_steps = 1000      # __init__.py:55
-    m.n_mirror_side, m.n_mirror_neg = len(mirror_right), len(mirror_neg)
-    for k, v in enumerate(mirror_right):
-        m.mirror_right[k] = v
-    for k, v in enumerate(mirror_left):
-        m.mirror_left[k] = v
-    for k, v in enumerate(mirror_neg):
-        m.mirror_neg[k] = v
+    _put(m.init_pos, init_pos)
+    _put(m.init_quat, init_quat_xyzw)
+    _set_walker_task(m, termination_height=0.7)
+    _set_mirror(m, mirror_right, mirror_left, mirror_neg)
     return m.finalize_tables()
 
 
@@ -900,6 +923,39 @@ def _rpy_mat(rpy) -> np.ndarray:
                      [-sp, cp * sr, cp * cr]])
 
 
+def _urdf_links(table, root: str, contents, R: np.ndarray = np.eye(3), t: np.ndarray = np.zeros(3)) -> List[_Link]:
+    """URDF front end: depth-first walk of a table module (`LINKS`, `JOINTS`: cassie_table, laikago_table) from link `root`, read
+    at call time.  Every moving joint starts a flat link named after it (axis normalised, a missing limit is +-1e30); a fixed joint
+    merges its child into the link it hangs from.  `contents(link, R, t)` -> (inertial parts, geoms) of the URDF link `link` placed
+    in its flat link's frame by x -> R x + t; the root link sits at (R, t)."""
+    kids: Dict[str, list] = {}
+    for j in table.JOINTS:
+        kids.setdefault(j["parent"], []).append(j)
+    links = [_Link(root, -1)]
+
+    def visit(name: str, b: int, R: np.ndarray, t: np.ndarray):
+        parts, geoms = contents(name, R, t)
+        links[b].parts += parts
+        links[b].geoms += geoms
+        for j in kids.get(name, []):
+            Rj, tj = R @ _rpy_mat(j["rpy"]), R @ np.asarray(j["xyz"], float) + t
+            if j["type"] == "fixed":
+                visit(j["child"], b, Rj, tj)
+            else:
+                axis = np.asarray(j["axis"], float)
+                links.append(_Link(j["name"], b, tj, Rj, axis / np.linalg.norm(axis),
+                                   j["lower"] if j["lower"] is not None else -1e30, j["upper"] if j["upper"] is not None else 1e30))
+                visit(j["child"], len(links) - 1, np.eye(3), np.zeros(3))
+
+    visit(root, 0, R, t)
+    return links
+
+
+def _urdf_point(p: np.ndarray, radius: float, friction: float, **kw) -> _FlatGeom:
+    """A contact sphere of a URDF robot; radius 0: a support point of a mesh's convex hull."""
+    return _FlatGeom(GEOM_SPHERE, radius, p, p, friction, **kw)
+
+
 CASSIE_ORDERED_JOINTS = [s % side for side in ("left", "right") for s in (
     "hip_abduction_%s", "hip_rotation_%s", "hip_flexion_%s", "knee_joint_%s", "knee_to_shin_%s", "ankle_joint_%s",
     "toe_joint_%s")]
@@ -915,31 +971,6 @@ CASSIE_SPRINGS = [4, 11]                                                        
 CASSIE_KP = np.array([100, 100, 88, 96, 50, 100, 100, 88, 96, 50, 400, 400]) / 1.9  # env_cassie.py:292-317
 
 
-# Bullet defaults the reference never touches (bullet_utils.py:338-350 sets the time step, 5 iterations, 4 substeps and the CONTACT erp only),
-# restated from the published source as recalled  [UNVERIFIED-BULLET]:
-#  * rows that are not contacts (joint limits, point-to-point closures) take infoGlobal.m_erp = 0.2, not the contact ERP (m_erp2) that
-#    setDefaultContactERP(0.9) sets: btMultiBodyConstraint::fillMultiBodyConstraint ("split impulse is not implemented yet for
-#    btMultiBody*": erp = infoGlobal.m_erp), btMultiBodyJointLimitConstraint::createConstraintRows;
-#  * multibody contact rows do NOT warm start: btMultiBodyConstraintSolver::setupMultiBodyContactConstraint, "disable warmstarting for
-#    btMultiBody, it has issues gaining energy (==explosion)", `if (0)`; later versions gate it behind SOLVER_USE_ARTICULATED_WARMSTARTING,
-#    which pybullet's default solver mode does not contain.  (Rounds 1-3 early used 0.85, btContactSolverInfo's rigid-body factor.)
-#  * the two friction rows of a contact are coupled ("implicit cone friction", Bullet >= 2.87): both candidate impulses from the same
-#    velocity state, the pair clipped to the circle of radius mu * lambda_n (btMultiBodyConstraintSolver::resolveConeFrictionConstraintRows);
-#    pybullet: setPhysicsEngineParameter(enableConeFriction=0) selects the pyramid, "cone is default".  (Pyramid until round 3 late.)
-#  * a joint-limit row exists only while the joint is at or past its limit: btMultiBodyJointLimitConstraint::createConstraintRows,
-#    "//todo: consider adding some safety threshold here / if (penetration > 0) continue;" -- the joint crosses the limit by up to
-#    speed x dt and is pushed back with the non-contact ERP.  (Until round 3 late: a row from a predicted gap of 0.05 rad on, which stops the
-#    joint AT the limit -- the older form of that file, whose positive-gap branch `velocityError = -penetration / dt` is still in the source.)
-#  * contacts open within the RELATIVE breaking threshold 0.02 x getAngularMotionDisc() of the smaller of the two collision objects
-#    (btCollisionDispatcher::getNewManifold, CD_USE_RELATIVE_CONTACT_BREAKING_THRESHOLD on by default; MoccaModel.g_margin): 3 - 6 mm for a
-#    walker's links.  (Until round 3 late: 20 mm for every pair.)
-CONTACT_BREAKING_THRESHOLD = 0.02
-MARGIN_UNIT = 2.0 ** -13      # slot_tab carries a geom's margin as an 8-bit multiple of this (0.122 mm; up to 31 mm)
-ERP_NONCONTACT = 0.2
-WARMSTART = 0.0
-FRICTION_CONE = 1
-LIMIT_AT_VIOLATION = 1
-
 CASSIE_PLAIN, CASSIE_PHASE_MOCCA, CASSIE_PHASE_MIRROR = 0, 1, 2   # MoccaModel.cassie_mode (include/mocca_model.h)
 # Cassie2D (env_cassie.py:279-282) loads cassie_collide_2d.urdf.  The class's path (data/cassie/urdf/) does not exist in the reference's
 # tree; the file it means lies beside the 3-D one, data/robots/cassie/urdf/cassie_collide_2d.urdf.  It differs from cassie_collide.urdf in
@@ -950,24 +981,40 @@ CASSIE_2D_LIMITS = {"hip_abduction_left": (-0.01, 0.01), "hip_rotation_left": (-
                     "hip_abduction_right": (-0.01, 0.01), "hip_rotation_right": (-0.01, 0.01)}
 
 
+def _cassie_links(planar: bool = False) -> List[_Link]:
+    """Cassie's flat links from mocca_envs_amd/cassie_table.py: inertia from file (env_cassie.py:81-99), 12 support points of each
+    toe's convex hull as radius-0 spheres; a toe is one convex mesh, so its points share one contact margin, at the toe link's COM."""
+    from . import cassie_table as CT
+
+    def contents(link, R, t):
+        e = CT.LINKS[link]
+        parts, geoms = [], []
+        if e["mass"] != 0.0:
+            Ri = R @ _rpy_mat(e["rpy"])
+            xx, yy, zz, xy, xz, yz = e["inertia"]
+            I = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
+            parts.append((e["mass"], R @ np.asarray(e["com"], float) + t, Ri @ I @ Ri.T))
+        if link.endswith("_toe"):
+            side = link.split("_")[0]
+            geoms = [_urdf_point(R @ np.asarray(p, float) + t, 0.0, e["friction"] or 1.0, foot=("right", "left").index(side))
+                     for p in CT.TOE_POINTS[side]]
+        return parts, geoms
+
+    links = _urdf_links(CT, "pelvis", contents)
+    for link in links:
+        if planar and link.name in CASSIE_2D_LIMITS:
+            link.lo, link.hi = CASSIE_2D_LIMITS[link.name]
+    return links
+
+
 def cassie_joint_names():
     """(joint names, link names) of the Cassie blob's bodies 1 .. 18, in blob order: the URDF's moving joints, depth-first as compile_cassie
     walks them (a joint named "fixed_*_achilles_rod_joint_*" is a CONTINUOUS joint: the reference only keeps it out of its ordered joints,
     env_cassie.py:189).  What pybullet_dump.from_pybullet_dump matches a PyBullet record against."""
     from . import cassie_table as CT
-    kids: Dict[str, list] = {}
-    for j in CT.JOINTS:
-        kids.setdefault(j["parent"], []).append(j)
-    jn, ln = [], []
-
-    def walk(link):
-        for j in kids.get(link, []):
-            if j["type"] != "fixed":
-                jn.append(j["name"]); ln.append(j["child"])
-            walk(j["child"])
-
-    walk("pelvis")
-    return jn, ln
+    child = {j["name"]: j["child"] for j in CT.JOINTS}
+    jn = [link.name for link in _cassie_links()[1:]]
+    return jn, [child[n] for n in jn]
 
 
 def compile_cassie(planar: bool = False, power_coef: float = 1.0, residual_control: bool = True, mode: int = CASSIE_PLAIN,
@@ -977,94 +1024,12 @@ def compile_cassie(planar: bool = False, power_coef: float = 1.0, residual_contr
     Ground contact: 12 support points of each toe's convex hull (radius-0 spheres); other meshes and mesh-mesh
     self collision are not modelled (the episode ends when the pelvis is 0.6 m above the lower toe, :406-412)."""
     from . import cassie_table as CT
-    kids: Dict[str, list] = {}
-    for j in CT.JOINTS:
-        kids.setdefault(j["parent"], []).append(j)
-    bodies = []  # dict(name, parent, jpos, jrot, axis, lo, hi, joint, parts[], points[])
-
-    def inertial(link, R, t):
-        e = CT.LINKS[link]
-        if e["mass"] == 0.0:
-            return None
-        Ri = R @ _rpy_mat(e["rpy"])
-        xx, yy, zz, xy, xz, yz = e["inertia"]
-        I = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
-        return e["mass"], R @ np.asarray(e["com"], float) + t, Ri @ I @ Ri.T
-
-    def visit(link, body, R, t):
-        part = inertial(link, R, t)
-        if part is not None:
-            bodies[body]["parts"].append(part)
-        if link.endswith("_toe"):
-            side = link.split("_")[0]
-            for p in CT.TOE_POINTS[side]:
-                bodies[body]["points"].append((R @ np.asarray(p, float) + t, CT.LINKS[link]["friction"] or 1.0))
-        bodies[body]["links"][link] = (R.copy(), t.copy())
-        for j in kids.get(link, []):
-            Rj, tj = R @ _rpy_mat(j["rpy"]), R @ np.asarray(j["xyz"], float) + t
-            if j["type"] == "fixed":
-                visit(j["child"], body, Rj, tj)
-            else:
-                lo = j["lower"] if j["lower"] is not None else -1e30
-                hi = j["upper"] if j["upper"] is not None else 1e30
-                if planar and j["name"] in CASSIE_2D_LIMITS:
-                    lo, hi = CASSIE_2D_LIMITS[j["name"]]
-                bodies.append(dict(name=j["name"], parent=body, jpos=tj, jrot=Rj, axis=np.asarray(j["axis"], float),
-                                   lo=lo, hi=hi, parts=[], points=[], links={}))
-                visit(j["child"], len(bodies) - 1, np.eye(3), np.zeros(3))
-
-    bodies.append(dict(name="pelvis", parent=-1, jpos=np.zeros(3), jrot=np.eye(3), axis=None, lo=0, hi=0, parts=[],
-                       points=[], links={}))
-    visit("pelvis", 0, np.eye(3), np.zeros(3))
-    nb = len(bodies)
-    m = MoccaModel()
-    m.magic, m.version = MAGIC, VERSION
-    m.n_bodies, m.n_joints = nb, nb - 1
-    names = [b["name"] for b in bodies]
-    g = 0
-    for b, bd in enumerate(bodies):
-        m.parent[b] = bd["parent"]
-        if b:
-            m.anc_mask[b] = m.anc_mask[bd["parent"]] | (1 << b)
-            m.depth[b] = m.depth[bd["parent"]] + 1
-            for k in range(3):
-                m.jpos[b][k] = bd["jpos"][k]
-                m.jaxis[b][k] = bd["axis"][k] / np.linalg.norm(bd["axis"])
-            for k in range(9):
-                m.jrot[b][k] = bd["jrot"].reshape(-1)[k]
-            m.jlo[b], m.jhi[b] = bd["lo"], bd["hi"]
-            stem = bd["name"].rsplit("_", 1)[0]
-            m.torque_limit[b] = power_coef * CASSIE_POWER.get(stem, 0.0)      # base_power * power_coef[name], env_cassie.py:192-195
-            m.init_q[b] = CASSIE_ROD_ANGLES.get(bd["name"], 0.0)
-        mass, com, I = _compose_inertial(bd["parts"])
-        m.mass[b] = mass
-        for k in range(3):
-            m.com[b][k] = com[k]
-        for k, (i, j) in enumerate([(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]):
-            m.inertia[b][k] = I[i, j]
-        for p, fr in bd["points"]:
-            m.g_body[g], m.g_type[g], m.g_radius[g], m.g_slot[g], m.g_terrain[g] = b, GEOM_SPHERE, 0.0, g, 1
-            m.g_friction[g] = fr
-            for k in range(3):
-                m.g_p1[g][k] = m.g_p2[g][k] = p[k]
-            g += 1
-    m.n_geoms = m.n_slots = g
-    m.n_pairs = 0
-    m.n_feet = 2
-    # relative contact breaking threshold of each toe (one convex mesh = one collision object): from the AABB of its hull points
-    groups = {}
-    for gi in range(m.n_geoms):
-        bb = m.g_body[gi]
-        groups.setdefault(bb, []).append((GEOM_SPHERE, 0.0, list(m.g_p1[gi]), list(m.g_p1[gi]), 1.0, list(m.com[bb])))
-    rel = relative_margins(CONTACT_BREAKING_THRESHOLD, groups)
-    for gi in range(m.n_geoms):
-        m.g_margin[gi] = rel[m.g_body[gi]]
-    m.foot_body[0], m.foot_body[1] = names.index("toe_joint_right"), names.index("toe_joint_left")  # env_cassie.py:72
-    for gi in range(m.n_geoms):
-        m.g_foot[gi] = next((k for k in range(2) if m.foot_body[k] == m.g_body[gi]), -1)
-    for k in range(2):
-        for i in range(3):
-            m.foot_point[k][i] = m.com[m.foot_body[k]][i]
+    links = _cassie_links(planar)
+    names = [link.name for link in links]
+    m = _assemble(links, [(names.index("toe_joint_right"), None), (names.index("toe_joint_left"), None)])   # env_cassie.py:72
+    for b in range(1, m.n_bodies):
+        m.torque_limit[b] = power_coef * CASSIE_POWER.get(names[b].rsplit("_", 1)[0], 0.0)   # base_power * power_coef[name], env_cassie.py:192-195
+        m.init_q[b] = CASSIE_ROD_ANGLES.get(names[b], 0.0)
     # ordered joints, controller
     m.n_ordered = len(CASSIE_ORDERED_JOINTS)
     for k, n in enumerate(CASSIE_ORDERED_JOINTS):
@@ -1089,45 +1054,34 @@ def compile_cassie(planar: bool = False, power_coef: float = 1.0, residual_contr
         # createConstraint frames are relative to each link's CENTRE-OF-MASS frame: with the COM offsets the two
         # pivots coincide to 2.9 mm in the nominal pose (and the rod pivot lands at 0.5012 m, the rod's length)
         ca, cb = CT.LINKS["%s_tarsus" % side]["com"], CT.LINKS["%s_achilles_rod" % side]["com"]
-        for i, v in enumerate((-0.22735404, 0.05761813, z)):
-            m.cl_point_a[k][i] = ca[i] + v
-        for i, v in enumerate((0.254001, 0.0, 0.0)):
-            m.cl_point_b[k][i] = cb[i] + v
+        _put(m.cl_point_a[k], [c + v for c, v in zip(ca, (-0.22735404, 0.05761813, z))])
+        _put(m.cl_point_b[k], [c + v for c, v in zip(cb, (0.254001, 0.0, 0.0))])
     # physics: env_cassie.py:287-289 control_step 0.03 / llc 50 / sim_frame_skip 1
-    m.gravity, m.dt, m.n_substeps, m.n_iters, m.erp = 9.8, 0.03 / 50, 1, 5, 0.9
-    m.erp_noncontact = ERP_NONCONTACT   # the two point-to-point closures (btMultiBodyPoint2Point -> fillMultiBodyConstraint) and the limits
-    m.friction_cone = FRICTION_CONE
-    m.limit_at_violation = LIMIT_AT_VIOLATION
-    m.n_llc = 50
-    m.contact_margin, m.lin_damp, m.ang_damp, m.max_qd, m.warmstart = CONTACT_BREAKING_THRESHOLD, 0.04, 0.04, 100.0, WARMSTART
-    m.ground_friction = 0.8
-    m.limit_slack, m.max_contacts, m.max_rows = 0.05, 12, 48
+    m.dt, m.n_substeps, m.n_llc = 0.03 / 50, 1, 50
     # each toe is ONE convex mesh in cassie_collide.urdf: Bullet keeps at most 4 contact points per pair of collision objects
     # (btPersistentManifold)  [UNVERIFIED-BULLET] -- of the twelve hull points of a toe on the ground four make contacts, not twelve
     # (which also overran the solver's 12-contact cap in 84 % of the substeps of a standing robot, profiles/archive/r03_cap_pressure.jsonl)
     m.manifold_max = 4
-    m.init_pos[0], m.init_pos[1], m.init_pos[2] = 0.0, 0.0, 1.085            # env_cassie.py:17
+    _put(m.init_pos, (0.0, 0.0, 1.085))                                      # env_cassie.py:17
     m.init_quat[3] = 1.0
     m.control_dt = 0.03
     m.max_episode_steps = 1000                                               # __init__.py:18-22
     m.jvel_alpha = min(10 / 50, 1)                                           # env_cassie.py:319
     m.alive_height = 0.6                                                     # env_cassie.py:406-412
-    m.cassie_target[0], m.cassie_target[1], m.cassie_target[2] = 1000.0, 0.0, 0.0  # env_cassie.py:366
+    _put(m.cassie_target, (1000.0, 0.0, 0.0))                                # env_cassie.py:366
     m.planar = int(planar)                                                   # env_cassie.py:326-341 (Cassie2DEnv-v0, __init__.py:24-29)
     # mocap / phase variants (env_cassie.py:481-660)
     m.cassie_mode, m.cassie_rsi, m.residual_control = int(mode), int(bool(rsi)), int(bool(residual_control))
-    for k, n in enumerate(("fixed_right_achilles_rod_joint_z", "fixed_right_achilles_rod_joint_y",
-                           "fixed_left_achilles_rod_joint_z", "fixed_left_achilles_rod_joint_y")):   # resetJoints, :591-596
-        m.rod_body[k] = names.index(n)
+    _put(m.rod_body, [names.index(n) for n in ("fixed_right_achilles_rod_joint_z", "fixed_right_achilles_rod_joint_y",
+                                                "fixed_left_achilles_rod_joint_z", "fixed_left_achilles_rod_joint_y")])   # resetJoints, :591-596
     if mode != CASSIE_PLAIN:
         # CassieMocapRewEnv.__init__ (:483-493): the joint terms share what the four fixed weights leave
         w = {"SpeedRew": 0.1, "CoMRew": 0.02 if planar else 0.05, "OrientationRew": 0.0 if planar else 0.05, "AngularSpeedRew": 0.1}
         wleft = 1 - sum(w.values())
         w["JPosRew"], w["JVelRew"] = wleft / 5 * 4, wleft / 5
-        for k, n in enumerate(("SpeedRew", "JPosRew", "JVelRew", "OrientationRew", "AngularSpeedRew", "CoMRew")):
-            m.mocap_w[k] = w[n]
+        _put(m.mocap_w, [w[n] for n in ("SpeedRew", "JPosRew", "JVelRew", "OrientationRew", "AngularSpeedRew", "CoMRew")])
         m.mocap_speed = 0.8                                                  # :498
-        m.init_vel[0], m.init_vel[1], m.init_vel[2] = 0.8, 0.0, 0.0          # CassieMoccaEnv.initial_velocity, :552
+        _put(m.init_vel, (0.8, 0.0, 0.0))                                    # CassieMoccaEnv.initial_velocity, :552
     return m.finalize_tables()
 
 
@@ -1149,119 +1103,52 @@ def compile_laikago(stepper: bool = False, plank_class: str = "LargePlank") -> M
     * Ground contact: the four toe spheres (the feet) and 28 support points of the link meshes' convex hulls (radius-0
       spheres, no foot index): touching the ground with any of those ends the episode.  Mesh-mesh self collision
       (URDF_USE_SELF_COLLISION) is not modelled.
+    * Contact margins: a toe sphere is a collision object of its own (fixed child link); the hull points of the mesh links are
+      grouped by the body they move with.
     """
     from . import laikago_table as LT
-    kids: Dict[str, list] = {}
-    for j in LT.JOINTS:
-        kids.setdefault(j["parent"], []).append(j)
-    bodies = []  # dict(name, parent, jpos, jrot, axis, lo, hi, parts[], geoms[])
 
-    def visit(link, body, R, t):
+    def contents(link, R, t):
         e = LT.LINKS[link]
-        Ri = R @ _rpy_mat(e["rpy"])
+        parts, geoms = [], []
         if e["mass"] > 0.0:
             if e["sphere"] is not None:
                 I = np.eye(3) * 0.4 * e["mass"] * e["sphere"]["radius"] ** 2
             else:
+                Ri = R @ _rpy_mat(e["rpy"])
                 hx, hy, hz = (h + LAIKAGO_SHAPE_MARGIN for h in e["box_half"])
                 I = Ri @ np.diag([hy * hy + hz * hz, hx * hx + hz * hz, hx * hx + hy * hy]) @ Ri.T * (e["mass"] / 3.0)
-            bodies[body]["parts"].append((e["mass"], R @ np.asarray(e["com"], float) + t, I))
+            parts.append((e["mass"], R @ np.asarray(e["com"], float) + t, I))
         fr = e["friction"] if e["friction"] is not None else 1.0
         if e["sphere"] is not None:
-            bodies[body]["geoms"].append((R @ np.asarray(e["sphere"]["center"], float) + t, e["sphere"]["radius"], fr, link))
-        for p in e["points"]:
-            bodies[body]["geoms"].append((R @ np.asarray(p, float) + t, 0.0, fr, None))
-        for j in kids.get(link, []):
-            Rj, tj = R @ _rpy_mat(j["rpy"]), R @ np.asarray(j["xyz"], float) + t
-            if j["type"] == "fixed":
-                visit(j["child"], body, Rj, tj)
-            else:
-                bodies.append(dict(name=j["name"], parent=body, jpos=tj, jrot=Rj, axis=np.asarray(j["axis"], float),
-                                   lo=j["lower"], hi=j["upper"], parts=[], geoms=[]))
-                visit(j["child"], len(bodies) - 1, np.eye(3), np.zeros(3))
+            g = _urdf_point(R @ np.asarray(e["sphere"]["center"], float) + t, e["sphere"]["radius"], fr)
+            if link in LAIKAGO_FEET:
+                g.foot, g.margin_key, g.margin_weight = LAIKAGO_FEET.index(link), link, (1.0, g.p1)
+            geoms.append(g)
+        geoms += [_urdf_point(R @ np.asarray(p, float) + t, 0.0, fr) for p in e["points"]]
+        return parts, geoms
 
     ch = LT.LINKS["chassis"]
     R0 = _rpy_mat(ch["rpy"]).T
-    bodies.append(dict(name="chassis", parent=-1, jpos=np.zeros(3), jrot=np.eye(3), axis=None, lo=0, hi=0, parts=[], geoms=[]))
-    visit("chassis", 0, R0, -R0 @ np.asarray(ch["com"], float))
-    names = [b["name"] for b in bodies]
-    assert names[1:] == LAIKAGO_JOINTS, names      # URDF order == ordered_joints order (robots.py:609-626)
-    nb = len(bodies)
-    m = MoccaModel()
-    m.magic, m.version = MAGIC, VERSION
-    m.n_bodies, m.n_joints = nb, nb - 1
-    g = 0
-    m.n_feet = 4
-    for b, bd in enumerate(bodies):
-        m.parent[b] = bd["parent"]
-        if b:
-            m.anc_mask[b] = m.anc_mask[bd["parent"]] | (1 << b)
-            m.depth[b] = m.depth[bd["parent"]] + 1
-            for k in range(3):
-                m.jpos[b][k] = bd["jpos"][k]
-                m.jaxis[b][k] = bd["axis"][k] / np.linalg.norm(bd["axis"])
-            for k in range(9):
-                m.jrot[b][k] = bd["jrot"].reshape(-1)[k]
-            m.jlo[b], m.jhi[b] = bd["lo"], bd["hi"]
-            m.gain[b] = 40.0                                                          # robots.py:561-574, base_power 1
-            m.init_q[b] = -math.pi / 6 if bd["name"].endswith("lower_leg_2_upper_leg_joint") else 0.0   # "running_start", :654-655
-        mass, com, I = _compose_inertial(bd["parts"])
-        m.mass[b] = mass
-        for k in range(3):
-            m.com[b][k] = com[k]
-        for k, (i, j) in enumerate([(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]):
-            m.inertia[b][k] = I[i, j]
-        for p, rad, fr, toe in bd["geoms"]:
-            m.g_body[g], m.g_type[g], m.g_radius[g], m.g_slot[g], m.g_terrain[g] = b, GEOM_SPHERE, rad, g, 1
-            m.g_friction[g] = fr
-            m.g_foot[g] = LAIKAGO_FEET.index(toe) if toe in LAIKAGO_FEET else -1
-            if toe in LAIKAGO_FEET:      # the foot link is the toe, a fixed child: its COM is the sphere centre
-                m.foot_body[LAIKAGO_FEET.index(toe)] = b
-                for k in range(3):
-                    m.foot_point[LAIKAGO_FEET.index(toe)][k] = p[k]
-            for k in range(3):
-                m.g_p1[g][k] = m.g_p2[g][k] = p[k]
-            g += 1
-    assert g <= MAX_GEOMS
-    m.n_geoms = m.n_slots = g
-    m.n_pairs = 0
-    # relative contact breaking thresholds: a toe sphere is a collision object of its own (fixed child link); the hull points of the
-    # mesh links are grouped by the body they move with
-    groups = {}
-    for gi in range(m.n_geoms):
-        bb, rr, pp = m.g_body[gi], m.g_radius[gi], list(m.g_p1[gi])
-        key = ("toe", gi) if m.g_foot[gi] >= 0 else ("body", bb)
-        groups.setdefault(key, []).append((GEOM_SPHERE, rr, pp, pp, 1.0, pp if m.g_foot[gi] >= 0 else list(m.com[bb])))
-    rel = relative_margins(CONTACT_BREAKING_THRESHOLD, groups)
-    for gi in range(m.n_geoms):
-        m.g_margin[gi] = rel[("toe", gi) if m.g_foot[gi] >= 0 else ("body", m.g_body[gi])]
-    # physics: control_step 1/60, sim_frame_skip 8 (env_locomotion.py:856-858) -> 8 substeps of 1/480 s
-    m.gravity, m.dt, m.n_substeps, m.n_iters, m.erp = 9.8, 1.0 / 480.0, 8, 5, 0.9
-    m.erp_noncontact = ERP_NONCONTACT
-    m.friction_cone = FRICTION_CONE
-    m.limit_at_violation = LIMIT_AT_VIOLATION
-    m.contact_margin, m.lin_damp, m.ang_damp, m.max_qd, m.warmstart = CONTACT_BREAKING_THRESHOLD, 0.04, 0.04, 100.0, WARMSTART
-    m.ground_friction = 0.8
-    m.limit_slack, m.max_contacts, m.max_rows = 0.05, 12, 48
-    m.init_pos[0], m.init_pos[1], m.init_pos[2] = 0.0, 0.0, 0.56                      # env_locomotion.py:864
+    links = _urdf_links(LT, "chassis", contents, R0, -R0 @ np.asarray(ch["com"], float))
+    assert [link.name for link in links[1:]] == LAIKAGO_JOINTS      # URDF order == ordered_joints order (robots.py:609-626)
+    # the foot link is the toe, a fixed child: its COM is the sphere centre
+    feet = {g.foot: (b, g.p1) for b, link in enumerate(links) for g in link.geoms if g.foot >= 0}
+    m = _assemble(links, [feet[k] for k in range(len(LAIKAGO_FEET))])
+    for b in range(1, m.n_bodies):
+        m.gain[b] = 40.0                                                          # robots.py:561-574, base_power 1
+        m.init_q[b] = -math.pi / 6 if links[b].name.endswith("lower_leg_2_upper_leg_joint") else 0.0   # "running_start", :654-655
+    # LaikagoStepperEnv (env_locomotion.py:893-979): sim_frame_skip 4 -> 4 substeps of 1/240 s, start at (0.25, 0, 0.53) moving
+    # at (0.5, 0, 0.25), four live planks of step_radius 0.16, its own reward / termination (MOCCA_TASKF_QUADRUPED_STEPPER);
+    # LaikagoCustomEnv: control_step 1/60, sim_frame_skip 8 (env_locomotion.py:856-858) -> 8 substeps of 1/480 s, start at (0, 0, 0.56)
+    m.dt, m.n_substeps = (1.0 / 240.0, 4) if stepper else (1.0 / 480.0, 8)
+    _put(m.init_pos, (0.25, 0.0, 0.53) if stepper else (0.0, 0.0, 0.56))     # :864
     m.init_quat[3] = 1.0
-    m.control_dt = 1.0 / 60.0
-    m.termination_height = 0.0                                                        # :862
-    m.electricity_cost, m.stall_torque_cost, m.joints_at_limit_cost = 4.5, 0.225, 0.1
-    m.max_episode_steps = 1000
-    right, left = [0, 1, 2, 6, 7, 8], [3, 4, 5, 9, 10, 11]                            # robots.py:578-580
-    m.n_mirror_side, m.n_mirror_neg = len(right), 0
-    for k, v in enumerate(right):
-        m.mirror_right[k] = v
-    for k, v in enumerate(left):
-        m.mirror_left[k] = v
+    _set_walker_task(m, termination_height=0.0)                               # :862
+    _set_mirror(m, [0, 1, 2, 6, 7, 8], [3, 4, 5, 9, 10, 11])                  # robots.py:578-580
     m.task_flags |= TASKF_BODY_CONTACT
     if stepper:
-        # LaikagoStepperEnv (env_locomotion.py:893-979): sim_frame_skip 4 -> 4 substeps of 1/240 s, start at (0.25, 0, 0.53) moving
-        # at (0.5, 0, 0.25), four live planks of step_radius 0.16, its own reward / termination (MOCCA_TASKF_QUADRUPED_STEPPER)
-        m.dt, m.n_substeps = 1.0 / 240.0, 4
-        m.init_pos[0], m.init_pos[1], m.init_pos[2] = 0.25, 0.0, 0.53
-        m.init_vel[0], m.init_vel[1], m.init_vel[2] = 0.5, 0.0, 0.25
+        _put(m.init_vel, (0.5, 0.0, 0.25))
         set_stepper_params(m, quadruped=True, plank_class=plank_class)
         m.task_flags = (m.task_flags & ~TASKF_BODY_CONTACT) | TASKF_QUADRUPED_STEPPER
     return m.finalize_tables()

@@ -156,11 +156,9 @@ def from_pybullet_dump(dump: Mapping[str, np.ndarray], template: M.MoccaModel, j
     for b in range(1, out.n_bodies):
         j = link_of[b]
         rel = frame[out.parent[b]].inv() @ frame[b]
-        for k in range(3):
-            out.jpos[b][k] = rel.t[k]
-            out.jaxis[b][k] = axis[j][k]
-        for k in range(9):
-            out.jrot[b][k] = rel.R.reshape(-1)[k]
+        M._put(out.jpos[b], rel.t)
+        M._put(out.jaxis[b], axis[j])
+        M._put(out.jrot[b], rel.R.reshape(-1))
         out.jlo[b], out.jhi[b] = float(dump["joint_limits"][j][0]), float(dump["joint_limits"][j][1])
         out.jdamp[b] = float(dump["joint_damping"][j])
         if armature is not None:
@@ -173,46 +171,27 @@ def from_pybullet_dump(dump: Mapping[str, np.ndarray], template: M.MoccaModel, j
             raise ValueError(f"hinge axis of {names[j]!r} differs from the template's")
 
     # inertial parameters: every Bullet link contributes to the template body it moves with
-    acc = {b: [0.0, np.zeros(3), []] for b in range(out.n_bodies)}
+    parts = {b: [] for b in range(out.n_bodies)}
     for k in range(n_links + 1):
         j = k - 1
         b = 0 if j < 0 else owner(j)
-        Cw = C[j]
-        rel = frame[b].inv() @ Cw                                   # inertial frame of the link in the body's frame
-        Ic = rel.R @ np.diag(inertia_diag[k]) @ rel.R.T
-        acc[b][0] += mass[k]
-        acc[b][1] += mass[k] * rel.t
-        acc[b][2].append((mass[k], rel.t, Ic))
-    for b in range(out.n_bodies):
-        mb = acc[b][0]
-        com = acc[b][1] / mb if mb > 0 else np.zeros(3)
-        I = np.zeros((3, 3))
-        for mk, ck, Ik in acc[b][2]:
-            d = ck - com
-            I += Ik + mk * ((d @ d) * np.eye(3) - np.outer(d, d))
-        out.mass[b] = mb
-        for k in range(3):
-            out.com[b][k] = com[k]
-        for k, (r, c) in enumerate([(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]):
-            out.inertia[b][k] = I[r, c]
+        rel = frame[b].inv() @ C[j]                                 # inertial frame of the link in the body's frame
+        parts[b].append((mass[k], rel.t, rel.R @ np.diag(inertia_diag[k]) @ rel.R.T))
+    for b, p in parts.items():
+        M._set_inertial(out, b, *M._compose_inertial(p))
 
     # geometry: the template's geoms (the robot file's shapes) re-expressed in the dump's link frames
     for g in range(out.n_geoms):
         b = out.g_body[g]
         re = frame[b].inv() @ tf[b]
-        for src, dst in ((template.g_p1[g], out.g_p1[g]), (template.g_p2[g], out.g_p2[g])):
-            p = re.apply(list(src))
-            for k in range(3):
-                dst[k] = p[k]
+        M._put(out.g_p1[g], re.apply(list(template.g_p1[g])))
+        M._put(out.g_p2[g], re.apply(list(template.g_p2[g])))
     for f in range(out.n_feet):
         fb = out.foot_body[f]
         if all(abs(template.foot_point[f][k] - template.com[fb][k]) < 1e-9 for k in range(3)):
-            for k in range(3):
-                out.foot_point[f][k] = out.com[fb][k]            # getLinkState()[0] = the foot link's centre of mass
+            M._put(out.foot_point[f], out.com[fb])              # getLinkState()[0] = the foot link's centre of mass
         else:
-            p = (frame[fb].inv() @ tf[fb]).apply(list(template.foot_point[f]))
-            for k in range(3):
-                out.foot_point[f][k] = p[k]
+            M._put(out.foot_point[f], (frame[fb].inv() @ tf[fb]).apply(list(template.foot_point[f])))
     # loop closures (Cassie: createConstraint(JOINT_POINT2POINT) tarsus <-> achilles rod, env_cassie.py:114-137): the record's
     # `constraints` rows [parent link, child link, joint type, parent pivot xyz, child pivot xyz] -- pivots in each link's INERTIAL frame,
     # as createConstraint takes them -- become the blob's pivots in its body frames
@@ -239,8 +218,8 @@ def from_pybullet_dump(dump: Mapping[str, np.ndarray], template: M.MoccaModel, j
             used.add(r)
             pa_b = (frame[template.cl_body_a[k]].inv() @ C[la]).apply(pa)
             pb_b = (frame[template.cl_body_b[k]].inv() @ C[lb]).apply(pb)
-            for i in range(3):
-                out.cl_point_a[k][i], out.cl_point_b[k][i] = pa_b[i], pb_b[i]
+            M._put(out.cl_point_a[k], pa_b)
+            M._put(out.cl_point_b[k], pb_b)
     # init_pos / init_quat are kept: the reference resets with resetBasePositionAndOrientation (bullet_utils.py:97-102), which
     # places Bullet's base frame -- now this blob's base frame -- at those values
     return out.finalize_tables()

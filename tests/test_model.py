@@ -33,7 +33,7 @@ def test_left_right_mirror_symmetry():
         assert m.gain[br] == m.gain[bl]
 
 
-def test_collision_filter():
+def test_collision_filter_on_flat_links():
     m = M.compile_walker3d()
     names = [g.name for g in _all_geoms(M.walker3d_description())]
     terrain = {names[g] for g in range(m.n_geoms) if m.g_terrain[g]}
@@ -50,25 +50,17 @@ def test_collision_filter():
 
 
 def _all_geoms(body):
-    # same DFS order as the compiler: own geoms, then merged hinge-less children, then hinged children
-    out = []
-
-    def rec(b, merged_into_parent):
-        out.extend(b.geoms)
-        for ch in b.children:
-            if not ch.hinges:
-                rec(ch, True)
-        for ch in b.children:
-            if ch.hinges:
-                rec(ch, False)
-    # the compiler's order is per flat body; rebuild by flat body index instead
-    flat, _, _ = M._flatten(body, "body_frame")
-    return [g for fb in flat for (g, _, _, _) in fb.geoms]
+    # the compiler's geom order: flat link by flat link
+    links, _, _ = M._flatten(body)
+    return [g.src for link in links for g in link.geoms]
 
 
 def test_topology_header_is_current():
-    hdr = open(os.path.join(ROOT, "mocca_envs_amd", "csrc", "topo_walker3d.h")).read()
-    assert hdr == M.topology_header(M.compile_walker3d(), "Walker3D"), "run python -m mocca_envs_amd.model"
+    for fname, build, name in (("walker3d", M.compile_walker3d, "Walker3D"), ("cassie", M.compile_cassie, "Cassie"),
+                               ("walker2d", M.compile_walker2d, "Walker2D"), ("crab2d", M.compile_crab2d, "Crab2D"),
+                               ("laikago", M.compile_laikago, "Laikago")):
+        hdr = open(os.path.join(ROOT, "mocca_envs_amd", "csrc", f"topo_{fname}.h")).read()
+        assert hdr == M.topology_header(build(), name), f"topo_{fname}.h is stale: run python -m mocca_envs_amd.model"
 
 
 def test_table_matches_reference_xml():

@@ -84,18 +84,8 @@ def main():
     assert rel.max() < 0.1, rel
 
     m = M.compile_cassie()
-    names = {b: None for b in range(m.n_bodies)}
     rod_bodies = []   # right z, right y, left z, left y (env_cassie.py:591-596)
-    # body order of the blob: recover names through the joint table used by compile_cassie
-    from mocca_envs_amd import cassie_table as CT
-    order = []
-
-    def walk(link):
-        for j in [j for j in CT.JOINTS if j["parent"] == link]:
-            if j["type"] != "fixed":
-                order.append(j["name"])
-            walk(j["child"])
-    walk("pelvis")
+    order = M.cassie_joint_names()[0]   # blob order of bodies 1 ..
     body_of = {n: i + 1 for i, n in enumerate(order)}
     for side in ("right", "left"):
         for ax in ("z", "y"):
