@@ -282,24 +282,42 @@ typedef struct MoccaModel {
 #define MOCCA_STATE_BASE 13
 #define MOCCA_STATE_DIM(nj, nslots) (13 + 2 * (nj) + (nslots))
 
-/* Per-env task record (32-bit words; f = float, i = int32), get/set_task():
- *   0 f walk_target.x   1 f walk_target.y   2 f walk_target.z
- *   3 f linear_potential 4 f angular_potential
- *   5 i close_count      6 f stop_frames     7 i done (sticky)
- *   8 i t (steps this episode)  9 i episode  10 i draw counter
- *  11 i mirrored        12 f feet_contact[0] 13 f feet_contact[1]
- *  14 f dist            15 f angle
- *  --- stepper only ---
- *  16 i next_step_index 17 i target_reached_count 18 i stop_on_next_step
- *  19 i set_stop_on_next_step 20 i curriculum 21 f applied_gain
- *  22 f prev_body_x  23 i constraint rows of the last physics substep (issue-priority hint for the next step: timing only)
- *  30..37 f reward weights of this step (Stepper with MOCCA_PARAM_RANDOM_REWARD, env_locomotion.py:533-547)
- *  --- quadrupeds only (n_feet == 4) ---
- *  24 f feet_contact[2]  25 f feet_contact[3]
- *  --- Cassie only ---
- *  3 f potential (shares linear_potential)  24..37 f jvel[14] (filtered joint speeds, env_cassie.py:451-468)
- *  38 f initial_z  39 i istep (mocap_time = istep * control_step / llc_frame_skip, env_cassie.py:359-360)
- */
+/* Per-env task record: MOCCA_TASK_WORDS 32-bit words per env, get/set_task().  The comment of each word gives its class (f = float,
+ * i = int32), then its length in words when it spans more than one, then the tasks that use it.  Entries at the same index are aliases:
+ * the env's task decides what the word holds.  (tests/test_task_record.py holds mocca_envs_amd/model.py TASK_RECORD to this enum.) */
+enum MoccaTaskWord {
+  MOCCA_TW_WALK_TARGET_X = 0,         /* f     walkers: walk_target */
+  MOCCA_TW_WALK_TARGET_Y = 1,         /* f     walkers */
+  MOCCA_TW_WALK_TARGET_Z = 2,         /* f     walkers */
+  MOCCA_TW_LINEAR_POTENTIAL = 3,      /* f     all (Cassie: its potential, env_cassie.py:348-354) */
+  MOCCA_TW_ANGULAR_POTENTIAL = 4,     /* f     walkers */
+  MOCCA_TW_CLOSE_COUNT = 5,           /* i     Custom */
+  MOCCA_TW_STOP_FRAMES = 6,           /* f     Custom */
+  MOCCA_TW_DONE = 7,                  /* i     all: sticky */
+  MOCCA_TW_T = 8,                     /* i     all: steps this episode */
+  MOCCA_TW_EPISODE = 9,               /* i     all */
+  MOCCA_TW_DRAW = 10,                 /* i     all: draw counter of the episode's random stream */
+  MOCCA_TW_MIRRORED = 11,             /* i     walkers */
+  MOCCA_TW_FEET_CONTACT_0 = 12,       /* f     walkers */
+  MOCCA_TW_FEET_CONTACT_1 = 13,       /* f     walkers */
+  MOCCA_TW_DIST = 14,                 /* f     Custom */
+  MOCCA_TW_ANGLE = 15,                /* f     Custom */
+  MOCCA_TW_NEXT_STEP_INDEX = 16,      /* i     Stepper */
+  MOCCA_TW_TARGET_REACHED_COUNT = 17, /* i     Stepper */
+  MOCCA_TW_STOP_ON_NEXT_STEP = 18,    /* i     Stepper */
+  MOCCA_TW_SET_STOP_ON_NEXT_STEP = 19, /* i     Stepper */
+  MOCCA_TW_CURRICULUM = 20,           /* i     Stepper */
+  MOCCA_TW_APPLIED_GAIN = 21,         /* f     all */
+  MOCCA_TW_PREV_BODY_X = 22,          /* f     walkers */
+  MOCCA_TW_LAST_ROWS = 23,            /* i     all: constraint rows of the last physics substep (issue-priority hint for the next step: timing only) */
+  MOCCA_TW_FEET_CONTACT_2 = 24,       /* f     quadrupeds (n_feet == 4) */
+  MOCCA_TW_JVEL = 24,                 /* f 14  Cassie: filtered joint speeds jvel[14] (env_cassie.py:451-468) */
+  MOCCA_TW_FEET_CONTACT_3 = 25,       /* f     quadrupeds */
+  MOCCA_TW_COVER = 26,                /* f     Stepper: cover mask of the last substep's contacts, as a float (MOCCA_TASKF_STALE_RESET_CONTACTS) */
+  MOCCA_TW_REWARD_WEIGHTS = 30,       /* f 8   Stepper: reward weights of this step (MOCCA_PARAM_RANDOM_REWARD, env_locomotion.py:533-547) */
+  MOCCA_TW_INITIAL_Z = 38,            /* f     Cassie */
+  MOCCA_TW_ISTEP = 39                 /* i     Cassie: mocap_time = istep * control_step / llc_frame_skip (env_cassie.py:359-360) */
+};
 #define MOCCA_TASK_WORDS 40
 
 #ifdef __cplusplus

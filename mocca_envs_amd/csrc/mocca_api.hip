@@ -47,7 +47,7 @@ __global__ __launch_bounds__(1024) void order_by_rows_kernel(const uint32_t* tas
   if (t < 64) hist[t] = 0;
   __syncthreads();
   for (int e = t; e < n; e += 1024) {
-    const uint32_t r = task[(size_t)e * MOCCA_TASK_WORDS + T_RES23];
+    const uint32_t r = task[(size_t)e * MOCCA_TASK_WORDS + MOCCA_TW_LAST_ROWS];
     atomicAdd(&hist[63 - (r > 63u ? 63u : r)], 1);   // bucket 0 = heaviest
   }
   __syncthreads();
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(1024) void order_by_rows_kernel(const uint32_t* tas
   }
   __syncthreads();
   for (int e = t; e < n; e += 1024) {
-    const uint32_t r = task[(size_t)e * MOCCA_TASK_WORDS + T_RES23];
+    const uint32_t r = task[(size_t)e * MOCCA_TASK_WORDS + MOCCA_TW_LAST_ROWS];
     order[atomicAdd(&start[63 - (r > 63u ? 63u : r)], 1)] = e;
   }
 }
@@ -300,8 +300,8 @@ int mocca_create(const void* model_blob, size_t nbytes, int task_id, int n_envs,
     const float one = 1.0f;
     uint32_t one_bits; std::memcpy(&one_bits, &one, 4);
     for (int i = 0; i < n_envs; ++i) {
-      tmp[(size_t)i * MOCCA_TASK_WORDS + T_EPISODE] = (uint32_t)-1;
-      tmp[(size_t)i * MOCCA_TASK_WORDS + T_GAIN] = one_bits;
+      tmp[(size_t)i * MOCCA_TASK_WORDS + MOCCA_TW_EPISODE] = (uint32_t)-1;
+      tmp[(size_t)i * MOCCA_TASK_WORDS + MOCCA_TW_APPLIED_GAIN] = one_bits;
     }
     e = hipMemcpy(h->d_task, tmp, task_b, hipMemcpyHostToDevice);
     delete[] tmp;
@@ -365,11 +365,11 @@ static StepArgs make_args(mocca_handle h) {
   a.hf = h->d_hf; a.hf_rows = h->hf_rows; a.hf_cols = h->hf_cols; a.hf_scale = h->hf_scale;
   return a;
 }
-// A scalar MOCCA_PARAM_APPLIED_GAIN is written into the task records (word T_GAIN, what apply_action reads) by the NEXT call that takes
+// A scalar MOCCA_PARAM_APPLIED_GAIN is written into the task records (word MOCCA_TW_APPLIED_GAIN, what apply_action reads) by the NEXT call that takes
 // a stream, on that stream: ordered against the caller's in-flight steps, which also write the word (store_task).
 static int flush_pending(mocca_handle h, hipStream_t s) {
   if (!h->gain_pending) return MOCCA_OK;
-  hipLaunchKernelGGL(set_task_word_kernel, dim3((h->n_envs + 255) / 256), dim3(256), 0, s, h->d_task, (int)T_GAIN, (const float*)nullptr, h->gain, 1, h->n_envs);
+  hipLaunchKernelGGL(set_task_word_kernel, dim3((h->n_envs + 255) / 256), dim3(256), 0, s, h->d_task, (int)MOCCA_TW_APPLIED_GAIN, (const float*)nullptr, h->gain, 1, h->n_envs);
   HIP_TRY(h, hipGetLastError());
   h->gain_pending = false;
   return MOCCA_OK;
@@ -623,7 +623,7 @@ int mocca_get_task(mocca_handle h, uint32_t* task_dev, void* stream) {
 int mocca_set_task(mocca_handle h, const uint32_t* task_dev, void* stream) {
   if (!h || !task_dev) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
-  // a restored snapshot wins over an earlier scalar applied_gain: every env's T_GAIN is the snapshot's; the handle's own copy (what a
+  // a restored snapshot wins over an earlier scalar applied_gain: every env's MOCCA_TW_APPLIED_GAIN is the snapshot's; the handle's own copy (what a
   // Custom env's reset writes, robot.applied_gain persists across resets) keeps the value of the last mocca_set_param
   h->gain_pending = false;
   HIP_TRY(h, hipMemcpyAsync(h->d_task, task_dev, (size_t)h->n_envs * MOCCA_TASK_WORDS * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -696,7 +696,7 @@ int mocca_set_param_v(mocca_handle h, int param_id, const float* values_dev, int
     // the per-env values supersede a scalar mocca_set_param(APPLIED_GAIN) that was not flushed yet: left pending, the next call with a
     // stream would overwrite every env's word with the stale scalar (call order must win, as it did when the scalar write was synchronous)
     h->gain_pending = false;
-    hipLaunchKernelGGL(set_task_word_kernel, dim3((h->n_envs + 255) / 256), dim3(256), 0, s, h->d_task, (int)T_GAIN, (const float*)h->d_pvec[slot], 0.0f, 0, h->n_envs);
+    hipLaunchKernelGGL(set_task_word_kernel, dim3((h->n_envs + 255) / 256), dim3(256), 0, s, h->d_task, (int)MOCCA_TW_APPLIED_GAIN, (const float*)h->d_pvec[slot], 0.0f, 0, h->n_envs);
     HIP_TRY(h, hipGetLastError());
   }
   h->pvec_on[slot] = true;

@@ -190,12 +190,6 @@ static_assert(L_J >= L_RT, "J rows may be written while S, U, 1/D, the factor of
 // contact record fields
 enum : int { C_BA = 0, C_BB = 1, C_SLOT = 2, C_P = 3, C_N = 6, C_DEPTH = 9, C_MU = 10, C_ERP = 11, C_CFM = 12, C_MA = 13, C_MB = 14 };
 
-// task record words (include/mocca_model.h)
-enum : int { T_WTX = 0, T_WTY, T_WTZ, T_LINPOT, T_ANGPOT, T_CLOSE, T_STOPF, T_DONE, T_T, T_EPISODE, T_DRAW, T_MIRROR,
-             T_FC0, T_FC1, T_DIST, T_ANGLE, T_NSI, T_TRC, T_STOP, T_SETSTOP, T_CUR, T_GAIN, T_PREVX, T_RES23,
-             T_JVEL = 24, T_FC2 = 24, T_FC3 = 25 /* quadrupeds; Cassie's jvel otherwise */, T_RW = 30 /* Stepper: 8 reward weights */,
-             T_INITZ = 38, T_ISTEP = 39 };
-
 struct StepArgs {
   const MoccaModel* model;
   float* dyn;        // [N][DYN_STRIDE]
@@ -2341,6 +2335,7 @@ DI void quat_to_rp_heading(const float* q, float* rp, float* cy, float* sy) {  /
   }
 }
 
+template <class T> constexpr int ROBOT_OBS = 6 + 2 * T::NJ + T::NFEET;   // robot_obs writes obs[0 .. ROBOT_OBS); the task's tail follows
 struct RobotObs { float rpy[3]; /* [2] unused: see cy, sy */ float cy, sy; int jal; float spd; float height; bool finite; };
 
 // WalkerBase.calc_state (robots.py:42-95): writes obs[0 .. 6+2NJ+NFEET) ; needs kinematics done (L_FEET).
@@ -2391,33 +2386,33 @@ struct TaskRegs {  // uniform across the wave
   int close, done, t, episode, draw, mirrored, nsi, trc, stop, setstop, cur, istep;
   int cover;   // Stepper: cover mask of the last step's contacts (word 26, as a float; ContactFlags / cover_targets) -- what reset() reads stale
 };
-// (`cassie`: words 38 / 39 -- initial_z, istep -- are Cassie's alone and sit in the third 64-byte line of the 160-byte record: the other tasks
-// neither read nor write them, which keeps that line out of a walker step's HBM traffic where it is not shared with the next env's record)
-DI void load_task(const uint32_t* tk, TaskRegs& t, bool quadruped = false, bool cassie = false) {
-  auto f = [&](int i) { return __uint_as_float(tk[i]); };
-  t.wt[0] = f(T_WTX); t.wt[1] = f(T_WTY); t.wt[2] = f(T_WTZ); t.linpot = f(T_LINPOT); t.angpot = f(T_ANGPOT);
-  t.close = (int)tk[T_CLOSE]; t.stopf = f(T_STOPF); t.done = (int)tk[T_DONE]; t.t = (int)tk[T_T];
-  t.episode = (int)tk[T_EPISODE]; t.draw = (int)tk[T_DRAW]; t.mirrored = (int)tk[T_MIRROR];
-  t.fc0 = f(T_FC0); t.fc1 = f(T_FC1); t.dist = f(T_DIST); t.angle = f(T_ANGLE);
-  t.fc2 = quadruped ? f(T_FC2) : 0.0f; t.fc3 = quadruped ? f(T_FC3) : 0.0f;
-  t.nsi = (int)tk[T_NSI]; t.trc = (int)tk[T_TRC]; t.stop = (int)tk[T_STOP]; t.setstop = (int)tk[T_SETSTOP];
-  t.cur = (int)tk[T_CUR]; t.gain = f(T_GAIN); t.prevx = f(T_PREVX);
-  t.initz = cassie ? f(T_INITZ) : 0.0f; t.istep = cassie ? (int)tk[T_ISTEP] : 0;
-  t.cover = 0;
+// The words a kernel moves, in record order (fw / iw: a float / int32 word and its register): the quadrupeds' feet_contact[2..3] follow from
+// the topology, Cassie's initial_z and istep from the task.  Words 38 / 39 sit in the third 64-byte line of the 160-byte record: the other
+// tasks neither read nor write them, which keeps that line out of a walker step's HBM traffic where it is not shared with the next env's
+// record.  The Stepper's cover mask (word 26, an int held as a float) moves with COVER: the reset kernel reads and writes it, the step
+// kernel only writes it (this step's mask replaces it) and the observe kernel leaves it alone.
+template <class T, int TASK, class R, class F, class I>
+DI void task_words(R& t, F fw, I iw) {
+  fw(MOCCA_TW_WALK_TARGET_X, t.wt[0]); fw(MOCCA_TW_WALK_TARGET_Y, t.wt[1]); fw(MOCCA_TW_WALK_TARGET_Z, t.wt[2]);
+  fw(MOCCA_TW_LINEAR_POTENTIAL, t.linpot); fw(MOCCA_TW_ANGULAR_POTENTIAL, t.angpot); iw(MOCCA_TW_CLOSE_COUNT, t.close); fw(MOCCA_TW_STOP_FRAMES, t.stopf);
+  iw(MOCCA_TW_DONE, t.done); iw(MOCCA_TW_T, t.t); iw(MOCCA_TW_EPISODE, t.episode); iw(MOCCA_TW_DRAW, t.draw); iw(MOCCA_TW_MIRRORED, t.mirrored);
+  fw(MOCCA_TW_FEET_CONTACT_0, t.fc0); fw(MOCCA_TW_FEET_CONTACT_1, t.fc1); fw(MOCCA_TW_DIST, t.dist); fw(MOCCA_TW_ANGLE, t.angle);
+  if constexpr (T::NFEET > 2) { fw(MOCCA_TW_FEET_CONTACT_2, t.fc2); fw(MOCCA_TW_FEET_CONTACT_3, t.fc3); }
+  iw(MOCCA_TW_NEXT_STEP_INDEX, t.nsi); iw(MOCCA_TW_TARGET_REACHED_COUNT, t.trc); iw(MOCCA_TW_STOP_ON_NEXT_STEP, t.stop);
+  iw(MOCCA_TW_SET_STOP_ON_NEXT_STEP, t.setstop); iw(MOCCA_TW_CURRICULUM, t.cur); fw(MOCCA_TW_APPLIED_GAIN, t.gain); fw(MOCCA_TW_PREV_BODY_X, t.prevx);
+  if constexpr (TASK == MOCCA_TASK_CASSIE) { fw(MOCCA_TW_INITIAL_Z, t.initz); iw(MOCCA_TW_ISTEP, t.istep); }
 }
-enum : int { T_COVER = 26 };
-DI void load_task_cover(const uint32_t* tk, TaskRegs& t) { t.cover = (int)__uint_as_float(tk[T_COVER]); }
-DI void store_task_cover(uint32_t* tk, const TaskRegs& t) { tk[T_COVER] = __float_as_uint((float)t.cover); }
-DI void store_task(uint32_t* tk, const TaskRegs& t, bool quadruped = false, bool cassie = false) {
-  auto u = [](float x) { return __float_as_uint(x); };
-  tk[T_WTX] = u(t.wt[0]); tk[T_WTY] = u(t.wt[1]); tk[T_WTZ] = u(t.wt[2]); tk[T_LINPOT] = u(t.linpot); tk[T_ANGPOT] = u(t.angpot);
-  tk[T_CLOSE] = (uint32_t)t.close; tk[T_STOPF] = u(t.stopf); tk[T_DONE] = (uint32_t)t.done; tk[T_T] = (uint32_t)t.t;
-  tk[T_EPISODE] = (uint32_t)t.episode; tk[T_DRAW] = (uint32_t)t.draw; tk[T_MIRROR] = (uint32_t)t.mirrored;
-  tk[T_FC0] = u(t.fc0); tk[T_FC1] = u(t.fc1); tk[T_DIST] = u(t.dist); tk[T_ANGLE] = u(t.angle);
-  if (quadruped) { tk[T_FC2] = u(t.fc2); tk[T_FC3] = u(t.fc3); }
-  tk[T_NSI] = (uint32_t)t.nsi; tk[T_TRC] = (uint32_t)t.trc; tk[T_STOP] = (uint32_t)t.stop; tk[T_SETSTOP] = (uint32_t)t.setstop;
-  tk[T_CUR] = (uint32_t)t.cur; tk[T_GAIN] = u(t.gain); tk[T_PREVX] = u(t.prevx);
-  if (cassie) { tk[T_INITZ] = u(t.initz); tk[T_ISTEP] = (uint32_t)t.istep; }
+template <class T, int TASK, bool COVER = false>
+DI TaskRegs load_task(const uint32_t* tk) {
+  TaskRegs t{};
+  task_words<T, TASK>(t, [&](int w, float& x) { x = __uint_as_float(tk[w]); }, [&](int w, int& x) { x = (int)tk[w]; });
+  if constexpr (COVER && TASK == MOCCA_TASK_WALKER3D_STEPPER) t.cover = (int)__uint_as_float(tk[MOCCA_TW_COVER]);
+  return t;
+}
+template <class T, int TASK, bool COVER = false>
+DI void store_task(uint32_t* tk, const TaskRegs& t) {
+  task_words<T, TASK>(t, [&](int w, float x) { tk[w] = __float_as_uint(x); }, [&](int w, int x) { tk[w] = (uint32_t)x; });
+  if constexpr (COVER && TASK == MOCCA_TASK_WALKER3D_STEPPER) tk[MOCCA_TW_COVER] = __float_as_uint((float)t.cover);
 }
 
 // calc_potential, env_locomotion.py:143-158
@@ -2535,6 +2530,25 @@ DI int live_curriculum(const StepArgs& a, int env) {  // env = index in this han
 }
 DI bool live_eval_mode(const StepArgs& a, int env) { return a.eval_mode_v ? a.eval_mode_v[env] != 0.0f : a.eval_mode != 0; }
 
+// The base pose every reset ends with, once the joints are in LDS: the model's initial base pose and velocity (robot_init_velocity,
+// env_locomotion.py:92,493), no warm-start impulses, then the kinematics.  Returns the base height it set (Cassie's initial_z).
+template <class T>
+DI float reset_base_pose(ModelP M, float* L, int lane) {
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { L[L_BASE + i] = M->init_pos[i]; L[L_BASE + 7 + i] = M->init_vel[i]; L[L_BASE + 10 + i] = 0; }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) L[L_BASE + 3 + i] = M->init_quat[i];
+  }
+  if (lane < MOCCA_MAX_SLOTS) L[L_WARM + lane] = 0.0f;
+  wsync();
+  const float z0 = L[L_BASE + 2];
+  stage_joints<T>(M, L, lane);
+  walk_kinematics<T, false>(M, L, lane, T::path_packed(lane < T::NB ? lane : 0));
+  wsync();
+  return z0;
+}
+
 template <class T, int TASK, bool INJECT = false>
 DI void reset_env(const StepArgs& a, ModelP M, float* L, float* ter, int env, int lane, TaskRegs& t,
                   float* obs) {
@@ -2597,18 +2611,7 @@ DI void reset_env(const StepArgs& a, ModelP M, float* L, float* ter, int env, in
     L[L_QD + b] = 0.0f;
   }
   if (a.random_pose) t.draw += T::NJ;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { L[L_BASE + i] = M->init_pos[i]; L[L_BASE + 7 + i] = M->init_vel[i]; L[L_BASE + 10 + i] = 0; }  // robot_init_velocity, :92,493
-#pragma unroll
-    for (int i = 0; i < 4; ++i) L[L_BASE + 3 + i] = M->init_quat[i];
-  }
-  if (lane < MOCCA_MAX_SLOTS) L[L_WARM + lane] = 0.0f;
-  wsync();
-  stage_joints<T>(M, L, lane);
-  walk_kinematics<T, false>(M, L, lane, T::path_packed(lane < T::NB ? lane : 0));
-  wsync();
-  const int nbo = 6 + 2 * T::NJ + T::NFEET;
+  reset_base_pose<T>(M, L, lane);
   RobotObs ro = robot_obs<T>(M, L, lane, 0.0f, 0.0f, obs);
   float dist, cd, sd;
   if (TASK == MOCCA_TASK_WALKER3D_PLANNER) {
@@ -2620,17 +2623,17 @@ DI void reset_env(const StepArgs& a, ModelP M, float* L, float* ter, int env, in
     t.wt[1] = -R + 2.0f * R * uy;
     t.wt[2] = hf_height_at(a.hf, a.hf_rows, a.hf_cols, a.hf_scale, t.wt[0], t.wt[1]);
     calc_potential(M, L, t, ro, &dist, &cd, &sd);
-    if (lane == 0) softsign_tail(sd, cd, obs + nbo);
+    if (lane == 0) softsign_tail(sd, cd, obs + ROBOT_OBS<T>);
   } else if (TASK == MOCCA_TASK_WALKER3D_CUSTOM) {
     calc_potential(M, L, t, ro, &dist, &cd, &sd);
     if (lane == 0) {
-      softsign_tail(sd, cd, obs + nbo);
-      if (M->task_flags & MOCCA_TASKF_RESET_TAIL_ZERO) { obs[nbo] = 0.0f; obs[nbo + 1] = 0.0f; }  // Walker2DCustomEnv.reset, :299-300
+      softsign_tail(sd, cd, obs + ROBOT_OBS<T>);
+      if (M->task_flags & MOCCA_TASKF_RESET_TAIL_ZERO) { obs[ROBOT_OBS<T>] = 0.0f; obs[ROBOT_OBS<T> + 1] = 0.0f; }  // Walker2DCustomEnv.reset, :299-300
     }
   } else {
     generate_terrain<INJECT>(a, M, env, t, L, ter, lane);
     t.nsi = M->lookbehind;                                                             // :499
-    delta_to_k_targets(M, L, ter, t, ro, lane, obs + nbo);
+    delta_to_k_targets(M, L, ter, t, ro, lane, obs + ROBOT_OBS<T>);
     calc_potential(M, L, t, ro, &dist, &cd, &sd);
   }
   t.prevx = L[L_BASE];
@@ -2755,6 +2758,11 @@ DI float cassie_mocap_reward(const StepArgs& a, ModelP M, const float* L, int la
   return M->mocap_w[0] * expf(-4.0f * vel_error) + M->mocap_w[1] * expf(-4.0f * joint_penalty) + M->mocap_w[2] * expf(-0.4f * jvel_penalty) +
          M->mocap_w[3] * expf(-4.0f * orientation) + M->mocap_w[4] * expf(-4.0f * angular) + M->mocap_w[5] * expf(-4.0f * com);
 }
+// the observation of the Cassie env: CassieEnv.get_obs, or the mocap variants' at this lane's joint speed `jvel` and the motion's `phase`
+DI void cassie_observe(ModelP M, const float* L, int lane, const CassieState& cs, float initial_z, float jvel, float phase, float* obs) {
+  if (M->cassie_mode == MOCCA_CASSIE_PLAIN) cassie_obs(M, L, lane, cs, initial_z, obs);
+  else cassie_mocap_obs(M, L, lane, cs, jvel, phase, obs);
+}
 DI float cassie_potential(ModelP M, const float* L) {  // calc_potential :348-354
   const float dx = M->cassie_target[0] - L[L_BASE], dy = M->cassie_target[1] - L[L_BASE + 1];
   return -sqrtf(dx * dx + dy * dy) / M->control_dt;
@@ -2790,22 +2798,19 @@ DI void cassie_reset_env(const StepArgs& a, ModelP M, float* L, int env, int lan
     }
     if (lane < 4) { L[L_Q + M->rod_body[lane]] = fr[28 + lane]; L[L_QD + M->rod_body[lane]] = 0.0f; }
   }
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { L[L_BASE + i] = M->init_pos[i]; L[L_BASE + 7 + i] = M->init_vel[i]; L[L_BASE + 10 + i] = 0; }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) L[L_BASE + 3 + i] = M->init_quat[i];
-  }
-  if (lane < MOCCA_MAX_SLOTS) L[L_WARM + lane] = 0.0f;
-  wsync();
-  t.initz = L[L_BASE + 2];
-  stage_joints<T>(M, L, lane);
-  walk_kinematics<T, false>(M, L, lane, T::path_packed(lane < T::NB ? lane : 0));
-  wsync();
+  t.initz = reset_base_pose<T>(M, L, lane);
   const CassieState cs = cassie_state(M, L, lane, t.initz);
-  if (mode == MOCCA_CASSIE_PLAIN) cassie_obs(M, L, lane, cs, t.initz, obs);
-  else cassie_mocap_obs(M, L, lane, cs, lane < MOCCA_MAX_CTRL ? L[L_JVEL + lane] : 0.0f, phase, obs);
+  cassie_observe(M, L, lane, cs, t.initz, lane < MOCCA_MAX_CTRL ? L[L_JVEL + lane] : 0.0f, phase, obs);
   t.linpot = cassie_potential(M, L);
+}
+
+// env.reset() of the env's task (auto-reset, mocca_reset_kernel); Cassie's new filtered joint speeds go straight to the record `tk`
+template <class T, int TASK, bool INJECT>
+DI void reset_task(const StepArgs& a, ModelP M, float* L, float* ter, uint32_t* tk, int env, int lane, TaskRegs& t, float* obs) {
+  if constexpr (TASK == MOCCA_TASK_CASSIE) {
+    cassie_reset_env<T, INJECT>(a, M, L, env, lane, t, obs);
+    if (lane < MOCCA_MAX_CTRL) tk[MOCCA_TW_JVEL + lane] = __float_as_uint(L[L_JVEL + lane]);
+  } else reset_env<T, TASK, INJECT>(a, M, L, ter, env, lane, t, obs);
 }
 
 // `warm` (wave-uniform): the per-slot normal impulses travel with the record.  A blob that does not warm-start its contact rows never reads

@@ -191,7 +191,8 @@ class Walker3DCustomEnv(EnvBase):
         obs, rew, done, _ = self._step_device(action)
         self._pull_robot()
         tk = task_to_float64(self._img["task"])[0]
-        self.walk_target, self.close_count = tk[0:3].copy(), int(tk[5])
+        wt = slice(M.TW.WALK_TARGET_X, M.TW.WALK_TARGET_Z + 1)
+        self.walk_target, self.close_count = tk[wt].copy(), int(tk[M.TW.CLOSE_COUNT])
         if self.close_count >= self.stop_frames:  # env_locomotion.py:214-222, host RandomState like the reference
             self.close_count = 0
             self.dist, self.angle, self.stop_frames = H.randomize_target(self.np_random, self.eval_mode)
@@ -200,8 +201,8 @@ class Walker3DCustomEnv(EnvBase):
             yaw = H.yaw_from_quat(*st[3:7])
             dx, dy = self.walk_target[0] - st[0], self.walk_target[1] - st[1]
             ang, dist = np.arctan2(dy, dx) - yaw, np.hypot(dx, dy)
-            tk[0:3], tk[5], tk[6], tk[14], tk[15] = self.walk_target, 0, self.stop_frames, self.dist, self.angle
-            tk[3], tk[4] = -dist / (1 / 60), np.cos(ang)  # calc_potential :143-158 (scene.dt = 1/60)
+            tk[wt], tk[M.TW.CLOSE_COUNT], tk[M.TW.STOP_FRAMES], tk[M.TW.DIST], tk[M.TW.ANGLE] = self.walk_target, 0, self.stop_frames, self.dist, self.angle
+            tk[M.TW.LINEAR_POTENTIAL], tk[M.TW.ANGULAR_POTENTIAL] = -dist / (1 / 60), np.cos(ang)  # calc_potential :143-158 (scene.dt = 1/60)
             self._vec.set_task(task_from_float64(tk[None]))
             s_, c_ = dist * np.sin(ang), dist * np.cos(ang)
             obs[-2], obs[-1] = s_ / (1 + abs(s_)), c_ / (1 + abs(c_))
@@ -317,13 +318,11 @@ class Walker3DStepperEnv(EnvBase):
         if (self.model.task_flags & M.TASKF_STALE_RESET_CONTACTS) and getattr(self, "_img", None) is not None and self._episode > 0:
             from .vec_env import task_to_float64
             old = task_to_float64(self._img["task"])[0]
-            fc = [old[12], old[13], old[24], old[25]][:nf]
-            task[12:14] = fc[:2]
-            if nf > 2:
-                task[24:26] = fc[2:4]
-            cover, old_nsi = int(old[26]), int(old[16])
+            for w in (M.TW.FEET_CONTACT_0, M.TW.FEET_CONTACT_1, M.TW.FEET_CONTACT_2, M.TW.FEET_CONTACT_3)[:nf]:
+                task[w] = old[w]
+            cover, old_nsi = int(old[M.TW.COVER]), int(old[M.TW.NEXT_STEP_INDEX])
             if any((cover >> (4 * f + old_nsi % int(self.model.n_planks))) & 1 for f in range(nf)):
-                task[17] = 1
+                task[M.TW.TARGET_REACHED_COUNT] = 1
         self._vec.set_param(2, cur)
         self._push(H.initial_state(self.model, q), task, terrain)
         obs = self._observe()
@@ -338,7 +337,7 @@ class Walker3DStepperEnv(EnvBase):
             # the LIVE record, not the host image of the last step: set_robot_params / VecEnv.seed / set_task may have changed the device
             # record since (a stale image written back would silently revert them -- ADVICE r3); one 160-byte download, this mode only
             tk = task_to_float64(self._vec.get_task())
-            tk[0, 30:38] = self.np_random.uniform(0.8, 1.2, 8)
+            tk[0, M.TW.REWARD_WEIGHTS:M.TW.REWARD_WEIGHTS + 8] = self.np_random.uniform(0.8, 1.2, 8)
             self._vec.set_task(task_from_float64(tk))
         cur = min(int(self.curriculum), self.max_curriculum)
         if cur != getattr(self, "_pushed_curriculum", None):   # terminal height follows self.curriculum at once (:628)

@@ -128,13 +128,9 @@ def initial_state(mdl: M.MoccaModel, q: np.ndarray) -> np.ndarray:
 def task_record(**kw) -> np.ndarray:
     """float64 task record in the layout of include/mocca_model.h (see vec_env.task_from_float64)."""
     t = np.zeros(M.TASK_WORDS, dtype=np.float64)
-    names = {"walk_target": 0, "linear_potential": 3, "angular_potential": 4, "close_count": 5, "stop_frames": 6,
-             "done": 7, "t": 8, "episode": 9, "draw": 10, "mirrored": 11, "feet_contact": 12, "dist": 14, "angle": 15,
-             "next_step_index": 16, "target_reached_count": 17, "stop_on_next_step": 18, "set_stop_on_next_step": 19,
-             "curriculum": 20, "applied_gain": 21, "prev_body_x": 22}
-    t[21] = 1.0
-    for k, v in kw.items():
-        i = names[k]
+    t[M.TW.APPLIED_GAIN] = 1.0
+    for k, v in kw.items():   # walk_target=(x, y, z) and feet_contact=(...) fill the words from the first one on
+        i = getattr(M.TW, {"walk_target": "WALK_TARGET_X", "feet_contact": "FEET_CONTACT_0"}.get(k, k.upper()))
         v = np.atleast_1d(np.asarray(v, dtype=np.float64))
         t[i:i + len(v)] = v
     return t

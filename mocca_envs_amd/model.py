@@ -19,6 +19,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -34,6 +35,20 @@ VERSION = 13
 GEOM_SPHERE, GEOM_CAPSULE = 0, 1
 TASK_WALKER3D_CUSTOM, TASK_WALKER3D_STEPPER, TASK_CASSIE, TASK_WALKER3D_PLANNER = 0, 1, 2, 3
 TASK_WORDS = 40
+# the per-env task record (include/mocca_model.h enum MoccaTaskWord): name (MOCCA_TW_<name>), first word, words, class (f float, i int32);
+# entries at the same word are aliases, the env's task decides which applies
+TASK_RECORD = (
+    ("WALK_TARGET_X", 0, 1, "f"), ("WALK_TARGET_Y", 1, 1, "f"), ("WALK_TARGET_Z", 2, 1, "f"),
+    ("LINEAR_POTENTIAL", 3, 1, "f"), ("ANGULAR_POTENTIAL", 4, 1, "f"), ("CLOSE_COUNT", 5, 1, "i"), ("STOP_FRAMES", 6, 1, "f"),
+    ("DONE", 7, 1, "i"), ("T", 8, 1, "i"), ("EPISODE", 9, 1, "i"), ("DRAW", 10, 1, "i"), ("MIRRORED", 11, 1, "i"),
+    ("FEET_CONTACT_0", 12, 1, "f"), ("FEET_CONTACT_1", 13, 1, "f"), ("DIST", 14, 1, "f"), ("ANGLE", 15, 1, "f"),
+    ("NEXT_STEP_INDEX", 16, 1, "i"), ("TARGET_REACHED_COUNT", 17, 1, "i"), ("STOP_ON_NEXT_STEP", 18, 1, "i"),
+    ("SET_STOP_ON_NEXT_STEP", 19, 1, "i"), ("CURRICULUM", 20, 1, "i"), ("APPLIED_GAIN", 21, 1, "f"), ("PREV_BODY_X", 22, 1, "f"),
+    ("LAST_ROWS", 23, 1, "i"), ("FEET_CONTACT_2", 24, 1, "f"), ("JVEL", 24, 14, "f"), ("FEET_CONTACT_3", 25, 1, "f"),
+    ("COVER", 26, 1, "f"), ("REWARD_WEIGHTS", 30, 8, "f"), ("INITIAL_Z", 38, 1, "f"), ("ISTEP", 39, 1, "i"),
+)
+TW = SimpleNamespace(**{name: word for name, word, _, _ in TASK_RECORD})   # M.TW.EPISODE == 9
+TASK_FLOAT_WORDS = tuple(sorted({w for _, word, n, c in TASK_RECORD if c == "f" for w in range(word, word + n)}))
 TASKF_NEVER_DONE, TASKF_RESET_TAIL_ZERO, TASKF_BODY_CONTACT, TASKF_QUADRUPED_STEPPER = 1, 2, 4, 8  # MoccaModel.task_flags (include/mocca_model.h)
 TASKF_STALE_RESET_CONTACTS = 16   # Stepper reset() reads the contact manifolds of the episode before (env_locomotion.py:484-499): the reference's behaviour
 PLANK_BOX, PLANK_CYLINDER = 0, 1

@@ -289,8 +289,8 @@ class VecEnv:
         _lib.check(self.lib.mocca_set_seed(self.h, self.seed_value), self.h)
         if rewind:
             tk = self.get_task()
-            tk[:, 9] = -1      # episode: the next reset is episode 0 (draws are keyed by (seed, global env id, episode, draw))
-            tk[:, 10] = 0      # draw counter
+            tk[:, M.TW.EPISODE] = -1   # the next reset is episode 0 (draws are keyed by (seed, global env id, episode, draw))
+            tk[:, M.TW.DRAW] = 0
             self.set_task(tk)
         return [seed]
 
@@ -527,16 +527,13 @@ class VecEnv:
         return out
 
 
-# task-record helpers: the device record is 24 x 32-bit words, floats and ints mixed (mocca_model.h)
-TASK_FLOAT_WORDS = (0, 1, 2, 3, 4, 6, 12, 13, 14, 15, 21, 22) + tuple(range(24, 39))
-
-
+# task-record helpers: the device record is M.TASK_WORDS 32-bit words, floats and ints mixed (M.TASK_RECORD)
 def task_to_float64(t: torch.Tensor) -> np.ndarray:
     """int32 view of the device task record -> float64 array in the oracle's get_task() layout."""
     a = (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(np.int32)
     out = a.astype(np.float64)
     fl = a.view(np.float32)
-    for w in TASK_FLOAT_WORDS:
+    for w in M.TASK_FLOAT_WORDS:
         out[:, w] = fl[:, w]
     return out
 
@@ -545,6 +542,6 @@ def task_from_float64(a: np.ndarray) -> torch.Tensor:
     a = np.asarray(a, np.float64)
     out = a.astype(np.int32)
     fl = out.view(np.float32)
-    for w in TASK_FLOAT_WORDS:
+    for w in M.TASK_FLOAT_WORDS:
         fl[:, w] = a[:, w].astype(np.float32)
     return torch.from_numpy(out)

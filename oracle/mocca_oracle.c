@@ -1931,16 +1931,23 @@ API void orc_get_task(void *h, double *t) {
     const Task *k = &o->task[e];
     double *p = t + (size_t)e * MOCCA_TASK_WORDS;
     memset(p, 0, MOCCA_TASK_WORDS * sizeof(double));
-    p[0] = k->walk_target[0]; p[1] = k->walk_target[1]; p[2] = k->walk_target[2];
-    p[3] = k->linear_potential; p[4] = k->angular_potential; p[5] = k->close_count; p[6] = k->stop_frames;
-    p[7] = k->done; p[8] = k->t; p[9] = k->episode; p[10] = k->draw; p[11] = k->mirrored;
-    p[12] = k->feet_contact[0]; p[13] = k->feet_contact[1]; p[14] = k->dist; p[15] = k->angle;
-    p[16] = k->next_step_index; p[17] = k->target_reached_count; p[18] = k->stop_on_next_step;
-    p[19] = k->set_stop_on_next_step; p[20] = k->curriculum; p[21] = k->applied_gain; p[22] = k->prev_body_x;
-    for (int j = 0; j < 14; ++j) p[24 + j] = k->jvel[j];
-    if (o->m.n_feet > 2) { p[24] = k->feet_contact[2]; p[25] = k->feet_contact[3]; } /* quadrupeds: words shared with Cassie's jvel */
-    p[38] = k->initial_z; p[39] = k->istep;
-    if (o->task_id == MOCCA_TASK_WALKER3D_STEPPER) { for (int j = 0; j < 8; ++j) p[30 + j] = k->rw[j]; p[26] = k->cover; }
+    for (int j = 0; j < 3; ++j) p[MOCCA_TW_WALK_TARGET_X + j] = k->walk_target[j];
+    p[MOCCA_TW_LINEAR_POTENTIAL] = k->linear_potential; p[MOCCA_TW_ANGULAR_POTENTIAL] = k->angular_potential;
+    p[MOCCA_TW_CLOSE_COUNT] = k->close_count; p[MOCCA_TW_STOP_FRAMES] = k->stop_frames;
+    p[MOCCA_TW_DONE] = k->done; p[MOCCA_TW_T] = k->t; p[MOCCA_TW_EPISODE] = k->episode; p[MOCCA_TW_DRAW] = k->draw;
+    p[MOCCA_TW_MIRRORED] = k->mirrored;
+    p[MOCCA_TW_FEET_CONTACT_0] = k->feet_contact[0]; p[MOCCA_TW_FEET_CONTACT_1] = k->feet_contact[1];
+    p[MOCCA_TW_DIST] = k->dist; p[MOCCA_TW_ANGLE] = k->angle;
+    p[MOCCA_TW_NEXT_STEP_INDEX] = k->next_step_index; p[MOCCA_TW_TARGET_REACHED_COUNT] = k->target_reached_count;
+    p[MOCCA_TW_STOP_ON_NEXT_STEP] = k->stop_on_next_step; p[MOCCA_TW_SET_STOP_ON_NEXT_STEP] = k->set_stop_on_next_step;
+    p[MOCCA_TW_CURRICULUM] = k->curriculum; p[MOCCA_TW_APPLIED_GAIN] = k->applied_gain; p[MOCCA_TW_PREV_BODY_X] = k->prev_body_x;
+    for (int j = 0; j < 14; ++j) p[MOCCA_TW_JVEL + j] = k->jvel[j];
+    if (o->m.n_feet > 2) { p[MOCCA_TW_FEET_CONTACT_2] = k->feet_contact[2]; p[MOCCA_TW_FEET_CONTACT_3] = k->feet_contact[3]; } /* quadrupeds: words shared with Cassie's jvel */
+    p[MOCCA_TW_INITIAL_Z] = k->initial_z; p[MOCCA_TW_ISTEP] = k->istep;
+    if (o->task_id == MOCCA_TASK_WALKER3D_STEPPER) {
+      for (int j = 0; j < 8; ++j) p[MOCCA_TW_REWARD_WEIGHTS + j] = k->rw[j];
+      p[MOCCA_TW_COVER] = k->cover;
+    }
   }
 }
 API void orc_set_task(void *h, const double *t) {
@@ -1948,18 +1955,24 @@ API void orc_set_task(void *h, const double *t) {
   for (int e = 0; e < o->n_envs; ++e) {
     Task *k = &o->task[e];
     const double *p = t + (size_t)e * MOCCA_TASK_WORDS;
-    k->walk_target[0] = (real)p[0]; k->walk_target[1] = (real)p[1]; k->walk_target[2] = (real)p[2];
-    k->linear_potential = (real)p[3]; k->angular_potential = (real)p[4]; k->close_count = (int)p[5];
-    k->stop_frames = (real)p[6]; k->done = (int)p[7]; k->t = (int)p[8]; k->episode = (int)p[9];
-    k->draw = (int)p[10]; k->mirrored = (int)p[11]; k->feet_contact[0] = (real)p[12]; k->feet_contact[1] = (real)p[13];
-    k->dist = (real)p[14]; k->angle = (real)p[15]; k->next_step_index = (int)p[16];
-    k->target_reached_count = (int)p[17]; k->stop_on_next_step = (int)p[18]; k->set_stop_on_next_step = (int)p[19];
-    k->curriculum = (int)p[20]; k->applied_gain = (real)p[21]; k->prev_body_x = (real)p[22];
-    for (int j = 0; j < 14; ++j) k->jvel[j] = (real)p[24 + j];
-    if (o->m.n_feet > 2) { k->feet_contact[2] = (real)p[24]; k->feet_contact[3] = (real)p[25]; }
-    k->initial_z = (real)p[38]; k->istep = (int)p[39];
-    if (o->task_id == MOCCA_TASK_WALKER3D_STEPPER) k->cover = (int)p[26];
-    if (o->task_id == MOCCA_TASK_WALKER3D_STEPPER) for (int j = 0; j < 8; ++j) k->rw[j] = (real)p[30 + j];
+    for (int j = 0; j < 3; ++j) k->walk_target[j] = (real)p[MOCCA_TW_WALK_TARGET_X + j];
+    k->linear_potential = (real)p[MOCCA_TW_LINEAR_POTENTIAL]; k->angular_potential = (real)p[MOCCA_TW_ANGULAR_POTENTIAL];
+    k->close_count = (int)p[MOCCA_TW_CLOSE_COUNT]; k->stop_frames = (real)p[MOCCA_TW_STOP_FRAMES];
+    k->done = (int)p[MOCCA_TW_DONE]; k->t = (int)p[MOCCA_TW_T]; k->episode = (int)p[MOCCA_TW_EPISODE]; k->draw = (int)p[MOCCA_TW_DRAW];
+    k->mirrored = (int)p[MOCCA_TW_MIRRORED];
+    k->feet_contact[0] = (real)p[MOCCA_TW_FEET_CONTACT_0]; k->feet_contact[1] = (real)p[MOCCA_TW_FEET_CONTACT_1];
+    k->dist = (real)p[MOCCA_TW_DIST]; k->angle = (real)p[MOCCA_TW_ANGLE];
+    k->next_step_index = (int)p[MOCCA_TW_NEXT_STEP_INDEX]; k->target_reached_count = (int)p[MOCCA_TW_TARGET_REACHED_COUNT];
+    k->stop_on_next_step = (int)p[MOCCA_TW_STOP_ON_NEXT_STEP]; k->set_stop_on_next_step = (int)p[MOCCA_TW_SET_STOP_ON_NEXT_STEP];
+    k->curriculum = (int)p[MOCCA_TW_CURRICULUM]; k->applied_gain = (real)p[MOCCA_TW_APPLIED_GAIN];
+    k->prev_body_x = (real)p[MOCCA_TW_PREV_BODY_X];
+    for (int j = 0; j < 14; ++j) k->jvel[j] = (real)p[MOCCA_TW_JVEL + j];
+    if (o->m.n_feet > 2) { k->feet_contact[2] = (real)p[MOCCA_TW_FEET_CONTACT_2]; k->feet_contact[3] = (real)p[MOCCA_TW_FEET_CONTACT_3]; }
+    k->initial_z = (real)p[MOCCA_TW_INITIAL_Z]; k->istep = (int)p[MOCCA_TW_ISTEP];
+    if (o->task_id == MOCCA_TASK_WALKER3D_STEPPER) {
+      k->cover = (int)p[MOCCA_TW_COVER];
+      for (int j = 0; j < 8; ++j) k->rw[j] = (real)p[MOCCA_TW_REWARD_WEIGHTS + j];
+    }
   }
 }
 API void orc_get_terrain(void *h, double *t) { /* [N][20][6] + plank_info appended per env [3] */

@@ -18,10 +18,7 @@ from mocca_envs_amd import model as M
 
 pytestmark = pytest.mark.gpu
 
-# task record words (mocca_envs_amd/csrc/mocca_device.h, include/mocca_model.h)
-T_WTX, T_WTY, T_WTZ, T_LINPOT, T_ANGPOT, T_CLOSE, T_STOPF, T_DONE, T_T, T_EPISODE, T_DRAW, T_MIRROR = range(12)
-T_FC0, T_FC1, T_DIST, T_ANGLE, T_NSI, T_TRC, T_STOP, T_SETSTOP, T_CUR, T_GAIN, T_PREVX, T_RES23 = range(12, 24)
-T_FC2, T_FC3, T_COVER, T_RW, T_INITZ, T_ISTEP = 24, 25, 26, 30, 38, 39
+TW = M.TW   # task record words (include/mocca_model.h MoccaTaskWord)
 
 # How each task word is compared after a step:
 #   "exact"   -- must be equal in every env whose done flags agree (counters, flags, draw-derived integers)
@@ -30,28 +27,30 @@ T_FC2, T_FC3, T_COVER, T_RW, T_INITZ, T_ISTEP = 24, 25, 26, 30, 38, 39
 #   "draw"    -- floats drawn at reset / re-target or copied: within the task atol of test_gpu_parity.test_reset_matches_oracle (1e-4)
 #   "cont"    -- continuous floats of the step: error units of test_gpu_parity (1e-3 + 1e-3 |x|), held to the f32-vs-f64 oracle yardstick
 #   "skip"    -- kernel-private, not part of the oracle's record (the reason is given)
-_COMMON = {T_WTX: "draw", T_WTY: "draw", T_WTZ: "draw", T_LINPOT: "cont", T_ANGPOT: "cont", T_CLOSE: "contact", T_STOPF: "draw",
-           T_DONE: "contact", T_T: "exact", T_EPISODE: "exact", T_DRAW: "exact", T_MIRROR: "exact", T_FC0: "contact", T_FC1: "contact",
-           T_DIST: "draw", T_ANGLE: "draw", T_NSI: "contact", T_TRC: "contact", T_STOP: "contact", T_SETSTOP: "contact", T_CUR: "exact",
-           T_GAIN: "draw", T_PREVX: "cont", T_RES23: "skip"}
-SKIP_REASONS = {T_RES23: "constraint rows of the last substep: the kernel's launch-priority hint for the next step (timing only)"}
+_COMMON = {TW.WALK_TARGET_X: "draw", TW.WALK_TARGET_Y: "draw", TW.WALK_TARGET_Z: "draw", TW.LINEAR_POTENTIAL: "cont",
+           TW.ANGULAR_POTENTIAL: "cont", TW.CLOSE_COUNT: "contact", TW.STOP_FRAMES: "draw", TW.DONE: "contact", TW.T: "exact",
+           TW.EPISODE: "exact", TW.DRAW: "exact", TW.MIRRORED: "exact", TW.FEET_CONTACT_0: "contact", TW.FEET_CONTACT_1: "contact",
+           TW.DIST: "draw", TW.ANGLE: "draw", TW.NEXT_STEP_INDEX: "contact", TW.TARGET_REACHED_COUNT: "contact",
+           TW.STOP_ON_NEXT_STEP: "contact", TW.SET_STOP_ON_NEXT_STEP: "contact", TW.CURRICULUM: "exact", TW.APPLIED_GAIN: "draw",
+           TW.PREV_BODY_X: "cont", TW.LAST_ROWS: "skip"}
+SKIP_REASONS = {TW.LAST_ROWS: "constraint rows of the last substep: the kernel's launch-priority hint for the next step (timing only)"}
 
 
 def task_word_classes(task: int, n_feet: int) -> dict:
     cls = dict(_COMMON)
     if task == M.TASK_CASSIE:
-        for w in range(24, 38):
+        for w in range(TW.JVEL, TW.JVEL + 14):
             cls[w] = "cont"                                           # jvel[14]: filtered joint speeds (env_cassie.py:451-468)
-        cls[T_INITZ], cls[T_ISTEP] = "cont", "exact"
+        cls[TW.INITIAL_Z], cls[TW.ISTEP] = "cont", "exact"
         return cls
-    for w in range(24, 40):
+    for w in range(TW.FEET_CONTACT_2, M.TASK_WORDS):
         cls[w] = "exact"                                              # unused words: must come back as they were forced
     if n_feet == 4:
-        cls[T_FC2], cls[T_FC3] = "contact", "contact"
+        cls[TW.FEET_CONTACT_2], cls[TW.FEET_CONTACT_3] = "contact", "contact"
     if task == M.TASK_WALKER3D_STEPPER:
-        cls[T_COVER] = "contact"                                      # cover mask of the last substep's contacts
+        cls[TW.COVER] = "contact"                                     # cover mask of the last substep's contacts
         for k in range(8):
-            cls[T_RW + k] = "draw"                                    # this episode's eight random-reward weights
+            cls[TW.REWARD_WEIGHTS + k] = "draw"                       # this episode's eight random-reward weights
     return cls
 
 
@@ -125,15 +124,15 @@ def _build_sample(t, env, o32, task, rng, field, n_planks, start):
     st, tk = o32.get_state(), o32.get_task()
     mx = int(env.model.max_episode_steps)
     if t == 0:
-        tk[0::3, T_T] = mx - 3                                    # a third of the envs reach the TimeLimit within 3 steps (test_gpu_edge_cases.py:245)
+        tk[0::3, TW.T] = mx - 3                                    # a third of the envs reach the TimeLimit within 3 steps (test_gpu_edge_cases.py:245)
         if field is not None:                                     # planner: robots scattered over the random field (test_gpu_edge_cases.py:340-344)
             for e in range(n):
                 xy = rng.uniform(-13, 13, 2)
                 st[e, 0:2], st[e, 2] = xy, o32.height_at(*xy) + 1.34
         if env.model.task_flags & M.TASKF_QUADRUPED_STEPPER:       # LaikagoStepperEnv: done = t > 240 and nsi <= 4 (env_locomotion.py:957-958)
-            tk[0::3, T_NSI] = 5                                   # ... which would end the TimeLimit third first
-            tk[1::6, T_T], tk[1::6, T_NSI] = 240, 3               # ... fires
-            tk[2::6, T_T], tk[2::6, T_NSI] = 240, 5               # ... does not
+            tk[0::3, TW.NEXT_STEP_INDEX] = 5                                   # ... which would end the TimeLimit third first
+            tk[1::6, TW.T], tk[1::6, TW.NEXT_STEP_INDEX] = 240, 3               # ... fires
+            tk[2::6, TW.T], tk[2::6, TW.NEXT_STEP_INDEX] = 240, 5               # ... does not
     if t in (0, 12) and task == M.TASK_WALKER3D_STEPPER:
         # plank advances: robots moved onto the target plank's cover (same offset from the plank centre as their reset pose had from the first
         # plank, test_stepper_standing_on_planks) with target_reached_count = 1, so that a foot on it advances next_step_index (trc >= 2);
@@ -144,14 +143,14 @@ def _build_sample(t, env, o32, task, rng, field, n_planks, start):
             nsi = 1 if j % 2 else n_planks - 1
             st[e] = start["state"][e]
             st[e, 0:3] += ter[e, 6 * nsi:6 * nsi + 3] - start["terrain"][e, 0:3]
-            tk[e, T_NSI], tk[e, T_TRC], tk[e, T_STOP], tk[e, T_SETSTOP] = nsi, 1, 0, 0
-            tk[e, T_T] = min(tk[e, T_T], mx - 10)
+            tk[e, TW.NEXT_STEP_INDEX], tk[e, TW.TARGET_REACHED_COUNT], tk[e, TW.STOP_ON_NEXT_STEP], tk[e, TW.SET_STOP_ON_NEXT_STEP] = nsi, 1, 0, 0
+            tk[e, TW.T] = min(tk[e, TW.T], mx - 10)
     if t in (0, 12) and task == M.TASK_WALKER3D_CUSTOM:
         # re-targets: the target put 5 cm from the robot with close_count = stop_frames - 1, so randomize_target runs inside the step
         sel = np.arange(2 + t % 3, n, 3)
-        tk[sel, T_WTX] = st[sel, 0] + 0.05
-        tk[sel, T_WTY] = st[sel, 1]
-        tk[sel, T_CLOSE] = np.maximum(np.ceil(tk[sel, T_STOPF]) - 1, 0)
+        tk[sel, TW.WALK_TARGET_X] = st[sel, 0] + 0.05
+        tk[sel, TW.WALK_TARGET_Y] = st[sel, 1]
+        tk[sel, TW.CLOSE_COUNT] = np.maximum(np.ceil(tk[sel, TW.STOP_FRAMES]) - 1, 0)
     o32.set_state(st)
     o32.set_task(tk)
 
@@ -250,11 +249,11 @@ def run_step_writes(env_id, task, n, steps, seed=9, kw=None, oracle_model_edit=N
             bad = run & (tgr != tcr).any(axis=1)
             if bad.any():
                 fail(f"t={t}: terrain record differs in running envs {np.nonzero(bad)[0][:8].tolist()}")
-            adv = run & (tc[:, T_NSI] > tk0[:, T_NSI])
+            adv = run & (tc[:, TW.NEXT_STEP_INDEX] > tk0[:, TW.NEXT_STEP_INDEX])
             S["advances"] += int(adv.sum())
             S["ring_writes"] += int((run & (tcr[:, 120:124] != ter0[:, 120:124]).any(axis=1)).sum())
         if task == M.TASK_WALKER3D_CUSTOM:
-            S["retargets"] += int((run & (tk0[:, T_CLOSE] >= tk0[:, T_STOPF] - 1) & (tc[:, T_DRAW] > tk0[:, T_DRAW])).sum())
+            S["retargets"] += int((run & (tk0[:, TW.CLOSE_COUNT] >= tk0[:, TW.STOP_FRAMES] - 1) & (tc[:, TW.DRAW] > tk0[:, TW.DRAW])).sum())
         # ---- envs that finished: the new episode the in-step reset started
         if fin.any():
             for name, g, c, atol in (("obs", og, oc, RESET_ATOL["obs"]), ("state", sg[:, :nd], sc[:, :nd], RESET_ATOL["state"])):
@@ -287,8 +286,8 @@ def run_step_writes(env_id, task, n, steps, seed=9, kw=None, oracle_model_edit=N
                 continue
             S["episodes"] += 1
             r, l, flags = rec[e, 1:2].view(np.float32)[0], int(rec[e, 2]), int(rec[e, 3])
-            if l != int(tk0[e, T_T]) + 1:
-                fail(f"t={t}: env {e}: episode length {l}, the oracle's is {int(tk0[e, T_T]) + 1}")
+            if l != int(tk0[e, TW.T]) + 1:
+                fail(f"t={t}: env {e}: episode length {l}, the oracle's is {int(tk0[e, TW.T]) + 1}")
             if (flags & 2) != (int(dc[e]) & 2):
                 fail(f"t={t}: env {e}: TimeLimit bit of the record {flags & 2}, the oracle's done {int(dc[e])}")
             # |r - f64 sum of the oracle's rewards| within the summed per-step tolerance, plus the f32 running sum's rounding
@@ -388,7 +387,7 @@ def test_the_step_write_comparison_catches_a_wrong_word(control):
         def corrupt(t, tk):
             if t == 3:
                 tk = tk.clone()
-                tk[5:, T_EPISODE] += 1                # one word of the record, in the envs that did not just reset
+                tk[5:, TW.EPISODE] += 1                # one word of the record, in the envs that did not just reset
             return tk
         fails, _ = run_step_writes("Walker3DStepperEnv-v0", M.TASK_WALKER3D_STEPPER, 32, 6, corrupt=corrupt)
     print(f"\n{control}: {len(fails)} failure(s), first: {fails[0] if fails else None}")
@@ -413,7 +412,7 @@ def _free_run_bitwise(env_id, kw, attach, n=192, steps=300):
     probe = attach(b_env)
     a_env.reset(); b_env.reset()
     tk = a_env.get_task()                                                   # TimeLimit truncations (and their in-step resets) in the sample
-    tk[::3, T_T] = int(a_env.model.max_episode_steps) - 5
+    tk[::3, TW.T] = int(a_env.model.max_episode_steps) - 5
     a_env.set_task(tk); b_env.set_task(tk)
     nd = 13 + 2 * int(a_env.model.n_joints)
     g = torch.Generator(device="cuda").manual_seed(6)
