@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MOCCA_ABI_VERSION 7
+#define MOCCA_ABI_VERSION 8
 
 typedef struct mocca_ctx *mocca_handle;
 
@@ -143,7 +143,8 @@ int mocca_destroy(mocca_handle h);
 
 int mocca_n_envs(mocca_handle h);
 int mocca_obs_dim(mocca_handle h);   /* 52 (Custom, env_locomotion.py:58; Planner, :1003-1005) / 65 (Stepper, :386-393) / 36 (CassieEnv) / 42 (CassiePhase*, env_cassie.py:633) */
-int mocca_act_dim(mocca_handle h);   /* 21, robots.py:21-23 (the planner envs too: the kernel takes the base controller's joint actions) */
+int mocca_act_dim(mocca_handle h);   /* 21, robots.py:21-23 (the planner envs too: mocca_step takes the base controller's joint actions) */
+int mocca_plan_dim(mocca_handle h);  /* planner task: 15 = (base_lookahead + base_lookbehind) x base_step_param_dim, env_locomotion.py:1006-1009; else MOCCA_E_ARG */
 int mocca_state_dim(mocca_handle h); /* MOCCA_STATE_DIM */
 
 /* env.reset() (env_locomotion.py:79-109 / :481-513) for every env whose mask byte is non-zero
@@ -255,6 +256,29 @@ int mocca_set_trajectory(mocca_handle h, const float *table_host, int n_frames, 
  * outside the grid there is no ground.  One grid shared by all envs of the handle
  * (the reference loads the same file for every env).  Required before reset / step / observe with MOCCA_TASK_WALKER3D_PLANNER. */
 int mocca_set_heightfield(mocca_handle h, const float *heights_host, int rows, int cols, double scale);
+
+/* The base controller of the planner envs (env_locomotion.py:1029-1040): the agent's action is a 15-number plan; inside step() an actor-critic
+ * pair of MLPs turns [robot_state(50), plan x action_scale] (65 floats, :1093) into the 21 joint actions, and the critic's value is part of the
+ * reward, progress + log(max(1, value)) / 3 (:1101).  params_host [n_floats] f32 and layers_host [n_layers_total][8] i32 (HOST memory): the
+ * actor's layers first (input to head), then the critic's; each row {net 0 / 1, in, out, in rounded up to a multiple of 16, out rounded up
+ * likewise, activation (0 identity, 1 relu, 2 tanh, 3 softsign), offset of W[out][in] (row-major) in params_host, offset of b[out]}.  The
+ * library pads the layers with zeros to the matrix cores' 16 x 16 tile and keeps them in the kernel's own order
+ * (mocca_envs_amd/csrc/mocca_controller.h).  At most 8 layers per net, widths <= 256, hidden widths multiples of 16, 65 in, 21 / 1 out; every
+ * dimension and offset is checked (MOCCA_E_ARG with a message).  Only for MOCCA_TASK_WALKER3D_PLANNER.  params_host == NULL detaches.
+ * Synchronises the device.
+ * While a controller is attached, every mocca_reset / mocca_step / mocca_task_step / mocca_observe also keeps the first 50 floats of the
+ * observation it produced (`self.robot_state`; under auto-reset the new episode's first observation) in a buffer of the handle, wherever
+ * obs_dev pointed: the controller's next input.  It is defined from the first such call after attaching. */
+int mocca_set_base_controller(mocca_handle h, const float *params_host, size_t n_floats, const int32_t *layers_host, int n_layers_total,
+                              double action_scale);
+/* env.step(plan) of the planner envs: the controller kernel (one launch: both nets, all envs; f32 on the matrix cores), then the step kernel on
+ * its joint actions, both on `stream`; the reward carries the value term -- rew_dev, and with it Monitor's returns, totals and records
+ * (mocca_set_episode_stats).  plan_dev [N][15] f32; the rest as mocca_step, and capturable in a hipGraph under the same conditions.
+ * MOCCA_E_ARG without a controller.  mocca_step on the same handle keeps its meaning: joint actions in, progress-only reward. */
+int mocca_plan_step(mocca_handle h, const float *plan_dev, float *obs_dev, float *rew_dev, uint8_t *done_dev, int32_t *info_dev, void *stream);
+/* what the controller produced in the last mocca_plan_step: action_dev [N][21] f32 (before apply_action's clip) and value_dev [N] f32
+ * (either may be NULL) */
+int mocca_get_base_outputs(mocca_handle h, float *action_dev, float *value_dev, void *stream);
 
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */

@@ -1,0 +1,143 @@
+"""`BaseController`: the low-level controller of the planner envs as one host object that both env surfaces take.
+
+In Walker3DPlannerEnv / MikePlannerEnv (env_locomotion.py:982-1133) the agent's action is a 15-number plan; `step` feeds
+`[robot_state(50), plan * action_scale]` to an actor-critic base controller (:1029-1040, :1093), applies the actor's 21 joint actions and
+adds `log(max(1, value)) / 3` to the reward (:1101).  A `BaseController` holds the two MLPs as plain numpy layers:
+
+* `VecEnv(env_id, n, base_controller=ctrl)` / `trainer_api.make_vec_envs(..., base_controller=ctrl)` read `ctrl.actor` / `ctrl.critic` and
+  run them on the device (`VecEnv.plan_step`);
+* `Walker3DPlannerEnv(base_controller=ctrl)` calls it: `ctrl(base_obs[65]) -> (value, action[21])`, float32 numpy.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+ACTIVATIONS = ("identity", "relu", "tanh", "softsign")     # index = the activation id of include/mocca.h mocca_set_base_controller
+INPUT_DIM, ACTION_DIM, MAX_WIDTH, MAX_LAYERS = 65, 21, 256, 8
+
+
+def _round16(n):
+    return -(-int(n) // 16) * 16
+
+
+def _net(layers, out_dim, name):
+    """validated copy of one net: [(W f32 [out][in], b f32 [out], activation)]"""
+    layers = list(layers)
+    if not 1 <= len(layers) <= MAX_LAYERS:
+        raise ValueError(f"{name}: between 1 and {MAX_LAYERS} layers")
+    net, fan_in = [], INPUT_DIM
+    for i, layer in enumerate(layers):
+        w, b, act = layer
+        w = np.array(w, dtype=np.float32, order="C")
+        b = np.array(b, dtype=np.float32).reshape(-1)
+        if act not in ACTIVATIONS:
+            raise ValueError(f"{name}[{i}]: unknown activation {act!r} (one of {ACTIVATIONS})")
+        if w.ndim != 2 or w.shape[1] != fan_in or b.size != w.shape[0]:
+            raise ValueError(f"{name}[{i}]: expected W[out][{fan_in}] and b[out]")
+        fan_in = w.shape[0]
+        if i + 1 == len(layers):
+            if fan_in != out_dim:
+                raise ValueError(f"{name}: the last layer has {fan_in} outputs, not {out_dim}")
+        elif fan_in % 16 or fan_in > MAX_WIDTH:
+            raise ValueError(f"{name}[{i}]: hidden width {fan_in} is not a multiple of 16 up to {MAX_WIDTH}")
+        net.append((w, b, act))
+    return net
+
+
+def _apply(net, x):
+    for w, b, act in net:
+        x = x @ w.T + b
+        if act == "relu":
+            x = np.maximum(x, np.float32(0))
+        elif act == "tanh":
+            x = np.tanh(x)
+        elif act == "softsign":
+            x = x / (np.float32(1) + np.abs(x))
+    return x
+
+
+class BaseController:
+    def __init__(self, actor, critic):
+        self.actor = _net(actor, ACTION_DIM, "actor")
+        self.critic = _net(critic, 1, "critic")
+
+    from_layers = classmethod(lambda cls, actor, critic: cls(actor, critic))
+
+    @classmethod
+    def from_torch(cls, actor_seq, critic_seq):
+        """from two torch.nn.Sequential of Linear / ReLU / Tanh / Softsign; any other module is a ValueError"""
+        from torch import nn
+        names = ((nn.ReLU, "relu"), (nn.Tanh, "tanh"), (nn.Softsign, "softsign"))
+
+        def convert(seq, which):
+            out = []
+            for mod in seq:
+                act = next((n for t, n in names if isinstance(mod, t)), None)
+                if isinstance(mod, nn.Linear):
+                    bias = np.zeros(mod.out_features, np.float32) if mod.bias is None else mod.bias.detach().cpu().numpy()
+                    out.append((mod.weight.detach().cpu().numpy(), bias, "identity"))
+                elif act is not None and out and out[-1][2] == "identity":
+                    out[-1] = out[-1][:2] + (act,)
+                else:
+                    raise ValueError(f"{which}: {type(mod).__name__} is not supported here (Linear, then at most one of ReLU / Tanh / Softsign)")
+            return out
+
+        return cls(convert(actor_seq, "actor"), convert(critic_seq, "critic"))
+
+    # ---- files: one .npz, arrays "<net>/<i>/W", "<net>/<i>/b" and the activation names "<net>/act" ----
+    def save_npz(self, path):
+        data = {}
+        for which in ("actor", "critic"):
+            net = getattr(self, which)
+            data[which + "/act"] = np.array([act for _, _, act in net])
+            for i, (w, b, _) in enumerate(net):
+                data[f"{which}/{i}/W"], data[f"{which}/{i}/b"] = w, b
+        np.savez(path, **data)
+
+    @classmethod
+    def from_npz(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            nets = [[(z[f"{which}/{i}/W"], z[f"{which}/{i}/b"], str(act)) for i, act in enumerate(z[which + "/act"])] for which in ("actor", "critic")]
+        return cls(*nets)
+
+    # ---- the callable Walker3DPlannerEnv(base_controller=...) takes ----
+    def __call__(self, base_obs):
+        x = np.asarray(base_obs, dtype=np.float32)
+        if x.shape[-1:] != (INPUT_DIM,):
+            raise ValueError(f"base_obs has {INPUT_DIM} entries: robot_state(50) and the scaled plan(15)")
+        return _apply(self.critic, x)[..., 0], _apply(self.actor, x)
+
+    # ---- the image the controller kernel reads (csrc/mocca_controller.h); the library builds the same one from .actor / .critic ----
+    def pack(self):
+        """-> (params float32 [n], table int32 [layers][8]): per layer, actor first, the weights padded with zeros to multiples of 16 both
+        ways and cut into 16 x 16 blocks [row block][column block][lane 0..63][4] -- lane l of a block holds row l % 16, columns
+        4 (l // 16) .. + 3 -- then the padded bias.  Table row: net, in, out, in_pad, out_pad, activation id, weight offset, bias offset."""
+        params, table = [], []
+        pos = 0
+        for net_id, net in enumerate((self.actor, self.critic)):
+            for w, b, act in net:
+                n_out, n_in = w.shape
+                p_out, p_in = _round16(n_out), _round16(n_in)
+                full = np.zeros((p_out, p_in), np.float32)
+                full[:n_out, :n_in] = w
+                blocks = full.reshape(p_out // 16, 16, p_in // 16, 4, 4)          # [rb][row][cb][quarter][4]
+                image = blocks.transpose(0, 2, 3, 1, 4).reshape(-1)                # [rb][cb][quarter][row][4]: lane = 16 quarter + row
+                bias = np.zeros(p_out, np.float32)
+                bias[:n_out] = b
+                table.append([net_id, n_in, n_out, p_in, p_out, ACTIVATIONS.index(act), pos, pos + image.size])
+                params += [image, bias]
+                pos += image.size + p_out
+        return np.concatenate(params), np.array(table, np.int32)
+
+    @classmethod
+    def unpack(cls, params, table):
+        """decode pack()'s image back into a controller; non-zero padding is a ValueError"""
+        nets = [[], []]
+        for net_id, n_in, n_out, p_in, p_out, act, w_pos, b_pos in np.asarray(table).tolist():
+            image = np.asarray(params[w_pos:w_pos + p_in * p_out], np.float32).reshape(p_out // 16, p_in // 16, 4, 16, 4)
+            full = image.transpose(0, 3, 1, 2, 4).reshape(p_out, p_in)
+            bias = np.asarray(params[b_pos:b_pos + p_out], np.float32)
+            if full[n_out:].any() or full[:, n_in:].any() or bias[n_out:].any():
+                raise ValueError("padding of a packed controller must be zeros")
+            nets[net_id].append((full[:n_out, :n_in], bias[:n_out], ACTIVATIONS[act]))
+        return cls(*nets)

@@ -7,8 +7,10 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "mocca.h"
+#include "mocca_controller.h"
 #include "mocca_kernels.h"
 
 using namespace mocca;
@@ -103,8 +105,17 @@ struct mocca_ctx {
   float* d_hf = nullptr;        // planner envs: the height field (mocca_set_heightfield), owned by the handle
   int hf_rows = 0, hf_cols = 0;
   float hf_scale = 0.0f;
+  // planner envs: the base controller (mocca_set_base_controller), all owned by the handle
+  float* d_ctrl_params = nullptr;
+  int32_t* d_ctrl_layers = nullptr;
+  int ctrl_n_actor = 0, ctrl_n_critic = 0;
+  float ctrl_scale = 0.0f;
+  float* d_robot_state = nullptr;    // [N][ROBOT_STATE_STRIDE] the controller's next input (StepArgs.robot_state)
+  float* d_base_act = nullptr;       // [N][21] the actor's output of the last mocca_plan_step
+  float* d_base_val = nullptr;       // [N] the critic's
   std::string err;
 };
+static_assert(ROBOT_STATE_STRIDE == mocca_ctrl::CTRL_RS_STRIDE, "the step kernels and the controller kernel share the robot_state buffer");
 
 static thread_local std::string g_err;
 
@@ -331,6 +342,11 @@ int mocca_destroy(mocca_handle h) {
   if (h->d_pace_acc) (void)hipFree(h->d_pace_acc);
   if (h->d_ep_ret) (void)hipFree(h->d_ep_ret);
   for (float* p : h->d_pvec) if (p) (void)hipFree(p);
+  if (h->d_ctrl_params) (void)hipFree(h->d_ctrl_params);
+  if (h->d_ctrl_layers) (void)hipFree(h->d_ctrl_layers);
+  if (h->d_robot_state) (void)hipFree(h->d_robot_state);
+  if (h->d_base_act) (void)hipFree(h->d_base_act);
+  if (h->d_base_val) (void)hipFree(h->d_base_val);
   delete h;
   return MOCCA_OK;
 }
@@ -340,6 +356,11 @@ int mocca_obs_dim(mocca_handle h) { return h ? h->obs_dim : MOCCA_E_ARG; }
 int mocca_act_dim(mocca_handle h) {
   if (!h) return MOCCA_E_ARG;
   return h->task_id == MOCCA_TASK_CASSIE ? h->model.n_ctrl - 2 : h->model.n_joints;
+}
+int mocca_plan_dim(mocca_handle h) {
+  if (!h) return MOCCA_E_ARG;
+  if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER) { h->err = "mocca_plan_dim: only the planner task takes plans"; return MOCCA_E_ARG; }
+  return mocca_ctrl::CTRL_PLAN;
 }
 int mocca_state_dim(mocca_handle h) { return h ? MOCCA_STATE_DIM(h->model.n_joints, h->model.n_slots) : MOCCA_E_ARG; }
 
@@ -363,6 +384,7 @@ static StepArgs make_args(mocca_handle h) {
   a.pace_acc = h->d_pace_acc;
   a.ep_ret = h->d_ep_ret; a.ep_masks = h->ep_masks; a.ep_bad = h->ep_bad; a.ep_totals = h->ep_totals;   // (ep_rec / ep_serial: mocca_step only)
   a.hf = h->d_hf; a.hf_rows = h->hf_rows; a.hf_cols = h->hf_cols; a.hf_scale = h->hf_scale;
+  a.robot_state = h->d_ctrl_params ? h->d_robot_state : nullptr;   // (base_value: mocca_plan_step only)
   return a;
 }
 // A scalar MOCCA_PARAM_APPLIED_GAIN is written into the task records (word MOCCA_TW_APPLIED_GAIN, what apply_action reads) by the NEXT call that takes
@@ -406,14 +428,12 @@ int mocca_reset(mocca_handle h, const uint8_t* mask_dev, uint64_t seed, float* o
   return MOCCA_OK;
 }
 
-int mocca_step(mocca_handle h, const float* act_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev, int32_t* info_dev,
-               void* stream) {
-  if (!h || !act_dev || !obs_dev || !rew_dev || !done_dev) return MOCCA_E_ARG;
-  if (need_trajectory(h) != MOCCA_OK) return MOCCA_E_ARG;
-  DeviceGuard guard(h->device);
+// the step-kernel launch of mocca_step / mocca_plan_step (base_value: the controller's value estimates, or null); the handle's device is current
+static int launch_step(mocca_handle h, const float* act_dev, const float* base_value, float* obs_dev, float* rew_dev, uint8_t* done_dev,
+                       int32_t* info_dev, hipStream_t s) {
   StepArgs a = make_args(h);
   a.act = act_dev; a.obs = obs_dev; a.rew = rew_dev; a.done = done_dev; a.info = info_dev;
-  hipStream_t s = (hipStream_t)stream;
+  a.base_value = base_value;
   if (int rc = flush_pending(h, s)) return rc;
   // mocca_step never allocates and never synchronises, and the pace calibrates itself on the device: the launch can be captured in a
   // hipGraph.  Two optional features keep HOST state per launch that a capture bakes into the kernel arguments: the episode-record ring
@@ -439,6 +459,131 @@ int mocca_step(mocca_handle h, const float* act_dev, float* obs_dev, float* rew_
     default: dispatch<LaunchStep>(h->topo, h->task_id, h->n_envs, s, a);
   }
   HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
+}
+
+int mocca_step(mocca_handle h, const float* act_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev, int32_t* info_dev,
+               void* stream) {
+  if (!h || !act_dev || !obs_dev || !rew_dev || !done_dev) return MOCCA_E_ARG;
+  if (need_trajectory(h) != MOCCA_OK) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  return launch_step(h, act_dev, nullptr, obs_dev, rew_dev, done_dev, info_dev, (hipStream_t)stream);
+}
+
+int mocca_plan_step(mocca_handle h, const float* plan_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev, int32_t* info_dev,
+                    void* stream) {
+  if (!h || !plan_dev || !obs_dev || !rew_dev || !done_dev) return MOCCA_E_ARG;
+  if (!h->d_ctrl_params) { h->err = "mocca_plan_step needs a base controller (mocca_set_base_controller)"; return MOCCA_E_ARG; }
+  if (need_trajectory(h) != MOCCA_OK) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  mocca_ctrl::ControllerArgs c{};
+  c.params = h->d_ctrl_params; c.layers = h->d_ctrl_layers; c.n_actor = h->ctrl_n_actor; c.n_critic = h->ctrl_n_critic;
+  c.robot_state = h->d_robot_state; c.plan = plan_dev; c.action_scale = h->ctrl_scale;
+  c.action = h->d_base_act; c.value = h->d_base_val; c.n_envs = h->n_envs;
+  mocca_ctrl::launch_controller(s, c);
+  HIP_TRY(h, hipGetLastError());
+  return launch_step(h, h->d_base_act, h->d_base_val, obs_dev, rew_dev, done_dev, info_dev, s);
+}
+
+int mocca_get_base_outputs(mocca_handle h, float* action_dev, float* value_dev, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (!h->d_ctrl_params) { h->err = "mocca_get_base_outputs needs a base controller (mocca_set_base_controller)"; return MOCCA_E_ARG; }
+  DeviceGuard guard(h->device);
+  if (action_dev) HIP_TRY(h, hipMemcpyAsync(action_dev, h->d_base_act, (size_t)h->n_envs * mocca_ctrl::CTRL_ACTION * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (value_dev) HIP_TRY(h, hipMemcpyAsync(value_dev, h->d_base_val, (size_t)h->n_envs * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return MOCCA_OK;
+}
+
+int mocca_set_base_controller(mocca_handle h, const float* params_host, size_t n_floats, const int32_t* layers_host, int n_layers_total,
+                              double action_scale) {
+  using namespace mocca_ctrl;
+  if (!h) return MOCCA_E_ARG;
+  if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER) { h->err = "mocca_set_base_controller: only the planner task (Walker3DPlannerEnv, MikePlannerEnv) has a base controller"; return MOCCA_E_ARG; }
+  DeviceGuard guard(h->device);
+  if (!params_host) {   // detach
+    HIP_TRY(h, hipDeviceSynchronize());   // a launch in flight may still read them
+    if (h->d_ctrl_params) (void)hipFree(h->d_ctrl_params);
+    if (h->d_ctrl_layers) (void)hipFree(h->d_ctrl_layers);
+    h->d_ctrl_params = nullptr; h->d_ctrl_layers = nullptr; h->ctrl_n_actor = h->ctrl_n_critic = 0;
+    return MOCCA_OK;
+  }
+  auto bad = [&](const std::string& what) { h->err = "mocca_set_base_controller: " + what; return MOCCA_E_ARG; };
+  if (!layers_host || n_layers_total < 2 || n_layers_total > 2 * CTRL_MAX_LAYERS) return bad("needs 1 .. 8 layers for each of the two nets");
+  if (n_floats == 0 || n_floats > ((size_t)1 << 28)) return bad("the parameter array is empty or larger than any valid controller");
+  if (!std::isfinite(action_scale)) return bad("action_scale is not finite");
+  int count[2] = {0, 0}, prev_out = 0, prev_out_pad = 0;
+  for (int i = 0; i < n_layers_total; ++i) {
+    const int32_t* r = layers_host + (size_t)i * CTRL_LAYER_WORDS;
+    const std::string at = "layer " + std::to_string(i) + ": ";
+    const int net = r[CL_NET];
+    if (net != 0 && net != 1) return bad(at + "net must be 0 (actor) or 1 (critic)");
+    if (i > 0 && net < layers_host[(size_t)(i - 1) * CTRL_LAYER_WORDS + CL_NET]) return bad(at + "the actor's layers come first, then the critic's");
+    const bool first = count[net] == 0;
+    if (++count[net] > CTRL_MAX_LAYERS) return bad(at + "more than 8 layers in one net");
+    const int in = r[CL_IN], out = r[CL_OUT], in_pad = r[CL_IN_PAD], out_pad = r[CL_OUT_PAD];
+    if (in < 1 || in > CTRL_MAX_WIDTH || out < 1 || out > CTRL_MAX_WIDTH) return bad(at + "widths must be 1 .. 256");
+    if (in_pad != (in + 15) / 16 * 16 || out_pad != (out + 15) / 16 * 16) return bad(at + "in_pad / out_pad must be the widths rounded up to a multiple of 16");
+    if (first ? (in != CTRL_IN) : (in != prev_out || in_pad != prev_out_pad)) return bad(at + (first ? "a net's first layer takes the 65-float input" : "input width differs from the previous layer's output"));
+    if (r[CL_ACT] < CTRL_ACT_IDENTITY || r[CL_ACT] > CTRL_ACT_SOFTSIGN) return bad(at + "unknown activation");
+    const long long w_off = r[CL_W_OFF], b_off = r[CL_B_OFF];
+    if (w_off < 0 || b_off < 0 || (unsigned long long)w_off + (size_t)in * out > n_floats || (unsigned long long)b_off + out > n_floats)
+      return bad(at + "weights W[out][in] / bias b[out] must lie inside the parameter array");
+    prev_out = out; prev_out_pad = out_pad;
+    const bool last = i + 1 == n_layers_total || layers_host[(size_t)(i + 1) * CTRL_LAYER_WORDS + CL_NET] != net;
+    if (last && out != (net == 0 ? CTRL_ACTION : 1)) return bad(at + "the actor ends in 21 outputs, the critic in 1");
+    if (!last && (out & 15)) return bad(at + "hidden widths must be multiples of 16");
+  }
+  if (count[0] < 1 || count[1] < 1) return bad("needs an actor and a critic");
+  // the kernel's image (mocca_controller.h): per layer the weights padded with zeros to the 16 x 16 MFMA tile, in fragment order, then the
+  // padded bias; the table's offsets point into it
+  std::vector<int32_t> table(layers_host, layers_host + (size_t)n_layers_total * CTRL_LAYER_WORDS);
+  std::vector<float> image;
+  for (int i = 0; i < n_layers_total; ++i) {
+    int32_t* r = &table[(size_t)i * CTRL_LAYER_WORDS];
+    const int in = r[CL_IN], out = r[CL_OUT], nkg = r[CL_IN_PAD] / 16, n_ot = r[CL_OUT_PAD] / 16;
+    const float *w = params_host + r[CL_W_OFF], *b = params_host + r[CL_B_OFF];
+    r[CL_W_OFF] = (int32_t)image.size();
+    for (int ot = 0; ot < n_ot; ++ot)
+      for (int kg = 0; kg < nkg; ++kg)
+        for (int l = 0; l < 64; ++l)
+          for (int j = 0; j < 4; ++j) {
+            const int row = 16 * ot + (l & 15), k = 16 * kg + 4 * (l >> 4) + j;
+            image.push_back(row < out && k < in ? w[(size_t)row * in + k] : 0.0f);
+          }
+    r[CL_B_OFF] = (int32_t)image.size();
+    for (int o = 0; o < 16 * n_ot; ++o) image.push_back(o < out ? b[o] : 0.0f);
+  }
+  float* d_p = nullptr;
+  int32_t* d_l = nullptr;
+  const size_t lbytes = table.size() * sizeof(int32_t), n = (size_t)h->n_envs;
+  hipError_t e = hipMalloc(&d_p, image.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&d_l, lbytes);
+  if (e == hipSuccess) e = hipMemcpy(d_p, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_l, table.data(), lbytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && !h->d_robot_state) {
+    e = hipMalloc(&h->d_robot_state, n * ROBOT_STATE_STRIDE * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(h->d_robot_state, 0, n * ROBOT_STATE_STRIDE * sizeof(float));
+  }
+  if (e == hipSuccess && !h->d_base_act) {
+    e = hipMalloc(&h->d_base_act, n * CTRL_ACTION * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(h->d_base_act, 0, n * CTRL_ACTION * sizeof(float));
+  }
+  if (e == hipSuccess && !h->d_base_val) {
+    e = hipMalloc(&h->d_base_val, n * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(h->d_base_val, 0, n * sizeof(float));
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // no launch in flight still reads the old controller
+  if (e != hipSuccess) {
+    if (d_p) (void)hipFree(d_p);
+    if (d_l) (void)hipFree(d_l);
+    h->err = std::string("mocca_set_base_controller: ") + hipGetErrorString(e);
+    return MOCCA_E_HIP;
+  }
+  if (h->d_ctrl_params) (void)hipFree(h->d_ctrl_params);
+  if (h->d_ctrl_layers) (void)hipFree(h->d_ctrl_layers);
+  h->d_ctrl_params = d_p; h->d_ctrl_layers = d_l;
+  h->ctrl_n_actor = count[0]; h->ctrl_n_critic = count[1]; h->ctrl_scale = (float)action_scale;
   return MOCCA_OK;
 }
 

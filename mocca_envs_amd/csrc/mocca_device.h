@@ -264,7 +264,14 @@ struct StepArgs {
   void* ep_rec;
   float* ep_totals;
   uint32_t ep_serial;
+  // planner envs with a base controller attached (mocca_set_base_controller), null otherwise.  robot_state [N][ROBOT_STATE_STRIDE]: the first
+  // ROBOT_OBS floats of the observation every reset / step / observe kernel produces (`self.robot_state`, env_locomotion.py:1093) -- under
+  // auto-reset the new episode's first -- wherever the caller pointed `obs`: the controller's next input.  base_value [N] (mocca_plan_step
+  // only): the critic's estimate, whose term log(max(1, v)) / 3 the step kernel adds to the reward (:1101)
+  float* robot_state;
+  const float* base_value;
 };
+constexpr int ROBOT_STATE_STRIDE = 64;   // = mocca_ctrl::CTRL_RS_STRIDE (mocca_controller.h; checked in mocca_api.hip)
 
 // ------------------------------------------------------------------ helpers
 DI void wsync() {

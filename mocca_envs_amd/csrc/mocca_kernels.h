@@ -27,6 +27,14 @@ DI void keep_terminal_obs(const StepArgs& a, const float* L, int env, int lane) 
   wsync();
 }
 
+// Planner envs with a base controller attached: the robot's part of the observation just flushed is also the controller's next input
+// (StepArgs.robot_state), one more coalesced store from LDS.
+template <class T>
+DI void keep_robot_state(const StepArgs& a, const float* L, int env, int lane) {
+  static_assert(ROBOT_OBS<T> <= 64 && ROBOT_OBS<T> <= ROBOT_STATE_STRIDE, "one store per lane");
+  if (a.robot_state && lane < ROBOT_OBS<T>) a.robot_state[(size_t)env * ROBOT_STATE_STRIDE + lane] = L[L_OBS + lane];
+}
+
 // Monitor + TimeLimitMask inside the launch (mocca_set_episode_stats, StepArgs.ep_*): what the reference's trainers wrap around every env --
 // baselines' Monitor (info["episode"] = {r, l} in the step that ends the episode) and a TimeLimitMask (info["bad_transition"] when the episode
 // was cut by max_episode_steps, /root/reference/mocca_envs/__init__.py:55) -- and the two mask columns their PPO loop builds from `done` /
@@ -55,16 +63,17 @@ DI void monitor_emit(const StepArgs& a, int env, float ret0, float rew, int dfla
 struct StepResult { float rew; int info; };   // what the step kernel's epilogue writes
 
 template <class T>
-DI StepResult planner_step(ModelP M, float* L, int lane, TaskRegs& __restrict__ t, const ContactFlags& fl, float* obs) {
+DI StepResult planner_step(ModelP M, float* L, int lane, TaskRegs& __restrict__ t, const ContactFlags& fl, float* obs, const float* base_value) {
   // Walker3DPlannerEnv.step (env_locomotion.py:1075-1128).  calc_state() is called without contact ids there: feet_contact keeps the zeros
-  // of robot.reset.  reward = progress; the second term of the reference, log(max(1, base_value)) / 3, is the external base controller's
-  // value estimate and is added by the caller.
+  // of robot.reset.  reward = progress + log(max(1, base_value)) / 3 (:1101); base_value: this env's entry of the base controller's value
+  // estimates (mocca_plan_step), or null -- joint actions came from the caller (mocca_step): the reward is the progress alone.
   t.fc0 = 0.0f; t.fc1 = 0.0f; t.fc2 = 0.0f; t.fc3 = 0.0f;
   RobotObs ro = robot_obs<T>(M, L, lane, 0.0f, 0.0f, obs);
   const float old = t.linpot;
   float dist, cd, sd;
   calc_potential(M, L, t, ro, &dist, &cd, &sd);
-  const float rew = t.linpot - old;
+  float rew = t.linpot - old;
+  if (base_value) rew += logf(fmaxf(1.0f, *base_value)) / 3.0f;
   // done = done or relative torso height < termination_height or z < -5 or the torso link touches anything (:1103-1111)
   if (ro.height < M->termination_height || L[L_BASE + 2] < M->fall_z || fl.body_touch) t.done = 1;
   if (lane == 0) softsign_tail(sd, cd, obs + ROBOT_OBS<T>);
@@ -390,7 +399,7 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
     }
     wsync();
     t.t += 1;
-    if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) r = planner_step<T>(M, L, lane, t, fl, obs);
+    if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) r = planner_step<T>(M, L, lane, t, fl, obs, a.base_value ? a.base_value + env : nullptr);
     else if constexpr (TASK == MOCCA_TASK_WALKER3D_CUSTOM) r = custom_step<T, INJECT>(a, M, L, env, lane, t, fl, act_raw, obs);
     else r = stepper_step<T, INJECT>(a, M, L, ter, tk, env, lane, t, fl, cover, act_raw, obs);
     t.prevx = L[L_BASE];
@@ -410,6 +419,7 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
   }
   wsync();
   flush_obs(L, obs_out, lane, a.obs_dim);
+  if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) keep_robot_state<T>(a, L, env, lane);
   store_dyn(st, L, lane, T::NJ, T::NSLOT, uni(__float_as_int(L[L_KEEPWARM])) != 0);
   if (lane == 0) store_task<T, TASK, true>(tk, t);
   if (!INJECT) pace_finish(a, L, lane, a.pace);
@@ -434,6 +444,7 @@ __global__ __launch_bounds__(64) void mocca_reset_kernel(StepArgs a) {
   reset_task<T, TASK, INJECT>(a, M, L, ter, tk, env + a.env_offset, lane, t, L + L_OBS);
   wsync();
   flush_obs(L, a.obs + (size_t)env * a.obs_dim, lane, a.obs_dim);
+  if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) keep_robot_state<T>(a, L, env, lane);
   store_dyn(st, L, lane, T::NJ, T::NSLOT);
   if (lane == 0) store_task<T, TASK, true>(tk, t);
 }
@@ -476,6 +487,7 @@ __global__ __launch_bounds__(64) void mocca_observe_kernel(StepArgs a) {
   }
   wsync();
   flush_obs(L, a.obs + (size_t)env * a.obs_dim, lane, a.obs_dim);
+  if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) keep_robot_state<T>(a, L, env, lane);
   if (lane == 0) store_task<T, TASK>(tk, t);
 }
 

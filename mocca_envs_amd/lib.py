@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # MOCCA_LIB_PATH selects another build of the same HIP library (A/B kernel experiments); never a CPU fallback
 LIB_PATH = os.environ.get("MOCCA_LIB_PATH") or os.path.join(HERE, "libmocca_hip.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 PARAM_AUTO_RESET, PARAM_EVAL_MODE, PARAM_CURRICULUM, PARAM_RANDOM_POSE, PARAM_HOST_RETARGET, PARAM_SEED, PARAM_ENV_OFFSET, PARAM_APPLIED_GAIN, PARAM_RANDOM_REWARD = 0, 1, 2, 3, 4, 5, 6, 7, 8
 PARAM_ISSUE_PRIORITY = 9   # timing only: row-count thresholds of the step kernel's issue priorities, t1 + 64 t2 + 4096 t3
 PARAM_PERSIST_IMPULSES = 10  # keep the last substep's normal impulses in the state record although the blob does not warm-start (diagnostic)
@@ -31,10 +31,14 @@ SYMBOLS = {
     "mocca_n_envs": (_i, [_vp]),
     "mocca_obs_dim": (_i, [_vp]),
     "mocca_act_dim": (_i, [_vp]),
+    "mocca_plan_dim": (_i, [_vp]),
     "mocca_state_dim": (_i, [_vp]),
     "mocca_reset": (_i, [_vp, _vp, _u64, _vp, _vp]),
     "mocca_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocca_task_step": (_i, [_vp] * 10),
+    "mocca_set_base_controller": (_i, [_vp, _vp, _sz, _vp, _i, _d]),
+    "mocca_plan_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mocca_get_base_outputs": (_i, [_vp, _vp, _vp, _vp]),
     "mocca_set_draw_tape": (_i, [_vp, _vp, _i]),
     "mocca_observe": (_i, [_vp, _vp, _vp]),
     "mocca_get_state": (_i, [_vp, _vp, _vp]),

@@ -44,6 +44,8 @@ class _Parts:
 
     def _build(self, env_id, counts, devices, seed, env_offset, auto_reset, terminal_obs, kw):
         self.env_id, self.n_envs = env_id, int(sum(counts))
+        if kw.get("base_controller") is not None:      # (the parts' step() would stay the 21-action one: refuse rather than mislead)
+            raise ValueError("base_controller: plan_step() exists on a single VecEnv only (sub_batches=1, one device)")
         self.parts, self.streams, self.slices = [], [], []
         lo = 0
         for cnt, dev in zip(counts, devices):

@@ -199,6 +199,13 @@ class TorchVecEnv:
         high = np.inf * np.ones(self.venv.obs_dim, dtype=np.float32)
         self.observation_space = gym_shim.Box(-high, high, dtype=np.float32)                      # robots.py:18-29, env_locomotion.py:58-60
         self.action_space = gym_shim.Box(-np.ones(self.venv.act_dim, np.float32), np.ones(self.venv.act_dim, np.float32), dtype=np.float32)
+        # a planner env with its base controller attached (base_controller=...): the action is the 15-number plan (unbounded box,
+        # env_locomotion.py:1006-1009) and every step goes through VecEnv.plan_step
+        self._plan = getattr(self.venv, "base_controller", None) is not None
+        self._venv_step = self.venv.plan_step if self._plan else self.venv.step
+        if self._plan:
+            high = np.inf * np.ones(self.venv.plan_dim, dtype=np.float32)
+            self.action_space = gym_shim.Box(-high, high, dtype=np.float32)
         ep = self.venv.episode_stats(True, slots=int(record_slots))
         self.masks = ep["masks"].unsqueeze(1)              # [N, 1], 0 where the episode ended in the last step; REWRITTEN IN PLACE by every step
         self.bad_masks = ep["bad_masks"].unsqueeze(1)      # [N, 1], 0 where it ended at the TimeLimit ("bad_transition")
@@ -274,9 +281,9 @@ class TorchVecEnv:
                 self.masks, self.bad_masks = into.get("masks", self.masks), into.get("bad_masks", self.bad_masks)
                 self.venv.episode_masks_into(self.masks, self.bad_masks)
             rew = into.get("reward", rew)
-            obs = self.venv.step(actions, obs_out=into.get("obs"), rew_out=into.get("reward"))[0]
+            obs = self._venv_step(actions, obs_out=into.get("obs"), rew_out=into.get("reward"))[0]
         else:
-            obs = self.venv.step(actions)[0]
+            obs = self._venv_step(actions)[0]
         if self._events is not None:
             self._events[slot].record(torch.cuda.current_stream(self.device))
         self._k = k + 1 if k < 0xFFFFFFFF else 1
@@ -315,7 +322,7 @@ class TorchVecEnv:
         def body(t):
             if into is None:
                 action = act_of(obs, t)
-                venv.step(action)
+                self._venv_step(action)
                 o, r = obs, rew
             else:
                 action = act_of(into(t - 1)["obs"], t)
@@ -323,7 +330,7 @@ class TorchVecEnv:
                 if "masks" in d or "bad_masks" in d:
                     self.masks, self.bad_masks = d.get("masks", self.masks), d.get("bad_masks", self.bad_masks)
                     venv.episode_masks_into(self.masks, self.bad_masks)
-                o, r = venv.step(action, obs_out=d.get("obs"), rew_out=d.get("reward"))[:2]
+                o, r = self._venv_step(action, obs_out=d.get("obs"), rew_out=d.get("reward"))[:2]
             if sink is not None:
                 sink(t, o, r, self.masks, self.bad_masks, action)
 

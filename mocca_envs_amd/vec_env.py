@@ -34,8 +34,8 @@ TASKS = {
     # the planar mocap / phase envs (__init__.py:31-43, env_cassie.py:481-660): Cassie topology, mocap targets and reward
     "CassiePhaseMocca2DEnv-v0": M.TASK_CASSIE,
     "CassiePhaseMirror2DEnv-v0": M.TASK_CASSIE,
-    # the walkers on the height field (env_locomotion.py:982-1133): Walker3D / Mike tree x Planner task; the kernel takes the 21 joint
-    # actions of the (external) base controller, the planner's 15 numbers are the caller's business
+    # the walkers on the height field (env_locomotion.py:982-1133): Walker3D / Mike tree x Planner task.  step() takes the 21 joint
+    # actions of an external base controller; with one attached (base_controller=) plan_step() takes the planner's 15 numbers
     "Walker3DPlannerEnv-v0": M.TASK_WALKER3D_PLANNER,
     "MikePlannerEnv-v0": M.TASK_WALKER3D_PLANNER,
 }
@@ -105,7 +105,8 @@ class VecEnv:
 
     def __init__(self, env_id: str = "Walker3DCustomEnv-v0", n_envs: int = 1, device: Optional[int] = None,
                  auto_reset: bool = True, seed: int = 0, model_blob: Optional[bytes] = None, env_offset: int = 0,
-                 terminal_obs: bool = False, max_rows: Optional[int] = None, max_contacts: Optional[int] = None, **model_kw):
+                 terminal_obs: bool = False, max_rows: Optional[int] = None, max_contacts: Optional[int] = None, base_controller=None,
+                 **model_kw):
         if env_id not in TASKS:
             raise KeyError(f"{env_id!r} has no GPU stepper yet; available: {sorted(TASKS)}")
         if not torch.cuda.is_available():
@@ -170,6 +171,10 @@ class VecEnv:
         if self.task_id == M.TASK_CASSIE and self.model.cassie_mode != M.CASSIE_PLAIN:
             from .trajectory import CassieTrajectory   # self.traj = CassieTrajectory(), env_cassie.py:576
             self.set_trajectory(CassieTrajectory())
+        self.base_controller = None
+        self.plan_dim = self.lib.mocca_plan_dim(h) if self.task_id == M.TASK_WALKER3D_PLANNER else 0
+        if base_controller is not None:
+            self.set_base_controller(base_controller)
 
     # ------------------------------------------------------------------
     def _stream(self) -> C.c_void_p:
@@ -228,6 +233,59 @@ class VecEnv:
             raise ValueError("heights must be a [rows][cols] grid")
         _lib.check(self.lib.mocca_set_heightfield(self.h, hf.ctypes.data_as(C.c_void_p), hf.shape[0], hf.shape[1], float(scale)), self.h)
         self.height_field = (hf, float(scale))
+
+    # ---- the planner envs' base controller (env_locomotion.py:1029-1040, :1091-1101) ----
+    from .controller import ACTIVATIONS
+
+    def set_base_controller(self, ctrl, action_scale: float = 2.0):
+        """Attach the base controller of a planner env (include/mocca.h mocca_set_base_controller; None detaches).  `ctrl`: a
+        `controller.BaseController` (or any object with `.actor` and `.critic`, or the pair (actor, critic)); each net a list of layers (W[out][in], b[out], activation) with activation one
+        of ACTIVATIONS -- actor 65 -> ... -> 21, critic 65 -> ... -> 1, hidden widths multiples of 16 up to 256, at most 8 layers per net.
+        `action_scale` multiplies the plan (Walker3DPlannerEnv.action_scale = 2).  From the next reset() / step() / observe() on the handle
+        keeps `robot_state` (the first 50 floats of the last observation) as the controller's input: attach before reset(), or call
+        observe() after attaching."""
+        if ctrl is None:
+            _lib.check(self.lib.mocca_set_base_controller(self.h, None, 0, None, 0, 0.0), self.h)
+            self.base_controller = None
+            return
+        actor, critic = (ctrl.actor, ctrl.critic) if hasattr(ctrl, "actor") else ctrl
+        rows, chunks, off = [], [], 0
+        for net, layers in enumerate((actor, critic)):
+            for w, b, act in layers:
+                w, b = np.ascontiguousarray(w, np.float32), np.ascontiguousarray(b, np.float32).reshape(-1)
+                if w.ndim != 2 or act not in self.ACTIVATIONS:
+                    raise ValueError(f"a layer is (W[out][in], b[out], activation in {self.ACTIVATIONS})")
+                out_dim, in_dim = w.shape
+                if b.size != out_dim:
+                    raise ValueError("a layer's bias has one entry per output")
+                rows.append((net, in_dim, out_dim, (in_dim + 15) // 16 * 16, (out_dim + 15) // 16 * 16, self.ACTIVATIONS.index(act), off, off + w.size))
+                chunks += [w.reshape(-1), b]
+                off += w.size + b.size
+        params = np.concatenate(chunks) if chunks else np.zeros(0, np.float32)
+        table = np.asarray(rows, np.int32).reshape(-1, 8)
+        _lib.check(self.lib.mocca_set_base_controller(self.h, params.ctypes.data_as(C.c_void_p), params.size, table.ctypes.data_as(C.c_void_p),
+                                                      table.shape[0], float(action_scale)), self.h)
+        self.base_controller = ctrl
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self._base_action, self._base_value = torch.zeros(self.n_envs, self.act_dim, **f32), torch.zeros(self.n_envs, **f32)
+
+    def plan_step(self, plans: torch.Tensor, obs_out: Optional[torch.Tensor] = None,
+                  rew_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """env.step(plan) of the planner envs (include/mocca.h mocca_plan_step): plans [N, 15] -> the attached base controller (one kernel)
+        -> the step kernel, on the same stream; the reward is progress + log(max(1, value)) / 3 and that is what episode_stats() sums.
+        Same contract as step() otherwise (obs_out / rew_out, streams)."""
+        if not self.plan_dim:
+            raise ValueError("plan_step: planner envs only")
+        return self._launch_step(self.lib.mocca_plan_step, plans, self.plan_dim, "plans", obs_out, rew_out)
+
+    def base_outputs(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(action [N, 21] before apply_action's clip, value [N]) of the controller in the last plan_step(): copies, on the device."""
+        if self.base_controller is None:
+            raise _lib.MoccaError("base_outputs needs a base controller (set_base_controller)")
+        _lib.check(self.lib.mocca_get_base_outputs(self.h, C.c_void_p(self._base_action.data_ptr()), C.c_void_p(self._base_value.data_ptr()),
+                                                   self._stream()), self.h)
+        self._out()
+        return self._base_action.clone(), self._base_value.clone()
 
     # ---- the reference's env-level setters, batched (env_base.py:103-118, env_locomotion.py:76-77,224-282) ----
     def set_env_params(self, params_dict):
@@ -384,18 +442,22 @@ class VecEnv:
         stream: see _in / _out above).  `obs_out` / `rew_out`: where THIS launch writes its observations [N, obs_dim] / rewards [N] (or
         [N, 1]) instead of `self.obs` / `self.rew` -- e.g. row t + 1 of a trainer's rollout storage, which PPO reads the next policy input
         from anyway: the kernel's outputs need no copy (mocca_step takes the pointers per call).  Contiguous float32 on the env's device."""
+        return self._launch_step(self.lib.mocca_step, actions, self.act_dim, "actions", obs_out, rew_out)
+
+    def _launch_step(self, entry, actions, width, what, obs_out, rew_out):
+        """step() / plan_step(): check the tensors, launch `entry` (mocca_step or mocca_plan_step: same argument list)"""
         if actions.device != self.device or actions.dtype != torch.float32 or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
-        if actions.shape != (self.n_envs, self.act_dim):
-            raise ValueError(f"actions must be [{self.n_envs}, {self.act_dim}]")
+        if actions.shape != (self.n_envs, width):
+            raise ValueError(f"{what} must be [{self.n_envs}, {width}]")
         obs, rew = self.obs if obs_out is None else obs_out, self.rew if rew_out is None else rew_out
         if obs_out is not None or rew_out is not None:
             if obs.shape != (self.n_envs, self.obs_dim) or rew.numel() != self.n_envs or obs.dtype != torch.float32 or rew.dtype != torch.float32 \
                     or not obs.is_contiguous() or not rew.is_contiguous() or obs.device != self.device or rew.device != self.device:
                 raise ValueError("obs_out / rew_out must be contiguous float32 [n_envs, obs_dim] / [n_envs] tensors on the env's device")
-        _lib.check(self.lib.mocca_step(self.h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
-                                       C.c_void_p(rew.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                                       C.c_void_p(self.info.data_ptr()), self._stream()), self.h)
+        _lib.check(entry(self.h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
+                         C.c_void_p(rew.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                         C.c_void_p(self.info.data_ptr()), self._stream()), self.h)
         return obs, rew, self.done, self.info
 
     def episode_masks_into(self, masks: torch.Tensor, bad_masks: torch.Tensor) -> None:
