@@ -280,6 +280,54 @@ int mocca_plan_step(mocca_handle h, const float *plan_dev, float *obs_dev, float
  * (either may be NULL) */
 int mocca_get_base_outputs(mocca_handle h, float *action_dev, float *value_dev, void *stream);
 
+/* ---- where the links are, and what an env looks like (no reference counterpart for the first; the second stands in for
+ *      EnvBase.render(mode="rgb_array"), env_base.py:120-159: getCameraImage with FOV 60, near 0.1, far 100) ---- */
+
+/* Link frames of every env from the state the handle currently holds: frames_dev [N][n_bodies][15] f32, per body R (9, row-major,
+ * world <- body), the body origin in world (3), the body's centre of mass in world (3).  A small kernel of its own (one thread per env);
+ * asynchronous on `stream`. */
+int mocca_get_link_frames(mocca_handle h, float *frames_dev, void *stream);
+
+/* A camera record, MOCCA_CAMERA_FLOATS f32: eye (3), right (3), up (3), forward (3) -- orthonormal, right = forward x up --,
+ * tan(fov_y / 2), aspect (width / height), near, far.  The pinhole of computeViewMatrixFromYawPitchRoll(upAxisIndex=2, roll 0) +
+ * computeProjectionMatrixFOV: the eye sits `dist` behind the target along `forward`, `up` has a non-negative z.  (mocca_envs_amd/render.py
+ * Camera counts yaw from +x: yaw 0, pitch 0 looks along +x with +z up.)
+ * Pixel centres: pixel (column i, row j), row 0 at the TOP of the image, looks along
+ *   d = forward + sx * right + sy * up,   sx = (2 (i + 1/2) / W - 1) * tan(fov_y / 2) * aspect,   sy = (1 - 2 (j + 1/2) / H) * tan(fov_y / 2)
+ * from the eye.  d . forward = 1, so the ray parameter t of a hit is its distance along the view axis: the depth. */
+#define MOCCA_CAMERA_FLOATS 16
+#define MOCCA_RENDER_MAX_SIZE 4096 /* width and height: 1 .. 4096 */
+
+/* values of the id image: -1 nothing, 0 .. n_geoms - 1 the robot geom that was hit, then: */
+enum {
+  MOCCA_RENDER_ID_NONE = -1,
+  MOCCA_RENDER_ID_GROUND = 32,       /* = MOCCA_MAX_GEOMS: the plane z = 0 (Custom and Cassie tasks) */
+  MOCCA_RENDER_ID_PLANK0 = 33,       /* + k: live plank k of the Stepper's terrain record, k < MOCCA_MAX_PLANKS */
+  MOCCA_RENDER_ID_HEIGHTFIELD = 37,  /* the planner envs' terrain */
+  MOCCA_RENDER_ID_TARGET = 38,       /* the walk target, a 0.15 m sphere (VSphere, env_locomotion.py:65,580,1027): visual only, it collides with nothing */
+  MOCCA_RENDER_ID_LINK0 = 64,        /* + b: link b of a robot that is drawn as its skeleton (below), 1 <= b < n_bodies */
+};
+
+/* One ray per pixel through the scene of env env_ids_dev[v], seen by camera v, for v < n_views (the same env may be listed more than once):
+ * the robot's geoms (spheres and capsules at the link frames above; a model whose geoms ALL have radius 0 -- Cassie, whose links are meshes in
+ * the reference and hull support points here -- is drawn as its skeleton instead: a capsule of 4 cm radius from every link's parent origin to its own
+ * origin, and for a link without children one from its origin through its centre of mass to twice that distance), the ground plane z = 0 (Custom and Cassie tasks), the live planks of the
+ * Stepper's terrain record (oriented boxes, or upright cylinders for MOCCA_PLANK_CYLINDER), the planner envs' height field (the triangle
+ * split mocca_set_heightfield documents, walked cell by cell along the ray) and the walk target of the walker tasks.  Meshes, textures and
+ * shadows are not drawn.  Outputs, each optional (NULL):
+ *   rgb_dev   [n_views][H][W][3] u8: base colour x (0.35 + 0.65 max(0, n . l)), l = (0.36, -0.48, 0.80) towards the one light, rounded to
+ *             nearest.  Base colours: robot geoms a palette of 8 by body index, ground a two-tone 1 m checker, planks wood, height field a
+ *             tint from low (green) to high (sand), target red; background (0.53, 0.71, 0.90) unshaded = (135, 181, 230).  Cosmetic.
+ *   depth_dev [n_views][H][W] f32: distance along the view axis in metres; exactly `far` where nothing is hit.  Hits nearer than `near`
+ *             are not seen (a surface is hit where the ray ENTERS it).
+ *   id_dev    [n_views][H][W] i32: MOCCA_RENDER_ID_*.
+ * Reads the state, task and terrain records and writes none of them.  Errors (MOCCA_E_ARG, with a message): an env index outside
+ * 0 .. n_envs - 1, a planner handle before mocca_set_heightfield, width or height outside 1 .. MOCCA_RENDER_MAX_SIZE, n_views < 1.
+ * The env indices are checked on the host: the call waits for `stream` once, before it launches (rendering is not on the training path;
+ * not capturable in a hipGraph).  The first call, and a call with more views than any before, allocates. */
+int mocca_render(mocca_handle h, const int32_t *env_ids_dev, int n_views, const float *cameras_dev, int width, int height, uint8_t *rgb_dev,
+                 float *depth_dev, int32_t *id_dev, void *stream);
+
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */
 int mocca_kernel_info(mocca_handle h, int *vgprs, int *sgprs, int *lds_bytes, int *scratch_bytes, int *max_blocks_per_cu);

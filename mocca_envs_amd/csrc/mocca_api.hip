@@ -12,6 +12,7 @@
 #include "mocca.h"
 #include "mocca_controller.h"
 #include "mocca_kernels.h"
+#include "mocca_render.h"
 
 using namespace mocca;
 
@@ -105,6 +106,9 @@ struct mocca_ctx {
   float* d_hf = nullptr;        // planner envs: the height field (mocca_set_heightfield), owned by the handle
   int hf_rows = 0, hf_cols = 0;
   float hf_scale = 0.0f;
+  float hf_zmin = 0.0f, hf_zmax = 0.0f;   // range of the heights (mocca_render clips its rays to it)
+  float* d_scenes = nullptr;    // mocca_render: world-space primitives of each view, owned by the handle, grown on demand
+  int scenes_cap = 0;           // views it holds
   // planner envs: the base controller (mocca_set_base_controller), all owned by the handle
   float* d_ctrl_params = nullptr;
   int32_t* d_ctrl_layers = nullptr;
@@ -338,6 +342,7 @@ int mocca_destroy(mocca_handle h) {
   if (h->d_terrain) (void)hipFree(h->d_terrain);
   if (h->d_traj) (void)hipFree(h->d_traj);
   if (h->d_hf) (void)hipFree(h->d_hf);
+  if (h->d_scenes) (void)hipFree(h->d_scenes);
   if (h->d_order) (void)hipFree(h->d_order);
   if (h->d_pace_acc) (void)hipFree(h->d_pace_acc);
   if (h->d_ep_ret) (void)hipFree(h->d_ep_ret);
@@ -726,6 +731,11 @@ int mocca_set_heightfield(mocca_handle h, const float* heights_host, int rows, i
   delete next;
   if (h->d_hf) (void)hipFree(h->d_hf);
   h->d_hf = d; h->hf_rows = rows; h->hf_cols = cols; h->hf_scale = (float)scale;
+  h->hf_zmin = h->hf_zmax = heights_host[0];
+  for (size_t k = 1; k < cells; ++k) {
+    h->hf_zmin = heights_host[k] < h->hf_zmin ? heights_host[k] : h->hf_zmin;
+    h->hf_zmax = heights_host[k] > h->hf_zmax ? heights_host[k] : h->hf_zmax;
+  }
   return MOCCA_OK;
 }
 
@@ -845,6 +855,58 @@ int mocca_set_param_v(mocca_handle h, int param_id, const float* values_dev, int
     HIP_TRY(h, hipGetLastError());
   }
   h->pvec_on[slot] = true;
+  return MOCCA_OK;
+}
+
+static mocca_rdr::SceneArgs scene_args(mocca_handle h) {
+  mocca_rdr::SceneArgs a{};
+  a.model = h->d_model; a.dyn = h->d_dyn; a.task = h->d_task; a.terrain = h->d_terrain;
+  a.dyn_stride = DYN_STRIDE; a.terrain_stride = TERRAIN_STRIDE; a.task_id = h->task_id;
+  return a;
+}
+
+int mocca_get_link_frames(mocca_handle h, float* frames_dev, void* stream) {
+  if (!h || !frames_dev) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  mocca_rdr::launch_link_frames((hipStream_t)stream, scene_args(h), h->n_envs, frames_dev);
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
+}
+
+int mocca_render(mocca_handle h, const int32_t* env_ids_dev, int n_views, const float* cameras_dev, int width, int height, uint8_t* rgb_dev,
+                 float* depth_dev, int32_t* id_dev, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (!env_ids_dev || !cameras_dev) { h->err = "mocca_render: env_ids_dev and cameras_dev must not be NULL"; return MOCCA_E_ARG; }
+  if (n_views < 1 || n_views > 65535) { h->err = "mocca_render: n_views must be 1 .. 65535"; return MOCCA_E_ARG; }
+  if (width < 1 || height < 1 || width > MOCCA_RENDER_MAX_SIZE || height > MOCCA_RENDER_MAX_SIZE) {
+    h->err = "mocca_render: width and height must be 1 .. " + std::to_string(MOCCA_RENDER_MAX_SIZE); return MOCCA_E_ARG;
+  }
+  if (h->task_id == MOCCA_TASK_WALKER3D_PLANNER && !h->d_hf) {
+    h->err = "mocca_render: the planner task needs mocca_set_heightfield first"; return MOCCA_E_ARG;
+  }
+  DeviceGuard guard(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> ids((size_t)n_views);
+  HIP_TRY(h, hipMemcpyAsync(ids.data(), env_ids_dev, ids.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  for (int v = 0; v < n_views; ++v)
+    if (ids[v] < 0 || ids[v] >= h->n_envs) {
+      h->err = "mocca_render: env index " + std::to_string(ids[v]) + " (view " + std::to_string(v) + ") is outside 0 .. " + std::to_string(h->n_envs - 1);
+      return MOCCA_E_ARG;
+    }
+  if (n_views > h->scenes_cap) {
+    if (h->d_scenes) { HIP_TRY(h, hipFree(h->d_scenes)); h->d_scenes = nullptr; h->scenes_cap = 0; }   // (hipFree waits for the launches that read it)
+    HIP_TRY(h, hipMalloc(&h->d_scenes, (size_t)n_views * mocca_rdr::SCENE_WORDS * sizeof(float)));
+    h->scenes_cap = n_views;
+  }
+  if (int rc = flush_pending(h, s)) return rc;
+  mocca_rdr::launch_scene(s, scene_args(h), env_ids_dev, h->n_envs, n_views, h->d_scenes);
+  HIP_TRY(h, hipGetLastError());
+  mocca_rdr::HeightField hf{nullptr, 0, 0, 0.0f, 0.0f, 0.0f};
+  if (h->task_id == MOCCA_TASK_WALKER3D_PLANNER) hf = mocca_rdr::HeightField{h->d_hf, h->hf_rows, h->hf_cols, h->hf_scale, h->hf_zmin, h->hf_zmax};
+  mocca_rdr::launch_raycast(s, h->d_scenes, cameras_dev, n_views, width, height, h->task_id, h->model.plank_shape, h->model.plank_half, hf,
+                               rgb_dev, depth_dev, id_dev);
+  HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
 }
 

@@ -7,7 +7,7 @@ info)` (4-tuple, no auto-reset), `seed`, `close`, `get_mirror_indices`, `evaluat
 What is replaced is `EnvBase._p` (the pybullet client) and everything the reference did through it.
 
 A facade env is a batch of one on the GPU; trainers that want throughput use `VecEnv` directly.
-Rendering (`render=True`, egl, ffmpeg) is out of scope and raises.
+`render("rgb_array")` ray-casts the scene on the GPU (VecEnv.render); there is no window, and egl / ffmpeg raise.
 """
 from __future__ import annotations
 
@@ -77,11 +77,13 @@ class EnvBase(gym.Env):
     task_id = None
 
     def __init__(self, render=False, remove_ground=False, use_egl=False, use_ffmpeg=False, device=None, model_kw=None, **kwargs):
-        if render or use_egl or use_ffmpeg:
-            raise NotImplementedError("rendering is outside the GPU stepper's scope (SURVEY.md section 2.1 #6)")
+        if use_egl or use_ffmpeg:
+            raise NotImplementedError("use_egl / use_ffmpeg (an OpenGL context, video encoding) are outside the GPU stepper's scope; render() ray-casts on the GPU")
         if kwargs:
             raise TypeError(f"unexpected arguments {sorted(kwargs)}")
-        self.is_rendered = False
+        from .render import Camera
+        self.is_rendered = bool(render)
+        self.camera = Camera()      # the follow camera, bullet_utils.py:383-418; it follows the robot once is_rendered
         self.metadata = dict(self.metadata)
         self.metadata["video.frames_per_second"] = int(1 / self.control_step)
         from .vec_env import VecEnv  # imports torch; needs the HIP library and a GPU (no CPU fallback)
@@ -101,8 +103,24 @@ class EnvBase(gym.Env):
             self._vec.close()
             self._vec = None
 
+    _render_width, _render_height = 960, 720   # env_base.py _render_width / _render_height
+
     def render(self, mode="human"):
-        raise NotImplementedError("rendering is outside the GPU stepper's scope")
+        """env_base.py:120-159.  "rgb_array": the scene through the env's follow camera, np.uint8 [720][960][3], ray-cast on the GPU
+        (VecEnv.render); any other mode returns an empty array as the reference does -- there is no window.  The camera follows the
+        robot from the first call on (or from the start with render=True); the reference rebuilds and resets the env at that point,
+        this one keeps the episode and points the camera at the robot."""
+        if not self.is_rendered:
+            self.is_rendered = True
+            self.camera.lookat(self.robot.body_xyz)
+        if mode != "rgb_array":
+            return np.array([])
+        return self._vec.render([0], self.camera, self._render_width, self._render_height)[0].cpu().numpy()
+
+    def _camera_follow(self, lookat=False):
+        """reset: camera.lookat(robot.body_xyz) (env_locomotion.py:97,503,1065); step: camera.track(...) (:133,554,1105)"""
+        if self.is_rendered:
+            (self.camera.lookat if lookat else self.camera.track)(self.robot.body_xyz)
 
     def set_env_params(self, params_dict):  # env_base.py:103-106
         for k, v in params_dict.items():
@@ -129,12 +147,13 @@ class EnvBase(gym.Env):
         if terrain is not None:
             self._vec.set_terrain(torch.from_numpy(np.asarray(terrain, np.float32)[None]))
 
-    def _pull_robot(self):
+    def _pull_robot(self, lookat=False):
         st = self._img["state"][0]      # the host image of the last step_host / observe_host / reset_host (one download per call)
         nj = self.model.n_joints
         self.robot.body_xyz = st[0:3].astype(np.float64)
         self.robot.joint_angles = st[13:13 + nj].copy()
         self.robot.joint_speeds = 0.1 * st[13 + nj:13 + 2 * nj]
+        self._camera_follow(lookat)
 
     def _step_device(self, action):
         import torch
@@ -183,7 +202,7 @@ class Walker3DCustomEnv(EnvBase):
                              mirrored=int(self.robot.mirrored), episode=self._episode)
         self._push(H.initial_state(self.model, q), task)
         obs = self._observe()
-        self._pull_robot()
+        self._pull_robot(lookat=True)
         return obs
 
     def step(self, action):
@@ -327,7 +346,7 @@ class Walker3DStepperEnv(EnvBase):
         self._push(H.initial_state(self.model, q), task, terrain)
         obs = self._observe()
         obs[6 + 2 * int(self.model.n_joints):6 + 2 * int(self.model.n_joints) + nf] = 0.0   # robot.reset()'s own calc_state: feet_contact.fill(0) (robots.py:197-200)
-        self._pull_robot()
+        self._pull_robot(lookat=True)
         return obs
 
     def step(self, action):
@@ -434,7 +453,7 @@ class Walker3DPlannerEnv(EnvBase):
         self._push(H.initial_state(self.model, q), task)
         obs = self._observe()
         self.robot_state = obs[:self.robot_obs_dim].copy()
-        self._pull_robot()
+        self._pull_robot(lookat=True)
         return obs
 
     def step(self, action):
@@ -495,6 +514,7 @@ class CassieEnv(EnvBase):
         self.walk_target = np.array([1000.0, 0.0, 0.0])
         img = self._img = self._vec.reset_host()                      # deterministic: nominal pose at rest
         self.robot.body_xyz = img["state"][0, 0:3].astype(np.float64)
+        self._camera_follow(lookat=True)
         return img["obs"][0].astype(np.float64)
 
     def step(self, a):
@@ -503,6 +523,7 @@ class CassieEnv(EnvBase):
         assert np.isfinite(a).all()  # env_cassie.py:226
         img = self._img = self._vec.step_host(a.astype(np.float32)[None])
         self.robot.body_xyz = img["state"][0, 0:3].astype(np.float64)
+        self._camera_follow()
         self.done = bool(int(img["done"][0]) & 1)
         return img["obs"][0].astype(np.float64), float(img["rew"][0]), self.done, {}
 

@@ -20,6 +20,9 @@ PARAM_KERNEL_VARIANT = 11    # timing only: 1 forces the 48-row step-kernel inst
 PARAM_ORDER_EVERY = 12       # timing only: every K-th step re-sorts the launch order, heaviest envs (most constraint rows) first
 PARAM_PACE_TICKS = 13        # timing only: pace priorities (target ticks per env.step of a wave) instead of the row-count priorities
 DEBUG_WORDS = 20
+CAMERA_FLOATS = 16   # MOCCA_CAMERA_FLOATS
+RENDER_MAX_SIZE = 4096   # MOCCA_RENDER_MAX_SIZE
+RENDER_ID_NONE, RENDER_ID_GROUND, RENDER_ID_PLANK0, RENDER_ID_HEIGHTFIELD, RENDER_ID_TARGET, RENDER_ID_LINK0 = -1, 32, 33, 37, 38, 64   # MOCCA_RENDER_ID_*
 
 # every symbol include/mocca.h declares: (name, restype, argtypes)
 _vp, _i, _u64, _sz, _d = C.c_void_p, C.c_int, C.c_uint64, C.c_size_t, C.c_double
@@ -56,6 +59,8 @@ SYMBOLS = {
     "mocca_episode_serial": (C.c_uint32, [_vp]),
     "mocca_set_trajectory": (_i, [_vp, _vp, _i, _d, _d]),
     "mocca_set_heightfield": (_i, [_vp, _vp, _i, _i, _d]),
+    "mocca_get_link_frames": (_i, [_vp, _vp, _vp]),
+    "mocca_render": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mocca_is_diagnostic_build": (_i, []),
     "mocca_kernel_info": (_i, [_vp] + [C.POINTER(_i)] * 5),
     "mocca_last_error": (C.c_char_p, [_vp]),

@@ -132,6 +132,40 @@ class _Parts:
     def get_task(self) -> torch.Tensor:
         return self._cat("get_task")
 
+    def link_frames(self, envs=None) -> torch.Tensor:
+        fr = self._cat("link_frames")
+        return fr if envs is None else fr[torch.as_tensor(envs, dtype=torch.long).to(fr.device)]
+
+    def render(self, envs, camera=None, width: int = 320, height: int = 240, depth: bool = False, ids: bool = False):
+        """VecEnv.render over the parts: every env id goes to the handle that owns it (ids are host integers here: the routing is done on
+        the host), the views come back in the order asked, on the first part's device."""
+        ev = np.asarray(envs if not isinstance(envs, torch.Tensor) else envs.cpu(), np.int64).reshape(-1)
+        if ev.size < 1:
+            raise ValueError("render: envs must list at least one env")
+        if ((ev < 0) | (ev >= self.n_envs)).any():
+            raise _lib.MoccaError(f"render: env index outside 0 .. {self.n_envs - 1}")
+        per_view = camera is not None and not hasattr(camera, "pack")
+        if per_view:
+            camera = torch.as_tensor(camera, dtype=torch.float32)
+            if tuple(camera.shape) != (ev.size, _lib.CAMERA_FLOATS):
+                raise ValueError(f"camera records must be [{ev.size}, {_lib.CAMERA_FLOATS}]")
+        dev = self.parts[0].device
+        outs = None
+        for e, sl in zip(self.parts, self.slices):
+            sel = np.nonzero((ev >= sl.start) & (ev < sl.stop))[0]
+            if sel.size == 0:
+                continue
+            got = e.render(ev[sel] - sl.start, camera[torch.from_numpy(sel)] if per_view else camera, width, height, True, True)
+            if outs is None:
+                outs = [torch.empty((ev.size,) + tuple(g.shape[1:]), dtype=g.dtype, device=dev) for g in got]
+            idx = torch.from_numpy(sel).to(dev)
+            for o, g in zip(outs, got):
+                o[idx] = g.to(dev)
+        rgb, dep, idt = outs
+        if not depth and not ids:
+            return rgb
+        return tuple(x for x, on in ((rgb, True), (dep, depth), (idt, ids)) if on)
+
     def set_state(self, st) -> None:
         st = torch.as_tensor(st, dtype=torch.float32).reshape(self.n_envs, self.state_dim)
         for e, sl in zip(self.parts, self.slices):

@@ -580,6 +580,53 @@ class VecEnv:
         _lib.check(self.lib.mocca_set_terrain(self.h, C.c_void_p(t.data_ptr()), self._stream()), self.h)
         self._sync()
 
+    # ---- where the links are, what an env looks like (include/mocca.h mocca_get_link_frames / mocca_render) ----
+    def link_frames(self, envs=None) -> torch.Tensor:
+        """Link frames of the current state, [N (or len(envs))][n_bodies][15] float32 on the device: per body R (9, row-major,
+        world <- body), origin in world (3), centre of mass in world (3) -- the order of the oracle's link_frames.  One small kernel;
+        nothing synchronises."""
+        fr = torch.empty(self.n_envs, int(self.model.n_bodies), 15, dtype=torch.float32, device=self.device)
+        self._in()
+        _lib.check(self.lib.mocca_get_link_frames(self.h, C.c_void_p(fr.data_ptr()), self._stream()), self.h)
+        self._out()
+        if envs is None:
+            return fr
+        return fr[torch.as_tensor(envs, dtype=torch.long).to(self.device)]
+
+    def render(self, envs, camera=None, width: int = 320, height: int = 240, depth: bool = False, ids: bool = False):
+        """Ray-cast the listed envs (an env may be listed more than once): rgb uint8 [K][height][width][3] on the device, or the tuple
+        (rgb, depth float32 [K][H][W] if depth, ids int32 [K][H][W] if ids).  `camera`: one render.Camera for all views, a
+        [K][CAMERA_FLOATS] tensor of records, or None: a follow camera (render.Camera's defaults) per env that looks at the env's base
+        position, which is read and turned into camera records on the device.  An env index out of range raises MoccaError."""
+        from . import render as R
+        ev = torch.as_tensor(envs, dtype=torch.int32).reshape(-1).to(self.device).contiguous()
+        k = int(ev.numel())
+        if k < 1:
+            raise ValueError("render: envs must list at least one env")
+        width, height = int(width), int(height)
+        if not (1 <= width <= _lib.RENDER_MAX_SIZE and 1 <= height <= _lib.RENDER_MAX_SIZE):   # (before the output tensors are sized by them)
+            raise _lib.MoccaError(f"render: width and height must be 1 .. {_lib.RENDER_MAX_SIZE}")
+        if camera is None or isinstance(camera, R.Camera):
+            if camera is None:
+                pos = self.get_state()[ev.long().clamp(0, self.n_envs - 1), 0:3]   # (the library refuses ids out of range below)
+                cams = R.follow_cameras(pos, width / height)
+            else:
+                cams = torch.from_numpy(camera.pack(width / height)).to(self.device).repeat(k, 1).contiguous()
+        else:
+            cams = torch.as_tensor(camera, dtype=torch.float32).to(self.device).contiguous()
+            if tuple(cams.shape) != (k, _lib.CAMERA_FLOATS):
+                raise ValueError(f"camera records must be [{k}, {_lib.CAMERA_FLOATS}]")
+        rgb = torch.empty(k, height, width, 3, dtype=torch.uint8, device=self.device)
+        dep = torch.empty(k, height, width, dtype=torch.float32, device=self.device) if depth else None
+        idt = torch.empty(k, height, width, dtype=torch.int32, device=self.device) if ids else None
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        self._in()
+        _lib.check(self.lib.mocca_render(self.h, ptr(ev), k, ptr(cams), int(width), int(height), ptr(rgb), ptr(dep), ptr(idt), self._stream()), self.h)
+        self._out()
+        if not depth and not ids:
+            return rgb
+        return tuple(x for x in (rgb, dep, idt) if x is not None)
+
     def kernel_info(self) -> dict:
         v = [C.c_int() for _ in range(5)]
         _lib.check(self.lib.mocca_kernel_info(self.h, *[C.byref(x) for x in v]), self.h)

@@ -1,0 +1,190 @@
+"""Rendering on the GPU: link frames against the oracle, the ray caster's ids and depths against the float64 numpy reference
+(tests/render_reference.py) away from edges, colour held loosely, semantics, the gym surface.  Figures: profiles/render_parity.json."""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import render_reference as RR  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+from mocca_envs_amd import lib as L  # noqa: E402
+from mocca_envs_amd import model as M  # noqa: E402
+from mocca_envs_amd.render import Camera  # noqa: E402
+from mocca_envs_amd.vec_env import VecEnv, task_from_float64  # noqa: E402
+
+FIGURES = os.environ.get("MOCCA_RENDER_FIGURES")      # a path: the measured errors are appended there as JSON lines
+
+
+def _record(**kw):
+    print(json.dumps(kw))
+    if FIGURES:
+        with open(FIGURES, "a") as f:
+            f.write(json.dumps(kw) + "\n")
+
+
+# ---- link frames ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("env_id", ["Walker3DCustomEnv-v0", "MikeStepperEnv-v0", "LaikagoCustomEnv-v0", "CassieEnv-v0", "Walker2DCustomEnv-v0"])
+def test_link_frames_match_the_oracle(env_id):
+    from oracle.oracle import Oracle
+    n = 64
+    env = VecEnv(env_id, n, device=0, auto_reset=False, seed=3)
+    nb = int(env.model.n_bodies)
+    o64, o32 = (Oracle(env.model.to_bytes(), env.task_id, n, p) for p in ("f64", "f32"))
+    env.reset()
+    g = torch.Generator().manual_seed(5)
+    done_steps = 0
+    for upto in (0, 1, 10, 100):
+        while done_steps < upto:
+            env.step((torch.rand(n, env.act_dim, generator=g) * 2 - 1).to(env.device))
+            done_steps += 1
+        st = env.get_state().cpu().numpy()
+        got = env.link_frames().cpu().numpy().astype(np.float64)
+        assert got.shape == (n, nb, 15)
+        o64.set_state(st.astype(np.float64)); o32.set_state(st.astype(np.float64))
+        ref = np.stack([o64.link_frames(e, nb) for e in range(n)])
+        r32 = np.stack([o32.link_frames(e, nb) for e in range(n)])
+        ok = np.isfinite(ref).all(axis=(1, 2))          # (a diverged env has no frames to compare)
+        for what, sl in (("rotation", slice(0, 9)), ("position", slice(9, 15))):
+            e32 = np.abs(r32[ok][..., sl] - ref[ok][..., sl]).max()
+            ek = np.abs(got[ok][..., sl] - ref[ok][..., sl]).max()
+            ulp = float(np.spacing(np.float32(np.abs(ref[ok][..., sl]).max())))
+            _record(test="link_frames", env=env_id, steps=upto, component=what, oracle_f32_err=e32, kernel_err=ek, ulp_floor=ulp)
+            assert ek <= 4 * e32 + ulp, (env_id, upto, what, ek, e32, ulp)
+    sub = env.link_frames([3, 3, 60]).cpu().numpy()
+    assert sub.shape == (3, nb, 15) and (sub[0] == sub[1]).all() and (sub[2] == got[60].astype(np.float32)).all()
+    env.close()
+
+
+# ---- ids and depth ----------------------------------------------------------------------------------------------------------------
+def _gpu_scene(name):
+    model, task_id, kw, st, tk, ter, hf = RR.scene_records(name)
+    env = VecEnv(RR.SCENES[name][0], RR.SCENE_ENVS, device=0, auto_reset=False, **kw)
+    env.reset()
+    env.set_state(st)
+    env.set_task(task_from_float64(tk))
+    t128 = np.zeros((RR.SCENE_ENVS, 128), np.float32)
+    t128[:, :ter.shape[1]] = ter
+    env.set_terrain(t128)
+    return env, RR.reference_scene(model, task_id, st, tk, ter, hf), st
+
+
+@pytest.mark.parametrize("name", list(RR.SCENES))
+def test_ids_and_depth_match_the_reference(name):
+    """ids: equal on EVERY pixel whose 3 x 3 neighbourhood in the float64 reference's id image is uniform.  depth: on those pixels the
+    largest relative error against the float64 reference is at most 4 x the float32 numpy reference's own; exactly `far` where nothing is hit."""
+    env, scene, st = _gpu_scene(name)
+    for (w, h) in RR.RESOLUTIONS:
+        for cname, cam in RR.scene_cameras(st[RR.SCENE_ENV, 0:3], w / h).items():
+            d64, i64 = RR.render(scene, cam, w, h, np.float64)
+            d32, _ = RR.render(scene, cam, w, h, np.float32)
+            rgb, dep, ids = env.render([RR.SCENE_ENV], torch.from_numpy(cam)[None], w, h, depth=True, ids=True)
+            dep, ids = dep[0].cpu().numpy(), ids[0].cpu().numpy()
+            keep = ~RR.edge_mask(i64)
+            hit = keep & (i64 >= 0)
+            wrong = int((ids != i64)[keep].sum())
+            e32 = float((np.abs(d32.astype(np.float64) - d64)[hit] / d64[hit]).max()) if hit.any() else 0.0
+            ek = float((np.abs(dep.astype(np.float64) - d64)[hit] / d64[hit]).max()) if hit.any() else 0.0
+            _record(test="render", scene=name, width=w, camera=cname, compared=int(keep.sum()), id_mismatches=wrong, numpy_f32_depth_err=e32, kernel_depth_err=ek)
+            assert wrong == 0, (name, w, cname, wrong)
+            assert ek <= 4 * e32, (name, w, cname, ek, e32)
+            assert (dep[ids == -1] == np.float32(cam[15])).all()
+            bg = rgb[0].cpu().numpy()[ids == -1]
+            assert (bg == np.array([135, 181, 230], np.uint8)).all()      # the background colour, exactly
+    env.close()
+
+
+def test_lambert_value_on_a_sphere_facing_the_light():
+    """The target marker (red 0.90, 0.15, 0.15), seen from the light's direction l: at the image centre n = l, so the colour is the base
+    colour x (0.35 + 0.65 x 1) = (229.5, 38.25, 38.25) -> within 1 of (230, 38, 38)."""
+    env = VecEnv("Walker3DStepperEnv-v0", 1, device=0, auto_reset=False)
+    env.reset()
+    tk = env.get_task()
+    tgt = np.array([40.0, 30.0, 20.0], np.float32)      # far from everything else in the scene
+    tk[:, 0:3] = torch.from_numpy(tgt.view(np.int32)).to(tk.device)
+    env.set_task(tk)
+    l = np.array([0.36, -0.48, 0.80])
+    cam = Camera(yaw=np.degrees(np.arctan2(-l[1], -l[0])), pitch=np.degrees(np.arcsin(-l[2])), dist=2.0)
+    cam.lookat(tgt)
+    rgb, ids = env.render([0], cam, 161, 121, ids=True)
+    assert int(ids[0, 60, 80]) == L.RENDER_ID_TARGET
+    assert np.abs(rgb[0, 60, 80].cpu().numpy().astype(int) - np.array([229.5, 38.25, 38.25])).max() <= 1.0
+    env.close()
+
+
+# ---- semantics --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("env_id", ["Walker3DStepperEnv-v0", "MikePlannerEnv-v0"])
+def test_render_changes_nothing(env_id):
+    outs = []
+    for with_render in (False, True):
+        env = VecEnv(env_id, 16, device=0, auto_reset=True, seed=9)
+        env.reset()
+        g = torch.Generator().manual_seed(1)
+        acts = [(torch.rand(16, env.act_dim, generator=g) * 2 - 1).to(env.device) for _ in range(4)]
+        for a in acts[:3]:
+            env.step(a)
+        if with_render:
+            env.render([0, 7, 15], depth=True, ids=True)
+            env.link_frames()
+        snap = [env.get_state().clone(), env.get_task().clone(), env.get_terrain().clone()]
+        snap += [x.clone() for x in env.step(acts[3])]
+        torch.cuda.synchronize()
+        outs.append([x.cpu().numpy() for x in snap])
+        env.close()
+    for a, b in zip(*outs):
+        assert a.tobytes() == b.tobytes()
+
+
+def test_repeated_ids_and_out_of_range():
+    env = VecEnv("Walker3DCustomEnv-v0", 1024, device=0, auto_reset=False, seed=2)
+    env.reset()
+    rgb, dep = env.render([5, 5, 900], depth=True)
+    assert rgb.shape == (3, 240, 320, 3) and rgb.dtype == torch.uint8 and dep.shape == (3, 240, 320)
+    assert torch.equal(rgb[0], rgb[1]) and torch.equal(dep[0], dep[1]) and not torch.equal(dep[0], dep[2])
+    for bad in ([1024], [-1], [0, 5000]):
+        with pytest.raises(L.MoccaError):
+            env.render(bad)
+    for (w, h) in ((0, 10), (10, -1), (5000, 10)):
+        with pytest.raises(L.MoccaError):
+            env.render([0], width=w, height=h)
+    env.close()
+
+
+def test_sub_batched_render_routes_env_ids():
+    from mocca_envs_amd.multi import SubBatchedVecEnv
+    whole = VecEnv("Walker3DCustomEnv-v0", 64, device=0, auto_reset=False, seed=4)
+    parts = SubBatchedVecEnv("Walker3DCustomEnv-v0", 64, sub_batches=2, device=0, auto_reset=False, seed=4)
+    whole.reset(); parts.reset()
+    a, b = whole.render([40, 3, 40], depth=True), parts.render([40, 3, 40], depth=True)
+    torch.cuda.synchronize()
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    assert torch.equal(whole.link_frames(), parts.link_frames())
+    with pytest.raises(L.MoccaError):
+        parts.render([64])
+    whole.close(); parts.close()
+
+
+# ---- gym surface ------------------------------------------------------------------------------------------------------------------
+def test_gym_render():
+    import mocca_envs_amd
+    env = mocca_envs_amd.make("Walker3DCustomEnv-v0").unwrapped
+    env.seed(0)
+    env.reset()
+    assert env.render("human").shape == (0,)
+    img = env.render("rgb_array")
+    assert img.shape == (720, 960, 3) and img.dtype == np.uint8 and img.min() != img.max()
+    t0 = env.camera.target.copy()
+    assert np.allclose(t0, env.robot.body_xyz)
+    for _ in range(30):
+        env.step(env.action_space.sample() * 0 + 0.3)
+    assert np.abs(env.camera.target - t0).max() > 1e-3 and np.allclose(env.camera.target[:2], env.robot.body_xyz[:2])
+    for kw in (dict(use_egl=True), dict(use_ffmpeg=True)):
+        with pytest.raises(NotImplementedError):
+            mocca_envs_amd.make("Walker3DCustomEnv-v0", **kw)
+    env.close()
