@@ -328,6 +328,37 @@ enum {
 int mocca_render(mocca_handle h, const int32_t *env_ids_dev, int n_views, const float *cameras_dev, int width, int height, uint8_t *rgb_dev,
                  float *depth_dev, int32_t *id_dev, void *stream);
 
+/* ---- what the ground around the robot looks like, ON the training path (no reference counterpart; the nearest is `use_egl`,
+ *      env_base.py:160-201: a camera image for the policy) ---- */
+
+/* The terrain height scan.  A pattern of n points (px, py), metres, in the robot's HEADING frame (x ahead, y to the left) is attached once;
+ * mocca_height_scan then writes, for every env e and point p,
+ *     clamp(hit_z - base_z, -max_drop, +z_above)
+ * where the base position and quaternion are words 0..6 of the state record, (cos yaw, sin yaw) come from the quaternion exactly as the
+ * observation's heading does (no atan2 / sin / cos round trip away from the gimbal branches, which are handled alike), the world point is
+ * xy = base_xy + R_z(yaw) (px, py), and hit_z is where the vertical ray that runs DOWN from z_start = base_z + z_above first meets the
+ * terrain: -max_drop where it meets nothing (or nothing within max_drop below the base), +z_above where the start point already lies
+ * inside a solid.  Only terrain is seen -- never the robot's own geoms or the walk target: the plane z = 0 (Custom and Cassie tasks); the live
+ * planks of the Stepper's terrain record, staged as mocca_render stages them (oriented boxes, upright cylinders for MOCCA_PLANK_CYLINDER;
+ * no ground); the planner envs' height field, the surface of the cell under the point with the triangle split mocca_set_heightfield
+ * documents (outside the grid there is no ground).
+ *   mocca_set_height_scan  points_host [n_points][2] f32 (HOST memory, copied into the handle), 1 <= n_points <= MOCCA_SCAN_MAX_POINTS, finite;
+ *                          z_above >= 0, max_drop > 0.  points_host == NULL detaches.  May synchronise the device.
+ *   mocca_scan_dim         n_points, 0 when no pattern is attached.
+ *   mocca_height_scan      obs_dev == NULL: row e is out_dev[e * row_stride .. + n_points).  obs_dev [N][obs_dim] f32: row e is
+ *                          [obs (obs_dim) | scan (n_points)] -- the same launch copies the observation, so a trainer's widened policy input
+ *                          costs one extra launch and no concatenation.  Floats of a row beyond what is written are left untouched; out_dev
+ *                          must not overlap obs_dev.  One kernel, one wave per env, asynchronous on `stream`: no allocation, no host read, no
+ *                          synchronisation, no atomics -- capturable in a hipGraph together with mocca_step / mocca_plan_step.  Reads the
+ *                          state, task and terrain records and writes none of them; the scan belongs to the state the handle holds when
+ *                          the launch runs (after an auto-reset step: the new episode's first state, like the observation).
+ * Errors (MOCCA_E_ARG, with a message): mocca_height_scan before mocca_set_height_scan, n_points outside 1 .. MOCCA_SCAN_MAX_POINTS, a
+ * non-finite point, z_above < 0 or max_drop <= 0, row_stride smaller than the row, a planner handle before mocca_set_heightfield. */
+#define MOCCA_SCAN_MAX_POINTS 256
+int mocca_set_height_scan(mocca_handle h, const float *points_host, int n_points, double z_above, double max_drop);
+int mocca_scan_dim(mocca_handle h);
+int mocca_height_scan(mocca_handle h, float *out_dev, int row_stride, const float *obs_dev, void *stream);
+
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */
 int mocca_kernel_info(mocca_handle h, int *vgprs, int *sgprs, int *lds_bytes, int *scratch_bytes, int *max_blocks_per_cu);

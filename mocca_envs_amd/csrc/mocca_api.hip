@@ -13,6 +13,7 @@
 #include "mocca_controller.h"
 #include "mocca_kernels.h"
 #include "mocca_render.h"
+#include "mocca_scan.h"
 
 using namespace mocca;
 
@@ -109,6 +110,9 @@ struct mocca_ctx {
   float hf_zmin = 0.0f, hf_zmax = 0.0f;   // range of the heights (mocca_render clips its rays to it)
   float* d_scenes = nullptr;    // mocca_render: world-space primitives of each view, owned by the handle, grown on demand
   int scenes_cap = 0;           // views it holds
+  float* d_scan_pts = nullptr;  // mocca_set_height_scan: the pattern [scan_n][2] in the heading frame, owned by the handle
+  int scan_n = 0;
+  float scan_above = 0.0f, scan_drop = 0.0f;
   // planner envs: the base controller (mocca_set_base_controller), all owned by the handle
   float* d_ctrl_params = nullptr;
   int32_t* d_ctrl_layers = nullptr;
@@ -343,6 +347,7 @@ int mocca_destroy(mocca_handle h) {
   if (h->d_traj) (void)hipFree(h->d_traj);
   if (h->d_hf) (void)hipFree(h->d_hf);
   if (h->d_scenes) (void)hipFree(h->d_scenes);
+  if (h->d_scan_pts) (void)hipFree(h->d_scan_pts);
   if (h->d_order) (void)hipFree(h->d_order);
   if (h->d_pace_acc) (void)hipFree(h->d_pace_acc);
   if (h->d_ep_ret) (void)hipFree(h->d_ep_ret);
@@ -906,6 +911,55 @@ int mocca_render(mocca_handle h, const int32_t* env_ids_dev, int n_views, const 
   if (h->task_id == MOCCA_TASK_WALKER3D_PLANNER) hf = mocca_rdr::HeightField{h->d_hf, h->hf_rows, h->hf_cols, h->hf_scale, h->hf_zmin, h->hf_zmax};
   mocca_rdr::launch_raycast(s, h->d_scenes, cameras_dev, n_views, width, height, h->task_id, h->model.plank_shape, h->model.plank_half, hf,
                                rgb_dev, depth_dev, id_dev);
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
+}
+
+int mocca_set_height_scan(mocca_handle h, const float* points_host, int n_points, double z_above, double max_drop) {
+  if (!h) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  if (!points_host) {   // detach
+    if (h->d_scan_pts) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(h->d_scan_pts); }   // a launch in flight may still read them
+    h->d_scan_pts = nullptr; h->scan_n = 0;
+    return MOCCA_OK;
+  }
+  auto bad = [&](const std::string& what) { h->err = "mocca_set_height_scan: " + what; return MOCCA_E_ARG; };
+  if (n_points < 1 || n_points > MOCCA_SCAN_MAX_POINTS) return bad("n_points must be 1 .. " + std::to_string(MOCCA_SCAN_MAX_POINTS));
+  if (!std::isfinite(z_above) || !std::isfinite(max_drop) || z_above < 0.0 || !(max_drop > 0.0)) return bad("needs a finite z_above >= 0 and max_drop > 0");
+  for (int k = 0; k < 2 * n_points; ++k)
+    if (!std::isfinite(points_host[k])) return bad("point " + std::to_string(k / 2) + " is not finite");
+  float* d = nullptr;
+  HIP_TRY(h, hipMalloc(&d, (size_t)n_points * 2 * sizeof(float)));
+  hipError_t e = hipMemcpy(d, points_host, (size_t)n_points * 2 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess && h->d_scan_pts) e = hipDeviceSynchronize();   // no launch in flight still reads the old pattern
+  if (e != hipSuccess) { (void)hipFree(d); h->err = std::string("mocca_set_height_scan: ") + hipGetErrorString(e); return MOCCA_E_HIP; }
+  if (h->d_scan_pts) (void)hipFree(h->d_scan_pts);
+  h->d_scan_pts = d; h->scan_n = n_points; h->scan_above = (float)z_above; h->scan_drop = (float)max_drop;
+  return MOCCA_OK;
+}
+
+int mocca_scan_dim(mocca_handle h) { return h ? h->scan_n : MOCCA_E_ARG; }
+
+int mocca_height_scan(mocca_handle h, float* out_dev, int row_stride, const float* obs_dev, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (!h->d_scan_pts) { h->err = "mocca_height_scan: no scan pattern (mocca_set_height_scan)"; return MOCCA_E_ARG; }
+  if (!out_dev) { h->err = "mocca_height_scan: out_dev must not be NULL"; return MOCCA_E_ARG; }
+  const int width = h->scan_n + (obs_dev ? h->obs_dim : 0);
+  if (row_stride < width) {
+    h->err = "mocca_height_scan: row_stride " + std::to_string(row_stride) + " is smaller than the row (" + std::to_string(width) + " floats)";
+    return MOCCA_E_ARG;
+  }
+  if (h->task_id == MOCCA_TASK_WALKER3D_PLANNER && !h->d_hf) {
+    h->err = "mocca_height_scan: the planner task needs mocca_set_heightfield first"; return MOCCA_E_ARG;
+  }
+  DeviceGuard guard(h->device);
+  mocca_scan::ScanArgs a{};
+  a.scene = scene_args(h);
+  a.hf = mocca_rdr::HeightField{nullptr, 0, 0, 0.0f, 0.0f, 0.0f};
+  if (h->task_id == MOCCA_TASK_WALKER3D_PLANNER) a.hf = mocca_rdr::HeightField{h->d_hf, h->hf_rows, h->hf_cols, h->hf_scale, h->hf_zmin, h->hf_zmax};
+  a.points = h->d_scan_pts; a.n_points = h->scan_n; a.z_above = h->scan_above; a.max_drop = h->scan_drop;
+  a.out = out_dev; a.row_stride = row_stride; a.obs = obs_dev; a.obs_dim = obs_dev ? h->obs_dim : 0;
+  mocca_scan::launch_height_scan((hipStream_t)stream, a, h->n_envs);
   HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
 }

@@ -5,25 +5,16 @@
 #include <cstdint>
 
 #include "mocca.h"
+#include "mocca_rays.h"
 
 namespace mocca_rdr {
 
 constexpr int TILE = 16;                               // a 16 x 16 pixel tile per workgroup: four waves
 constexpr int MAX_PRIMS = MOCCA_MAX_GEOMS + 1;         // the robot's geoms and the walk target
 constexpr int PRIM_WORDS = 12;                         // p1 (3), radius, p2 (3), id, colour (3), kind
-constexpr int PLANK_WORDS = 12;                        // rotation (9, world <- plank), box centre (3)
 // one view's scene as the assembly kernel leaves it: [MAX_PRIMS][PRIM_WORDS] then [MOCCA_MAX_PLANKS][PLANK_WORDS] then {n_prims, n_planks, 0, 0}
 constexpr int SCENE_WORDS = MAX_PRIMS * PRIM_WORDS + MOCCA_MAX_PLANKS * PLANK_WORDS + 4;
 static_assert(SCENE_WORDS * 4 <= 2048, "the scene of one env stays under 2 KB of LDS");
-
-struct SceneArgs {
-  const MoccaModel* model;
-  const float* dyn;        // [N][dyn_stride]
-  const uint32_t* task;    // [N][MOCCA_TASK_WORDS]
-  const float* terrain;    // [N][terrain_stride]
-  int dyn_stride, terrain_stride, task_id;
-};
-struct HeightField { const float* data; int rows, cols; float scale, zmin, zmax; };   // data == nullptr: none
 
 // frames [n][n_bodies][15] of the handle's n envs
 void launch_link_frames(hipStream_t s, const SceneArgs& a, int n, float* frames);

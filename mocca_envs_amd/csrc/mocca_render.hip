@@ -90,13 +90,6 @@ __global__ __launch_bounds__(64) void link_frames_kernel(SceneArgs a, int n, flo
   walk_frames(M, a.dyn + (size_t)e * a.dyn_stride, frames + (size_t)e * M->n_bodies * 15);
 }
 
-DI void euler_to_mat(float roll, float pitch, float yaw, float* R) {
-  const float cr = cosf(roll), sr = sinf(roll), cp = cosf(pitch), sp = sinf(pitch), cy = cosf(yaw), sy = sinf(yaw);
-  R[0] = cy * cp; R[1] = cy * sp * sr - sy * cr; R[2] = cy * sp * cr + sy * sr;
-  R[3] = sy * cp; R[4] = sy * sp * sr + cy * cr; R[5] = sy * sp * cr - cy * sr;
-  R[6] = -sp;     R[7] = cp * sr;                R[8] = cp * cr;
-}
-
 // one wave per view
 __global__ __launch_bounds__(64) void scene_kernel(SceneArgs a, const int32_t* env_ids, int n_envs, float* scenes) {
   __shared__ float fr[MOCCA_MAX_BODIES * 15];
@@ -165,17 +158,7 @@ __global__ __launch_bounds__(64) void scene_kernel(SceneArgs a, const int32_t* e
   const int npl = a.task_id == MOCCA_TASK_WALKER3D_STEPPER ? M->n_planks : 0;
   if (lane >= 32 && lane < 32 + npl) {   // the live planks, as the step kernel stages them (mocca_device.h stage_planks)
     const int k = lane - 32;
-    const float* ter = a.terrain + (size_t)e * a.terrain_stride;
-    int row = (int)ter[6 * MOCCA_MAX_TERRAIN_STEPS + k];
-    row = row < 0 ? 0 : (row > MOCCA_MAX_TERRAIN_STEPS - 1 ? MOCCA_MAX_TERRAIN_STEPS - 1 : row);
-    const float* ti = ter + 6 * row;
-    float Rb[9];
-    euler_to_mat(ti[4], ti[5], ti[3], Rb);
-    const float cz = M->plank_com_z, dz = -M->plank_half[2] - cz;
-    float* o = out + MAX_PRIMS * PRIM_WORDS + k * PLANK_WORDS;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) o[i] = Rb[i];
-    o[9] = ti[0] + Rb[2] * dz; o[10] = ti[1] + Rb[5] * dz; o[11] = ti[2] + Rb[8] * dz + cz;
+    stage_plank(M, a.terrain + (size_t)e * a.terrain_stride, k, out + MAX_PRIMS * PRIM_WORDS + k * PLANK_WORDS);
   }
   if (lane == 62) {
     float* o = out + MAX_PRIMS * PRIM_WORDS + MOCCA_MAX_PLANKS * PLANK_WORDS;
@@ -207,48 +190,7 @@ DI float hit_tube(const float* o, const float* d, float dd, const float* pa, con
   const float yy = baoa + t * bard;
   return (yy > 0.0f && yy < baba) ? t : -1.0f;
 }
-DI float hit_box(const float* lo, const float* ld, const float* h, int* axis) {   // ray in the box frame
-  float t0 = -1e30f, t1 = 1e30f;
-  int ax = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    if (fabsf(ld[k]) < 1e-20f) {
-      if (fabsf(lo[k]) > h[k]) return -1.0f;
-    } else {
-      const float inv = 1.0f / ld[k];
-      float ta = (-h[k] - lo[k]) * inv, tb = (h[k] - lo[k]) * inv;
-      if (ta > tb) { const float s = ta; ta = tb; tb = s; }
-      if (ta > t0) { t0 = ta; ax = k; }
-      t1 = fminf(t1, tb);
-    }
-  }
-  *axis = ax;
-  return t0 <= t1 ? t0 : -1.0f;
-}
-// upright cylinder in the plank frame: radius h[0], half height h[2]; part: 0 side, 1 cap
-DI float hit_cylinder(const float* lo, const float* ld, const float* h, int* part) {
-  float best = -1.0f;
-  *part = 0;
-  const float A = ld[0] * ld[0] + ld[1] * ld[1], B = lo[0] * ld[0] + lo[1] * ld[1], C = lo[0] * lo[0] + lo[1] * lo[1] - h[0] * h[0];
-  if (A > 1e-20f) {
-    const float disc = B * B - A * C;
-    if (disc >= 0.0f) {
-      const float t = (-B - sqrtf(disc)) / A;
-      if (fabsf(lo[2] + t * ld[2]) <= h[2]) best = t;
-    }
-  }
-  if (fabsf(ld[2]) > 1e-20f) {
-    const float t = ((ld[2] < 0.0f ? h[2] : -h[2]) - lo[2]) / ld[2];   // the cap that faces the ray
-    const float px = lo[0] + t * ld[0], py = lo[1] + t * ld[1];
-    if (px * px + py * py <= h[0] * h[0] && (best < 0.0f || t < best)) { best = t; *part = 1; }
-  }
-  return best;
-}
-
-// height of cell (i, j)'s surface at cell coordinates (u, v): two triangles split from (i + 1, j) to (i, j + 1) (mocca_set_heightfield)
-DI float cell_height(float h00, float h10, float h01, float h11, float u, float v) {
-  return u + v <= 1.0f ? h00 + u * (h10 - h00) + v * (h01 - h00) : h11 + (1.0f - u) * (h01 - h11) + (1.0f - v) * (h10 - h11);
-}
+// (hit_box, hit_cylinder and cell_height: mocca_rays.h, shared with the height scan)
 
 // The height-field march.  The surface is a height function, so along the ray g(t) = z(t) - height(x(t), y(t)) is continuous and piecewise
 // linear, with a kink where the ray crosses a cell border or a cell's diagonal; the first sign change of g is the hit.  The march walks

@@ -117,6 +117,17 @@ class EnvBase(gym.Env):
             return np.array([])
         return self._vec.render([0], self.camera, self._render_width, self._render_height)[0].cpu().numpy()
 
+    def height_scan(self, points=None, z_above=1.0, max_drop=2.0):
+        """Terrain heights around the robot relative to its base (VecEnv.height_scan), np.float32 [P]: `points` [P, 2] metres in the heading
+        frame (x ahead, y to the left) become the env's pattern; None keeps the pattern set before, or an 11 x 7 grid 0.15 m apart from
+        0.45 m behind the base if there is none yet.  No reference counterpart (its terrain-aware input is the use_egl camera image)."""
+        if points is None and self._vec.scan_dim == 0:
+            from .perception import scan_grid
+            points = scan_grid((-0.45, 1.05), (-0.45, 0.45), 11, 7)
+        if points is not None:
+            self._vec.set_height_scan(points, z_above, max_drop)
+        return self._vec.height_scan()[0].cpu().numpy()
+
     def _camera_follow(self, lookat=False):
         """reset: camera.lookat(robot.body_xyz) (env_locomotion.py:97,503,1065); step: camera.track(...) (:133,554,1105)"""
         if self.is_rendered:

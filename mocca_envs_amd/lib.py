@@ -22,6 +22,7 @@ PARAM_PACE_TICKS = 13        # timing only: pace priorities (target ticks per en
 DEBUG_WORDS = 20
 CAMERA_FLOATS = 16   # MOCCA_CAMERA_FLOATS
 RENDER_MAX_SIZE = 4096   # MOCCA_RENDER_MAX_SIZE
+SCAN_MAX_POINTS = 256   # MOCCA_SCAN_MAX_POINTS
 RENDER_ID_NONE, RENDER_ID_GROUND, RENDER_ID_PLANK0, RENDER_ID_HEIGHTFIELD, RENDER_ID_TARGET, RENDER_ID_LINK0 = -1, 32, 33, 37, 38, 64   # MOCCA_RENDER_ID_*
 
 # every symbol include/mocca.h declares: (name, restype, argtypes)
@@ -61,6 +62,9 @@ SYMBOLS = {
     "mocca_set_heightfield": (_i, [_vp, _vp, _i, _i, _d]),
     "mocca_get_link_frames": (_i, [_vp, _vp, _vp]),
     "mocca_render": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "mocca_set_height_scan": (_i, [_vp, _vp, _i, _d, _d]),
+    "mocca_scan_dim": (_i, [_vp]),
+    "mocca_height_scan": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mocca_is_diagnostic_build": (_i, []),
     "mocca_kernel_info": (_i, [_vp] + [C.POINTER(_i)] * 5),
     "mocca_last_error": (C.c_char_p, [_vp]),

@@ -188,15 +188,34 @@ class TorchVecEnv:
     `done` as a real numpy array (one synchronise per step -- for code that insists on `isinstance(done, np.ndarray)`); `record_events=False`
     drops the per-step event (for loops that read `masks` / `episode_totals` only).  `terminal_observation=True` gives every record slot
     terminal-observation rows of its own (launch k writes slot k % record_slots), so `infos[i]["terminal_observation"]` is the final
-    observation of THAT step's episode however late it is read."""
+    observation of THAT step's episode however late it is read.
+    `height_scan=dict(points=[P, 2], z_above=1.0, max_drop=2.0)` (perception.scan_grid builds patterns) appends the terrain height scan to
+    every observation: `observation_space` grows by P, and reset() / step() / step(into=...) / capture_rollout return and fill rows
+    [obs | scan] -- the step kernel's launch, then ONE more (include/mocca.h mocca_height_scan, which copies the observation into the wide row
+    itself): no torch.cat, no copy or synchronise on the host.  Under auto-reset the scan, like the observation, belongs to the new episode's
+    first state."""
 
     def __init__(self, env_id: str, num_envs: int, seed: int = 0, device: Optional[int] = None, sub_batches: int = 1,
-                 terminal_observation: bool = False, record_slots: int = 8, eager_done: bool = False, record_events: bool = True, **kw):
+                 terminal_observation: bool = False, record_slots: int = 8, eager_done: bool = False, record_events: bool = True,
+                 height_scan: Optional[dict] = None, **kw):
+        if height_scan is not None and terminal_observation:
+            raise NotImplementedError("height_scan with terminal_observation=True: the scan runs after the step's launch, when an env that finished "
+                                      "already holds its next episode's first state -- the terminal state is gone, so no scan can be appended to "
+                                      "the terminal observation")
+        if height_scan is not None and sub_batches > 1:
+            raise NotImplementedError("height_scan needs one handle (sub_batches=1)")
         self.venv = make_vec_env(env_id, num_envs, sub_batches=sub_batches, seed=seed, auto_reset=True,
                                  **({"device": device} if device is not None else {}), **kw)
         self.env_id, self.num_envs = env_id, int(num_envs)
         self.device = self.venv.device
-        high = np.inf * np.ones(self.venv.obs_dim, dtype=np.float32)
+        self._scan, self._wide = 0, None
+        if height_scan is not None:
+            if not hasattr(self.venv, "lib"):
+                raise NotImplementedError("height_scan needs one handle (one device, sub_batches=1)")
+            self.venv.set_height_scan(**height_scan)
+            self._scan = self.venv.scan_dim
+            self._wide = torch.zeros(self.num_envs, self.venv.obs_dim + self._scan, dtype=torch.float32, device=self.device)
+        high = np.inf * np.ones(self.venv.obs_dim + self._scan, dtype=np.float32)
         self.observation_space = gym_shim.Box(-high, high, dtype=np.float32)                      # robots.py:18-29, env_locomotion.py:58-60
         self.action_space = gym_shim.Box(-np.ones(self.venv.act_dim, np.float32), np.ones(self.venv.act_dim, np.float32), dtype=np.float32)
         # a planner env with its base controller attached (base_controller=...): the action is the 15-number plan (unbounded box,
@@ -255,7 +274,21 @@ class TorchVecEnv:
 
     # ---- the VecPyTorch surface ----
     def reset(self) -> torch.Tensor:
-        return self.venv.reset()       # (the reset kernel zeroes the envs' running returns: Monitor.reset)
+        obs = self.venv.reset()        # (the reset kernel zeroes the envs' running returns: Monitor.reset)
+        return self.venv.height_scan(out=self._wide, obs=obs) if self._scan else obs
+
+    def _step_obs(self, actions, obs_out=None, rew_out=None):
+        """the step's launch and, with a height scan, the launch that writes the wide row [obs | scan] (into `obs_out` or this object's own
+        buffer; the step's own observation stays in the handle's buffer) -> (obs, reward)"""
+        if not self._scan:
+            if obs_out is None and rew_out is None:      # (the sub-batched step takes the actions only)
+                return self._venv_step(actions)[:2]
+            return self._venv_step(actions, obs_out=obs_out, rew_out=rew_out)[:2]
+        wide = self._wide if obs_out is None else obs_out
+        if wide.shape != self._wide.shape or not wide.is_contiguous():
+            raise ValueError("with a height scan the observation rows are contiguous float32 [n_envs, obs_dim + scan_dim]")
+        o, r = self._venv_step(actions, rew_out=rew_out)[:2]
+        return self.venv.height_scan(out=wide, obs=o), r
 
     def step(self, actions: torch.Tensor, into: Optional[dict] = None):
         """`into` (one handle only): {"obs": [N, obs_dim], "reward": [N, 1], "masks": [N, 1], "bad_masks": [N, 1]} -- any subset -- tensors of the
@@ -281,9 +314,9 @@ class TorchVecEnv:
                 self.masks, self.bad_masks = into.get("masks", self.masks), into.get("bad_masks", self.bad_masks)
                 self.venv.episode_masks_into(self.masks, self.bad_masks)
             rew = into.get("reward", rew)
-            obs = self._venv_step(actions, obs_out=into.get("obs"), rew_out=into.get("reward"))[0]
+            obs = self._step_obs(actions, obs_out=into.get("obs"), rew_out=into.get("reward"))[0]
         else:
-            obs = self._venv_step(actions)[0]
+            obs = self._step_obs(actions)[0]
         if self._events is not None:
             self._events[slot].record(torch.cuda.current_stream(self.device))
         self._k = k + 1 if k < 0xFFFFFFFF else 1
@@ -313,7 +346,7 @@ class TorchVecEnv:
             if self.rollout_terminal_obs is None:
                 self.rollout_terminal_obs = torch.zeros_like(self._term_bufs[0])
             self._attach_terminal(self.rollout_terminal_obs)
-        obs, rew = venv.obs, self._rew2
+        obs, rew = (self._wide if self._scan else venv.obs), self._rew2
         if len(inspect.signature(policy).parameters) >= 2:        # policy(obs, t): e.g. to write its action into the storage's row t
             act_of = policy
         else:
@@ -322,7 +355,7 @@ class TorchVecEnv:
         def body(t):
             if into is None:
                 action = act_of(obs, t)
-                self._venv_step(action)
+                self._step_obs(action)
                 o, r = obs, rew
             else:
                 action = act_of(into(t - 1)["obs"], t)
@@ -330,7 +363,7 @@ class TorchVecEnv:
                 if "masks" in d or "bad_masks" in d:
                     self.masks, self.bad_masks = d.get("masks", self.masks), d.get("bad_masks", self.bad_masks)
                     venv.episode_masks_into(self.masks, self.bad_masks)
-                o, r = self._venv_step(action, obs_out=d.get("obs"), rew_out=d.get("reward"))[:2]
+                o, r = self._step_obs(action, obs_out=d.get("obs"), rew_out=d.get("reward"))[:2]
             if sink is not None:
                 sink(t, o, r, self.masks, self.bad_masks, action)
 

@@ -627,6 +627,50 @@ class VecEnv:
             return rgb
         return tuple(x for x in (rgb, dep, idt) if x is not None)
 
+    # ---- the terrain height scan (include/mocca.h mocca_set_height_scan / mocca_height_scan) ----
+    @property
+    def scan_dim(self) -> int:
+        """points of the attached scan pattern, 0 when there is none"""
+        return int(self.lib.mocca_scan_dim(self.h))
+
+    def set_height_scan(self, points, z_above: float = 1.0, max_drop: float = 2.0) -> None:
+        """Attach the pattern of the height scan: `points` [P, 2] metres in the heading frame (x ahead, y to the left; perception.scan_grid
+        builds grids), 1 <= P <= 256; the rays start `z_above` over the base and see `max_drop` below it.  None detaches.  The points
+        are copied into the handle; may synchronise."""
+        if points is None:
+            _lib.check(self.lib.mocca_set_height_scan(self.h, None, 0, 0.0, 0.0), self.h)
+            return
+        pts = np.ascontiguousarray(points.detach().cpu().numpy() if isinstance(points, torch.Tensor) else points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 2:
+            raise ValueError("height-scan points must be [P, 2]")
+        _lib.check(self.lib.mocca_set_height_scan(self.h, pts.ctypes.data_as(C.c_void_p), pts.shape[0], float(z_above), float(max_drop)), self.h)
+
+    def height_scan(self, out: Optional[torch.Tensor] = None, obs: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Terrain heights under the pattern, relative to the base, of the state the handle holds: float32 [N, P] on the device, one launch,
+        nothing synchronises.  With `obs` (contiguous float32 [N, obs_dim] on the device, e.g. what step() just returned) the rows are
+        [obs | scan], [N, obs_dim + P], written by the same launch.  `out`: where to write -- a float32 [N, >= width] tensor on the device
+        whose rows are contiguous (a view of wider storage will do: floats of a row beyond `width` are left untouched; it must not overlap
+        `obs`); returned, narrowed to the width written."""
+        p = self.scan_dim
+        if p == 0:
+            raise _lib.MoccaError("height_scan needs a pattern (set_height_scan)")
+        width = p
+        if obs is not None:
+            if obs.shape != (self.n_envs, self.obs_dim) or obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device:
+                raise ValueError("obs must be a contiguous float32 [n_envs, obs_dim] tensor on the env's device")
+            width += self.obs_dim
+        if out is None:
+            out = torch.empty(self.n_envs, width, dtype=torch.float32, device=self.device)
+        elif out.dim() != 2 or out.shape[0] != self.n_envs or out.shape[1] < width or out.dtype != torch.float32 or out.device != self.device \
+                or out.stride(1) != 1 or (self.n_envs > 1 and out.stride(0) < out.shape[1]):
+            raise ValueError(f"out must be a float32 [n_envs, >= {width}] tensor on the env's device with contiguous rows")
+        stride = out.stride(0) if self.n_envs > 1 else max(out.stride(0), width)
+        self._in()
+        _lib.check(self.lib.mocca_height_scan(self.h, C.c_void_p(out.data_ptr()), int(stride), None if obs is None else C.c_void_p(obs.data_ptr()),
+                                              self._stream()), self.h)
+        self._out()
+        return out if out.shape[1] == width else out[:, :width]
+
     def kernel_info(self) -> dict:
         v = [C.c_int() for _ in range(5)]
         _lib.check(self.lib.mocca_kernel_info(self.h, *[C.byref(x) for x in v]), self.h)
