@@ -317,7 +317,8 @@ __global__ __launch_bounds__(TILE * TILE) void raycast_kernel(const float* scene
       if (t2 >= 0.0f && (t < 0.0f || t2 < t)) { t = t2; part = 1; }
       if (t3 >= 0.0f && (t < 0.0f || t3 < t)) { t = t3; part = 2; }
     }
-    if (t >= tnear && t < best) { best = t; bestk = k; sub = part; }
+    // (a geom of radius 0 -- a hull support point -- is nothing a ray can enter, though rounding can make its discriminant >= 0)
+    if (r > 0.0f && t >= tnear && t < best) { best = t; bestk = k; sub = part; }
   }
   if (bestk >= 0) {
     const float* P = S + bestk * PRIM_WORDS;

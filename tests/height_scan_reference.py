@@ -20,7 +20,7 @@ GRID_NX, GRID_NY, GRID_STEP, GRID_X0 = 11, 7, 0.15, -0.45
 Z_ABOVE, MAX_DROP = 1.0, 2.0
 EDGE_DELTA = 1e-3            # a point is excluded when the float64 class differs 1 mm away along +-x or +-y
 MAX_EXCLUDED = 0.05          # ... and a scene may lose at most this share of its points
-GRID_OFFSET = {}             # per scene: (dx, dy) added to the pattern, should a scene exceed the cap at (0, 0)
+GRID_OFFSET = {}             # per scene name: (dx, dy) added to the pattern (comparison_grid, synthetic_pattern), should a scene exceed the cap at (0, 0)
 
 
 def comparison_grid(name=None) -> np.ndarray:
@@ -45,9 +45,9 @@ def heading(q, dtype=np.float64):
     return dt(B * n), dt(A * n)
 
 
-def plank_frames(model, terrain, dtype=np.float64):
+def plank_frames(model, terrain, dtype=np.float64, mutate=None):
     """[n_planks][12]: rotation (9, world <- plank) and centre (3) of the live planks of one env's terrain record, as
-    render_reference.scene_from_records stages them"""
+    render_reference.scene_from_records stages them; `mutate`: one of render_reference.MUTATIONS (a wrong frame, for the negative controls)"""
     dt = np.dtype(dtype).type
     ter = np.asarray(terrain, np.float32).astype(dtype)       # the device record is float32
     half2, cz = dt(model.plank_half[2]), dt(model.plank_com_z)
@@ -56,12 +56,17 @@ def plank_frames(model, terrain, dtype=np.float64):
     for k in range(int(model.n_planks)):
         row = int(np.clip(int(ter[6 * MAX_TERRAIN_STEPS + k]), 0, MAX_TERRAIN_STEPS - 1))
         ti = ter[6 * row:6 * row + 6]
-        Rb = euler_to_mat(ti[4], ti[5], ti[3]).astype(dtype)
+        Rb = (euler_to_mat(ti[5], ti[4], ti[3]) if mutate == "roll_pitch_swapped" else euler_to_mat(ti[4], ti[5], ti[3])).astype(dtype)
+        if mutate == "transposed":
+            Rb = Rb.reshape(3, 3).T.ravel()
+        if mutate == "com_rotated":
+            out.append([*Rb, ti[0] + Rb[2] * (dz + cz), ti[1] + Rb[5] * (dz + cz), ti[2] + Rb[8] * (dz + cz)])
+            continue
         out.append([*Rb, ti[0] + Rb[2] * dz, ti[1] + Rb[5] * dz, ti[2] + Rb[8] * dz + cz])
     return np.array(out, dtype).reshape(-1, 12)
 
 
-def scan(state, task_id, points, z_above=Z_ABOVE, max_drop=MAX_DROP, model=None, terrain=None, hf=None, dtype=np.float64):
+def scan(state, task_id, points, z_above=Z_ABOVE, max_drop=MAX_DROP, model=None, terrain=None, hf=None, dtype=np.float64, mutate=None):
     """One env: `state` its state record (words 0..6 are read), `points` [P][2] float32 in the heading frame, `terrain` the env's terrain
     record and `model` the blob (Stepper), `hf` = (heights [rows][cols], scale) (planner)."""
     dt = np.dtype(dtype).type
@@ -71,7 +76,7 @@ def scan(state, task_id, points, z_above=Z_ABOVE, max_drop=MAX_DROP, model=None,
     pts = np.asarray(points, np.float32).astype(dtype)
     za, md = dt(np.float32(z_above)), dt(np.float32(max_drop))
     zs, tfar = bz + za, za + md
-    planks = plank_frames(model, terrain, dtype) if task_id == TASK_STEPPER else np.zeros((0, 12), dtype)
+    planks = plank_frames(model, terrain, dtype, mutate) if task_id == TASK_STEPPER else np.zeros((0, 12), dtype)
     if task_id == TASK_STEPPER:
         half = np.asarray(model.plank_half[:], np.float32).astype(dtype)
         cylinder = int(model.plank_shape) == 1
@@ -102,7 +107,10 @@ def scan(state, task_id, points, z_above=Z_ABOVE, max_drop=MAX_DROP, model=None,
             gx, gy = x * sc + dt(0.5) * dt(cols - 1), y * sc + dt(0.5) * dt(rows - 1)
             if 0 <= gx <= cols - 1 and 0 <= gy <= rows - 1:
                 i, j = min(int(np.floor(gx)), cols - 2), min(int(np.floor(gy)), rows - 2)
-                v = dt(_cell_height(hts[j, i], hts[j, i + 1], hts[j + 1, i], hts[j + 1, i + 1], gx - dt(i), gy - dt(j))) - bz
+                if mutate == "other_diagonal":      # the cell mirrored in u: split from (i, j) to (i + 1, j + 1)
+                    v = dt(_cell_height(hts[j, i + 1], hts[j, i], hts[j + 1, i + 1], hts[j + 1, i], dt(1) - (gx - dt(i)), gy - dt(j))) - bz
+                else:
+                    v = dt(_cell_height(hts[j, i], hts[j, i + 1], hts[j + 1, i], hts[j + 1, i + 1], gx - dt(i), gy - dt(j))) - bz
                 c = CLS_HEIGHTFIELD
         if not v > -md:          # max_drop or more below the base (or nothing at all): none
             c = CLS_NONE
@@ -130,3 +138,72 @@ def scene_kwargs(model, task_id, terrain_row, hf):
     if task_id == TASK_PLANNER:
         kw.update(hf=hf)
     return kw
+
+
+# ---- the synthetic scenes (render_reference.synthetic_records): rotated live planks; planner bases over the hills, at the border, outside
+# ---- the grid, and one low over the hills for a max_drop smaller than the relief ----
+PLANK_SCENES = RR.PLANK_SCENES
+
+
+def wide_grid(n=16, half=20.0):
+    """n x n points over +-half metres: larger than the planner's grid (+-15.875 m), so many points fall outside it; 256 points at n = 16"""
+    from mocca_envs_amd.perception import scan_grid
+    return scan_grid((-half, half), (-half, half), n, n)
+
+
+# name: (pattern, z_above, max_drop) -- what each synthetic scene is scanned with
+PLANK_CASES = {
+    "grid": (comparison_grid, Z_ABOVE, MAX_DROP),
+    "z_above_0": (comparison_grid, 0.0, MAX_DROP),
+    "inside": (comparison_grid, 0.1, MAX_DROP),                # the base is moved INTO the middle live plank: +z_above where the ray starts in a solid
+    "dense_256": (lambda: wide_grid(16, 1.2), Z_ABOVE, MAX_DROP),
+}
+PLANNER_CASES = {
+    "grid": (comparison_grid, Z_ABOVE, MAX_DROP),
+    "z_above_0": (comparison_grid, 0.0, MAX_DROP),
+    "short_drop": (lambda: wide_grid(16, 6.0), 0.5, 0.6),      # bases 1.3 m (and 0.3 m, env 3) up; the relief under the pattern exceeds 0.6 m
+    "wide_256": (wide_grid, Z_ABOVE, 4.0),
+}
+LOW_CLEARANCE = 0.3
+
+
+def synthetic_scan_records(name, case):
+    """(model, task_id, kw, state f32, task, terrain, hf) of render_reference.synthetic_records, arranged for the scan: the planner gets a
+    fourth env low over the hills; in the case "inside" every base sits 15 cm under the top-face centre of its middle live plank, so with
+    z_above = 0.1 the rays start 5 cm inside it"""
+    model, task_id, kw, st, tk, ter, hf = RR.synthetic_records(name)
+    if name == "planner":
+        st, tk, ter = (np.concatenate([a, a[:1]]) for a in (st, tk, ter))
+        st[3, 2] += np.float32(LOW_CLEARANCE - RR.BASE_CLEARANCE)
+    elif case == "inside":
+        st[:, 2] -= np.float32(RR.BASE_CLEARANCE + 0.15)
+    return model, task_id, kw, st, tk, ter, hf
+
+
+def accepts(got, state, task_id, points, z_above=Z_ABOVE, max_drop=MAX_DROP, mutate=None, **kw):
+    """The GPU comparison's rule for one env (tests/test_gpu_height_scan.py): on kept points the class is equal and
+    |got - float64| <= 4 x |float32 reference - float64| + one float32 ulp of the largest |float64 value|: (ok, figures)"""
+    r64, c64 = scan(state, task_id, points, z_above, max_drop, dtype=np.float64, mutate=mutate, **kw)
+    r32, _ = scan(state, task_id, points, z_above, max_drop, dtype=np.float32, mutate=mutate, **kw)
+    pts = np.asarray(points, np.float64)
+    keep = np.ones(len(pts), bool)
+    for dx, dy in ((0, 0), (EDGE_DELTA, 0), (-EDGE_DELTA, 0), (0, EDGE_DELTA), (0, -EDGE_DELTA)):
+        _, c = scan(state, task_id, (pts + np.array([dx, dy])).astype(np.float32), z_above, max_drop, dtype=np.float64, mutate=mutate, **kw)
+        keep &= c == c64
+    got = np.asarray(got)
+    wrong = int(((got == np.float32(-max_drop)) != (c64 == CLS_NONE))[keep].sum())
+    e32 = float(np.abs(r32.astype(np.float64) - r64)[keep].max()) if keep.any() else 0.0
+    ek = float(np.abs(got.astype(np.float64) - r64)[keep].max()) if keep.any() else 0.0
+    ulp = float(np.spacing(np.float32(np.abs(r64[keep]).max()))) if keep.any() else 0.0
+    return wrong == 0 and ek <= 4 * e32 + ulp, dict(compared=int(keep.sum()), excluded=int((~keep).sum()), class_mismatches=wrong, numpy_f32_err=e32, kernel_err=ek, ulp_floor=ulp)
+
+
+def synthetic_pattern(name, case) -> np.ndarray:
+    """the points of one case of a synthetic scene, moved by GRID_OFFSET[name] like comparison_grid(name)"""
+    pat = (PLANNER_CASES if name == "planner" else PLANK_CASES)[case][0]
+    return (pat() + np.asarray(GRID_OFFSET.get(name, (0.0, 0.0)), np.float32)).astype(np.float32)
+
+
+def sees_terrain(state, task_id, points, z_above=Z_ABOVE, max_drop=MAX_DROP, **kw) -> bool:
+    """whether any point of the pattern meets terrain in the float64 reference: an env that sees none cannot tell a wrong terrain from the right one"""
+    return bool((scan(state, task_id, points, z_above, max_drop, **kw)[1] != CLS_NONE).any())

@@ -356,3 +356,53 @@ def test_gym_class_height_scan():
     v = env.height_scan(points=[[0.0, 0.0], [0.5, 0.0]], z_above=0.5, max_drop=0.25)
     assert v.tolist() == [-0.25, -0.25]                            # the ground lies further below the base than max_drop
     env.close()
+
+
+# ---- rotated planks, the hills, the border, outside the grid: synthetic scenes (height_scan_reference.synthetic_scan_records) ---------
+def _synthetic_cases():
+    return [(n, c) for n in HS.PLANK_SCENES for c in HS.PLANK_CASES] + [("planner", c) for c in HS.PLANNER_CASES]
+
+
+@pytest.mark.parametrize("name,case", _synthetic_cases())
+def test_synthetic_scenes_match_the_reference(name, case):
+    """Every synthetic scene and pattern under the rule of this file (class equal and 4 x e32 + 1 ulp on kept points, per env); then, on
+    the comparison grid, the kernel's values must FAIL that rule against each mutated reference."""
+    model, task_id, kw, st, tk, ter, hf = HS.synthetic_scan_records(name, case)
+    _, za, md = (HS.PLANNER_CASES if name == "planner" else HS.PLANK_CASES)[case]
+    pts = HS.synthetic_pattern(name, case)
+    env_id = HS.RR.PLANNER_ENV if name == "planner" else HS.PLANK_SCENES[name][0]
+    env = VecEnv(env_id, st.shape[0], device=0, auto_reset=False, **kw)
+    env.reset()
+    env.set_state(st)
+    env.set_task(task_from_float64(tk))
+    env.set_terrain(ter.astype(np.float32))
+    env.set_height_scan(pts, za, md)
+    assert env.scan_dim == len(pts)
+    got = env.height_scan().cpu().numpy()
+    st_dev = env.get_state().cpu().numpy()
+    assert st_dev.tobytes() == st.tobytes()
+    total = dict(compared=0, excluded=0, class_mismatches=0, numpy_f32_err=0.0, kernel_err=0.0, ulp_floor=0.0)
+    sat = 0
+    for e in range(st.shape[0]):
+        skw = HS.scene_kwargs(model, task_id, ter[e].astype(np.float32), hf)
+        ok, fig = HS.accepts(got[e], st[e], task_id, pts, za, md, **skw)
+        for k in ("compared", "excluded", "class_mismatches"):
+            total[k] += fig[k]
+        for k in ("numpy_f32_err", "kernel_err", "ulp_floor"):
+            total[k] = max(total[k], fig[k])
+        sat += int((got[e] == np.float32(za)).sum())
+        assert ok, (name, case, e, fig)
+    _record(test="synthetic", scene=name, case=case, points=len(pts), z_above=za, max_drop=md, saturated=sat, **total)
+    assert total["excluded"] <= HS.MAX_EXCLUDED * got.size
+    if case in ("inside", "short_drop"):
+        assert sat > 0
+    if case == "grid":      # negative controls: every env that sees terrain must reject every wrong reference
+        for mut in HS.RR.HF_MUTATIONS if name == "planner" else HS.RR.PLANK_MUTATIONS:
+            for e in range(st.shape[0]):
+                skw = HS.scene_kwargs(model, task_id, ter[e].astype(np.float32), hf)
+                if not HS.sees_terrain(st[e], task_id, pts, za, md, **skw):
+                    continue
+                bad, fig = HS.accepts(got[e], st[e], task_id, pts, za, md, mutate=mut, **skw)
+                _record(test="negative_control", scene=name, env=e, mutation=mut, accepted=bool(bad), **fig)
+                assert not bad, (name, mut, e, fig)
+    env.close()

@@ -188,3 +188,105 @@ def test_gym_render():
         with pytest.raises(NotImplementedError):
             mocca_envs_amd.make("Walker3DCustomEnv-v0", **kw)
     env.close()
+
+
+# ---- rotated planks, the hills, the border, outside the grid: synthetic scenes (render_reference.synthetic_records) -------------------
+BRUTE_LATTICE = 6          # the brute force runs on every 6th pixel of every 6th row of images beyond 17 x 33 (its cost is per ray), on all of smaller ones
+
+
+def _gpu_synthetic(name):
+    rec = RR.synthetic_records(name)
+    model, task_id, kw, st, tk, ter, hf = rec
+    env_id = RR.PLANNER_ENV if name == "planner" else RR.PLANK_SCENES[name][0]
+    env = VecEnv(env_id, RR.NEW_ENVS, device=0, auto_reset=False, **kw)
+    env.reset()
+    env.set_state(st)
+    env.set_task(task_from_float64(tk))
+    env.set_terrain(ter.astype(np.float32))
+    return env, rec
+
+
+@pytest.mark.parametrize("name", list(RR.PLANK_SCENES) + ["planner"])
+def test_synthetic_scenes_match_the_reference(name):
+    """Ids, depth and colour of every case of render_reference.compared_cases (scene x env x camera x resolution).  Ids and depth: the rule
+    of test_ids_and_depth_match_the_reference; planner scenes: the same depth bound against the brute-force nearest triangle too.  Colour,
+    on the pixels whose (id, part) neighbourhood is uniform: |rgb - v64| <= 0.5 + 4 e32 levels.  Then the images of the control camera,
+    as rendered above, must FAIL the rule against each mutated reference: a pure comparison."""
+    env, rec = _gpu_synthetic(name)
+    model, task_id, kw, st, tk, ter, hf = rec
+    scenes, control = {}, {}
+    for label, where, e, cname, cam, w, h in RR.compared_cases(name, rec):
+        if e not in scenes:
+            scenes[e] = RR.reference_scene(model, task_id, st, tk, ter, hf, env=e)
+        d64, i64, s64 = RR.render(scenes[e], cam, w, h, np.float64, shading=True)
+        d32, _, s32 = RR.render(scenes[e], cam, w, h, np.float32, shading=True)
+        rgb, dep, ids = env.render([e], torch.from_numpy(cam)[None], w, h, depth=True, ids=True)
+        rgb, dep, ids = rgb[0].cpu().numpy(), dep[0].cpu().numpy(), ids[0].cpu().numpy()
+        if cname == RR.CONTROL_CAMERA and (w, h) == RR.CONTROL_SIZE:
+            control[e] = (cam, dep, ids)
+        ok, fig = RR.accepts(dep, ids, d64, i64, d32, cam[15])
+        tags = dict(test="render_synthetic", scene=label, env=e, width=w, height=h, camera=cname)
+        if name == "planner":
+            step = 1 if w * h <= RR.TINY else BRUTE_LATTICE
+            sel = np.zeros((h, w), bool)
+            sel[::step, ::step] = True
+            sel &= ~RR.edge_mask(i64) & (i64 == RR.ID_HEIGHTFIELD)
+            o, d = RR.rays(cam, w, h, np.float64)
+            tb = RR.hit_heightfield_brute(o, d[sel], hf[0], hf[1], float(cam[14]), float(cam[15]))
+            assert (tb >= 0).all(), (label, cname, w)          # what the march sees, the brute force sees
+            eb32 = float((np.abs(d32.astype(np.float64)[sel] - tb) / tb).max()) if sel.any() else 0.0
+            ebk = float((np.abs(dep.astype(np.float64)[sel] - tb) / tb).max()) if sel.any() else 0.0
+            fig.update(brute_compared=int(sel.sum()), numpy_f32_brute_err=eb32, kernel_brute_err=ebk)
+            assert ebk <= 4 * eb32, (tags, fig)
+        colour = (label, cname, w) not in RR.NO_COLOUR
+        if colour:
+            cok, cfig = RR.colour_accepts(rgb, s64, s32, i64)
+            fig.update(cfig)
+        _record(**tags, **fig)
+        assert ok, (tags, fig)
+        assert not colour or cok, (tags, fig)
+        assert (rgb[ids == -1] == np.array([135, 181, 230], np.uint8)).all()
+        if e == 0 and cname == "short_far" and w * h > RR.TINY:
+            assert (dep == np.float32(cam[15])).mean() > 0.1
+    w, h = RR.CONTROL_SIZE
+    cases = [c for c in RR.control_cases() if c[0] == name]
+    assert cases and all(c[2] in control for c in cases)
+    for _, mutation, e, where in cases:
+        cam, dep, ids = control[e]
+        bad, fig = RR.accepts(dep, ids, *RR.mutated_references(mutation, rec, e, cam, w, h), cam[15])
+        _record(test="render_negative_control", scene=name, env=e, mutation=mutation, **fig)
+        assert not bad, (name, mutation, fig)
+        if mutation in RR.HF_MUTATIONS:      # the same view: what is rejected is the depth of the other split
+            assert fig["id_mismatches"] <= 0.001 * fig["compared"] and fig["kernel_depth_err"] > 100 * fig["numpy_f32_depth_err"], fig
+    env.close()
+
+
+@pytest.mark.parametrize("name", ["stress_box", "planner"])
+def test_several_views_in_one_call(name):
+    """Seven views, distinct envs and distinct cameras, in one call (more views than any call before: the allocation path): each view is
+    bit for bit the view rendered alone, each matches the reference of ITS env and ITS camera, and fails the rule against the reference
+    of another view's camera."""
+    env, rec = _gpu_synthetic(name)
+    model, task_id, kw, st, tk, ter, hf = rec
+    kind = "planner" if name == "planner" else "plank"
+    where_of = {e: w for w, e in RR.PLANNER_ENV_OF.items()}
+    w, h = 161, 121
+    envs = [2, 0, 1, 1, 0, 2, 0]
+    names = ["follow", "oblique", "down", "level90", "short_far", "level180", "level270"]
+    cams = np.stack([RR.new_cameras(kind, st[e, 0:3], w / h, hf, where_of.get(e) if kind == "planner" else None)[c] for e, c in zip(envs, names)])
+    env.render([0], torch.from_numpy(cams[:1]), w, h)                       # (a one-view call first)
+    rgb, dep, ids = env.render(envs, torch.from_numpy(cams), w, h, depth=True, ids=True)
+    refs = []
+    for v, (e, c) in enumerate(zip(envs, names)):
+        one = env.render([e], torch.from_numpy(cams[v:v + 1]), w, h, depth=True, ids=True)
+        assert all(torch.equal(a[v], b[0]) for a, b in zip((rgb, dep, ids), one)), (v, e, c)
+        scene = RR.reference_scene(model, task_id, st, tk, ter, hf, env=e)
+        d64, i64 = RR.render(scene, cams[v], w, h, np.float64)
+        d32, _ = RR.render(scene, cams[v], w, h, np.float32)
+        refs.append((d64, i64, d32, cams[v][15]))
+        ok, fig = RR.accepts(dep[v].cpu().numpy(), ids[v].cpu().numpy(), *refs[-1])
+        _record(test="render_views", scene=name, view=v, env=e, camera=c, **fig)
+        assert ok, (v, e, c, fig)
+    for v, u in ((0, 1), (1, 0), (2, 3)):                                   # two views' cameras exchanged
+        assert not RR.accepts(dep[v].cpu().numpy(), ids[v].cpu().numpy(), *refs[u])[0], (v, u)
+    env.close()

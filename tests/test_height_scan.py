@@ -193,3 +193,72 @@ def test_scenes_exclude_at_most_five_percent(name):
         if task_id != HS.TASK_STEPPER:
             assert not ex.any()          # the plane and the height field are continuous: nothing is excluded
     assert lost <= HS.MAX_EXCLUDED * seen, (name, lost, seen)
+
+
+# ---- the synthetic scenes: rotated live planks, the hills, the border, outside the grid -------------------------------------------
+def _scan_cases():
+    return [(n, c) for n in HS.PLANK_SCENES for c in HS.PLANK_CASES] + [("planner", c) for c in HS.PLANNER_CASES]
+
+
+@pytest.mark.parametrize("name,case", _scan_cases())
+def test_synthetic_scan_scenes_exclude_at_most_five_percent(name, case):
+    """the cap of the committed scenes, unchanged, on every synthetic scene and pattern; and each case shows what it is there for"""
+    model, task_id, kw, st, tk, ter, hf = HS.synthetic_scan_records(name, case)
+    pat, za, md = (HS.PLANNER_CASES if name == "planner" else HS.PLANK_CASES)[case]
+    pts = HS.synthetic_pattern(name, case)
+    lost = seen = sat = none = hit = 0
+    for e in range(st.shape[0]):
+        skw = HS.scene_kwargs(model, task_id, ter[e], hf)
+        ex = HS.excluded(st[e], task_id, pts, z_above=za, max_drop=md, **skw)
+        v, c = HS.scan(st[e], task_id, pts, z_above=za, max_drop=md, **skw)
+        keep = ~ex
+        lost, seen = lost + int(ex.sum()), seen + len(pts)
+        sat, none, hit = sat + int((v == np.float64(np.float32(za)))[keep].sum()), none + int((c == HS.CLS_NONE)[keep].sum()), hit + int((c != HS.CLS_NONE)[keep].sum())
+    print(name, case, "excluded", lost, "of", seen, "saturated", sat, "none", none, "hit", hit)
+    assert lost <= HS.MAX_EXCLUDED * seen, (name, case, lost, seen)
+    assert hit >= 0.1 * seen
+    if case in ("inside", "short_drop"):
+        assert sat > 0                       # rays that start inside a solid / under the surface
+    if case in ("short_drop", "wide_256", "dense_256"):
+        assert none > 0.1 * seen and len(pts) == 256
+
+
+def test_scan_reference_equals_the_vertical_brute_force():
+    """height_scan_reference.scan on the planner bases (hills, border, outside, low) against the vertical brute-force ray over every
+    triangle near the point: hit / miss equal on every kept point, heights within 1e-12 m (measured: 8.9e-16)."""
+    model, task_id, kw, st, tk, ter, hf = HS.synthetic_scan_records("planner", "wide_256")
+    worst, top = 0.0, float(np.max(hf[0])) + 1.0
+    for pat, za, md in (HS.PLANNER_CASES["grid"], HS.PLANNER_CASES["wide_256"]):
+        pts = pat()
+        for e in range(st.shape[0]):
+            v, c = HS.scan(st[e], task_id, pts, z_above=za, max_drop=md, hf=hf)
+            keep = ~HS.excluded(st[e], task_id, pts, z_above=za, max_drop=md, hf=hf)
+            cy, sy = HS.heading(st[e, 3:7].astype(np.float64))
+            b = st[e, 0:3].astype(np.float64)
+            for p in np.nonzero(keep)[0]:
+                px, py = pts[p].astype(np.float64)
+                z = HS.RR.drop_heightfield_brute(b[0] + cy * px - sy * py, b[1] + sy * px + cy * py, top, hf[0], hf[1], 1e3)      # from above the highest vertex: a height field has one surface
+                seen = z is not None and z - b[2] > -md
+                assert seen == (c[p] == HS.CLS_HEIGHTFIELD), (e, p)
+                if seen:
+                    worst = max(worst, abs(min(z - b[2], float(np.float32(za))) - v[p]))
+    print("scan vs vertical brute force: largest difference", worst)
+    assert worst <= 1e-12
+
+
+@pytest.mark.parametrize("name,mutation", [(n, m) for n in HS.PLANK_SCENES for m in HS.RR.PLANK_MUTATIONS] + [("planner", m) for m in HS.RR.HF_MUTATIONS])
+def test_the_scan_rule_rejects_a_mutated_reference(name, mutation):
+    """the float32 reference of the true scene passes the GPU comparison's rule (4 x e32 + 1 ulp on kept points) against the right float64
+    reference in every env, and fails it against one with a wrong plank frame / the other cell split in EVERY env whose pattern sees
+    terrain at all (the planner's env outside the grid sees none)"""
+    model, task_id, kw, st, tk, ter, hf = HS.synthetic_scan_records(name, "grid")
+    pts = HS.synthetic_pattern(name, "grid")
+    for e in range(st.shape[0]):
+        skw = HS.scene_kwargs(model, task_id, ter[e], hf)
+        got, _ = HS.scan(st[e], task_id, pts, dtype=np.float32, **skw)
+        assert HS.accepts(got, st[e], task_id, pts, **skw)[0], (name, e)
+        if HS.sees_terrain(st[e], task_id, pts, **skw):
+            ok, fig = HS.accepts(got, st[e], task_id, pts, mutate=mutation, **skw)
+            assert not ok, (name, mutation, e, fig)
+        else:
+            assert name == "planner" and e == HS.RR.PLANNER_ENV_OF["outside"]

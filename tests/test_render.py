@@ -198,3 +198,179 @@ def test_comparison_scenes_are_valid(name):
             print(f"{name} {w}x{h} {cname}: edge {edge.mean():.4f} robot-not-edge {robot.mean():.4f}")
             assert edge.mean() <= 0.15, (name, w, cname, edge.mean())
             assert robot.mean() >= 0.02, (name, w, cname, robot.mean())
+
+
+# ---- the synthetic scenes: rotated planks, the hills, the border, outside the grid (render_reference.synthetic_records) ----------
+def _synthetic(name):
+    """[(label, where, env, scene64, base)] of one synthetic scene, and its records"""
+    rec = RR.synthetic_records(name)
+    model, task_id, kw, st, tk, ter, hf = rec
+    if name == "planner":
+        return rec, [(w, w, e, RR.reference_scene(model, task_id, st, tk, ter, hf, env=e), st[e, 0:3]) for w, e in RR.PLANNER_ENV_OF.items()]
+    return rec, [(name, None, 0, RR.reference_scene(model, task_id, st, tk, ter, hf, env=0), st[0, 0:3])]
+
+
+def test_synthetic_planks_are_rotated():
+    """every live plank of every plank scene carries three non-zero angles; the stress set reaches beyond 0.2 rad in each"""
+    for name, (_, _, kind) in RR.PLANK_SCENES.items():
+        model, _, _, _, _, ter, _ = RR.synthetic_records(name)
+        assert int(model.n_planks) == (4 if "laikago" in name else 3)
+        for e in range(RR.NEW_ENVS):
+            rows = [ter[e, 6 * int(r):][:6] for r in ter[e, 120:120 + int(model.n_planks)]]
+            for row in rows:
+                assert (np.abs(row[3:6]) > (0.2 if kind == "stress" else 1e-4)).all() and (np.abs(row[3:6]) <= RR.STRESS_MAX).all()
+            assert (ter[e, 124:] == 0).all()
+
+
+@pytest.mark.parametrize("name", list(RR.PLANK_SCENES) + ["planner"])
+def test_synthetic_scenes_are_valid(name):
+    """Every case the GPU comparison renders (render_reference.compared_cases: scene x env x camera x resolution) on the float64 reference
+    alone: at most 15 % id-edge pixels; at least 2 % of the pixels are plank (plank scenes) or height-field (planner) pixels away from
+    edges; the (id, part) mask of the colour comparison leaves out at most 35 % unless the case is listed in render_reference.NO_COLOUR.
+    Images of up to 17 x 33 pixels are exempt and compared in full."""
+    rec = RR.synthetic_records(name)
+    model, task_id, kw, st, tk, ter, hf = rec
+    scenes = {}
+    for label, where, e, cname, cam, w, h in RR.compared_cases(name, rec):
+        if w * h <= RR.TINY:
+            continue
+        if e not in scenes:
+            scenes[e] = RR.reference_scene(model, task_id, st, tk, ter, hf, env=e)
+        _, ids, sh = RR.render(scenes[e], cam, w, h, np.float64, shading=True)
+        edge, cedge = RR.edge_mask(ids), RR.edge_mask(ids, sh["part"])
+        want = (ids == RR.ID_HEIGHTFIELD) if name == "planner" else ((ids >= RR.ID_PLANK0) & (ids < RR.ID_HEIGHTFIELD))
+        share = (want & ~edge).mean()
+        print(f"{label} env {e} {cname} {w}x{h}: edge {edge.mean():.4f} share {share:.4f} colour-edge {cedge.mean():.4f}")
+        assert edge.mean() <= RR.MAX_ID_EDGE, (label, e, cname, w, edge.mean())
+        assert share >= RR.MIN_SHARE, (label, e, cname, w, share)
+        if (label, cname, w) not in RR.NO_COLOUR:
+            assert cedge.mean() <= RR.MAX_COLOUR_EDGE, (label, e, cname, w, cedge.mean())
+        if cname == "short_far":
+            assert 0.1 < (ids == -1).mean() < 0.95          # `far` really ends inside the scene
+
+
+BRUTE_SIZES = ((33, 25), (17, 33))          # odd: the centre column and row carry the rays with exactly zero components
+BRUTE_REL = 1e-12
+
+
+def test_march_equals_brute_force_on_every_planner_camera():
+    """The numpy march (the kernel's algorithm) against the brute-force nearest hit over all 32 258 triangles, float64, the height field
+    alone, on every planner camera of the three bases at 33 x 25 and 17 x 33: hit / miss equal on EVERY ray, depth within 1e-12 relative.
+    Measured: the largest relative difference over all cameras is 1.7e-14 (float64 rounding through two different formulas); the camera
+    under the surface looking up agrees like the others, so it stays in the comparison."""
+    (model, task_id, kw, st, tk, ter, hf), views = _synthetic("planner")
+    worst, seen_zero = 0.0, set()
+    for label, where, e, scene, base in views:
+        for (w, h) in BRUTE_SIZES:
+            for cname, cam in RR.new_cameras("planner", base, w / h, hf, where).items():
+                o, d = RR.rays(cam, w, h, np.float64)
+                tn, tf = float(cam[14]), float(cam[15])
+                a = RR.hit_heightfield(o, d, hf[0], hf[1], tn, np.full((h, w), tf))
+                b = RR.hit_heightfield_brute(o, d, hf[0], hf[1], tn, tf)
+                assert ((a >= 0) == (b >= 0)).all(), (label, cname, w, int(((a >= 0) != (b >= 0)).sum()))
+                m = a >= 0
+                if m.any():
+                    worst = max(worst, float((np.abs(a - b)[m] / b[m]).max()))
+                seen_zero |= {k for k in range(3) if (d[..., k] == 0).any()}
+    print("march vs brute force: largest relative depth difference", worst)
+    assert worst <= BRUTE_REL
+    assert seen_zero == {0, 1, 2}          # rays with dx == 0, dy == 0 and dz == 0 were among them
+
+
+def test_brute_force_closed_forms():
+    hts = np.array([[0.1, 0.4], [0.7, 0.2]])
+    o = np.array([-0.2, -0.1, 5.0])
+    t, tri = RR.hit_heightfield_brute(o, np.array([[0.0, 0.0, -1.0]]), hts, 1.0, 0.0, 100.0, return_triangle=True)
+    assert abs(t[0] - (5.0 - (0.1 + 0.3 * 0.3 + 0.4 * 0.6))) < 1e-14 and tri[0] == 0
+    t, tri = RR.hit_heightfield_brute(np.array([0.25, 0.3, 5.0]), np.array([[0.0, 0.0, -1.0]]), hts, 1.0, 0.0, 100.0, return_triangle=True)
+    assert abs(t[0] - (5.0 - (0.2 + 0.25 * 0.5 + 0.2 * 0.2))) < 1e-14 and tri[0] == 1
+    t = RR.hit_heightfield_brute(np.array([0.0, 0.0, 5.0]), np.array([[0.0, 0.0, -1.0]]), hts, 1.0, 0.0, 100.0, other_diagonal=True)
+    assert abs(t[0] - (5.0 - 0.5 * (0.1 + 0.2))) < 1e-14            # on the other diagonal: the mean of (0, 0) and (1, 1)
+    assert RR.hit_heightfield_brute(np.array([0.9, 0.0, 5.0]), np.array([[0.0, 0.0, -1.0]]), hts, 1.0, 0.0, 100.0)[0] == -1
+    assert RR.drop_heightfield_brute(-0.2, -0.1, 5.0, hts, 1.0, 10.0) == pytest.approx(0.1 + 0.09 + 0.24, abs=1e-14)
+    assert RR.drop_heightfield_brute(-0.2, -0.1, 5.0, hts, 1.0, 4.0) is None
+
+
+# ---- the shading reference against closed forms ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_shading_box_top_rolled_is_R_ez(dtype):
+    tol = 1e-12 if dtype is np.float64 else 1e-6
+    for roll, pitch, yaw in ((0.3, 0.0, 0.0), (0.3, -0.2, 0.7)):
+        R = RR.euler_to_mat(roll, pitch, yaw)
+        scene = dict(prims=[], planks=[[*R, 4.0, 0.0, 0.0]], plank_half=(0.5, 1.0, 0.2), plank_shape=0)
+        _, ids, sh = RR.render(scene, _cam(eye=(4.0, 0.0, 3.0), pitch=-90), W, H, dtype, shading=True)
+        n = R.reshape(3, 3)[:, 2]
+        assert ids[CJ, CI] == RR.ID_PLANK0 and sh["part"][CJ, CI] == 5 and np.abs(sh["normal"][CJ, CI] - n).max() < tol
+        want = np.array(RR.PLANK_RGB) * (0.35 + 0.65 * max(0.0, float(n @ np.array(RR.LIGHT)))) * 255
+        assert np.abs(sh["colour"][CJ, CI] - want).max() < 255 * 4 * tol
+    assert roll != 0 and abs(n[1]) > 0.1          # (a roll about x tips the normal towards -y: a swapped roll / pitch would tip it along x)
+    _, ids, sh = RR.render(scene, _cam(), W, H, dtype, shading=True)      # nothing hit at the corner: the background, unshaded
+    assert ids[0, 0] == -1 and sh["part"][0, 0] == RR.PART_NONE and np.allclose(sh["colour"][0, 0], np.array(RR.BG_RGB) * 255, rtol=1e-6)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_shading_triangle_normal_is_the_cross_product(dtype):
+    hts = np.array([[0.1, 0.4], [0.7, 0.2]])
+    scene = dict(prims=[], hf=(hts, 1.0))
+    V = {(i, j): np.array([i - 0.5, j - 0.5, hts[j, i]]) for i in (0, 1) for j in (0, 1)}
+    for (x, y), tri, (a, b, c) in (((-0.2, -0.1), 0, ((0, 0), (1, 0), (0, 1))), ((0.25, 0.3), 1, ((1, 1), (0, 1), (1, 0)))):
+        _, ids, sh = RR.render(scene, _cam(eye=(x, y, 5.0), pitch=-90), W, H, dtype, shading=True)
+        n = np.cross(V[b] - V[a], V[c] - V[a])
+        n /= np.linalg.norm(n)
+        assert n[2] > 0 and ids[CJ, CI] == RR.ID_HEIGHTFIELD and sh["part"][CJ, CI] == tri
+        assert np.abs(sh["normal"][CJ, CI] - n).max() < (1e-12 if dtype is np.float64 else 1e-6)
+
+
+def test_shading_checker_cylinder_and_capsule_parts():
+    scene = dict(prims=[], ground=True)
+    for (x, y), parity in (((0.5, 0.5), 0), ((1.5, 0.5), 1), ((-0.5, 0.5), 1), ((-0.5, -0.5), 0), ((2.5, -1.5), 0), ((2.5, -0.5), 1)):
+        _, ids, sh = RR.render(scene, _cam(eye=(x, y, 2.0), pitch=-90), W, H, np.float64, shading=True)
+        assert ids[CJ, CI] == RR.ID_GROUND and sh["part"][CJ, CI] == parity
+        assert np.allclose(sh["colour"][CJ, CI], np.array(RR.GROUND_RGB[parity]) * (0.35 + 0.65 * 0.8) * 255, rtol=1e-12)
+    pillar = dict(prims=[], planks=[[*np.eye(3).ravel(), 4.0, 0.0, 0.0]], plank_half=(0.5, 0.5, 0.2), plank_shape=1)
+    _, _, sh = RR.render(pillar, _cam(), W, H, np.float64, shading=True)
+    assert sh["part"][CJ, CI] == 0 and np.allclose(sh["normal"][CJ, CI], (-1, 0, 0), atol=1e-7)
+    _, _, sh = RR.render(pillar, _cam(eye=(4.2, 0.1, 3.0), pitch=-90), W, H, np.float64, shading=True)
+    assert sh["part"][CJ, CI] == 1 and np.allclose(sh["normal"][CJ, CI], (0, 0, 1), atol=1e-12)
+    _, _, sh = RR.render(pillar, _cam(eye=(4.2, 0.1, -3.0), pitch=90), W, H, np.float64, shading=True)
+    assert sh["part"][CJ, CI] == 2 and np.allclose(sh["normal"][CJ, CI], (0, 0, -1), atol=1e-12)
+    side_on = dict(prims=[_prim((2.5, -1.0, 0), (2.5, 1.0, 0), 0.25, 2, 1)])
+    _, _, sh = RR.render(side_on, _cam(), W, H, np.float64, shading=True)
+    assert sh["part"][CJ, CI] == 2 and np.allclose(sh["normal"][CJ, CI], (-1, 0, 0), atol=1e-7)
+    ids = np.zeros((5, 5), np.int32)
+    part = np.zeros((5, 5), np.int64)
+    part[:, 3:] = 1
+    assert not RR.edge_mask(ids).any() and RR.edge_mask(ids, part).sum() == 10 and not RR.edge_mask(ids, part)[:, [0, 1, 4]].any()
+
+
+# ---- negative controls: the comparison's own rule must tell a wrong frame from the right one -------------------------------------
+@pytest.mark.parametrize("name,mutation,e,where", RR.control_cases())
+def test_the_rule_rejects_a_mutated_reference(name, mutation, e, where):
+    """The float32 reference of the TRUE scene passes the GPU comparison's rule against the true float64 reference and fails it against a
+    float64 reference whose plank rotation is transposed, whose roll and pitch are swapped, whose COM offset turns with the plank, or
+    whose cells are split along the other diagonal."""
+    rec = RR.synthetic_records(name)
+    model, task_id, kw, st, tk, ter, hf = rec
+    w, h = RR.CONTROL_SIZE
+    cam = RR.new_cameras("planner" if name == "planner" else "plank", st[e, 0:3], w / h, hf, where)[RR.CONTROL_CAMERA]
+    scene = RR.reference_scene(model, task_id, st, tk, ter, hf, env=e)
+    d64, i64 = RR.render(scene, cam, w, h, np.float64)
+    d32, i32 = RR.render(scene, cam, w, h, np.float32)
+    assert RR.accepts(d32, i32, d64, i64, d32, cam[15])[0]
+    ok, fig = RR.accepts(d32, i32, *RR.mutated_references(mutation, rec, e, cam, w, h), cam[15])
+    print(name, mutation, fig)
+    assert not ok, (name, mutation, fig)
+    if mutation in RR.HF_MUTATIONS:          # the same view of the same hills: it is the depth of the other split that is rejected, not the picture
+        assert fig["id_mismatches"] <= 0.001 * fig["compared"] and fig["kernel_depth_err"] > 100 * fig["numpy_f32_depth_err"], fig
+
+
+def test_the_rule_rejects_exchanged_cameras():
+    for name in ("stress_box", "planner"):
+        model, task_id, kw, st, tk, ter, hf = RR.synthetic_records(name)
+        kind, where = ("planner", "hills") if name == "planner" else ("plank", None)
+        cams = RR.new_cameras(kind, st[0, 0:3], 160 / 120, hf, where)
+        scene = RR.reference_scene(model, task_id, st, tk, ter, hf, env=0)
+        a, b = cams["follow"], cams["oblique"]
+        d32, i32 = RR.render(scene, a, 160, 120, np.float32)
+        d64, i64 = RR.render(scene, b, 160, 120, np.float64)
+        assert not RR.accepts(d32, i32, d64, i64, RR.render(scene, b, 160, 120, np.float32)[0], b[15])[0]
