@@ -359,6 +359,43 @@ int mocca_set_height_scan(mocca_handle h, const float *points_host, int n_points
 int mocca_scan_dim(mocca_handle h);
 int mocca_height_scan(mocca_handle h, float *out_dev, int row_stride, const float *obs_dev, void *stream);
 
+/* ---- the trainer's own policy on the device (no reference counterpart: the reference's trainers, README.md:33-39, run their
+ *      pytorch-a2c-ppo-acktr `actor_critic.act()` in torch, four small kernels and a sampler per step) ---- */
+
+/* A diagonal-Gaussian actor-critic: an actor MLP (the mean), a critic MLP, a state-independent log_std[act_dim] and, optionally, the
+ * observation normalisation x = clamp((x - mean[k]) * inv_std[k], -clip, +clip) (VecNormalize; inv_std = 1 / sqrt(var + eps), formed by the
+ * caller in f32) in front of both nets.  Layout, arithmetic and the noise: mocca_envs_amd/csrc/mocca_policy.h.
+ *
+ * mocca_set_policy      replaces building the trainer's `Policy(obs_shape, action_space)`: SHAPES only.  layers_host [n_layers_total][8] i32 (HOST
+ *                       memory), the rows of mocca_set_base_controller -- {net 0 actor / 1 critic, in, out, in rounded up to a multiple of 16, out
+ *                       rounded up likewise, activation (0 identity, 1 relu, 2 tanh, 3 softsign), ignored, ignored} --, the actor's layers first.
+ *                       At most 8 layers per net; a net's first layer takes in_dim inputs (1 .. 336); hidden widths multiples of 16 up to 256;
+ *                       the actor ends in act_dim (1 .. 32) outputs, the critic in 1; clip finite and > 0.  Every dimension is checked
+ *                       (MOCCA_E_ARG with a message).  Allocates the kernel's image; layers_host == NULL detaches.  May synchronise.
+ * mocca_update_policy   replaces nothing in the trainer -- it is what makes `optimizer.step()` visible to the kernel: call it once per PPO
+ *                       iteration.  params_dev [n_floats] f32 (DEVICE memory): per layer in table order W[out][in] row-major then b[out], then
+ *                       log_std[act_dim]; optionally mean[in_dim] and inv_std[in_dim] follow (n_floats tells which; without them the input is
+ *                       not normalised).  One repack kernel on `stream` writes the image; no synchronisation, no host read: inside or between
+ *                       replays of a captured graph the next mocca_act on the stream sees the new parameters.
+ * mocca_act             replaces `value, action, action_log_prob = actor_critic.act(obs)`: one launch.  in_dev [N][in_stride] f32, the first
+ *                       in_dim floats of each row are read (rollouts.obs[t], or a wider [obs | scan] row).  eps_dev [N][act_dim] f32 or NULL;
+ *                       deterministic != 0: action = mean; both off: noise drawn in the kernel from (seed, global env id, the env's step and
+ *                       episode counters) -- two calls without a mocca_step in between draw the same noise.  Outputs: action_dev [N][act_dim]
+ *                       (not clipped: apply_action clips), logp_dev [N] or NULL (sum over j of -eps^2 / 2 - log_std - log(2 pi) / 2), value_dev
+ *                       [N] or NULL, mean_dev [N][act_dim] or NULL.  No allocation, no synchronisation, no atomics, no host state.
+ * mocca_act_step        replaces `act()` followed by `envs.step(action)`: mocca_act, then mocca_step on action_dev, on the same stream; the
+ *                       step's results are mocca_step's bit for bit, and the pair is capturable in a hipGraph under mocca_step's conditions.
+ * Errors (MOCCA_E_ARG, with a message): a NULL handle, any bad dimension, mocca_update_policy / mocca_act before mocca_set_policy, mocca_act
+ * before mocca_update_policy, n_floats that fits neither form, in_stride < in_dim, mocca_act_step with act_dim other than the env's, global env
+ * ids (MOCCA_PARAM_ENV_OFFSET + n_envs) beyond 2^28 (the noise's counter holds 16 x env id in one 32-bit word). */
+int mocca_set_policy(mocca_handle h, const int32_t *layers_host, int n_layers_total, int in_dim, int act_dim, double clip);
+int mocca_update_policy(mocca_handle h, const float *params_dev, size_t n_floats, void *stream);
+int mocca_act(mocca_handle h, const float *in_dev, int in_stride, const float *eps_dev, int deterministic, float *action_dev, float *logp_dev,
+              float *value_dev, float *mean_dev, void *stream);
+int mocca_act_step(mocca_handle h, const float *in_dev, int in_stride, const float *eps_dev, int deterministic, float *action_dev,
+                   float *logp_dev, float *value_dev, float *mean_dev, float *obs_dev, float *rew_dev, uint8_t *done_dev, int32_t *info_dev,
+                   void *stream);
+
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */
 int mocca_kernel_info(mocca_handle h, int *vgprs, int *sgprs, int *lds_bytes, int *scratch_bytes, int *max_blocks_per_cu);

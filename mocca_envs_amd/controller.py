@@ -56,6 +56,24 @@ def _apply(net, x):
     return x
 
 
+def layers_from_sequential(seq, which):
+    """a torch.nn.Sequential of Linear, each followed by at most one of ReLU / Tanh / Softsign -> [(W, b, activation)]; any other module
+    is a ValueError"""
+    from torch import nn
+    names = ((nn.ReLU, "relu"), (nn.Tanh, "tanh"), (nn.Softsign, "softsign"))
+    out = []
+    for mod in seq:
+        act = next((n for t, n in names if isinstance(mod, t)), None)
+        if isinstance(mod, nn.Linear):
+            bias = np.zeros(mod.out_features, np.float32) if mod.bias is None else mod.bias.detach().cpu().numpy()
+            out.append((mod.weight.detach().cpu().numpy(), bias, "identity"))
+        elif act is not None and out and out[-1][2] == "identity":
+            out[-1] = out[-1][:2] + (act,)
+        else:
+            raise ValueError(f"{which}: {type(mod).__name__} is not supported here (Linear, then at most one of ReLU / Tanh / Softsign)")
+    return out
+
+
 class BaseController:
     def __init__(self, actor, critic):
         self.actor = _net(actor, ACTION_DIM, "actor")
@@ -66,23 +84,7 @@ class BaseController:
     @classmethod
     def from_torch(cls, actor_seq, critic_seq):
         """from two torch.nn.Sequential of Linear / ReLU / Tanh / Softsign; any other module is a ValueError"""
-        from torch import nn
-        names = ((nn.ReLU, "relu"), (nn.Tanh, "tanh"), (nn.Softsign, "softsign"))
-
-        def convert(seq, which):
-            out = []
-            for mod in seq:
-                act = next((n for t, n in names if isinstance(mod, t)), None)
-                if isinstance(mod, nn.Linear):
-                    bias = np.zeros(mod.out_features, np.float32) if mod.bias is None else mod.bias.detach().cpu().numpy()
-                    out.append((mod.weight.detach().cpu().numpy(), bias, "identity"))
-                elif act is not None and out and out[-1][2] == "identity":
-                    out[-1] = out[-1][:2] + (act,)
-                else:
-                    raise ValueError(f"{which}: {type(mod).__name__} is not supported here (Linear, then at most one of ReLU / Tanh / Softsign)")
-            return out
-
-        return cls(convert(actor_seq, "actor"), convert(critic_seq, "critic"))
+        return cls(layers_from_sequential(actor_seq, "actor"), layers_from_sequential(critic_seq, "critic"))
 
     # ---- files: one .npz, arrays "<net>/<i>/W", "<net>/<i>/b" and the activation names "<net>/act" ----
     def save_npz(self, path):

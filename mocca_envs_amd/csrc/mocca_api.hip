@@ -12,6 +12,7 @@
 #include "mocca.h"
 #include "mocca_controller.h"
 #include "mocca_kernels.h"
+#include "mocca_policy.h"
 #include "mocca_render.h"
 #include "mocca_scan.h"
 
@@ -121,6 +122,13 @@ struct mocca_ctx {
   float* d_robot_state = nullptr;    // [N][ROBOT_STATE_STRIDE] the controller's next input (StepArgs.robot_state)
   float* d_base_act = nullptr;       // [N][21] the actor's output of the last mocca_plan_step
   float* d_base_val = nullptr;       // [N] the critic's
+  // a trainer's policy (mocca_set_policy), owned by the handle
+  float* d_pol_image = nullptr;      // the kernel's image (mocca_policy.h)
+  int32_t* d_pol_layers = nullptr;
+  mocca_pol::PolicyArgs pol{};       // shapes and image offsets; the per-call pointers are filled by mocca_act
+  mocca_pol::RepackArgs pol_repack{};   // rows of the repack kernel; src offsets in the caller's flat parameters
+  size_t pol_n_base = 0;             // floats of mocca_update_policy's params_dev without the normalisation arrays
+  bool pol_filled = false;           // mocca_update_policy has run since mocca_set_policy
   std::string err;
 };
 static_assert(ROBOT_STATE_STRIDE == mocca_ctrl::CTRL_RS_STRIDE, "the step kernels and the controller kernel share the robot_state buffer");
@@ -357,6 +365,8 @@ int mocca_destroy(mocca_handle h) {
   if (h->d_robot_state) (void)hipFree(h->d_robot_state);
   if (h->d_base_act) (void)hipFree(h->d_base_act);
   if (h->d_base_val) (void)hipFree(h->d_base_val);
+  if (h->d_pol_image) (void)hipFree(h->d_pol_image);
+  if (h->d_pol_layers) (void)hipFree(h->d_pol_layers);
   delete h;
   return MOCCA_OK;
 }
@@ -962,6 +972,163 @@ int mocca_height_scan(mocca_handle h, float* out_dev, int row_stride, const floa
   mocca_scan::launch_height_scan((hipStream_t)stream, a, h->n_envs);
   HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
+}
+
+int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) {
+  using namespace mocca_ctrl;
+  using namespace mocca_pol;
+  if (!h) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  if (!layers_host) {   // detach
+    if (h->d_pol_image) HIP_TRY(h, hipDeviceSynchronize());   // a launch in flight may still read it
+    if (h->d_pol_image) (void)hipFree(h->d_pol_image);
+    if (h->d_pol_layers) (void)hipFree(h->d_pol_layers);
+    h->d_pol_image = nullptr; h->d_pol_layers = nullptr; h->pol_filled = false;
+    return MOCCA_OK;
+  }
+  auto bad = [&](const std::string& what) { h->err = "mocca_set_policy: " + what; return MOCCA_E_ARG; };
+  if (n_layers_total < 2 || n_layers_total > 2 * POL_MAX_LAYERS) return bad("needs 1 .. 8 layers for each of the two nets");
+  if (in_dim < 1 || in_dim > POL_MAX_IN) return bad("in_dim must be 1 .. " + std::to_string(POL_MAX_IN));
+  if (act_dim < 1 || act_dim > POL_MAX_ACTION) return bad("act_dim must be 1 .. " + std::to_string(POL_MAX_ACTION));
+  if (!std::isfinite(clip) || !(clip > 0.0)) return bad("clip must be finite and positive");
+  const int in_pad = (in_dim + 15) / 16 * 16;
+  int count[2] = {0, 0}, prev_out = 0;
+  for (int i = 0; i < n_layers_total; ++i) {
+    const int32_t* r = layers_host + (size_t)i * CTRL_LAYER_WORDS;
+    const std::string at = "layer " + std::to_string(i) + ": ";
+    const int net = r[CL_NET];
+    if (net != 0 && net != 1) return bad(at + "net must be 0 (actor) or 1 (critic)");
+    if (i > 0 && net < layers_host[(size_t)(i - 1) * CTRL_LAYER_WORDS + CL_NET]) return bad(at + "the actor's layers come first, then the critic's");
+    const bool first = count[net] == 0;
+    if (++count[net] > POL_MAX_LAYERS) return bad(at + "more than 8 layers in one net");
+    const int in = r[CL_IN], out = r[CL_OUT];
+    if (first && in != in_dim) return bad(at + "a net's first layer takes in_dim = " + std::to_string(in_dim) + " inputs, not " + std::to_string(in));
+    if (!first && in != prev_out) return bad(at + "input width differs from the previous layer's output");
+    if (out < 1 || out > POL_MAX_WIDTH) return bad(at + "widths must be 1 .. 256");
+    if (r[CL_IN_PAD] != (in + 15) / 16 * 16 || r[CL_OUT_PAD] != (out + 15) / 16 * 16) return bad(at + "in_pad / out_pad must be the widths rounded up to a multiple of 16");
+    if (r[CL_ACT] < CTRL_ACT_IDENTITY || r[CL_ACT] > CTRL_ACT_SOFTSIGN) return bad(at + "unknown activation");
+    prev_out = out;
+    const bool last = i + 1 == n_layers_total || layers_host[(size_t)(i + 1) * CTRL_LAYER_WORDS + CL_NET] != net;
+    if (last && out != (net == 0 ? act_dim : 1)) return bad(at + "the actor ends in act_dim = " + std::to_string(act_dim) + " outputs, the critic in 1");
+    if (!last && (out & 15)) return bad(at + "hidden widths must be multiples of 16");
+  }
+  if (count[0] < 1 || count[1] < 1) return bad("needs an actor and a critic");
+  // the image (mocca_policy.h) and the rows that tell the repack kernel where each piece of the caller's flat parameters goes
+  std::vector<int32_t> table(layers_host, layers_host + (size_t)n_layers_total * CTRL_LAYER_WORDS);
+  RepackArgs rp{};
+  int pos = 0, src = 0, nr = 0;
+  auto row = [&](int floats, int src_off, int in, int out, int ipad, float fill) {
+    RepackRow& q = rp.rows[nr++];
+    q.dst = pos; q.dst_end = pos + floats; q.src = src_off; q.in = in; q.out = out; q.in_pad = ipad; q.fill = fill;
+    pos += floats;
+    return q.dst;
+  };
+  for (int i = 0; i < n_layers_total; ++i) {
+    int32_t* r = &table[(size_t)i * CTRL_LAYER_WORDS];
+    const int in = r[CL_IN], out = r[CL_OUT];
+    r[CL_W_OFF] = row(r[CL_IN_PAD] * r[CL_OUT_PAD], src, in, out, r[CL_IN_PAD], 0.0f);
+    src += in * out;
+    r[CL_B_OFF] = row(r[CL_OUT_PAD], src, 0, out, 0, 0.0f);
+    src += out;
+  }
+  PolicyArgs pa{};
+  pa.log_std_off = row(POL_MAX_ACTION, src, 0, act_dim, 0, 0.0f);
+  src += act_dim;
+  pa.flags_off = row(POL_FLAG_WORDS, -1, 0, 1, 0, 0.0f);        // (rows nr - 3 .. nr - 1: mocca_update_policy sets their source per call)
+  pa.mean_off = row(in_pad, -1, 0, in_dim, 0, 0.0f);
+  pa.inv_std_off = row(in_pad, -1, 0, in_dim, 0, 0.0f);
+  rp.n_rows = nr; rp.image_floats = pos;
+  float* d_p = nullptr;
+  int32_t* d_l = nullptr;
+  const size_t lbytes = table.size() * sizeof(int32_t);
+  hipError_t e = hipMalloc(&d_p, (size_t)pos * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&d_l, lbytes);
+  if (e == hipSuccess) e = hipMemset(d_p, 0, (size_t)pos * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d_l, table.data(), lbytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // no launch in flight still reads the old policy
+  if (e != hipSuccess) {
+    if (d_p) (void)hipFree(d_p);
+    if (d_l) (void)hipFree(d_l);
+    h->err = std::string("mocca_set_policy: ") + hipGetErrorString(e);
+    return MOCCA_E_HIP;
+  }
+  if (h->d_pol_image) (void)hipFree(h->d_pol_image);
+  if (h->d_pol_layers) (void)hipFree(h->d_pol_layers);
+  h->d_pol_image = d_p; h->d_pol_layers = d_l;
+  pa.params = d_p; pa.layers = d_l; pa.n_actor = count[0]; pa.n_critic = count[1];
+  pa.in_dim = in_dim; pa.in_pad = in_pad; pa.act_dim = act_dim; pa.clip = (float)clip;
+  rp.image = d_p;
+  h->pol = pa; h->pol_repack = rp; h->pol_n_base = (size_t)src; h->pol_filled = false;
+  return MOCCA_OK;
+}
+
+int mocca_update_policy(mocca_handle h, const float* params_dev, size_t n_floats, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (!h->d_pol_image) { h->err = "mocca_update_policy needs a policy (mocca_set_policy)"; return MOCCA_E_ARG; }
+  if (!params_dev) { h->err = "mocca_update_policy: params_dev must not be NULL"; return MOCCA_E_ARG; }
+  const size_t base = h->pol_n_base, in_dim = (size_t)h->pol.in_dim;
+  if (n_floats != base && n_floats != base + 2 * in_dim) {
+    h->err = "mocca_update_policy: this policy takes " + std::to_string(base) + " floats (layers, log_std), or " + std::to_string(base + 2 * in_dim) +
+             " with mean and inv_std, not " + std::to_string(n_floats);
+    return MOCCA_E_ARG;
+  }
+  DeviceGuard guard(h->device);
+  mocca_pol::RepackArgs rp = h->pol_repack;
+  rp.src = params_dev;
+  const bool norm = n_floats != base;
+  rp.rows[rp.n_rows - 3].fill = norm ? 1.0f : 0.0f;
+  rp.rows[rp.n_rows - 2].src = norm ? (int32_t)base : -1;
+  rp.rows[rp.n_rows - 1].src = norm ? (int32_t)(base + in_dim) : -1;
+  mocca_pol::launch_repack((hipStream_t)stream, rp);
+  HIP_TRY(h, hipGetLastError());
+  h->pol_filled = true;
+  return MOCCA_OK;
+}
+
+// the policy kernel's launch of mocca_act / mocca_act_step; the handle's device is current
+static int launch_act(mocca_handle h, const char* who, const float* in_dev, int in_stride, const float* eps_dev, int deterministic, float* action_dev,
+                      float* logp_dev, float* value_dev, float* mean_dev, hipStream_t s) {
+  if (!h->d_pol_image || !h->pol_filled) {
+    h->err = std::string(who) + " needs a policy (mocca_set_policy, then mocca_update_policy)"; return MOCCA_E_ARG;
+  }
+  if (!in_dev || !action_dev) { h->err = std::string(who) + ": in_dev and action_dev must not be NULL"; return MOCCA_E_ARG; }
+  if (in_stride < h->pol.in_dim) {
+    h->err = std::string(who) + ": in_stride " + std::to_string(in_stride) + " is smaller than the policy's in_dim (" + std::to_string(h->pol.in_dim) + ")";
+    return MOCCA_E_ARG;
+  }
+  if ((long long)h->env_offset + h->n_envs > (1ll << 28) || h->env_offset < 0) {
+    h->err = std::string(who) + ": the noise is keyed by global env ids below 2^28 (MOCCA_PARAM_ENV_OFFSET + n_envs)"; return MOCCA_E_ARG;
+  }
+  mocca_pol::PolicyArgs a = h->pol;
+  a.in = in_dev; a.in_stride = in_stride; a.eps = eps_dev; a.deterministic = deterministic != 0;
+  a.task = h->d_task; a.task_words = MOCCA_TASK_WORDS; a.tw_t = MOCCA_TW_T; a.tw_episode = MOCCA_TW_EPISODE;
+  a.env_offset = h->env_offset; a.seed_lo = (uint32_t)h->seed; a.seed_hi = (uint32_t)(h->seed >> 32);
+  a.action = action_dev; a.logp = logp_dev; a.value = value_dev; a.mean = mean_dev; a.n_envs = h->n_envs;
+  mocca_pol::launch_policy(s, a);
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
+}
+
+int mocca_act(mocca_handle h, const float* in_dev, int in_stride, const float* eps_dev, int deterministic, float* action_dev, float* logp_dev,
+              float* value_dev, float* mean_dev, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  return launch_act(h, "mocca_act", in_dev, in_stride, eps_dev, deterministic, action_dev, logp_dev, value_dev, mean_dev, (hipStream_t)stream);
+}
+
+int mocca_act_step(mocca_handle h, const float* in_dev, int in_stride, const float* eps_dev, int deterministic, float* action_dev, float* logp_dev,
+                   float* value_dev, float* mean_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev, int32_t* info_dev, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (!obs_dev || !rew_dev || !done_dev) { h->err = "mocca_act_step: obs_dev, rew_dev and done_dev must not be NULL"; return MOCCA_E_ARG; }
+  if (h->d_pol_image && h->pol.act_dim != mocca_act_dim(h)) {
+    h->err = "mocca_act_step: the policy's act_dim (" + std::to_string(h->pol.act_dim) + ") is not the env's (" + std::to_string(mocca_act_dim(h)) + ")";
+    return MOCCA_E_ARG;
+  }
+  if (need_trajectory(h) != MOCCA_OK) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = launch_act(h, "mocca_act_step", in_dev, in_stride, eps_dev, deterministic, action_dev, logp_dev, value_dev, mean_dev, s)) return rc;
+  return launch_step(h, action_dev, nullptr, obs_dev, rew_dev, done_dev, info_dev, s);
 }
 
 #ifdef MOCCA_STAMPS

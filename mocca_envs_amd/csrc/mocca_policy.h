@@ -1,0 +1,83 @@
+// mocca_policy.h -- layout of a trainer's Gaussian actor-critic as the policy kernel reads it (mocca_policy.hip), and the host-side launchers.
+// mocca_set_policy (mocca_api.hip) checks the caller's shapes and sizes this image; mocca_update_policy fills it from plain row-major
+// parameters on the device (one repack kernel); mocca_act / mocca_act_step launch the kernel.
+//
+// The policy of a SymmetricRL / ALLSTEPS / a2c-ppo-acktr trainer: a diagonal-Gaussian actor (an MLP that gives the mean, a state-independent
+// log_std), a critic MLP over the same input, and optionally a running observation normalisation in front of both.
+//
+// Layer table: the controller's (mocca_controller.h): n_layers_total rows of CTRL_LAYER_WORDS int32, the actor's layers first, then the
+// critic's; w_off / b_off point into the image below.
+// Image: one f32 array.
+//   per layer   weights [out_pad / 16][in_pad / 16][64][4] in MFMA fragment order, then bias [out_pad] -- exactly the controller's layout
+//   log_std     [POL_MAX_ACTION], zeros past act_dim
+//   flags       [4]: flags[0] != 0: normalise the input (the repack kernel sets it when the caller's parameters carry mean / inv_std -- a
+//               DEVICE word, so that an update between two replays of a captured launch switches it without a recapture)
+//   mean        [in_pad], zeros past in_dim
+//   inv_std     [in_pad], zeros past in_dim        x = clamp((x - mean[k]) * inv_std[k], -clip, +clip), f32, in that operation order
+//
+// Noise.  mocca_act has three modes: deterministic (eps = 0: the action is the mean), caller noise (eps_dev [N][act_dim]) and, the default,
+// noise drawn in the kernel: Philox4x32-10 under the handle's seed key with the counter
+//     ( 16 * env + (j >> 1),  task word MOCCA_TW_T,  task word MOCCA_TW_EPISODE,  1 )
+// env = MOCCA_PARAM_ENV_OFFSET + index: the GLOBAL env id; the fourth word is 1 where the env's own draws (mocca_device.h rng_uniform) use 0,
+// so the two streams never collide; word 0 is 32 bits wide, so global env ids stay below 2^28 (mocca_act refuses a handle whose ids reach it).
+// Output words 0 and 1 give u1 = ((w0 >> 8) + 1) / 2^24 in (0, 1] and u2 = (w1 >> 8) / 2^24 in [0, 1);
+// Box-Muller, r = sqrt(-2 log u1), gives eps[2 (j >> 1)] = r cos(2 pi u2) and eps[2 (j >> 1) + 1] = r sin(2 pi u2).  The noise is a function
+// of device state only (seed, env id, the env's step and episode counters): the kernel keeps no host state and can be captured; a shard
+// reproduces its rows of the whole batch; restoring state and task replays the noise.  CONSEQUENCE: two mocca_act calls without a
+// mocca_step in between draw the SAME noise (the step counter has not moved).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mocca_controller.h"
+
+namespace mocca_pol {
+
+using mocca_ctrl::CTRL_LAYER_WORDS;
+constexpr int POL_MAX_IN = 336;       // input floats after padding to 16: obs_dim 36 .. 65, or [obs | scan] up to 65 + 256
+constexpr int POL_MAX_ACTION = 32;    // actor head
+constexpr int POL_MAX_WIDTH = mocca_ctrl::CTRL_MAX_WIDTH, POL_MAX_LAYERS = mocca_ctrl::CTRL_MAX_LAYERS;
+constexpr int POL_FLAG_WORDS = 4;
+constexpr int POL_TILE = 16;          // envs per workgroup (the controller measured 16 as best: profiles/HISTORY.md)
+
+struct PolicyArgs {
+  const float* params;          // device: the image
+  const int32_t* layers;        // device, [n_actor + n_critic][CTRL_LAYER_WORDS]
+  int n_actor, n_critic;
+  int log_std_off, flags_off, mean_off, inv_std_off;   // float offsets into the image
+  const float* in;              // [N][in_stride], the first in_dim floats of a row are read
+  int in_stride, in_dim, in_pad, act_dim;
+  float clip;
+  const float* eps;             // [N][act_dim] caller noise, or null
+  int deterministic;
+  const uint32_t* task;         // the handle's task records (MOCCA_TW_T, MOCCA_TW_EPISODE), read only for in-kernel noise
+  int task_words, tw_t, tw_episode;
+  int env_offset;
+  uint32_t seed_lo, seed_hi;
+  float* action;                // [N][act_dim], not clipped (apply_action clips; a2c-ppo-acktr stores the raw sample)
+  float* logp;                  // [N] or null
+  float* value;                 // [N] or null: the critic's workgroups are not launched
+  float* mean;                  // [N][act_dim] or null
+  int n_envs;
+};
+
+// one row of the repack kernel's table, one per layer and one per tail array (log_std, mean, inv_std: out = 1 row, no fragment order)
+struct RepackRow {
+  int32_t dst, dst_end;         // image range [dst, dst_end)
+  int32_t src;                  // offset in the caller's parameters, < 0: the first `out` floats are `fill`, the rest zeros
+  int32_t in, out, in_pad;      // weights: W[out][in] -> fragment order over in_pad columns; in_pad = 0: a plain array of `out` floats, zero padded
+  float fill;
+  int32_t pad_;
+};
+constexpr int POL_MAX_REPACK_ROWS = 4 * POL_MAX_LAYERS + 4;   // weights + bias of 16 layers, log_std, flags, mean, inv_std
+struct RepackArgs {
+  const float* src;
+  float* image;
+  int n_rows, image_floats;
+  RepackRow rows[POL_MAX_REPACK_ROWS];
+};
+
+void launch_policy(hipStream_t s, const PolicyArgs& a);
+void launch_repack(hipStream_t s, const RepackArgs& a);
+
+}  // namespace mocca_pol

@@ -1,0 +1,219 @@
+// mocca_policy.hip -- a trainer's Gaussian actor-critic on the device: observation normalisation, actor and critic MLPs, the action sample,
+// its log-probability and the value for all N envs in ONE launch (mocca_act; mocca_act_step runs it ahead of the step kernel).  Layout of the
+// parameters and the keying of the in-kernel noise: mocca_policy.h.
+//
+// Arithmetic: the controller kernel's contract (mocca_controller.hip).  f32 in, f32 accumulate on the matrix cores
+// (v_mfma_f32_16x16x4_f32); an output is the sum of FOUR partial sums, one accumulator per MFMA j of a 16-wide k-group (the k with
+// k mod 4 = j), each in ascending k, added as (p0 + p1) + (p2 + p3) ahead of the bias and the activation.  The layer loop below is that
+// kernel's, restated over a wider LDS row (the input may be [obs | scan], up to 336 floats): mocca_controller.hip itself is left as it is
+// (profiles/kernel_resources_policy.md).
+//
+// A workgroup of four waves owns POL_TILE envs of ONE net (blockIdx.y: 0 actor, 1 critic).  The activations of the tile stay in LDS from the
+// normalised input to the head, X[env][feature], two buffers; the weights stream from L2 in fragment order.  The head's outputs go to LDS
+// like a hidden layer's; then ONE lane per env forms, in ascending j,
+//     action[j] = mean[j] + exp(log_std[j]) * eps[j]            logp = sum_j ( -1/2 eps[j]^2 - log_std[j] - 1/2 log 2 pi )
+// (actor workgroups) or stores the value (critic workgroups).  The in-kernel noise of the tile is drawn by all 256 lanes (16 envs x 16 Philox
+// blocks of two normals) ahead of the layers.  The order of every sum is fixed and does not depend on N: same inputs -> same bits.  No
+// atomics, no host state.
+#include <hip/hip_runtime.h>
+
+#include "mocca_policy.h"
+
+namespace mocca_pol {
+
+using namespace mocca_ctrl;   // CL_*, CTRL_ACT_*
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int LDS_STRIDE = POL_MAX_IN + 4;   // floats per env row: 16-byte aligned rows, rows 0..7 start on different bank groups (340 = 20 mod 32)
+constexpr int NP = 4;                        // partial sums per output
+constexpr int NT = 4;                        // output tiles per wave: 16 tiles of 16 rows (width 256) over 4 waves
+constexpr int TILE = POL_TILE;
+static_assert(TILE == 16, "one 16-env MFMA sub-tile per workgroup; the noise stage deals 16 envs x 16 Philox blocks to 256 lanes");
+static_assert(POL_MAX_WIDTH <= POL_MAX_IN && POL_MAX_ACTION <= 32, "LDS rows hold the widest layer; 16 Philox blocks give 32 normals");
+
+__device__ __forceinline__ float activate(float x, int act) {
+  switch (act) {
+    case CTRL_ACT_RELU: return fmaxf(x, 0.0f);
+    case CTRL_ACT_TANH: return tanhf(x);
+    case CTRL_ACT_SOFTSIGN: return x / (1.0f + fabsf(x));
+    default: return x;
+  }
+}
+
+// Philox4x32-10 (the rounds of mocca_device.h philox4x32): words 0 and 1 of the block
+__device__ __forceinline__ void philox2(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t& o0, uint32_t& o1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  o0 = c0; o1 = c1;
+}
+
+__global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
+  __shared__ __attribute__((aligned(16))) float X[2][TILE * LDS_STRIDE];
+  __shared__ float Z[TILE * POL_MAX_ACTION];   // the tile's noise, Z[env][j]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int env0 = blockIdx.x * TILE, net = blockIdx.y;
+  const int col = lane & 15, quad = lane >> 4;
+
+  // input: the first in_dim floats of the env's row, normalised, zeros up to in_pad; rows past the batch are zeros (nothing of them is stored)
+  {
+    const bool norm = a.params[a.flags_off] != 0.0f;
+    const float *mu = a.params + a.mean_off, *is = a.params + a.inv_std_off;
+    for (int i = tid; i < TILE * a.in_pad; i += 256) {
+      const int e = i / a.in_pad, k = i - e * a.in_pad, env = env0 + e;
+      float v = 0.0f;
+      if (env < a.n_envs && k < a.in_dim) {
+        v = a.in[(size_t)env * a.in_stride + k];
+        if (norm) v = fminf(fmaxf((v - mu[k]) * is[k], -a.clip), a.clip);
+      }
+      X[0][e * LDS_STRIDE + k] = v;
+    }
+  }
+  // in-kernel noise (header: Noise): lane (env e = tid / 16, block p = tid % 16) draws the normals 2 p and 2 p + 1 of env e
+  if (net == 0 && !a.deterministic && !a.eps) {
+    const int e = tid >> 4, p = tid & 15, env = env0 + e;
+    if (env < a.n_envs && 2 * p < a.act_dim) {
+      const uint32_t* tk = a.task + (size_t)env * a.task_words;
+      uint32_t w0, w1;
+      philox2(16u * (uint32_t)(a.env_offset + env) + (uint32_t)p, tk[a.tw_t], tk[a.tw_episode], 1u, a.seed_lo, a.seed_hi, w0, w1);
+      const float u1 = (float)((w0 >> 8) + 1u) * (1.0f / 16777216.0f), u2 = (float)(w1 >> 8) * (1.0f / 16777216.0f);
+      const float r = sqrtf(-2.0f * logf(u1)), th = 6.28318530717958647692f * u2;
+      Z[e * POL_MAX_ACTION + 2 * p] = r * cosf(th);
+      Z[e * POL_MAX_ACTION + 2 * p + 1] = r * sinf(th);
+    }
+  }
+  __syncthreads();
+
+  const int first = net == 0 ? 0 : a.n_actor, count = net == 0 ? a.n_actor : a.n_critic;
+  int cur = 0;
+#pragma unroll 1
+  for (int li = 0; li < count; ++li) {
+    const int32_t* lr = a.layers + (size_t)(first + li) * CTRL_LAYER_WORDS;
+    const int nkg = lr[CL_IN_PAD] >> 4, n_ot = lr[CL_OUT_PAD] >> 4, act = lr[CL_ACT];
+    const f32x4* W = (const f32x4*)(a.params + lr[CL_W_OFF]);
+    const float* B = a.params + lr[CL_B_OFF];
+    const int nt_w = wave < n_ot ? (n_ot - wave + 3) >> 2 : 0;   // output tiles of this wave (wave-uniform)
+    const float* Xin = X[cur];
+    float* Xout = X[cur ^ 1];
+
+    f32x4 acc[NT][NP];   // [..][j]: the partial sum fed by MFMA j of every k-group
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int j = 0; j < NP; ++j) acc[t][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    if (nt_w > 0) {
+      // weight fragments of this wave's tiles at k-group kg (tiles past the wave's last re-read that one: loaded, never multiplied)
+      const f32x4* wp[NT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int ot = wave + 4 * (t < nt_w ? t : nt_w - 1);
+        wp[t] = W + (size_t)ot * nkg * 64 + lane;
+      }
+      // the weights come from L2: the fragments of k-groups kg + 1 and kg + 2 are in flight while kg multiplies
+      f32x4 w0[NT], w1[NT], w2[NT];
+      auto load = [&](f32x4 (&w)[NT], int kg) {
+        const int kc = kg < nkg ? kg : nkg - 1;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) w[t] = wp[t][(size_t)kc * 64];
+      };
+      auto multiply = [&](const f32x4 (&w)[NT], int kg) {
+        const f32x4 b = *(const f32x4*)&Xin[col * LDS_STRIDE + kg * 16 + quad * 4];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+          if (t < nt_w) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][j], b[j], acc[t][j], 0, 0, 0);
+          }
+      };
+      // three k-groups per trip: the three fragment sets rotate by name, not by register moves
+      load(w0, 0); load(w1, 1);
+#pragma unroll 1
+      for (int kg = 0; kg < nkg; kg += 3) {
+        load(w2, kg + 2); multiply(w0, kg);
+        if (kg + 1 >= nkg) break;
+        load(w0, kg + 3); multiply(w1, kg + 1);
+        if (kg + 2 >= nkg) break;
+        load(w1, kg + 4); multiply(w2, kg + 2);
+      }
+      // epilogue: lane holds rows 16 ot + 4 quad + 0..3 of env column `col`; bias, activation, then LDS (the next layer, or the head stage)
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+        if (t < nt_w) {
+          const int o = (wave + 4 * t) * 16 + quad * 4;
+          const f32x4 bias = *(const f32x4*)(B + o);
+          const f32x4 sum = (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]);
+          f32x4 y;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) y[r] = activate(sum[r] + bias[r], act);
+          *(f32x4*)&Xout[col * LDS_STRIDE + o] = y;
+        }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // head stage: one lane per env
+  const int env = env0 + tid;
+  if (tid >= TILE || env >= a.n_envs) return;
+  const float* head = &X[cur][tid * LDS_STRIDE];
+  if (net == 1) {
+    a.value[env] = head[0];
+    return;
+  }
+  const float* log_std = a.params + a.log_std_off;
+  const int A = a.act_dim;
+  float lp = 0.0f;
+  for (int j = 0; j < A; ++j) {
+    const float m = head[j], ls = log_std[j];
+    float e = 0.0f, act = m;
+    if (!a.deterministic) {
+      e = a.eps ? a.eps[(size_t)env * A + j] : Z[tid * POL_MAX_ACTION + j];
+      act = m + expf(ls) * e;
+    }
+    lp += (-0.5f * e) * e - ls - 0.91893853320467274178f;
+    a.action[(size_t)env * A + j] = act;
+    if (a.mean) a.mean[(size_t)env * A + j] = m;
+  }
+  if (a.logp) a.logp[env] = lp;
+}
+
+// plain row-major parameters -> the image (header: Image); one thread per image float
+__global__ __launch_bounds__(256) void repack_kernel(RepackArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.image_floats) return;
+  float v = 0.0f;
+  for (int r = 0; r < a.n_rows; ++r) {
+    const RepackRow& row = a.rows[r];
+    if (i < row.dst || i >= row.dst_end) continue;
+    const int idx = i - row.dst;
+    if (row.src < 0) { v = idx < row.out ? row.fill : 0.0f; break; }   // a constant in the first `out` floats
+    if (row.in_pad == 0) {   // a plain array, zero padded
+      v = idx < row.out ? a.src[row.src + idx] : 0.0f;
+      break;
+    }
+    // weights: [ot][kg][lane][4], the float4 of lane l in block (ot, kg) is W[16 ot + (l & 15)][16 kg + 4 (l >> 4) + 0..3]
+    const int nkg = row.in_pad >> 4;
+    const int ot = idx / (nkg * 256), rem = idx - ot * nkg * 256, kg = rem >> 8, l = (rem & 255) >> 2, j = rem & 3;
+    const int orow = 16 * ot + (l & 15), k = 16 * kg + 4 * (l >> 4) + j;
+    v = orow < row.out && k < row.in ? a.src[row.src + (size_t)orow * row.in + k] : 0.0f;
+    break;
+  }
+  a.image[i] = v;
+}
+
+void launch_policy(hipStream_t s, const PolicyArgs& a) {
+  hipLaunchKernelGGL(policy_kernel, dim3((a.n_envs + TILE - 1) / TILE, a.value ? 2 : 1), dim3(256), 0, s, a);
+}
+
+void launch_repack(hipStream_t s, const RepackArgs& a) {
+  hipLaunchKernelGGL(repack_kernel, dim3((a.image_floats + 255) / 256), dim3(256), 0, s, a);
+}
+
+}  // namespace mocca_pol

@@ -65,6 +65,10 @@ SYMBOLS = {
     "mocca_set_height_scan": (_i, [_vp, _vp, _i, _d, _d]),
     "mocca_scan_dim": (_i, [_vp]),
     "mocca_height_scan": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "mocca_set_policy": (_i, [_vp, _vp, _i, _i, _i, _d]),
+    "mocca_update_policy": (_i, [_vp, _vp, _sz, _vp]),
+    "mocca_act": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mocca_act_step": (_i, [_vp, _vp, _i, _vp, _i] + [_vp] * 9),
     "mocca_is_diagnostic_build": (_i, []),
     "mocca_kernel_info": (_i, [_vp] + [C.POINTER(_i)] * 5),
     "mocca_last_error": (C.c_char_p, [_vp]),

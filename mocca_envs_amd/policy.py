@@ -1,0 +1,171 @@
+"""`DevicePolicy`: a trainer's Gaussian actor-critic as one host object that both env surfaces take.
+
+The reference's trainers (SymmetricRL, ALLSTEPS: pytorch-a2c-ppo-acktr's `Policy`) act with a diagonal-Gaussian actor MLP, a critic MLP, a
+state-independent `log_std` and, optionally, a running observation normalisation.  A `DevicePolicy` holds those as plain numpy arrays:
+
+* `VecEnv.set_policy(p)` / `TorchVecEnv.attach_policy(p)` run it on the device, one launch in front of the step kernel
+  (`act`, `act_step`; include/mocca.h mocca_act); `update_policy` refreshes the weights once per PPO iteration;
+* the single-env gym classes call it: `p(obs[in_dim]) -> (action, logp, value, mean)`, float32 numpy.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .controller import ACTIVATIONS, MAX_LAYERS, MAX_WIDTH, _apply, _round16, layers_from_sequential
+
+MAX_IN, MAX_ACTION, FLAG_WORDS = 336, 32, 4       # csrc/mocca_policy.h POL_MAX_IN / POL_MAX_ACTION / POL_FLAG_WORDS
+HALF_LOG_2PI = 0.9189385332046727
+
+
+def _net(layers, in_dim, out_dim, name):
+    """validated copy of one net: [(W f32 [out][in], b f32 [out], activation)]"""
+    layers = list(layers)
+    if not 1 <= len(layers) <= MAX_LAYERS:
+        raise ValueError(f"{name}: between 1 and {MAX_LAYERS} layers")
+    net, fan_in = [], in_dim
+    for i, (w, b, act) in enumerate(layers):
+        w = np.array(w, dtype=np.float32, order="C")
+        b = np.array(b, dtype=np.float32).reshape(-1)
+        if act not in ACTIVATIONS:
+            raise ValueError(f"{name}[{i}]: unknown activation {act!r} (one of {ACTIVATIONS})")
+        if w.ndim != 2 or w.shape[1] != fan_in or b.size != w.shape[0]:
+            raise ValueError(f"{name}[{i}]: expected W[out][{fan_in}] and b[out]")
+        fan_in = w.shape[0]
+        if i + 1 == len(layers):
+            if fan_in != out_dim:
+                raise ValueError(f"{name}: the last layer has {fan_in} outputs, not {out_dim}")
+        elif fan_in % 16 or fan_in > MAX_WIDTH:
+            raise ValueError(f"{name}[{i}]: hidden width {fan_in} is not a multiple of 16 up to {MAX_WIDTH}")
+        net.append((w, b, act))
+    return net
+
+
+class DevicePolicy:
+    def __init__(self, actor, critic, log_std, obs_mean=None, obs_var=None, eps=1e-8, clip=10.0, inv_std=None):
+        actor = list(actor)
+        self.in_dim = int(np.shape(actor[0][0])[1])
+        self.log_std = np.array(log_std, dtype=np.float32).reshape(-1)
+        self.act_dim = int(self.log_std.size)
+        if not 1 <= self.in_dim <= MAX_IN or not 1 <= self.act_dim <= MAX_ACTION:
+            raise ValueError(f"in_dim must be 1 .. {MAX_IN} and act_dim 1 .. {MAX_ACTION}")
+        self.actor = _net(actor, self.in_dim, self.act_dim, "actor")
+        self.critic = _net(critic, self.in_dim, 1, "critic")
+        self.clip = float(clip)
+        if not (np.isfinite(self.clip) and self.clip > 0):
+            raise ValueError("clip must be finite and positive")
+        self.obs_mean = self.inv_std = None
+        if obs_mean is not None:
+            self.obs_mean = np.array(obs_mean, dtype=np.float32).reshape(-1)
+            if inv_std is None:     # 1 / sqrt(var + eps) in float32: what the kernel multiplies by
+                inv_std = np.float32(1) / np.sqrt(np.array(obs_var, dtype=np.float32).reshape(-1) + np.float32(eps))
+            self.inv_std = np.array(inv_std, dtype=np.float32).reshape(-1)
+            if self.obs_mean.size != self.in_dim or self.inv_std.size != self.in_dim:
+                raise ValueError(f"obs_mean / obs_var have {self.in_dim} entries")
+
+    @classmethod
+    def from_layers(cls, actor, critic, log_std, **kw):
+        """from layer lists [(W[out][in], b[out], activation)]; keywords as the constructor's"""
+        return cls(actor, critic, log_std, **kw)
+
+    @classmethod
+    def from_torch(cls, actor_seq, critic_seq, log_std, obs_mean=None, obs_var=None, eps=1e-8, clip=10.0):
+        """from two torch.nn.Sequential of Linear / ReLU / Tanh / Softsign (controller.BaseController.from_torch's grammar), the log_std
+        parameter and, optionally, the running observation statistics (tensors or arrays)"""
+        import torch
+        actor, critic = layers_from_sequential(actor_seq, "actor"), layers_from_sequential(critic_seq, "critic")
+        arr = lambda x: None if x is None else (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x))
+        return cls(actor, critic, arr(log_std), obs_mean=arr(obs_mean), obs_var=arr(obs_var), eps=eps, clip=clip)
+
+    @classmethod
+    def from_npz(cls, path, clip=10.0, eps=1e-8):
+        """tools/ppo_demo.py's <out>_policy.npz: `pi_<2i>_weight` / `pi_<2i>_bias` (tanh between the layers), `log_std`, `obs_mean`, `obs_var`
+        and, when the file has them, the critic's `vf_*`; a file without a critic gets a zero critic (one layer of zeros: value 0)."""
+        with np.load(path, allow_pickle=False) as z:
+            def net(prefix):
+                idx = sorted(int(k.split("_")[1]) for k in z.files if k.startswith(prefix + "_") and k.endswith("_weight"))
+                return [(z[f"{prefix}_{i}_weight"], z[f"{prefix}_{i}_bias"], "identity" if i == idx[-1] else "tanh") for i in idx]
+            actor = net("pi")
+            has_vf = any(k.startswith("vf_") for k in z.files)
+            critic = net("vf") if has_vf else [(np.zeros((1, actor[0][0].shape[1]), np.float32), np.zeros(1, np.float32), "identity")]
+            mean = z["obs_mean"] if "obs_mean" in z.files else None
+            return cls(actor, critic, z["log_std"], obs_mean=mean, obs_var=z["obs_var"] if mean is not None else None, eps=eps, clip=clip)
+
+    # ---- the callable of the single-env gym classes ----
+    def normalise(self, obs):
+        x = np.asarray(obs, dtype=np.float32)
+        if x.shape[-1] < self.in_dim:
+            raise ValueError(f"the policy's input has {self.in_dim} entries")
+        x = x[..., :self.in_dim]
+        if self.obs_mean is not None:
+            x = np.clip((x - self.obs_mean) * self.inv_std, np.float32(-self.clip), np.float32(self.clip))
+        return x
+
+    def __call__(self, obs, eps=None):
+        """-> (action, logp, value, mean), float32; eps None: the deterministic action (the mean)"""
+        x = self.normalise(obs)
+        mean, value = _apply(self.actor, x), _apply(self.critic, x)[..., 0]
+        e = np.zeros_like(mean) if eps is None else np.asarray(eps, np.float32)
+        action = mean if eps is None else mean + np.exp(self.log_std) * e
+        logp = (np.float32(-0.5) * e * e - self.log_std - np.float32(HALF_LOG_2PI)).sum(-1, dtype=np.float32)
+        return action, logp, value, mean
+
+    # ---- what the library takes (include/mocca.h mocca_set_policy / mocca_update_policy) ----
+    def table(self):
+        """int32 [layers][8], the actor first: net, in, out, in_pad, out_pad, activation id, 0, 0"""
+        return np.array([[net_id, w.shape[1], w.shape[0], _round16(w.shape[1]), _round16(w.shape[0]), ACTIVATIONS.index(act), 0, 0]
+                         for net_id, net in enumerate((self.actor, self.critic)) for w, b, act in net], np.int32)
+
+    def flat_params(self):
+        """float32 [n]: per layer W[out][in] row-major then b[out], then log_std, then (with normalisation) mean and inv_std"""
+        parts = [p.reshape(-1) for net in (self.actor, self.critic) for w, b, _ in net for p in (w, b)] + [self.log_std]
+        if self.obs_mean is not None:
+            parts += [self.obs_mean, self.inv_std]
+        return np.concatenate(parts).astype(np.float32)
+
+    # ---- the image the policy kernel reads (csrc/mocca_policy.h); the library's repack kernel builds the same one from flat_params() ----
+    def pack(self):
+        """-> (image float32 [n], table int32 [layers][8] with the weight / bias offsets, offsets dict): per layer the controller's fragment
+        order (controller.BaseController.pack), then log_std [32], flags [4] (flags[0] = 1: normalise), mean and inv_std [in_pad]"""
+        params, table, pos = [], self.table(), 0
+        for row, (w, b, _) in zip(table, self.actor + self.critic):
+            n_out, n_in = w.shape
+            p_out, p_in = int(row[4]), int(row[3])
+            full = np.zeros((p_out, p_in), np.float32)
+            full[:n_out, :n_in] = w
+            image = full.reshape(p_out // 16, 16, p_in // 16, 4, 4).transpose(0, 2, 3, 1, 4).reshape(-1)
+            bias = np.zeros(p_out, np.float32)
+            bias[:n_out] = b
+            row[6], row[7] = pos, pos + image.size
+            params += [image, bias]
+            pos += image.size + p_out
+        in_pad = _round16(self.in_dim)
+        tail = np.zeros(MAX_ACTION + FLAG_WORDS + 2 * in_pad, np.float32)
+        tail[:self.act_dim] = self.log_std
+        if self.obs_mean is not None:
+            tail[MAX_ACTION] = 1.0
+            tail[MAX_ACTION + FLAG_WORDS:][:self.in_dim] = self.obs_mean
+            tail[MAX_ACTION + FLAG_WORDS + in_pad:][:self.in_dim] = self.inv_std
+        offsets = {"log_std": pos, "flags": pos + MAX_ACTION, "mean": pos + MAX_ACTION + FLAG_WORDS, "inv_std": pos + MAX_ACTION + FLAG_WORDS + in_pad,
+                   "in_dim": self.in_dim, "act_dim": self.act_dim, "clip": self.clip}
+        return np.concatenate(params + [tail]), table, offsets
+
+    @classmethod
+    def unpack(cls, image, table, offsets):
+        """decode pack()'s image back into a policy; non-zero padding is a ValueError"""
+        image = np.asarray(image, np.float32)
+        nets = [[], []]
+        for net_id, n_in, n_out, p_in, p_out, act, w_pos, b_pos in np.asarray(table).tolist():
+            full = image[w_pos:w_pos + p_in * p_out].reshape(p_out // 16, p_in // 16, 4, 16, 4).transpose(0, 3, 1, 2, 4).reshape(p_out, p_in)
+            bias = image[b_pos:b_pos + p_out]
+            if full[n_out:].any() or full[:, n_in:].any() or bias[n_out:].any():
+                raise ValueError("padding of a packed policy must be zeros")
+            nets[net_id].append((full[:n_out, :n_in], bias[:n_out], ACTIVATIONS[act]))
+        in_dim, act_dim, in_pad = offsets["in_dim"], offsets["act_dim"], _round16(offsets["in_dim"])
+        log_std = image[offsets["log_std"]:offsets["log_std"] + MAX_ACTION]
+        mean, inv_std = image[offsets["mean"]:offsets["mean"] + in_pad], image[offsets["inv_std"]:offsets["inv_std"] + in_pad]
+        norm = image[offsets["flags"]] != 0
+        if log_std[act_dim:].any() or mean[in_dim:].any() or inv_std[in_dim:].any() or image[offsets["flags"] + 1:offsets["flags"] + FLAG_WORDS].any() \
+                or (not norm and (mean.any() or inv_std.any())):
+            raise ValueError("padding of a packed policy must be zeros")
+        return cls(nets[0], nets[1], log_std[:act_dim], obs_mean=mean[:in_dim] if norm else None, inv_std=inv_std[:in_dim] if norm else None,
+                   clip=offsets["clip"])

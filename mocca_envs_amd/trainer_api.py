@@ -277,17 +277,19 @@ class TorchVecEnv:
         obs = self.venv.reset()        # (the reset kernel zeroes the envs' running returns: Monitor.reset)
         return self.venv.height_scan(out=self._wide, obs=obs) if self._scan else obs
 
-    def _step_obs(self, actions, obs_out=None, rew_out=None):
+    def _step_obs(self, actions, obs_out=None, rew_out=None, launch=None):
         """the step's launch and, with a height scan, the launch that writes the wide row [obs | scan] (into `obs_out` or this object's own
-        buffer; the step's own observation stays in the handle's buffer) -> (obs, reward)"""
+        buffer; the step's own observation stays in the handle's buffer) -> (obs, reward).  `launch`: what steps instead of step() /
+        plan_step() (act_step: `actions` is then the policy's input row)"""
+        launch = launch or self._venv_step
         if not self._scan:
             if obs_out is None and rew_out is None:      # (the sub-batched step takes the actions only)
-                return self._venv_step(actions)[:2]
-            return self._venv_step(actions, obs_out=obs_out, rew_out=rew_out)[:2]
+                return launch(actions)[:2]
+            return launch(actions, obs_out=obs_out, rew_out=rew_out)[:2]
         wide = self._wide if obs_out is None else obs_out
         if wide.shape != self._wide.shape or not wide.is_contiguous():
             raise ValueError("with a height scan the observation rows are contiguous float32 [n_envs, obs_dim + scan_dim]")
-        o, r = self._venv_step(actions, rew_out=rew_out)[:2]
+        o, r = launch(actions, rew_out=rew_out)[:2]
         return self.venv.height_scan(out=wide, obs=o), r
 
     def step(self, actions: torch.Tensor, into: Optional[dict] = None):
@@ -295,6 +297,12 @@ class TorchVecEnv:
         TRAINER's storage that this step's launch writes directly (row t + 1 of the rollout buffers: PPO reads its next policy input from
         there anyway), instead of this object's own buffers: no copy kernels between the env and the storage.  The returned `obs` / `reward`
         are those tensors; `envs.masks` / `envs.bad_masks` keep pointing at the last buffers handed in."""
+        if actions.device != self.device or actions.dtype != torch.float32 or not actions.is_contiguous():
+            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        return self._step(actions, into, None)
+
+    def _step(self, actions, into, launch):
+        """step() / act_step(): the record bookkeeping around one launch of `launch` (None: step() / plan_step())"""
         k = self._k
         slot = k % self._slots
         old = self._live[slot]
@@ -302,8 +310,6 @@ class TorchVecEnv:
             old = old()
             if old is not None:
                 old.materialise()      # its slot is about to be rewritten: fetch it now (its launch finished long ago)
-        if actions.device != self.device or actions.dtype != torch.float32 or not actions.is_contiguous():
-            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
         if self._term_attach is not None:
             self._use_terminal(slot)
         rew = self._rew2
@@ -314,9 +320,9 @@ class TorchVecEnv:
                 self.masks, self.bad_masks = into.get("masks", self.masks), into.get("bad_masks", self.bad_masks)
                 self.venv.episode_masks_into(self.masks, self.bad_masks)
             rew = into.get("reward", rew)
-            obs = self._step_obs(actions, obs_out=into.get("obs"), rew_out=into.get("reward"))[0]
+            obs = self._step_obs(actions, obs_out=into.get("obs"), rew_out=into.get("reward"), launch=launch)[0]
         else:
-            obs = self._step_obs(actions)[0]
+            obs = self._step_obs(actions, launch=launch)[0]
         if self._events is not None:
             self._events[slot].record(torch.cuda.current_stream(self.device))
         self._k = k + 1 if k < 0xFFFFFFFF else 1
@@ -324,7 +330,45 @@ class TorchVecEnv:
         self._live[slot] = weakref.ref(rec)
         return obs, rew, (_LazyDone(rec).numpy() if self._eager else _LazyDone(rec)), _Infos(self.num_envs, rec)
 
-    def capture_rollout(self, policy, num_steps: int, sink=None, warmup: int = 2, into=None):
+    # ---- the trainer's own policy on the device (VecEnv.set_policy / act_step, include/mocca.h mocca_act_step) ----
+    def attach_policy(self, policy) -> None:
+        """Attach a `policy.DevicePolicy` whose input is this env's observation row ([obs | scan] with a height scan) and whose actions are
+        the env's; `update_policy(policy_or_flat_tensor)` refreshes its weights once per PPO iteration.  One handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("a device policy needs one handle (sub_batches=1)")
+        if self._plan:
+            raise NotImplementedError("a device policy acts with joint actions: not on a planner env that steps through its base controller")
+        if policy is not None and (policy.in_dim != self.observation_space.shape[0] or policy.act_dim != self.venv.act_dim):
+            raise ValueError(f"the policy maps {policy.in_dim} -> {policy.act_dim}, the env {self.observation_space.shape[0]} -> {self.venv.act_dim}")
+        self.venv.set_policy(policy)
+        n, f32 = self.num_envs, dict(dtype=torch.float32, device=self.device)
+        self._pol_bufs = None if policy is None else {"action": torch.zeros(n, policy.act_dim, **f32), "logp": torch.zeros(n, 1, **f32),
+                                                      "value": torch.zeros(n, 1, **f32)}
+
+    def update_policy(self, params) -> None:
+        self.venv.update_policy(params)
+
+    def _act_launch(self, into):
+        """the launcher _step_obs() calls: act_step with the policy's outputs going to `into`'s "action" / "logp" / "value" (this object's
+        own buffers where a key is missing); sets `self.last_act` to the three tensors written"""
+        if getattr(self, "_pol_bufs", None) is None:
+            raise _lib.MoccaError("act_step needs a device policy (attach_policy)")
+        out = {k: (into or {}).get(k, self._pol_bufs[k]) for k in ("action", "logp", "value")}
+        self.last_act = out
+        return lambda row, **kw: self.venv.act_step(row, action_out=out["action"], logp_out=out["logp"], value_out=out["value"], **kw)
+
+    def act_step(self, obs: Optional[torch.Tensor] = None, into: Optional[dict] = None):
+        """`value, action, logp = actor_critic.act(obs); envs.step(action)` as two launches and no torch op: the attached policy reads `obs`
+        (rollouts.obs[t]; None: the observation the last reset() / step() returned) and writes action [N, A], log-probability and value
+        ([N, 1]) into `into["action"]` / `into["logp"]` / `into["value"]` -- rows t of the trainer's storage; this object's own buffers,
+        `envs.last_act`, where a key is missing --, then the step runs on that action.  The rest of `into` and the return value are
+        step()'s.  The noise comes from the kernel (seed, env, the env's step and episode counters)."""
+        launch = self._act_launch(into)
+        if obs is None:
+            obs = self._wide if self._scan else self.venv.obs
+        return self._step(obs, into, launch)
+
+    def capture_rollout(self, policy=None, num_steps: int = 1, sink=None, warmup: int = 2, into=None):
         """The collection phase as ONE CUDA graph: `num_steps` x { action = policy(obs); env.step(action); sink(t, obs, reward, masks, bad_masks,
         action) } captured once, replayed with `.replay()` (returns the `torch.cuda.CUDAGraph`).  `policy` maps the observation tensor [N, obs_dim] to
         actions [N, act_dim] with torch ops only (no host reads; `policy(obs, t)` is called with the step index if it takes two arguments);
@@ -338,7 +382,10 @@ class TorchVecEnv:
         `rollouts.after_update()` copies the last row there; this call leaves it filled): the rollout needs no copy kernels at all.
         `terminal_observation=True`: the graph's launches all write their finished envs' final observations into ONE buffer of their own,
         `envs.rollout_terminal_obs` [N, obs_dim] (apart from the record slots of `step()`; rows of envs that did not finish keep older
-        content), which is also `envs.venv.terminal_obs` while `sink` runs -- a sink that wants them copies them at step t."""
+        content), which is also `envs.venv.terminal_obs` while `sink` runs -- a sink that wants them copies them at step t.
+        `policy=None`: the attached device policy (attach_policy) acts -- every step of the graph is act_step's two launches; `into(t)` may
+        carry "action" / "logp" / "value" rows, and `sink`'s `action` is the tensor the policy wrote.  `update_policy` between replays
+        changes what the graph computes: no recapture."""
         if not hasattr(self.venv, "lib"):
             raise NotImplementedError("capture_rollout needs one handle (sub_batches=1): sub-batches step on streams of their own")
         venv, dev = self.venv, self.device
@@ -347,12 +394,26 @@ class TorchVecEnv:
                 self.rollout_terminal_obs = torch.zeros_like(self._term_bufs[0])
             self._attach_terminal(self.rollout_terminal_obs)
         obs, rew = (self._wide if self._scan else venv.obs), self._rew2
-        if len(inspect.signature(policy).parameters) >= 2:        # policy(obs, t): e.g. to write its action into the storage's row t
+        if policy is None:
+            act_of = None
+        elif len(inspect.signature(policy).parameters) >= 2:        # policy(obs, t): e.g. to write its action into the storage's row t
             act_of = policy
         else:
             act_of = lambda o, t: policy(o)
 
         def body(t):
+            if act_of is None:       # the device policy: its input row is where the last step wrote its observation
+                d = {} if into is None else into(t)
+                launch = self._act_launch(d)
+                if "masks" in d or "bad_masks" in d:
+                    self.masks, self.bad_masks = d.get("masks", self.masks), d.get("bad_masks", self.bad_masks)
+                    venv.episode_masks_into(self.masks, self.bad_masks)
+                o, r = self._step_obs(obs if into is None else into(t - 1)["obs"], obs_out=d.get("obs"), rew_out=d.get("reward"), launch=launch)[:2]
+                if into is None:
+                    o, r = obs, rew
+                if sink is not None:
+                    sink(t, o, r, self.masks, self.bad_masks, self.last_act["action"])
+                return
             if into is None:
                 action = act_of(obs, t)
                 self._step_obs(action)

@@ -287,6 +287,96 @@ class VecEnv:
         self._out()
         return self._base_action.clone(), self._base_value.clone()
 
+    # ---- the trainer's own policy on the device (include/mocca.h mocca_set_policy / mocca_update_policy / mocca_act / mocca_act_step) ----
+    policy = None
+
+    def set_policy(self, policy) -> None:
+        """Attach a `policy.DevicePolicy` (None detaches): its shapes size the kernel's image, its weights are uploaded (update_policy).
+        May synchronise."""
+        if policy is None:
+            _lib.check(self.lib.mocca_set_policy(self.h, None, 0, 0, 0, 0.0), self.h)
+            self.policy = None
+            return
+        table = np.ascontiguousarray(policy.table(), np.int32)
+        _lib.check(self.lib.mocca_set_policy(self.h, table.ctypes.data_as(C.c_void_p), table.shape[0], int(policy.in_dim), int(policy.act_dim),
+                                             float(policy.clip)), self.h)
+        self.policy = policy
+        self.update_policy(policy)
+
+    def update_policy(self, params) -> None:
+        """New weights for the attached policy, once per PPO iteration: a `DevicePolicy` of the same shapes, or a flat float32 tensor in
+        `DevicePolicy.flat_params()`'s order that is already on the device (what a trainer builds with one torch.cat of its parameters,
+        log_std and observation statistics).  One repack kernel on the stream; nothing synchronises."""
+        if self.policy is None:
+            raise _lib.MoccaError("update_policy needs a policy (set_policy)")
+        flat = torch.from_numpy(params.flat_params()) if hasattr(params, "flat_params") else params
+        flat = flat.detach().to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
+        self._in()
+        _lib.check(self.lib.mocca_update_policy(self.h, C.c_void_p(flat.data_ptr()), flat.numel(), self._stream()), self.h)
+        self._out()       # `flat` may be freed (and its memory reused on the current stream) as soon as this returns
+
+    def _act_args(self, obs, eps, deterministic, out, logp, value):
+        """check the tensors of act() / act_step() -> (ctypes arguments in_dev .. mean_dev, the output dict)"""
+        p = self.policy
+        if p is None:
+            raise _lib.MoccaError("act needs a policy (set_policy)")
+        n, a = self.n_envs, p.act_dim
+        if obs.dim() != 2 or obs.shape[0] != n or obs.shape[1] < p.in_dim or obs.dtype != torch.float32 or obs.device != self.device or obs.stride(1) != 1:
+            raise ValueError(f"the policy's input must be a float32 [n_envs, >= {p.in_dim}] tensor on the env's device with contiguous rows")
+        if eps is not None:
+            if eps.shape != (n, a) or eps.dtype != torch.float32 or eps.device != self.device or not eps.is_contiguous():
+                raise ValueError(f"eps must be a contiguous float32 [n_envs, {a}] tensor on the env's device")
+        out = dict(out or {})
+        f32 = dict(dtype=torch.float32, device=self.device)
+        if "action" not in out:
+            out["action"] = torch.empty(n, a, **f32)
+        if logp and "logp" not in out:
+            out["logp"] = torch.empty(n, **f32)
+        if value and "value" not in out:
+            out["value"] = torch.empty(n, **f32)
+        for k, numel in (("action", n * a), ("logp", n), ("value", n), ("mean", n * a)):
+            t = out.get(k)
+            if t is not None and (t.numel() != numel or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()):
+                raise ValueError(f"out[{k!r}] must be a contiguous float32 tensor of {numel} elements on the env's device")
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        stride = obs.stride(0) if n > 1 else max(obs.stride(0), obs.shape[1])
+        return (ptr(obs), int(stride), ptr(eps), int(bool(deterministic)), ptr(out["action"]), ptr(out.get("logp")), ptr(out.get("value")),
+                ptr(out.get("mean"))), out
+
+    def act(self, obs: torch.Tensor, eps: Optional[torch.Tensor] = None, deterministic: bool = False, out: Optional[dict] = None) -> dict:
+        """`actor_critic.act(obs)` as one launch: -> {"action" [N, A], "logp" [N], "value" [N]} (and "mean" [N, A] when `out` has that key),
+        float32 on the device.  `obs`: float32 [N, >= in_dim] with contiguous rows (a view of wider storage will do).  `eps` [N, A]: the
+        caller's standard-normal noise; `deterministic`: the mean; neither: noise drawn in the kernel from (seed, env id, the env's step and
+        episode counters) -- two calls without a step() in between draw the same noise.  `out`: any of the output tensors, caller-owned
+        (rows of a trainer's rollout storage; "logp" / "value" may be [N, 1])."""
+        args, out = self._act_args(obs, eps, deterministic, out, True, True)
+        self._in()
+        _lib.check(self.lib.mocca_act(self.h, *args, self._stream()), self.h)
+        self._out()
+        return out
+
+    def act_step(self, obs: torch.Tensor, eps: Optional[torch.Tensor] = None, deterministic: bool = False, action_out: Optional[torch.Tensor] = None,
+                 logp_out: Optional[torch.Tensor] = None, value_out: Optional[torch.Tensor] = None, obs_out: Optional[torch.Tensor] = None,
+                 rew_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """act(obs) and step(action) as two launches of one C call (include/mocca.h mocca_act_step): the action, its log-probability and the
+        value go to `action_out` / `logp_out` / `value_out` (logp and value only where given; the action to a buffer of this object
+        otherwise: `self.last_action`), the step's results are step()'s, bit for bit.  Same contract as step() otherwise."""
+        given = {k: v for k, v in (("action", action_out), ("logp", logp_out), ("value", value_out)) if v is not None}
+        if "action" not in given and self.policy is not None:
+            if getattr(self, "_pol_action", None) is None or self._pol_action.shape[1] != self.policy.act_dim:
+                self._pol_action = torch.zeros(self.n_envs, self.policy.act_dim, dtype=torch.float32, device=self.device)
+            given["action"] = self._pol_action
+        args, out = self._act_args(obs, eps, deterministic, given, False, False)
+        self.last_action = out["action"]
+        obs_o, rew = self.obs if obs_out is None else obs_out, self.rew if rew_out is None else rew_out
+        if obs_out is not None or rew_out is not None:
+            if obs_o.shape != (self.n_envs, self.obs_dim) or rew.numel() != self.n_envs or obs_o.dtype != torch.float32 or rew.dtype != torch.float32 \
+                    or not obs_o.is_contiguous() or not rew.is_contiguous() or obs_o.device != self.device or rew.device != self.device:
+                raise ValueError("obs_out / rew_out must be contiguous float32 [n_envs, obs_dim] / [n_envs] tensors on the env's device")
+        _lib.check(self.lib.mocca_act_step(self.h, *args, C.c_void_p(obs_o.data_ptr()), C.c_void_p(rew.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                                           C.c_void_p(self.info.data_ptr()), self._stream()), self.h)
+        return obs_o, rew, self.done, self.info
+
     # ---- the reference's env-level setters, batched (env_base.py:103-118, env_locomotion.py:76-77,224-282) ----
     def set_env_params(self, params_dict):
         """`set_env_params({"curriculum": k})`: one value for all envs or one per env (takes effect at each env's next reset; the

@@ -8,6 +8,10 @@ reward / masks / bad_masks straight into the rollout storage (`step(action, into
 No symmetry loss, no curriculum: this is a sanity run, not SymmetricRL.
 
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
+                           [--device-policy]
+--device-policy: collection runs through `envs.act_step(obs[t], into=...)` -- the policy kernel (normalisation, both nets, the sample, its
+log-probability, the value) and the step kernel, two launches per step and no torch op; `envs.update_policy(flat)` once per iteration hands the
+kernel the optimiser's new weights and the running observation statistics.  The noise then comes from the kernel, not from torch.randn.
 writes <out>.jsonl (one line per logged iteration: env-steps so far, mean episode return / length of the episodes that ended since the last line,
 wall-clock env-steps/s of the whole loop incl. learning) and <out>_policy.npz (weights + observation statistics: `bench.py`'s workload
 bracket loads profiles/ppo_policy_walker3d.npz as its `ppo_policy` workload)."""
@@ -38,6 +42,7 @@ def main():
     ap.add_argument("--log-std", type=float, default=-1.0, help="initial log of the action noise's standard deviation")
     ap.add_argument("--fixed-std", action="store_true", help="keep the action noise fixed (the policy cannot collapse onto standing still)")
     ap.add_argument("--out", default="gpurun_out/r06_ppo_demo")
+    ap.add_argument("--device-policy", action="store_true", help="collect with the policy on the device (act_step)")
     args = ap.parse_args()
     import torch
     import torch.nn as nn
@@ -69,6 +74,14 @@ def main():
     def logprob(mu, a):
         return (-0.5 * ((a - mu) / log_std.exp()) ** 2 - log_std - 0.9189385332046727).sum(-1, keepdim=True)
 
+    if args.device_policy:
+        from mocca_envs_amd.policy import DevicePolicy
+        envs.attach_policy(DevicePolicy.from_torch(pi, vf, log_std, obs_mean=mean, obs_var=var, eps=1e-8, clip=10.0))
+        row_act = lambda t: dict(row(t), action=S["act"][t], logp=S["logp"][t], value=S["value"][t])
+        # DevicePolicy.flat_params()'s order, built on the device: layers of pi then vf (W, b), log_std, mean, 1 / sqrt(var + eps)
+        flat_params = lambda: torch.cat([q.reshape(-1) for net in (pi, vf) for m in net if isinstance(m, nn.Linear) for q in (m.weight, m.bias)]
+                                        + [log_std, mean, 1.0 / torch.sqrt(var + 1e-8)])
+
     S["obs"][0].copy_(envs.reset())
     envs.episode_totals.zero_()
     log = open(args.out + ".jsonl", "w")
@@ -83,7 +96,12 @@ def main():
             mean = mean + d * bn / tot
             var = (var * count + bv * bn + d * d * count * bn / tot) / tot
             count = tot
+            if args.device_policy:
+                envs.update_policy(flat_params())
             for t in range(T):
+                if args.device_policy:
+                    envs.act_step(S["obs"][t], into=row_act(t))
+                    continue
                 o = norm(S["obs"][t])
                 mu = pi(o)
                 a = mu + log_std.exp() * torch.randn_like(mu)
@@ -135,6 +153,7 @@ def main():
     import numpy as np
     np.savez(args.out + "_policy.npz", obs_mean=mean.cpu().numpy(), obs_var=var.cpu().numpy(), log_std=log_std.detach().cpu().numpy(),
              **{f"pi_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in pi.state_dict().items()},
+             **{f"vf_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in vf.state_dict().items()},
              env_id=np.array(args.env_id), env_steps=np.array(total_steps))
     envs.close()
 

@@ -12,7 +12,12 @@ Policy: MLP obs-64-act on the GPU; every loop writes the masked observation into
   trainer_loop_in_place       PPO's own structure: the policy reads rollouts.obs[t]; the step kernel writes observation, reward, masks and
                               bad_masks of step t STRAIGHT into rows t + 1 / t of the storage (`step(action, into=...)`), the policy its action
                               into rollouts.actions[t]: `rollouts.insert` without a copy kernel; `_graphed`: the same from one CUDA graph
-  python tools/trainer_loop_bench.py [--envs 4096] [--steps 300] [--env-id Walker3DCustomEnv-v0] [--sub-batches 1] [--chunk 10]"""
+  trainer_loop_device_policy  the same storage, the policy on the device too (`attach_policy`, `act_step(into=...)`): the policy kernel writes action,
+                              log-probability and value into rows t, the step kernel the rest -- two launches per step and no torch op;
+                              `_graphed`: `capture_rollout()` with the attached policy.  It does MORE than the torch policy of the other rows
+                              (critic, noise, log-probability, observation normalisation)
+  --net ppo: every loop's policy is tools/ppo_demo.py's obs-256-256-act tanh MLP instead of obs-64-act
+  python tools/trainer_loop_bench.py [--envs 4096] [--steps 300] [--env-id Walker3DCustomEnv-v0] [--sub-batches 1] [--chunk 10] [--net bench|ppo]"""
 import argparse
 import json
 import os
@@ -30,6 +35,7 @@ def main():
     ap.add_argument("--sub-batches", type=int, default=1)
     ap.add_argument("--chunk", type=int, default=10)
     ap.add_argument("--skip-verbatim", action="store_true")
+    ap.add_argument("--net", choices=("bench", "ppo"), default="bench")
     args = ap.parse_args()
     import torch
     from mocca_envs_amd.trainer_api import make_vec_envs
@@ -41,6 +47,11 @@ def main():
     w1 = torch.randn(envs.observation_space.shape[0], 64, device=dev, generator=g) * 0.3
     w2 = torch.randn(64, envs.action_space.shape[0], device=dev, generator=g) * 0.3
     policy = lambda o: torch.tanh(torch.tanh(o @ w1) @ w2)
+    if args.net == "ppo":       # ppo_demo's actor: obs-256-256-act, tanh between the layers
+        v1 = torch.randn(envs.observation_space.shape[0], 256, device=dev, generator=g) * 0.1
+        v2 = torch.randn(256, 256, device=dev, generator=g) * 0.06
+        v3 = torch.randn(256, envs.action_space.shape[0], device=dev, generator=g) * 0.06
+        policy = lambda o: torch.tanh(torch.tanh(o @ v1) @ v2) @ v3
     steps = (args.steps // args.chunk) * args.chunk
     rollouts = torch.zeros(max(steps, 50) + 1, args.envs, envs.observation_space.shape[0], device=dev)
 
@@ -101,6 +112,8 @@ def main():
          "act": torch.zeros(T, args.envs, ad, device=dev)}
     row = lambda t: {"obs": S["obs"][t + 1], "reward": S["reward"][t], "masks": S["masks"][t + 1], "bad_masks": S["bad_masks"][t + 1]} if t >= 0 else {"obs": S["obs"][0]}
     policy_into = lambda o, t: torch.tanh(torch.tanh(o @ w1) @ w2, out=S["act"][t])
+    if args.net == "ppo":
+        policy_into = lambda o, t: torch.matmul(torch.tanh(torch.tanh(o @ v1) @ v2), v3, out=S["act"][t])
 
     def in_place(steps):
         e = envs_totals
@@ -126,10 +139,52 @@ def main():
             S["obs"][0].copy_(S["obs"][T]); S["masks"][0].copy_(S["masks"][T]); S["bad_masks"][0].copy_(S["bad_masks"][T])
         return int(e.episode_totals[2].item())
 
-    out = {"env_id": args.env_id, "envs": args.envs, "sub_batches": args.sub_batches, "steps": steps, "graph_chunk": args.chunk}
+    # ---- the policy on the device as well: the same nets as a DevicePolicy (plus a critic of the actor's shape, log_std, normalisation)
+    def device_policy():
+        from mocca_envs_amd.policy import DevicePolicy
+        cpu = lambda w: w.t().contiguous().cpu().numpy()
+        if args.net == "ppo":
+            ws, acts = [v1, v2, v3], ["tanh", "tanh", "identity"]
+        else:
+            ws, acts = [w1, w2], ["tanh", "tanh"]
+        actor = [(cpu(w), torch.zeros(w.shape[1]).numpy(), a) for w, a in zip(ws, acts)]
+        critic = actor[:-1] + [(actor[-1][0][:1], actor[-1][1][:1], "identity")]
+        return DevicePolicy(actor, critic, torch.full((ad,), -1.0).numpy(), obs_mean=torch.zeros(od).numpy(), obs_var=torch.ones(od).numpy())
+
+    S["logp"], S["value"] = torch.zeros(T, args.envs, 1, device=dev), torch.zeros(T, args.envs, 1, device=dev)
+    row_dp = lambda t: dict(row(t), action=S["act"][t], logp=S["logp"][t], value=S["value"][t]) if t >= 0 else row(t)
+
+    def dev_policy(steps):
+        e = envs_totals
+        if getattr(e, "_pol_bufs", None) is None:
+            e.attach_policy(device_policy())
+        S["obs"][0].copy_(e.reset()); e.episode_totals.zero_()
+        for r in range(steps // T):
+            for t in range(T):
+                e.act_step(S["obs"][t], into=row_dp(t))
+            S["obs"][0].copy_(S["obs"][T]); S["masks"][0].copy_(S["masks"][T]); S["bad_masks"][0].copy_(S["bad_masks"][T])
+        return int(e.episode_totals[2].item())
+
+    graph_dp = None
+
+    def dev_policy_graphed(steps):
+        nonlocal graph_dp
+        e = envs_totals
+        if graph_dp is None:
+            if getattr(e, "_pol_bufs", None) is None:
+                e.attach_policy(device_policy())
+            graph_dp = e.capture_rollout(num_steps=T, into=row_dp)
+        S["obs"][0].copy_(e.reset()); e.episode_totals.zero_()
+        for r in range(steps // T):
+            graph_dp.replay()
+            S["obs"][0].copy_(S["obs"][T]); S["masks"][0].copy_(S["masks"][T]); S["bad_masks"][0].copy_(S["bad_masks"][T])
+        return int(e.episode_totals[2].item())
+
+    out = {"env_id": args.env_id, "envs": args.envs, "sub_batches": args.sub_batches, "steps": steps, "graph_chunk": args.chunk, "net": args.net}
     loops = [("trainer_loop_verbatim", verbatim), ("trainer_loop_device_masks", lean), ("trainer_loop_device_totals", totals)]
     if args.sub_batches == 1:
-        loops += [("trainer_loop_graphed", graphed), ("trainer_loop_in_place", in_place), ("trainer_loop_in_place_graphed", in_place_graphed)]
+        loops += [("trainer_loop_graphed", graphed), ("trainer_loop_in_place", in_place), ("trainer_loop_in_place_graphed", in_place_graphed),
+                  ("trainer_loop_device_policy", dev_policy), ("trainer_loop_device_policy_graphed", dev_policy_graphed)]
     for name, fn in loops:
         if args.skip_verbatim and fn is verbatim:
             continue
