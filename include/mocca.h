@@ -396,6 +396,48 @@ int mocca_act_step(mocca_handle h, const float *in_dev, int in_stride, const flo
                    float *logp_dev, float *value_dev, float *mean_dev, float *obs_dev, float *rew_dev, uint8_t *done_dev, int32_t *info_dev,
                    void *stream);
 
+/* ---- the end of a rollout on the device (no reference counterpart: the reference's trainers run these in torch, a Python loop over the
+ *      rollout's steps and a handful of reductions per iteration) ---- */
+
+/* mocca_gae         replaces `rollouts.compute_returns(next_value, use_gae=True, gamma, gae_lambda, use_proper_time_limits=True)` and the
+ *                   advantage normalisation of `ppo.update` (`advantages = returns[:-1] - value_preds[:-1]`, then `(advantages -
+ *                   advantages.mean()) / (advantages.std() + 1e-5)`): two launches.  All arrays contiguous f32 on the device, N = n_envs,
+ *                   T = n_steps: rew_dev [T][N]; value_dev, masks_dev, bad_masks_dev [T + 1][N] -- a2c-ppo-acktr's storage with the trailing 1
+ *                   dropped; value_dev[T] is next_value, rows 1 .. T of the two masks are read.  Each line element below is ONE IEEE f32
+ *                   operation, in this order, never contracted into an FMA:
+ *                       g = f32(gamma);  c = f32(gamma * lam, the product in double);  s = f32(reward_scale);  gae = 0
+ *                       for t = T - 1 .. 0:
+ *                           delta  = ((r[t] * s) + ((g * v[t + 1]) * m[t + 1])) - v[t]
+ *                           gae    = (delta + ((c * m[t + 1]) * gae)) * bm[t + 1]
+ *                           adv[t] = gae;   ret[t] = gae + v[t]
+ *                   so an episode cut by the TimeLimit (bad_masks = 0) has advantage 0 at the cut and nothing flows through it.  returns_dev
+ *                   and adv_dev [T][N] (returns_dev may be NULL; adv_dev and moments_dev may be NULL only with normalise == 0).  The sums of
+ *                   adv and adv^2 are taken in f64 in a fixed order (per env, per workgroup, then the workgroups in index order; no atomics:
+ *                   the same bits on every run); with B = T N, moments_dev[0] = mean = f32(S1 / B) and moments_dev[1] = std =
+ *                   f32(sqrt(max(S2 - S1^2 / B, 0) / (B - 1))) (Bessel's correction, torch's .std(); NaN for B = 1); normalise != 0
+ *                   rewrites adv <- (adv - mean) / (std + f32(adv_eps)) in f32 with a correctly rounded division.  1 <= T <= 65536.
+ * mocca_obs_stats   replaces VecNormalize's `ob_rms.update(obs)` (baselines' RunningMeanStd) over a whole rollout: two launches.  rows_dev
+ *                   [n_rows][row_stride] f32, the first dim (1 .. 336) floats of a row are read and nothing beyond them (rollouts.obs[1:],
+ *                   or wider [obs | scan | ...] rows).  state_dev f64 [1 + 2 dim] = count, mean[dim], var[dim], CALLER-owned; a fresh state is
+ *                   count 1e-4, mean 0, var 1.  In f64, with d = x - mean[k] summed in a fixed order (no atomics) and n = n_rows:
+ *                       bm = mean + sum(d) / n;  bv = sum(d^2) / n - (sum(d) / n)^2;  delta = bm - mean;  tot = count + n
+ *                       mean' = mean + delta n / tot;  var' = (var count + bv n + delta^2 count n / tot) / tot;  count' = tot
+ *                   The state is written back; mean_dev[k] = f32(mean') and inv_std_dev[k] = 1.0f / sqrtf(f32(var') + f32(eps)) (square
+ *                   root and division correctly rounded) go to two caller arrays of dim floats, either may be NULL -- meant to be the tail
+ *                   of the params_dev that mocca_update_policy takes, so that the trainer's flat parameter tensor needs no torch.cat.
+ * Both keep their scratch in the handle: it is allocated on the first call and on a later call that needs more (more envs' workgroups, more
+ * rows or a larger dim), and such a call may synchronise.  Every other call is asynchronous on `stream`: no allocation, no host read, no
+ * synchronisation, no atomics -- after one warm call with the same shapes both are capturable in a hipGraph (a linear chain on one stream).
+ * They read and write none of the handle's env records.
+ * Errors (MOCCA_E_ARG, with a message): a NULL handle or required pointer, n_steps outside 1 .. 65536, normalise with T N < 2 or without
+ * adv_dev / moments_dev, non-finite gamma / lam / reward_scale, a non-finite or negative adv_eps / eps, dim outside 1 .. 336, row_stride <
+ * dim, n_rows < 1. */
+int mocca_gae(mocca_handle h, const float *rew_dev, const float *value_dev, const float *masks_dev, const float *bad_masks_dev,
+              int n_steps, double gamma, double lam, double reward_scale, float *returns_dev, float *adv_dev,
+              int normalise, double adv_eps, float *moments_dev, void *stream);
+int mocca_obs_stats(mocca_handle h, const float *rows_dev, int64_t n_rows, int row_stride, int dim, double *state_dev, double eps,
+                    float *mean_dev, float *inv_std_dev, void *stream);
+
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */
 int mocca_kernel_info(mocca_handle h, int *vgprs, int *sgprs, int *lds_bytes, int *scratch_bytes, int *max_blocks_per_cu);

@@ -14,6 +14,7 @@
 #include "mocca_kernels.h"
 #include "mocca_policy.h"
 #include "mocca_render.h"
+#include "mocca_rollout.h"
 #include "mocca_scan.h"
 
 using namespace mocca;
@@ -129,6 +130,11 @@ struct mocca_ctx {
   mocca_pol::RepackArgs pol_repack{};   // rows of the repack kernel; src offsets in the caller's flat parameters
   size_t pol_n_base = 0;             // floats of mocca_update_policy's params_dev without the normalisation arrays
   bool pol_filled = false;           // mocca_update_policy has run since mocca_set_policy
+  // scratch of mocca_gae / mocca_obs_stats (mocca_rollout.h), owned by the handle, grown on demand
+  double* d_gae_part = nullptr;      // [blocks][2]
+  size_t gae_part_cap = 0;           // doubles
+  double* d_obs_part = nullptr;      // [blocks][dim][2]
+  size_t obs_part_cap = 0;
   std::string err;
 };
 static_assert(ROBOT_STATE_STRIDE == mocca_ctrl::CTRL_RS_STRIDE, "the step kernels and the controller kernel share the robot_state buffer");
@@ -367,6 +373,8 @@ int mocca_destroy(mocca_handle h) {
   if (h->d_base_val) (void)hipFree(h->d_base_val);
   if (h->d_pol_image) (void)hipFree(h->d_pol_image);
   if (h->d_pol_layers) (void)hipFree(h->d_pol_layers);
+  if (h->d_gae_part) (void)hipFree(h->d_gae_part);
+  if (h->d_obs_part) (void)hipFree(h->d_obs_part);
   delete h;
   return MOCCA_OK;
 }
@@ -1129,6 +1137,69 @@ int mocca_act_step(mocca_handle h, const float* in_dev, int in_stride, const flo
   hipStream_t s = (hipStream_t)stream;
   if (int rc = launch_act(h, "mocca_act_step", in_dev, in_stride, eps_dev, deterministic, action_dev, logp_dev, value_dev, mean_dev, s)) return rc;
   return launch_step(h, action_dev, nullptr, obs_dev, rew_dev, done_dev, info_dev, s);
+}
+
+// scratch of the rollout kernels: allocated on the first call and on one that needs more; only such a call synchronises
+static int grow_scratch(mocca_handle h, const char* who, double** buf, size_t* cap, size_t need) {
+  if (need <= *cap) return MOCCA_OK;
+  hipError_t e = hipSuccess;
+  if (*buf) e = hipDeviceSynchronize();   // a launch in flight may still use the old one
+  double* p = nullptr;
+  if (e == hipSuccess) e = hipMalloc(&p, need * sizeof(double));
+  if (e != hipSuccess) { h->err = std::string(who) + ": scratch: " + hipGetErrorString(e); return MOCCA_E_HIP; }
+  if (*buf) (void)hipFree(*buf);
+  *buf = p; *cap = need;
+  return MOCCA_OK;
+}
+
+int mocca_gae(mocca_handle h, const float* rew_dev, const float* value_dev, const float* masks_dev, const float* bad_masks_dev, int n_steps,
+              double gamma, double lam, double reward_scale, float* returns_dev, float* adv_dev, int normalise, double adv_eps,
+              float* moments_dev, void* stream) {
+  if (!h) { g_err = "mocca_gae: NULL handle"; return MOCCA_E_ARG; }
+  auto bad = [&](const std::string& what) { h->err = "mocca_gae: " + what; return MOCCA_E_ARG; };
+  if (!rew_dev || !value_dev || !masks_dev || !bad_masks_dev) return bad("rew_dev, value_dev, masks_dev and bad_masks_dev must not be NULL");
+  if (normalise && (!adv_dev || !moments_dev)) return bad("normalise needs adv_dev and moments_dev");
+  if (n_steps < 1 || n_steps > 65536) return bad("n_steps must be 1 .. 65536, not " + std::to_string(n_steps));
+  const long long count = (long long)n_steps * h->n_envs;
+  if (normalise && count < 2) return bad("normalise needs at least two advantages (n_steps x n_envs >= 2)");
+  if (!std::isfinite(gamma) || !std::isfinite(lam) || !std::isfinite(reward_scale)) return bad("gamma, lam and reward_scale must be finite");
+  if (!std::isfinite(adv_eps) || adv_eps < 0.0) return bad("adv_eps must be finite and not negative");
+  DeviceGuard guard(h->device);
+  const int blocks = mocca_ro::gae_blocks(h->n_envs);
+  if (int rc = grow_scratch(h, "mocca_gae", &h->d_gae_part, &h->gae_part_cap, 2 * (size_t)blocks)) return rc;
+  mocca_ro::GaeArgs a{};
+  a.rew = rew_dev; a.value = value_dev; a.masks = masks_dev; a.bad_masks = bad_masks_dev; a.returns = returns_dev; a.adv = adv_dev;
+  a.partials = h->d_gae_part; a.n_envs = h->n_envs; a.n_steps = n_steps;
+  a.g = (float)gamma; a.c = (float)(gamma * lam); a.s = (float)reward_scale;
+  mocca_ro::launch_gae((hipStream_t)stream, a);
+  if (normalise || moments_dev) {
+    mocca_ro::MomentsArgs m{};
+    m.partials = h->d_gae_part; m.n_partials = blocks; m.count = count; m.adv = adv_dev; m.moments = moments_dev; m.eps = (float)adv_eps;
+    m.normalise = normalise != 0;
+    mocca_ro::launch_moments((hipStream_t)stream, m);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
+}
+
+int mocca_obs_stats(mocca_handle h, const float* rows_dev, int64_t n_rows, int row_stride, int dim, double* state_dev, double eps, float* mean_dev,
+                    float* inv_std_dev, void* stream) {
+  if (!h) { g_err = "mocca_obs_stats: NULL handle"; return MOCCA_E_ARG; }
+  auto bad = [&](const std::string& what) { h->err = "mocca_obs_stats: " + what; return MOCCA_E_ARG; };
+  if (!rows_dev || !state_dev) return bad("rows_dev and state_dev must not be NULL");
+  if (dim < 1 || dim > mocca_ro::OBS_MAX_DIM) return bad("dim must be 1 .. " + std::to_string(mocca_ro::OBS_MAX_DIM) + ", not " + std::to_string(dim));
+  if (row_stride < dim) return bad("row_stride " + std::to_string(row_stride) + " is smaller than dim (" + std::to_string(dim) + ")");
+  if (n_rows < 1) return bad("n_rows must be at least 1");
+  if (!std::isfinite(eps) || eps < 0.0) return bad("eps must be finite and not negative");
+  DeviceGuard guard(h->device);
+  mocca_ro::ObsArgs a{};
+  a.rows = rows_dev; a.n_rows = n_rows; a.row_stride = row_stride; a.dim = dim;
+  mocca_ro::obs_grid(n_rows, dim, &a.rows_per_block, &a.n_blocks);
+  if (int rc = grow_scratch(h, "mocca_obs_stats", &h->d_obs_part, &h->obs_part_cap, 2 * (size_t)a.n_blocks * dim)) return rc;
+  a.state = state_dev; a.partials = h->d_obs_part; a.eps = (float)eps; a.mean_out = mean_dev; a.inv_std_out = inv_std_dev;
+  mocca_ro::launch_obs_stats((hipStream_t)stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
 }
 
 #ifdef MOCCA_STAMPS

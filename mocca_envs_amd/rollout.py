@@ -1,0 +1,147 @@
+"""The end of a PPO rollout: `ObsStats`, the running observation statistics both env surfaces take, and the argument checks of
+`VecEnv.finish_rollout` / `VecEnv.update_obs_stats` (include/mocca.h mocca_gae / mocca_obs_stats).
+
+The reference's trainers (SymmetricRL, ALLSTEPS: pytorch-a2c-ppo-acktr) normalise observations with VecNormalize's `ob_rms`, baselines'
+RunningMeanStd: count, mean and variance per feature, merged batch by batch (Chan et al.).  An `ObsStats` holds them as ONE float64 tensor
+`state` = [count, mean[dim], var[dim]]:
+
+* `VecEnv.update_obs_stats(stats, rows)` / `TorchVecEnv.update_obs_stats` merge a whole rollout's rows on the device, two launches, and
+  write float32 mean and 1 / sqrt(var + eps) where the caller says -- the tail of the flat tensor `update_policy` takes;
+* `stats.update(rows)` is the same definition in numpy, for the single-env gym classes (and the tests).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+MAX_DIM = 336            # csrc/mocca_rollout.h OBS_MAX_DIM = policy.MAX_IN
+MAX_STEPS = 65536        # include/mocca.h mocca_gae
+INITIAL_COUNT = 1e-4     # baselines' RunningMeanStd(epsilon=1e-4)
+
+
+class ObsStats:
+    def __init__(self, dim: int, device=None, eps: float = 1e-8):
+        import torch
+        self.dim, self.eps = int(dim), float(eps)
+        if not 1 <= self.dim <= MAX_DIM:
+            raise ValueError(f"dim must be 1 .. {MAX_DIM}")
+        if not (np.isfinite(self.eps) and self.eps >= 0.0):
+            raise ValueError("eps must be finite and not negative")
+        self.device = torch.device("cpu" if device is None else device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.state = torch.empty(1 + 2 * self.dim, dtype=torch.float64, device=self.device)
+        self.reset()
+
+    def reset(self) -> None:
+        """count 1e-4, mean 0, var 1"""
+        import torch
+        self.state.copy_(torch.from_numpy(initial_state(self.dim)))
+
+    # views of the state tensor (on its device)
+    @property
+    def count(self):
+        return self.state[0]
+
+    @property
+    def mean(self):
+        return self.state[1:1 + self.dim]
+
+    @property
+    def var(self):
+        return self.state[1 + self.dim:]
+
+    def normalisation(self):
+        """(mean, inv_std) as float32 numpy arrays: what `policy.DevicePolicy` and the policy kernel use"""
+        return normalisation(self.state.cpu().numpy(), self.eps)
+
+    def update(self, rows) -> None:
+        """merge rows [..., >= dim] (numpy or tensor; the first dim entries of a row count) on the host, in float64"""
+        import torch
+        x = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+        self.state.copy_(torch.from_numpy(merge(self.state.cpu().numpy(), x, self.dim)))
+
+
+def initial_state(dim: int) -> np.ndarray:
+    return np.concatenate([[INITIAL_COUNT], np.zeros(dim), np.ones(dim)])
+
+
+def merge(state: np.ndarray, rows: np.ndarray, dim: int) -> np.ndarray:
+    """the kernel's definition: batch moments of d = x - mean (shifted by the running mean), then Chan's merge, all in float64"""
+    x = np.asarray(rows)
+    if x.ndim == 0 or x.shape[-1] < dim:
+        raise ValueError(f"rows must be [..., >= {dim}]")
+    x = x.reshape(-1, x.shape[-1])[:, :dim].astype(np.float64)
+    n = x.shape[0]
+    if n < 1:
+        raise ValueError("rows must hold at least one row")
+    count, mean, var = state[0], state[1:1 + dim], state[1 + dim:]
+    d = x - mean
+    md = d.sum(0) / n
+    bm, bv = mean + md, (d * d).sum(0) / n - md * md
+    delta, tot = bm - mean, count + n
+    return np.concatenate([[tot], mean + delta * n / tot, (var * count + bv * n + delta * delta * count * n / tot) / tot])
+
+
+def normalisation(state: np.ndarray, eps: float):
+    dim = (state.size - 1) // 2
+    mean, var = state[1:1 + dim].astype(np.float32), state[1 + dim:].astype(np.float32)
+    return mean, np.float32(1) / np.sqrt(var + np.float32(eps))
+
+
+# ---- argument checks of VecEnv.finish_rollout / update_obs_stats: they need no device ----
+
+def _storage(name, t, rows, n_envs, device):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device or not t.is_contiguous() \
+            or tuple(t.shape) not in ((rows, n_envs), (rows, n_envs, 1)):
+        raise ValueError(f"{name} must be a contiguous float32 [{rows}, {n_envs}] or [{rows}, {n_envs}, 1] tensor on the env's device")
+
+
+def gae_args(n_envs, device, reward, value, masks, bad_masks, gamma, lam, reward_scale, returns, adv, normalise, adv_eps):
+    """check the tensors and numbers of finish_rollout -> T; ValueError otherwise"""
+    import torch
+    if not isinstance(reward, torch.Tensor) or reward.dim() not in (2, 3):
+        raise ValueError(f"reward must be a float32 [T, {n_envs}] or [T, {n_envs}, 1] tensor")
+    T = int(reward.shape[0])
+    if not 1 <= T <= MAX_STEPS:
+        raise ValueError(f"the rollout must have 1 .. {MAX_STEPS} steps")
+    _storage("reward", reward, T, n_envs, device)
+    for name, t in (("value", value), ("masks", masks), ("bad_masks", bad_masks)):
+        _storage(name, t, T + 1, n_envs, device)
+    for name, t in (("returns", returns), ("adv", adv)):
+        if t is not None:
+            _storage(name, t, T, n_envs, device)
+    if not all(np.isfinite(float(x)) for x in (gamma, lam, reward_scale)):
+        raise ValueError("gamma, lam and reward_scale must be finite")
+    if not (np.isfinite(float(adv_eps)) and float(adv_eps) >= 0.0):
+        raise ValueError("adv_eps must be finite and not negative")
+    if normalise and T * n_envs < 2:
+        raise ValueError("normalise needs at least two advantages")
+    return T
+
+
+def rows_2d(rows, dim: int):
+    """rows [..., >= dim] with contiguous last dimension and one stride between consecutive rows -> (n_rows, row_stride in floats)"""
+    import torch
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.dim() < 1 or rows.shape[-1] < dim \
+            or (rows.shape[-1] > 1 and rows.stride(-1) != 1):
+        raise ValueError(f"rows must be a float32 [..., >= {dim}] tensor with a contiguous last dimension")
+    lead = [(int(n), int(s)) for n, s in zip(rows.shape[:-1], rows.stride()[:-1]) if n != 1]
+    if any(n == 0 for n, _ in lead):
+        raise ValueError("rows must hold at least one row")
+    stride = lead[-1][1] if lead else int(rows.shape[-1])
+    for (n0, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
+        if s0 != n1 * s1:
+            raise ValueError("rows must have one uniform stride between consecutive rows (a slice of contiguous storage along the first axis will do)")
+    if stride < dim:
+        raise ValueError(f"the row stride ({stride}) is smaller than dim ({dim})")
+    n_rows = 1
+    for n, _ in lead:
+        n_rows *= n
+    return n_rows, stride
+
+
+def stats_out(name, t, dim, device):
+    import torch
+    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device or t.numel() != dim or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous float32 tensor of {dim} elements on the env's device")

@@ -348,6 +348,20 @@ class TorchVecEnv:
     def update_policy(self, params) -> None:
         self.venv.update_policy(params)
 
+    # ---- the end of a rollout on the device (VecEnv.finish_rollout / update_obs_stats, include/mocca.h mocca_gae / mocca_obs_stats) ----
+    def finish_rollout(self, reward, value, masks, bad_masks, *args, **kw) -> dict:
+        """returns, advantages (normalised by default) and their moments from the rollout storage, two launches: `VecEnv.finish_rollout`.
+        One handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("finish_rollout needs one handle (sub_batches=1)")
+        return self.venv.finish_rollout(reward, value, masks, bad_masks, *args, **kw)
+
+    def update_obs_stats(self, stats, rows, mean_out=None, inv_std_out=None) -> None:
+        """merge a rollout's observation rows into a `rollout.ObsStats`, two launches: `VecEnv.update_obs_stats`.  One handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("update_obs_stats needs one handle (sub_batches=1)")
+        self.venv.update_obs_stats(stats, rows, mean_out=mean_out, inv_std_out=inv_std_out)
+
     def _act_launch(self, into):
         """the launcher _step_obs() calls: act_step with the policy's outputs going to `into`'s "action" / "logp" / "value" (this object's
         own buffers where a key is missing); sets `self.last_act` to the three tensors written"""

@@ -14,6 +14,7 @@ import torch
 
 from . import lib as _lib
 from . import model as M
+from . import rollout as _ro
 
 TASKS = {
     "Walker3DCustomEnv-v0": M.TASK_WALKER3D_CUSTOM,
@@ -376,6 +377,47 @@ class VecEnv:
         _lib.check(self.lib.mocca_act_step(self.h, *args, C.c_void_p(obs_o.data_ptr()), C.c_void_p(rew.data_ptr()), C.c_void_p(self.done.data_ptr()),
                                            C.c_void_p(self.info.data_ptr()), self._stream()), self.h)
         return obs_o, rew, self.done, self.info
+
+    # ---- the end of a rollout on the device (include/mocca.h mocca_gae / mocca_obs_stats) ----
+    def finish_rollout(self, reward: torch.Tensor, value: torch.Tensor, masks: torch.Tensor, bad_masks: torch.Tensor, gamma: float = 0.99,
+                       lam: float = 0.95, reward_scale: float = 1.0, returns: Optional[torch.Tensor] = None, adv: Optional[torch.Tensor] = None,
+                       normalise: bool = True, adv_eps: float = 1e-8, moments: Optional[torch.Tensor] = None) -> dict:
+        """`rollouts.compute_returns(next_value, True, gamma, lam, use_proper_time_limits=True)` and the advantage normalisation of
+        `ppo.update` as two launches: -> {"returns", "adv" (normalised when `normalise`), "moments" [2] = mean and std of the raw advantages}.
+        `reward` [T, N] or [T, N, 1]; `value`, `masks`, `bad_masks` [T + 1, N(, 1)] (value[T] is next_value; rows 1 .. T of the masks are
+        read): contiguous float32 on the env's device -- a trainer's rollout storage as it is.  `reward_scale` multiplies the reward.
+        `returns` / `adv` / `moments`: caller-owned outputs; allocated where none is given.  The arithmetic is fixed operation by
+        operation (include/mocca.h) and the sums have a fixed order: the same bits on every run."""
+        T = _ro.gae_args(self.n_envs, self.device, reward, value, masks, bad_masks, gamma, lam, reward_scale, returns, adv, normalise, adv_eps)
+        _ro.stats_out("moments", moments, 2, self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        returns = torch.empty(reward.shape, **f32) if returns is None else returns
+        adv = torch.empty(reward.shape, **f32) if adv is None else adv
+        moments = torch.empty(2, **f32) if moments is None else moments
+        ptr = lambda x: C.c_void_p(x.data_ptr())
+        self._in()
+        _lib.check(self.lib.mocca_gae(self.h, ptr(reward), ptr(value), ptr(masks), ptr(bad_masks), T, float(gamma), float(lam), float(reward_scale),
+                                      ptr(returns), ptr(adv), int(bool(normalise)), float(adv_eps), ptr(moments), self._stream()), self.h)
+        self._out()
+        return {"returns": returns, "adv": adv, "moments": moments}
+
+    def update_obs_stats(self, stats, rows: torch.Tensor, mean_out: Optional[torch.Tensor] = None, inv_std_out: Optional[torch.Tensor] = None) -> None:
+        """VecNormalize's `ob_rms.update` over a whole rollout as two launches: merges `rows` [..., >= stats.dim] (float32 on the env's device,
+        contiguous last dimension, one stride between rows: `rollouts.obs[1:]`; only the first `stats.dim` floats of a row are read) into
+        the `rollout.ObsStats`' float64 state, and writes float32 mean and 1 / sqrt(var + eps) to `mean_out` / `inv_std_out` where given --
+        the tail of the flat parameter tensor `update_policy` takes."""
+        if stats.state.device != self.device:
+            raise ValueError("the statistics' state must be on the env's device")
+        if rows.device != self.device:
+            raise ValueError("rows must be on the env's device")
+        n_rows, stride = _ro.rows_2d(rows, stats.dim)
+        _ro.stats_out("mean_out", mean_out, stats.dim, self.device)
+        _ro.stats_out("inv_std_out", inv_std_out, stats.dim, self.device)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        self._in()
+        _lib.check(self.lib.mocca_obs_stats(self.h, ptr(rows), n_rows, stride, stats.dim, ptr(stats.state), float(stats.eps), ptr(mean_out),
+                                            ptr(inv_std_out), self._stream()), self.h)
+        self._out()
 
     # ---- the reference's env-level setters, batched (env_base.py:103-118, env_locomotion.py:76-77,224-282) ----
     def set_env_params(self, params_dict):

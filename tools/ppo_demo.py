@@ -8,10 +8,15 @@ reward / masks / bad_masks straight into the rollout storage (`step(action, into
 No symmetry loss, no curriculum: this is a sanity run, not SymmetricRL.
 
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
-                           [--device-policy]
+                           [--device-policy [--device-returns]]
 --device-policy: collection runs through `envs.act_step(obs[t], into=...)` -- the policy kernel (normalisation, both nets, the sample, its
 log-probability, the value) and the step kernel, two launches per step and no torch op; `envs.update_policy(flat)` once per iteration hands the
 kernel the optimiser's new weights and the running observation statistics.  The noise then comes from the kernel, not from torch.randn.
+--device-returns (with --device-policy): what follows collection runs on the device too.  value[T] comes from the policy kernel
+(`envs.venv.act(obs[T], deterministic=True)`), returns, advantages and their normalisation from `envs.finish_rollout` (two launches instead of
+the Python loop over t), and the running observation statistics from `envs.update_obs_stats`, which sees EVERY observation of the rollout
+(rows 1 .. T) and writes mean and 1 / sqrt(var + eps) straight into the tail of the flat parameter tensor; that tensor is allocated once and
+only its head is refreshed from the optimiser's parameters.
 writes <out>.jsonl (one line per logged iteration: env-steps so far, mean episode return / length of the episodes that ended since the last line,
 wall-clock env-steps/s of the whole loop incl. learning) and <out>_policy.npz (weights + observation statistics: `bench.py`'s workload
 bracket loads profiles/ppo_policy_walker3d.npz as its `ppo_policy` workload)."""
@@ -43,7 +48,13 @@ def main():
     ap.add_argument("--fixed-std", action="store_true", help="keep the action noise fixed (the policy cannot collapse onto standing still)")
     ap.add_argument("--out", default="gpurun_out/r06_ppo_demo")
     ap.add_argument("--device-policy", action="store_true", help="collect with the policy on the device (act_step)")
+    ap.add_argument("--device-returns", action="store_true", help="GAE, advantage normalisation and observation statistics on the device (finish_rollout, update_obs_stats)")
+    ap.add_argument("--verify-returns", action="store_true", help="with --device-returns: also run the torch GAE loop on the same storage and insist on the same bits")
     args = ap.parse_args()
+    if args.device_returns and not args.device_policy:
+        ap.error("--device-returns requires --device-policy")
+    if args.verify_returns and not args.device_returns:
+        ap.error("--verify-returns requires --device-returns")
     import torch
     import torch.nn as nn
     from mocca_envs_amd.trainer_api import make_vec_envs
@@ -82,42 +93,78 @@ def main():
         flat_params = lambda: torch.cat([q.reshape(-1) for net in (pi, vf) for m in net if isinstance(m, nn.Linear) for q in (m.weight, m.bias)]
                                         + [log_std, mean, 1.0 / torch.sqrt(var + 1e-8)])
 
+    if args.device_returns:
+        from mocca_envs_amd.rollout import ObsStats
+        stats = ObsStats(od, dev, eps=1e-8)
+        head = [q for net in (pi, vf) for m in net if isinstance(m, nn.Linear) for q in (m.weight, m.bias)] + [log_std]
+        n_head = sum(q.numel() for q in head)
+        flat = torch.zeros(n_head + 2 * od, device=dev)      # DevicePolicy.flat_params()'s order; allocated once
+        mean, inv_std = flat[n_head:n_head + od], flat[n_head + od:]      # the statistics tail: update_obs_stats writes it
+        norm = lambda o: ((o - mean) * inv_std).clamp(-10.0, 10.0)       # the policy kernel's formula
+        adv_buf, ret_buf = torch.zeros(T, N, 1, device=dev), torch.zeros(T, N, 1, device=dev)
+
     S["obs"][0].copy_(envs.reset())
     envs.episode_totals.zero_()
     log = open(args.out + ".jsonl", "w")
     t_start, total_steps, last_tot = time.perf_counter(), 0, torch.zeros(4, device=dev)
     for it in range(args.iters):
         # ---- collect
-        with torch.no_grad():
-            flat = S["obs"][0]
-            bm, bv, bn = flat.mean(0), flat.var(0, unbiased=False), flat.shape[0]     # running observation statistics (one row per iteration is enough)
-            d = bm - mean
-            tot = count + bn
-            mean = mean + d * bn / tot
-            var = (var * count + bv * bn + d * d * count * bn / tot) / tot
-            count = tot
-            if args.device_policy:
-                envs.update_policy(flat_params())
-            for t in range(T):
-                if args.device_policy:
+        if args.device_returns:
+            with torch.no_grad():
+                # the statistics see every observation collected so far: the reset row first, then rows 1 .. T of the previous rollout
+                envs.update_obs_stats(stats, S["obs"][1:] if it else S["obs"][:1], mean_out=mean, inv_std_out=inv_std)
+                torch.cat([q.reshape(-1) for q in head], out=flat[:n_head])
+                envs.update_policy(flat)
+                for t in range(T):
                     envs.act_step(S["obs"][t], into=row_act(t))
-                    continue
-                o = norm(S["obs"][t])
-                mu = pi(o)
-                a = mu + log_std.exp() * torch.randn_like(mu)
-                S["act"][t].copy_(a); S["logp"][t].copy_(logprob(mu, a)); S["value"][t].copy_(vf(o))
-                envs.step(S["act"][t], into=row(t))
-            S["value"][T].copy_(vf(norm(S["obs"][T])))
-            # GAE; an episode cut by the TimeLimit (bad_masks = 0) is not bootstrapped through: its advantage stops there (a2c-ppo-acktr's use_proper_time_limits)
-            adv = torch.zeros(T, N, 1, device=dev)
-            gae = torch.zeros(N, 1, device=dev)
-            rew = S["reward"] * args.reward_scale
-            for t in reversed(range(T)):
-                delta = rew[t] + args.gamma * S["value"][t + 1] * S["masks"][t + 1] - S["value"][t]
-                gae = (delta + args.gamma * args.lam * S["masks"][t + 1] * gae) * S["bad_masks"][t + 1]
-                adv[t] = gae
-            ret = adv + S["value"][:T]
-            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+                envs.venv.act(S["obs"][T], deterministic=True, out={"value": S["value"][T]})
+                if args.verify_returns:
+                    raw = envs.finish_rollout(S["reward"], S["value"], S["masks"], S["bad_masks"], args.gamma, args.lam, args.reward_scale, normalise=False)
+                    adv_t = torch.zeros(T, N, 1, device=dev)
+                    gae = torch.zeros(N, 1, device=dev)
+                    rew = S["reward"] * args.reward_scale
+                    for t in reversed(range(T)):
+                        delta = rew[t] + args.gamma * S["value"][t + 1] * S["masks"][t + 1] - S["value"][t]
+                        gae = (delta + args.gamma * args.lam * S["masks"][t + 1] * gae) * S["bad_masks"][t + 1]
+                        adv_t[t] = gae
+                    same = lambda u, v: bool((u.view(torch.int32) == v.view(torch.int32)).all().item())
+                    if not (same(raw["adv"], adv_t) and same(raw["returns"], adv_t + S["value"][:T])):
+                        raise SystemExit("finish_rollout differs from the torch GAE loop")
+                    print(json.dumps({"verify_returns": "ok", "iter": it + 1}), flush=True)
+                fin = envs.finish_rollout(S["reward"], S["value"], S["masks"], S["bad_masks"], args.gamma, args.lam, args.reward_scale,
+                                          returns=ret_buf, adv=adv_buf, normalise=True, adv_eps=1e-8)
+                adv, ret = fin["adv"], fin["returns"]
+        else:
+            with torch.no_grad():
+                flat = S["obs"][0]
+                bm, bv, bn = flat.mean(0), flat.var(0, unbiased=False), flat.shape[0]     # running observation statistics (one row per iteration is enough)
+                d = bm - mean
+                tot = count + bn
+                mean = mean + d * bn / tot
+                var = (var * count + bv * bn + d * d * count * bn / tot) / tot
+                count = tot
+                if args.device_policy:
+                    envs.update_policy(flat_params())
+                for t in range(T):
+                    if args.device_policy:
+                        envs.act_step(S["obs"][t], into=row_act(t))
+                        continue
+                    o = norm(S["obs"][t])
+                    mu = pi(o)
+                    a = mu + log_std.exp() * torch.randn_like(mu)
+                    S["act"][t].copy_(a); S["logp"][t].copy_(logprob(mu, a)); S["value"][t].copy_(vf(o))
+                    envs.step(S["act"][t], into=row(t))
+                S["value"][T].copy_(vf(norm(S["obs"][T])))
+                # GAE; an episode cut by the TimeLimit (bad_masks = 0) is not bootstrapped through: its advantage stops there (a2c-ppo-acktr's use_proper_time_limits)
+                adv = torch.zeros(T, N, 1, device=dev)
+                gae = torch.zeros(N, 1, device=dev)
+                rew = S["reward"] * args.reward_scale
+                for t in reversed(range(T)):
+                    delta = rew[t] + args.gamma * S["value"][t + 1] * S["masks"][t + 1] - S["value"][t]
+                    gae = (delta + args.gamma * args.lam * S["masks"][t + 1] * gae) * S["bad_masks"][t + 1]
+                    adv[t] = gae
+                ret = adv + S["value"][:T]
+                adv = (adv - adv.mean()) / (adv.std() + 1e-8)
         total_steps += N * T
         # ---- learn
         B = N * T
@@ -151,6 +198,8 @@ def main():
             if wall > 60.0 * args.minutes:
                 break
     import numpy as np
+    if args.device_returns:
+        mean, var = stats.mean.float(), stats.var.float()
     np.savez(args.out + "_policy.npz", obs_mean=mean.cpu().numpy(), obs_var=var.cpu().numpy(), log_std=log_std.detach().cpu().numpy(),
              **{f"pi_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in pi.state_dict().items()},
              **{f"vf_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in vf.state_dict().items()},

@@ -16,8 +16,14 @@ Policy: MLP obs-64-act on the GPU; every loop writes the masked observation into
                               log-probability and value into rows t, the step kernel the rest -- two launches per step and no torch op;
                               `_graphed`: `capture_rollout()` with the attached policy.  It does MORE than the torch policy of the other rows
                               (critic, noise, log-probability, observation normalisation)
+  --finish: ONLY the `finish` section -- what a PPO iteration does between collection and learning, T = --finish-steps (32) at each of
+                              --finish-envs (4096,8192), HIP events around the phase, the two paths alternating in one process:
+                              `torch`  tools/ppo_demo.py's default path restated: the running observation statistics from row 0 of the storage
+                                       (a handful of reductions) and the GAE loop over t, returns, advantage normalisation;
+                              `device` `finish_rollout` + `update_obs_stats` over ALL T x N observation rows: 4 launches
   --net ppo: every loop's policy is tools/ppo_demo.py's obs-256-256-act tanh MLP instead of obs-64-act
-  python tools/trainer_loop_bench.py [--envs 4096] [--steps 300] [--env-id Walker3DCustomEnv-v0] [--sub-batches 1] [--chunk 10] [--net bench|ppo]"""
+  python tools/trainer_loop_bench.py [--envs 4096] [--steps 300] [--env-id Walker3DCustomEnv-v0] [--sub-batches 1] [--chunk 10] [--net bench|ppo]
+  python tools/trainer_loop_bench.py --finish [--finish-envs 4096,8192] [--finish-steps 32] [--finish-rounds 200]"""
 import argparse
 import json
 import os
@@ -25,6 +31,84 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def finish_section(args):
+    """returns, advantages, their normalisation and the observation statistics of one PPO iteration: torch (the demo's default path) against
+    the rollout kernels, on a storage a random policy filled"""
+    import statistics
+    import torch
+    from mocca_envs_amd.rollout import ObsStats
+    from mocca_envs_amd.trainer_api import make_vec_envs
+    T, gamma, lam, scale = args.finish_steps, 0.99, 0.95, 0.1
+    out = {"section": "finish", "env_id": args.env_id, "steps": T, "rounds": args.finish_rounds, "timer": "HIP events around the phase, ms",
+           "protocol": "20 warm rounds, then the two paths alternate for `rounds` rounds in one process; median, min and the 10 % / 90 % quantiles", "rows": []}
+    for N in [int(x) for x in args.finish_envs.split(",")]:
+        envs = make_vec_envs(args.env_id, seed=0, num_processes=N, record_events=False)
+        dev, od, ad = envs.device, envs.observation_space.shape[0], envs.action_space.shape[0]
+        S = {"obs": torch.zeros(T + 1, N, od, device=dev), "reward": torch.zeros(T, N, 1, device=dev), "masks": torch.ones(T + 1, N, 1, device=dev),
+             "bad_masks": torch.ones(T + 1, N, 1, device=dev), "value": torch.randn(T + 1, N, 1, device=dev)}
+        S["obs"][0].copy_(envs.reset())
+        for t in range(T):      # a real rollout: rewards, masks and time limits as the step kernel writes them
+            envs.step(torch.randn(N, ad, device=dev).clamp(-1, 1), into={"obs": S["obs"][t + 1], "reward": S["reward"][t], "masks": S["masks"][t + 1],
+                                                                       "bad_masks": S["bad_masks"][t + 1]})
+        state = {"mean": torch.zeros(od, device=dev), "var": torch.ones(od, device=dev), "count": 1e-4}
+
+        def torch_path():      # tools/ppo_demo.py's default path: the statistics update, then the GAE loop, returns, normalisation
+            mean, var, count = state["mean"], state["var"], state["count"]
+            flat = S["obs"][0]
+            bm, bv, bn = flat.mean(0), flat.var(0, unbiased=False), flat.shape[0]
+            d = bm - mean
+            tot = count + bn
+            state["mean"] = mean + d * bn / tot
+            state["var"] = (var * count + bv * bn + d * d * count * bn / tot) / tot
+            state["count"] = tot
+            adv = torch.zeros(T, N, 1, device=dev)
+            gae = torch.zeros(N, 1, device=dev)
+            rew = S["reward"] * scale
+            for t in reversed(range(T)):
+                delta = rew[t] + gamma * S["value"][t + 1] * S["masks"][t + 1] - S["value"][t]
+                gae = (delta + gamma * lam * S["masks"][t + 1] * gae) * S["bad_masks"][t + 1]
+                adv[t] = gae
+            ret = adv + S["value"][:T]
+            return (adv - adv.mean()) / (adv.std() + 1e-8), ret
+
+        stats = ObsStats(od, dev)
+        bufs = {k: torch.zeros(T, N, 1, device=dev) for k in ("returns", "adv")}
+        moments, tail = torch.zeros(2, device=dev), torch.zeros(2 * od, device=dev)
+
+        def device_path():
+            envs.finish_rollout(S["reward"], S["value"], S["masks"], S["bad_masks"], gamma, lam, scale, returns=bufs["returns"], adv=bufs["adv"],
+                                normalise=True, adv_eps=1e-8, moments=moments)
+            envs.update_obs_stats(stats, S["obs"][1:], mean_out=tail[:od], inv_std_out=tail[od:])
+            return bufs["adv"], bufs["returns"]
+
+        with torch.no_grad():
+            for _ in range(20):
+                a_t, r_t = torch_path(); a_d, r_d = device_path()
+            same = lambda u, v: bool((u.view(torch.int32) == v.view(torch.int32)).all().item())
+            times = {"torch": [], "device": []}
+            ev = lambda: torch.cuda.Event(enable_timing=True)
+            for _ in range(args.finish_rounds):
+                for name, fn in (("torch", torch_path), ("device", device_path)):
+                    e0, e1 = ev(), ev()
+                    e0.record(); fn(); e1.record()
+                    e1.synchronize()
+                    times[name].append(e0.elapsed_time(e1))
+        q = lambda xs, f: sorted(xs)[min(len(xs) - 1, int(f * len(xs)))]
+        row = {"envs": N, "returns_bit_identical": same(r_t, r_d), "normalised_adv_max_abs_diff": float((a_t - a_d).abs().max().item())}
+        for name, xs in times.items():
+            row[name + "_ms"] = {"median": statistics.median(xs), "min": min(xs), "p10": q(xs, 0.1), "p90": q(xs, 0.9)}
+        # launches, counted from the code above: per step 8 elementwise kernels and the copy into adv[t]; two fills, the reward scale, the
+        # returns, mean, std (one kernel each) and three elementwise kernels of the normalisation; 2 reductions and 9 elementwise kernels of
+        # the statistics.  The device path: gae, moments / normalise, statistics partials, statistics merge.
+        row["torch_launches"] = 9 * T + 2 + 1 + 1 + 5 + 11
+        row["device_launches"] = 4
+        row["torch_obs_rows_seen"], row["device_obs_rows_seen"] = N, T * N
+        row["speedup_median"] = row["torch_ms"]["median"] / row["device_ms"]["median"]
+        out["rows"].append(row)
+        envs.close()
+    print(json.dumps(out))
 
 
 def main():
@@ -36,7 +120,13 @@ def main():
     ap.add_argument("--chunk", type=int, default=10)
     ap.add_argument("--skip-verbatim", action="store_true")
     ap.add_argument("--net", choices=("bench", "ppo"), default="bench")
+    ap.add_argument("--finish", action="store_true")
+    ap.add_argument("--finish-envs", default="4096,8192")
+    ap.add_argument("--finish-steps", type=int, default=32)
+    ap.add_argument("--finish-rounds", type=int, default=200)
     args = ap.parse_args()
+    if args.finish:
+        return finish_section(args)
     import torch
     from mocca_envs_amd.trainer_api import make_vec_envs
     envs = make_vec_envs(args.env_id, seed=0, num_processes=args.envs, sub_batches=args.sub_batches)
