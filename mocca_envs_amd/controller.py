@@ -20,14 +20,13 @@ def _round16(n):
     return -(-int(n) // 16) * 16
 
 
-def _net(layers, out_dim, name):
+def _net(layers, in_dim, out_dim, name):
     """validated copy of one net: [(W f32 [out][in], b f32 [out], activation)]"""
     layers = list(layers)
     if not 1 <= len(layers) <= MAX_LAYERS:
         raise ValueError(f"{name}: between 1 and {MAX_LAYERS} layers")
-    net, fan_in = [], INPUT_DIM
-    for i, layer in enumerate(layers):
-        w, b, act = layer
+    net, fan_in = [], in_dim
+    for i, (w, b, act) in enumerate(layers):
         w = np.array(w, dtype=np.float32, order="C")
         b = np.array(b, dtype=np.float32).reshape(-1)
         if act not in ACTIVATIONS:
@@ -56,6 +55,54 @@ def _apply(net, x):
     return x
 
 
+def layer_table(actor, critic, offsets=None):
+    """int32 [layers][8], the actor first: net, in, out, in_pad, out_pad, activation id, weight offset, bias offset (include/mocca.h).
+    `offsets`: "flat" -- into W[out][in] row-major, then b[out], layer after layer; "image" -- into the layer images below; None -- zeros.
+    Checks nothing: the classes' constructors do (_net), and what else reaches the library is the library's to refuse."""
+    rows, pos = [], 0
+    for net_id, net in enumerate((actor, critic)):
+        for w, _, act in net:
+            n_out, n_in = np.shape(w)
+            p_out, p_in = _round16(n_out), _round16(n_in)
+            n_w, n_b = {None: (0, 0), "flat": (n_out * n_in, n_out), "image": (p_out * p_in, p_out)}[offsets]
+            rows.append((net_id, n_in, n_out, p_in, p_out, ACTIVATIONS.index(act), pos, pos + n_w))
+            pos += n_w + n_b
+    return np.array(rows, np.int32).reshape(-1, 8)
+
+
+def layer_image(w, b):
+    """one layer as the kernels read it (csrc/mocca_controller.h) -> (weights float32 [out_pad * in_pad], bias float32 [out_pad]): W padded
+    with zeros to multiples of 16 both ways and cut into 16 x 16 blocks [row block][column block][lane 0..63][4] -- lane l of a block holds
+    row l % 16, columns 4 (l // 16) .. + 3 -- and the padded bias"""
+    n_out, n_in = w.shape
+    p_out, p_in = _round16(n_out), _round16(n_in)
+    full = np.zeros((p_out, p_in), np.float32)
+    full[:n_out, :n_in] = w
+    bias = np.zeros(p_out, np.float32)
+    bias[:n_out] = b
+    blocks = full.reshape(p_out // 16, 16, p_in // 16, 4, 4)                       # [rb][row][cb][quarter][4]
+    return blocks.transpose(0, 2, 3, 1, 4).reshape(-1), bias                       # [rb][cb][quarter][row][4]: lane = 16 quarter + row
+
+
+def pack_nets(actor, critic):
+    """-> (float32 [n]: per layer, actor first, layer_image's weights then its bias; layer_table with the offsets into it)"""
+    return np.concatenate([part for w, b, _ in actor + critic for part in layer_image(w, b)]), layer_table(actor, critic, "image")
+
+
+def unpack_nets(params, table, what):
+    """pack_nets' inverse -> [actor, critic]; non-zero padding is a ValueError"""
+    params = np.asarray(params, np.float32)
+    nets = [[], []]
+    for net_id, n_in, n_out, p_in, p_out, act, w_pos, b_pos in np.asarray(table).tolist():
+        image = params[w_pos:w_pos + p_in * p_out].reshape(p_out // 16, p_in // 16, 4, 16, 4)
+        full = image.transpose(0, 3, 1, 2, 4).reshape(p_out, p_in)
+        bias = params[b_pos:b_pos + p_out]
+        if full[n_out:].any() or full[:, n_in:].any() or bias[n_out:].any():
+            raise ValueError(f"padding of a packed {what} must be zeros")
+        nets[net_id].append((full[:n_out, :n_in], bias[:n_out], ACTIVATIONS[act]))
+    return nets
+
+
 def layers_from_sequential(seq, which):
     """a torch.nn.Sequential of Linear, each followed by at most one of ReLU / Tanh / Softsign -> [(W, b, activation)]; any other module
     is a ValueError"""
@@ -76,8 +123,8 @@ def layers_from_sequential(seq, which):
 
 class BaseController:
     def __init__(self, actor, critic):
-        self.actor = _net(actor, ACTION_DIM, "actor")
-        self.critic = _net(critic, 1, "critic")
+        self.actor = _net(actor, INPUT_DIM, ACTION_DIM, "actor")
+        self.critic = _net(critic, INPUT_DIM, 1, "critic")
 
     from_layers = classmethod(lambda cls, actor, critic: cls(actor, critic))
 
@@ -111,35 +158,11 @@ class BaseController:
 
     # ---- the image the controller kernel reads (csrc/mocca_controller.h); the library builds the same one from .actor / .critic ----
     def pack(self):
-        """-> (params float32 [n], table int32 [layers][8]): per layer, actor first, the weights padded with zeros to multiples of 16 both
-        ways and cut into 16 x 16 blocks [row block][column block][lane 0..63][4] -- lane l of a block holds row l % 16, columns
-        4 (l // 16) .. + 3 -- then the padded bias.  Table row: net, in, out, in_pad, out_pad, activation id, weight offset, bias offset."""
-        params, table = [], []
-        pos = 0
-        for net_id, net in enumerate((self.actor, self.critic)):
-            for w, b, act in net:
-                n_out, n_in = w.shape
-                p_out, p_in = _round16(n_out), _round16(n_in)
-                full = np.zeros((p_out, p_in), np.float32)
-                full[:n_out, :n_in] = w
-                blocks = full.reshape(p_out // 16, 16, p_in // 16, 4, 4)          # [rb][row][cb][quarter][4]
-                image = blocks.transpose(0, 2, 3, 1, 4).reshape(-1)                # [rb][cb][quarter][row][4]: lane = 16 quarter + row
-                bias = np.zeros(p_out, np.float32)
-                bias[:n_out] = b
-                table.append([net_id, n_in, n_out, p_in, p_out, ACTIVATIONS.index(act), pos, pos + image.size])
-                params += [image, bias]
-                pos += image.size + p_out
-        return np.concatenate(params), np.array(table, np.int32)
+        """-> (params float32 [n], table int32 [layers][8]): per layer, actor first, the weights in fragment order, then the padded bias
+        (layer_image); the table's offsets point into params (layer_table)"""
+        return pack_nets(self.actor, self.critic)
 
     @classmethod
     def unpack(cls, params, table):
         """decode pack()'s image back into a controller; non-zero padding is a ValueError"""
-        nets = [[], []]
-        for net_id, n_in, n_out, p_in, p_out, act, w_pos, b_pos in np.asarray(table).tolist():
-            image = np.asarray(params[w_pos:w_pos + p_in * p_out], np.float32).reshape(p_out // 16, p_in // 16, 4, 16, 4)
-            full = image.transpose(0, 3, 1, 2, 4).reshape(p_out, p_in)
-            bias = np.asarray(params[b_pos:b_pos + p_out], np.float32)
-            if full[n_out:].any() or full[:, n_in:].any() or bias[n_out:].any():
-                raise ValueError("padding of a packed controller must be zeros")
-            nets[net_id].append((full[:n_out, :n_in], bias[:n_out], ACTIVATIONS[act]))
-        return cls(*nets)
+        return cls(*unpack_nets(params, table, "controller"))

@@ -5,8 +5,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "mocca.h"
@@ -68,14 +70,43 @@ __global__ __launch_bounds__(1024) void order_by_rows_kernel(const uint32_t* tas
   }
 }
 
+// Owner of one device allocation: move-only, freed by its destructor.  Whatever the handle owns on the device is one of these, so destroying
+// the handle frees it; a setter builds its new buffers in locals and swaps them into the handle after its last fallible step (commit_ready),
+// and the locals' destructors free whichever side lost: the new buffers of a refused call, the old ones of a successful one.
+template <class T>
+class DevBuf {
+  T* p_ = nullptr;
+
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept { swap(o); return *this; }   // (the source's destructor frees what this one held)
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+  }
+  void swap(DevBuf& o) noexcept { std::swap(p_, o.p_); }
+  // `count` elements in place of what it held, zero-filled on request; empty when that fails
+  hipError_t alloc(size_t count, bool zero) {
+    reset();
+    hipError_t e = hipMalloc(&p_, count * sizeof(T));
+    if (e != hipSuccess) { p_ = nullptr; return e; }
+    if (zero && (e = hipMemset(p_, 0, count * sizeof(T))) != hipSuccess) reset();
+    return e;
+  }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+};
+
 struct mocca_ctx {
   MoccaModel model;
   int task_id = 0, n_envs = 0, device = 0, obs_dim = 0;
-  MoccaModel* d_model = nullptr;
+  DevBuf<MoccaModel> d_model;
   int topo = 0;  // TOPO_*
-  float* d_dyn = nullptr;
-  uint32_t* d_task = nullptr;
-  float* d_terrain = nullptr;
+  DevBuf<float> d_dyn;
+  DevBuf<uint32_t> d_task;
+  DevBuf<float> d_terrain;
   int auto_reset = 0, eval_mode = 0, random_pose = 1, curriculum = 0, host_retarget = 0, env_offset = 0, random_reward = 0;
   float gain = 1.0f;
   bool compact = false;        // the blob fits the compact step-kernel instance (compact_ok); MOCCA_PARAM_KERNEL_VARIANT = 1 overrides
@@ -83,9 +114,9 @@ struct mocca_ctx {
   int force_full = 0;          // MOCCA_PARAM_KERNEL_VARIANT: 1 forces the 48-row instance, 2 the 64-row one
   int persist_warm = 0;        // MOCCA_PARAM_PERSIST_IMPULSES
   int pace = -18;              // MOCCA_PARAM_PACE_TICKS: self-calibrating pace priorities, 18/16 of the previous launch's mean wave time (profiles/archive/r04_pace_*.jsonl)
-  unsigned long long* d_pace_acc = nullptr;  // self-calibration samples of the pace, one packed word (StepArgs.pace_acc), owned by the handle
+  DevBuf<unsigned long long> d_pace_acc;     // self-calibration samples of the pace, one packed word (StepArgs.pace_acc), owned by the handle
   // Monitor / TimeLimitMask inside the launch (mocca_set_episode_stats)
-  float* d_ep_ret = nullptr;       // [N] running episode returns, owned by the handle
+  DevBuf<float> d_ep_ret;          // [N] running episode returns, owned by the handle
   float *ep_masks = nullptr, *ep_bad = nullptr, *ep_totals = nullptr;   // caller-owned
   char* ep_rec = nullptr;          // caller-owned record ring: n_slots slots of [N] x 16 bytes, ep_stride bytes apart
   int ep_slots = 0;
@@ -93,47 +124,47 @@ struct mocca_ctx {
   uint32_t ep_serial = 1;          // stamped into the records of the next mocca_step (0 never: a zeroed ring holds no record)
   int order_every = 0;         // MOCCA_PARAM_ORDER_EVERY: re-sort the launch order every K steps (0: envs run in index order)
   int order_age = 0;           // steps since the last sort
-  int32_t* d_order = nullptr;  // [N] the permutation, owned by the handle
+  DevBuf<int32_t> d_order;     // [N] the permutation, owned by the handle
   bool gain_pending = false;   // a scalar MOCCA_PARAM_APPLIED_GAIN not yet written into the task records (flush_pending)
   float* final_obs = nullptr;  // caller-owned (mocca_set_terminal_obs_buffer)
-  float* d_pvec[3] = {nullptr, nullptr, nullptr};  // per-env curriculum / eval_mode / applied_gain (mocca_set_param_v), lazily allocated
+  DevBuf<float> d_pvec[3];     // per-env curriculum / eval_mode / applied_gain (mocca_set_param_v), lazily allocated
   bool pvec_on[3] = {false, false, false};
   const float* tape = nullptr;  // caller-owned (mocca_set_draw_tape)
   int tape_n = 0;
   int32_t* dbg = nullptr;       // caller-owned (mocca_set_debug_buffer)
   int prio = MOCCA_PRIO_T1 + 64 * MOCCA_PRIO_T2 + 4096 * MOCCA_PRIO_T3;   // MOCCA_PARAM_ISSUE_PRIORITY
   uint64_t seed = 0;
-  float* d_traj = nullptr;      // Cassie mocap / phase envs: the motion table (mocca_set_trajectory), owned by the handle
+  DevBuf<float> d_traj;         // Cassie mocap / phase envs: the motion table (mocca_set_trajectory), owned by the handle
   int traj_n = 0;
   double traj_tmax = 0.0, traj_cstep = 0.0;
-  float* d_hf = nullptr;        // planner envs: the height field (mocca_set_heightfield), owned by the handle
+  DevBuf<float> d_hf;           // planner envs: the height field (mocca_set_heightfield), owned by the handle
   int hf_rows = 0, hf_cols = 0;
   float hf_scale = 0.0f;
   float hf_zmin = 0.0f, hf_zmax = 0.0f;   // range of the heights (mocca_render clips its rays to it)
-  float* d_scenes = nullptr;    // mocca_render: world-space primitives of each view, owned by the handle, grown on demand
+  DevBuf<float> d_scenes;       // mocca_render: world-space primitives of each view, owned by the handle, grown on demand
   int scenes_cap = 0;           // views it holds
-  float* d_scan_pts = nullptr;  // mocca_set_height_scan: the pattern [scan_n][2] in the heading frame, owned by the handle
+  DevBuf<float> d_scan_pts;     // mocca_set_height_scan: the pattern [scan_n][2] in the heading frame, owned by the handle
   int scan_n = 0;
   float scan_above = 0.0f, scan_drop = 0.0f;
   // planner envs: the base controller (mocca_set_base_controller), all owned by the handle
-  float* d_ctrl_params = nullptr;
-  int32_t* d_ctrl_layers = nullptr;
+  DevBuf<float> d_ctrl_params;
+  DevBuf<int32_t> d_ctrl_layers;
   int ctrl_n_actor = 0, ctrl_n_critic = 0;
   float ctrl_scale = 0.0f;
-  float* d_robot_state = nullptr;    // [N][ROBOT_STATE_STRIDE] the controller's next input (StepArgs.robot_state)
-  float* d_base_act = nullptr;       // [N][21] the actor's output of the last mocca_plan_step
-  float* d_base_val = nullptr;       // [N] the critic's
+  DevBuf<float> d_robot_state;       // [N][ROBOT_STATE_STRIDE] the controller's next input (StepArgs.robot_state)
+  DevBuf<float> d_base_act;          // [N][21] the actor's output of the last mocca_plan_step
+  DevBuf<float> d_base_val;          // [N] the critic's
   // a trainer's policy (mocca_set_policy), owned by the handle
-  float* d_pol_image = nullptr;      // the kernel's image (mocca_policy.h)
-  int32_t* d_pol_layers = nullptr;
+  DevBuf<float> d_pol_image;         // the kernel's image (mocca_policy.h)
+  DevBuf<int32_t> d_pol_layers;
   mocca_pol::PolicyArgs pol{};       // shapes and image offsets; the per-call pointers are filled by mocca_act
   mocca_pol::RepackArgs pol_repack{};   // rows of the repack kernel; src offsets in the caller's flat parameters
   size_t pol_n_base = 0;             // floats of mocca_update_policy's params_dev without the normalisation arrays
   bool pol_filled = false;           // mocca_update_policy has run since mocca_set_policy
   // scratch of mocca_gae / mocca_obs_stats (mocca_rollout.h), owned by the handle, grown on demand
-  double* d_gae_part = nullptr;      // [blocks][2]
+  DevBuf<double> d_gae_part;         // [blocks][2]
   size_t gae_part_cap = 0;           // doubles
-  double* d_obs_part = nullptr;      // [blocks][dim][2]
+  DevBuf<double> d_obs_part;         // [blocks][dim][2]
   size_t obs_part_cap = 0;
   std::string err;
 };
@@ -149,6 +180,63 @@ static thread_local std::string g_err;
       return MOCCA_E_HIP;                                                        \
     }                                                                            \
   } while (0)
+
+// The ABI boundary of the calls that build host images (std::vector, std::string): a failed host allocation is a code and a message.
+static int out_of_host_memory(mocca_handle h, const char* who) {
+  (h ? h->err : g_err) = std::string(who) + ": out of host memory";
+  return MOCCA_E_ARG;
+}
+
+// Attach / replace / detach of what a handle owns (mocca_set_*, mocca_render's scenes) is one sequence: validate; build the new buffers in local
+// DevBufs and upload (`e`: how that went); commit_ready; swap the locals into the handle and set its scalar fields.  commit_ready is the last
+// step that can fail, so a refused call leaves the handle exactly as it was; after it no launch in flight still reads the old buffers.
+static int commit_ready(mocca_handle h, const char* who, hipError_t e = hipSuccess) {
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) return MOCCA_OK;
+  h->err = std::string(who) + ": " + hipGetErrorString(e);
+  return MOCCA_E_HIP;
+}
+
+// The rules of an actor-critic layer table (mocca_controller.h: CTRL_LAYER_WORDS int32 per layer, the actor's layers first), shared by the base
+// controller and the policy: -> "" and the two layer counts, or what is wrong with the first layer that breaks a rule.  `in_dim`: what a net's
+// first layer takes (`first_takes` says so in words; a "%d" in it becomes the width found instead); `head`: the actor's outputs (`ends_in`);
+// `n_params`: floats of the array the weight and bias offsets point into, or NO_OFFSETS where they are not read.  A layer's input is in_dim or
+// the previous layer's output, so it needs no bound of its own.
+constexpr size_t NO_OFFSETS = ~(size_t)0;
+static std::string check_layer_table(const int32_t* layers, int n_layers_total, int in_dim, int head, size_t n_params, const std::string& first_takes,
+                                     const std::string& ends_in, int count[2]) {
+  using namespace mocca_ctrl;
+  if (!layers || n_layers_total < 2 || n_layers_total > 2 * CTRL_MAX_LAYERS) return "needs 1 .. 8 layers for each of the two nets";
+  count[0] = count[1] = 0;
+  int prev_out = 0;
+  for (int i = 0; i < n_layers_total; ++i) {
+    const int32_t* r = layers + (size_t)i * CTRL_LAYER_WORDS;
+    const std::string at = "layer " + std::to_string(i) + ": ";
+    const int net = r[CL_NET];
+    if (net != 0 && net != 1) return at + "net must be 0 (actor) or 1 (critic)";
+    if (i > 0 && net < (r - CTRL_LAYER_WORDS)[CL_NET]) return at + "the actor's layers come first, then the critic's";
+    const bool first = count[net] == 0;
+    if (++count[net] > CTRL_MAX_LAYERS) return at + "more than 8 layers in one net";
+    const int in = r[CL_IN], out = r[CL_OUT];
+    if (first && in != in_dim) {
+      std::string what = first_takes;
+      const size_t k = what.find("%d");
+      return at + (k == std::string::npos ? what : what.replace(k, 2, std::to_string(in)));
+    }
+    if (!first && in != prev_out) return at + "input width differs from the previous layer's output";
+    if (out < 1 || out > CTRL_MAX_WIDTH) return at + "widths must be 1 .. 256";
+    if (r[CL_IN_PAD] != (in + 15) / 16 * 16 || r[CL_OUT_PAD] != (out + 15) / 16 * 16) return at + "in_pad / out_pad must be the widths rounded up to a multiple of 16";
+    if (r[CL_ACT] < CTRL_ACT_IDENTITY || r[CL_ACT] > CTRL_ACT_SOFTSIGN) return at + "unknown activation";
+    const long long w_off = r[CL_W_OFF], b_off = r[CL_B_OFF];
+    if (n_params != NO_OFFSETS && (w_off < 0 || b_off < 0 || (size_t)w_off + (size_t)in * out > n_params || (size_t)b_off + out > n_params))
+      return at + "weights W[out][in] / bias b[out] must lie inside the parameter array";
+    prev_out = out;
+    const bool last = i + 1 == n_layers_total || (r + CTRL_LAYER_WORDS)[CL_NET] != net;
+    if (last && out != (net == 0 ? head : 1)) return at + ends_in;
+    if (!last && (out & 15)) return at + "hidden widths must be multiples of 16";
+  }
+  return count[0] < 1 || count[1] < 1 ? "needs an actor and a critic" : "";
+}
 
 // does the blob give mass or inertia to a link the compiled topology T treats as massless?
 template <class T>
@@ -261,6 +349,12 @@ static int step_instance(const mocca_ctx* h) {
   return INST_FULL;
 }
 
+// copy_param_kernel / set_task_word_kernel: one thread per env, 256 to a workgroup
+template <class... P>
+static void launch_per_env(void (*kernel)(P...), mocca_handle h, hipStream_t s, std::common_type_t<P>... args) {
+  hipLaunchKernelGGL(kernel, dim3((h->n_envs + 255) / 256), dim3(256), 0, s, args...);
+}
+
 extern "C" {
 
 int mocca_abi_version(void) { return MOCCA_ABI_VERSION; }
@@ -268,7 +362,7 @@ size_t mocca_model_sizeof(void) { return sizeof(MoccaModel); }
 
 const char* mocca_last_error(mocca_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
 
-int mocca_create(const void* model_blob, size_t nbytes, int task_id, int n_envs, int device, mocca_handle* out) {
+int mocca_create(const void* model_blob, size_t nbytes, int task_id, int n_envs, int device, mocca_handle* out) try {
   if (!out) return MOCCA_E_ARG;
   *out = nullptr;
   if (!model_blob || nbytes != sizeof(MoccaModel)) { g_err = "model blob has the wrong size"; return MOCCA_E_ARG; }
@@ -277,22 +371,17 @@ int mocca_create(const void* model_blob, size_t nbytes, int task_id, int n_envs,
       task_id != MOCCA_TASK_WALKER3D_PLANNER) {
     g_err = "unknown task id"; return MOCCA_E_ARG;
   }
-  mocca_ctx* h = new (std::nothrow) mocca_ctx();
-  if (!h) return MOCCA_E_ARG;
+  std::unique_ptr<mocca_ctx> h(new mocca_ctx());   // (every return below that is not the last one frees it, and with it what it owns on the device)
   std::memcpy(&h->model, model_blob, sizeof(MoccaModel));
-  if (h->model.magic != MOCCA_MODEL_MAGIC || h->model.version != MOCCA_MODEL_VERSION) {
-    g_err = "bad model blob magic/version"; delete h; return MOCCA_E_ARG;
-  }
+  if (h->model.magic != MOCCA_MODEL_MAGIC || h->model.version != MOCCA_MODEL_VERSION) { g_err = "bad model blob magic/version"; return MOCCA_E_ARG; }
   int rc = check_topology(h->model, task_id, &h->topo, g_err);
-  if (rc != MOCCA_OK) { delete h; return rc; }
+  if (rc != MOCCA_OK) return rc;
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-    g_err = "no such HIP device"; delete h; return MOCCA_E_NODEVICE;
-  }
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { g_err = "no such HIP device"; return MOCCA_E_NODEVICE; }
   h->task_id = task_id; h->n_envs = n_envs; h->device = device;
   h->compact = compact_ok(h->model, h->topo);
   h->wide = wide_needed(h->model);
-  if (h->wide && mocca_r64_args_sizeof() != sizeof(StepArgs)) { g_err = "the 64-row kernel instance was built from another StepArgs"; delete h; return MOCCA_E_ARG; }
+  if (h->wide && mocca_r64_args_sizeof() != sizeof(StepArgs)) { g_err = "the 64-row kernel instance was built from another StepArgs"; return MOCCA_E_ARG; }
   // pace priorities make the waves of a SIMD finish together -- right when all of a batch is resident (or whole generations are); the compact
   // instance exists for batches beyond one generation, whose partial last generation wants its slots refilled one by one: measured 1.5 - 2.5 %
   // slower with the pace than with the row-count priorities (8192 / 16384 envs), so its default is off
@@ -302,80 +391,49 @@ int mocca_create(const void* model_blob, size_t nbytes, int task_id, int n_envs,
                    : 6 + 2 * h->model.n_joints + h->model.n_feet + (task_id == MOCCA_TASK_WALKER3D_STEPPER ? 5 * (h->model.lookbehind + 2) : 2);
   if (task_id == MOCCA_TASK_CASSIE && (h->model.cassie_mode < MOCCA_CASSIE_PLAIN || h->model.cassie_mode > MOCCA_CASSIE_PHASE_MIRROR ||
                                        (h->model.cassie_mode != MOCCA_CASSIE_PLAIN && h->model.n_ordered != 14))) {
-    g_err = "Cassie blob: unknown cassie_mode (the mocap / phase envs need the 14 ordered joints)"; delete h; return MOCCA_E_ARG;
+    g_err = "Cassie blob: unknown cassie_mode (the mocap / phase envs need the 14 ordered joints)"; return MOCCA_E_ARG;
   }
   if (task_id == MOCCA_TASK_WALKER3D_STEPPER &&
       (h->model.n_planks < 1 || h->model.n_planks > MOCCA_MAX_PLANKS || h->model.lookbehind < 1 || h->model.lookbehind > 2)) {
-    g_err = "Stepper blob: n_planks must be 1..4 and lookbehind 1 or 2"; delete h; return MOCCA_E_ARG;
+    g_err = "Stepper blob: n_planks must be 1..4 and lookbehind 1 or 2"; return MOCCA_E_ARG;
   }
   auto fail = [&](const char* what, hipError_t e) {
     g_err = std::string(what) + ": " + hipGetErrorString(e);
-    mocca_destroy(h);
     return MOCCA_E_HIP;
   };
   hipError_t e;
   DeviceGuard guard(device);  // the caller's current device is restored on return
   if ((e = guard.err) != hipSuccess) return fail("hipSetDevice", e);
-  if ((e = hipMalloc(&h->d_model, sizeof(MoccaModel))) != hipSuccess) return fail("hipMalloc(model)", e);
+  if ((e = h->d_model.alloc(1, false)) != hipSuccess) return fail("hipMalloc(model)", e);
   if ((e = hipMemcpy(h->d_model, &h->model, sizeof(MoccaModel), hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy(model)", e);
-  const size_t dyn_b = (size_t)n_envs * DYN_STRIDE * sizeof(float), task_b = (size_t)n_envs * MOCCA_TASK_WORDS * 4;
-  const size_t ter_b = (size_t)n_envs * TERRAIN_STRIDE * sizeof(float);
-  if ((e = hipMalloc(&h->d_dyn, dyn_b)) != hipSuccess) return fail("hipMalloc(state)", e);
-  if ((e = hipMalloc(&h->d_task, task_b)) != hipSuccess) return fail("hipMalloc(task)", e);
-  if ((e = hipMalloc(&h->d_terrain, ter_b)) != hipSuccess) return fail("hipMalloc(terrain)", e);
-  if ((e = hipMalloc(&h->d_pace_acc, sizeof(unsigned long long))) != hipSuccess) return fail("hipMalloc(pace samples)", e);
-  if ((e = hipMemset(h->d_pace_acc, 0, sizeof(unsigned long long))) != hipSuccess) return fail("hipMemset", e);
-  if ((e = hipMemset(h->d_dyn, 0, dyn_b)) != hipSuccess) return fail("hipMemset", e);
-  if ((e = hipMemset(h->d_terrain, 0, ter_b)) != hipSuccess) return fail("hipMemset", e);
+  const size_t n = (size_t)n_envs;
+  if ((e = h->d_dyn.alloc(n * DYN_STRIDE, false)) != hipSuccess) return fail("hipMalloc(state)", e);
+  if ((e = h->d_task.alloc(n * MOCCA_TASK_WORDS, false)) != hipSuccess) return fail("hipMalloc(task)", e);
+  if ((e = h->d_terrain.alloc(n * TERRAIN_STRIDE, true)) != hipSuccess) return fail("hipMalloc(terrain)", e);
+  if ((e = h->d_pace_acc.alloc(1, true)) != hipSuccess) return fail("hipMalloc(pace samples)", e);
   // task records: episode = -1 so the first reset is episode 0; applied_gain = 1
   {
-    uint32_t* tmp = new uint32_t[(size_t)n_envs * MOCCA_TASK_WORDS]();
+    std::vector<uint32_t> tmp(n * MOCCA_TASK_WORDS);
     const float one = 1.0f;
     uint32_t one_bits; std::memcpy(&one_bits, &one, 4);
-    for (int i = 0; i < n_envs; ++i) {
-      tmp[(size_t)i * MOCCA_TASK_WORDS + MOCCA_TW_EPISODE] = (uint32_t)-1;
-      tmp[(size_t)i * MOCCA_TASK_WORDS + MOCCA_TW_APPLIED_GAIN] = one_bits;
+    for (size_t i = 0; i < n; ++i) {
+      tmp[i * MOCCA_TASK_WORDS + MOCCA_TW_EPISODE] = (uint32_t)-1;
+      tmp[i * MOCCA_TASK_WORDS + MOCCA_TW_APPLIED_GAIN] = one_bits;
     }
-    e = hipMemcpy(h->d_task, tmp, task_b, hipMemcpyHostToDevice);
-    delete[] tmp;
-    if (e != hipSuccess) return fail("hipMemcpy(task)", e);
+    if ((e = hipMemcpy(h->d_task, tmp.data(), tmp.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy(task)", e);
   }
   // identity quaternion so an un-reset env is still a valid state
   {
-    float* tmp = new float[(size_t)n_envs * DYN_STRIDE]();
-    for (int i = 0; i < n_envs; ++i) tmp[(size_t)i * DYN_STRIDE + 6] = 1.0f;
-    e = hipMemcpy(h->d_dyn, tmp, dyn_b, hipMemcpyHostToDevice);
-    delete[] tmp;
-    if (e != hipSuccess) return fail("hipMemcpy(state)", e);
+    std::vector<float> tmp(n * DYN_STRIDE);
+    for (size_t i = 0; i < n; ++i) tmp[i * DYN_STRIDE + 6] = 1.0f;
+    if ((e = hipMemcpy(h->d_dyn, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy(state)", e);
   }
-  *out = h;
+  *out = h.release();
   return MOCCA_OK;
-}
+} catch (const std::bad_alloc&) { return out_of_host_memory(nullptr, "mocca_create"); }
 
 int mocca_destroy(mocca_handle h) {
-  if (!h) return MOCCA_OK;
-  if (h->d_model) (void)hipFree(h->d_model);
-  if (h->d_dyn) (void)hipFree(h->d_dyn);
-  if (h->d_task) (void)hipFree(h->d_task);
-  if (h->d_terrain) (void)hipFree(h->d_terrain);
-  if (h->d_traj) (void)hipFree(h->d_traj);
-  if (h->d_hf) (void)hipFree(h->d_hf);
-  if (h->d_scenes) (void)hipFree(h->d_scenes);
-  if (h->d_scan_pts) (void)hipFree(h->d_scan_pts);
-  if (h->d_order) (void)hipFree(h->d_order);
-  if (h->d_pace_acc) (void)hipFree(h->d_pace_acc);
-  if (h->d_ep_ret) (void)hipFree(h->d_ep_ret);
-  for (float* p : h->d_pvec) if (p) (void)hipFree(p);
-  if (h->d_ctrl_params) (void)hipFree(h->d_ctrl_params);
-  if (h->d_ctrl_layers) (void)hipFree(h->d_ctrl_layers);
-  if (h->d_robot_state) (void)hipFree(h->d_robot_state);
-  if (h->d_base_act) (void)hipFree(h->d_base_act);
-  if (h->d_base_val) (void)hipFree(h->d_base_val);
-  if (h->d_pol_image) (void)hipFree(h->d_pol_image);
-  if (h->d_pol_layers) (void)hipFree(h->d_pol_layers);
-  if (h->d_gae_part) (void)hipFree(h->d_gae_part);
-  if (h->d_obs_part) (void)hipFree(h->d_obs_part);
-  delete h;
+  delete h;   // its DevBufs free the device memory
   return MOCCA_OK;
 }
 
@@ -399,9 +457,9 @@ static StepArgs make_args(mocca_handle h) {
   a.auto_reset = h->auto_reset; a.eval_mode = h->eval_mode; a.random_pose = h->random_pose; a.curriculum = h->curriculum;
   a.host_retarget = h->host_retarget; a.env_offset = h->env_offset; a.random_reward = h->random_reward;
   a.seed_lo = (uint32_t)h->seed; a.seed_hi = (uint32_t)(h->seed >> 32);
-  a.curriculum_v = h->pvec_on[0] ? h->d_pvec[0] : nullptr;
-  a.eval_mode_v = h->pvec_on[1] ? h->d_pvec[1] : nullptr;
-  a.gain_v = h->pvec_on[2] ? h->d_pvec[2] : nullptr;
+  a.curriculum_v = h->pvec_on[0] ? h->d_pvec[0].get() : nullptr;
+  a.eval_mode_v = h->pvec_on[1] ? h->d_pvec[1].get() : nullptr;
+  a.gain_v = h->pvec_on[2] ? h->d_pvec[2].get() : nullptr;
   a.gain = h->gain;
   a.dbg = h->dbg;
   a.prio = h->prio;
@@ -412,34 +470,42 @@ static StepArgs make_args(mocca_handle h) {
   a.pace_acc = h->d_pace_acc;
   a.ep_ret = h->d_ep_ret; a.ep_masks = h->ep_masks; a.ep_bad = h->ep_bad; a.ep_totals = h->ep_totals;   // (ep_rec / ep_serial: mocca_step only)
   a.hf = h->d_hf; a.hf_rows = h->hf_rows; a.hf_cols = h->hf_cols; a.hf_scale = h->hf_scale;
-  a.robot_state = h->d_ctrl_params ? h->d_robot_state : nullptr;   // (base_value: mocca_plan_step only)
+  a.robot_state = h->d_ctrl_params ? h->d_robot_state.get() : nullptr;   // (base_value: mocca_plan_step only)
   return a;
 }
 // A scalar MOCCA_PARAM_APPLIED_GAIN is written into the task records (word MOCCA_TW_APPLIED_GAIN, what apply_action reads) by the NEXT call that takes
 // a stream, on that stream: ordered against the caller's in-flight steps, which also write the word (store_task).
 static int flush_pending(mocca_handle h, hipStream_t s) {
   if (!h->gain_pending) return MOCCA_OK;
-  hipLaunchKernelGGL(set_task_word_kernel, dim3((h->n_envs + 255) / 256), dim3(256), 0, s, h->d_task, (int)MOCCA_TW_APPLIED_GAIN, (const float*)nullptr, h->gain, 1, h->n_envs);
+  launch_per_env(set_task_word_kernel, h, s, h->d_task, MOCCA_TW_APPLIED_GAIN, nullptr, h->gain, 1, h->n_envs);
   HIP_TRY(h, hipGetLastError());
   h->gain_pending = false;
   return MOCCA_OK;
 }
-// the mocap / phase envs read their targets, reset poses and reward references from the motion table
-static int need_trajectory(mocca_handle h) {
+// the planner envs stand on the height field (`who`: the calling function and a colon, or nothing; `when`: the end of the sentence)
+static int need_heightfield(mocca_handle h, const char* who, const char* when) {
+  if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER || h->d_hf) return MOCCA_OK;
+  h->err = std::string(who) + "the planner task needs mocca_set_heightfield " + when;
+  return MOCCA_E_ARG;
+}
+// ... and this is what the ray caster and the height scan read of it; the other tasks have no grid
+static mocca_rdr::HeightField heightfield_record(mocca_handle h) {
+  if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER) return mocca_rdr::HeightField{nullptr, 0, 0, 0.0f, 0.0f, 0.0f};
+  return mocca_rdr::HeightField{h->d_hf, h->hf_rows, h->hf_cols, h->hf_scale, h->hf_zmin, h->hf_zmax};
+}
+// what reset / step / observe cannot run without: the mocap / phase envs read their targets, reset poses and reward references from the
+// motion table, the planner envs their ground from the height field
+static int need_attachments(mocca_handle h) {
   if (h->task_id == MOCCA_TASK_CASSIE && h->model.cassie_mode != MOCCA_CASSIE_PLAIN && !h->d_traj) {
     h->err = "this Cassie blob (cassie_mode != 0) needs mocca_set_trajectory before reset / step / observe";
     return MOCCA_E_ARG;
   }
-  if (h->task_id == MOCCA_TASK_WALKER3D_PLANNER && !h->d_hf) {   // the planner envs stand on the height field
-    h->err = "the planner task needs mocca_set_heightfield before reset / step / observe";
-    return MOCCA_E_ARG;
-  }
-  return MOCCA_OK;
+  return need_heightfield(h, "", "before reset / step / observe");
 }
 
 int mocca_reset(mocca_handle h, const uint8_t* mask_dev, uint64_t seed, float* obs_dev, void* stream) {
   if (!h || !obs_dev) return MOCCA_E_ARG;
-  if (need_trajectory(h) != MOCCA_OK) return MOCCA_E_ARG;
+  if (need_attachments(h) != MOCCA_OK) return MOCCA_E_ARG;
   h->seed = seed;
   DeviceGuard guard(h->device);
   StepArgs a = make_args(h);
@@ -493,7 +559,7 @@ static int launch_step(mocca_handle h, const float* act_dev, const float* base_v
 int mocca_step(mocca_handle h, const float* act_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev, int32_t* info_dev,
                void* stream) {
   if (!h || !act_dev || !obs_dev || !rew_dev || !done_dev) return MOCCA_E_ARG;
-  if (need_trajectory(h) != MOCCA_OK) return MOCCA_E_ARG;
+  if (need_attachments(h) != MOCCA_OK) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   return launch_step(h, act_dev, nullptr, obs_dev, rew_dev, done_dev, info_dev, (hipStream_t)stream);
 }
@@ -502,7 +568,7 @@ int mocca_plan_step(mocca_handle h, const float* plan_dev, float* obs_dev, float
                     void* stream) {
   if (!h || !plan_dev || !obs_dev || !rew_dev || !done_dev) return MOCCA_E_ARG;
   if (!h->d_ctrl_params) { h->err = "mocca_plan_step needs a base controller (mocca_set_base_controller)"; return MOCCA_E_ARG; }
-  if (need_trajectory(h) != MOCCA_OK) return MOCCA_E_ARG;
+  if (need_attachments(h) != MOCCA_OK) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   hipStream_t s = (hipStream_t)stream;
   mocca_ctrl::ControllerArgs c{};
@@ -524,45 +590,23 @@ int mocca_get_base_outputs(mocca_handle h, float* action_dev, float* value_dev, 
 }
 
 int mocca_set_base_controller(mocca_handle h, const float* params_host, size_t n_floats, const int32_t* layers_host, int n_layers_total,
-                              double action_scale) {
+                              double action_scale) try {
   using namespace mocca_ctrl;
   if (!h) return MOCCA_E_ARG;
   if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER) { h->err = "mocca_set_base_controller: only the planner task (Walker3DPlannerEnv, MikePlannerEnv) has a base controller"; return MOCCA_E_ARG; }
   DeviceGuard guard(h->device);
   if (!params_host) {   // detach
-    HIP_TRY(h, hipDeviceSynchronize());   // a launch in flight may still read them
-    if (h->d_ctrl_params) (void)hipFree(h->d_ctrl_params);
-    if (h->d_ctrl_layers) (void)hipFree(h->d_ctrl_layers);
-    h->d_ctrl_params = nullptr; h->d_ctrl_layers = nullptr; h->ctrl_n_actor = h->ctrl_n_critic = 0;
+    if (int rc = commit_ready(h, "mocca_set_base_controller")) return rc;
+    h->d_ctrl_params.reset(); h->d_ctrl_layers.reset(); h->ctrl_n_actor = h->ctrl_n_critic = 0;
     return MOCCA_OK;
   }
   auto bad = [&](const std::string& what) { h->err = "mocca_set_base_controller: " + what; return MOCCA_E_ARG; };
-  if (!layers_host || n_layers_total < 2 || n_layers_total > 2 * CTRL_MAX_LAYERS) return bad("needs 1 .. 8 layers for each of the two nets");
   if (n_floats == 0 || n_floats > ((size_t)1 << 28)) return bad("the parameter array is empty or larger than any valid controller");
   if (!std::isfinite(action_scale)) return bad("action_scale is not finite");
-  int count[2] = {0, 0}, prev_out = 0, prev_out_pad = 0;
-  for (int i = 0; i < n_layers_total; ++i) {
-    const int32_t* r = layers_host + (size_t)i * CTRL_LAYER_WORDS;
-    const std::string at = "layer " + std::to_string(i) + ": ";
-    const int net = r[CL_NET];
-    if (net != 0 && net != 1) return bad(at + "net must be 0 (actor) or 1 (critic)");
-    if (i > 0 && net < layers_host[(size_t)(i - 1) * CTRL_LAYER_WORDS + CL_NET]) return bad(at + "the actor's layers come first, then the critic's");
-    const bool first = count[net] == 0;
-    if (++count[net] > CTRL_MAX_LAYERS) return bad(at + "more than 8 layers in one net");
-    const int in = r[CL_IN], out = r[CL_OUT], in_pad = r[CL_IN_PAD], out_pad = r[CL_OUT_PAD];
-    if (in < 1 || in > CTRL_MAX_WIDTH || out < 1 || out > CTRL_MAX_WIDTH) return bad(at + "widths must be 1 .. 256");
-    if (in_pad != (in + 15) / 16 * 16 || out_pad != (out + 15) / 16 * 16) return bad(at + "in_pad / out_pad must be the widths rounded up to a multiple of 16");
-    if (first ? (in != CTRL_IN) : (in != prev_out || in_pad != prev_out_pad)) return bad(at + (first ? "a net's first layer takes the 65-float input" : "input width differs from the previous layer's output"));
-    if (r[CL_ACT] < CTRL_ACT_IDENTITY || r[CL_ACT] > CTRL_ACT_SOFTSIGN) return bad(at + "unknown activation");
-    const long long w_off = r[CL_W_OFF], b_off = r[CL_B_OFF];
-    if (w_off < 0 || b_off < 0 || (unsigned long long)w_off + (size_t)in * out > n_floats || (unsigned long long)b_off + out > n_floats)
-      return bad(at + "weights W[out][in] / bias b[out] must lie inside the parameter array");
-    prev_out = out; prev_out_pad = out_pad;
-    const bool last = i + 1 == n_layers_total || layers_host[(size_t)(i + 1) * CTRL_LAYER_WORDS + CL_NET] != net;
-    if (last && out != (net == 0 ? CTRL_ACTION : 1)) return bad(at + "the actor ends in 21 outputs, the critic in 1");
-    if (!last && (out & 15)) return bad(at + "hidden widths must be multiples of 16");
-  }
-  if (count[0] < 1 || count[1] < 1) return bad("needs an actor and a critic");
+  int count[2];
+  const std::string wrong = check_layer_table(layers_host, n_layers_total, CTRL_IN, CTRL_ACTION, n_floats, "a net's first layer takes the 65-float input",
+                                              "the actor ends in 21 outputs, the critic in 1", count);
+  if (!wrong.empty()) return bad(wrong);
   // the kernel's image (mocca_controller.h): per layer the weights padded with zeros to the 16 x 16 MFMA tile, in fragment order, then the
   // padded bias; the table's offsets point into it
   std::vector<int32_t> table(layers_host, layers_host + (size_t)n_layers_total * CTRL_LAYER_WORDS);
@@ -582,44 +626,31 @@ int mocca_set_base_controller(mocca_handle h, const float* params_host, size_t n
     r[CL_B_OFF] = (int32_t)image.size();
     for (int o = 0; o < 16 * n_ot; ++o) image.push_back(o < out ? b[o] : 0.0f);
   }
-  float* d_p = nullptr;
-  int32_t* d_l = nullptr;
-  const size_t lbytes = table.size() * sizeof(int32_t), n = (size_t)h->n_envs;
-  hipError_t e = hipMalloc(&d_p, image.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_l, lbytes);
-  if (e == hipSuccess) e = hipMemcpy(d_p, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_l, table.data(), lbytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess && !h->d_robot_state) {
-    e = hipMalloc(&h->d_robot_state, n * ROBOT_STATE_STRIDE * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(h->d_robot_state, 0, n * ROBOT_STATE_STRIDE * sizeof(float));
-  }
-  if (e == hipSuccess && !h->d_base_act) {
-    e = hipMalloc(&h->d_base_act, n * CTRL_ACTION * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(h->d_base_act, 0, n * CTRL_ACTION * sizeof(float));
-  }
-  if (e == hipSuccess && !h->d_base_val) {
-    e = hipMalloc(&h->d_base_val, n * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(h->d_base_val, 0, n * sizeof(float));
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();   // no launch in flight still reads the old controller
-  if (e != hipSuccess) {
-    if (d_p) (void)hipFree(d_p);
-    if (d_l) (void)hipFree(d_l);
-    h->err = std::string("mocca_set_base_controller: ") + hipGetErrorString(e);
-    return MOCCA_E_HIP;
-  }
-  if (h->d_ctrl_params) (void)hipFree(h->d_ctrl_params);
-  if (h->d_ctrl_layers) (void)hipFree(h->d_ctrl_layers);
-  h->d_ctrl_params = d_p; h->d_ctrl_layers = d_l;
+  // the per-env buffers outlive a controller: made by the first attach, kept (with their content) by a replace and by a detach
+  DevBuf<float> params, state, act, val;
+  DevBuf<int32_t> layers;
+  const size_t n = (size_t)h->n_envs;
+  hipError_t e = params.alloc(image.size(), false);
+  if (e == hipSuccess) e = layers.alloc(table.size(), false);
+  if (e == hipSuccess) e = hipMemcpy(params, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(layers, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !h->d_robot_state) e = state.alloc(n * ROBOT_STATE_STRIDE, true);
+  if (e == hipSuccess && !h->d_base_act) e = act.alloc(n * CTRL_ACTION, true);
+  if (e == hipSuccess && !h->d_base_val) e = val.alloc(n, true);
+  if (int rc = commit_ready(h, "mocca_set_base_controller", e)) return rc;
+  h->d_ctrl_params.swap(params); h->d_ctrl_layers.swap(layers);
+  if (state) h->d_robot_state.swap(state);
+  if (act) h->d_base_act.swap(act);
+  if (val) h->d_base_val.swap(val);
   h->ctrl_n_actor = count[0]; h->ctrl_n_critic = count[1]; h->ctrl_scale = (float)action_scale;
   return MOCCA_OK;
-}
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_base_controller"); }
 
 int mocca_task_step(mocca_handle h, const float* act_dev, const int32_t* touch_dev, const int32_t* target_dev, const int32_t* body_dev,
                     float* obs_dev, float* rew_dev, uint8_t* done_dev, int32_t* info_dev, void* stream) {
   if (!h || !act_dev || !obs_dev || !rew_dev || !done_dev) return MOCCA_E_ARG;
   if (!touch_dev && h->task_id != MOCCA_TASK_CASSIE) { h->err = "mocca_task_step needs the foot contact flags"; return MOCCA_E_ARG; }
-  if (need_trajectory(h) != MOCCA_OK) return MOCCA_E_ARG;
+  if (need_attachments(h) != MOCCA_OK) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   StepArgs a = make_args(h);
   a.act = act_dev; a.obs = obs_dev; a.rew = rew_dev; a.done = done_dev; a.info = info_dev;
@@ -659,12 +690,10 @@ int mocca_set_episode_stats(mocca_handle h, float* masks_dev, float* bad_masks_d
   }
   DeviceGuard guard(h->device);
   if (on && !h->d_ep_ret) {
-    HIP_TRY(h, hipMalloc(&h->d_ep_ret, (size_t)h->n_envs * sizeof(float)));
-    HIP_TRY(h, hipMemset(h->d_ep_ret, 0, (size_t)h->n_envs * sizeof(float)));
+    HIP_TRY(h, h->d_ep_ret.alloc((size_t)h->n_envs, true));
   } else if (!on && h->d_ep_ret) {
     HIP_TRY(h, hipDeviceSynchronize());   // a launch in flight may still add to it
-    HIP_TRY(h, hipFree(h->d_ep_ret));
-    h->d_ep_ret = nullptr;
+    h->d_ep_ret.reset();
   }
   h->ep_masks = masks_dev; h->ep_bad = bad_masks_dev; h->ep_totals = totals_dev;
   h->ep_rec = (char*)records; h->ep_slots = records ? n_slots : 0; h->ep_stride = records ? slot_stride_bytes : 0;
@@ -691,17 +720,17 @@ int mocca_set_trajectory(mocca_handle h, const float* table_host, int n_frames, 
   if (!h) return MOCCA_E_ARG;
   if (!table_host || n_frames <= 0 || !(max_time > 0.0) || !(control_step > 0.0)) { h->err = "mocca_set_trajectory: empty table or non-positive times"; return MOCCA_E_ARG; }
   DeviceGuard guard(h->device);
-  const size_t bytes = (size_t)n_frames * MOCCA_TRAJ_STRIDE * sizeof(float);
-  float* d = nullptr;
-  HIP_TRY(h, hipMalloc(&d, bytes));
-  hipError_t e = hipMemcpy(d, table_host, bytes, hipMemcpyHostToDevice);   // synchronous: no kernel in flight still reads the old table
-  if (e != hipSuccess) { (void)hipFree(d); h->err = std::string("hipMemcpy(trajectory): ") + hipGetErrorString(e); return MOCCA_E_HIP; }
-  if (h->d_traj) { (void)hipDeviceSynchronize(); (void)hipFree(h->d_traj); }
-  h->d_traj = d; h->traj_n = n_frames; h->traj_tmax = max_time; h->traj_cstep = control_step;
+  const size_t floats = (size_t)n_frames * MOCCA_TRAJ_STRIDE;
+  DevBuf<float> traj;
+  hipError_t e = traj.alloc(floats, false);
+  if (e == hipSuccess) e = hipMemcpy(traj, table_host, floats * sizeof(float), hipMemcpyHostToDevice);
+  if (int rc = commit_ready(h, "mocca_set_trajectory", e)) return rc;
+  h->d_traj.swap(traj);
+  h->traj_n = n_frames; h->traj_tmax = max_time; h->traj_cstep = control_step;
   return MOCCA_OK;
 }
 
-int mocca_set_heightfield(mocca_handle h, const float* heights_host, int rows, int cols, double scale) {
+int mocca_set_heightfield(mocca_handle h, const float* heights_host, int rows, int cols, double scale) try {
   if (!h) return MOCCA_E_ARG;
   if (!heights_host || rows < 2 || cols < 2 || !(scale > 0.0)) { h->err = "mocca_set_heightfield: needs at least 2 x 2 heights and a positive scale"; return MOCCA_E_ARG; }
   // Search window of every terrain contact slot: a sphere of reach rho = radius + margin around a centre that is at most half a cell from
@@ -722,12 +751,11 @@ int mocca_set_heightfield(mocca_handle h, const float* heights_host, int rows, i
   DeviceGuard guard(h->device);
   // the heights, followed by one max-pooled copy per window 2 .. wmax (copy k: the highest point within k + 1 cells of each grid point): what a
   // wide sphere's search is pruned by with one load
-  const size_t cells = (size_t)rows * cols, bytes = cells * wmax * sizeof(float);
-  float* host = new (std::nothrow) float[cells * wmax];
-  if (!host) { h->err = "mocca_set_heightfield: out of host memory"; return MOCCA_E_ARG; }
-  std::memcpy(host, heights_host, cells * sizeof(float));
+  const size_t cells = (size_t)rows * cols;
+  std::vector<float> host(cells * wmax);
+  std::memcpy(host.data(), heights_host, cells * sizeof(float));
   for (int w = 2; w <= wmax; ++w) {
-    float* out = host + cells * (w - 1);
+    float* out = host.data() + cells * (w - 1);
     for (int j = 0; j < rows; ++j)
       for (int i = 0; i < cols; ++i) {
         float m = -1e30f;
@@ -737,34 +765,31 @@ int mocca_set_heightfield(mocca_handle h, const float* heights_host, int rows, i
         out[(size_t)j * cols + i] = m;
       }
   }
-  float* d = nullptr;
-  hipError_t e = hipMalloc(&d, bytes);
-  if (e == hipSuccess) e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);   // synchronous: no kernel in flight still reads the old grid
-  delete[] host;
-  if (e != hipSuccess) { if (d) (void)hipFree(d); h->err = std::string("mocca_set_heightfield: ") + hipGetErrorString(e); return MOCCA_E_HIP; }
-  (void)hipDeviceSynchronize();   // ... nor the old slot records
-  // the window bits go into a COPY of the model; the handle's host image takes them only once the device has them (a failed upload leaves
-  // host and device records as they were: "refused and leaves the handle intact")
-  MoccaModel* next = new (std::nothrow) MoccaModel(h->model);
-  if (!next) { (void)hipFree(d); h->err = "mocca_set_heightfield: out of host memory"; return MOCCA_E_ARG; }
+  // the window bits go into a COPY of the model; the handle's host image takes them only once the device has them
+  auto next = std::make_unique<MoccaModel>(h->model);
   for (int sl = 0; sl < next->n_slots; ++sl) std::memcpy(&next->slot_tab[sl][2], &wbits[sl], 4);
-  e = hipMemcpy(h->d_model, next, sizeof(MoccaModel), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { delete next; (void)hipFree(d); h->err = std::string("hipMemcpy(model): ") + hipGetErrorString(e); return MOCCA_E_HIP; }
+  DevBuf<float> hf;
+  hipError_t e = hf.alloc(host.size(), false);
+  if (e == hipSuccess) e = hipMemcpy(hf, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (int rc = commit_ready(h, "mocca_set_heightfield", e)) return rc;   // no launch in flight still reads the old grid or the old slot records
+  // the device model is rewritten in place: the last step that can fail, and one that fails leaves host and device records as they were
+  if ((e = hipMemcpy(h->d_model, next.get(), sizeof(MoccaModel), hipMemcpyHostToDevice)) != hipSuccess) {
+    h->err = std::string("hipMemcpy(model): ") + hipGetErrorString(e); return MOCCA_E_HIP;
+  }
   h->model = *next;
-  delete next;
-  if (h->d_hf) (void)hipFree(h->d_hf);
-  h->d_hf = d; h->hf_rows = rows; h->hf_cols = cols; h->hf_scale = (float)scale;
+  h->d_hf.swap(hf);
+  h->hf_rows = rows; h->hf_cols = cols; h->hf_scale = (float)scale;
   h->hf_zmin = h->hf_zmax = heights_host[0];
   for (size_t k = 1; k < cells; ++k) {
     h->hf_zmin = heights_host[k] < h->hf_zmin ? heights_host[k] : h->hf_zmin;
     h->hf_zmax = heights_host[k] > h->hf_zmax ? heights_host[k] : h->hf_zmax;
   }
   return MOCCA_OK;
-}
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_heightfield"); }
 
 int mocca_observe(mocca_handle h, float* obs_dev, void* stream) {
   if (!h || !obs_dev) return MOCCA_E_ARG;
-  if (need_trajectory(h) != MOCCA_OK) return MOCCA_E_ARG;
+  if (need_attachments(h) != MOCCA_OK) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   StepArgs a = make_args(h);
   a.obs = obs_dev;
@@ -849,7 +874,7 @@ int mocca_set_param(mocca_handle h, int param_id, double value) {
       h->order_every = (int)value; h->order_age = h->order_every;
       if (h->order_every > 0 && !h->d_order) {   // (allocated here, not in mocca_step)
         DeviceGuard guard(h->device);
-        HIP_TRY(h, hipMalloc(&h->d_order, (size_t)h->n_envs * sizeof(int32_t)));
+        HIP_TRY(h, h->d_order.alloc((size_t)h->n_envs, false));
       }
       break;
     case MOCCA_PARAM_KERNEL_VARIANT:
@@ -866,15 +891,15 @@ int mocca_set_param_v(mocca_handle h, int param_id, const float* values_dev, int
   const int slot = param_id == MOCCA_PARAM_CURRICULUM ? 0 : param_id == MOCCA_PARAM_EVAL_MODE ? 1 : param_id == MOCCA_PARAM_APPLIED_GAIN ? 2 : -1;
   if (slot < 0) { h->err = "this parameter has no per-env form"; return MOCCA_E_ARG; }
   DeviceGuard guard(h->device);
-  if (!h->d_pvec[slot]) HIP_TRY(h, hipMalloc(&h->d_pvec[slot], (size_t)h->n_envs * sizeof(float)));
+  if (!h->d_pvec[slot]) HIP_TRY(h, h->d_pvec[slot].alloc((size_t)h->n_envs, false));
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(copy_param_kernel, dim3((h->n_envs + 255) / 256), dim3(256), 0, s, h->d_pvec[slot], values_dev, broadcast != 0, h->n_envs);
+  launch_per_env(copy_param_kernel, h, s, h->d_pvec[slot], values_dev, broadcast != 0, h->n_envs);
   HIP_TRY(h, hipGetLastError());
   if (slot == 2) {  // applied_gain acts at once (robots.py:33)
     // the per-env values supersede a scalar mocca_set_param(APPLIED_GAIN) that was not flushed yet: left pending, the next call with a
     // stream would overwrite every env's word with the stale scalar (call order must win, as it did when the scalar write was synchronous)
     h->gain_pending = false;
-    hipLaunchKernelGGL(set_task_word_kernel, dim3((h->n_envs + 255) / 256), dim3(256), 0, s, h->d_task, (int)MOCCA_TW_APPLIED_GAIN, (const float*)h->d_pvec[slot], 0.0f, 0, h->n_envs);
+    launch_per_env(set_task_word_kernel, h, s, h->d_task, MOCCA_TW_APPLIED_GAIN, h->d_pvec[slot], 0.0f, 0, h->n_envs);
     HIP_TRY(h, hipGetLastError());
   }
   h->pvec_on[slot] = true;
@@ -897,16 +922,14 @@ int mocca_get_link_frames(mocca_handle h, float* frames_dev, void* stream) {
 }
 
 int mocca_render(mocca_handle h, const int32_t* env_ids_dev, int n_views, const float* cameras_dev, int width, int height, uint8_t* rgb_dev,
-                 float* depth_dev, int32_t* id_dev, void* stream) {
+                 float* depth_dev, int32_t* id_dev, void* stream) try {
   if (!h) return MOCCA_E_ARG;
   if (!env_ids_dev || !cameras_dev) { h->err = "mocca_render: env_ids_dev and cameras_dev must not be NULL"; return MOCCA_E_ARG; }
   if (n_views < 1 || n_views > 65535) { h->err = "mocca_render: n_views must be 1 .. 65535"; return MOCCA_E_ARG; }
   if (width < 1 || height < 1 || width > MOCCA_RENDER_MAX_SIZE || height > MOCCA_RENDER_MAX_SIZE) {
     h->err = "mocca_render: width and height must be 1 .. " + std::to_string(MOCCA_RENDER_MAX_SIZE); return MOCCA_E_ARG;
   }
-  if (h->task_id == MOCCA_TASK_WALKER3D_PLANNER && !h->d_hf) {
-    h->err = "mocca_render: the planner task needs mocca_set_heightfield first"; return MOCCA_E_ARG;
-  }
+  if (need_heightfield(h, "mocca_render: ", "first") != MOCCA_OK) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   hipStream_t s = (hipStream_t)stream;
   std::vector<int32_t> ids((size_t)n_views);
@@ -917,28 +940,27 @@ int mocca_render(mocca_handle h, const int32_t* env_ids_dev, int n_views, const 
       h->err = "mocca_render: env index " + std::to_string(ids[v]) + " (view " + std::to_string(v) + ") is outside 0 .. " + std::to_string(h->n_envs - 1);
       return MOCCA_E_ARG;
     }
-  if (n_views > h->scenes_cap) {
-    if (h->d_scenes) { HIP_TRY(h, hipFree(h->d_scenes)); h->d_scenes = nullptr; h->scenes_cap = 0; }   // (hipFree waits for the launches that read it)
-    HIP_TRY(h, hipMalloc(&h->d_scenes, (size_t)n_views * mocca_rdr::SCENE_WORDS * sizeof(float)));
+  if (n_views > h->scenes_cap) {   // grow: an earlier render in flight may still read the old scenes
+    DevBuf<float> scenes;
+    if (int rc = commit_ready(h, "mocca_render", scenes.alloc((size_t)n_views * mocca_rdr::SCENE_WORDS, false))) return rc;
+    h->d_scenes.swap(scenes);
     h->scenes_cap = n_views;
   }
   if (int rc = flush_pending(h, s)) return rc;
   mocca_rdr::launch_scene(s, scene_args(h), env_ids_dev, h->n_envs, n_views, h->d_scenes);
   HIP_TRY(h, hipGetLastError());
-  mocca_rdr::HeightField hf{nullptr, 0, 0, 0.0f, 0.0f, 0.0f};
-  if (h->task_id == MOCCA_TASK_WALKER3D_PLANNER) hf = mocca_rdr::HeightField{h->d_hf, h->hf_rows, h->hf_cols, h->hf_scale, h->hf_zmin, h->hf_zmax};
-  mocca_rdr::launch_raycast(s, h->d_scenes, cameras_dev, n_views, width, height, h->task_id, h->model.plank_shape, h->model.plank_half, hf,
-                               rgb_dev, depth_dev, id_dev);
+  mocca_rdr::launch_raycast(s, h->d_scenes, cameras_dev, n_views, width, height, h->task_id, h->model.plank_shape, h->model.plank_half,
+                            heightfield_record(h), rgb_dev, depth_dev, id_dev);
   HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
-}
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_render"); }
 
 int mocca_set_height_scan(mocca_handle h, const float* points_host, int n_points, double z_above, double max_drop) {
   if (!h) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   if (!points_host) {   // detach
-    if (h->d_scan_pts) { HIP_TRY(h, hipDeviceSynchronize()); (void)hipFree(h->d_scan_pts); }   // a launch in flight may still read them
-    h->d_scan_pts = nullptr; h->scan_n = 0;
+    if (int rc = commit_ready(h, "mocca_set_height_scan")) return rc;
+    h->d_scan_pts.reset(); h->scan_n = 0;
     return MOCCA_OK;
   }
   auto bad = [&](const std::string& what) { h->err = "mocca_set_height_scan: " + what; return MOCCA_E_ARG; };
@@ -946,13 +968,12 @@ int mocca_set_height_scan(mocca_handle h, const float* points_host, int n_points
   if (!std::isfinite(z_above) || !std::isfinite(max_drop) || z_above < 0.0 || !(max_drop > 0.0)) return bad("needs a finite z_above >= 0 and max_drop > 0");
   for (int k = 0; k < 2 * n_points; ++k)
     if (!std::isfinite(points_host[k])) return bad("point " + std::to_string(k / 2) + " is not finite");
-  float* d = nullptr;
-  HIP_TRY(h, hipMalloc(&d, (size_t)n_points * 2 * sizeof(float)));
-  hipError_t e = hipMemcpy(d, points_host, (size_t)n_points * 2 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && h->d_scan_pts) e = hipDeviceSynchronize();   // no launch in flight still reads the old pattern
-  if (e != hipSuccess) { (void)hipFree(d); h->err = std::string("mocca_set_height_scan: ") + hipGetErrorString(e); return MOCCA_E_HIP; }
-  if (h->d_scan_pts) (void)hipFree(h->d_scan_pts);
-  h->d_scan_pts = d; h->scan_n = n_points; h->scan_above = (float)z_above; h->scan_drop = (float)max_drop;
+  DevBuf<float> pts;
+  hipError_t e = pts.alloc((size_t)n_points * 2, false);
+  if (e == hipSuccess) e = hipMemcpy(pts, points_host, (size_t)n_points * 2 * sizeof(float), hipMemcpyHostToDevice);
+  if (int rc = commit_ready(h, "mocca_set_height_scan", e)) return rc;
+  h->d_scan_pts.swap(pts);
+  h->scan_n = n_points; h->scan_above = (float)z_above; h->scan_drop = (float)max_drop;
   return MOCCA_OK;
 }
 
@@ -967,14 +988,11 @@ int mocca_height_scan(mocca_handle h, float* out_dev, int row_stride, const floa
     h->err = "mocca_height_scan: row_stride " + std::to_string(row_stride) + " is smaller than the row (" + std::to_string(width) + " floats)";
     return MOCCA_E_ARG;
   }
-  if (h->task_id == MOCCA_TASK_WALKER3D_PLANNER && !h->d_hf) {
-    h->err = "mocca_height_scan: the planner task needs mocca_set_heightfield first"; return MOCCA_E_ARG;
-  }
+  if (need_heightfield(h, "mocca_height_scan: ", "first") != MOCCA_OK) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   mocca_scan::ScanArgs a{};
   a.scene = scene_args(h);
-  a.hf = mocca_rdr::HeightField{nullptr, 0, 0, 0.0f, 0.0f, 0.0f};
-  if (h->task_id == MOCCA_TASK_WALKER3D_PLANNER) a.hf = mocca_rdr::HeightField{h->d_hf, h->hf_rows, h->hf_cols, h->hf_scale, h->hf_zmin, h->hf_zmax};
+  a.hf = heightfield_record(h);
   a.points = h->d_scan_pts; a.n_points = h->scan_n; a.z_above = h->scan_above; a.max_drop = h->scan_drop;
   a.out = out_dev; a.row_stride = row_stride; a.obs = obs_dev; a.obs_dim = obs_dev ? h->obs_dim : 0;
   mocca_scan::launch_height_scan((hipStream_t)stream, a, h->n_envs);
@@ -982,45 +1000,26 @@ int mocca_height_scan(mocca_handle h, float* out_dev, int row_stride, const floa
   return MOCCA_OK;
 }
 
-int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) {
+int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) try {
   using namespace mocca_ctrl;
   using namespace mocca_pol;
   if (!h) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   if (!layers_host) {   // detach
-    if (h->d_pol_image) HIP_TRY(h, hipDeviceSynchronize());   // a launch in flight may still read it
-    if (h->d_pol_image) (void)hipFree(h->d_pol_image);
-    if (h->d_pol_layers) (void)hipFree(h->d_pol_layers);
-    h->d_pol_image = nullptr; h->d_pol_layers = nullptr; h->pol_filled = false;
+    if (int rc = commit_ready(h, "mocca_set_policy")) return rc;
+    h->d_pol_image.reset(); h->d_pol_layers.reset(); h->pol_filled = false;
     return MOCCA_OK;
   }
   auto bad = [&](const std::string& what) { h->err = "mocca_set_policy: " + what; return MOCCA_E_ARG; };
-  if (n_layers_total < 2 || n_layers_total > 2 * POL_MAX_LAYERS) return bad("needs 1 .. 8 layers for each of the two nets");
   if (in_dim < 1 || in_dim > POL_MAX_IN) return bad("in_dim must be 1 .. " + std::to_string(POL_MAX_IN));
   if (act_dim < 1 || act_dim > POL_MAX_ACTION) return bad("act_dim must be 1 .. " + std::to_string(POL_MAX_ACTION));
   if (!std::isfinite(clip) || !(clip > 0.0)) return bad("clip must be finite and positive");
   const int in_pad = (in_dim + 15) / 16 * 16;
-  int count[2] = {0, 0}, prev_out = 0;
-  for (int i = 0; i < n_layers_total; ++i) {
-    const int32_t* r = layers_host + (size_t)i * CTRL_LAYER_WORDS;
-    const std::string at = "layer " + std::to_string(i) + ": ";
-    const int net = r[CL_NET];
-    if (net != 0 && net != 1) return bad(at + "net must be 0 (actor) or 1 (critic)");
-    if (i > 0 && net < layers_host[(size_t)(i - 1) * CTRL_LAYER_WORDS + CL_NET]) return bad(at + "the actor's layers come first, then the critic's");
-    const bool first = count[net] == 0;
-    if (++count[net] > POL_MAX_LAYERS) return bad(at + "more than 8 layers in one net");
-    const int in = r[CL_IN], out = r[CL_OUT];
-    if (first && in != in_dim) return bad(at + "a net's first layer takes in_dim = " + std::to_string(in_dim) + " inputs, not " + std::to_string(in));
-    if (!first && in != prev_out) return bad(at + "input width differs from the previous layer's output");
-    if (out < 1 || out > POL_MAX_WIDTH) return bad(at + "widths must be 1 .. 256");
-    if (r[CL_IN_PAD] != (in + 15) / 16 * 16 || r[CL_OUT_PAD] != (out + 15) / 16 * 16) return bad(at + "in_pad / out_pad must be the widths rounded up to a multiple of 16");
-    if (r[CL_ACT] < CTRL_ACT_IDENTITY || r[CL_ACT] > CTRL_ACT_SOFTSIGN) return bad(at + "unknown activation");
-    prev_out = out;
-    const bool last = i + 1 == n_layers_total || layers_host[(size_t)(i + 1) * CTRL_LAYER_WORDS + CL_NET] != net;
-    if (last && out != (net == 0 ? act_dim : 1)) return bad(at + "the actor ends in act_dim = " + std::to_string(act_dim) + " outputs, the critic in 1");
-    if (!last && (out & 15)) return bad(at + "hidden widths must be multiples of 16");
-  }
-  if (count[0] < 1 || count[1] < 1) return bad("needs an actor and a critic");
+  int count[2];
+  const std::string wrong = check_layer_table(layers_host, n_layers_total, in_dim, act_dim, NO_OFFSETS,
+                                              "a net's first layer takes in_dim = " + std::to_string(in_dim) + " inputs, not %d",
+                                              "the actor ends in act_dim = " + std::to_string(act_dim) + " outputs, the critic in 1", count);
+  if (!wrong.empty()) return bad(wrong);
   // the image (mocca_policy.h) and the rows that tell the repack kernel where each piece of the caller's flat parameters goes
   std::vector<int32_t> table(layers_host, layers_host + (size_t)n_layers_total * CTRL_LAYER_WORDS);
   RepackArgs rp{};
@@ -1046,29 +1045,19 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
   pa.mean_off = row(in_pad, -1, 0, in_dim, 0, 0.0f);
   pa.inv_std_off = row(in_pad, -1, 0, in_dim, 0, 0.0f);
   rp.n_rows = nr; rp.image_floats = pos;
-  float* d_p = nullptr;
-  int32_t* d_l = nullptr;
-  const size_t lbytes = table.size() * sizeof(int32_t);
-  hipError_t e = hipMalloc(&d_p, (size_t)pos * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_l, lbytes);
-  if (e == hipSuccess) e = hipMemset(d_p, 0, (size_t)pos * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(d_l, table.data(), lbytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();   // no launch in flight still reads the old policy
-  if (e != hipSuccess) {
-    if (d_p) (void)hipFree(d_p);
-    if (d_l) (void)hipFree(d_l);
-    h->err = std::string("mocca_set_policy: ") + hipGetErrorString(e);
-    return MOCCA_E_HIP;
-  }
-  if (h->d_pol_image) (void)hipFree(h->d_pol_image);
-  if (h->d_pol_layers) (void)hipFree(h->d_pol_layers);
-  h->d_pol_image = d_p; h->d_pol_layers = d_l;
-  pa.params = d_p; pa.layers = d_l; pa.n_actor = count[0]; pa.n_critic = count[1];
+  DevBuf<float> image;
+  DevBuf<int32_t> layers;
+  hipError_t e = image.alloc((size_t)pos, true);
+  if (e == hipSuccess) e = layers.alloc(table.size(), false);
+  if (e == hipSuccess) e = hipMemcpy(layers, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (int rc = commit_ready(h, "mocca_set_policy", e)) return rc;
+  h->d_pol_image.swap(image); h->d_pol_layers.swap(layers);
+  pa.params = h->d_pol_image; pa.layers = h->d_pol_layers; pa.n_actor = count[0]; pa.n_critic = count[1];
   pa.in_dim = in_dim; pa.in_pad = in_pad; pa.act_dim = act_dim; pa.clip = (float)clip;
-  rp.image = d_p;
+  rp.image = h->d_pol_image;
   h->pol = pa; h->pol_repack = rp; h->pol_n_base = (size_t)src; h->pol_filled = false;
   return MOCCA_OK;
-}
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy"); }
 
 int mocca_update_policy(mocca_handle h, const float* params_dev, size_t n_floats, void* stream) {
   if (!h) return MOCCA_E_ARG;
@@ -1132,7 +1121,7 @@ int mocca_act_step(mocca_handle h, const float* in_dev, int in_stride, const flo
     h->err = "mocca_act_step: the policy's act_dim (" + std::to_string(h->pol.act_dim) + ") is not the env's (" + std::to_string(mocca_act_dim(h)) + ")";
     return MOCCA_E_ARG;
   }
-  if (need_trajectory(h) != MOCCA_OK) return MOCCA_E_ARG;
+  if (need_attachments(h) != MOCCA_OK) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   hipStream_t s = (hipStream_t)stream;
   if (int rc = launch_act(h, "mocca_act_step", in_dev, in_stride, eps_dev, deterministic, action_dev, logp_dev, value_dev, mean_dev, s)) return rc;
@@ -1140,15 +1129,14 @@ int mocca_act_step(mocca_handle h, const float* in_dev, int in_stride, const flo
 }
 
 // scratch of the rollout kernels: allocated on the first call and on one that needs more; only such a call synchronises
-static int grow_scratch(mocca_handle h, const char* who, double** buf, size_t* cap, size_t need) {
+static int grow_scratch(mocca_handle h, const char* who, DevBuf<double>& buf, size_t* cap, size_t need) {
   if (need <= *cap) return MOCCA_OK;
-  hipError_t e = hipSuccess;
-  if (*buf) e = hipDeviceSynchronize();   // a launch in flight may still use the old one
-  double* p = nullptr;
-  if (e == hipSuccess) e = hipMalloc(&p, need * sizeof(double));
+  DevBuf<double> next;
+  hipError_t e = buf ? hipDeviceSynchronize() : hipSuccess;   // a launch in flight may still use the old one
+  if (e == hipSuccess) e = next.alloc(need, false);
   if (e != hipSuccess) { h->err = std::string(who) + ": scratch: " + hipGetErrorString(e); return MOCCA_E_HIP; }
-  if (*buf) (void)hipFree(*buf);
-  *buf = p; *cap = need;
+  buf.swap(next);
+  *cap = need;
   return MOCCA_OK;
 }
 
@@ -1166,7 +1154,7 @@ int mocca_gae(mocca_handle h, const float* rew_dev, const float* value_dev, cons
   if (!std::isfinite(adv_eps) || adv_eps < 0.0) return bad("adv_eps must be finite and not negative");
   DeviceGuard guard(h->device);
   const int blocks = mocca_ro::gae_blocks(h->n_envs);
-  if (int rc = grow_scratch(h, "mocca_gae", &h->d_gae_part, &h->gae_part_cap, 2 * (size_t)blocks)) return rc;
+  if (int rc = grow_scratch(h, "mocca_gae", h->d_gae_part, &h->gae_part_cap, 2 * (size_t)blocks)) return rc;
   mocca_ro::GaeArgs a{};
   a.rew = rew_dev; a.value = value_dev; a.masks = masks_dev; a.bad_masks = bad_masks_dev; a.returns = returns_dev; a.adv = adv_dev;
   a.partials = h->d_gae_part; a.n_envs = h->n_envs; a.n_steps = n_steps;
@@ -1195,7 +1183,7 @@ int mocca_obs_stats(mocca_handle h, const float* rows_dev, int64_t n_rows, int r
   mocca_ro::ObsArgs a{};
   a.rows = rows_dev; a.n_rows = n_rows; a.row_stride = row_stride; a.dim = dim;
   mocca_ro::obs_grid(n_rows, dim, &a.rows_per_block, &a.n_blocks);
-  if (int rc = grow_scratch(h, "mocca_obs_stats", &h->d_obs_part, &h->obs_part_cap, 2 * (size_t)a.n_blocks * dim)) return rc;
+  if (int rc = grow_scratch(h, "mocca_obs_stats", h->d_obs_part, &h->obs_part_cap, 2 * (size_t)a.n_blocks * dim)) return rc;
   a.state = state_dev; a.partials = h->d_obs_part; a.eps = (float)eps; a.mean_out = mean_dev; a.inv_std_out = inv_std_dev;
   mocca_ro::launch_obs_stats((hipStream_t)stream, a);
   HIP_TRY(h, hipGetLastError());

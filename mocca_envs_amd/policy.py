@@ -11,33 +11,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from .controller import ACTIVATIONS, MAX_LAYERS, MAX_WIDTH, _apply, _round16, layers_from_sequential
+from .controller import _apply, _net, _round16, layer_table, layers_from_sequential, pack_nets, unpack_nets
 
 MAX_IN, MAX_ACTION, FLAG_WORDS = 336, 32, 4       # csrc/mocca_policy.h POL_MAX_IN / POL_MAX_ACTION / POL_FLAG_WORDS
 HALF_LOG_2PI = 0.9189385332046727
-
-
-def _net(layers, in_dim, out_dim, name):
-    """validated copy of one net: [(W f32 [out][in], b f32 [out], activation)]"""
-    layers = list(layers)
-    if not 1 <= len(layers) <= MAX_LAYERS:
-        raise ValueError(f"{name}: between 1 and {MAX_LAYERS} layers")
-    net, fan_in = [], in_dim
-    for i, (w, b, act) in enumerate(layers):
-        w = np.array(w, dtype=np.float32, order="C")
-        b = np.array(b, dtype=np.float32).reshape(-1)
-        if act not in ACTIVATIONS:
-            raise ValueError(f"{name}[{i}]: unknown activation {act!r} (one of {ACTIVATIONS})")
-        if w.ndim != 2 or w.shape[1] != fan_in or b.size != w.shape[0]:
-            raise ValueError(f"{name}[{i}]: expected W[out][{fan_in}] and b[out]")
-        fan_in = w.shape[0]
-        if i + 1 == len(layers):
-            if fan_in != out_dim:
-                raise ValueError(f"{name}: the last layer has {fan_in} outputs, not {out_dim}")
-        elif fan_in % 16 or fan_in > MAX_WIDTH:
-            raise ValueError(f"{name}[{i}]: hidden width {fan_in} is not a multiple of 16 up to {MAX_WIDTH}")
-        net.append((w, b, act))
-    return net
 
 
 class DevicePolicy:
@@ -112,8 +89,7 @@ class DevicePolicy:
     # ---- what the library takes (include/mocca.h mocca_set_policy / mocca_update_policy) ----
     def table(self):
         """int32 [layers][8], the actor first: net, in, out, in_pad, out_pad, activation id, 0, 0"""
-        return np.array([[net_id, w.shape[1], w.shape[0], _round16(w.shape[1]), _round16(w.shape[0]), ACTIVATIONS.index(act), 0, 0]
-                         for net_id, net in enumerate((self.actor, self.critic)) for w, b, act in net], np.int32)
+        return layer_table(self.actor, self.critic)
 
     def flat_params(self):
         """float32 [n]: per layer W[out][in] row-major then b[out], then log_std, then (with normalisation) mean and inv_std"""
@@ -126,19 +102,8 @@ class DevicePolicy:
     def pack(self):
         """-> (image float32 [n], table int32 [layers][8] with the weight / bias offsets, offsets dict): per layer the controller's fragment
         order (controller.BaseController.pack), then log_std [32], flags [4] (flags[0] = 1: normalise), mean and inv_std [in_pad]"""
-        params, table, pos = [], self.table(), 0
-        for row, (w, b, _) in zip(table, self.actor + self.critic):
-            n_out, n_in = w.shape
-            p_out, p_in = int(row[4]), int(row[3])
-            full = np.zeros((p_out, p_in), np.float32)
-            full[:n_out, :n_in] = w
-            image = full.reshape(p_out // 16, 16, p_in // 16, 4, 4).transpose(0, 2, 3, 1, 4).reshape(-1)
-            bias = np.zeros(p_out, np.float32)
-            bias[:n_out] = b
-            row[6], row[7] = pos, pos + image.size
-            params += [image, bias]
-            pos += image.size + p_out
-        in_pad = _round16(self.in_dim)
+        params, table = pack_nets(self.actor, self.critic)
+        pos, in_pad = params.size, _round16(self.in_dim)
         tail = np.zeros(MAX_ACTION + FLAG_WORDS + 2 * in_pad, np.float32)
         tail[:self.act_dim] = self.log_std
         if self.obs_mean is not None:
@@ -147,19 +112,13 @@ class DevicePolicy:
             tail[MAX_ACTION + FLAG_WORDS + in_pad:][:self.in_dim] = self.inv_std
         offsets = {"log_std": pos, "flags": pos + MAX_ACTION, "mean": pos + MAX_ACTION + FLAG_WORDS, "inv_std": pos + MAX_ACTION + FLAG_WORDS + in_pad,
                    "in_dim": self.in_dim, "act_dim": self.act_dim, "clip": self.clip}
-        return np.concatenate(params + [tail]), table, offsets
+        return np.concatenate([params, tail]), table, offsets
 
     @classmethod
     def unpack(cls, image, table, offsets):
         """decode pack()'s image back into a policy; non-zero padding is a ValueError"""
         image = np.asarray(image, np.float32)
-        nets = [[], []]
-        for net_id, n_in, n_out, p_in, p_out, act, w_pos, b_pos in np.asarray(table).tolist():
-            full = image[w_pos:w_pos + p_in * p_out].reshape(p_out // 16, p_in // 16, 4, 16, 4).transpose(0, 3, 1, 2, 4).reshape(p_out, p_in)
-            bias = image[b_pos:b_pos + p_out]
-            if full[n_out:].any() or full[:, n_in:].any() or bias[n_out:].any():
-                raise ValueError("padding of a packed policy must be zeros")
-            nets[net_id].append((full[:n_out, :n_in], bias[:n_out], ACTIVATIONS[act]))
+        nets = unpack_nets(image, table, "policy")
         in_dim, act_dim, in_pad = offsets["in_dim"], offsets["act_dim"], _round16(offsets["in_dim"])
         log_std = image[offsets["log_std"]:offsets["log_std"] + MAX_ACTION]
         mean, inv_std = image[offsets["mean"]:offsets["mean"] + in_pad], image[offsets["inv_std"]:offsets["inv_std"] + in_pad]

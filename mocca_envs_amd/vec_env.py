@@ -15,6 +15,7 @@ import torch
 from . import lib as _lib
 from . import model as M
 from . import rollout as _ro
+from .controller import ACTIVATIONS, layer_table
 
 TASKS = {
     "Walker3DCustomEnv-v0": M.TASK_WALKER3D_CUSTOM,
@@ -236,8 +237,6 @@ class VecEnv:
         self.height_field = (hf, float(scale))
 
     # ---- the planner envs' base controller (env_locomotion.py:1029-1040, :1091-1101) ----
-    from .controller import ACTIVATIONS
-
     def set_base_controller(self, ctrl, action_scale: float = 2.0):
         """Attach the base controller of a planner env (include/mocca.h mocca_set_base_controller; None detaches).  `ctrl`: a
         `controller.BaseController` (or any object with `.actor` and `.critic`, or the pair (actor, critic)); each net a list of layers (W[out][in], b[out], activation) with activation one
@@ -250,20 +249,11 @@ class VecEnv:
             self.base_controller = None
             return
         actor, critic = (ctrl.actor, ctrl.critic) if hasattr(ctrl, "actor") else ctrl
-        rows, chunks, off = [], [], 0
-        for net, layers in enumerate((actor, critic)):
-            for w, b, act in layers:
-                w, b = np.ascontiguousarray(w, np.float32), np.ascontiguousarray(b, np.float32).reshape(-1)
-                if w.ndim != 2 or act not in self.ACTIVATIONS:
-                    raise ValueError(f"a layer is (W[out][in], b[out], activation in {self.ACTIVATIONS})")
-                out_dim, in_dim = w.shape
-                if b.size != out_dim:
-                    raise ValueError("a layer's bias has one entry per output")
-                rows.append((net, in_dim, out_dim, (in_dim + 15) // 16 * 16, (out_dim + 15) // 16 * 16, self.ACTIVATIONS.index(act), off, off + w.size))
-                chunks += [w.reshape(-1), b]
-                off += w.size + b.size
-        params = np.concatenate(chunks) if chunks else np.zeros(0, np.float32)
-        table = np.asarray(rows, np.int32).reshape(-1, 8)
+        layers = [(np.asarray(w, np.float32), np.asarray(b, np.float32), act) for w, b, act in list(actor) + list(critic)]
+        if any(w.ndim != 2 or b.size != w.shape[0] or act not in ACTIVATIONS for w, b, act in layers):    # the widths are the library's to refuse
+            raise ValueError(f"a layer is (W[out][in], b[out], activation in {ACTIVATIONS})")
+        params = np.concatenate([x.reshape(-1) for w, b, _ in layers for x in (w, b)] + [np.zeros(0, np.float32)])
+        table = layer_table(actor, critic, "flat")
         _lib.check(self.lib.mocca_set_base_controller(self.h, params.ctypes.data_as(C.c_void_p), params.size, table.ctypes.data_as(C.c_void_p),
                                                       table.shape[0], float(action_scale)), self.h)
         self.base_controller = ctrl
