@@ -12,7 +12,6 @@
 #include <vector>
 
 #include "mocca.h"
-#include "mocca_controller.h"
 #include "mocca_kernels.h"
 #include "mocca_policy.h"
 #include "mocca_render.h"
@@ -147,10 +146,9 @@ struct mocca_ctx {
   int scan_n = 0;
   float scan_above = 0.0f, scan_drop = 0.0f;
   // planner envs: the base controller (mocca_set_base_controller), all owned by the handle
-  DevBuf<float> d_ctrl_params;
+  DevBuf<float> d_ctrl_image;        // the kernel's image (mocca_controller.h; the tail of mocca_policy.h's image is there and not read)
   DevBuf<int32_t> d_ctrl_layers;
-  int ctrl_n_actor = 0, ctrl_n_critic = 0;
-  float ctrl_scale = 0.0f;
+  mocca_ctrl::ControllerArgs ctrl{}; // everything of mocca_plan_step's launch but the plans
   DevBuf<float> d_robot_state;       // [N][ROBOT_STATE_STRIDE] the controller's next input (StepArgs.robot_state)
   DevBuf<float> d_base_act;          // [N][21] the actor's output of the last mocca_plan_step
   DevBuf<float> d_base_val;          // [N] the critic's
@@ -236,6 +234,54 @@ static std::string check_layer_table(const int32_t* layers, int n_layers_total, 
     if (!last && (out & 15)) return at + "hidden widths must be multiples of 16";
   }
   return count[0] < 1 || count[1] < 1 ? "needs an actor and a critic" : "";
+}
+
+// The image of a checked layer table (mocca_policy.h) in new device buffers: the table with its offsets pointing into the image, the zeroed
+// image, the rows that tell the repack kernel where each piece of the source parameters goes, and the kernel's shapes and image offsets.
+// `packed`: the source is W[out][in], b[out] layer after layer, then log_std (n_src: floats of that); otherwise the table's own w_off /
+// b_off say where a layer's weights and bias lie in it, and log_std is zeros.  The last three rows (flags, mean, inv_std) come out as zeros:
+// mocca_update_policy sets their source per call.
+struct NetImage {
+  DevBuf<float> image;
+  DevBuf<int32_t> layers;
+  mocca_pol::PolicyArgs pa{};
+  mocca_pol::RepackArgs rp{};
+  size_t n_src = 0;
+};
+static hipError_t build_image(NetImage& im, const int32_t* layers_host, int n_layers_total, const int count[2], int in_dim, int act_dim, bool packed) {
+  using namespace mocca_ctrl;
+  using namespace mocca_pol;
+  std::vector<int32_t> table(layers_host, layers_host + (size_t)n_layers_total * CTRL_LAYER_WORDS);
+  const int in_pad = (in_dim + 15) / 16 * 16;
+  int pos = 0, src = 0, nr = 0;
+  auto row = [&](int floats, int src_off, int in, int out, int ipad) {
+    RepackRow& q = im.rp.rows[nr++];
+    q.dst = pos; q.dst_end = pos + floats; q.src = src_off; q.in = in; q.out = out; q.in_pad = ipad; q.fill = 0.0f;
+    pos += floats;
+    return q.dst;
+  };
+  for (int i = 0; i < n_layers_total; ++i) {
+    int32_t* r = &table[(size_t)i * CTRL_LAYER_WORDS];
+    const int in = r[CL_IN], out = r[CL_OUT];
+    r[CL_W_OFF] = row(r[CL_IN_PAD] * r[CL_OUT_PAD], packed ? src : r[CL_W_OFF], in, out, r[CL_IN_PAD]);
+    src += in * out;
+    r[CL_B_OFF] = row(r[CL_OUT_PAD], packed ? src : r[CL_B_OFF], 0, out, 0);
+    src += out;
+  }
+  PolicyArgs& pa = im.pa;
+  pa.log_std_off = row(POL_MAX_ACTION, packed ? src : -1, 0, act_dim, 0);
+  im.n_src = (size_t)src + act_dim;
+  pa.flags_off = row(POL_FLAG_WORDS, -1, 0, 1, 0);
+  pa.mean_off = row(in_pad, -1, 0, in_dim, 0);
+  pa.inv_std_off = row(in_pad, -1, 0, in_dim, 0);
+  im.rp.n_rows = nr; im.rp.image_floats = pos;
+  hipError_t e = im.image.alloc((size_t)pos, true);
+  if (e == hipSuccess) e = im.layers.alloc(table.size(), false);
+  if (e == hipSuccess) e = hipMemcpy(im.layers, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  im.rp.image = im.image;
+  pa.params = im.image; pa.layers = im.layers; pa.n_actor = count[0]; pa.n_critic = count[1];
+  pa.in_dim = in_dim; pa.in_pad = in_pad; pa.act_dim = act_dim;
+  return e;
 }
 
 // does the blob give mass or inertia to a link the compiled topology T treats as massless?
@@ -470,7 +516,7 @@ static StepArgs make_args(mocca_handle h) {
   a.pace_acc = h->d_pace_acc;
   a.ep_ret = h->d_ep_ret; a.ep_masks = h->ep_masks; a.ep_bad = h->ep_bad; a.ep_totals = h->ep_totals;   // (ep_rec / ep_serial: mocca_step only)
   a.hf = h->d_hf; a.hf_rows = h->hf_rows; a.hf_cols = h->hf_cols; a.hf_scale = h->hf_scale;
-  a.robot_state = h->d_ctrl_params ? h->d_robot_state.get() : nullptr;   // (base_value: mocca_plan_step only)
+  a.robot_state = h->d_ctrl_image ? h->d_robot_state.get() : nullptr;   // (base_value: mocca_plan_step only)
   return a;
 }
 // A scalar MOCCA_PARAM_APPLIED_GAIN is written into the task records (word MOCCA_TW_APPLIED_GAIN, what apply_action reads) by the NEXT call that takes
@@ -567,14 +613,12 @@ int mocca_step(mocca_handle h, const float* act_dev, float* obs_dev, float* rew_
 int mocca_plan_step(mocca_handle h, const float* plan_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev, int32_t* info_dev,
                     void* stream) {
   if (!h || !plan_dev || !obs_dev || !rew_dev || !done_dev) return MOCCA_E_ARG;
-  if (!h->d_ctrl_params) { h->err = "mocca_plan_step needs a base controller (mocca_set_base_controller)"; return MOCCA_E_ARG; }
+  if (!h->d_ctrl_image) { h->err = "mocca_plan_step needs a base controller (mocca_set_base_controller)"; return MOCCA_E_ARG; }
   if (need_attachments(h) != MOCCA_OK) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   hipStream_t s = (hipStream_t)stream;
-  mocca_ctrl::ControllerArgs c{};
-  c.params = h->d_ctrl_params; c.layers = h->d_ctrl_layers; c.n_actor = h->ctrl_n_actor; c.n_critic = h->ctrl_n_critic;
-  c.robot_state = h->d_robot_state; c.plan = plan_dev; c.action_scale = h->ctrl_scale;
-  c.action = h->d_base_act; c.value = h->d_base_val; c.n_envs = h->n_envs;
+  mocca_ctrl::ControllerArgs c = h->ctrl;
+  c.plan = plan_dev;
   mocca_ctrl::launch_controller(s, c);
   HIP_TRY(h, hipGetLastError());
   return launch_step(h, h->d_base_act, h->d_base_val, obs_dev, rew_dev, done_dev, info_dev, s);
@@ -582,7 +626,7 @@ int mocca_plan_step(mocca_handle h, const float* plan_dev, float* obs_dev, float
 
 int mocca_get_base_outputs(mocca_handle h, float* action_dev, float* value_dev, void* stream) {
   if (!h) return MOCCA_E_ARG;
-  if (!h->d_ctrl_params) { h->err = "mocca_get_base_outputs needs a base controller (mocca_set_base_controller)"; return MOCCA_E_ARG; }
+  if (!h->d_ctrl_image) { h->err = "mocca_get_base_outputs needs a base controller (mocca_set_base_controller)"; return MOCCA_E_ARG; }
   DeviceGuard guard(h->device);
   if (action_dev) HIP_TRY(h, hipMemcpyAsync(action_dev, h->d_base_act, (size_t)h->n_envs * mocca_ctrl::CTRL_ACTION * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   if (value_dev) HIP_TRY(h, hipMemcpyAsync(value_dev, h->d_base_val, (size_t)h->n_envs * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -597,7 +641,7 @@ int mocca_set_base_controller(mocca_handle h, const float* params_host, size_t n
   DeviceGuard guard(h->device);
   if (!params_host) {   // detach
     if (int rc = commit_ready(h, "mocca_set_base_controller")) return rc;
-    h->d_ctrl_params.reset(); h->d_ctrl_layers.reset(); h->ctrl_n_actor = h->ctrl_n_critic = 0;
+    h->d_ctrl_image.reset(); h->d_ctrl_layers.reset(); h->ctrl = {};
     return MOCCA_OK;
   }
   auto bad = [&](const std::string& what) { h->err = "mocca_set_base_controller: " + what; return MOCCA_E_ARG; };
@@ -607,42 +651,33 @@ int mocca_set_base_controller(mocca_handle h, const float* params_host, size_t n
   const std::string wrong = check_layer_table(layers_host, n_layers_total, CTRL_IN, CTRL_ACTION, n_floats, "a net's first layer takes the 65-float input",
                                               "the actor ends in 21 outputs, the critic in 1", count);
   if (!wrong.empty()) return bad(wrong);
-  // the kernel's image (mocca_controller.h): per layer the weights padded with zeros to the 16 x 16 MFMA tile, in fragment order, then the
-  // padded bias; the table's offsets point into it
-  std::vector<int32_t> table(layers_host, layers_host + (size_t)n_layers_total * CTRL_LAYER_WORDS);
-  std::vector<float> image;
-  for (int i = 0; i < n_layers_total; ++i) {
-    int32_t* r = &table[(size_t)i * CTRL_LAYER_WORDS];
-    const int in = r[CL_IN], out = r[CL_OUT], nkg = r[CL_IN_PAD] / 16, n_ot = r[CL_OUT_PAD] / 16;
-    const float *w = params_host + r[CL_W_OFF], *b = params_host + r[CL_B_OFF];
-    r[CL_W_OFF] = (int32_t)image.size();
-    for (int ot = 0; ot < n_ot; ++ot)
-      for (int kg = 0; kg < nkg; ++kg)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 4; ++j) {
-            const int row = 16 * ot + (l & 15), k = 16 * kg + 4 * (l >> 4) + j;
-            image.push_back(row < out && k < in ? w[(size_t)row * in + k] : 0.0f);
-          }
-    r[CL_B_OFF] = (int32_t)image.size();
-    for (int o = 0; o < 16 * n_ot; ++o) image.push_back(o < out ? b[o] : 0.0f);
-  }
-  // the per-env buffers outlive a controller: made by the first attach, kept (with their content) by a replace and by a detach
-  DevBuf<float> params, state, act, val;
-  DevBuf<int32_t> layers;
+  // the image: the caller's parameters go to the device as they are and the repack kernel puts them in fragment order; it has ended when
+  // `flat` and a refused call's image are freed (on success commit_ready synchronises, after a failure the line below does).  The per-env
+  // buffers outlive a controller: made by the first attach, kept (with their content) by a replace and by a detach
+  NetImage im;
+  DevBuf<float> flat, state, act, val;
   const size_t n = (size_t)h->n_envs;
-  hipError_t e = params.alloc(image.size(), false);
-  if (e == hipSuccess) e = layers.alloc(table.size(), false);
-  if (e == hipSuccess) e = hipMemcpy(params, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(layers, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  hipError_t e = build_image(im, layers_host, n_layers_total, count, CTRL_IN, CTRL_ACTION, false);
+  if (e == hipSuccess) e = flat.alloc(n_floats, false);
+  if (e == hipSuccess) e = hipMemcpy(flat, params_host, n_floats * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    im.rp.src = flat;
+    mocca_pol::launch_repack(nullptr, im.rp);
+    e = hipGetLastError();
+  }
   if (e == hipSuccess && !h->d_robot_state) e = state.alloc(n * ROBOT_STATE_STRIDE, true);
   if (e == hipSuccess && !h->d_base_act) e = act.alloc(n * CTRL_ACTION, true);
   if (e == hipSuccess && !h->d_base_val) e = val.alloc(n, true);
+  if (e != hipSuccess) (void)hipDeviceSynchronize();
   if (int rc = commit_ready(h, "mocca_set_base_controller", e)) return rc;
-  h->d_ctrl_params.swap(params); h->d_ctrl_layers.swap(layers);
+  h->d_ctrl_image.swap(im.image); h->d_ctrl_layers.swap(im.layers);
   if (state) h->d_robot_state.swap(state);
   if (act) h->d_base_act.swap(act);
   if (val) h->d_base_val.swap(val);
-  h->ctrl_n_actor = count[0]; h->ctrl_n_critic = count[1]; h->ctrl_scale = (float)action_scale;
+  mocca_ctrl::ControllerArgs& c = h->ctrl;
+  c.params = im.pa.params; c.layers = im.pa.layers; c.n_actor = count[0]; c.n_critic = count[1];
+  c.robot_state = h->d_robot_state; c.action_scale = (float)action_scale;
+  c.action = h->d_base_act; c.value = h->d_base_val; c.n_envs = h->n_envs;
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_base_controller"); }
 
@@ -1001,7 +1036,6 @@ int mocca_height_scan(mocca_handle h, float* out_dev, int row_stride, const floa
 }
 
 int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) try {
-  using namespace mocca_ctrl;
   using namespace mocca_pol;
   if (!h) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
@@ -1014,48 +1048,16 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
   if (in_dim < 1 || in_dim > POL_MAX_IN) return bad("in_dim must be 1 .. " + std::to_string(POL_MAX_IN));
   if (act_dim < 1 || act_dim > POL_MAX_ACTION) return bad("act_dim must be 1 .. " + std::to_string(POL_MAX_ACTION));
   if (!std::isfinite(clip) || !(clip > 0.0)) return bad("clip must be finite and positive");
-  const int in_pad = (in_dim + 15) / 16 * 16;
   int count[2];
   const std::string wrong = check_layer_table(layers_host, n_layers_total, in_dim, act_dim, NO_OFFSETS,
                                               "a net's first layer takes in_dim = " + std::to_string(in_dim) + " inputs, not %d",
                                               "the actor ends in act_dim = " + std::to_string(act_dim) + " outputs, the critic in 1", count);
   if (!wrong.empty()) return bad(wrong);
-  // the image (mocca_policy.h) and the rows that tell the repack kernel where each piece of the caller's flat parameters goes
-  std::vector<int32_t> table(layers_host, layers_host + (size_t)n_layers_total * CTRL_LAYER_WORDS);
-  RepackArgs rp{};
-  int pos = 0, src = 0, nr = 0;
-  auto row = [&](int floats, int src_off, int in, int out, int ipad, float fill) {
-    RepackRow& q = rp.rows[nr++];
-    q.dst = pos; q.dst_end = pos + floats; q.src = src_off; q.in = in; q.out = out; q.in_pad = ipad; q.fill = fill;
-    pos += floats;
-    return q.dst;
-  };
-  for (int i = 0; i < n_layers_total; ++i) {
-    int32_t* r = &table[(size_t)i * CTRL_LAYER_WORDS];
-    const int in = r[CL_IN], out = r[CL_OUT];
-    r[CL_W_OFF] = row(r[CL_IN_PAD] * r[CL_OUT_PAD], src, in, out, r[CL_IN_PAD], 0.0f);
-    src += in * out;
-    r[CL_B_OFF] = row(r[CL_OUT_PAD], src, 0, out, 0, 0.0f);
-    src += out;
-  }
-  PolicyArgs pa{};
-  pa.log_std_off = row(POL_MAX_ACTION, src, 0, act_dim, 0, 0.0f);
-  src += act_dim;
-  pa.flags_off = row(POL_FLAG_WORDS, -1, 0, 1, 0, 0.0f);        // (rows nr - 3 .. nr - 1: mocca_update_policy sets their source per call)
-  pa.mean_off = row(in_pad, -1, 0, in_dim, 0, 0.0f);
-  pa.inv_std_off = row(in_pad, -1, 0, in_dim, 0, 0.0f);
-  rp.n_rows = nr; rp.image_floats = pos;
-  DevBuf<float> image;
-  DevBuf<int32_t> layers;
-  hipError_t e = image.alloc((size_t)pos, true);
-  if (e == hipSuccess) e = layers.alloc(table.size(), false);
-  if (e == hipSuccess) e = hipMemcpy(layers, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (int rc = commit_ready(h, "mocca_set_policy", e)) return rc;
-  h->d_pol_image.swap(image); h->d_pol_layers.swap(layers);
-  pa.params = h->d_pol_image; pa.layers = h->d_pol_layers; pa.n_actor = count[0]; pa.n_critic = count[1];
-  pa.in_dim = in_dim; pa.in_pad = in_pad; pa.act_dim = act_dim; pa.clip = (float)clip;
-  rp.image = h->d_pol_image;
-  h->pol = pa; h->pol_repack = rp; h->pol_n_base = (size_t)src; h->pol_filled = false;
+  NetImage im;
+  if (int rc = commit_ready(h, "mocca_set_policy", build_image(im, layers_host, n_layers_total, count, in_dim, act_dim, true))) return rc;
+  h->d_pol_image.swap(im.image); h->d_pol_layers.swap(im.layers);
+  h->pol = im.pa; h->pol.clip = (float)clip;
+  h->pol_repack = im.rp; h->pol_n_base = im.n_src; h->pol_filled = false;
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy"); }
 

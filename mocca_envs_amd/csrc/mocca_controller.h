@@ -1,5 +1,6 @@
 // mocca_controller.h -- layout of the planner envs' base controller as the controller kernel reads it (mocca_controller.hip), and the
-// host-side launcher.  mocca_set_base_controller (mocca_api.hip) checks the caller's plain row-major layers and builds this image.
+// host-side launcher.  mocca_set_base_controller (mocca_api.hip) checks the caller's plain row-major layers and has the repack kernel
+// (mocca_policy.hip) build this image on the device.
 //
 // The base controller of Walker3DPlannerEnv / MikePlannerEnv (env_locomotion.py:1029-1040, :1091-1101) is an actor-critic pair of MLPs over
 // one 65-float input, [robot_state(50), plan(15) * action_scale]: the actor's 21 outputs are the joint actions of the step, the critic's one

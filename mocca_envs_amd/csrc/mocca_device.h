@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "mocca_model.h"
+#include "mocca_philox.h"
 #include "topo_walker3d.h"
 #include "topo_cassie.h"
 #include "topo_walker2d.h"
@@ -434,18 +435,6 @@ DI float wave_max(float v) {
   return fmaxf(fmaxf(readlane(v, 0), readlane(v, 16)), fmaxf(readlane(v, 32), readlane(v, 48)));
 }
 
-// Philox4x32-10; identical to oracle/mocca_oracle.c so device resets are reproducible on the host
-DI void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-    uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 DI float rng_uniform(uint32_t slo, uint32_t shi, uint32_t env, uint32_t episode, uint32_t d) {
   uint32_t o[4];
   philox4x32(d >> 2, episode, env, 0u, slo, shi, o);

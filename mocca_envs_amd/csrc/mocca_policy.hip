@@ -17,6 +17,7 @@
 // atomics, no host state.
 #include <hip/hip_runtime.h>
 
+#include "mocca_philox.h"
 #include "mocca_policy.h"
 
 namespace mocca_pol {
@@ -39,19 +40,6 @@ __device__ __forceinline__ float activate(float x, int act) {
     case CTRL_ACT_SOFTSIGN: return x / (1.0f + fabsf(x));
     default: return x;
   }
-}
-
-// Philox4x32-10 (the rounds of mocca_device.h philox4x32): words 0 and 1 of the block
-__device__ __forceinline__ void philox2(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t& o0, uint32_t& o1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  o0 = c0; o1 = c1;
 }
 
 __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
@@ -80,9 +68,9 @@ __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
     const int e = tid >> 4, p = tid & 15, env = env0 + e;
     if (env < a.n_envs && 2 * p < a.act_dim) {
       const uint32_t* tk = a.task + (size_t)env * a.task_words;
-      uint32_t w0, w1;
-      philox2(16u * (uint32_t)(a.env_offset + env) + (uint32_t)p, tk[a.tw_t], tk[a.tw_episode], 1u, a.seed_lo, a.seed_hi, w0, w1);
-      const float u1 = (float)((w0 >> 8) + 1u) * (1.0f / 16777216.0f), u2 = (float)(w1 >> 8) * (1.0f / 16777216.0f);
+      uint32_t w[4];
+      philox4x32(16u * (uint32_t)(a.env_offset + env) + (uint32_t)p, tk[a.tw_t], tk[a.tw_episode], 1u, a.seed_lo, a.seed_hi, w);
+      const float u1 = (float)((w[0] >> 8) + 1u) * (1.0f / 16777216.0f), u2 = (float)(w[1] >> 8) * (1.0f / 16777216.0f);
       const float r = sqrtf(-2.0f * logf(u1)), th = 6.28318530717958647692f * u2;
       Z[e * POL_MAX_ACTION + 2 * p] = r * cosf(th);
       Z[e * POL_MAX_ACTION + 2 * p + 1] = r * sinf(th);

@@ -76,6 +76,29 @@ def test_controller_parity_with_the_f64_forward(kind, n):
     env.close()
 
 
+@pytest.mark.parametrize("kind", sorted(R.SHAPES))
+@pytest.mark.parametrize("n", [1, 17, 63])
+def test_base_outputs_are_the_policy_kernels_bits(kind, n):
+    """The controller is the deterministic, unnormalised case of a trainer's policy: the same two nets attached as a `DevicePolicy` (log_std
+    zeros) and run by act() on [robot_state, plan * action_scale] give plan_step's base outputs bit for bit.  n: one env, a 16-env tile
+    boundary, a ragged last tile."""
+    import torch
+    from mocca_envs_amd.policy import DevicePolicy
+    ctrl, scale = R.random_controller(kind, seed=7), 2.0
+    env = _env(n)
+    env.set_base_controller(ctrl, action_scale=scale)
+    env.reset()
+    plans = _plans(n, 2, seed=n)
+    env.plan_step(plans[0])
+    rs = env.obs[:, :50].clone()
+    env.plan_step(plans[1])
+    act, val = env.base_outputs()
+    env.set_policy(DevicePolicy(ctrl.actor, ctrl.critic, np.zeros(R.ACTION, np.float32)))
+    out = env.act(torch.cat([rs, plans[1] * scale], 1), deterministic=True)
+    assert torch.equal(out["action"], act) and torch.equal(out["value"], val)
+    env.close()
+
+
 @pytest.mark.parametrize("env_id", ["MikePlannerEnv-v0", "Walker3DPlannerEnv-v0"])
 def test_plan_step_is_controller_plus_step_and_monitor_sees_the_reward(env_id):
     """A: plan_step(plan).  B: step(A's controller actions).  Everything but the reward identical in every step and env; A's reward is B's
