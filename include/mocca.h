@@ -385,9 +385,21 @@ int mocca_height_scan(mocca_handle h, float *out_dev, int row_stride, const floa
  *                       [N] or NULL, mean_dev [N][act_dim] or NULL.  No allocation, no synchronisation, no atomics, no host state.
  * mocca_act_step        replaces `act()` followed by `envs.step(action)`: mocca_act, then mocca_step on action_dev, on the same stream; the
  *                       step's results are mocca_step's bit for bit, and the pair is capturable in a hipGraph under mocca_step's conditions.
- * Errors (MOCCA_E_ARG, with a message): a NULL handle, any bad dimension, mocca_update_policy / mocca_act before mocca_set_policy, mocca_act
- * before mocca_update_policy, n_floats that fits neither form, in_stride < in_dim, mocca_act_step with act_dim other than the env's, global env
- * ids (MOCCA_PARAM_ENV_OFFSET + n_envs) beyond 2^28 (the noise's counter holds 16 x env id in one 32-bit word). */
+ * mocca_set_policy_symmetry  replaces SymmetricRL's symmetric network (`SymmetricNet` around the actor and the critic, built from the env's
+ *                       `get_mirror_indices()`): the attached policy becomes mirror-symmetric by construction,
+ *                           mean_sym(s) = 1/2 (f(n(s)) + M_a f(n(M_o s)))        value_sym(s) = 1/2 (V(n(s)) + V(n(M_o s)))
+ *                       with (M x)[k] = sign[k] * x[perm[k]], n the normalisation (the mirror acts on the raw row) and log_std replaced by
+ *                       1/2 (log_std[j] + log_std[act_perm[j]]).  in_perm_host i32 / in_sign_host f32 [in_dim], act_perm_host i32 /
+ *                       act_sign_host f32 [act_dim] (HOST memory, copied into the handle).  Each table must be valid: indices in range,
+ *                       perm[perm[k]] == k, sign[k] +1 or -1, sign[perm[k]] == sign[k] (so that M M = I); a violation is MOCCA_E_ARG with a
+ *                       message and leaves the handle as it was.  While attached, mocca_act / mocca_act_step launch the kernel's symmetric
+ *                       instance -- still one launch, twice the matrix work; their contract holds as it stands (outputs, NULL options, noise
+ *                       keying, capture conditions; mean_dev receives mean_sym).  in_perm_host == NULL detaches; mocca_set_policy drops an
+ *                       attached symmetry (the shapes may have changed); mocca_update_policy leaves it alone.  May synchronise.
+ * Errors (MOCCA_E_ARG, with a message): a NULL handle, any bad dimension, mocca_update_policy / mocca_act / mocca_set_policy_symmetry before
+ * mocca_set_policy, mocca_act before mocca_update_policy, n_floats that fits neither form, in_stride < in_dim, mocca_act_step with act_dim other
+ * than the env's, an invalid mirror table, global env ids (MOCCA_PARAM_ENV_OFFSET + n_envs) beyond 2^28 (the noise's counter holds 16 x env id
+ * in one 32-bit word). */
 int mocca_set_policy(mocca_handle h, const int32_t *layers_host, int n_layers_total, int in_dim, int act_dim, double clip);
 int mocca_update_policy(mocca_handle h, const float *params_dev, size_t n_floats, void *stream);
 int mocca_act(mocca_handle h, const float *in_dev, int in_stride, const float *eps_dev, int deterministic, float *action_dev, float *logp_dev,
@@ -395,6 +407,8 @@ int mocca_act(mocca_handle h, const float *in_dev, int in_stride, const float *e
 int mocca_act_step(mocca_handle h, const float *in_dev, int in_stride, const float *eps_dev, int deterministic, float *action_dev,
                    float *logp_dev, float *value_dev, float *mean_dev, float *obs_dev, float *rew_dev, uint8_t *done_dev, int32_t *info_dev,
                    void *stream);
+int mocca_set_policy_symmetry(mocca_handle h, const int32_t *in_perm_host, const float *in_sign_host, const int32_t *act_perm_host,
+                              const float *act_sign_host);
 
 /* ---- the end of a rollout on the device (no reference counterpart: the reference's trainers run these in torch, a Python loop over the
  *      rollout's steps and a handful of reductions per iteration) ---- */

@@ -159,6 +159,8 @@ struct mocca_ctx {
   mocca_pol::RepackArgs pol_repack{};   // rows of the repack kernel; src offsets in the caller's flat parameters
   size_t pol_n_base = 0;             // floats of mocca_update_policy's params_dev without the normalisation arrays
   bool pol_filled = false;           // mocca_update_policy has run since mocca_set_policy
+  DevBuf<int32_t> d_pol_sym_perm;    // mocca_set_policy_symmetry: in_perm [in_dim] then act_perm [act_dim]; pol.in_perm / act_perm point into it
+  DevBuf<float> d_pol_sym_sign;      // in_sign [in_dim] then act_sign [act_dim]
   // scratch of mocca_gae / mocca_obs_stats (mocca_rollout.h), owned by the handle, grown on demand
   DevBuf<double> d_gae_part;         // [blocks][2]
   size_t gae_part_cap = 0;           // doubles
@@ -1035,6 +1037,13 @@ int mocca_height_scan(mocca_handle h, float* out_dev, int row_stride, const floa
   return MOCCA_OK;
 }
 
+// detach the mirror tables of the policy (mocca_set_policy_symmetry); the caller has made sure that no launch in flight reads them
+static void drop_policy_symmetry(mocca_handle h) {
+  h->d_pol_sym_perm.reset(); h->d_pol_sym_sign.reset();
+  h->pol.in_perm = h->pol.act_perm = nullptr;
+  h->pol.in_sign = h->pol.act_sign = nullptr;
+}
+
 int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) try {
   using namespace mocca_pol;
   if (!h) return MOCCA_E_ARG;
@@ -1042,6 +1051,7 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
   if (!layers_host) {   // detach
     if (int rc = commit_ready(h, "mocca_set_policy")) return rc;
     h->d_pol_image.reset(); h->d_pol_layers.reset(); h->pol_filled = false;
+    drop_policy_symmetry(h);
     return MOCCA_OK;
   }
   auto bad = [&](const std::string& what) { h->err = "mocca_set_policy: " + what; return MOCCA_E_ARG; };
@@ -1058,8 +1068,57 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
   h->d_pol_image.swap(im.image); h->d_pol_layers.swap(im.layers);
   h->pol = im.pa; h->pol.clip = (float)clip;
   h->pol_repack = im.rp; h->pol_n_base = im.n_src; h->pol_filled = false;
+  drop_policy_symmetry(h);   // the shapes may have changed
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy"); }
+
+// The rules of one mirror table (mocca_policy.h: Symmetry): -> "" or what is wrong with the first entry that breaks one.
+static std::string check_mirror_table(const int32_t* perm, const float* sign, int dim, const char* perm_name, const char* sign_name) {
+  for (int k = 0; k < dim; ++k) {
+    const std::string at = std::string(perm_name) + "[" + std::to_string(k) + "]";
+    if (perm[k] < 0 || perm[k] >= dim) return at + " = " + std::to_string(perm[k]) + " is outside 0 .. " + std::to_string(dim - 1);
+    if (!(sign[k] == 1.0f || sign[k] == -1.0f)) return std::string(sign_name) + "[" + std::to_string(k) + "] must be +1 or -1";
+  }
+  for (int k = 0; k < dim; ++k) {
+    const std::string at = std::string(perm_name) + "[" + std::to_string(k) + "]";
+    if (perm[perm[k]] != k) return at + ": the permutation is not an involution (perm[perm[k]] != k)";
+    if (sign[perm[k]] != sign[k]) return at + ": " + sign_name + " differs across the swapped pair (M M must be the identity)";
+  }
+  return "";
+}
+
+int mocca_set_policy_symmetry(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
+                              const float* act_sign_host) try {
+  if (!h) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  auto bad = [&](const std::string& what) { h->err = "mocca_set_policy_symmetry: " + what; return MOCCA_E_ARG; };
+  if (!h->d_pol_image) return bad("needs a policy (mocca_set_policy)");
+  if (!in_perm_host) {   // detach
+    if (int rc = commit_ready(h, "mocca_set_policy_symmetry")) return rc;
+    drop_policy_symmetry(h);
+    return MOCCA_OK;
+  }
+  if (!in_sign_host || !act_perm_host || !act_sign_host) return bad("in_sign_host, act_perm_host and act_sign_host must not be NULL");
+  const int in_dim = h->pol.in_dim, act_dim = h->pol.act_dim;
+  std::string wrong = check_mirror_table(in_perm_host, in_sign_host, in_dim, "in_perm", "in_sign");
+  if (wrong.empty()) wrong = check_mirror_table(act_perm_host, act_sign_host, act_dim, "act_perm", "act_sign");
+  if (!wrong.empty()) return bad(wrong);
+  std::vector<int32_t> perm(in_perm_host, in_perm_host + in_dim);
+  perm.insert(perm.end(), act_perm_host, act_perm_host + act_dim);
+  std::vector<float> sign(in_sign_host, in_sign_host + in_dim);
+  sign.insert(sign.end(), act_sign_host, act_sign_host + act_dim);
+  DevBuf<int32_t> d_perm;
+  DevBuf<float> d_sign;
+  hipError_t e = d_perm.alloc(perm.size(), false);
+  if (e == hipSuccess) e = d_sign.alloc(sign.size(), false);
+  if (e == hipSuccess) e = hipMemcpy(d_perm, perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_sign, sign.data(), sign.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (int rc = commit_ready(h, "mocca_set_policy_symmetry", e)) return rc;
+  h->d_pol_sym_perm.swap(d_perm); h->d_pol_sym_sign.swap(d_sign);
+  h->pol.in_perm = h->d_pol_sym_perm; h->pol.act_perm = h->d_pol_sym_perm.get() + in_dim;
+  h->pol.in_sign = h->d_pol_sym_sign; h->pol.act_sign = h->d_pol_sym_sign.get() + in_dim;
+  return MOCCA_OK;
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy_symmetry"); }
 
 int mocca_update_policy(mocca_handle h, const float* params_dev, size_t n_floats, void* stream) {
   if (!h) return MOCCA_E_ARG;

@@ -25,6 +25,26 @@
 // of device state only (seed, env id, the env's step and episode counters): the kernel keeps no host state and can be captured; a shard
 // reproduces its rows of the whole batch; restoring state and task replays the noise.  CONSEQUENCE: two mocca_act calls without a
 // mocca_step in between draw the SAME noise (the step counter has not moved).
+//
+// Symmetry.  With mirror tables attached (mocca_set_policy_symmetry: in_perm / in_sign [in_dim], act_perm / act_sign [act_dim], each an
+// involution with (M x)[k] = sign[k] * x[perm[k]] and sign[perm[k]] = sign[k]) the kernel's symmetric instance runs; the policy is
+//     mean_sym(s) = 1/2 ( f(n(s)) + M_a f(n(M_o s)) )        value_sym(s) = 1/2 ( V(n(s)) + V(n(M_o s)) )
+// with n the normalisation above.  Columns: the 16 MFMA columns of a workgroup are POL_SYM_TILE = 8 envs x {as given, mirrored}: column c < 8
+// is env env0 + c, column 8 + c its mirror image; the grid is ceil(N / 8) x {actor, critic}.  Staging of a mirrored column, feature k:
+//     v = in[env][in_perm[k]] * in_sign[k]          then, as for the plain column,  clamp((v - mean[k]) * inv_std[k], -clip, +clip)
+// -- the mirror acts on the RAW row and the statistics are indexed by k: running statistics are not symmetric, and only so is the pair
+// {n(s), n(M_o s)} exactly swapped when the input is mirrored.  The layer loop is the plain one: the two columns of an env are the same dot
+// products in the same order wherever they sit.  Head stage: one lane per env, j ascending, each line ONE f32 operation in this order:
+//     m      = head[c][j]
+//     m'     = head[8 + c][act_perm[j]] * act_sign[j]
+//     mean   = 0.5f * (m + m')
+//     ls     = 0.5f * (log_std[j] + log_std[act_perm[j]])               the symmetrised log_std
+//     action = mean + expf(ls) * eps[j]
+//     logp  += (-0.5f * eps[j]) * eps[j] - ls - 0.9189385...
+//     value  = 0.5f * (v + v')                                          critic workgroups
+// mean_dev receives `mean`; deterministic: action = mean bit for bit.  The noise is the plain instance's: same keying, each env's normals drawn
+// once, so for the same seed, env and counters both instances see the same eps.  CONSEQUENCE: act(M_o s) = M_a act(s) and value(M_o s) =
+// value(s) hold numerically (==; a sum that cancels may come out as -0 on one side and +0 on the other): the combine is commutative.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +59,7 @@ constexpr int POL_MAX_ACTION = 32;    // actor head
 constexpr int POL_MAX_WIDTH = mocca_ctrl::CTRL_MAX_WIDTH, POL_MAX_LAYERS = mocca_ctrl::CTRL_MAX_LAYERS;
 constexpr int POL_FLAG_WORDS = 4;
 constexpr int POL_TILE = 16;          // envs per workgroup (the controller measured 16 as best: profiles/HISTORY.md)
+constexpr int POL_SYM_TILE = 8;       // envs per workgroup of the symmetric instance: each takes two of the 16 MFMA columns
 
 struct PolicyArgs {
   const float* params;          // device: the image
@@ -59,6 +80,11 @@ struct PolicyArgs {
   float* value;                 // [N] or null: the critic's workgroups are not launched
   float* mean;                  // [N][act_dim] or null
   int n_envs;
+  // the mirror tables (header: Symmetry), device; in_perm null: the plain instance
+  const int32_t* in_perm;       // [in_dim]
+  const float* in_sign;         // [in_dim]
+  const int32_t* act_perm;      // [act_dim]
+  const float* act_sign;        // [act_dim]
 };
 
 // one row of the repack kernel's table, one per layer and one per tail array (log_std, mean, inv_std: out = 1 row, no fragment order)

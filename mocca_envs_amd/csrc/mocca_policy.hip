@@ -15,6 +15,10 @@
 // (actor workgroups) or stores the value (critic workgroups).  The in-kernel noise of the tile is drawn by all 256 lanes (16 envs x 16 Philox
 // blocks of two normals) ahead of the layers.  The order of every sum is fixed and does not depend on N: same inputs -> same bits.  No
 // atomics, no host state.
+//
+// The mirror-symmetric instance (SYM; header: Symmetry) gives the 16 MFMA columns to 8 envs x {as given, mirrored}: the staging writes column
+// 8 + c from the raw row of env c through in_perm / in_sign ahead of the same normalisation, the layer loop is the plain one, and the head
+// stage's lane folds the two columns of its env into one mean (or value).
 #include <hip/hip_runtime.h>
 
 #include "mocca_philox.h"
@@ -29,8 +33,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int LDS_STRIDE = POL_MAX_IN + 4;   // floats per env row: 16-byte aligned rows, rows 0..7 start on different bank groups (340 = 20 mod 32)
 constexpr int NP = 4;                        // partial sums per output
 constexpr int NT = 4;                        // output tiles per wave: 16 tiles of 16 rows (width 256) over 4 waves
-constexpr int TILE = POL_TILE;
+constexpr int TILE = POL_TILE;          // MFMA columns of a workgroup: 16 envs, or (SYM) POL_SYM_TILE envs and their mirror images
 static_assert(TILE == 16, "one 16-env MFMA sub-tile per workgroup; the noise stage deals 16 envs x 16 Philox blocks to 256 lanes");
+static_assert(2 * POL_SYM_TILE == TILE, "the symmetric instance: column c the env as given, column POL_SYM_TILE + c its mirror image");
 static_assert(POL_MAX_WIDTH <= POL_MAX_IN && POL_MAX_ACTION <= 32, "LDS rows hold the widest layer; 16 Philox blocks give 32 normals");
 
 __device__ __forceinline__ float activate(float x, int act) {
@@ -42,22 +47,26 @@ __device__ __forceinline__ float activate(float x, int act) {
   }
 }
 
+template <bool SYM>
 __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
+  constexpr int ENVS = SYM ? POL_SYM_TILE : TILE;   // envs of a workgroup
   __shared__ __attribute__((aligned(16))) float X[2][TILE * LDS_STRIDE];
-  __shared__ float Z[TILE * POL_MAX_ACTION];   // the tile's noise, Z[env][j]
+  __shared__ float Z[ENVS * POL_MAX_ACTION];   // the tile's noise, Z[env][j]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int env0 = blockIdx.x * TILE, net = blockIdx.y;
+  const int env0 = blockIdx.x * ENVS, net = blockIdx.y;
   const int col = lane & 15, quad = lane >> 4;
 
-  // input: the first in_dim floats of the env's row, normalised, zeros up to in_pad; rows past the batch are zeros (nothing of them is stored)
+  // input: the first in_dim floats of the env's row, normalised, zeros up to in_pad; rows past the batch are zeros (nothing of them is stored).
+  // SYM: column e >= ENVS is the mirror image of env e - ENVS, formed from the RAW row (the statistics are not symmetric) and normalised by k
   {
     const bool norm = a.params[a.flags_off] != 0.0f;
     const float *mu = a.params + a.mean_off, *is = a.params + a.inv_std_off;
     for (int i = tid; i < TILE * a.in_pad; i += 256) {
-      const int e = i / a.in_pad, k = i - e * a.in_pad, env = env0 + e;
+      const int e = i / a.in_pad, k = i - e * a.in_pad, env = env0 + (SYM ? e & (ENVS - 1) : e);
       float v = 0.0f;
       if (env < a.n_envs && k < a.in_dim) {
-        v = a.in[(size_t)env * a.in_stride + k];
+        if (SYM && e >= ENVS) v = a.in[(size_t)env * a.in_stride + a.in_perm[k]] * a.in_sign[k];
+        else v = a.in[(size_t)env * a.in_stride + k];
         if (norm) v = fminf(fmaxf((v - mu[k]) * is[k], -a.clip), a.clip);
       }
       X[0][e * LDS_STRIDE + k] = v;
@@ -66,7 +75,7 @@ __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
   // in-kernel noise (header: Noise): lane (env e = tid / 16, block p = tid % 16) draws the normals 2 p and 2 p + 1 of env e
   if (net == 0 && !a.deterministic && !a.eps) {
     const int e = tid >> 4, p = tid & 15, env = env0 + e;
-    if (env < a.n_envs && 2 * p < a.act_dim) {
+    if (e < ENVS && env < a.n_envs && 2 * p < a.act_dim) {
       const uint32_t* tk = a.task + (size_t)env * a.task_words;
       uint32_t w[4];
       philox4x32(16u * (uint32_t)(a.env_offset + env) + (uint32_t)p, tk[a.tw_t], tk[a.tw_episode], 1u, a.seed_lo, a.seed_hi, w);
@@ -149,17 +158,24 @@ __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
 
   // head stage: one lane per env
   const int env = env0 + tid;
-  if (tid >= TILE || env >= a.n_envs) return;
+  if (tid >= ENVS || env >= a.n_envs) return;
   const float* head = &X[cur][tid * LDS_STRIDE];
+  const float* mirror = &X[cur][(SYM ? ENVS + tid : tid) * LDS_STRIDE];   // SYM: the head of the env's mirrored column
   if (net == 1) {
-    a.value[env] = head[0];
+    a.value[env] = SYM ? 0.5f * (head[0] + mirror[0]) : head[0];
     return;
   }
   const float* log_std = a.params + a.log_std_off;
   const int A = a.act_dim;
   float lp = 0.0f;
   for (int j = 0; j < A; ++j) {
-    const float m = head[j], ls = log_std[j];
+    float m = head[j], ls = log_std[j];
+    if (SYM) {   // header: Symmetry -- one f32 operation per line of it, in that order
+      const int pj = a.act_perm[j];
+      const float mm = mirror[pj] * a.act_sign[j];
+      m = 0.5f * (m + mm);
+      ls = 0.5f * (ls + log_std[pj]);
+    }
     float e = 0.0f, act = m;
     if (!a.deterministic) {
       e = a.eps ? a.eps[(size_t)env * A + j] : Z[tid * POL_MAX_ACTION + j];
@@ -197,7 +213,8 @@ __global__ __launch_bounds__(256) void repack_kernel(RepackArgs a) {
 }
 
 void launch_policy(hipStream_t s, const PolicyArgs& a) {
-  hipLaunchKernelGGL(policy_kernel, dim3((a.n_envs + TILE - 1) / TILE, a.value ? 2 : 1), dim3(256), 0, s, a);
+  if (a.in_perm) hipLaunchKernelGGL(policy_kernel<true>, dim3((a.n_envs + POL_SYM_TILE - 1) / POL_SYM_TILE, a.value ? 2 : 1), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(policy_kernel<false>, dim3((a.n_envs + TILE - 1) / TILE, a.value ? 2 : 1), dim3(256), 0, s, a);
 }
 
 void launch_repack(hipStream_t s, const RepackArgs& a) {

@@ -69,6 +69,7 @@ SYMBOLS = {
     "mocca_update_policy": (_i, [_vp, _vp, _sz, _vp]),
     "mocca_act": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "mocca_act_step": (_i, [_vp, _vp, _i, _vp, _i] + [_vp] * 9),
+    "mocca_set_policy_symmetry": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mocca_gae": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _d, _d, _d, _vp, _vp, _i, _d, _vp, _vp]),
     "mocca_obs_stats": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, _d, _vp, _vp, _vp]),
     "mocca_is_diagnostic_build": (_i, []),

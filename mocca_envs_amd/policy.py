@@ -6,6 +6,9 @@ state-independent `log_std` and, optionally, a running observation normalisation
 * `VecEnv.set_policy(p)` / `TorchVecEnv.attach_policy(p)` run it on the device, one launch in front of the step kernel
   (`act`, `act_step`; include/mocca.h mocca_act); `update_policy` refreshes the weights once per PPO iteration;
 * the single-env gym classes call it: `p(obs[in_dim]) -> (action, logp, value, mean)`, float32 numpy.
+
+With `symmetry=` (symmetry.mirror_tables) the policy is SymmetricRL's symmetric network, mirror-symmetric by construction
+(csrc/mocca_policy.h: Symmetry); the tables are not parameters: `flat_params()`, `pack()`, `unpack()` and `table()` do not see them.
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ HALF_LOG_2PI = 0.9189385332046727
 
 
 class DevicePolicy:
-    def __init__(self, actor, critic, log_std, obs_mean=None, obs_var=None, eps=1e-8, clip=10.0, inv_std=None):
+    def __init__(self, actor, critic, log_std, obs_mean=None, obs_var=None, eps=1e-8, clip=10.0, inv_std=None, symmetry=None):
         actor = list(actor)
         self.in_dim = int(np.shape(actor[0][0])[1])
         self.log_std = np.array(log_std, dtype=np.float32).reshape(-1)
@@ -38,6 +41,18 @@ class DevicePolicy:
             self.inv_std = np.array(inv_std, dtype=np.float32).reshape(-1)
             if self.obs_mean.size != self.in_dim or self.inv_std.size != self.in_dim:
                 raise ValueError(f"obs_mean / obs_var have {self.in_dim} entries")
+        self.symmetry = None
+        if symmetry is not None:    # (in_perm, in_sign, act_perm, act_sign)
+            from .symmetry import check_tables
+            self.symmetry = check_tables(symmetry, self.in_dim, self.act_dim)
+
+    def with_symmetry(self, symmetry):
+        """a copy of this policy (the arrays are shared) with the mirror tables `symmetry`; None: without any"""
+        import copy
+        from .symmetry import check_tables
+        q = copy.copy(self)
+        q.symmetry = None if symmetry is None else check_tables(symmetry, self.in_dim, self.act_dim)
+        return q
 
     @classmethod
     def from_layers(cls, actor, critic, log_std, **kw):
@@ -45,13 +60,14 @@ class DevicePolicy:
         return cls(actor, critic, log_std, **kw)
 
     @classmethod
-    def from_torch(cls, actor_seq, critic_seq, log_std, obs_mean=None, obs_var=None, eps=1e-8, clip=10.0):
+    def from_torch(cls, actor_seq, critic_seq, log_std, obs_mean=None, obs_var=None, eps=1e-8, clip=10.0, symmetry=None):
         """from two torch.nn.Sequential of Linear / ReLU / Tanh / Softsign (controller.BaseController.from_torch's grammar), the log_std
-        parameter and, optionally, the running observation statistics (tensors or arrays)"""
+        parameter and, optionally, the running observation statistics (tensors or arrays); `symmetry`: the tables a
+        symmetry.SymmetricGaussian over the same modules was built with"""
         import torch
         actor, critic = layers_from_sequential(actor_seq, "actor"), layers_from_sequential(critic_seq, "critic")
         arr = lambda x: None if x is None else (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x))
-        return cls(actor, critic, arr(log_std), obs_mean=arr(obs_mean), obs_var=arr(obs_var), eps=eps, clip=clip)
+        return cls(actor, critic, arr(log_std), obs_mean=arr(obs_mean), obs_var=arr(obs_var), eps=eps, clip=clip, symmetry=symmetry)
 
     @classmethod
     def from_npz(cls, path, clip=10.0, eps=1e-8):
@@ -72,18 +88,32 @@ class DevicePolicy:
         x = np.asarray(obs, dtype=np.float32)
         if x.shape[-1] < self.in_dim:
             raise ValueError(f"the policy's input has {self.in_dim} entries")
-        x = x[..., :self.in_dim]
+        return self._normalised(x[..., :self.in_dim])
+
+    def _normalised(self, x):
         if self.obs_mean is not None:
             x = np.clip((x - self.obs_mean) * self.inv_std, np.float32(-self.clip), np.float32(self.clip))
         return x
 
     def __call__(self, obs, eps=None):
-        """-> (action, logp, value, mean), float32; eps None: the deterministic action (the mean)"""
+        """-> (action, logp, value, mean), float32; eps None: the deterministic action (the mean).  With a symmetry: the symmetric mean and
+        value, the sample and its log-probability under the symmetrised log_std (csrc/mocca_policy.h: Symmetry)"""
         x = self.normalise(obs)
-        mean, value = _apply(self.actor, x), _apply(self.critic, x)[..., 0]
+        if self.symmetry is not None:
+            # the row as given and its mirror image (formed from the RAW row) go through the nets as two arrays of ONE memory layout: the same
+            # row then gives the same bits on either side, and policy(M_o x) == (M_a mean, value) holds numerically
+            in_perm, in_sign, act_perm, act_sign = self.symmetry
+            raw = np.asarray(obs, dtype=np.float32)[..., :self.in_dim]
+            x, xm = np.ascontiguousarray(x), np.ascontiguousarray(self._normalised(raw[..., in_perm] * in_sign))
+        mean, value, log_std = _apply(self.actor, x), _apply(self.critic, x)[..., 0], self.log_std
+        if self.symmetry is not None:
+            half = np.float32(0.5)
+            mean = half * (mean + _apply(self.actor, xm)[..., act_perm] * act_sign)
+            value = half * (value + _apply(self.critic, xm)[..., 0])
+            log_std = half * (log_std + log_std[act_perm])
         e = np.zeros_like(mean) if eps is None else np.asarray(eps, np.float32)
-        action = mean if eps is None else mean + np.exp(self.log_std) * e
-        logp = (np.float32(-0.5) * e * e - self.log_std - np.float32(HALF_LOG_2PI)).sum(-1, dtype=np.float32)
+        action = mean if eps is None else mean + np.exp(log_std) * e
+        logp = (np.float32(-0.5) * e * e - log_std - np.float32(HALF_LOG_2PI)).sum(-1, dtype=np.float32)
         return action, logp, value, mean
 
     # ---- what the library takes (include/mocca.h mocca_set_policy / mocca_update_policy) ----

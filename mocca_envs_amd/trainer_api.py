@@ -333,7 +333,8 @@ class TorchVecEnv:
     # ---- the trainer's own policy on the device (VecEnv.set_policy / act_step, include/mocca.h mocca_act_step) ----
     def attach_policy(self, policy) -> None:
         """Attach a `policy.DevicePolicy` whose input is this env's observation row ([obs | scan] with a height scan) and whose actions are
-        the env's; `update_policy(policy_or_flat_tensor)` refreshes its weights once per PPO iteration.  One handle only."""
+        the env's; `update_policy(policy_or_flat_tensor)` refreshes its weights once per PPO iteration.  One handle only.  A policy with
+        mirror tables (`symmetric_policy(p)`, `DevicePolicy(symmetry=)`) acts as the symmetric network: the tables cover the whole row."""
         if not hasattr(self.venv, "lib"):
             raise NotImplementedError("a device policy needs one handle (sub_batches=1)")
         if self._plan:
@@ -347,6 +348,12 @@ class TorchVecEnv:
 
     def update_policy(self, params) -> None:
         self.venv.update_policy(params)
+
+    def symmetric_policy(self, policy):
+        """a copy of `policy` with this env's mirror tables, the attached height scan's pattern included: `VecEnv.symmetric_policy`"""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("a device policy needs one handle (sub_batches=1)")
+        return self.venv.symmetric_policy(policy)
 
     # ---- the end of a rollout on the device (VecEnv.finish_rollout / update_obs_stats, include/mocca.h mocca_gae / mocca_obs_stats) ----
     def finish_rollout(self, reward, value, masks, bad_masks, *args, **kw) -> dict:

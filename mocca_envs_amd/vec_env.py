@@ -293,6 +293,40 @@ class VecEnv:
                                              float(policy.clip)), self.h)
         self.policy = policy
         self.update_policy(policy)
+        if getattr(policy, "symmetry", None) is not None:      # after the shapes: mocca_set_policy has dropped whatever was attached
+            self.set_policy_symmetry(policy.symmetry)
+
+    def set_policy_symmetry(self, tables) -> None:
+        """Attach mirror tables (symmetry.mirror_tables: in_perm, in_sign, act_perm, act_sign) to the policy set_policy attached: act() and
+        act_step() then run the symmetric policy (csrc/mocca_policy.h: Symmetry), still one launch.  None detaches.  set_policy() with a
+        `DevicePolicy(symmetry=)` calls this; update_policy() leaves the symmetry alone.  May synchronise."""
+        if self.policy is None:
+            raise _lib.MoccaError("set_policy_symmetry needs a policy (set_policy)")
+        if tables is None:
+            _lib.check(self.lib.mocca_set_policy_symmetry(self.h, None, None, None, None), self.h)
+        else:
+            t = [np.ascontiguousarray(x, d) for x, d in zip(tables, (np.int32, np.float32, np.int32, np.float32))]
+            if (t[0].size, t[1].size, t[2].size, t[3].size) != (self.policy.in_dim, self.policy.in_dim, self.policy.act_dim, self.policy.act_dim):
+                raise ValueError(f"the mirror tables have {self.policy.in_dim} input and {self.policy.act_dim} action entries")
+            _lib.check(self.lib.mocca_set_policy_symmetry(self.h, *[x.ctypes.data_as(C.c_void_p) for x in t]), self.h)
+        if hasattr(self.policy, "with_symmetry"):
+            self.policy = self.policy.with_symmetry(tables)
+
+    def symmetric_policy(self, policy):
+        """A copy of `policy` (a `policy.DevicePolicy`) with the mirror tables of THIS env: built from get_mirror_indices() and, where the
+        policy's input is [obs | scan], the attached scan pattern (symmetry.mirror_tables).  Envs whose reference publishes no six index
+        lists raise NotImplementedError."""
+        from .symmetry import mirror_tables
+        mi = self.get_mirror_indices()
+        if isinstance(mi, dict):
+            raise NotImplementedError("the Cassie mocap envs publish a dict of index lists (env_cassie.py:554-571), not get_mirror_indices()'s six")
+        scan = getattr(self, "_scan_points", None)
+        if policy.in_dim == self.obs_dim:
+            scan = None
+        elif scan is None or policy.in_dim != self.obs_dim + len(scan):
+            raise ValueError(f"the policy's input has {policy.in_dim} entries, the env's observation {self.obs_dim}"
+                             + ("" if scan is None else f" and its height scan {len(scan)}"))
+        return policy.with_symmetry(mirror_tables(mi, self.obs_dim, policy.act_dim, scan_points=scan))
 
     def update_policy(self, params) -> None:
         """New weights for the attached policy, once per PPO iteration: a `DevicePolicy` of the same shapes, or a flat float32 tensor in
@@ -761,11 +795,13 @@ class VecEnv:
         are copied into the handle; may synchronise."""
         if points is None:
             _lib.check(self.lib.mocca_set_height_scan(self.h, None, 0, 0.0, 0.0), self.h)
+            self._scan_points = None
             return
         pts = np.ascontiguousarray(points.detach().cpu().numpy() if isinstance(points, torch.Tensor) else points, np.float32)
         if pts.ndim != 2 or pts.shape[1] != 2:
             raise ValueError("height-scan points must be [P, 2]")
         _lib.check(self.lib.mocca_set_height_scan(self.h, pts.ctypes.data_as(C.c_void_p), pts.shape[0], float(z_above), float(max_drop)), self.h)
+        self._scan_points = pts.copy()       # symmetric_policy() mirrors the pattern
 
     def height_scan(self, out: Optional[torch.Tensor] = None, obs: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Terrain heights under the pattern, relative to the base, of the state the handle holds: float32 [N, P] on the device, one launch,
