@@ -452,6 +452,69 @@ int mocca_gae(mocca_handle h, const float *rew_dev, const float *value_dev, cons
 int mocca_obs_stats(mocca_handle h, const float *rows_dev, int64_t n_rows, int row_stride, int dim, double *state_dev, double eps,
                     float *mean_dev, float *inv_std_dev, void *stream);
 
+/* ---- a PPO minibatch step on the device (no reference counterpart: the reference's trainers run it in torch, a few dozen small launches
+ *      per minibatch) ---- */
+
+/* mocca_ppo_grad    replaces the body of `ppo.update`'s minibatch loop up to `optimizer.step()`: `evaluate_actions`, the clipped surrogate,
+ *                   the value loss, `loss.backward()` -- four launches, for the plain policy of mocca_set_policy.  R rollout rows, B = n_rows
+ *                   of them form the minibatch.  obs_dev [R][obs_stride] f32: the first in_dim floats of a row are read, RAW (normalised in
+ *                   the kernel exactly as mocca_act does); action_dev [R][act_dim] the stored samples; old_logp_dev, adv_dev, returns_dev
+ *                   [R]; old_value_dev [R], may be NULL when value_clip == 0.  idx_dev [B] i64 (a chunk of torch.randperm): minibatch row b
+ *                   is rollout row idx_dev[b]; NULL: rows 0 .. B - 1.  THE INDEX RANGE IS NOT CHECKED on the device: every idx_dev[b] must
+ *                   lie in 0 .. R - 1, that is the caller's duty.  With every mean over the B rows:
+ *                       logp = sum_j ( -1/2 ((a_j - mu_j) / sigma_j)^2 - log_std_j - 1/2 log 2 pi )      r = exp(logp - old_logp)
+ *                       L_pi = -mean( min(r A, clamp(r, 1 - clip, 1 + clip) A) )
+ *                       L_v  = 1/2 mean( (v - ret)^2 )      value_clip != 0: 1/2 mean( max((v - ret)^2, (v_old + clamp(v - v_old, -clip, clip) - ret)^2) )
+ *                       H    = sum_j ( log_std_j + 1/2 + 1/2 log 2 pi )
+ *                       L    = L_pi + value_coef L_v - entropy_coef H
+ *                   The gradient is torch autograd's for that expression: a row reaches the actor unless A > 0 and r > 1 + clip, or A < 0
+ *                   and r < 1 - clip; the value-clip max passes the gradient of the larger term, of the unclipped one at a tie.  Per row,
+ *                   each line ONE IEEE f32 operation in this order, never contracted into an FMA; ib = 1.0f / f32(B), lo = 1.0f - f32(clip),
+ *                   hi = 1.0f + f32(clip), c = f32(clip), mu / v the heads of the actor / critic, ls = log_std:
+ *                       for j ascending:   s = expf(ls[j]);  d = a[j] - mu[j];  z = d / s
+ *                                          t = -0.5f * z;  t = t * z;  t = t - ls[j];  t = t - 0.9189385...;  logp = logp + f64(t)
+ *                       dl = f32(logp - f64(old_logp));  r = expf(dl)      (logp alone is summed in f64: ~20 terms of size 1 added in
+ *                                                                           f32 would leave 1e-6 in every ratio)
+ *                       s1 = r * A;  rc = min(max(r, lo), hi);  s2 = rc * A;  surrogate = min(s1, s2)
+ *                       g = A * r;  g = g * ib;  g = -g            (dL/dlogp; g = 0 for a row that does not reach the actor)
+ *                       for j:             w = z / s;  dL/dmu[j] = g * w
+ *                                          q = z * z;  q = q - 1.0f;  dL/dlog_std[j] (the row's term) = g * q
+ *                       e = v - ret;  l = e * e;  dv = e
+ *                       value_clip:        dd = v - v_old;  dc = min(max(dd, -c), c);  vc = v_old + dc;  e2 = vc - ret;  l2 = e2 * e2
+ *                                          if (dd < -c or dd > c) and l2 > l:  l = l2;  dv = 0
+ *                                          (where the clamp passes, -c <= dd <= c, vc IS v and the two terms are the same function of v: a
+ *                                          tie, so the unclipped term and its gradient are used rather than a rounding of vc)
+ *                       value loss = 0.5f * l;  dv = f32(value_coef) * dv;  dL/dv = dv * ib
+ *                   Through the layers: dZ = dA * act'(x), the derivative formed in the forward from the pre-activation x -- tanh:
+ *                   sech^2 x = 4 e / (1 + e)^2 with e = expf(-2 |x|); relu: 1 where x > 0; softsign: 1 / (1 + |x|)^2; identity: 1 -- and kept
+ *                   where dZ will go: the same functions as 1 - y y and (1 - |y|)^2 of the output y, without their cancellation where a unit
+ *                   saturates.  The matrix products run on the matrix cores in f32 with a fixed order of sums
+ *                   (mocca_envs_amd/csrc/mocca_ppo.h), rows ascending: the same inputs give the same bits on every run and on every
+ *                   device.  grad_dev [n_head] f32 in mocca_update_policy's order -- per layer W[out][in] row-major then b[out], actor then
+ *                   critic, then log_std[act_dim], n_head = that order's length without mean / inv_std -- is fully overwritten; log_std's
+ *                   entry is the rows' sum minus f32(entropy_coef).  stats_dev [8] f32 or NULL: mean of the surrogate (= -L_pi), L_v,
+ *                   H (summed in f64, stored as f32), mean(old_logp - logp), the fraction of rows with r outside [lo, hi] (the count divided by B), the sum of grad_dev^2
+ *                   (summed in f64, stored as f32), 0, 0.  The means multiply by ib.
+ *                   The forward is mocca_act's layer loop with ONE difference: tanh is (float)tanh((double)x), rounded once, where
+ *                   mocca_act calls tanhf; logp and the value recomputed at unchanged weights therefore differ from what mocca_act stored by
+ *                   an ulp or two, and the first minibatch's ratio is 1 +- 1e-6 rather than exactly 1.
+ *                   Scratch (every layer's activations and their gradients for B rows) is kept in the handle: allocated on the first call
+ *                   and on one that needs more, and such a call may synchronise.  Its size is 4 B (in_pad + 2 sum of the layers' out_pad
+ *                   + 48) bytes plus 16 padded gradients at most: for the 52 -> 256 -> 256 -> {21, 1} policy 9 KB per row, 150 MB at
+ *                   B = 16384 and 38 GB at the bound of 2^22 rows, where the allocation may fail (MOCCA_E_HIP; the handle keeps its old
+ *                   scratch).  A call that grows the scratch FREES the old one: a graph captured at a smaller B still points to it and
+ *                   must be recaptured -- warm the handle with the largest B it will see before capturing.  Every other call is asynchronous on `stream`: no
+ *                   allocation, no host read, no synchronisation, no atomics -- after one warm call with the same B it is capturable in a
+ *                   hipGraph as a linear chain.  It reads the policy image that mocca_update_policy last wrote (an update between two
+ *                   replays is seen) and none of the handle's env records; it writes only grad_dev, stats_dev and its scratch.
+ * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): a NULL handle; called before mocca_set_policy / mocca_update_policy; a
+ * NULL obs_dev, action_dev, old_logp_dev, adv_dev, returns_dev or grad_dev; value_clip with old_value_dev NULL; n_rows < 1 or > 2^22;
+ * obs_stride < in_dim; a non-finite or negative clip, value_coef or entropy_coef; a handle with mirror tables attached
+ * (mocca_set_policy_symmetry) -- the symmetric policy's backward is not implemented: detach the tables first. */
+int mocca_ppo_grad(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
+                   const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
+                   double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
+
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */
 int mocca_kernel_info(mocca_handle h, int *vgprs, int *sgprs, int *lds_bytes, int *scratch_bytes, int *max_blocks_per_cu);

@@ -84,6 +84,21 @@ def layer_image(w, b):
     return blocks.transpose(0, 2, 3, 1, 4).reshape(-1), bias                       # [rb][cb][quarter][row][4]: lane = 16 quarter + row
 
 
+def layer_image_transposed(w):
+    """the second copy of a layer's weights that the PPO backward reads (csrc/mocca_ppo.h: Image): layer_image's fragment order of W.T --
+    in and out swap roles and padding -> float32 [in_pad * out_pad]"""
+    return layer_image(np.ascontiguousarray(np.asarray(w, np.float32).T), np.zeros(np.shape(w)[1], np.float32))[0]
+
+
+def unpack_transposed(image, n_in, n_out):
+    """layer_image_transposed's inverse -> W float32 [out][in]; non-zero padding is a ValueError"""
+    p_in, p_out = _round16(n_in), _round16(n_out)
+    full = np.asarray(image, np.float32).reshape(p_in // 16, p_out // 16, 4, 16, 4).transpose(0, 3, 1, 2, 4).reshape(p_in, p_out)
+    if full[n_in:].any() or full[:, n_out:].any():
+        raise ValueError("padding of a transposed layer image must be zeros")
+    return np.ascontiguousarray(full[:n_in, :n_out].T)
+
+
 def pack_nets(actor, critic):
     """-> (float32 [n]: per layer, actor first, layer_image's weights then its bias; layer_table with the offsets into it)"""
     return np.concatenate([part for w, b, _ in actor + critic for part in layer_image(w, b)]), layer_table(actor, critic, "image")

@@ -14,6 +14,7 @@
 #include "mocca.h"
 #include "mocca_kernels.h"
 #include "mocca_policy.h"
+#include "mocca_ppo.h"
 #include "mocca_render.h"
 #include "mocca_rollout.h"
 #include "mocca_scan.h"
@@ -159,6 +160,9 @@ struct mocca_ctx {
   mocca_pol::RepackArgs pol_repack{};   // rows of the repack kernel; src offsets in the caller's flat parameters
   size_t pol_n_base = 0;             // floats of mocca_update_policy's params_dev without the normalisation arrays
   bool pol_filled = false;           // mocca_update_policy has run since mocca_set_policy
+  int pol_tail_row = 0;              // pol_repack's row of the flags; the rows of mean and inv_std follow it
+  std::vector<int32_t> pol_table;    // host copy of d_pol_layers (offsets into the image)
+  int pol_wt_off[mocca_ppo::PPO_MAX_TABLE] = {};   // the layers' transposed copies in the image (mocca_ppo.h), -1: none
   DevBuf<int32_t> d_pol_sym_perm;    // mocca_set_policy_symmetry: in_perm [in_dim] then act_perm [act_dim]; pol.in_perm / act_perm point into it
   DevBuf<float> d_pol_sym_sign;      // in_sign [in_dim] then act_sign [act_dim]
   // scratch of mocca_gae / mocca_obs_stats (mocca_rollout.h), owned by the handle, grown on demand
@@ -166,6 +170,8 @@ struct mocca_ctx {
   size_t gae_part_cap = 0;           // doubles
   DevBuf<double> d_obs_part;         // [blocks][dim][2]
   size_t obs_part_cap = 0;
+  DevBuf<double> d_ppo;              // scratch of mocca_ppo_grad (mocca_ppo.h), grown on demand
+  size_t ppo_cap = 0;
   std::string err;
 };
 static_assert(ROBOT_STATE_STRIDE == mocca_ctrl::CTRL_RS_STRIDE, "the step kernels and the controller kernel share the robot_state buffer");
@@ -241,24 +247,29 @@ static std::string check_layer_table(const int32_t* layers, int n_layers_total, 
 // The image of a checked layer table (mocca_policy.h) in new device buffers: the table with its offsets pointing into the image, the zeroed
 // image, the rows that tell the repack kernel where each piece of the source parameters goes, and the kernel's shapes and image offsets.
 // `packed`: the source is W[out][in], b[out] layer after layer, then log_std (n_src: floats of that); otherwise the table's own w_off /
-// b_off say where a layer's weights and bias lie in it, and log_std is zeros.  The last three rows (flags, mean, inv_std) come out as zeros:
-// mocca_update_policy sets their source per call.
+// b_off say where a layer's weights and bias lie in it, and log_std is zeros.  The rows tail_row .. + 2 (flags, mean, inv_std) come out as
+// zeros: mocca_update_policy sets their source per call.  A packed image ends in the transposed copies of the weights of every layer but a
+// net's first (mocca_ppo.h: Image), behind everything the policy kernel reads: wt_off says where, -1 for a layer without one.
 struct NetImage {
   DevBuf<float> image;
   DevBuf<int32_t> layers;
   mocca_pol::PolicyArgs pa{};
   mocca_pol::RepackArgs rp{};
   size_t n_src = 0;
+  int tail_row = 0;
+  std::vector<int32_t> table;
+  int wt_off[mocca_ppo::PPO_MAX_TABLE];
 };
 static hipError_t build_image(NetImage& im, const int32_t* layers_host, int n_layers_total, const int count[2], int in_dim, int act_dim, bool packed) {
   using namespace mocca_ctrl;
   using namespace mocca_pol;
-  std::vector<int32_t> table(layers_host, layers_host + (size_t)n_layers_total * CTRL_LAYER_WORDS);
+  std::vector<int32_t>& table = im.table;
+  table.assign(layers_host, layers_host + (size_t)n_layers_total * CTRL_LAYER_WORDS);
   const int in_pad = (in_dim + 15) / 16 * 16;
   int pos = 0, src = 0, nr = 0;
   auto row = [&](int floats, int src_off, int in, int out, int ipad) {
     RepackRow& q = im.rp.rows[nr++];
-    q.dst = pos; q.dst_end = pos + floats; q.src = src_off; q.in = in; q.out = out; q.in_pad = ipad; q.fill = 0.0f;
+    q.dst = pos; q.dst_end = pos + floats; q.src = src_off; q.in = in; q.out = out; q.in_pad = ipad; q.fill = 0.0f; q.transposed = 0;
     pos += floats;
     return q.dst;
   };
@@ -273,9 +284,19 @@ static hipError_t build_image(NetImage& im, const int32_t* layers_host, int n_la
   PolicyArgs& pa = im.pa;
   pa.log_std_off = row(POL_MAX_ACTION, packed ? src : -1, 0, act_dim, 0);
   im.n_src = (size_t)src + act_dim;
+  im.tail_row = nr;
   pa.flags_off = row(POL_FLAG_WORDS, -1, 0, 1, 0);
   pa.mean_off = row(in_pad, -1, 0, in_dim, 0);
   pa.inv_std_off = row(in_pad, -1, 0, in_dim, 0);
+  for (int i = 0, s = 0; i < n_layers_total; ++i) {   // W^T of a layer: in and out swap roles and padding
+    const int32_t* r = &table[(size_t)i * CTRL_LAYER_WORDS];
+    im.wt_off[i] = -1;
+    if (packed && i != 0 && i != count[0]) {
+      im.wt_off[i] = row(r[CL_IN_PAD] * r[CL_OUT_PAD], s, r[CL_OUT], r[CL_IN], r[CL_OUT_PAD]);
+      im.rp.rows[nr - 1].transposed = 1;
+    }
+    s += r[CL_IN] * r[CL_OUT] + r[CL_OUT];
+  }
   im.rp.n_rows = nr; im.rp.image_floats = pos;
   hipError_t e = im.image.alloc((size_t)pos, true);
   if (e == hipSuccess) e = im.layers.alloc(table.size(), false);
@@ -1068,6 +1089,8 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
   h->d_pol_image.swap(im.image); h->d_pol_layers.swap(im.layers);
   h->pol = im.pa; h->pol.clip = (float)clip;
   h->pol_repack = im.rp; h->pol_n_base = im.n_src; h->pol_filled = false;
+  h->pol_tail_row = im.tail_row; h->pol_table.swap(im.table);
+  std::memcpy(h->pol_wt_off, im.wt_off, sizeof(im.wt_off));
   drop_policy_symmetry(h);   // the shapes may have changed
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy"); }
@@ -1134,9 +1157,9 @@ int mocca_update_policy(mocca_handle h, const float* params_dev, size_t n_floats
   mocca_pol::RepackArgs rp = h->pol_repack;
   rp.src = params_dev;
   const bool norm = n_floats != base;
-  rp.rows[rp.n_rows - 3].fill = norm ? 1.0f : 0.0f;
-  rp.rows[rp.n_rows - 2].src = norm ? (int32_t)base : -1;
-  rp.rows[rp.n_rows - 1].src = norm ? (int32_t)(base + in_dim) : -1;
+  rp.rows[h->pol_tail_row].fill = norm ? 1.0f : 0.0f;
+  rp.rows[h->pol_tail_row + 1].src = norm ? (int32_t)base : -1;
+  rp.rows[h->pol_tail_row + 2].src = norm ? (int32_t)(base + in_dim) : -1;
   mocca_pol::launch_repack((hipStream_t)stream, rp);
   HIP_TRY(h, hipGetLastError());
   h->pol_filled = true;
@@ -1247,6 +1270,62 @@ int mocca_obs_stats(mocca_handle h, const float* rows_dev, int64_t n_rows, int r
   if (int rc = grow_scratch(h, "mocca_obs_stats", h->d_obs_part, &h->obs_part_cap, 2 * (size_t)a.n_blocks * dim)) return rc;
   a.state = state_dev; a.partials = h->d_obs_part; a.eps = (float)eps; a.mean_out = mean_dev; a.inv_std_out = inv_std_dev;
   mocca_ro::launch_obs_stats((hipStream_t)stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
+}
+
+int mocca_ppo_grad(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev, const float* adv_dev,
+                   const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev, int64_t n_rows, double clip, double value_coef,
+                   double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
+  using namespace mocca_ctrl;
+  using namespace mocca_ppo;
+  if (!h) { g_err = "mocca_ppo_grad: NULL handle"; return MOCCA_E_ARG; }
+  auto bad = [&](const std::string& what) { h->err = "mocca_ppo_grad: " + what; return MOCCA_E_ARG; };
+  if (!h->d_pol_image || !h->pol_filled) return bad("needs a policy (mocca_set_policy, then mocca_update_policy)");
+  if (h->pol.in_perm) return bad("the symmetric policy's backward is not implemented: detach the mirror tables (mocca_set_policy_symmetry)");
+  if (!obs_dev || !action_dev || !old_logp_dev || !adv_dev || !returns_dev || !grad_dev)
+    return bad("obs_dev, action_dev, old_logp_dev, adv_dev, returns_dev and grad_dev must not be NULL");
+  if (value_clip && !old_value_dev) return bad("value_clip needs old_value_dev");
+  if (n_rows < 1 || n_rows > PPO_MAX_ROWS) return bad("n_rows must be 1 .. 2^22, not " + std::to_string(n_rows));
+  if (obs_stride < h->pol.in_dim)
+    return bad("obs_stride " + std::to_string(obs_stride) + " is smaller than the policy's in_dim (" + std::to_string(h->pol.in_dim) + ")");
+  if (!std::isfinite(clip) || clip < 0.0 || !std::isfinite(value_coef) || value_coef < 0.0 || !std::isfinite(entropy_coef) || entropy_coef < 0.0)
+    return bad("clip, value_coef and entropy_coef must be finite and not negative");
+  DeviceGuard guard(h->device);
+  PpoArgs a{};
+  const mocca_pol::PolicyArgs& p = h->pol;
+  a.params = p.params; a.layers = p.layers; a.n_actor = p.n_actor; a.n_critic = p.n_critic;
+  a.log_std_off = p.log_std_off; a.flags_off = p.flags_off; a.mean_off = p.mean_off; a.inv_std_off = p.inv_std_off;
+  a.in_dim = p.in_dim; a.in_pad = p.in_pad; a.act_dim = p.act_dim; a.norm_clip = p.clip;
+  std::memcpy(a.wt_off, h->pol_wt_off, sizeof(a.wt_off));
+  a.obs = obs_dev; a.obs_stride = obs_stride; a.action = action_dev; a.old_logp = old_logp_dev; a.adv = adv_dev; a.returns = returns_dev;
+  a.old_value = old_value_dev; a.idx = idx_dev;
+  a.n_rows = (int)n_rows; a.b_pad = (int)((n_rows + 15) / 16 * 16);
+  a.clip = (float)clip; a.value_coef = (float)value_coef; a.entropy_coef = (float)entropy_coef; a.inv_b = 1.0f / (float)n_rows;
+  a.value_clip = value_clip != 0;
+  // the scratch (mocca_ppo.h), in floats; every piece a multiple of 4 floats, so that rows stay 16-byte aligned
+  const long long bp = a.b_pad;
+  const int n_layers = p.n_actor + p.n_critic;
+  long long pos = 0;
+  int n_tiles = PPO_ROW_COLS / 16, n_head = p.act_dim;
+  a.a0_off = pos; pos += bp * p.in_pad;
+  for (int i = 0; i < n_layers; ++i) {
+    const int32_t* r = &h->pol_table[(size_t)i * CTRL_LAYER_WORDS];
+    a.a_off[i] = pos; pos += bp * r[CL_OUT_PAD];
+    a.dz_off[i] = pos; pos += bp * r[CL_OUT_PAD];
+    n_tiles += (r[CL_OUT_PAD] / 16) * (r[CL_IN_PAD] / 16) + r[CL_OUT_PAD] / 16;
+    n_head += r[CL_IN] * r[CL_OUT] + r[CL_OUT];
+  }
+  a.r_off = pos; pos += bp * PPO_ROW_COLS;
+  ppo_chunks(a.b_pad, &a.n_chunks, &a.chunk_rows);
+  a.p_floats = p.log_std_off + PPO_ROW_COLS;
+  a.p_off = pos; pos += (long long)a.n_chunks * a.p_floats;
+  a.n_tiles = n_tiles; a.n_head = n_head; a.n_reduce_blocks = (n_head + PPO_REDUCE_BLOCK - 1) / PPO_REDUCE_BLOCK;
+  const size_t f_doubles = (size_t)(pos + 1) / 2;
+  if (int rc = grow_scratch(h, "mocca_ppo_grad", h->d_ppo, &h->ppo_cap, f_doubles + (size_t)a.n_reduce_blocks)) return rc;
+  a.scratch = (float*)h->d_ppo.get(); a.sq_part = h->d_ppo.get() + f_doubles;
+  a.grad = grad_dev; a.stats = stats_dev;
+  launch_ppo((hipStream_t)stream, a);
   HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
 }

@@ -14,6 +14,8 @@
 //               DEVICE word, so that an update between two replays of a captured launch switches it without a recapture)
 //   mean        [in_pad], zeros past in_dim
 //   inv_std     [in_pad], zeros past in_dim        x = clamp((x - mean[k]) * inv_std[k], -clip, +clip), f32, in that operation order
+//   transposed  behind everything above (the policy kernel reads none of it): the weights of every layer but a net's first once more,
+//               transposed, for mocca_ppo_grad's backward (mocca_ppo.h: Image)
 //
 // Noise.  mocca_act has three modes: deterministic (eps = 0: the action is the mean), caller noise (eps_dev [N][act_dim]) and, the default,
 // noise drawn in the kernel: Philox4x32-10 under the handle's seed key with the counter
@@ -93,9 +95,9 @@ struct RepackRow {
   int32_t src;                  // offset in the caller's parameters, < 0: the first `out` floats are `fill`, the rest zeros
   int32_t in, out, in_pad;      // weights: W[out][in] -> fragment order over in_pad columns; in_pad = 0: a plain array of `out` floats, zero padded
   float fill;
-  int32_t pad_;
+  int32_t transposed;           // weights: != 0: the row's matrix [out][in] is the transpose of the source's W[in][out] (mocca_ppo.h: Image)
 };
-constexpr int POL_MAX_REPACK_ROWS = 4 * POL_MAX_LAYERS + 4;   // weights + bias of 16 layers, log_std, flags, mean, inv_std
+constexpr int POL_MAX_REPACK_ROWS = 6 * POL_MAX_LAYERS + 4;   // weights + bias of 16 layers, log_std, flags, mean, inv_std; 16 transposed copies
 struct RepackArgs {
   const float* src;
   float* image;

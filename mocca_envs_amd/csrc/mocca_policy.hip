@@ -206,7 +206,9 @@ __global__ __launch_bounds__(256) void repack_kernel(RepackArgs a) {
     const int nkg = row.in_pad >> 4;
     const int ot = idx / (nkg * 256), rem = idx - ot * nkg * 256, kg = rem >> 8, l = (rem & 255) >> 2, j = rem & 3;
     const int orow = 16 * ot + (l & 15), k = 16 * kg + 4 * (l >> 4) + j;
-    v = orow < row.out && k < row.in ? a.src[row.src + (size_t)orow * row.in + k] : 0.0f;
+    // transposed (mocca_ppo.h: Image): the row's matrix is the source's transpose, its element [orow][k] the source's [k][orow]
+    const size_t at = row.transposed ? (size_t)k * row.out + orow : (size_t)orow * row.in + k;
+    v = orow < row.out && k < row.in ? a.src[row.src + at] : 0.0f;
     break;
   }
   a.image[i] = v;

@@ -1,0 +1,91 @@
+// mocca_ppo.h -- the body of a PPO minibatch step up to optimizer.step() as kernels (mocca_ppo.hip): evaluate_actions, the clipped
+// surrogate, the value loss and loss.backward() for the plain Gaussian actor-critic of mocca_policy.h.  mocca_ppo_grad (mocca_api.hip) checks
+// the caller's arguments, owns the scratch and launches them.  The loss and the per-row formulas: include/mocca.h.
+//
+// Image.  The kernels read the policy image of mocca_policy.h and, behind it, a SECOND copy of every layer's weights but a net's first,
+// transposed: layer l's W[out][in] as the [in_pad / 16][out_pad / 16][64][4] fragment order of W^T (in and out swap roles and padding), so
+// that dA_{l-1} = W^T dZ_l runs through the forward's MFMA loop.  The repack kernel writes both copies in its one launch (RepackRow.transposed);
+// PpoArgs.wt_off[layer] is the float offset of a layer's transposed copy, -1 for a first layer.
+//
+// Scratch (f32, owned by the handle), B_pad = B rounded up to 16, layer = row of the layer table:
+//   A0      [B_pad][in_pad]               the normalised input (written by the actor's workgroups)
+//   A[l]    [B_pad][out_pad_l]            layer l's output activation y
+//   dZ[l]   [B_pad][out_pad_l]            dL/d(pre-activation) of layer l; between the forward and the backward: act'(x) of layer l
+//   R       [B_pad][PPO_ROW_COLS]         per row: 0 .. 31 the log_std gradient terms, 32 surrogate, 33 value loss, 34 old_logp - logp,
+//                                         35 clipped (0 / 1), 36 .. 47 zeros
+//   P       [n_chunks][p_floats]          chunk partials of the padded gradient: a layer's dW[out_pad][in_pad] row-major at the image's
+//                                         w_off, its db[out_pad] at b_off, the column sums of R at log_std_off
+//   Q       [reduce blocks] f64           sums of grad^2 of the reduce kernel's workgroups
+// Rows past B are zeros everywhere, so the row loops of launch 2 have no bounds logic.
+//
+// Launch 1 (ppo_rows_kernel): grid ceil(B / 16) x {actor, critic}, 256 threads.  A workgroup gathers its 16 rows through idx, normalises them
+// as the policy kernel does and runs that kernel's layer loop (same operand layout, same order of sums; tanh alone differs: (float)tanh((double)x), rounded once,
+// where the policy kernel calls tanhf -- so logp and value recomputed at unchanged weights differ from what mocca_act stored by an ulp or
+// two and the first minibatch's ratio is 1 +- 1e-6, not exactly 1), storing every layer's output.  Head stage: one lane per row forms the row's loss terms and dL/dhead.  Backward, from the head down:
+//     dZ_l = dA_l * act'(x_l)      tanh: sech^2 x;  relu: x > 0;  softsign: 1 / (1 + |x|)^2;  identity: 1    (formed in the forward from the
+//                                  pre-activation x and parked in dZ_l: 1 - y y from the output cancels where a unit saturates)
+//     dA_{l-1} = W_l^T dZ_l        the forward's MFMA loop over the transposed copy; not formed for a net's first layer
+// Launch 2 (ppo_wgrad_kernel): one wave per (tile, row chunk).  A weight tile is 16 x 16 of dW_l = sum_rows dZ_l[row][o] A_{l-1}[row][k]:
+// v_mfma_f32_16x16x4_f32 over the chunk's rows in ascending order, 16 rows per trip into FOUR accumulators (MFMA j takes rows 4 j .. 4 j + 3
+// of the trip), combined (p0 + p1) + (p2 + p3).  A column tile sums 16 columns of dZ_l (db_l) or of R: lane (quad, column) adds rows quad,
+// quad + 4, .. in f64, the four quads are added (q0 + q1) + (q2 + q3).  The chunk count is a function of B alone (ppo_chunks): the result
+// does not depend on the device.
+// Launch 3 (ppo_reduce_kernel): one thread per gradient float, un-padded, in mocca_update_policy's order: adds the chunks' partials in chunk
+// order in f32, scales nothing (the 1 / B is in dL/dhead), adds -entropy_coef to log_std's; a workgroup adds its squares in f64 in a fixed tree.
+// Launch 4 (ppo_stats_kernel): ONE workgroup adds the workgroups' squares in index order in f64 and writes stats[0..7].
+// No atomics; every sum's order is a function of B and the shapes alone: the same inputs give the same bits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mocca_policy.h"
+
+namespace mocca_ppo {
+
+constexpr int PPO_ROW_COLS = 48;         // floats per row of R
+constexpr int PPO_COL_SURR = 32, PPO_COL_VLOSS = 33, PPO_COL_DLOGP = 34, PPO_COL_CLIPPED = 35;
+constexpr int PPO_MAX_CHUNKS = 16;       // row chunks of launch 2
+constexpr int PPO_CHUNK_MIN_ROWS = 512;  // a chunk holds at least this many rows
+constexpr int PPO_REDUCE_BLOCK = 256;
+constexpr int PPO_MAX_TABLE = 2 * mocca_pol::POL_MAX_LAYERS;
+constexpr long long PPO_MAX_ROWS = 1ll << 22;
+
+struct PpoArgs {
+  // the policy: image, layer table, shapes (PolicyArgs of the handle)
+  const float* params;
+  const int32_t* layers;
+  int n_actor, n_critic;
+  int log_std_off, flags_off, mean_off, inv_std_off;
+  int in_dim, in_pad, act_dim;
+  float norm_clip;
+  int wt_off[PPO_MAX_TABLE];             // transposed copies (header: Image)
+  // the minibatch
+  const float* obs; int obs_stride;
+  const float *action, *old_logp, *adv, *returns, *old_value;
+  const int64_t* idx;                    // [B] or null: rows 0 .. B - 1
+  int n_rows, b_pad;                     // B, B rounded up to 16
+  float clip, value_coef, entropy_coef, inv_b;
+  int value_clip;
+  // scratch (header: Scratch); float offsets of A[l] / dZ[l] from `scratch`
+  float* scratch;
+  long long a0_off, a_off[PPO_MAX_TABLE], dz_off[PPO_MAX_TABLE], r_off, p_off;
+  int p_floats, n_chunks, chunk_rows;    // chunk_rows: a multiple of 16
+  int n_tiles;                           // weight and column tiles of launch 2
+  double* sq_part;                       // Q
+  int n_head, n_reduce_blocks;
+  float* grad;                           // [n_head]
+  float* stats;                          // [8] or null
+};
+
+// row chunks of launch 2 for a minibatch of b_pad rows: a function of B alone
+inline void ppo_chunks(int b_pad, int* n_chunks, int* chunk_rows) {
+  int c = (b_pad + PPO_CHUNK_MIN_ROWS - 1) / PPO_CHUNK_MIN_ROWS;
+  if (c > PPO_MAX_CHUNKS) c = PPO_MAX_CHUNKS;
+  const int rows = ((b_pad / 16 + c - 1) / c) * 16;
+  *chunk_rows = rows;
+  *n_chunks = (b_pad + rows - 1) / rows;
+}
+
+void launch_ppo(hipStream_t s, const PpoArgs& a);
+
+}  // namespace mocca_ppo

@@ -1,0 +1,382 @@
+// mocca_ppo.hip -- PPO's minibatch loss and its gradient with respect to every parameter of the plain Gaussian actor-critic, on the device
+// (mocca_ppo_grad).  What each launch does, the scratch and the transposed weight copy: mocca_ppo.h.  The loss and the per-row formulas:
+// include/mocca.h.
+//
+// Arithmetic: the policy kernel's (mocca_policy.hip).  The layer loop below is that kernel's loop, copied -- mocca_policy.hip's kernel is left
+// as it is -- with the epilogue as a parameter: the forward adds the bias, activates and also stores the output to scratch; the backward
+// (the same loop over the transposed copy) stores dA to LDS only.
+#include <hip/hip_runtime.h>
+
+#include "mocca_ppo.h"
+
+// every f32 / f64 operation written below is that IEEE operation: a * b + c stays two roundings (include/mocca.h names each of them)
+#pragma clang fp contract(off)
+
+namespace mocca_ppo {
+
+using namespace mocca_ctrl;   // CL_*, CTRL_ACT_*
+using namespace mocca_pol;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int LDS_STRIDE = POL_MAX_IN + 4;   // the policy kernel's LDS row
+constexpr int NP = 4, NT = 4, TILE = POL_TILE;
+static_assert(TILE == 16, "one 16-row MFMA sub-tile per workgroup");
+
+__device__ __forceinline__ float activate(float x, int act) {
+  switch (act) {
+    case CTRL_ACT_RELU: return fmaxf(x, 0.0f);
+    case CTRL_ACT_TANH: return (float)tanh((double)x);   // rounded once: the stored activations feed dW, and tanhf's 2 ulp showed in small nets
+    case CTRL_ACT_SOFTSIGN: return x / (1.0f + fabsf(x));
+    default: return x;
+  }
+}
+// the activation's derivative, from its INPUT x: where the unit saturates, 1 - y y and (1 - |y|)^2 cancel and carry the rounding of y
+// magnified by 1 / (1 - |y|); from x the derivative keeps a few ulp of relative error at any x
+__device__ __forceinline__ float activate_slope(float x, int act) {
+  switch (act) {
+    case CTRL_ACT_RELU: return x > 0.0f ? 1.0f : 0.0f;
+    case CTRL_ACT_TANH: { const float e = expf(-2.0f * fabsf(x)), d = 1.0f + e; return (4.0f * e) / (d * d); }   // sech^2 x
+    case CTRL_ACT_SOFTSIGN: { const float u = 1.0f / (1.0f + fabsf(x)); return u * u; }
+    default: return 1.0f;
+  }
+}
+
+// out[o][col] = sum_k W[o][k] Xin[col][k] for the 16 columns of the workgroup: W in fragment order [n_ot][nkg][64][4]; epi(o, sum) receives
+// rows o .. o + 3 of column `col` (lane & 15), sum = (p0 + p1) + (p2 + p3).  mocca_policy.hip's loop.
+template <class Epi>
+__device__ __forceinline__ void mfma_layer(const f32x4* W, int nkg, int n_ot, const float* Xin, int wave, int lane, Epi epi) {
+  const int col = lane & 15, quad = lane >> 4;
+  const int nt_w = wave < n_ot ? (n_ot - wave + 3) >> 2 : 0;   // output tiles of this wave (wave-uniform)
+  if (nt_w == 0) return;
+  f32x4 acc[NT][NP];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int j = 0; j < NP; ++j) acc[t][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  const f32x4* wp[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int ot = wave + 4 * (t < nt_w ? t : nt_w - 1);
+    wp[t] = W + (size_t)ot * nkg * 64 + lane;
+  }
+  f32x4 w0[NT], w1[NT], w2[NT];
+  auto load = [&](f32x4 (&w)[NT], int kg) {
+    const int kc = kg < nkg ? kg : nkg - 1;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) w[t] = wp[t][(size_t)kc * 64];
+  };
+  auto multiply = [&](const f32x4 (&w)[NT], int kg) {
+    const f32x4 b = *(const f32x4*)&Xin[col * LDS_STRIDE + kg * 16 + quad * 4];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (t < nt_w) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][j], b[j], acc[t][j], 0, 0, 0);
+      }
+  };
+  load(w0, 0); load(w1, 1);
+#pragma unroll 1
+  for (int kg = 0; kg < nkg; kg += 3) {
+    load(w2, kg + 2); multiply(w0, kg);
+    if (kg + 1 >= nkg) break;
+    load(w0, kg + 3); multiply(w1, kg + 1);
+    if (kg + 2 >= nkg) break;
+    load(w1, kg + 4); multiply(w2, kg + 2);
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    if (t < nt_w) epi((wave + 4 * t) * 16 + quad * 4, (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]));
+}
+
+__global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
+  __shared__ __attribute__((aligned(16))) float X[2][TILE * LDS_STRIDE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.x * TILE, net = blockIdx.y;
+  const int col = lane & 15;
+  const int B = a.n_rows;
+
+  // input: the policy kernel's staging, the rows gathered through idx; the normalised tile also goes to A0
+  {
+    const bool norm = a.params[a.flags_off] != 0.0f;
+    const float *mu = a.params + a.mean_off, *is = a.params + a.inv_std_off;
+    float* A0 = a.scratch + a.a0_off;
+    for (int i = tid; i < TILE * a.in_pad; i += 256) {
+      const int e = i / a.in_pad, k = i - e * a.in_pad, row = row0 + e;
+      float v = 0.0f;
+      if (row < B && k < a.in_dim) {
+        const long long src = a.idx ? (long long)a.idx[row] : row;
+        v = a.obs[(size_t)src * a.obs_stride + k];
+        if (norm) v = fminf(fmaxf((v - mu[k]) * is[k], -a.norm_clip), a.norm_clip);
+      }
+      X[0][e * LDS_STRIDE + k] = v;
+      if (net == 0) A0[(size_t)row * a.in_pad + k] = v;
+    }
+  }
+  __syncthreads();
+
+  const int first = net == 0 ? 0 : a.n_actor, count = net == 0 ? a.n_actor : a.n_critic;
+  const bool live = row0 + col < B;   // this lane's MFMA column is a row of the minibatch
+  int cur = 0;
+#pragma unroll 1
+  for (int li = 0; li < count; ++li) {
+    const int32_t* lr = a.layers + (size_t)(first + li) * CTRL_LAYER_WORDS;
+    const int out_pad = lr[CL_OUT_PAD], act = lr[CL_ACT];
+    const float* Bias = a.params + lr[CL_B_OFF];
+    float* Xout = X[cur ^ 1];
+    float* Y = a.scratch + a.a_off[first + li] + (size_t)(row0 + col) * out_pad;
+    float* S = a.scratch + a.dz_off[first + li] + (size_t)(row0 + col) * out_pad;
+    mfma_layer((const f32x4*)(a.params + lr[CL_W_OFF]), lr[CL_IN_PAD] >> 4, out_pad >> 4, X[cur], wave, lane, [&](int o, f32x4 sum) {
+      const f32x4 bias = *(const f32x4*)(Bias + o);
+      f32x4 y, slope;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float x = sum[r] + bias[r];
+        y[r] = activate(x, act);
+        slope[r] = live ? activate_slope(x, act) : 0.0f;
+      }
+      *(f32x4*)(S + o) = slope;   // act'(x) waits in dZ's place until the backward multiplies it by dA
+      *(f32x4*)&Xout[col * LDS_STRIDE + o] = y;
+      *(f32x4*)(Y + o) = live ? y : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    });
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // head stage: one lane per row -> the row's loss terms (R) and dL/dhead, the backward's first dA, in the other LDS buffer
+  if (tid < TILE) {
+    const int row = row0 + tid;
+    const float* head = &X[cur][tid * LDS_STRIDE];
+    float* dA = &X[cur ^ 1][tid * LDS_STRIDE];
+    float* R = a.scratch + a.r_off + (size_t)row * PPO_ROW_COLS;
+    const int head_pad = (a.layers + (size_t)(first + count - 1) * CTRL_LAYER_WORDS)[CL_OUT_PAD];
+    const long long src = row < B ? (a.idx ? (long long)a.idx[row] : row) : 0;
+    if (net == 1) {
+      float dv = 0.0f, vloss = 0.0f;
+      if (row < B) {   // include/mocca.h: one f32 operation per line of it, in that order
+        const float v = head[0], ret = a.returns[src];
+        const float e = v - ret;
+        float l = e * e;
+        dv = e;
+        if (a.value_clip) {
+          const float vo = a.old_value[src];
+          const float dl = v - vo;
+          const float dc = fminf(fmaxf(dl, -a.clip), a.clip);
+          const float vc = vo + dc;
+          const float e2 = vc - ret;
+          const float l2 = e2 * e2;
+          // where the clamp passes, vc is v and both terms are the same function of v: a tie, the unclipped term is used
+          if ((dl < -a.clip || dl > a.clip) && l2 > l) {
+            l = l2;
+            dv = 0.0f;
+          }
+        }
+        vloss = 0.5f * l;
+        dv = a.value_coef * dv;
+        dv = dv * a.inv_b;
+      }
+      R[PPO_COL_VLOSS] = vloss;
+      for (int j = 0; j < head_pad; ++j) dA[j] = j == 0 ? dv : 0.0f;
+    } else {
+      const float* log_std = a.params + a.log_std_off;
+      const int A = a.act_dim;
+      float g = 0.0f, surr = 0.0f, dlogp = 0.0f, clipped = 0.0f;
+      if (row < B) {
+        double lp64 = 0.0;   // the terms are f32, their sum is f64: 21 terms of size ~1 in f32 would leave ~1e-6 in the ratio
+        for (int j = 0; j < A; ++j) {
+          const float ls = log_std[j];
+          const float s = expf(ls);
+          const float d = a.action[(size_t)src * A + j] - head[j];
+          const float z = d / s;
+          lp64 += (double)((-0.5f * z) * z - ls - 0.91893853320467274178f);
+        }
+        const float olp = a.old_logp[src], adv = a.adv[src];
+        const float dl = (float)(lp64 - (double)olp);
+        const float r = expf(dl);
+        const float lo = 1.0f - a.clip, hi = 1.0f + a.clip;
+        const float s1 = r * adv;
+        const float rc = fminf(fmaxf(r, lo), hi);
+        const float s2 = rc * adv;
+        surr = fminf(s1, s2);
+        dlogp = -dl;
+        clipped = r > hi || r < lo ? 1.0f : 0.0f;
+        const bool inactive = (adv > 0.0f && r > hi) || (adv < 0.0f && r < lo);
+        if (!inactive) {
+          g = adv * r;
+          g = g * a.inv_b;
+          g = -g;
+        }
+      }
+      for (int j = 0; j < head_pad || j < POL_MAX_ACTION; ++j) {
+        float dmu = 0.0f, dls = 0.0f;
+        if (row < B && j < A) {
+          const float s = expf(log_std[j]);
+          const float d = a.action[(size_t)src * A + j] - head[j];
+          const float z = d / s;
+          const float w = z / s;
+          dmu = g * w;
+          const float q = z * z - 1.0f;
+          dls = g * q;
+        }
+        if (j < head_pad) dA[j] = dmu;
+        if (j < POL_MAX_ACTION) R[j] = dls;
+      }
+      R[PPO_COL_SURR] = surr; R[PPO_COL_DLOGP] = dlogp; R[PPO_COL_CLIPPED] = clipped;
+      for (int j = PPO_COL_CLIPPED + 1; j < PPO_ROW_COLS; ++j) R[j] = 0.0f;
+    }
+  }
+  __syncthreads();   // also orders this workgroup's stores of Y ahead of the loads below
+  cur ^= 1;
+
+  // backward, from the head down: X[cur] holds dA_l
+#pragma unroll 1
+  for (int li = count - 1; li >= 0; --li) {
+    const int32_t* lr = a.layers + (size_t)(first + li) * CTRL_LAYER_WORDS;
+    const int out_pad = lr[CL_OUT_PAD];
+    float* dZ = a.scratch + a.dz_off[first + li] + (size_t)row0 * out_pad;
+    float* Xd = X[cur];
+    for (int i = tid; i < TILE * out_pad; i += 256) {
+      const int e = i / out_pad, o = i - e * out_pad;
+      const float dz = Xd[e * LDS_STRIDE + o] * dZ[i];   // dZ holds act'(x) from the forward
+      Xd[e * LDS_STRIDE + o] = dz;
+      dZ[i] = dz;
+    }
+    if (li == 0) break;
+    __syncthreads();
+    float* Xout = X[cur ^ 1];
+    mfma_layer((const f32x4*)(a.params + a.wt_off[first + li]), out_pad >> 4, lr[CL_IN_PAD] >> 4, Xd, wave, lane,
+               [&](int o, f32x4 sum) { *(f32x4*)&Xout[col * LDS_STRIDE + o] = sum; });
+    __syncthreads();
+    cur ^= 1;
+  }
+}
+
+// launch 2 (header): blockIdx.x the tile -- per layer of the table its n_ot x n_kt weight tiles, then its n_ot bias tiles; after the layers
+// the PPO_ROW_COLS / 16 column tiles of R --, blockIdx.y the row chunk; one wave
+__global__ __launch_bounds__(64) void ppo_wgrad_kernel(PpoArgs a) {
+  const int lane = threadIdx.x, col = lane & 15, quad = lane >> 4;
+  const int chunk = blockIdx.y;
+  const int r_begin = chunk * a.chunk_rows, r_end = min(r_begin + a.chunk_rows, a.b_pad);
+  float* P = a.scratch + a.p_off + (size_t)chunk * a.p_floats;
+  int t = blockIdx.x;
+  const int n_layers = a.n_actor + a.n_critic;
+  const float* M = nullptr;   // a column tile: 16 columns of M [b_pad][m_stride] from column m_col, summed to P[m_dst ..]
+  int m_stride = 0, m_col = 0, m_dst = 0;
+  bool found = false;
+  for (int gl = 0; gl < n_layers && !found; ++gl) {
+    const int32_t* lr = a.layers + (size_t)gl * CTRL_LAYER_WORDS;
+    const int in_pad = lr[CL_IN_PAD], out_pad = lr[CL_OUT_PAD], n_kt = in_pad >> 4, n_ot = out_pad >> 4;
+    const float* dZ = a.scratch + a.dz_off[gl];
+    if (t < n_ot * n_kt) {
+      const int ot = t / n_kt, kt = t - ot * n_kt;
+      const bool first = gl == 0 || gl == a.n_actor;
+      const float* Ap = a.scratch + (first ? a.a0_off : a.a_off[gl - 1]);   // the layer's input [b_pad][in_pad]
+      const float* pz = dZ + (size_t)(r_begin + quad) * out_pad + 16 * ot + col;
+      const float* pa = Ap + (size_t)(r_begin + quad) * in_pad + 16 * kt + col;
+      f32x4 acc[NP];
+#pragma unroll
+      for (int j = 0; j < NP; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      for (int r = r_begin; r < r_end; r += 16) {
+        float z[NP], x[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) { z[j] = pz[(size_t)(4 * j) * out_pad]; x[j] = pa[(size_t)(4 * j) * in_pad]; }
+#pragma unroll
+        for (int j = 0; j < NP; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(z[j], x[j], acc[j], 0, 0, 0);
+        pz += (size_t)16 * out_pad; pa += (size_t)16 * in_pad;
+      }
+      const f32x4 sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+      float* dst = P + lr[CL_W_OFF] + (size_t)(16 * ot + 4 * quad) * in_pad + 16 * kt + col;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) dst[(size_t)rr * in_pad] = sum[rr];
+      return;
+    }
+    t -= n_ot * n_kt;
+    if (t < n_ot) { M = dZ; m_stride = out_pad; m_col = 16 * t; m_dst = lr[CL_B_OFF] + 16 * t; found = true; }
+    else t -= n_ot;
+  }
+  if (!found) {
+    if (t >= PPO_ROW_COLS / 16) return;
+    M = a.scratch + a.r_off; m_stride = PPO_ROW_COLS; m_col = 16 * t; m_dst = a.log_std_off + 16 * t;
+  }
+  double s = 0.0;
+  const float* p = M + (size_t)(r_begin + quad) * m_stride + m_col + col;
+  for (int r = r_begin; r < r_end; r += 4) { s += (double)*p; p += (size_t)4 * m_stride; }
+  s += __shfl_xor(s, 16);   // (q0 + q1), (q2 + q3)
+  s += __shfl_xor(s, 32);   // (q0 + q1) + (q2 + q3): the same bits in all four quads
+  if (quad == 0) P[m_dst + col] = (float)s;
+}
+
+// launch 3 (header): thread i forms grad[i]
+__global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_reduce_kernel(PpoArgs a) {
+  __shared__ double sq[PPO_REDUCE_BLOCK];
+  const int tid = threadIdx.x, i = blockIdx.x * PPO_REDUCE_BLOCK + tid;
+  double g2 = 0.0;
+  if (i < a.n_head) {
+    const int n_layers = a.n_actor + a.n_critic;
+    int pos = 0, src = -1;
+    for (int gl = 0; gl < n_layers; ++gl) {
+      const int32_t* lr = a.layers + (size_t)gl * CTRL_LAYER_WORDS;
+      const int in = lr[CL_IN], out = lr[CL_OUT], n_w = in * out;
+      if (i < pos + n_w) { const int o = (i - pos) / in, k = (i - pos) - o * in; src = lr[CL_W_OFF] + o * lr[CL_IN_PAD] + k; break; }
+      if (i < pos + n_w + out) { src = lr[CL_B_OFF] + (i - pos - n_w); break; }
+      pos += n_w + out;
+    }
+    const bool is_log_std = src < 0;
+    if (is_log_std) src = a.log_std_off + (i - pos);
+    const float* P = a.scratch + a.p_off + src;
+    float g = P[0];
+    for (int c = 1; c < a.n_chunks; ++c) g += P[(size_t)c * a.p_floats];
+    if (is_log_std) g = g - a.entropy_coef;   // dH / dlog_std_j = 1
+    a.grad[i] = g;
+    g2 = (double)g * (double)g;
+  }
+  sq[tid] = g2;
+  __syncthreads();
+  for (int s = PPO_REDUCE_BLOCK / 2; s > 0; s >>= 1) {
+    if (tid < s) sq[tid] += sq[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) a.sq_part[blockIdx.x] = sq[0];
+}
+
+// launch 4 (header): one workgroup
+__global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_stats_kernel(PpoArgs a) {
+  __shared__ double sq[PPO_REDUCE_BLOCK];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int b = tid; b < a.n_reduce_blocks; b += PPO_REDUCE_BLOCK) s += a.sq_part[b];
+  sq[tid] = s;
+  __syncthreads();
+  for (int h = PPO_REDUCE_BLOCK / 2; h > 0; h >>= 1) {
+    if (tid < h) sq[tid] += sq[tid + h];
+    __syncthreads();
+  }
+  if (tid != 0 || !a.stats) return;
+  float sum[4];   // the columns 32 .. 35 of R over all rows: the chunks' sums in chunk order
+  for (int k = 0; k < 4; ++k) {
+    const float* P = a.scratch + a.p_off + a.log_std_off + PPO_COL_SURR + k;
+    float v = P[0];
+    for (int c = 1; c < a.n_chunks; ++c) v += P[(size_t)c * a.p_floats];
+    sum[k] = v;
+  }
+  const float* log_std = a.params + a.log_std_off;
+  double h = 0.0;   // the entropy: summed in f64, j ascending, rounded once
+  for (int j = 0; j < a.act_dim; ++j) h += ((double)log_std[j] + 0.5) + 0.91893853320467274178;
+  a.stats[0] = sum[0] * a.inv_b;
+  a.stats[1] = sum[1] * a.inv_b;
+  a.stats[2] = (float)h;
+  a.stats[3] = sum[2] * a.inv_b;
+  a.stats[4] = sum[3] / (float)a.n_rows;   // a count over B, correctly rounded
+  a.stats[5] = (float)sq[0];
+  a.stats[6] = 0.0f;
+  a.stats[7] = 0.0f;
+}
+
+void launch_ppo(hipStream_t s, const PpoArgs& a) {
+  hipLaunchKernelGGL(ppo_rows_kernel, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(a.n_tiles, a.n_chunks), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(ppo_reduce_kernel, dim3(a.n_reduce_blocks), dim3(PPO_REDUCE_BLOCK), 0, s, a);
+  hipLaunchKernelGGL(ppo_stats_kernel, dim3(1), dim3(PPO_REDUCE_BLOCK), 0, s, a);
+}
+
+}  // namespace mocca_ppo

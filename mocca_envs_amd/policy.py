@@ -128,6 +128,24 @@ class DevicePolicy:
             parts += [self.obs_mean, self.inv_std]
         return np.concatenate(parts).astype(np.float32)
 
+    def n_head(self):
+        """floats of flat_params() ahead of the statistics tail: the layers and log_std -- the length of ppo_grad's gradient"""
+        return sum(w.size + b.size for net in (self.actor, self.critic) for w, b, _ in net) + self.act_dim
+
+    def split_grad(self, flat):
+        """views into a flat array or tensor of n_head() entries in flat_params()' order (ppo_grad's gradient, or the parameters themselves)
+        -> {"actor": [(W[out][in], b[out])], "critic": [...], "log_std": [act_dim]}"""
+        if flat.ndim != 1 or flat.shape[0] < self.n_head():
+            raise ValueError(f"expected a flat array of at least {self.n_head()} entries")
+        out, pos = {}, 0
+        for name, net in (("actor", self.actor), ("critic", self.critic)):
+            out[name] = []
+            for w, b, _ in net:
+                out[name].append((flat[pos:pos + w.size].reshape(w.shape), flat[pos + w.size:pos + w.size + b.size]))
+                pos += w.size + b.size
+        out["log_std"] = flat[pos:pos + self.act_dim]
+        return out
+
     # ---- the image the policy kernel reads (csrc/mocca_policy.h); the library's repack kernel builds the same one from flat_params() ----
     def pack(self):
         """-> (image float32 [n], table int32 [layers][8] with the weight / bias offsets, offsets dict): per layer the controller's fragment

@@ -141,6 +141,40 @@ def rows_2d(rows, dim: int):
     return n_rows, stride
 
 
+MAX_MINIBATCH = 1 << 22   # include/mocca.h mocca_ppo_grad
+
+
+def ppo_args(policy, device, obs, action, old_logp, adv, returns, idx, old_value, clip, value_coef, entropy_coef, value_clip, grad, stats):
+    """check the tensors and numbers of ppo_grad -> (R rollout rows, obs row stride, B minibatch rows); ValueError otherwise"""
+    import torch
+    if not isinstance(obs, torch.Tensor) or obs.device != device:
+        raise ValueError("obs must be a float32 tensor on the env's device")
+    n_rows, stride = rows_2d(obs, policy.in_dim)
+    a = policy.act_dim
+    if not isinstance(action, torch.Tensor) or action.dtype != torch.float32 or action.device != device or not action.is_contiguous() \
+            or action.dim() < 1 or action.shape[-1] != a or action.numel() != n_rows * a:
+        raise ValueError(f"action must be a contiguous float32 [..., {a}] tensor of {n_rows} rows on the env's device")
+    for name, t in (("old_logp", old_logp), ("adv", adv), ("returns", returns), ("old_value", old_value)):
+        if t is None and name == "old_value" and not value_clip:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device or not t.is_contiguous() or t.numel() != n_rows:
+            raise ValueError(f"{name} must be a contiguous float32 tensor of {n_rows} elements (one per row of obs) on the env's device")
+    if idx is None:
+        n_batch = n_rows
+    else:
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.device != device or idx.dim() != 1 or not idx.is_contiguous():
+            raise ValueError("idx must be a contiguous int64 [B] tensor on the env's device (a chunk of torch.randperm)")
+        n_batch = int(idx.numel())
+    if not 1 <= n_batch <= MAX_MINIBATCH:
+        raise ValueError(f"the minibatch must have 1 .. {MAX_MINIBATCH} rows")
+    for name, x in (("clip", clip), ("value_coef", value_coef), ("entropy_coef", entropy_coef)):
+        if not (np.isfinite(float(x)) and float(x) >= 0.0):
+            raise ValueError(f"{name} must be finite and not negative")
+    stats_out("grad", grad, policy.n_head(), device)
+    stats_out("stats", stats, 8, device)
+    return n_rows, stride, n_batch
+
+
 def stats_out(name, t, dim, device):
     import torch
     if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device or t.numel() != dim or not t.is_contiguous()):

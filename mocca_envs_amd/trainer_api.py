@@ -369,6 +369,12 @@ class TorchVecEnv:
             raise NotImplementedError("update_obs_stats needs one handle (sub_batches=1)")
         self.venv.update_obs_stats(stats, rows, mean_out=mean_out, inv_std_out=inv_std_out)
 
+    def ppo_grad(self, obs, action, old_logp, adv, returns, *args, **kw) -> dict:
+        """PPO's minibatch loss and its gradient over the rollout storage, four launches: `VecEnv.ppo_grad`.  One handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("ppo_grad needs one handle (sub_batches=1)")
+        return self.venv.ppo_grad(obs, action, old_logp, adv, returns, *args, **kw)
+
     def _act_launch(self, into):
         """the launcher _step_obs() calls: act_step with the policy's outputs going to `into`'s "action" / "logp" / "value" (this object's
         own buffers where a key is missing); sets `self.last_act` to the three tensors written"""

@@ -443,6 +443,34 @@ class VecEnv:
                                             ptr(inv_std_out), self._stream()), self.h)
         self._out()
 
+    # ---- a PPO minibatch step on the device (include/mocca.h mocca_ppo_grad) ----
+    def ppo_grad(self, obs: torch.Tensor, action: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor, returns: torch.Tensor,
+                 idx: Optional[torch.Tensor] = None, old_value: Optional[torch.Tensor] = None, clip: float = 0.2, value_coef: float = 0.5,
+                 entropy_coef: float = 0.0, value_clip: bool = False, grad: Optional[torch.Tensor] = None,
+                 stats: Optional[torch.Tensor] = None) -> dict:
+        """The body of `ppo.update`'s minibatch loop up to `optimizer.step()` -- `evaluate_actions`, the clipped surrogate, the value loss,
+        `loss.backward()` -- as four launches: -> {"grad" [policy.n_head()] in `DevicePolicy.flat_params()`'s order (`split_grad` gives
+        per-layer views), "stats" [8]: mean surrogate, value loss, entropy, mean(old_logp - logp), clip fraction, sum of grad^2, 0, 0}.
+        `obs` [R, >= in_dim] or [T, N, >= in_dim] RAW rows with a contiguous last dimension and one stride between rows (`rollouts.obs[:-1]`);
+        `action` [.., act_dim], `old_logp`, `adv`, `returns`, `old_value` ([..] or [.., 1]; `old_value` only for `value_clip`): contiguous
+        float32 of the same R rows.  `idx` int64 [B]: the minibatch's rows (a chunk of `torch.randperm(R)`), every entry in 0 .. R - 1 -- the
+        kernel does not check; None: all R rows.  Reads the weights `update_policy` last wrote; the plain policy only.  `grad` / `stats`:
+        caller-owned outputs, allocated where none is given.  The same inputs give the same bits on every run."""
+        if self.policy is None:
+            raise _lib.MoccaError("ppo_grad needs a policy (set_policy)")
+        _, stride, n_batch = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, idx, old_value, clip, value_coef,
+                                          entropy_coef, value_clip, grad, stats)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        grad = torch.empty(self.policy.n_head(), **f32) if grad is None else grad
+        stats = torch.empty(8, **f32) if stats is None else stats
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        self._in()
+        _lib.check(self.lib.mocca_ppo_grad(self.h, ptr(obs), stride, ptr(action), ptr(old_logp), ptr(adv), ptr(returns), ptr(old_value), ptr(idx),
+                                           n_batch, float(clip), float(value_coef), float(entropy_coef), int(bool(value_clip)), ptr(grad),
+                                           ptr(stats), self._stream()), self.h)
+        self._out()
+        return {"grad": grad, "stats": stats}
+
     # ---- the reference's env-level setters, batched (env_base.py:103-118, env_locomotion.py:76-77,224-282) ----
     def set_env_params(self, params_dict):
         """`set_env_params({"curriculum": k})`: one value for all envs or one per env (takes effect at each env's next reset; the

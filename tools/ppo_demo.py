@@ -8,7 +8,7 @@ reward / masks / bad_masks straight into the rollout storage (`step(action, into
 No symmetry loss, no curriculum: this is a sanity run, not SymmetricRL.
 
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
-                           [--device-policy [--device-returns]]
+                           [--device-policy [--device-returns [--device-grad]]]
 --device-policy: collection runs through `envs.act_step(obs[t], into=...)` -- the policy kernel (normalisation, both nets, the sample, its
 log-probability, the value) and the step kernel, two launches per step and no torch op; `envs.update_policy(flat)` once per iteration hands the
 kernel the optimiser's new weights and the running observation statistics.  The noise then comes from the kernel, not from torch.randn.
@@ -17,6 +17,11 @@ kernel the optimiser's new weights and the running observation statistics.  The 
 the Python loop over t), and the running observation statistics from `envs.update_obs_stats`, which sees EVERY observation of the rollout
 (rows 1 .. T) and writes mean and 1 / sqrt(var + eps) straight into the tail of the flat parameter tensor; that tensor is allocated once and
 only its head is refreshed from the optimiser's parameters.
+--device-grad (with --device-returns): learning runs on the device as well.  The parameters live in ONE flat tensor in
+`DevicePolicy.flat_params()`'s order (the nn.Linear weights are views into it); each minibatch is one `envs.ppo_grad` on the raw rollout
+storage and the `perm` chunk -- evaluate_actions, the clipped surrogate, the value loss and backward() in four launches --, the global-norm
+clip scales the gradient by its own `stats[5]`, torch.optim.Adam steps the flat parameter and `envs.update_policy(flat)` follows every step.
+--verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor.
 writes <out>.jsonl (one line per logged iteration: env-steps so far, mean episode return / length of the episodes that ended since the last line,
 wall-clock env-steps/s of the whole loop incl. learning) and <out>_policy.npz (weights + observation statistics: `bench.py`'s workload
 bracket loads profiles/ppo_policy_walker3d.npz as its `ppo_policy` workload)."""
@@ -50,7 +55,13 @@ def main():
     ap.add_argument("--device-policy", action="store_true", help="collect with the policy on the device (act_step)")
     ap.add_argument("--device-returns", action="store_true", help="GAE, advantage normalisation and observation statistics on the device (finish_rollout, update_obs_stats)")
     ap.add_argument("--verify-returns", action="store_true", help="with --device-returns: also run the torch GAE loop on the same storage and insist on the same bits")
+    ap.add_argument("--device-grad", action="store_true", help="with --device-returns: each minibatch's loss and gradient on the device (ppo_grad); the parameters live in one flat tensor")
+    ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args()
+    if args.device_grad and not args.device_returns:
+        ap.error("--device-grad requires --device-returns")
+    if args.verify_grad and not args.device_grad:
+        ap.error("--verify-grad requires --device-grad")
     if args.device_returns and not args.device_policy:
         ap.error("--device-returns requires --device-policy")
     if args.verify_returns and not args.device_returns:
@@ -103,6 +114,18 @@ def main():
         norm = lambda o: ((o - mean) * inv_std).clamp(-10.0, 10.0)       # the policy kernel's formula
         adv_buf, ret_buf = torch.zeros(T, N, 1, device=dev), torch.zeros(T, N, 1, device=dev)
 
+    if args.device_grad:
+        # the parameters live in ONE flat tensor, flat[:n_head]; the modules' weights are views into it (for saving and --verify-grad)
+        with torch.no_grad():
+            torch.cat([q.reshape(-1) for q in head], out=flat[:n_head])
+        pos = 0
+        for q in head:
+            q.data = flat[pos:pos + q.numel()].view_as(q)
+            pos += q.numel()
+        w_flat = flat[:n_head].requires_grad_()
+        opt = torch.optim.Adam([w_flat], lr=args.lr, eps=1e-5)
+        g_buf, s_buf = torch.zeros(n_head, device=dev), torch.zeros(8, device=dev)
+
     S["obs"][0].copy_(envs.reset())
     envs.episode_totals.zero_()
     log = open(args.out + ".jsonl", "w")
@@ -113,7 +136,8 @@ def main():
             with torch.no_grad():
                 # the statistics see every observation collected so far: the reset row first, then rows 1 .. T of the previous rollout
                 envs.update_obs_stats(stats, S["obs"][1:] if it else S["obs"][:1], mean_out=mean, inv_std_out=inv_std)
-                torch.cat([q.reshape(-1) for q in head], out=flat[:n_head])
+                if not args.device_grad:
+                    torch.cat([q.reshape(-1) for q in head], out=flat[:n_head])
                 envs.update_policy(flat)
                 for t in range(T):
                     envs.act_step(S["obs"][t], into=row_act(t))
@@ -172,7 +196,31 @@ def main():
         adv_all, ret_all = adv.reshape(B, 1), ret.reshape(B, 1)
         for ep in range(args.epochs):
             perm = torch.randperm(B, device=dev)
-            for mb in perm.chunk(args.minibatches):
+            for k, mb in enumerate(perm.chunk(args.minibatches)):
+                if args.device_grad:
+                    # evaluate_actions, the clipped surrogate, the value loss and backward() as one call on the raw storage
+                    envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf)
+                    if args.verify_grad and ep == 0 and k == 0:
+                        mu = pi(o_all[mb])
+                        ratio = (logprob(mu, a_all[mb]) - lp_all[mb]).exp()
+                        surr = torch.min(ratio * adv_all[mb], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_all[mb]).mean()
+                        v_loss = 0.5 * (vf(o_all[mb]) - ret_all[mb]).pow(2).mean()
+                        auto = torch.autograd.grad(-surr + 0.5 * v_loss, head[:-1] if args.fixed_std else head)
+                        worst, pos = 0.0, 0
+                        for g in auto:
+                            worst = max(worst, ((g_buf[pos:pos + g.numel()] - g.reshape(-1)).abs().max() / g.abs().max().clamp_min(1e-30)).item())
+                            pos += g.numel()
+                        print(json.dumps({"verify_grad": worst, "iter": it + 1}), flush=True)
+                    with torch.no_grad():
+                        sq = s_buf[5]
+                        if args.fixed_std:      # log_std is not a parameter then: its entries leave the norm and the step
+                            sq = (sq - g_buf[n_head - ad:].square().sum()).clamp(min=0.0)
+                            g_buf[n_head - ad:].zero_()
+                        g_buf.mul_((0.5 / (sq.sqrt() + 1e-6)).clamp(max=1.0))      # clip_grad_norm_(.., 0.5) from the sum of grad^2
+                    w_flat.grad = g_buf
+                    opt.step()
+                    envs.update_policy(flat)
+                    continue
                 mu = pi(o_all[mb])
                 ratio = (logprob(mu, a_all[mb]) - lp_all[mb]).exp()
                 surr = torch.min(ratio * adv_all[mb], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_all[mb]).mean()

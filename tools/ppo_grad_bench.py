@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Timing of `mocca_ppo_grad` and of what it touches, on one GPU: fills profiles/ppo_grad.json.
+
+  python tools/ppo_grad_bench.py grad   [--out profiles/ppo_grad.json]
+      B = 16384 rows gathered from 131072 of the 52 -> 256 -> 256 -> {21, 1} tanh policy: `VecEnv.ppo_grad` against the same minibatch
+      through torch eager as tools/ppo_demo.py's learn loop does it (forward, loss, zero_grad, backward); HIP events, 5 blocks of 200 warm calls.
+  python tools/ppo_grad_bench.py act --key NAME [--package-root DIR] [--out ...]
+      `update_policy` and `act` at 4096 envs, 7 blocks of 200 warm calls, stored under "act_update"[NAME].  --package-root: the tree whose
+      mocca_envs_amd (with its built library) is imported -- a checkout of the parent commit gives the A/B; run the two alternately.
+  rocprofv3 --kernel-trace -d DIR -o ppo -- python tools/ppo_grad_bench.py trace        (30 calls, nothing written)
+  python tools/ppo_grad_bench.py per-launch --kernel-db DIR/ppo_results.db [--out ...]
+      medians of the four launches' durations in that trace, stored under "per_launch_us_kernel_trace".
+Each mode merges its figures into the json; nothing else is touched."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+B, ROWS = 16384, 131072
+
+
+def merge(path, key, value):
+    doc = json.load(open(path)) if os.path.exists(path) else {}
+    doc[key] = value
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def timed(torch, fn, reps=200, blocks=5, warm=30):
+    import numpy as np
+    for _ in range(warm):
+        fn()
+    out = []
+    for _ in range(blocks):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(round(a.elapsed_time(b) * 1e3 / reps, 2))
+    return {"us_per_call_blocks": out, "us_per_call_median": round(float(np.median(out)), 2)}
+
+
+def random_net(rng, dims):
+    import numpy as np
+    return [(rng.normal(0, 1 / np.sqrt(i), (o, i)).astype(np.float32), rng.normal(0, 0.1, o).astype(np.float32),
+             "tanh" if k < len(dims) - 2 else "identity") for k, (i, o) in enumerate(zip(dims[:-1], dims[1:]))]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", choices=("grad", "act", "trace", "per-launch"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_grad.json"))
+    ap.add_argument("--key", default="this")
+    ap.add_argument("--package-root", default=ROOT)
+    ap.add_argument("--kernel-db")
+    args = ap.parse_args()
+    if args.mode == "per-launch":
+        import sqlite3
+        import statistics
+        rows = sqlite3.connect(args.kernel_db).execute("select name, duration from kernels where name like '%mocca_ppo%'").fetchall()
+        by = {}
+        for name, ns in rows:
+            by.setdefault(name.split("(")[0].split("::")[-1], []).append(ns)
+        merge(args.out, "per_launch_us_kernel_trace", {"what": "median duration of each launch in a rocprofv3 kernel trace of 30 calls at B = 16384 "
+              "(the profiler adds to every launch; the HIP-event total is the figure to compare)",
+              **{k: {"median": round(statistics.median(v) / 1e3, 2), "calls": len(v)} for k, v in sorted(by.items())}})
+        return
+    sys.path.insert(0, args.package_root)
+    import numpy as np
+    import torch
+    import torch.nn as nn
+    import mocca_envs_amd
+    from mocca_envs_amd.policy import DevicePolicy
+    from mocca_envs_amd.vec_env import VecEnv
+    rng = np.random.default_rng(0)
+    dp = DevicePolicy(random_net(rng, [52, 256, 256, 21]), random_net(rng, [52, 256, 256, 1]), np.full(21, -1.0, np.float32),
+                      obs_mean=np.zeros(52, np.float32), obs_var=np.ones(52, np.float32))
+    if args.mode == "act":
+        env = VecEnv("Walker3DCustomEnv-v0", 4096, device=0)
+        env.set_policy(dp)
+        obs = env.reset()
+        flat = torch.from_numpy(dp.flat_params()).cuda()
+        out = env.act(obs)
+        res = {"package": os.path.relpath(os.path.dirname(mocca_envs_amd.__file__), ROOT),
+               "update_policy": timed(torch, lambda: env.update_policy(flat), blocks=7), "act_4096_envs": timed(torch, lambda: env.act(obs, out=out), blocks=7)}
+        doc = json.load(open(args.out)).get("act_update", {}) if os.path.exists(args.out) else {}
+        doc[args.key] = res
+        merge(args.out, "act_update", doc)
+        print(json.dumps({args.key: res}))
+        env.close()
+        return
+    env = VecEnv("Walker3DCustomEnv-v0", 4, device=0)
+    env.set_policy(dp)
+    f = lambda *s: torch.from_numpy(rng.normal(0, 1, s).astype(np.float32)).cuda()
+    obs, act, olp, adv, ret = f(ROWS, 52) * 3, f(ROWS, 21), f(ROWS) - 20, f(ROWS), f(ROWS)
+    idx = torch.randperm(ROWS, device="cuda")[:B]
+    grad, stats = torch.empty(dp.n_head(), device="cuda"), torch.empty(8, device="cuda")
+    call = lambda: env.ppo_grad(obs, act, olp, adv, ret, idx=idx, grad=grad, stats=stats)
+    if args.mode == "trace":
+        for _ in range(30):
+            call()
+        torch.cuda.synchronize()
+        env.close()
+        return
+    res = {"what": f"B = {B} rows gathered from {ROWS}, policy 52 -> 256 -> 256 -> {{21, 1}} tanh, HIP events, 5 blocks of 200 warm calls"}
+    res["mocca_ppo_grad"] = timed(torch, call)
+
+    def mlp(o):
+        return nn.Sequential(nn.Linear(52, 256), nn.Tanh(), nn.Linear(256, 256), nn.Tanh(), nn.Linear(256, o)).cuda()
+    pi, vf = mlp(21), mlp(1)
+    log_std = nn.Parameter(torch.full((21,), -1.0, device="cuda"))
+    opt = torch.optim.Adam(list(pi.parameters()) + list(vf.parameters()) + [log_std], lr=3e-4)
+    o_all = obs.clamp(-10, 10)
+    lp_all, adv_all, ret_all = olp.reshape(-1, 1), adv.reshape(-1, 1), ret.reshape(-1, 1)
+    logprob = lambda mu, a: (-0.5 * ((a - mu) / log_std.exp()) ** 2 - log_std - 0.9189385332046727).sum(-1, keepdim=True)
+
+    def eager():
+        mu = pi(o_all[idx])
+        ratio = (logprob(mu, act[idx]) - lp_all[idx]).exp()
+        surr = torch.min(ratio * adv_all[idx], ratio.clamp(0.8, 1.2) * adv_all[idx]).mean()
+        v_loss = 0.5 * (vf(o_all[idx]) - ret_all[idx]).pow(2).mean()
+        opt.zero_grad(set_to_none=True)
+        (-surr + 0.5 * v_loss).backward()
+
+    res["torch_eager"] = timed(torch, eager)
+    res["speedup"] = round(res["torch_eager"]["us_per_call_median"] / res["mocca_ppo_grad"]["us_per_call_median"], 2)
+    merge(args.out, "minibatch", res)
+    print(json.dumps(res))
+    env.close()
+
+
+if __name__ == "__main__":
+    main()
