@@ -456,7 +456,7 @@ int mocca_obs_stats(mocca_handle h, const float *rows_dev, int64_t n_rows, int r
  *      per minibatch) ---- */
 
 /* mocca_ppo_grad    replaces the body of `ppo.update`'s minibatch loop up to `optimizer.step()`: `evaluate_actions`, the clipped surrogate,
- *                   the value loss, `loss.backward()` -- four launches, for the plain policy of mocca_set_policy.  R rollout rows, B = n_rows
+ *                   the value loss, `loss.backward()` -- four launches, for the plain policy of mocca_set_policy (the symmetric one: mocca_ppo_grad_sym below).  R rollout rows, B = n_rows
  *                   of them form the minibatch.  obs_dev [R][obs_stride] f32: the first in_dim floats of a row are read, RAW (normalised in
  *                   the kernel exactly as mocca_act does); action_dev [R][act_dim] the stored samples; old_logp_dev, adv_dev, returns_dev
  *                   [R]; old_value_dev [R], may be NULL when value_clip == 0.  idx_dev [B] i64 (a chunk of torch.randperm): minibatch row b
@@ -510,10 +510,50 @@ int mocca_obs_stats(mocca_handle h, const float *rows_dev, int64_t n_rows, int r
  * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): a NULL handle; called before mocca_set_policy / mocca_update_policy; a
  * NULL obs_dev, action_dev, old_logp_dev, adv_dev, returns_dev or grad_dev; value_clip with old_value_dev NULL; n_rows < 1 or > 2^22;
  * obs_stride < in_dim; a non-finite or negative clip, value_coef or entropy_coef; a handle with mirror tables attached
- * (mocca_set_policy_symmetry) -- the symmetric policy's backward is not implemented: detach the tables first. */
+ * (mocca_set_policy_symmetry) -- the symmetric policy's gradient is mocca_ppo_grad_sym: call that, or detach the tables first. */
 int mocca_ppo_grad(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
                    const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
                    double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
+
+/* mocca_ppo_grad_sym  mocca_ppo_grad for the mirror-symmetric policy of mocca_set_policy_symmetry (SymmetricRL's symmetric network): replaces
+ *                   the same minibatch body with `evaluate_actions` of the symmetric net -- two passes through both nets forward and back --
+ *                   in the same four launches.  The argument list, the arrays, idx_dev (NOT range-checked), grad_dev's order and stats_dev
+ *                   are mocca_ppo_grad's.  It differentiates mocca_act's symmetric policy: with x1 = n(s) and x2 = n(M_o s) -- the mirror
+ *                   (M x)[k] = sign[k] * x[perm[k]] taken on the RAW row, the statistics indexed by k --,
+ *                       f1 = actor(x1)   f2 = actor(x2)   v1 = critic(x1)   v2 = critic(x2)
+ *                   and per row, each line ONE IEEE f32 operation in this order, never contracted into an FMA, pj = act_perm[j]:
+ *                       for j ascending:   mm = f2[pj] * act_sign[j];  mu[j] = f1[j] + mm;  mu[j] = 0.5f * mu[j]
+ *                                          ls[j] = log_std[j] + log_std[pj];  ls[j] = 0.5f * ls[j]
+ *                       v = v1 + v2;  v = 0.5f * v
+ *                   mocca_ppo_grad's per-row lines follow UNCHANGED on mu, ls and v: logp summed in f64, r, the surrogate, g,
+ *                   dL/dmu[j] = g * w, the row's log_std term g * q, the value loss with its clamp tie rule, dL/dv.  The heads receive
+ *                       for j:             h = 0.5f * dL/dmu[j];  dL/df1[j] = h;  dL/df2[pj] = h * act_sign[j]
+ *                                          (each pj is written once: act_perm is a bijection)
+ *                       dL/dv1 = dL/dv2 = 0.5f * dL/dv
+ *                   and both passes run mocca_ppo_grad's backward; every weight's and bias's gradient is the sum over BOTH passes (the
+ *                   matrix cores add them in one fixed order, as-given and mirrored columns interleaved eight by eight).  log_std: with T[j]
+ *                   the rows' sum of g * q_j (the row chunks added in chunk order, as in mocca_ppo_grad),
+ *                       grad[log_std j] = 0.5f * (T[j] + T[pj]) - f32(entropy_coef)
+ *                   (H = sum_j ls[j] + const has derivative 1 with respect to every log_std[j]: the perm is a bijection).  stats_dev keeps
+ *                   its meanings: the means are over the B rows, not the 2 B columns; stats[2] is the entropy of the SYMMETRISED log_std,
+ *                   sum_j (f64(ls[j]) + 1/2 + 1/2 log 2 pi) in f64 with j ascending, ls[j] the f32 value above.
+ *                   The forward is mocca_act's symmetric instance with mocca_ppo_grad's one difference (tanh rounded once).
+ *                   Scratch: the handle's, shared with mocca_ppo_grad, and TWICE its size per row -- the activations of both passes,
+ *                   16 ceil(B / 8) scratch rows: 8 (in_pad + 2 sum of the layers' out_pad + 48) B bytes, 18 KB per row for the 52 -> 256 ->
+ *                   256 -> {21, 1} policy, 300 MB at B = 16384; n_rows is 1 .. 2^21, so that the scratch's row count stays within what
+ *                   mocca_ppo_grad allows.  Growing FREES the old scratch, for the pair: a symmetric call at some B after a plain call
+ *                   at the same B grows it, and a graph captured before -- of either call -- must be recaptured; warm the handle with the
+ *                   largest call it will see (a symmetric call at B covers a plain one at 2 B) before capturing.  A captured call also
+ *                   holds the mirror tables' device arrays: mocca_set_policy_symmetry and mocca_set_policy replace them, and a graph
+ *                   captured before must be recaptured.  Otherwise mocca_ppo_grad's conditions hold as they stand: asynchronous on `stream`,
+ *                   no allocation, no host read, no synchronisation, no atomics, every sum's order a function of B and the shapes alone
+ *                   -- the same inputs give the same bits --, capturable as a linear chain after one warm call with the same B; it sees
+ *                   a mocca_update_policy made between two replays; it writes only grad_dev, stats_dev and its scratch.
+ * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): those of mocca_ppo_grad with n_rows > 2^21 in place of 2^22; and a
+ * policy WITHOUT mirror tables attached (mocca_set_policy_symmetry) -- the plain policy's gradient is mocca_ppo_grad. */
+int mocca_ppo_grad_sym(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
+                       const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
+                       double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
 
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */

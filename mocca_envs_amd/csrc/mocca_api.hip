@@ -1274,19 +1274,23 @@ int mocca_obs_stats(mocca_handle h, const float* rows_dev, int64_t n_rows, int r
   return MOCCA_OK;
 }
 
-int mocca_ppo_grad(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev, const float* adv_dev,
-                   const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev, int64_t n_rows, double clip, double value_coef,
-                   double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
+// mocca_ppo_grad (sym == false) and mocca_ppo_grad_sym (sym == true): one argument list, one scratch, the same four launches
+static int ppo_grad(mocca_handle h, const char* name, bool sym, const float* obs_dev, int obs_stride, const float* action_dev,
+                    const float* old_logp_dev, const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev,
+                    int64_t n_rows, double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev,
+                    void* stream) {
   using namespace mocca_ctrl;
   using namespace mocca_ppo;
-  if (!h) { g_err = "mocca_ppo_grad: NULL handle"; return MOCCA_E_ARG; }
-  auto bad = [&](const std::string& what) { h->err = "mocca_ppo_grad: " + what; return MOCCA_E_ARG; };
+  if (!h) { g_err = std::string(name) + ": NULL handle"; return MOCCA_E_ARG; }
+  auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
   if (!h->d_pol_image || !h->pol_filled) return bad("needs a policy (mocca_set_policy, then mocca_update_policy)");
-  if (h->pol.in_perm) return bad("the symmetric policy's backward is not implemented: detach the mirror tables (mocca_set_policy_symmetry)");
+  if (!sym && h->pol.in_perm)
+    return bad("the policy has mirror tables attached: the symmetric policy's gradient is mocca_ppo_grad_sym (or detach the tables: mocca_set_policy_symmetry)");
+  if (sym && !h->pol.in_perm) return bad("needs a policy with mirror tables attached (mocca_set_policy_symmetry); the plain policy's gradient is mocca_ppo_grad");
   if (!obs_dev || !action_dev || !old_logp_dev || !adv_dev || !returns_dev || !grad_dev)
     return bad("obs_dev, action_dev, old_logp_dev, adv_dev, returns_dev and grad_dev must not be NULL");
   if (value_clip && !old_value_dev) return bad("value_clip needs old_value_dev");
-  if (n_rows < 1 || n_rows > PPO_MAX_ROWS) return bad("n_rows must be 1 .. 2^22, not " + std::to_string(n_rows));
+  if (n_rows < 1 || n_rows > (sym ? PPO_MAX_ROWS_SYM : PPO_MAX_ROWS)) return bad(std::string("n_rows must be 1 .. ") + (sym ? "2^21" : "2^22") + ", not " + std::to_string(n_rows));
   if (obs_stride < h->pol.in_dim)
     return bad("obs_stride " + std::to_string(obs_stride) + " is smaller than the policy's in_dim (" + std::to_string(h->pol.in_dim) + ")");
   if (!std::isfinite(clip) || clip < 0.0 || !std::isfinite(value_coef) || value_coef < 0.0 || !std::isfinite(entropy_coef) || entropy_coef < 0.0)
@@ -1298,9 +1302,11 @@ int mocca_ppo_grad(mocca_handle h, const float* obs_dev, int obs_stride, const f
   a.log_std_off = p.log_std_off; a.flags_off = p.flags_off; a.mean_off = p.mean_off; a.inv_std_off = p.inv_std_off;
   a.in_dim = p.in_dim; a.in_pad = p.in_pad; a.act_dim = p.act_dim; a.norm_clip = p.clip;
   std::memcpy(a.wt_off, h->pol_wt_off, sizeof(a.wt_off));
+  if (sym) { a.in_perm = p.in_perm; a.in_sign = p.in_sign; a.act_perm = p.act_perm; a.act_sign = p.act_sign; }
   a.obs = obs_dev; a.obs_stride = obs_stride; a.action = action_dev; a.old_logp = old_logp_dev; a.adv = adv_dev; a.returns = returns_dev;
   a.old_value = old_value_dev; a.idx = idx_dev;
-  a.n_rows = (int)n_rows; a.b_pad = (int)((n_rows + 15) / 16 * 16);
+  a.n_rows = (int)n_rows;
+  a.b_pad = sym ? (int)((n_rows + PPO_SYM_TILE - 1) / PPO_SYM_TILE * 16) : (int)((n_rows + 15) / 16 * 16);   // the scratch's rows (mocca_ppo.h)
   a.clip = (float)clip; a.value_coef = (float)value_coef; a.entropy_coef = (float)entropy_coef; a.inv_b = 1.0f / (float)n_rows;
   a.value_clip = value_clip != 0;
   // the scratch (mocca_ppo.h), in floats; every piece a multiple of 4 floats, so that rows stay 16-byte aligned
@@ -1322,12 +1328,26 @@ int mocca_ppo_grad(mocca_handle h, const float* obs_dev, int obs_stride, const f
   a.p_off = pos; pos += (long long)a.n_chunks * a.p_floats;
   a.n_tiles = n_tiles; a.n_head = n_head; a.n_reduce_blocks = (n_head + PPO_REDUCE_BLOCK - 1) / PPO_REDUCE_BLOCK;
   const size_t f_doubles = (size_t)(pos + 1) / 2;
-  if (int rc = grow_scratch(h, "mocca_ppo_grad", h->d_ppo, &h->ppo_cap, f_doubles + (size_t)a.n_reduce_blocks)) return rc;
+  if (int rc = grow_scratch(h, name, h->d_ppo, &h->ppo_cap, f_doubles + (size_t)a.n_reduce_blocks)) return rc;
   a.scratch = (float*)h->d_ppo.get(); a.sq_part = h->d_ppo.get() + f_doubles;
   a.grad = grad_dev; a.stats = stats_dev;
   launch_ppo((hipStream_t)stream, a);
   HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
+}
+
+int mocca_ppo_grad(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev, const float* adv_dev,
+                   const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev, int64_t n_rows, double clip, double value_coef,
+                   double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
+  return ppo_grad(h, "mocca_ppo_grad", false, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, idx_dev, n_rows, clip,
+                  value_coef, entropy_coef, value_clip, grad_dev, stats_dev, stream);
+}
+
+int mocca_ppo_grad_sym(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev,
+                       const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev, int64_t n_rows, double clip,
+                       double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
+  return ppo_grad(h, "mocca_ppo_grad_sym", true, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, idx_dev, n_rows,
+                  clip, value_coef, entropy_coef, value_clip, grad_dev, stats_dev, stream);
 }
 
 #ifdef MOCCA_STAMPS

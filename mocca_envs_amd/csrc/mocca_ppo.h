@@ -1,13 +1,13 @@
 // mocca_ppo.h -- the body of a PPO minibatch step up to optimizer.step() as kernels (mocca_ppo.hip): evaluate_actions, the clipped
-// surrogate, the value loss and loss.backward() for the plain Gaussian actor-critic of mocca_policy.h.  mocca_ppo_grad (mocca_api.hip) checks
-// the caller's arguments, owns the scratch and launches them.  The loss and the per-row formulas: include/mocca.h.
+// surrogate, the value loss and loss.backward() for the Gaussian actor-critic of mocca_policy.h, plain or mirror-symmetric.  mocca_ppo_grad /
+// mocca_ppo_grad_sym (mocca_api.hip) check the caller's arguments, own the scratch and launch them.  The loss and the per-row formulas: include/mocca.h.
 //
 // Image.  The kernels read the policy image of mocca_policy.h and, behind it, a SECOND copy of every layer's weights but a net's first,
 // transposed: layer l's W[out][in] as the [in_pad / 16][out_pad / 16][64][4] fragment order of W^T (in and out swap roles and padding), so
 // that dA_{l-1} = W^T dZ_l runs through the forward's MFMA loop.  The repack kernel writes both copies in its one launch (RepackRow.transposed);
 // PpoArgs.wt_off[layer] is the float offset of a layer's transposed copy, -1 for a first layer.
 //
-// Scratch (f32, owned by the handle), B_pad = B rounded up to 16, layer = row of the layer table:
+// Scratch (f32, owned by the handle), B_pad = B rounded up to 16 (the symmetric call: below), layer = row of the layer table:
 //   A0      [B_pad][in_pad]               the normalised input (written by the actor's workgroups)
 //   A[l]    [B_pad][out_pad_l]            layer l's output activation y
 //   dZ[l]   [B_pad][out_pad_l]            dL/d(pre-activation) of layer l; between the forward and the backward: act'(x) of layer l
@@ -34,6 +34,17 @@
 // order in f32, scales nothing (the 1 / B is in dL/dhead), adds -entropy_coef to log_std's; a workgroup adds its squares in f64 in a fixed tree.
 // Launch 4 (ppo_stats_kernel): ONE workgroup adds the workgroups' squares in index order in f64 and writes stats[0..7].
 // No atomics; every sum's order is a function of B and the shapes alone: the same inputs give the same bits.
+//
+// Symmetric policy (mocca_ppo_grad_sym; mocca_policy.h: Symmetry).  The same four launches on TWICE the columns: ppo_rows_kernel<true>
+// gives its 16 MFMA columns to PPO_SYM_TILE = 8 minibatch rows x {as given, mirrored}, policy_kernel<true>'s layout -- column c is row
+// row0 + c, column 8 + c its mirror image, staged as obs[src * stride + in_perm[k]] * in_sign[k] ahead of the same normalisation --, the grid
+// is ceil(B / 8) x {actor, critic}, and column e of workgroup t owns SCRATCH ROW 16 t + e of A0, A[l], dZ[l] and R: B_pad = 16 ceil(B / 8), twice
+// the plain call's rows.  The layer loop and the backward loop are the plain instance's (LDS is unchanged).  Head stage: lane c < 8 reads
+// the heads of columns c and 8 + c, forms the symmetrised mean, log_std and value, runs the plain per-row lines on them and hands
+// each head its half (include/mocca.h); R's terms go to the as-given column's row, the mirrored column's R row and every row of a column
+// without a minibatch row are zeros.  Launch 2 is unchanged: summing dZ^T A over the scratch rows adds both passes' weight gradients, in
+// scratch-row order.  Launch 3 forms log_std's entries as 0.5f * (T[j] + T[act_perm[j]]) from the chunk sums T; launch 4 takes the entropy
+// of the symmetrised log_std.  Both read PpoArgs.act_perm; null selects the plain arithmetic.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -49,6 +60,8 @@ constexpr int PPO_CHUNK_MIN_ROWS = 512;  // a chunk holds at least this many row
 constexpr int PPO_REDUCE_BLOCK = 256;
 constexpr int PPO_MAX_TABLE = 2 * mocca_pol::POL_MAX_LAYERS;
 constexpr long long PPO_MAX_ROWS = 1ll << 22;
+constexpr int PPO_SYM_TILE = mocca_pol::POL_SYM_TILE;   // minibatch rows per workgroup of the symmetric instance: each takes two of the 16 MFMA columns
+constexpr long long PPO_MAX_ROWS_SYM = PPO_MAX_ROWS / 2;   // the same bound on the scratch's rows
 
 struct PpoArgs {
   // the policy: image, layer table, shapes (PolicyArgs of the handle)
@@ -59,11 +72,14 @@ struct PpoArgs {
   int in_dim, in_pad, act_dim;
   float norm_clip;
   int wt_off[PPO_MAX_TABLE];             // transposed copies (header: Image)
+  // the mirror tables (mocca_policy.h: Symmetry), device; in_perm null: the plain policy
+  const int32_t *in_perm, *act_perm;     // [in_dim], [act_dim]
+  const float *in_sign, *act_sign;
   // the minibatch
   const float* obs; int obs_stride;
   const float *action, *old_logp, *adv, *returns, *old_value;
   const int64_t* idx;                    // [B] or null: rows 0 .. B - 1
-  int n_rows, b_pad;                     // B, B rounded up to 16
+  int n_rows, b_pad;                     // B; the scratch's rows: B rounded up to 16, symmetric: 16 ceil(B / 8)
   float clip, value_coef, entropy_coef, inv_b;
   int value_clip;
   // scratch (header: Scratch); float offsets of A[l] / dZ[l] from `scratch`

@@ -1,6 +1,6 @@
-// mocca_ppo.hip -- PPO's minibatch loss and its gradient with respect to every parameter of the plain Gaussian actor-critic, on the device
-// (mocca_ppo_grad).  What each launch does, the scratch and the transposed weight copy: mocca_ppo.h.  The loss and the per-row formulas:
-// include/mocca.h.
+// mocca_ppo.hip -- PPO's minibatch loss and its gradient with respect to every parameter of the Gaussian actor-critic, plain (mocca_ppo_grad)
+// or mirror-symmetric (mocca_ppo_grad_sym), on the device.  What each launch does, the scratch and the transposed weight copy: mocca_ppo.h.
+// The loss and the per-row formulas: include/mocca.h.
 //
 // Arithmetic: the policy kernel's (mocca_policy.hip).  The layer loop below is that kernel's loop, copied -- mocca_policy.hip's kernel is left
 // as it is -- with the epilogue as a parameter: the forward adds the bias, activates and also stores the output to scratch; the backward
@@ -22,6 +22,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int LDS_STRIDE = POL_MAX_IN + 4;   // the policy kernel's LDS row
 constexpr int NP = 4, NT = 4, TILE = POL_TILE;
 static_assert(TILE == 16, "one 16-row MFMA sub-tile per workgroup");
+static_assert(2 * PPO_SYM_TILE == TILE, "the symmetric instance: column c the row as given, column PPO_SYM_TILE + c its mirror image");
 
 __device__ __forceinline__ float activate(float x, int act) {
   switch (act) {
@@ -89,34 +90,41 @@ __device__ __forceinline__ void mfma_layer(const f32x4* W, int nkg, int n_ot, co
     if (t < nt_w) epi((wave + 4 * t) * 16 + quad * 4, (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]));
 }
 
+// SYM (header: Symmetry): the 16 MFMA columns are PPO_SYM_TILE = 8 minibatch rows x {as given, mirrored} -- policy_kernel<true>'s layout:
+// column c is row row0 + c, column 8 + c its mirror image -- and column e's activations live in scratch row 16 * tile + e.  The plain
+// instance has one column per row and scratch row = minibatch row.
+template <bool SYM>
 __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
   __shared__ __attribute__((aligned(16))) float X[2][TILE * LDS_STRIDE];
+  constexpr int ROWS = SYM ? PPO_SYM_TILE : TILE;   // minibatch rows of a workgroup
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int row0 = blockIdx.x * TILE, net = blockIdx.y;
+  const int row0 = blockIdx.x * ROWS, srow0 = blockIdx.x * TILE, net = blockIdx.y;
   const int col = lane & 15;
   const int B = a.n_rows;
 
-  // input: the policy kernel's staging, the rows gathered through idx; the normalised tile also goes to A0
+  // input: the policy kernel's staging, the rows gathered through idx; the normalised tile also goes to A0.  SYM: column e >= ROWS is the
+  // mirror image of row e - ROWS, formed from the RAW row through in_perm / in_sign and normalised by k
   {
     const bool norm = a.params[a.flags_off] != 0.0f;
     const float *mu = a.params + a.mean_off, *is = a.params + a.inv_std_off;
     float* A0 = a.scratch + a.a0_off;
     for (int i = tid; i < TILE * a.in_pad; i += 256) {
-      const int e = i / a.in_pad, k = i - e * a.in_pad, row = row0 + e;
+      const int e = i / a.in_pad, k = i - e * a.in_pad, row = row0 + (SYM ? e & (ROWS - 1) : e);
       float v = 0.0f;
       if (row < B && k < a.in_dim) {
         const long long src = a.idx ? (long long)a.idx[row] : row;
-        v = a.obs[(size_t)src * a.obs_stride + k];
+        if (SYM && e >= ROWS) v = a.obs[(size_t)src * a.obs_stride + a.in_perm[k]] * a.in_sign[k];
+        else v = a.obs[(size_t)src * a.obs_stride + k];
         if (norm) v = fminf(fmaxf((v - mu[k]) * is[k], -a.norm_clip), a.norm_clip);
       }
       X[0][e * LDS_STRIDE + k] = v;
-      if (net == 0) A0[(size_t)row * a.in_pad + k] = v;
+      if (net == 0) A0[(size_t)(srow0 + e) * a.in_pad + k] = v;
     }
   }
   __syncthreads();
 
   const int first = net == 0 ? 0 : a.n_actor, count = net == 0 ? a.n_actor : a.n_critic;
-  const bool live = row0 + col < B;   // this lane's MFMA column is a row of the minibatch
+  const bool live = row0 + (SYM ? col & (ROWS - 1) : col) < B;   // this lane's MFMA column is a row of the minibatch (SYM: or its mirror image)
   int cur = 0;
 #pragma unroll 1
   for (int li = 0; li < count; ++li) {
@@ -124,8 +132,8 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
     const int out_pad = lr[CL_OUT_PAD], act = lr[CL_ACT];
     const float* Bias = a.params + lr[CL_B_OFF];
     float* Xout = X[cur ^ 1];
-    float* Y = a.scratch + a.a_off[first + li] + (size_t)(row0 + col) * out_pad;
-    float* S = a.scratch + a.dz_off[first + li] + (size_t)(row0 + col) * out_pad;
+    float* Y = a.scratch + a.a_off[first + li] + (size_t)(srow0 + col) * out_pad;
+    float* S = a.scratch + a.dz_off[first + li] + (size_t)(srow0 + col) * out_pad;
     mfma_layer((const f32x4*)(a.params + lr[CL_W_OFF]), lr[CL_IN_PAD] >> 4, out_pad >> 4, X[cur], wave, lane, [&](int o, f32x4 sum) {
       const f32x4 bias = *(const f32x4*)(Bias + o);
       f32x4 y, slope;
@@ -143,86 +151,118 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
     cur ^= 1;
   }
 
-  // head stage: one lane per row -> the row's loss terms (R) and dL/dhead, the backward's first dA, in the other LDS buffer
+  // head stage: one lane per row -> the row's loss terms (R) and dL/dhead, the backward's first dA, in the other LDS buffer.  SYM: the
+  // row's lane reads the heads of its two columns and writes dA for both; R's terms go to the as-given column's scratch row, the lane of
+  // the mirrored column zeroes that column's R row
   if (tid < TILE) {
-    const int row = row0 + tid;
-    const float* head = &X[cur][tid * LDS_STRIDE];
-    float* dA = &X[cur ^ 1][tid * LDS_STRIDE];
-    float* R = a.scratch + a.r_off + (size_t)row * PPO_ROW_COLS;
+    const int row = row0 + (SYM ? tid & (ROWS - 1) : tid);
+    float* R = a.scratch + a.r_off + (size_t)(srow0 + tid) * PPO_ROW_COLS;
     const int head_pad = (a.layers + (size_t)(first + count - 1) * CTRL_LAYER_WORDS)[CL_OUT_PAD];
-    const long long src = row < B ? (a.idx ? (long long)a.idx[row] : row) : 0;
-    if (net == 1) {
-      float dv = 0.0f, vloss = 0.0f;
-      if (row < B) {   // include/mocca.h: one f32 operation per line of it, in that order
-        const float v = head[0], ret = a.returns[src];
-        const float e = v - ret;
-        float l = e * e;
-        dv = e;
-        if (a.value_clip) {
-          const float vo = a.old_value[src];
-          const float dl = v - vo;
-          const float dc = fminf(fmaxf(dl, -a.clip), a.clip);
-          const float vc = vo + dc;
-          const float e2 = vc - ret;
-          const float l2 = e2 * e2;
-          // where the clamp passes, vc is v and both terms are the same function of v: a tie, the unclipped term is used
-          if ((dl < -a.clip || dl > a.clip) && l2 > l) {
-            l = l2;
-            dv = 0.0f;
+    if (SYM && tid >= ROWS) {
+      for (int j = 0; j < PPO_ROW_COLS; ++j)
+        if ((j == PPO_COL_VLOSS) == (net == 1)) R[j] = 0.0f;
+    } else {
+      const int mcol = SYM ? ROWS + tid : tid;   // SYM: the row's mirrored column
+      const float *head = &X[cur][tid * LDS_STRIDE], *mirror = &X[cur][mcol * LDS_STRIDE];
+      float *dA = &X[cur ^ 1][tid * LDS_STRIDE], *dAm = &X[cur ^ 1][mcol * LDS_STRIDE];
+      const long long src = row < B ? (a.idx ? (long long)a.idx[row] : row) : 0;
+      if (net == 1) {
+        float dv = 0.0f, vloss = 0.0f;
+        if (row < B) {   // include/mocca.h: one f32 operation per line of it, in that order
+          const float v = SYM ? 0.5f * (head[0] + mirror[0]) : head[0], ret = a.returns[src];
+          const float e = v - ret;
+          float l = e * e;
+          dv = e;
+          if (a.value_clip) {
+            const float vo = a.old_value[src];
+            const float dl = v - vo;
+            const float dc = fminf(fmaxf(dl, -a.clip), a.clip);
+            const float vc = vo + dc;
+            const float e2 = vc - ret;
+            const float l2 = e2 * e2;
+            // where the clamp passes, vc is v and both terms are the same function of v: a tie, the unclipped term is used
+            if ((dl < -a.clip || dl > a.clip) && l2 > l) {
+              l = l2;
+              dv = 0.0f;
+            }
+          }
+          vloss = 0.5f * l;
+          dv = a.value_coef * dv;
+          dv = dv * a.inv_b;
+          if (SYM) dv = 0.5f * dv;   // dL/dv1 = dL/dv2
+        }
+        R[PPO_COL_VLOSS] = vloss;
+        for (int j = 0; j < head_pad; ++j) {
+          dA[j] = j == 0 ? dv : 0.0f;
+          if (SYM) dAm[j] = j == 0 ? dv : 0.0f;
+        }
+      } else {
+        const float* log_std = a.params + a.log_std_off;
+        const int A = a.act_dim;
+        // the Gaussian of action j: its mean (returned) and log_std.  SYM: the symmetrised ones of mocca_policy.h, one f32 operation each
+        auto gaussian = [&](int j, float* ls) {
+          if (SYM) {
+            const int pj = a.act_perm[j];
+            const float mm = mirror[pj] * a.act_sign[j];
+            *ls = 0.5f * (log_std[j] + log_std[pj]);
+            return 0.5f * (head[j] + mm);
+          }
+          *ls = log_std[j];
+          return head[j];
+        };
+        float g = 0.0f, surr = 0.0f, dlogp = 0.0f, clipped = 0.0f;
+        if (row < B) {
+          double lp64 = 0.0;   // the terms are f32, their sum is f64: 21 terms of size ~1 in f32 would leave ~1e-6 in the ratio
+          for (int j = 0; j < A; ++j) {
+            float ls;
+            const float mu = gaussian(j, &ls);
+            const float s = expf(ls);
+            const float d = a.action[(size_t)src * A + j] - mu;
+            const float z = d / s;
+            lp64 += (double)((-0.5f * z) * z - ls - 0.91893853320467274178f);
+          }
+          const float olp = a.old_logp[src], adv = a.adv[src];
+          const float dl = (float)(lp64 - (double)olp);
+          const float r = expf(dl);
+          const float lo = 1.0f - a.clip, hi = 1.0f + a.clip;
+          const float s1 = r * adv;
+          const float rc = fminf(fmaxf(r, lo), hi);
+          const float s2 = rc * adv;
+          surr = fminf(s1, s2);
+          dlogp = -dl;
+          clipped = r > hi || r < lo ? 1.0f : 0.0f;
+          const bool inactive = (adv > 0.0f && r > hi) || (adv < 0.0f && r < lo);
+          if (!inactive) {
+            g = adv * r;
+            g = g * a.inv_b;
+            g = -g;
           }
         }
-        vloss = 0.5f * l;
-        dv = a.value_coef * dv;
-        dv = dv * a.inv_b;
-      }
-      R[PPO_COL_VLOSS] = vloss;
-      for (int j = 0; j < head_pad; ++j) dA[j] = j == 0 ? dv : 0.0f;
-    } else {
-      const float* log_std = a.params + a.log_std_off;
-      const int A = a.act_dim;
-      float g = 0.0f, surr = 0.0f, dlogp = 0.0f, clipped = 0.0f;
-      if (row < B) {
-        double lp64 = 0.0;   // the terms are f32, their sum is f64: 21 terms of size ~1 in f32 would leave ~1e-6 in the ratio
-        for (int j = 0; j < A; ++j) {
-          const float ls = log_std[j];
-          const float s = expf(ls);
-          const float d = a.action[(size_t)src * A + j] - head[j];
-          const float z = d / s;
-          lp64 += (double)((-0.5f * z) * z - ls - 0.91893853320467274178f);
+        if (SYM)   // every act_perm[j] below is written once more (a bijection of 0 .. A - 1); the padding stays 0
+          for (int j = 0; j < head_pad; ++j) dAm[j] = 0.0f;
+        for (int j = 0; j < head_pad || j < POL_MAX_ACTION; ++j) {
+          float dmu = 0.0f, dls = 0.0f;
+          if (row < B && j < A) {
+            float ls;
+            const float mu = gaussian(j, &ls);
+            const float s = expf(ls);
+            const float d = a.action[(size_t)src * A + j] - mu;
+            const float z = d / s;
+            const float w = z / s;
+            dmu = g * w;
+            const float q = z * z - 1.0f;
+            dls = g * q;
+            if (SYM) {   // dL/df1[j] = h, dL/df2[pj] = h * act_sign[j]
+              dmu = 0.5f * dmu;
+              dAm[a.act_perm[j]] = dmu * a.act_sign[j];
+            }
+          }
+          if (j < head_pad) dA[j] = dmu;
+          if (j < POL_MAX_ACTION) R[j] = dls;
         }
-        const float olp = a.old_logp[src], adv = a.adv[src];
-        const float dl = (float)(lp64 - (double)olp);
-        const float r = expf(dl);
-        const float lo = 1.0f - a.clip, hi = 1.0f + a.clip;
-        const float s1 = r * adv;
-        const float rc = fminf(fmaxf(r, lo), hi);
-        const float s2 = rc * adv;
-        surr = fminf(s1, s2);
-        dlogp = -dl;
-        clipped = r > hi || r < lo ? 1.0f : 0.0f;
-        const bool inactive = (adv > 0.0f && r > hi) || (adv < 0.0f && r < lo);
-        if (!inactive) {
-          g = adv * r;
-          g = g * a.inv_b;
-          g = -g;
-        }
+        R[PPO_COL_SURR] = surr; R[PPO_COL_DLOGP] = dlogp; R[PPO_COL_CLIPPED] = clipped;
+        for (int j = PPO_COL_CLIPPED + 1; j < PPO_ROW_COLS; ++j) R[j] = 0.0f;
       }
-      for (int j = 0; j < head_pad || j < POL_MAX_ACTION; ++j) {
-        float dmu = 0.0f, dls = 0.0f;
-        if (row < B && j < A) {
-          const float s = expf(log_std[j]);
-          const float d = a.action[(size_t)src * A + j] - head[j];
-          const float z = d / s;
-          const float w = z / s;
-          dmu = g * w;
-          const float q = z * z - 1.0f;
-          dls = g * q;
-        }
-        if (j < head_pad) dA[j] = dmu;
-        if (j < POL_MAX_ACTION) R[j] = dls;
-      }
-      R[PPO_COL_SURR] = surr; R[PPO_COL_DLOGP] = dlogp; R[PPO_COL_CLIPPED] = clipped;
-      for (int j = PPO_COL_CLIPPED + 1; j < PPO_ROW_COLS; ++j) R[j] = 0.0f;
     }
   }
   __syncthreads();   // also orders this workgroup's stores of Y ahead of the loads below
@@ -233,7 +273,7 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
   for (int li = count - 1; li >= 0; --li) {
     const int32_t* lr = a.layers + (size_t)(first + li) * CTRL_LAYER_WORDS;
     const int out_pad = lr[CL_OUT_PAD];
-    float* dZ = a.scratch + a.dz_off[first + li] + (size_t)row0 * out_pad;
+    float* dZ = a.scratch + a.dz_off[first + li] + (size_t)srow0 * out_pad;
     float* Xd = X[cur];
     for (int i = tid; i < TILE * out_pad; i += 256) {
       const int e = i / out_pad, o = i - e * out_pad;
@@ -326,7 +366,13 @@ __global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_reduce_kernel(PpoArgs a)
     const float* P = a.scratch + a.p_off + src;
     float g = P[0];
     for (int c = 1; c < a.n_chunks; ++c) g += P[(size_t)c * a.p_floats];
-    if (is_log_std) g = g - a.entropy_coef;   // dH / dlog_std_j = 1
+    if (is_log_std && a.act_perm) {   // the symmetrised log_std: 0.5f * (T[j] + T[act_perm[j]])
+      const float* Pm = a.scratch + a.p_off + a.log_std_off + a.act_perm[i - pos];
+      float gm = Pm[0];
+      for (int c = 1; c < a.n_chunks; ++c) gm += Pm[(size_t)c * a.p_floats];
+      g = 0.5f * (g + gm);
+    }
+    if (is_log_std) g = g - a.entropy_coef;   // dH / dlog_std_j = 1 (act_perm is a bijection)
     a.grad[i] = g;
     g2 = (double)g * (double)g;
   }
@@ -360,8 +406,11 @@ __global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_stats_kernel(PpoArgs a) 
     sum[k] = v;
   }
   const float* log_std = a.params + a.log_std_off;
-  double h = 0.0;   // the entropy: summed in f64, j ascending, rounded once
-  for (int j = 0; j < a.act_dim; ++j) h += ((double)log_std[j] + 0.5) + 0.91893853320467274178;
+  double h = 0.0;   // the entropy: summed in f64, j ascending, rounded once; with act_perm: of the symmetrised log_std (f32, as the head stage forms it)
+  for (int j = 0; j < a.act_dim; ++j) {
+    const float ls = a.act_perm ? 0.5f * (log_std[j] + log_std[a.act_perm[j]]) : log_std[j];
+    h += ((double)ls + 0.5) + 0.91893853320467274178;
+  }
   a.stats[0] = sum[0] * a.inv_b;
   a.stats[1] = sum[1] * a.inv_b;
   a.stats[2] = (float)h;
@@ -373,7 +422,8 @@ __global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_stats_kernel(PpoArgs a) 
 }
 
 void launch_ppo(hipStream_t s, const PpoArgs& a) {
-  hipLaunchKernelGGL(ppo_rows_kernel, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
+  if (a.in_perm) hipLaunchKernelGGL(ppo_rows_kernel<true>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(ppo_rows_kernel<false>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(a.n_tiles, a.n_chunks), dim3(64), 0, s, a);
   hipLaunchKernelGGL(ppo_reduce_kernel, dim3(a.n_reduce_blocks), dim3(PPO_REDUCE_BLOCK), 0, s, a);
   hipLaunchKernelGGL(ppo_stats_kernel, dim3(1), dim3(PPO_REDUCE_BLOCK), 0, s, a);

@@ -142,10 +142,13 @@ def rows_2d(rows, dim: int):
 
 
 MAX_MINIBATCH = 1 << 22   # include/mocca.h mocca_ppo_grad
+MAX_MINIBATCH_SYM = 1 << 21   # mocca_ppo_grad_sym: two scratch rows per minibatch row
 
 
-def ppo_args(policy, device, obs, action, old_logp, adv, returns, idx, old_value, clip, value_coef, entropy_coef, value_clip, grad, stats):
-    """check the tensors and numbers of ppo_grad -> (R rollout rows, obs row stride, B minibatch rows); ValueError otherwise"""
+def ppo_args(policy, device, obs, action, old_logp, adv, returns, idx, old_value, clip, value_coef, entropy_coef, value_clip, grad, stats,
+             symmetric=False):
+    """check the tensors and numbers of ppo_grad -> (R rollout rows, obs row stride, B minibatch rows); ValueError otherwise.  `symmetric`:
+    the call is mocca_ppo_grad_sym, whose minibatch holds at most MAX_MINIBATCH_SYM rows"""
     import torch
     if not isinstance(obs, torch.Tensor) or obs.device != device:
         raise ValueError("obs must be a float32 tensor on the env's device")
@@ -165,8 +168,9 @@ def ppo_args(policy, device, obs, action, old_logp, adv, returns, idx, old_value
         if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.device != device or idx.dim() != 1 or not idx.is_contiguous():
             raise ValueError("idx must be a contiguous int64 [B] tensor on the env's device (a chunk of torch.randperm)")
         n_batch = int(idx.numel())
-    if not 1 <= n_batch <= MAX_MINIBATCH:
-        raise ValueError(f"the minibatch must have 1 .. {MAX_MINIBATCH} rows")
+    most = MAX_MINIBATCH_SYM if symmetric else MAX_MINIBATCH
+    if not 1 <= n_batch <= most:
+        raise ValueError(f"the minibatch must have 1 .. {most} rows")
     for name, x in (("clip", clip), ("value_coef", value_coef), ("entropy_coef", entropy_coef)):
         if not (np.isfinite(float(x)) and float(x) >= 0.0):
             raise ValueError(f"{name} must be finite and not negative")

@@ -370,7 +370,8 @@ class TorchVecEnv:
         self.venv.update_obs_stats(stats, rows, mean_out=mean_out, inv_std_out=inv_std_out)
 
     def ppo_grad(self, obs, action, old_logp, adv, returns, *args, **kw) -> dict:
-        """PPO's minibatch loss and its gradient over the rollout storage, four launches: `VecEnv.ppo_grad`.  One handle only."""
+        """PPO's minibatch loss and its gradient over the rollout storage, four launches: `VecEnv.ppo_grad` -- of the symmetric network
+        where the attached policy carries mirror tables (`symmetric_policy`).  One handle only."""
         if not hasattr(self.venv, "lib"):
             raise NotImplementedError("ppo_grad needs one handle (sub_batches=1)")
         return self.venv.ppo_grad(obs, action, old_logp, adv, returns, *args, **kw)

@@ -443,7 +443,7 @@ class VecEnv:
                                             ptr(inv_std_out), self._stream()), self.h)
         self._out()
 
-    # ---- a PPO minibatch step on the device (include/mocca.h mocca_ppo_grad) ----
+    # ---- a PPO minibatch step on the device (include/mocca.h mocca_ppo_grad / mocca_ppo_grad_sym) ----
     def ppo_grad(self, obs: torch.Tensor, action: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor, returns: torch.Tensor,
                  idx: Optional[torch.Tensor] = None, old_value: Optional[torch.Tensor] = None, clip: float = 0.2, value_coef: float = 0.5,
                  entropy_coef: float = 0.0, value_clip: bool = False, grad: Optional[torch.Tensor] = None,
@@ -454,20 +454,24 @@ class VecEnv:
         `obs` [R, >= in_dim] or [T, N, >= in_dim] RAW rows with a contiguous last dimension and one stride between rows (`rollouts.obs[:-1]`);
         `action` [.., act_dim], `old_logp`, `adv`, `returns`, `old_value` ([..] or [.., 1]; `old_value` only for `value_clip`): contiguous
         float32 of the same R rows.  `idx` int64 [B]: the minibatch's rows (a chunk of `torch.randperm(R)`), every entry in 0 .. R - 1 -- the
-        kernel does not check; None: all R rows.  Reads the weights `update_policy` last wrote; the plain policy only.  `grad` / `stats`:
-        caller-owned outputs, allocated where none is given.  The same inputs give the same bits on every run."""
+        kernel does not check; None: all R rows.  Reads the weights `update_policy` last wrote.  A policy with mirror tables attached
+        (`DevicePolicy(symmetry=)`, `set_policy_symmetry`) takes the symmetric network's gradient, what autograd gives through
+        `symmetry.SymmetricGaussian.evaluate_actions` (mocca_ppo_grad_sym: the same four launches on twice the columns; the entropy is the
+        symmetrised log_std's); at most 2^21 rows then, 2^22 otherwise.  `grad` / `stats`: caller-owned outputs, allocated where none is
+        given.  The same inputs give the same bits on every run."""
         if self.policy is None:
             raise _lib.MoccaError("ppo_grad needs a policy (set_policy)")
+        symmetric = getattr(self.policy, "symmetry", None) is not None
         _, stride, n_batch = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, idx, old_value, clip, value_coef,
-                                          entropy_coef, value_clip, grad, stats)
+                                          entropy_coef, value_clip, grad, stats, symmetric=symmetric)
         f32 = dict(dtype=torch.float32, device=self.device)
         grad = torch.empty(self.policy.n_head(), **f32) if grad is None else grad
         stats = torch.empty(8, **f32) if stats is None else stats
         ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
         self._in()
-        _lib.check(self.lib.mocca_ppo_grad(self.h, ptr(obs), stride, ptr(action), ptr(old_logp), ptr(adv), ptr(returns), ptr(old_value), ptr(idx),
-                                           n_batch, float(clip), float(value_coef), float(entropy_coef), int(bool(value_clip)), ptr(grad),
-                                           ptr(stats), self._stream()), self.h)
+        call = self.lib.mocca_ppo_grad_sym if symmetric else self.lib.mocca_ppo_grad
+        _lib.check(call(self.h, ptr(obs), stride, ptr(action), ptr(old_logp), ptr(adv), ptr(returns), ptr(old_value), ptr(idx), n_batch, float(clip),
+                        float(value_coef), float(entropy_coef), int(bool(value_clip)), ptr(grad), ptr(stats), self._stream()), self.h)
         self._out()
         return {"grad": grad, "stats": stats}
 

@@ -5,10 +5,10 @@ that LEARNS, and what does the step kernel cost on the workload a trained policy
 Plain PPO in the pytorch-a2c-ppo-acktr mould the reference's trainers (README.md:33-39) follow -- Gaussian MLP policy 2 x 256 tanh, separate value
 net, GAE(0.95), clipped surrogate, Adam, running observation normalisation -- with everything on the device: the step kernel writes observation /
 reward / masks / bad_masks straight into the rollout storage (`step(action, into=...)`), Monitor's statistics come from `envs.episode_totals`.
-No symmetry loss, no curriculum: this is a sanity run, not SymmetricRL.
+No symmetry loss, no curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it SymmetricRL's symmetric network.
 
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
-                           [--device-policy [--device-returns [--device-grad]]]
+                           [--device-policy [--device-returns [--device-grad]]] [--symmetric]
 --device-policy: collection runs through `envs.act_step(obs[t], into=...)` -- the policy kernel (normalisation, both nets, the sample, its
 log-probability, the value) and the step kernel, two launches per step and no torch op; `envs.update_policy(flat)` once per iteration hands the
 kernel the optimiser's new weights and the running observation statistics.  The noise then comes from the kernel, not from torch.randn.
@@ -21,6 +21,9 @@ only its head is refreshed from the optimiser's parameters.
 `DevicePolicy.flat_params()`'s order (the nn.Linear weights are views into it); each minibatch is one `envs.ppo_grad` on the raw rollout
 storage and the `perm` chunk -- evaluate_actions, the clipped surrogate, the value loss and backward() in four launches --, the global-norm
 clip scales the gradient by its own `stats[5]`, torch.optim.Adam steps the flat parameter and `envs.update_policy(flat)` follows every step.
+--symmetric: the policy is the mirror-symmetric network built from the env's get_mirror_indices() (`symmetry.SymmetricGaussian` over the same
+`pi`, `vf` and `log_std`): it serves the torch update, torch collection and --verify-grad; with --device-policy the attached policy carries
+`envs.symmetric_policy(...)`'s mirror tables, and with --device-grad each minibatch is one symmetric `ppo_grad` (mocca_ppo_grad_sym).
 --verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor.
 writes <out>.jsonl (one line per logged iteration: env-steps so far, mean episode return / length of the episodes that ended since the last line,
 wall-clock env-steps/s of the whole loop incl. learning) and <out>_policy.npz (weights + observation statistics: `bench.py`'s workload
@@ -56,6 +59,7 @@ def main():
     ap.add_argument("--device-returns", action="store_true", help="GAE, advantage normalisation and observation statistics on the device (finish_rollout, update_obs_stats)")
     ap.add_argument("--verify-returns", action="store_true", help="with --device-returns: also run the torch GAE loop on the same storage and insist on the same bits")
     ap.add_argument("--device-grad", action="store_true", help="with --device-returns: each minibatch's loss and gradient on the device (ppo_grad); the parameters live in one flat tensor")
+    ap.add_argument("--symmetric", action="store_true", help="SymmetricRL's symmetric network: mean, value and log_std symmetrised through the env's mirror tables")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args()
     if args.device_grad and not args.device_returns:
@@ -96,9 +100,24 @@ def main():
     def logprob(mu, a):
         return (-0.5 * ((a - mu) / log_std.exp()) ** 2 - log_std - 0.9189385332046727).sum(-1, keepdim=True)
 
+    if args.symmetric:
+        from mocca_envs_amd.policy import DevicePolicy
+        from mocca_envs_amd.symmetry import SymmetricGaussian
+        tables = envs.symmetric_policy(DevicePolicy.from_torch(pi, vf, log_std)).symmetry
+        sym = SymmetricGaussian(pi, vf, log_std, tables).to(dev)      # shares pi, vf and log_std
+        inv_std_now = lambda: inv_std if args.device_returns else 1.0 / torch.sqrt(var + 1e-8)
+
+    def evaluate(mb):
+        """(logp [b, 1], value [b, 1]) of the minibatch's stored actions under the current parameters"""
+        if args.symmetric:      # the mirror acts on the RAW row
+            lp, _, v = sym.evaluate_actions(raw_all[mb], a_all[mb], mean, inv_std_now(), 10.0)
+            return lp.unsqueeze(-1), v.unsqueeze(-1)
+        return logprob(pi(o_all[mb]), a_all[mb]), vf(o_all[mb])
+
     if args.device_policy:
         from mocca_envs_amd.policy import DevicePolicy
-        envs.attach_policy(DevicePolicy.from_torch(pi, vf, log_std, obs_mean=mean, obs_var=var, eps=1e-8, clip=10.0))
+        dp = DevicePolicy.from_torch(pi, vf, log_std, obs_mean=mean, obs_var=var, eps=1e-8, clip=10.0)
+        envs.attach_policy(envs.symmetric_policy(dp) if args.symmetric else dp)
         row_act = lambda t: dict(row(t), action=S["act"][t], logp=S["logp"][t], value=S["value"][t])
         # DevicePolicy.flat_params()'s order, built on the device: layers of pi then vf (W, b), log_std, mean, 1 / sqrt(var + eps)
         flat_params = lambda: torch.cat([q.reshape(-1) for net in (pi, vf) for m in net if isinstance(m, nn.Linear) for q in (m.weight, m.bias)]
@@ -173,12 +192,19 @@ def main():
                     if args.device_policy:
                         envs.act_step(S["obs"][t], into=row_act(t))
                         continue
+                    if args.symmetric:
+                        mu, ls, v = sym(S["obs"][t], mean, inv_std_now(), 10.0)
+                        eps = torch.randn_like(mu)
+                        S["act"][t].copy_(mu + ls.exp() * eps)
+                        S["logp"][t].copy_((-0.5 * eps * eps - ls - 0.9189385332046727).sum(-1, keepdim=True)); S["value"][t].copy_(v.unsqueeze(-1))
+                        envs.step(S["act"][t], into=row(t))
+                        continue
                     o = norm(S["obs"][t])
                     mu = pi(o)
                     a = mu + log_std.exp() * torch.randn_like(mu)
                     S["act"][t].copy_(a); S["logp"][t].copy_(logprob(mu, a)); S["value"][t].copy_(vf(o))
                     envs.step(S["act"][t], into=row(t))
-                S["value"][T].copy_(vf(norm(S["obs"][T])))
+                S["value"][T].copy_(sym(S["obs"][T], mean, inv_std_now(), 10.0)[2].unsqueeze(-1) if args.symmetric else vf(norm(S["obs"][T])))
                 # GAE; an episode cut by the TimeLimit (bad_masks = 0) is not bootstrapped through: its advantage stops there (a2c-ppo-acktr's use_proper_time_limits)
                 adv = torch.zeros(T, N, 1, device=dev)
                 gae = torch.zeros(N, 1, device=dev)
@@ -193,18 +219,19 @@ def main():
         # ---- learn
         B = N * T
         o_all, a_all, lp_all = norm(S["obs"][:T]).reshape(B, od), S["act"].reshape(B, ad), S["logp"].reshape(B, 1)
-        adv_all, ret_all = adv.reshape(B, 1), ret.reshape(B, 1)
+        adv_all, ret_all, raw_all = adv.reshape(B, 1), ret.reshape(B, 1), S["obs"][:T].reshape(B, od)
         for ep in range(args.epochs):
             perm = torch.randperm(B, device=dev)
             for k, mb in enumerate(perm.chunk(args.minibatches)):
                 if args.device_grad:
-                    # evaluate_actions, the clipped surrogate, the value loss and backward() as one call on the raw storage
+                    # evaluate_actions, the clipped surrogate, the value loss and backward() as one call on the raw storage (--symmetric: of
+                    # the symmetric network -- the attached policy carries the mirror tables)
                     envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf)
                     if args.verify_grad and ep == 0 and k == 0:
-                        mu = pi(o_all[mb])
-                        ratio = (logprob(mu, a_all[mb]) - lp_all[mb]).exp()
+                        lp, v = evaluate(mb)
+                        ratio = (lp - lp_all[mb]).exp()
                         surr = torch.min(ratio * adv_all[mb], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_all[mb]).mean()
-                        v_loss = 0.5 * (vf(o_all[mb]) - ret_all[mb]).pow(2).mean()
+                        v_loss = 0.5 * (v - ret_all[mb]).pow(2).mean()
                         auto = torch.autograd.grad(-surr + 0.5 * v_loss, head[:-1] if args.fixed_std else head)
                         worst, pos = 0.0, 0
                         for g in auto:
@@ -221,10 +248,10 @@ def main():
                     opt.step()
                     envs.update_policy(flat)
                     continue
-                mu = pi(o_all[mb])
-                ratio = (logprob(mu, a_all[mb]) - lp_all[mb]).exp()
+                lp, v = evaluate(mb)
+                ratio = (lp - lp_all[mb]).exp()
                 surr = torch.min(ratio * adv_all[mb], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_all[mb]).mean()
-                v_loss = 0.5 * (vf(o_all[mb]) - ret_all[mb]).pow(2).mean()
+                v_loss = 0.5 * (v - ret_all[mb]).pow(2).mean()
                 opt.zero_grad(set_to_none=True)
                 (-surr + 0.5 * v_loss).backward()
                 nn.utils.clip_grad_norm_(list(pi.parameters()) + list(vf.parameters()) + ([] if args.fixed_std else [log_std]), 0.5)

@@ -4,6 +4,9 @@
   python tools/ppo_grad_bench.py grad   [--out profiles/ppo_grad.json]
       B = 16384 rows gathered from 131072 of the 52 -> 256 -> 256 -> {21, 1} tanh policy: `VecEnv.ppo_grad` against the same minibatch
       through torch eager as tools/ppo_demo.py's learn loop does it (forward, loss, zero_grad, backward); HIP events, 5 blocks of 200 warm calls.
+  python tools/ppo_grad_bench.py grad --symmetric   [--out profiles/ppo_grad_sym.json]
+      the same for the mirror-symmetric policy (the env's own mirror tables): mocca_ppo_grad_sym against the minibatch through
+      `symmetry.SymmetricGaussian` in torch eager, as tools/ppo_demo.py --symmetric does it; both in one process.
   python tools/ppo_grad_bench.py act --key NAME [--package-root DIR] [--out ...]
       `update_policy` and `act` at 4096 envs, 7 blocks of 200 warm calls, stored under "act_update"[NAME].  --package-root: the tree whose
       mocca_envs_amd (with its built library) is imported -- a checkout of the parent commit gives the A/B; run the two alternately.
@@ -53,11 +56,15 @@ def random_net(rng, dims):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("mode", choices=("grad", "act", "trace", "per-launch"))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_grad.json"))
+    ap.add_argument("--out")
+    ap.add_argument("--symmetric", action="store_true", help="grad: the mirror-symmetric policy (mocca_ppo_grad_sym against SymmetricGaussian)")
     ap.add_argument("--key", default="this")
     ap.add_argument("--package-root", default=ROOT)
     ap.add_argument("--kernel-db")
     args = ap.parse_args()
+    if args.symmetric and args.mode != "grad":
+        ap.error("--symmetric goes with the grad mode")
+    args.out = args.out or os.path.join(ROOT, "profiles", "ppo_grad_sym.json" if args.symmetric else "ppo_grad.json")
     if args.mode == "per-launch":
         import sqlite3
         import statistics
@@ -94,6 +101,8 @@ def main():
         env.close()
         return
     env = VecEnv("Walker3DCustomEnv-v0", 4, device=0)
+    if args.symmetric:
+        dp = env.symmetric_policy(dp)
     env.set_policy(dp)
     f = lambda *s: torch.from_numpy(rng.normal(0, 1, s).astype(np.float32)).cuda()
     obs, act, olp, adv, ret = f(ROWS, 52) * 3, f(ROWS, 21), f(ROWS) - 20, f(ROWS), f(ROWS)
@@ -107,7 +116,10 @@ def main():
         env.close()
         return
     res = {"what": f"B = {B} rows gathered from {ROWS}, policy 52 -> 256 -> 256 -> {{21, 1}} tanh, HIP events, 5 blocks of 200 warm calls"}
-    res["mocca_ppo_grad"] = timed(torch, call)
+    name = "mocca_ppo_grad_sym" if args.symmetric else "mocca_ppo_grad"
+    if args.symmetric:
+        res["what"] += "; the mirror-symmetric policy of the env's mirror tables, torch eager through symmetry.SymmetricGaussian"
+    res[name] = timed(torch, call)
 
     def mlp(o):
         return nn.Sequential(nn.Linear(52, 256), nn.Tanh(), nn.Linear(256, 256), nn.Tanh(), nn.Linear(256, o)).cuda()
@@ -118,6 +130,19 @@ def main():
     lp_all, adv_all, ret_all = olp.reshape(-1, 1), adv.reshape(-1, 1), ret.reshape(-1, 1)
     logprob = lambda mu, a: (-0.5 * ((a - mu) / log_std.exp()) ** 2 - log_std - 0.9189385332046727).sum(-1, keepdim=True)
 
+    if args.symmetric:
+        from mocca_envs_amd.symmetry import SymmetricGaussian
+        sym = SymmetricGaussian(pi, vf, log_std, dp.symmetry).cuda()
+        zero, one = torch.zeros(52, device="cuda"), torch.ones(52, device="cuda")
+
+    def eager_sym():
+        logp, _, value = sym.evaluate_actions(obs[idx], act[idx], zero, one, 10.0)
+        ratio = (logp.unsqueeze(-1) - lp_all[idx]).exp()
+        surr = torch.min(ratio * adv_all[idx], ratio.clamp(0.8, 1.2) * adv_all[idx]).mean()
+        v_loss = 0.5 * (value.unsqueeze(-1) - ret_all[idx]).pow(2).mean()
+        opt.zero_grad(set_to_none=True)
+        (-surr + 0.5 * v_loss).backward()
+
     def eager():
         mu = pi(o_all[idx])
         ratio = (logprob(mu, act[idx]) - lp_all[idx]).exp()
@@ -126,8 +151,8 @@ def main():
         opt.zero_grad(set_to_none=True)
         (-surr + 0.5 * v_loss).backward()
 
-    res["torch_eager"] = timed(torch, eager)
-    res["speedup"] = round(res["torch_eager"]["us_per_call_median"] / res["mocca_ppo_grad"]["us_per_call_median"], 2)
+    res["torch_eager"] = timed(torch, eager_sym if args.symmetric else eager)
+    res["speedup"] = round(res["torch_eager"]["us_per_call_median"] / res[name]["us_per_call_median"], 2)
     merge(args.out, "minibatch", res)
     print(json.dumps(res))
     env.close()
