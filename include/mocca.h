@@ -555,6 +555,75 @@ int mocca_ppo_grad_sym(mocca_handle h, const float *obs_dev, int obs_stride, con
                        const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
                        double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
 
+/* ---- PPO's optimiser step and update loop on the device (no reference counterpart: the reference's trainers run clip_grad_norm_, Adam and
+ *      the minibatch loop in torch and Python) ---- */
+
+/* mocca_adam_step   replaces `nn.utils.clip_grad_norm_(params, max_grad_norm)`, `optimizer.step()` of torch.optim.Adam (no weight decay, no
+ *                   amsgrad) and the mocca_update_policy that makes the step visible to the kernels -- three launches on `stream`.
+ *                   params_dev [n_floats] f32: the flat tensor mocca_update_policy takes, in either of its two lengths, updated IN PLACE.
+ *                   Its first n_params floats (1 .. n_head, n_head the length without mean / inv_std) are the trainable ones; n_head -
+ *                   act_dim keeps log_std out of the norm and the step (a fixed action noise).  grad_dev: at least n_params f32 in the same
+ *                   order (mocca_ppo_grad's grad_dev).  moments_dev f32 [2][n_head]: Adam's m, then v; caller-owned, fresh state zeros.
+ *                   clock_dev f64 [4]: {t, beta1^t, beta2^t, skipped steps}; caller-owned, fresh state {0, 1, 1, 0}.
+ *                   Launch A, one workgroup of 256: S = sum f64(g[i])^2 over i < n_params -- thread tid adds i = tid, tid + 256, ..
+ *                   ascending, then the tree sq[tid] += sq[tid + h], h = 128 .. 1 -- and, in f64,
+ *                       nrm = sqrt(S);  coef = max_grad_norm > 0 ? min(1, max_grad_norm / (nrm + 1e-6)) : 1, rounded once to f32
+ *                   S not finite (a NaN or an infinity in the gradient): the step is SKIPPED -- clock[3] += 1; params, moments, t and the
+ *                   two products stay bit for bit as they were, so that one bad minibatch does not poison a long run.  Otherwise
+ *                       t += 1;  p1 = p1 * beta1;  p2 = p2 * beta2          (running products: every bit is defined without pow)
+ *                       ss = f32(lr / (1 - p1));  bc = f32(sqrt(1 - p2));  b2 = f32(beta2);  w1 = f32(1 - beta1);  w2 = f32(1 - beta2);
+ *                       e = f32(eps)
+ *                   Launch B, one thread per trainable float, each line ONE IEEE f32 operation in this order, never contracted into an
+ *                   FMA, square root and division correctly rounded:
+ *                       g = grad[i] * coef
+ *                       d = g - m;  d = d * w1;  m = m + d
+ *                       v = v * b2;  q = g * g;  q = q * w2;  v = v + q
+ *                       s = sqrtf(v);  s = s / bc;  s = s + e
+ *                       u = m / s;  u = ss * u;  p = p - u
+ *                   Launch C is mocca_update_policy's repack of params_dev, n_floats: the next mocca_act / mocca_ppo_grad on the stream
+ *                   sees the step (and a call before any mocca_update_policy fills the image).  Floats of params_dev and moments_dev
+ *                   beyond n_params are not touched.  Asynchronous on `stream`; the first call allocates a 32-byte record and the
+ *                   gradient buffer of mocca_ppo_update in the handle and may synchronise, every other call allocates nothing, reads
+ *                   nothing on the host and uses no atomics: after one warm call it is capturable in a hipGraph.  The clock is on the
+ *                   device, so a replay advances it; lr, the betas, eps and max_grad_norm are kernel arguments and are BAKED INTO a
+ *                   captured call -- a trainer that decays lr captures again or calls eagerly.
+ * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): a NULL handle, params_dev, grad_dev, moments_dev or clock_dev; called
+ * before mocca_set_policy; n_floats that fits neither form; n_params outside 1 .. n_head; a non-finite or negative lr or eps; a beta outside
+ * [0, 1); a NaN or negative max_grad_norm (0: no clip). */
+int mocca_adam_step(mocca_handle h, float *params_dev, size_t n_floats, const float *grad_dev, int64_t n_params, float *moments_dev,
+                    double *clock_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm, void *stream);
+
+/* mocca_ppo_update  replaces a2c-ppo-acktr's `ppo.update(rollouts)`: epochs x M minibatches of [shuffle, gradient, clip, Adam, repack] in one
+ *                   call, nothing read on the host.  R = n_rollout_rows, B = minibatch_rows, M = R / B minibatches per epoch, the
+ *                   remainder dropped (`BatchSampler(.., drop_last=True)`).  The arrays obs_dev .. old_value_dev, clip, value_coef,
+ *                   entropy_coef and value_clip are mocca_ppo_grad's; params_dev .. max_grad_norm are mocca_adam_step's.  Per epoch ONE
+ *                   launch fills a handle-owned i64 [R] with a permutation of 0 .. R - 1; per minibatch u follow the four launches of
+ *                   mocca_ppo_grad -- of mocca_ppo_grad_sym when the policy has mirror tables attached: this entry point serves both --
+ *                   with idx_dev = that array + u B and a handle-owned gradient [n_head], then mocca_adam_step's three launches on it.
+ *                   The result is, bit for bit, what that sequence of calls gives.
+ *                   The permutation is closed-form and defined in integers: w = max(2, bit_length(R - 1)) rounded up to even,
+ *                   half = w / 2, mask = 2^half - 1.  One pass maps x = (L << half) | Rr through six Feistel rounds
+ *                       (L, Rr) <- (Rr, L ^ (F & mask))
+ *                       F = philox4x32(c0 = Rr, c1 = round, c2 = t mod 2^32, c3 = t >> 32, k0 = seed mod 2^32, k1 = seed >> 32)[0]
+ *                   (Philox4x32-10); entry b starts at x = b and takes passes until x < R.  A pass is a bijection of 0 .. 2^w - 1, so the
+ *                   walk returns below R and the entries are a bijection of 0 .. R - 1.  t is clock_dev[0] as the fill kernel READS IT ON
+ *                   THE DEVICE when the epoch starts: a replayed graph shuffles anew, and a fresh clock with the same seed repeats a run.
+ *                   stats_dev [epochs M][8] f32 or NULL: row k holds the k-th minibatch's mocca_ppo_grad statistics, with [6] overwritten
+ *                   by the clip coefficient applied (0 on a skipped step) and [7] left 0; the trainer's `value_loss_epoch` etc. are the
+ *                   rows' mean, and the rows' [3] is what a KL monitor reads.
+ *                   params_dev must hold what mocca_update_policy (or mocca_adam_step) last wrote.  mocca_ppo_grad's conditions hold as
+ *                   they stand -- growing either scratch FREES the old one: warm the handle with the largest B and R it will see --; the
+ *                   call is a linear chain of epochs (1 + 7 M) launches on `stream`, capturable after one warm call of the same shapes,
+ *                   with mocca_adam_step's scalars and `seed` baked in.
+ * Errors (MOCCA_E_ARG, with a message; the handle is left as it was and nothing is launched): those of mocca_adam_step and of mocca_ppo_grad
+ * (/ mocca_ppo_grad_sym) but for their grad_dev and idx_dev; minibatch_rows outside 1 .. n_rollout_rows; epochs < 1; n_rollout_rows < 1 or
+ * beyond mocca_ppo_grad's bound (2^22, with mirror tables 2^21). */
+int mocca_ppo_update(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
+                     const float *adv_dev, const float *returns_dev, const float *old_value_dev, int64_t n_rollout_rows,
+                     int64_t minibatch_rows, int epochs, double clip, double value_coef, double entropy_coef, int value_clip,
+                     float *params_dev, size_t n_floats, int64_t n_params, float *moments_dev, double *clock_dev, double lr,
+                     double beta1, double beta2, double eps, double max_grad_norm, uint64_t seed, float *stats_dev, void *stream);
+
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */
 int mocca_kernel_info(mocca_handle h, int *vgprs, int *sgprs, int *lds_bytes, int *scratch_bytes, int *max_blocks_per_cu);

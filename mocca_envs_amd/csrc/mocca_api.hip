@@ -13,6 +13,7 @@
 
 #include "mocca.h"
 #include "mocca_kernels.h"
+#include "mocca_optim.h"
 #include "mocca_policy.h"
 #include "mocca_ppo.h"
 #include "mocca_render.h"
@@ -172,6 +173,8 @@ struct mocca_ctx {
   size_t obs_part_cap = 0;
   DevBuf<double> d_ppo;              // scratch of mocca_ppo_grad (mocca_ppo.h), grown on demand
   size_t ppo_cap = 0;
+  DevBuf<double> d_optim;            // scratch of mocca_adam_step / mocca_ppo_update (mocca_optim.h): the record, the gradient, the permutation
+  size_t optim_cap = 0;
   std::string err;
 };
 static_assert(ROBOT_STATE_STRIDE == mocca_ctrl::CTRL_RS_STRIDE, "the step kernels and the controller kernel share the robot_state buffer");
@@ -1143,24 +1146,34 @@ int mocca_set_policy_symmetry(mocca_handle h, const int32_t* in_perm_host, const
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy_symmetry"); }
 
-int mocca_update_policy(mocca_handle h, const float* params_dev, size_t n_floats, void* stream) {
-  if (!h) return MOCCA_E_ARG;
-  if (!h->d_pol_image) { h->err = "mocca_update_policy needs a policy (mocca_set_policy)"; return MOCCA_E_ARG; }
-  if (!params_dev) { h->err = "mocca_update_policy: params_dev must not be NULL"; return MOCCA_E_ARG; }
+// what n_floats of a flat parameter tensor must be (mocca_update_policy, mocca_adam_step): -> "" or what is wrong
+static std::string check_n_floats(mocca_handle h, size_t n_floats) {
   const size_t base = h->pol_n_base, in_dim = (size_t)h->pol.in_dim;
-  if (n_floats != base && n_floats != base + 2 * in_dim) {
-    h->err = "mocca_update_policy: this policy takes " + std::to_string(base) + " floats (layers, log_std), or " + std::to_string(base + 2 * in_dim) +
-             " with mean and inv_std, not " + std::to_string(n_floats);
-    return MOCCA_E_ARG;
-  }
-  DeviceGuard guard(h->device);
+  if (n_floats == base || n_floats == base + 2 * in_dim) return "";
+  return "this policy takes " + std::to_string(base) + " floats (layers, log_std), or " + std::to_string(base + 2 * in_dim) +
+         " with mean and inv_std, not " + std::to_string(n_floats);
+}
+
+// the repack launch of mocca_update_policy; n_floats has been checked, the handle's device is current
+static void repack_policy(mocca_handle h, const float* params_dev, size_t n_floats, hipStream_t s) {
+  const size_t base = h->pol_n_base, in_dim = (size_t)h->pol.in_dim;
   mocca_pol::RepackArgs rp = h->pol_repack;
   rp.src = params_dev;
   const bool norm = n_floats != base;
   rp.rows[h->pol_tail_row].fill = norm ? 1.0f : 0.0f;
   rp.rows[h->pol_tail_row + 1].src = norm ? (int32_t)base : -1;
   rp.rows[h->pol_tail_row + 2].src = norm ? (int32_t)(base + in_dim) : -1;
-  mocca_pol::launch_repack((hipStream_t)stream, rp);
+  mocca_pol::launch_repack(s, rp);
+}
+
+int mocca_update_policy(mocca_handle h, const float* params_dev, size_t n_floats, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (!h->d_pol_image) { h->err = "mocca_update_policy needs a policy (mocca_set_policy)"; return MOCCA_E_ARG; }
+  if (!params_dev) { h->err = "mocca_update_policy: params_dev must not be NULL"; return MOCCA_E_ARG; }
+  const std::string wrong = check_n_floats(h, n_floats);
+  if (!wrong.empty()) { h->err = "mocca_update_policy: " + wrong; return MOCCA_E_ARG; }
+  DeviceGuard guard(h->device);
+  repack_policy(h, params_dev, n_floats, (hipStream_t)stream);
   HIP_TRY(h, hipGetLastError());
   h->pol_filled = true;
   return MOCCA_OK;
@@ -1278,7 +1291,7 @@ int mocca_obs_stats(mocca_handle h, const float* rows_dev, int64_t n_rows, int r
 static int ppo_grad(mocca_handle h, const char* name, bool sym, const float* obs_dev, int obs_stride, const float* action_dev,
                     const float* old_logp_dev, const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev,
                     int64_t n_rows, double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev,
-                    void* stream) {
+                    void* stream, bool check_only = false) {   // check_only: the refusals alone (mocca_ppo_update asks before its first launch)
   using namespace mocca_ctrl;
   using namespace mocca_ppo;
   if (!h) { g_err = std::string(name) + ": NULL handle"; return MOCCA_E_ARG; }
@@ -1295,6 +1308,7 @@ static int ppo_grad(mocca_handle h, const char* name, bool sym, const float* obs
     return bad("obs_stride " + std::to_string(obs_stride) + " is smaller than the policy's in_dim (" + std::to_string(h->pol.in_dim) + ")");
   if (!std::isfinite(clip) || clip < 0.0 || !std::isfinite(value_coef) || value_coef < 0.0 || !std::isfinite(entropy_coef) || entropy_coef < 0.0)
     return bad("clip, value_coef and entropy_coef must be finite and not negative");
+  if (check_only) return MOCCA_OK;
   DeviceGuard guard(h->device);
   PpoArgs a{};
   const mocca_pol::PolicyArgs& p = h->pol;
@@ -1348,6 +1362,93 @@ int mocca_ppo_grad_sym(mocca_handle h, const float* obs_dev, int obs_stride, con
                        double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
   return ppo_grad(h, "mocca_ppo_grad_sym", true, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, idx_dev, n_rows,
                   clip, value_coef, entropy_coef, value_clip, grad_dev, stats_dev, stream);
+}
+
+// the refusals of mocca_adam_step's arguments (mocca_ppo_update shares them): -> MOCCA_OK, or MOCCA_E_ARG with the message set
+static int adam_check(mocca_handle h, const char* name, const float* params_dev, size_t n_floats, const float* grad_dev, bool need_grad,
+                      int64_t n_params, const float* moments_dev, const double* clock_dev, double lr, double beta1, double beta2, double eps,
+                      double max_grad_norm) {
+  if (!h) { g_err = std::string(name) + ": NULL handle"; return MOCCA_E_ARG; }
+  auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
+  if (!h->d_pol_image) return bad("needs a policy (mocca_set_policy)");
+  if (!params_dev || (need_grad && !grad_dev) || !moments_dev || !clock_dev)
+    return bad(std::string("params_dev, ") + (need_grad ? "grad_dev, " : "") + "moments_dev and clock_dev must not be NULL");
+  const std::string wrong = check_n_floats(h, n_floats);
+  if (!wrong.empty()) return bad(wrong);
+  if (n_params < 1 || n_params > (int64_t)h->pol_n_base)
+    return bad("n_params must be 1 .. " + std::to_string(h->pol_n_base) + " (the floats ahead of mean / inv_std), not " + std::to_string(n_params));
+  if (!std::isfinite(lr) || lr < 0.0 || !std::isfinite(eps) || eps < 0.0) return bad("lr and eps must be finite and not negative");
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return bad("beta1 and beta2 must lie in [0, 1)");
+  if (std::isnan(max_grad_norm) || max_grad_norm < 0.0) return bad("max_grad_norm must not be NaN or negative (0: no clip)");
+  return MOCCA_OK;
+}
+
+// f64 words of d_optim ahead of the permutation (mocca_optim.h: Scratch)
+static size_t optim_head_words(mocca_handle h) { return mocca_optim::OPT_REC_WORDS + (h->pol_n_base + 1) / 2; }
+
+// launches A, B and C of mocca_adam_step; the arguments have been checked, d_optim holds the record, the handle's device is current
+static void adam_launch(mocca_handle h, float* params_dev, size_t n_floats, const float* grad_dev, int64_t n_params, float* moments_dev,
+                        double* clock_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm, float* stats_row, hipStream_t s) {
+  mocca_optim::AdamArgs a{};
+  a.params = params_dev; a.grad = grad_dev; a.n_params = (int)n_params;
+  a.m = moments_dev; a.v = moments_dev + h->pol_n_base; a.clock = clock_dev;
+  a.rec = (mocca_optim::AdamRecord*)h->d_optim.get();
+  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_grad_norm = max_grad_norm; a.stats = stats_row;
+  mocca_optim::launch_adam(s, a);
+  repack_policy(h, params_dev, n_floats, s);
+}
+
+int mocca_adam_step(mocca_handle h, float* params_dev, size_t n_floats, const float* grad_dev, int64_t n_params, float* moments_dev,
+                    double* clock_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm, void* stream) {
+  if (int rc = adam_check(h, "mocca_adam_step", params_dev, n_floats, grad_dev, true, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps,
+                          max_grad_norm)) return rc;
+  DeviceGuard guard(h->device);
+  if (int rc = grow_scratch(h, "mocca_adam_step", h->d_optim, &h->optim_cap, optim_head_words(h))) return rc;
+  adam_launch(h, params_dev, n_floats, grad_dev, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm, nullptr, (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  h->pol_filled = true;
+  return MOCCA_OK;
+}
+
+int mocca_ppo_update(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev,
+                     const float* adv_dev, const float* returns_dev, const float* old_value_dev, int64_t n_rollout_rows,
+                     int64_t minibatch_rows, int epochs, double clip, double value_coef, double entropy_coef, int value_clip,
+                     float* params_dev, size_t n_floats, int64_t n_params, float* moments_dev, double* clock_dev, double lr,
+                     double beta1, double beta2, double eps, double max_grad_norm, uint64_t seed, float* stats_dev, void* stream) {
+  const char* name = "mocca_ppo_update";
+  if (int rc = adam_check(h, name, params_dev, n_floats, nullptr, false, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm))
+    return rc;
+  auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
+  const bool sym = h->pol.in_perm != nullptr;   // one entry point: the attached policy decides, as VecEnv.ppo_grad does
+  const long long most = sym ? mocca_ppo::PPO_MAX_ROWS_SYM : mocca_ppo::PPO_MAX_ROWS;
+  if (n_rollout_rows < 1 || n_rollout_rows > most)
+    return bad(std::string("n_rollout_rows must be 1 .. ") + (sym ? "2^21" : "2^22") + ", not " + std::to_string(n_rollout_rows));
+  if (minibatch_rows < 1 || minibatch_rows > n_rollout_rows)
+    return bad("minibatch_rows must be 1 .. n_rollout_rows (" + std::to_string(n_rollout_rows) + "), not " + std::to_string(minibatch_rows));
+  if (epochs < 1) return bad("epochs must be at least 1, not " + std::to_string(epochs));
+  float* const unset = params_dev;   // stands for grad_dev in the check: the gradient buffer is the handle's
+  if (int rc = ppo_grad(h, name, sym, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, nullptr, minibatch_rows,
+                        clip, value_coef, entropy_coef, value_clip, unset, nullptr, stream, true)) return rc;
+  DeviceGuard guard(h->device);
+  const size_t head = optim_head_words(h);
+  if (int rc = grow_scratch(h, name, h->d_optim, &h->optim_cap, head + (size_t)n_rollout_rows)) return rc;
+  float* const grad = (float*)(h->d_optim.get() + mocca_optim::OPT_REC_WORDS);
+  int64_t* const perm = (int64_t*)(h->d_optim.get() + head);
+  mocca_optim::ShuffleArgs sh{};
+  sh.perm = perm; sh.n = (int)n_rollout_rows; sh.half = mocca_optim::shuffle_half(n_rollout_rows); sh.mask = (1u << sh.half) - 1u;
+  sh.seed_lo = (uint32_t)seed; sh.seed_hi = (uint32_t)(seed >> 32); sh.clock = clock_dev;
+  const int64_t per_epoch = n_rollout_rows / minibatch_rows;   // BatchSampler(drop_last=True)
+  for (int ep = 0; ep < epochs; ++ep) {
+    mocca_optim::launch_shuffle((hipStream_t)stream, sh);
+    for (int64_t u = 0; u < per_epoch; ++u) {
+      float* const row = stats_dev ? stats_dev + 8 * ((size_t)ep * per_epoch + u) : nullptr;
+      if (int rc = ppo_grad(h, name, sym, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev,
+                            perm + u * minibatch_rows, minibatch_rows, clip, value_coef, entropy_coef, value_clip, grad, row, stream)) return rc;
+      adam_launch(h, params_dev, n_floats, grad, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm, row, (hipStream_t)stream);
+    }
+  }
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
 }
 
 #ifdef MOCCA_STAMPS

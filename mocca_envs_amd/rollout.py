@@ -1,5 +1,6 @@
 """The end of a PPO rollout: `ObsStats`, the running observation statistics both env surfaces take, and the argument checks of
-`VecEnv.finish_rollout` / `VecEnv.update_obs_stats` (include/mocca.h mocca_gae / mocca_obs_stats).
+`VecEnv.finish_rollout` / `VecEnv.update_obs_stats` (include/mocca.h mocca_gae / mocca_obs_stats); and the update that follows it:
+`AdamState`, the optimiser's state on the device, and the argument checks of `VecEnv.ppo_grad` / `adam_step` / `ppo_update`.
 
 The reference's trainers (SymmetricRL, ALLSTEPS: pytorch-a2c-ppo-acktr) normalise observations with VecNormalize's `ob_rms`, baselines'
 RunningMeanStd: count, mean and variance per feature, merged batch by batch (Chan et al.).  An `ObsStats` holds them as ONE float64 tensor
@@ -177,6 +178,82 @@ def ppo_args(policy, device, obs, action, old_logp, adv, returns, idx, old_value
     stats_out("grad", grad, policy.n_head(), device)
     stats_out("stats", stats, 8, device)
     return n_rows, stride, n_batch
+
+
+class AdamState:
+    """Adam's state for the flat parameter tensor of `update_policy`, on the device (include/mocca.h mocca_adam_step): `moments` float32
+    [2, n_head] -- m, then v -- and `clock` float64 [4] = {t, beta1^t, beta2^t, skipped steps}.  `n_head`: `DevicePolicy.n_head()`."""
+
+    def __init__(self, n_head: int, device):
+        import torch
+        self.n_head = int(n_head)
+        if self.n_head < 1:
+            raise ValueError("n_head must be at least 1")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.moments = torch.empty(2, self.n_head, dtype=torch.float32, device=self.device)
+        self.clock = torch.empty(4, dtype=torch.float64, device=self.device)
+        self.reset()
+
+    def reset(self) -> None:
+        """moments 0, clock {0, 1, 1, 0}"""
+        import torch
+        self.moments.zero_()
+        self.clock.copy_(torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64))
+
+    def state_dict(self) -> dict:
+        """copies on the host, for a checkpoint"""
+        return {"moments": self.moments.detach().cpu().clone(), "clock": self.clock.detach().cpu().clone()}
+
+    def load_state_dict(self, d: dict) -> None:
+        import torch
+        m, c = torch.as_tensor(d["moments"]), torch.as_tensor(d["clock"])
+        if tuple(m.shape) != (2, self.n_head) or tuple(c.shape) != (4,):
+            raise ValueError(f"the state holds moments [2, {self.n_head}] and clock [4]")
+        self.moments.copy_(m.to(torch.float32))
+        self.clock.copy_(c.to(torch.float64))
+
+
+def adam_args(policy, device, params, grad, state, n_params, lr, betas, eps, max_grad_norm):
+    """check the tensors and numbers of adam_step (`grad` None: ppo_update, which owns its gradient) -> n_params; ValueError otherwise"""
+    import torch
+    n_head = policy.n_head()
+    if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.device != device or params.dim() != 1 \
+            or not params.is_contiguous() or params.numel() not in (n_head, n_head + 2 * policy.in_dim):
+        raise ValueError(f"params must be a contiguous float32 [{n_head}] or [{n_head + 2 * policy.in_dim}] tensor on the env's device "
+                         "(DevicePolicy.flat_params()'s order); it is updated in place")
+    n_params = n_head if n_params is None else int(n_params)
+    if not 1 <= n_params <= n_head:
+        raise ValueError(f"n_params must be 1 .. {n_head}")
+    if grad is not None and (not isinstance(grad, torch.Tensor) or grad.dtype != torch.float32 or grad.device != device or grad.dim() != 1
+                             or not grad.is_contiguous() or grad.numel() < n_params):
+        raise ValueError(f"grad must be a contiguous float32 tensor of at least {n_params} elements on the env's device")
+    if not isinstance(state, AdamState) or state.n_head != n_head or state.device != device:
+        raise ValueError(f"state must be an AdamState({n_head}) on the env's device")
+    if not (np.isfinite(float(lr)) and float(lr) >= 0.0 and np.isfinite(float(eps)) and float(eps) >= 0.0):
+        raise ValueError("lr and eps must be finite and not negative")
+    if len(betas) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
+        raise ValueError("betas must be two numbers in [0, 1)")
+    if not float(max_grad_norm) >= 0.0:
+        raise ValueError("max_grad_norm must not be NaN or negative (0: no clip)")
+    return n_params
+
+
+def update_args(n_rows, minibatch_rows, epochs, seed, stats, device, symmetric=False):
+    """check ppo_update's own numbers for R = n_rows rollout rows -> M minibatches per epoch; ValueError otherwise"""
+    most = MAX_MINIBATCH_SYM if symmetric else MAX_MINIBATCH
+    if not 1 <= n_rows <= most:
+        raise ValueError(f"the rollout must have 1 .. {most} rows")
+    if not 1 <= int(minibatch_rows) <= n_rows:
+        raise ValueError(f"minibatch_rows must be 1 .. {n_rows}")
+    if int(epochs) < 1:
+        raise ValueError("epochs must be at least 1")
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed must be 0 .. 2^64 - 1")
+    per_epoch = n_rows // int(minibatch_rows)
+    stats_out("stats", stats, int(epochs) * per_epoch * 8, device)
+    return per_epoch
 
 
 def stats_out(name, t, dim, device):

@@ -376,6 +376,18 @@ class TorchVecEnv:
             raise NotImplementedError("ppo_grad needs one handle (sub_batches=1)")
         return self.venv.ppo_grad(obs, action, old_logp, adv, returns, *args, **kw)
 
+    def adam_step(self, params, grad, state, **kw) -> None:
+        """clip_grad_norm_, Adam's step and update_policy on the flat parameter tensor, three launches: `VecEnv.adam_step`.  One handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("adam_step needs one handle (sub_batches=1)")
+        self.venv.adam_step(params, grad, state, **kw)
+
+    def ppo_update(self, obs, action, old_logp, adv, returns, params, state, minibatch_rows, epochs, **kw) -> dict:
+        """a2c-ppo-acktr's `agent.update(rollouts)` over the rollout storage as one call: `VecEnv.ppo_update`.  One handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("ppo_update needs one handle (sub_batches=1)")
+        return self.venv.ppo_update(obs, action, old_logp, adv, returns, params, state, minibatch_rows, epochs, **kw)
+
     def _act_launch(self, into):
         """the launcher _step_obs() calls: act_step with the policy's outputs going to `into`'s "action" / "logp" / "value" (this object's
         own buffers where a key is missing); sets `self.last_act` to the three tensors written"""

@@ -475,6 +475,54 @@ class VecEnv:
         self._out()
         return {"grad": grad, "stats": stats}
 
+    # ---- the optimiser step and the whole update on the device (include/mocca.h mocca_adam_step / mocca_ppo_update) ----
+    def adam_step(self, params: torch.Tensor, grad: torch.Tensor, state, n_params: Optional[int] = None, lr: float = 3e-4,
+                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5) -> None:
+        """`clip_grad_norm_(.., max_grad_norm)`, `optimizer.step()` of torch.optim.Adam and `update_policy(params)` as three launches.
+        `params`: the flat float32 tensor `update_policy` takes (with or without the statistics tail), updated IN PLACE; its first
+        `n_params` floats are trainable (None: all `policy.n_head()`; `n_head - act_dim` keeps log_std fixed).  `grad`: `ppo_grad`'s
+        gradient.  `state`: a `rollout.AdamState(policy.n_head(), device)`.  `max_grad_norm` 0: no clip.  A gradient whose norm is not
+        finite skips the step and counts it in `state.clock[3]`.  Nothing synchronises; the arithmetic is fixed operation by operation."""
+        if self.policy is None:
+            raise _lib.MoccaError("adam_step needs a policy (set_policy)")
+        n_params = _ro.adam_args(self.policy, self.device, params, grad, state, n_params, lr, betas, eps, max_grad_norm)
+        ptr = lambda x: C.c_void_p(x.data_ptr())
+        self._in()
+        _lib.check(self.lib.mocca_adam_step(self.h, ptr(params), params.numel(), ptr(grad), n_params, ptr(state.moments), ptr(state.clock), float(lr),
+                                            float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm), self._stream()), self.h)
+        self._out()
+
+    def ppo_update(self, obs: torch.Tensor, action: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor, returns: torch.Tensor,
+                   params: torch.Tensor, state, minibatch_rows: int, epochs: int, old_value: Optional[torch.Tensor] = None, clip: float = 0.2,
+                   value_coef: float = 0.5, entropy_coef: float = 0.0, value_clip: bool = False, n_params: Optional[int] = None, lr: float = 3e-4,
+                   betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5, seed: int = 0,
+                   stats: Optional[torch.Tensor] = None) -> dict:
+        """a2c-ppo-acktr's `agent.update(rollouts)` as one call: `epochs` passes over the R rollout rows, each a fresh shuffle cut into
+        M = R // minibatch_rows minibatches (the remainder is dropped), each minibatch `ppo_grad` on its rows and `adam_step` on `params`
+        -- the same bits as that loop.  The storage tensors are `ppo_grad`'s, `params` / `state` / `n_params` / `lr` .. `max_grad_norm`
+        `adam_step`'s; `params` must hold what `update_policy` last received.  The shuffle is keyed by `seed` and the state's step count.
+        -> {"stats": [epochs * M, 8]}: `ppo_grad`'s statistics per minibatch, [6] the clip coefficient applied (0: a skipped step);
+        `stats`: a caller-owned output.  Nothing synchronises or is read on the host; capturable after one warm call of the same shapes
+        (the scalars and the seed are baked into the capture)."""
+        if self.policy is None:
+            raise _lib.MoccaError("ppo_update needs a policy (set_policy)")
+        symmetric = getattr(self.policy, "symmetry", None) is not None
+        n_rows, stride, _ = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, None, old_value, clip, value_coef,
+                                         entropy_coef, value_clip, None, None, symmetric=symmetric)
+        n_params = _ro.adam_args(self.policy, self.device, params, None, state, n_params, lr, betas, eps, max_grad_norm)
+        per_epoch = _ro.update_args(n_rows, minibatch_rows, epochs, seed, stats, self.device, symmetric=symmetric)
+        if stats is None:
+            stats = torch.empty(int(epochs) * per_epoch, 8, dtype=torch.float32, device=self.device)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        self._in()
+        _lib.check(self.lib.mocca_ppo_update(self.h, ptr(obs), stride, ptr(action), ptr(old_logp), ptr(adv), ptr(returns), ptr(old_value), n_rows,
+                                             int(minibatch_rows), int(epochs), float(clip), float(value_coef), float(entropy_coef),
+                                             int(bool(value_clip)), ptr(params), params.numel(), n_params, ptr(state.moments), ptr(state.clock),
+                                             float(lr), float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm), int(seed), ptr(stats),
+                                             self._stream()), self.h)
+        self._out()
+        return {"stats": stats.view(int(epochs) * per_epoch, 8)}
+
     # ---- the reference's env-level setters, batched (env_base.py:103-118, env_locomotion.py:76-77,224-282) ----
     def set_env_params(self, params_dict):
         """`set_env_params({"curriculum": k})`: one value for all envs or one per env (takes effect at each env's next reset; the

@@ -8,7 +8,7 @@ reward / masks / bad_masks straight into the rollout storage (`step(action, into
 No symmetry loss, no curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it SymmetricRL's symmetric network.
 
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
-                           [--device-policy [--device-returns [--device-grad]]] [--symmetric]
+                           [--device-policy [--device-returns [--device-grad [--device-update]]]] [--symmetric]
 --device-policy: collection runs through `envs.act_step(obs[t], into=...)` -- the policy kernel (normalisation, both nets, the sample, its
 log-probability, the value) and the step kernel, two launches per step and no torch op; `envs.update_policy(flat)` once per iteration hands the
 kernel the optimiser's new weights and the running observation statistics.  The noise then comes from the kernel, not from torch.randn.
@@ -21,6 +21,9 @@ only its head is refreshed from the optimiser's parameters.
 `DevicePolicy.flat_params()`'s order (the nn.Linear weights are views into it); each minibatch is one `envs.ppo_grad` on the raw rollout
 storage and the `perm` chunk -- evaluate_actions, the clipped surrogate, the value loss and backward() in four launches --, the global-norm
 clip scales the gradient by its own `stats[5]`, torch.optim.Adam steps the flat parameter and `envs.update_policy(flat)` follows every step.
+--device-update (with --device-grad): the whole learn block is ONE call, `envs.ppo_update` on the flat tensor -- per epoch a shuffle on the
+device, per minibatch the gradient, the global-norm clip, Adam's step (`rollout.AdamState` holds the moments and the step count on the device)
+and the repack --; no torch.randperm, no torch.optim.Adam, nothing read on the host.  --fixed-std keeps log_std out through `n_params`.
 --symmetric: the policy is the mirror-symmetric network built from the env's get_mirror_indices() (`symmetry.SymmetricGaussian` over the same
 `pi`, `vf` and `log_std`): it serves the torch update, torch collection and --verify-grad; with --device-policy the attached policy carries
 `envs.symmetric_policy(...)`'s mirror tables, and with --device-grad each minibatch is one symmetric `ppo_grad` (mocca_ppo_grad_sym).
@@ -59,11 +62,16 @@ def main():
     ap.add_argument("--device-returns", action="store_true", help="GAE, advantage normalisation and observation statistics on the device (finish_rollout, update_obs_stats)")
     ap.add_argument("--verify-returns", action="store_true", help="with --device-returns: also run the torch GAE loop on the same storage and insist on the same bits")
     ap.add_argument("--device-grad", action="store_true", help="with --device-returns: each minibatch's loss and gradient on the device (ppo_grad); the parameters live in one flat tensor")
+    ap.add_argument("--device-update", action="store_true", help="with --device-grad: the whole update -- shuffle, gradient, clip, Adam, repack for every epoch and minibatch -- as one call (ppo_update)")
     ap.add_argument("--symmetric", action="store_true", help="SymmetricRL's symmetric network: mean, value and log_std symmetrised through the env's mirror tables")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args()
     if args.device_grad and not args.device_returns:
         ap.error("--device-grad requires --device-returns")
+    if args.device_update and not args.device_grad:
+        ap.error("--device-update requires --device-grad")
+    if args.device_update and args.verify_grad:
+        ap.error("--verify-grad checks the minibatch loop: not with --device-update")
     if args.verify_grad and not args.device_grad:
         ap.error("--verify-grad requires --device-grad")
     if args.device_returns and not args.device_policy:
@@ -141,9 +149,14 @@ def main():
         for q in head:
             q.data = flat[pos:pos + q.numel()].view_as(q)
             pos += q.numel()
-        w_flat = flat[:n_head].requires_grad_()
-        opt = torch.optim.Adam([w_flat], lr=args.lr, eps=1e-5)
-        g_buf, s_buf = torch.zeros(n_head, device=dev), torch.zeros(8, device=dev)
+        if args.device_update:
+            from mocca_envs_amd.rollout import AdamState
+            adam = AdamState(n_head, dev)      # the optimiser's state lives on the device
+            u_stats = torch.zeros(args.epochs * args.minibatches, 8, device=dev)
+        else:
+            w_flat = flat[:n_head].requires_grad_()
+            opt = torch.optim.Adam([w_flat], lr=args.lr, eps=1e-5)
+            g_buf, s_buf = torch.zeros(n_head, device=dev), torch.zeros(8, device=dev)
 
     S["obs"][0].copy_(envs.reset())
     envs.episode_totals.zero_()
@@ -220,7 +233,12 @@ def main():
         B = N * T
         o_all, a_all, lp_all = norm(S["obs"][:T]).reshape(B, od), S["act"].reshape(B, ad), S["logp"].reshape(B, 1)
         adv_all, ret_all, raw_all = adv.reshape(B, 1), ret.reshape(B, 1), S["obs"][:T].reshape(B, od)
-        for ep in range(args.epochs):
+        if args.device_update:
+            # ppo.update() as one call: epochs x minibatches of [shuffle, ppo_grad, clip, Adam, repack]; u_stats keeps a row per minibatch
+            envs.ppo_update(S["obs"][:T], S["act"], S["logp"], adv, ret, flat, adam, minibatch_rows=B // args.minibatches, epochs=args.epochs,
+                            clip=args.clip, value_coef=0.5, n_params=n_head - ad if args.fixed_std else n_head, lr=args.lr, eps=1e-5,
+                            max_grad_norm=0.5, seed=args.seed, stats=u_stats)
+        for ep in range(0 if args.device_update else args.epochs):
             perm = torch.randperm(B, device=dev)
             for k, mb in enumerate(perm.chunk(args.minibatches)):
                 if args.device_grad:
