@@ -396,9 +396,19 @@ int mocca_height_scan(mocca_handle h, float *out_dev, int row_stride, const floa
  *                       instance -- still one launch, twice the matrix work; their contract holds as it stands (outputs, NULL options, noise
  *                       keying, capture conditions; mean_dev receives mean_sym).  in_perm_host == NULL detaches; mocca_set_policy drops an
  *                       attached symmetry (the shapes may have changed); mocca_update_policy leaves it alone.  May synchronise.
+ * mocca_set_policy_mirror_loss  attaches SymmetricRL's mirror-symmetry LOSS (`--mirror_method loss`, `symmetry_coef`) FOR THE GRADIENT ONLY:
+ *                       the four tables of mocca_set_policy_symmetry under the same validity rules, and mirror_coef, a finite weight
+ *                       >= 0 (0: the term is monitored, not trained on).  The policy stays the plain one: while attached, mocca_act /
+ *                       mocca_act_step launch the plain instance and give the bits they give with nothing attached; mocca_ppo_grad_mirror
+ *                       (below) is the gradient, mocca_ppo_update runs it, and mocca_ppo_grad / mocca_ppo_grad_sym refuse.  The two
+ *                       attachments exclude each other -- a symmetric network has zero mirror loss by construction --: each setter
+ *                       refuses while the other's attachment is in place, the caller detaches first.  in_perm_host == NULL detaches;
+ *                       mocca_set_policy drops the attachment; mocca_update_policy leaves it alone.  A violation (an invalid table, a
+ *                       negative or non-finite mirror_coef, a symmetry attached) is MOCCA_E_ARG with a message and leaves the handle as
+ *                       it was.  May synchronise.
  * Errors (MOCCA_E_ARG, with a message): a NULL handle, any bad dimension, mocca_update_policy / mocca_act / mocca_set_policy_symmetry before
  * mocca_set_policy, mocca_act before mocca_update_policy, n_floats that fits neither form, in_stride < in_dim, mocca_act_step with act_dim other
- * than the env's, an invalid mirror table, global env ids (MOCCA_PARAM_ENV_OFFSET + n_envs) beyond 2^28 (the noise's counter holds 16 x env id
+ * than the env's, an invalid mirror table, a negative or non-finite mirror_coef, either of the two mirror attachments while the other is in place, global env ids (MOCCA_PARAM_ENV_OFFSET + n_envs) beyond 2^28 (the noise's counter holds 16 x env id
  * in one 32-bit word). */
 int mocca_set_policy(mocca_handle h, const int32_t *layers_host, int n_layers_total, int in_dim, int act_dim, double clip);
 int mocca_update_policy(mocca_handle h, const float *params_dev, size_t n_floats, void *stream);
@@ -409,6 +419,8 @@ int mocca_act_step(mocca_handle h, const float *in_dev, int in_stride, const flo
                    void *stream);
 int mocca_set_policy_symmetry(mocca_handle h, const int32_t *in_perm_host, const float *in_sign_host, const int32_t *act_perm_host,
                               const float *act_sign_host);
+int mocca_set_policy_mirror_loss(mocca_handle h, const int32_t *in_perm_host, const float *in_sign_host, const int32_t *act_perm_host,
+                                 const float *act_sign_host, double mirror_coef);
 
 /* ---- the end of a rollout on the device (no reference counterpart: the reference's trainers run these in torch, a Python loop over the
  *      rollout's steps and a handful of reductions per iteration) ---- */
@@ -510,7 +522,8 @@ int mocca_obs_stats(mocca_handle h, const float *rows_dev, int64_t n_rows, int r
  * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): a NULL handle; called before mocca_set_policy / mocca_update_policy; a
  * NULL obs_dev, action_dev, old_logp_dev, adv_dev, returns_dev or grad_dev; value_clip with old_value_dev NULL; n_rows < 1 or > 2^22;
  * obs_stride < in_dim; a non-finite or negative clip, value_coef or entropy_coef; a handle with mirror tables attached
- * (mocca_set_policy_symmetry) -- the symmetric policy's gradient is mocca_ppo_grad_sym: call that, or detach the tables first. */
+ * (mocca_set_policy_symmetry) -- the symmetric policy's gradient is mocca_ppo_grad_sym: call that, or detach the tables first; a handle
+ * with a mirror loss attached (mocca_set_policy_mirror_loss) -- that loss's gradient is mocca_ppo_grad_mirror. */
 int mocca_ppo_grad(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
                    const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
                    double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
@@ -550,10 +563,44 @@ int mocca_ppo_grad(mocca_handle h, const float *obs_dev, int obs_stride, const f
  *                   -- the same inputs give the same bits --, capturable as a linear chain after one warm call with the same B; it sees
  *                   a mocca_update_policy made between two replays; it writes only grad_dev, stats_dev and its scratch.
  * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): those of mocca_ppo_grad with n_rows > 2^21 in place of 2^22; and a
- * policy WITHOUT mirror tables attached (mocca_set_policy_symmetry) -- the plain policy's gradient is mocca_ppo_grad. */
+ * policy WITHOUT mirror tables attached (mocca_set_policy_symmetry) -- the plain policy's gradient is mocca_ppo_grad; a handle with a mirror
+ * loss attached (mocca_ppo_grad_mirror is its gradient). */
 int mocca_ppo_grad_sym(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
                        const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
                        double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
+
+/* mocca_ppo_grad_mirror  mocca_ppo_grad with SymmetricRL's mirror-symmetry loss added (mocca_set_policy_mirror_loss): the PLAIN policy, and an
+ *                   auxiliary term that pulls it towards mirror symmetry, in the same four launches.  The argument list, the arrays,
+ *                   idx_dev (NOT range-checked) and grad_dev's order are mocca_ppo_grad's.  With f1 = actor(n(s)), f2 = actor(n(M_o s))
+ *                   -- the mirror (M x)[k] = sign[k] * x[perm[k]] taken on the RAW row, as in mocca_ppo_grad_sym --, pj = act_perm[j], A =
+ *                   act_dim:
+ *                       L   = L_ppo (mocca_ppo_grad's L of the plain policy) + mirror_coef L_m
+ *                       d_j = f1[j] - act_sign[j] f2[pj]        L_m = 1 / (B A) sum_rows sum_j d_j^2
+ *                   which is torch's `(mirror(actor(mirror_obs)) - actor(obs)).pow(2).mean()`; BOTH passes carry gradient, nothing is
+ *                   detached (a trainer whose loss differs by a constant factor folds it into mirror_coef).  mu = f1, ls = log_std and
+ *                   v = critic(n(s)) are NOT symmetrised: mocca_ppo_grad's per-row lines, log_std's gradient and the entropy apply to
+ *                   them unchanged.  The mirror term per row, each line ONE IEEE f32 operation in this order, never contracted into an
+ *                   FMA; ib as in mocca_ppo_grad:
+ *                       ia = 1.0f / f32(A);  k2 = f32(2 mirror_coef)      (the product in double)
+ *                       for j ascending:   mm = f2[pj] * act_sign[j];  d = f1[j] - mm
+ *                                          q = d * d;  m64 = m64 + f64(q)
+ *                                          u = d * ib;  u = u * ia;  u = u * k2
+ *                                          dL/df1[j] = (g * w) + u          (mocca_ppo_grad's dL/dmu[j] plus u)
+ *                                          dL/df2[pj] = -(u * act_sign[j])  (each pj is written once: act_perm is a bijection)
+ *                       the row's mirror term = f32(m64) * ia
+ *                   Both actor passes run mocca_ppo_grad's backward and every actor weight's and bias's gradient is the sum over both, as
+ *                   in mocca_ppo_grad_sym.  The critic receives NO mirror term: its mirrored columns hold zeros and contribute exactly
+ *                   nothing to any gradient.  stats_dev [8]: [0..5] keep mocca_ppo_grad's meanings, [6] = 0, [7] = L_m -- the rows' mirror
+ *                   terms summed in f64 like the other statistics (row chunks in chunk order), times ib.
+ *                   Scratch, the n_rows bound (2^21), the grow-FREES-the-old rule and the capture conditions are mocca_ppo_grad_sym's: twice
+ *                   the plain call's scratch per row, shared with the other two calls; a captured call holds the attachment's device
+ *                   tables, and mirror_coef is a kernel argument, BAKED INTO a captured call: mocca_set_policy_mirror_loss and
+ *                   mocca_set_policy ask for a new capture.
+ * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): those of mocca_ppo_grad with n_rows > 2^21 in place of 2^22; and a
+ * handle WITHOUT a mirror loss attached (mocca_set_policy_mirror_loss). */
+int mocca_ppo_grad_mirror(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
+                          const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
+                          double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
 
 /* ---- PPO's optimiser step and update loop on the device (no reference counterpart: the reference's trainers run clip_grad_norm_, Adam and
  *      the minibatch loop in torch and Python) ---- */
@@ -598,7 +645,8 @@ int mocca_adam_step(mocca_handle h, float *params_dev, size_t n_floats, const fl
  *                   remainder dropped (`BatchSampler(.., drop_last=True)`).  The arrays obs_dev .. old_value_dev, clip, value_coef,
  *                   entropy_coef and value_clip are mocca_ppo_grad's; params_dev .. max_grad_norm are mocca_adam_step's.  Per epoch ONE
  *                   launch fills a handle-owned i64 [R] with a permutation of 0 .. R - 1; per minibatch u follow the four launches of
- *                   mocca_ppo_grad -- of mocca_ppo_grad_sym when the policy has mirror tables attached: this entry point serves both --
+ *                   mocca_ppo_grad -- of mocca_ppo_grad_sym when the policy has mirror tables attached, of mocca_ppo_grad_mirror when a
+ *                   mirror loss is attached: this entry point serves all three --
  *                   with idx_dev = that array + u B and a handle-owned gradient [n_head], then mocca_adam_step's three launches on it.
  *                   The result is, bit for bit, what that sequence of calls gives.
  *                   The permutation is closed-form and defined in integers: w = max(2, bit_length(R - 1)) rounded up to even,
@@ -609,15 +657,16 @@ int mocca_adam_step(mocca_handle h, float *params_dev, size_t n_floats, const fl
  *                   walk returns below R and the entries are a bijection of 0 .. R - 1.  t is clock_dev[0] as the fill kernel READS IT ON
  *                   THE DEVICE when the epoch starts: a replayed graph shuffles anew, and a fresh clock with the same seed repeats a run.
  *                   stats_dev [epochs M][8] f32 or NULL: row k holds the k-th minibatch's mocca_ppo_grad statistics, with [6] overwritten
- *                   by the clip coefficient applied (0 on a skipped step) and [7] left 0; the trainer's `value_loss_epoch` etc. are the
+ *                   by the clip coefficient applied (0 on a skipped step) and [7] left as the gradient call wrote it (L_m with a mirror loss attached, else
+ *                   0); the trainer's `value_loss_epoch` etc. are the
  *                   rows' mean, and the rows' [3] is what a KL monitor reads.
  *                   params_dev must hold what mocca_update_policy (or mocca_adam_step) last wrote.  mocca_ppo_grad's conditions hold as
  *                   they stand -- growing either scratch FREES the old one: warm the handle with the largest B and R it will see --; the
  *                   call is a linear chain of epochs (1 + 7 M) launches on `stream`, capturable after one warm call of the same shapes,
  *                   with mocca_adam_step's scalars and `seed` baked in.
  * Errors (MOCCA_E_ARG, with a message; the handle is left as it was and nothing is launched): those of mocca_adam_step and of mocca_ppo_grad
- * (/ mocca_ppo_grad_sym) but for their grad_dev and idx_dev; minibatch_rows outside 1 .. n_rollout_rows; epochs < 1; n_rollout_rows < 1 or
- * beyond mocca_ppo_grad's bound (2^22, with mirror tables 2^21). */
+ * (/ mocca_ppo_grad_sym / mocca_ppo_grad_mirror) but for their grad_dev and idx_dev; minibatch_rows outside 1 .. n_rollout_rows; epochs < 1; n_rollout_rows < 1 or
+ * beyond mocca_ppo_grad's bound (2^22, with mirror tables or a mirror loss 2^21). */
 int mocca_ppo_update(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
                      const float *adv_dev, const float *returns_dev, const float *old_value_dev, int64_t n_rollout_rows,
                      int64_t minibatch_rows, int epochs, double clip, double value_coef, double entropy_coef, int value_clip,

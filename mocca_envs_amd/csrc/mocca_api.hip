@@ -166,6 +166,9 @@ struct mocca_ctx {
   int pol_wt_off[mocca_ppo::PPO_MAX_TABLE] = {};   // the layers' transposed copies in the image (mocca_ppo.h), -1: none
   DevBuf<int32_t> d_pol_sym_perm;    // mocca_set_policy_symmetry: in_perm [in_dim] then act_perm [act_dim]; pol.in_perm / act_perm point into it
   DevBuf<float> d_pol_sym_sign;      // in_sign [in_dim] then act_sign [act_dim]
+  DevBuf<int32_t> d_pol_ml_perm;     // mocca_set_policy_mirror_loss: the same two layouts, read by mocca_ppo_grad_mirror ALONE (pol stays plain)
+  DevBuf<float> d_pol_ml_sign;
+  double pol_ml_coef = 0.0;          // mirror_coef; meaningful while d_pol_ml_perm is set
   // scratch of mocca_gae / mocca_obs_stats (mocca_rollout.h), owned by the handle, grown on demand
   DevBuf<double> d_gae_part;         // [blocks][2]
   size_t gae_part_cap = 0;           // doubles
@@ -1068,6 +1071,12 @@ static void drop_policy_symmetry(mocca_handle h) {
   h->pol.in_sign = h->pol.act_sign = nullptr;
 }
 
+// detach the mirror loss (mocca_set_policy_mirror_loss); as above
+static void drop_policy_mirror_loss(mocca_handle h) {
+  h->d_pol_ml_perm.reset(); h->d_pol_ml_sign.reset();
+  h->pol_ml_coef = 0.0;
+}
+
 int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) try {
   using namespace mocca_pol;
   if (!h) return MOCCA_E_ARG;
@@ -1076,6 +1085,7 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
     if (int rc = commit_ready(h, "mocca_set_policy")) return rc;
     h->d_pol_image.reset(); h->d_pol_layers.reset(); h->pol_filled = false;
     drop_policy_symmetry(h);
+    drop_policy_mirror_loss(h);
     return MOCCA_OK;
   }
   auto bad = [&](const std::string& what) { h->err = "mocca_set_policy: " + what; return MOCCA_E_ARG; };
@@ -1095,6 +1105,7 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
   h->pol_tail_row = im.tail_row; h->pol_table.swap(im.table);
   std::memcpy(h->pol_wt_off, im.wt_off, sizeof(im.wt_off));
   drop_policy_symmetry(h);   // the shapes may have changed
+  drop_policy_mirror_loss(h);
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy"); }
 
@@ -1113,6 +1124,26 @@ static std::string check_mirror_table(const int32_t* perm, const float* sign, in
   return "";
 }
 
+// The four mirror tables of a policy, checked and copied to the device: perm = in_perm [in_dim] then act_perm [act_dim], sign likewise.
+// -> "" with *e set (the copies' status), or what is wrong with the tables (nothing allocated).
+static std::string upload_mirror_tables(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
+                                        const float* act_sign_host, DevBuf<int32_t>& d_perm, DevBuf<float>& d_sign, hipError_t* e) {
+  if (!in_sign_host || !act_perm_host || !act_sign_host) return "in_sign_host, act_perm_host and act_sign_host must not be NULL";
+  const int in_dim = h->pol.in_dim, act_dim = h->pol.act_dim;
+  std::string wrong = check_mirror_table(in_perm_host, in_sign_host, in_dim, "in_perm", "in_sign");
+  if (wrong.empty()) wrong = check_mirror_table(act_perm_host, act_sign_host, act_dim, "act_perm", "act_sign");
+  if (!wrong.empty()) return wrong;
+  std::vector<int32_t> perm(in_perm_host, in_perm_host + in_dim);
+  perm.insert(perm.end(), act_perm_host, act_perm_host + act_dim);
+  std::vector<float> sign(in_sign_host, in_sign_host + in_dim);
+  sign.insert(sign.end(), act_sign_host, act_sign_host + act_dim);
+  *e = d_perm.alloc(perm.size(), false);
+  if (*e == hipSuccess) *e = d_sign.alloc(sign.size(), false);
+  if (*e == hipSuccess) *e = hipMemcpy(d_perm, perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (*e == hipSuccess) *e = hipMemcpy(d_sign, sign.data(), sign.size() * sizeof(float), hipMemcpyHostToDevice);
+  return "";
+}
+
 int mocca_set_policy_symmetry(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
                               const float* act_sign_host) try {
   if (!h) return MOCCA_E_ARG;
@@ -1124,27 +1155,45 @@ int mocca_set_policy_symmetry(mocca_handle h, const int32_t* in_perm_host, const
     drop_policy_symmetry(h);
     return MOCCA_OK;
   }
-  if (!in_sign_host || !act_perm_host || !act_sign_host) return bad("in_sign_host, act_perm_host and act_sign_host must not be NULL");
-  const int in_dim = h->pol.in_dim, act_dim = h->pol.act_dim;
-  std::string wrong = check_mirror_table(in_perm_host, in_sign_host, in_dim, "in_perm", "in_sign");
-  if (wrong.empty()) wrong = check_mirror_table(act_perm_host, act_sign_host, act_dim, "act_perm", "act_sign");
-  if (!wrong.empty()) return bad(wrong);
-  std::vector<int32_t> perm(in_perm_host, in_perm_host + in_dim);
-  perm.insert(perm.end(), act_perm_host, act_perm_host + act_dim);
-  std::vector<float> sign(in_sign_host, in_sign_host + in_dim);
-  sign.insert(sign.end(), act_sign_host, act_sign_host + act_dim);
+  if (h->d_pol_ml_perm)
+    return bad("a mirror loss is attached (mocca_set_policy_mirror_loss): a symmetric network has no mirror loss, detach it first");
   DevBuf<int32_t> d_perm;
   DevBuf<float> d_sign;
-  hipError_t e = d_perm.alloc(perm.size(), false);
-  if (e == hipSuccess) e = d_sign.alloc(sign.size(), false);
-  if (e == hipSuccess) e = hipMemcpy(d_perm, perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_sign, sign.data(), sign.size() * sizeof(float), hipMemcpyHostToDevice);
+  hipError_t e = hipSuccess;
+  const std::string wrong = upload_mirror_tables(h, in_perm_host, in_sign_host, act_perm_host, act_sign_host, d_perm, d_sign, &e);
+  if (!wrong.empty()) return bad(wrong);
   if (int rc = commit_ready(h, "mocca_set_policy_symmetry", e)) return rc;
+  const int in_dim = h->pol.in_dim;
   h->d_pol_sym_perm.swap(d_perm); h->d_pol_sym_sign.swap(d_sign);
   h->pol.in_perm = h->d_pol_sym_perm; h->pol.act_perm = h->d_pol_sym_perm.get() + in_dim;
   h->pol.in_sign = h->d_pol_sym_sign; h->pol.act_sign = h->d_pol_sym_sign.get() + in_dim;
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy_symmetry"); }
+
+int mocca_set_policy_mirror_loss(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
+                                 const float* act_sign_host, double mirror_coef) try {
+  if (!h) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  auto bad = [&](const std::string& what) { h->err = "mocca_set_policy_mirror_loss: " + what; return MOCCA_E_ARG; };
+  if (!h->d_pol_image) return bad("needs a policy (mocca_set_policy)");
+  if (!in_perm_host) {   // detach
+    if (int rc = commit_ready(h, "mocca_set_policy_mirror_loss")) return rc;
+    drop_policy_mirror_loss(h);
+    return MOCCA_OK;
+  }
+  if (h->pol.in_perm)
+    return bad("the policy is mirror-symmetric (mocca_set_policy_symmetry): its mirror loss is zero by construction, detach the symmetry first");
+  if (!std::isfinite(mirror_coef) || mirror_coef < 0.0) return bad("mirror_coef must be finite and not negative");
+  DevBuf<int32_t> d_perm;
+  DevBuf<float> d_sign;
+  hipError_t e = hipSuccess;
+  const std::string wrong = upload_mirror_tables(h, in_perm_host, in_sign_host, act_perm_host, act_sign_host, d_perm, d_sign, &e);
+  if (!wrong.empty()) return bad(wrong);
+  if (int rc = commit_ready(h, "mocca_set_policy_mirror_loss", e)) return rc;
+  h->d_pol_ml_perm.swap(d_perm); h->d_pol_ml_sign.swap(d_sign);
+  h->pol_ml_coef = mirror_coef;
+  return MOCCA_OK;
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy_mirror_loss"); }
 
 // what n_floats of a flat parameter tensor must be (mocca_update_policy, mocca_adam_step): -> "" or what is wrong
 static std::string check_n_floats(mocca_handle h, size_t n_floats) {
@@ -1287,8 +1336,14 @@ int mocca_obs_stats(mocca_handle h, const float* rows_dev, int64_t n_rows, int r
   return MOCCA_OK;
 }
 
-// mocca_ppo_grad (sym == false) and mocca_ppo_grad_sym (sym == true): one argument list, one scratch, the same four launches
-static int ppo_grad(mocca_handle h, const char* name, bool sym, const float* obs_dev, int obs_stride, const float* action_dev,
+// what the handle's attachments make mocca_ppo_update differentiate: the mirror loss, the symmetric network, or the plain policy
+static mocca_ppo::PpoMode ppo_mode(mocca_handle h) {
+  return h->d_pol_ml_perm ? mocca_ppo::PPO_MIRROR : h->pol.in_perm ? mocca_ppo::PPO_SYM : mocca_ppo::PPO_PLAIN;
+}
+
+// mocca_ppo_grad (PPO_PLAIN), mocca_ppo_grad_sym (PPO_SYM) and mocca_ppo_grad_mirror (PPO_MIRROR): one argument list, one scratch, the same
+// four launches; the last two share the two-column scratch layout (mocca_ppo.h)
+static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, const float* obs_dev, int obs_stride, const float* action_dev,
                     const float* old_logp_dev, const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev,
                     int64_t n_rows, double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev,
                     void* stream, bool check_only = false) {   // check_only: the refusals alone (mocca_ppo_update asks before its first launch)
@@ -1297,9 +1352,14 @@ static int ppo_grad(mocca_handle h, const char* name, bool sym, const float* obs
   if (!h) { g_err = std::string(name) + ": NULL handle"; return MOCCA_E_ARG; }
   auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
   if (!h->d_pol_image || !h->pol_filled) return bad("needs a policy (mocca_set_policy, then mocca_update_policy)");
-  if (!sym && h->pol.in_perm)
+  const bool sym = mode != PPO_PLAIN;   // twice the columns
+  if (mode != PPO_MIRROR && h->d_pol_ml_perm)
+    return bad("a mirror loss is attached: the gradient of PPO's loss with the mirror term is mocca_ppo_grad_mirror (or detach it: mocca_set_policy_mirror_loss)");
+  if (mode == PPO_MIRROR && !h->d_pol_ml_perm)
+    return bad("needs a mirror loss attached (mocca_set_policy_mirror_loss); the plain loss's gradient is mocca_ppo_grad");
+  if (mode == PPO_PLAIN && h->pol.in_perm)
     return bad("the policy has mirror tables attached: the symmetric policy's gradient is mocca_ppo_grad_sym (or detach the tables: mocca_set_policy_symmetry)");
-  if (sym && !h->pol.in_perm) return bad("needs a policy with mirror tables attached (mocca_set_policy_symmetry); the plain policy's gradient is mocca_ppo_grad");
+  if (mode == PPO_SYM && !h->pol.in_perm) return bad("needs a policy with mirror tables attached (mocca_set_policy_symmetry); the plain policy's gradient is mocca_ppo_grad");
   if (!obs_dev || !action_dev || !old_logp_dev || !adv_dev || !returns_dev || !grad_dev)
     return bad("obs_dev, action_dev, old_logp_dev, adv_dev, returns_dev and grad_dev must not be NULL");
   if (value_clip && !old_value_dev) return bad("value_clip needs old_value_dev");
@@ -1316,7 +1376,13 @@ static int ppo_grad(mocca_handle h, const char* name, bool sym, const float* obs
   a.log_std_off = p.log_std_off; a.flags_off = p.flags_off; a.mean_off = p.mean_off; a.inv_std_off = p.inv_std_off;
   a.in_dim = p.in_dim; a.in_pad = p.in_pad; a.act_dim = p.act_dim; a.norm_clip = p.clip;
   std::memcpy(a.wt_off, h->pol_wt_off, sizeof(a.wt_off));
-  if (sym) { a.in_perm = p.in_perm; a.in_sign = p.in_sign; a.act_perm = p.act_perm; a.act_sign = p.act_sign; }
+  a.mode = mode;
+  if (mode == PPO_SYM) { a.in_perm = p.in_perm; a.in_sign = p.in_sign; a.act_perm = p.act_perm; a.act_sign = p.act_sign; }
+  if (mode == PPO_MIRROR) {
+    a.in_perm = h->d_pol_ml_perm; a.act_perm = h->d_pol_ml_perm.get() + p.in_dim;
+    a.in_sign = h->d_pol_ml_sign; a.act_sign = h->d_pol_ml_sign.get() + p.in_dim;
+    a.mirror_k2 = (float)(2.0 * h->pol_ml_coef);
+  }
   a.obs = obs_dev; a.obs_stride = obs_stride; a.action = action_dev; a.old_logp = old_logp_dev; a.adv = adv_dev; a.returns = returns_dev;
   a.old_value = old_value_dev; a.idx = idx_dev;
   a.n_rows = (int)n_rows;
@@ -1353,15 +1419,22 @@ static int ppo_grad(mocca_handle h, const char* name, bool sym, const float* obs
 int mocca_ppo_grad(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev, const float* adv_dev,
                    const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev, int64_t n_rows, double clip, double value_coef,
                    double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
-  return ppo_grad(h, "mocca_ppo_grad", false, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, idx_dev, n_rows, clip,
+  return ppo_grad(h, "mocca_ppo_grad", mocca_ppo::PPO_PLAIN, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, idx_dev, n_rows, clip,
                   value_coef, entropy_coef, value_clip, grad_dev, stats_dev, stream);
 }
 
 int mocca_ppo_grad_sym(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev,
                        const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev, int64_t n_rows, double clip,
                        double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
-  return ppo_grad(h, "mocca_ppo_grad_sym", true, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, idx_dev, n_rows,
+  return ppo_grad(h, "mocca_ppo_grad_sym", mocca_ppo::PPO_SYM, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, idx_dev, n_rows,
                   clip, value_coef, entropy_coef, value_clip, grad_dev, stats_dev, stream);
+}
+
+int mocca_ppo_grad_mirror(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev,
+                          const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev, int64_t n_rows,
+                          double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
+  return ppo_grad(h, "mocca_ppo_grad_mirror", mocca_ppo::PPO_MIRROR, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev,
+                  idx_dev, n_rows, clip, value_coef, entropy_coef, value_clip, grad_dev, stats_dev, stream);
 }
 
 // the refusals of mocca_adam_step's arguments (mocca_ppo_update shares them): -> MOCCA_OK, or MOCCA_E_ARG with the message set
@@ -1419,7 +1492,8 @@ int mocca_ppo_update(mocca_handle h, const float* obs_dev, int obs_stride, const
   if (int rc = adam_check(h, name, params_dev, n_floats, nullptr, false, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm))
     return rc;
   auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
-  const bool sym = h->pol.in_perm != nullptr;   // one entry point: the attached policy decides, as VecEnv.ppo_grad does
+  const mocca_ppo::PpoMode mode = ppo_mode(h);   // one entry point: the handle's attachments decide, as VecEnv.ppo_grad does
+  const bool sym = mode != mocca_ppo::PPO_PLAIN;
   const long long most = sym ? mocca_ppo::PPO_MAX_ROWS_SYM : mocca_ppo::PPO_MAX_ROWS;
   if (n_rollout_rows < 1 || n_rollout_rows > most)
     return bad(std::string("n_rollout_rows must be 1 .. ") + (sym ? "2^21" : "2^22") + ", not " + std::to_string(n_rollout_rows));
@@ -1427,7 +1501,7 @@ int mocca_ppo_update(mocca_handle h, const float* obs_dev, int obs_stride, const
     return bad("minibatch_rows must be 1 .. n_rollout_rows (" + std::to_string(n_rollout_rows) + "), not " + std::to_string(minibatch_rows));
   if (epochs < 1) return bad("epochs must be at least 1, not " + std::to_string(epochs));
   float* const unset = params_dev;   // stands for grad_dev in the check: the gradient buffer is the handle's
-  if (int rc = ppo_grad(h, name, sym, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, nullptr, minibatch_rows,
+  if (int rc = ppo_grad(h, name, mode, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, nullptr, minibatch_rows,
                         clip, value_coef, entropy_coef, value_clip, unset, nullptr, stream, true)) return rc;
   DeviceGuard guard(h->device);
   const size_t head = optim_head_words(h);
@@ -1442,7 +1516,7 @@ int mocca_ppo_update(mocca_handle h, const float* obs_dev, int obs_stride, const
     mocca_optim::launch_shuffle((hipStream_t)stream, sh);
     for (int64_t u = 0; u < per_epoch; ++u) {
       float* const row = stats_dev ? stats_dev + 8 * ((size_t)ep * per_epoch + u) : nullptr;
-      if (int rc = ppo_grad(h, name, sym, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev,
+      if (int rc = ppo_grad(h, name, mode, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev,
                             perm + u * minibatch_rows, minibatch_rows, clip, value_coef, entropy_coef, value_clip, grad, row, stream)) return rc;
       adam_launch(h, params_dev, n_floats, grad, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm, row, (hipStream_t)stream);
     }

@@ -1,6 +1,6 @@
 // mocca_ppo.h -- the body of a PPO minibatch step up to optimizer.step() as kernels (mocca_ppo.hip): evaluate_actions, the clipped
-// surrogate, the value loss and loss.backward() for the Gaussian actor-critic of mocca_policy.h, plain or mirror-symmetric.  mocca_ppo_grad /
-// mocca_ppo_grad_sym (mocca_api.hip) check the caller's arguments, own the scratch and launch them.  The loss and the per-row formulas: include/mocca.h.
+// surrogate, the value loss and loss.backward() for the Gaussian actor-critic of mocca_policy.h, plain, mirror-symmetric, or plain with the
+// mirror-symmetry loss added.  mocca_ppo_grad / mocca_ppo_grad_sym / mocca_ppo_grad_mirror (mocca_api.hip) check the caller's arguments, own the scratch and launch them.  The loss and the per-row formulas: include/mocca.h.
 //
 // Image.  The kernels read the policy image of mocca_policy.h and, behind it, a SECOND copy of every layer's weights but a net's first,
 // transposed: layer l's W[out][in] as the [in_pad / 16][out_pad / 16][64][4] fragment order of W^T (in and out swap roles and padding), so
@@ -12,7 +12,7 @@
 //   A[l]    [B_pad][out_pad_l]            layer l's output activation y
 //   dZ[l]   [B_pad][out_pad_l]            dL/d(pre-activation) of layer l; between the forward and the backward: act'(x) of layer l
 //   R       [B_pad][PPO_ROW_COLS]         per row: 0 .. 31 the log_std gradient terms, 32 surrogate, 33 value loss, 34 old_logp - logp,
-//                                         35 clipped (0 / 1), 36 .. 47 zeros
+//                                         35 clipped (0 / 1), 36 the mirror term (mirror loss; else 0), 37 .. 47 zeros
 //   P       [n_chunks][p_floats]          chunk partials of the padded gradient: a layer's dW[out_pad][in_pad] row-major at the image's
 //                                         w_off, its db[out_pad] at b_off, the column sums of R at log_std_off
 //   Q       [reduce blocks] f64           sums of grad^2 of the reduce kernel's workgroups
@@ -44,7 +44,16 @@
 // each head its half (include/mocca.h); R's terms go to the as-given column's row, the mirrored column's R row and every row of a column
 // without a minibatch row are zeros.  Launch 2 is unchanged: summing dZ^T A over the scratch rows adds both passes' weight gradients, in
 // scratch-row order.  Launch 3 forms log_std's entries as 0.5f * (T[j] + T[act_perm[j]]) from the chunk sums T; launch 4 takes the entropy
-// of the symmetrised log_std.  Both read PpoArgs.act_perm; null selects the plain arithmetic.
+// of the symmetrised log_std.  Both select that arithmetic by PpoArgs.mode == PPO_SYM.
+//
+// Mirror loss (mocca_ppo_grad_mirror; include/mocca.h).  The PLAIN policy with w mean_rows mean_j (f1[j] - act_sign[j] f2[act_perm[j]])^2 added
+// to the loss, f2 the actor on the mirror image.  ppo_rows_kernel<PPO_MIRROR> is the symmetric instance -- its staging, column layout,
+// scratch-row ownership, B_pad, layer loop and backward loop -- with another head stage: lane c < 8 runs the plain per-row lines on the
+// as-given column's heads (mean f1, log_std and value un-symmetrised), adds the mirror term's gradient u to dL/df1 and hands the mirrored
+// actor column -(u * act_sign) through act_perm; the row's term goes to column 36 of R.  The critic has no mirror term: its workgroups still
+// stage 8 + 8 columns, but the mirrored ones are NOT LIVE -- zero activations and zero slopes stored, zero dA --, so their scratch rows add
+// exactly nothing to the critic's dW and db in launch 2.  Launches 3 and 4 use the plain log_std arithmetic (mode, not the tables, selects
+// it); launch 4 writes stats[7] = (column 36's sum) * ib, which the other modes leave 0.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,7 +63,8 @@
 namespace mocca_ppo {
 
 constexpr int PPO_ROW_COLS = 48;         // floats per row of R
-constexpr int PPO_COL_SURR = 32, PPO_COL_VLOSS = 33, PPO_COL_DLOGP = 34, PPO_COL_CLIPPED = 35;
+constexpr int PPO_COL_SURR = 32, PPO_COL_VLOSS = 33, PPO_COL_DLOGP = 34, PPO_COL_CLIPPED = 35, PPO_COL_MIRROR = 36;
+enum PpoMode { PPO_PLAIN = 0, PPO_SYM = 1, PPO_MIRROR = 2 };   // mocca_ppo_grad, mocca_ppo_grad_sym, mocca_ppo_grad_mirror
 constexpr int PPO_MAX_CHUNKS = 16;       // row chunks of launch 2
 constexpr int PPO_CHUNK_MIN_ROWS = 512;  // a chunk holds at least this many rows
 constexpr int PPO_REDUCE_BLOCK = 256;
@@ -72,9 +82,11 @@ struct PpoArgs {
   int in_dim, in_pad, act_dim;
   float norm_clip;
   int wt_off[PPO_MAX_TABLE];             // transposed copies (header: Image)
-  // the mirror tables (mocca_policy.h: Symmetry), device; in_perm null: the plain policy
+  // the mirror tables (mocca_policy.h: Symmetry), device; null in PPO_PLAIN.  mode, not the tables, selects every kernel's arithmetic
   const int32_t *in_perm, *act_perm;     // [in_dim], [act_dim]
   const float *in_sign, *act_sign;
+  int mode;                              // PpoMode
+  float mirror_k2;                       // PPO_MIRROR: f32(2 mirror_coef)
   // the minibatch
   const float* obs; int obs_stride;
   const float *action, *old_logp, *adv, *returns, *old_value;

@@ -1,5 +1,6 @@
-// mocca_ppo.hip -- PPO's minibatch loss and its gradient with respect to every parameter of the Gaussian actor-critic, plain (mocca_ppo_grad)
-// or mirror-symmetric (mocca_ppo_grad_sym), on the device.  What each launch does, the scratch and the transposed weight copy: mocca_ppo.h.
+// mocca_ppo.hip -- PPO's minibatch loss and its gradient with respect to every parameter of the Gaussian actor-critic, plain (mocca_ppo_grad),
+// mirror-symmetric (mocca_ppo_grad_sym) or plain with the mirror-symmetry loss added (mocca_ppo_grad_mirror), on the device.  What each launch
+// does, the scratch and the transposed weight copy: mocca_ppo.h.
 // The loss and the per-row formulas: include/mocca.h.
 //
 // Arithmetic: the policy kernel's (mocca_policy.hip).  The layer loop below is that kernel's loop, copied -- mocca_policy.hip's kernel is left
@@ -90,12 +91,17 @@ __device__ __forceinline__ void mfma_layer(const f32x4* W, int nkg, int n_ot, co
     if (t < nt_w) epi((wave + 4 * t) * 16 + quad * 4, (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]));
 }
 
-// SYM (header: Symmetry): the 16 MFMA columns are PPO_SYM_TILE = 8 minibatch rows x {as given, mirrored} -- policy_kernel<true>'s layout:
-// column c is row row0 + c, column 8 + c its mirror image -- and column e's activations live in scratch row 16 * tile + e.  The plain
-// instance has one column per row and scratch row = minibatch row.
-template <bool SYM>
+// MODE (header: Symmetric policy, Mirror loss).  PPO_SYM and PPO_MIRROR (SYM below): the 16 MFMA columns are PPO_SYM_TILE = 8 minibatch rows x
+// {as given, mirrored} -- policy_kernel<true>'s layout: column c is row row0 + c, column 8 + c its mirror image -- and column e's activations
+// live in scratch row 16 * tile + e.  The plain instance has one column per row and scratch row = minibatch row.
+// PPO_SYM's head stage symmetrises mean, log_std and value over the two columns; PPO_MIRROR's leaves the policy the as-given column's and
+// adds the mirror term over the actor's two columns, and its critic's mirrored columns are not live.
+template <int MODE>
 __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
   __shared__ __attribute__((aligned(16))) float X[2][TILE * LDS_STRIDE];
+  constexpr bool SYM = MODE != PPO_PLAIN;     // the two-column layout
+  constexpr bool NET = MODE == PPO_SYM;       // the symmetric network's head stage
+  constexpr bool ML = MODE == PPO_MIRROR;     // the mirror loss's head stage
   constexpr int ROWS = SYM ? PPO_SYM_TILE : TILE;   // minibatch rows of a workgroup
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row0 = blockIdx.x * ROWS, srow0 = blockIdx.x * TILE, net = blockIdx.y;
@@ -124,7 +130,8 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
   __syncthreads();
 
   const int first = net == 0 ? 0 : a.n_actor, count = net == 0 ? a.n_actor : a.n_critic;
-  const bool live = row0 + (SYM ? col & (ROWS - 1) : col) < B;   // this lane's MFMA column is a row of the minibatch (SYM: or its mirror image)
+  // this lane's MFMA column is a row of the minibatch (SYM: or its mirror image; ML: the critic has no use for the mirror image)
+  const bool live = row0 + (SYM ? col & (ROWS - 1) : col) < B && !(ML && net == 1 && col >= ROWS);
   int cur = 0;
 #pragma unroll 1
   for (int li = 0; li < count; ++li) {
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
 
   // head stage: one lane per row -> the row's loss terms (R) and dL/dhead, the backward's first dA, in the other LDS buffer.  SYM: the
   // row's lane reads the heads of its two columns and writes dA for both; R's terms go to the as-given column's scratch row, the lane of
-  // the mirrored column zeroes that column's R row
+  // the mirrored column zeroes that column's R row.  ML: the critic's lane reads its as-given column alone and hands the mirrored one zeros
   if (tid < TILE) {
     const int row = row0 + (SYM ? tid & (ROWS - 1) : tid);
     float* R = a.scratch + a.r_off + (size_t)(srow0 + tid) * PPO_ROW_COLS;
@@ -169,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
       if (net == 1) {
         float dv = 0.0f, vloss = 0.0f;
         if (row < B) {   // include/mocca.h: one f32 operation per line of it, in that order
-          const float v = SYM ? 0.5f * (head[0] + mirror[0]) : head[0], ret = a.returns[src];
+          const float v = NET ? 0.5f * (head[0] + mirror[0]) : head[0], ret = a.returns[src];
           const float e = v - ret;
           float l = e * e;
           dv = e;
@@ -189,19 +196,19 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
           vloss = 0.5f * l;
           dv = a.value_coef * dv;
           dv = dv * a.inv_b;
-          if (SYM) dv = 0.5f * dv;   // dL/dv1 = dL/dv2
+          if (NET) dv = 0.5f * dv;   // dL/dv1 = dL/dv2
         }
         R[PPO_COL_VLOSS] = vloss;
         for (int j = 0; j < head_pad; ++j) {
           dA[j] = j == 0 ? dv : 0.0f;
-          if (SYM) dAm[j] = j == 0 ? dv : 0.0f;
+          if (SYM) dAm[j] = NET && j == 0 ? dv : 0.0f;
         }
       } else {
         const float* log_std = a.params + a.log_std_off;
         const int A = a.act_dim;
-        // the Gaussian of action j: its mean (returned) and log_std.  SYM: the symmetrised ones of mocca_policy.h, one f32 operation each
+        // the Gaussian of action j: its mean (returned) and log_std.  NET: the symmetrised ones of mocca_policy.h, one f32 operation each
         auto gaussian = [&](int j, float* ls) {
-          if (SYM) {
+          if (NET) {
             const int pj = a.act_perm[j];
             const float mm = mirror[pj] * a.act_sign[j];
             *ls = 0.5f * (log_std[j] + log_std[pj]);
@@ -240,6 +247,8 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
         }
         if (SYM)   // every act_perm[j] below is written once more (a bijection of 0 .. A - 1); the padding stays 0
           for (int j = 0; j < head_pad; ++j) dAm[j] = 0.0f;
+        const float ia = 1.0f / (float)A;
+        double m64 = 0.0;   // ML: the row's sum of d_j^2, the terms f32
         for (int j = 0; j < head_pad || j < POL_MAX_ACTION; ++j) {
           float dmu = 0.0f, dls = 0.0f;
           if (row < B && j < A) {
@@ -252,16 +261,31 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
             dmu = g * w;
             const float q = z * z - 1.0f;
             dls = g * q;
-            if (SYM) {   // dL/df1[j] = h, dL/df2[pj] = h * act_sign[j]
+            if (NET) {   // dL/df1[j] = h, dL/df2[pj] = h * act_sign[j]
               dmu = 0.5f * dmu;
               dAm[a.act_perm[j]] = dmu * a.act_sign[j];
+            }
+            if (ML) {   // include/mocca.h: the mirror term's lines, one f32 operation each
+              const int pj = a.act_perm[j];
+              const float sg = a.act_sign[j];
+              const float mm = mirror[pj] * sg;
+              const float dm = head[j] - mm;
+              const float qm = dm * dm;
+              m64 += (double)qm;
+              float u = dm * a.inv_b;
+              u = u * ia;
+              u = u * a.mirror_k2;
+              dmu = dmu + u;
+              const float um = u * sg;
+              dAm[pj] = -um;
             }
           }
           if (j < head_pad) dA[j] = dmu;
           if (j < POL_MAX_ACTION) R[j] = dls;
         }
         R[PPO_COL_SURR] = surr; R[PPO_COL_DLOGP] = dlogp; R[PPO_COL_CLIPPED] = clipped;
-        for (int j = PPO_COL_CLIPPED + 1; j < PPO_ROW_COLS; ++j) R[j] = 0.0f;
+        R[PPO_COL_MIRROR] = ML ? (float)m64 * ia : 0.0f;
+        for (int j = PPO_COL_MIRROR + 1; j < PPO_ROW_COLS; ++j) R[j] = 0.0f;
       }
     }
   }
@@ -366,7 +390,7 @@ __global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_reduce_kernel(PpoArgs a)
     const float* P = a.scratch + a.p_off + src;
     float g = P[0];
     for (int c = 1; c < a.n_chunks; ++c) g += P[(size_t)c * a.p_floats];
-    if (is_log_std && a.act_perm) {   // the symmetrised log_std: 0.5f * (T[j] + T[act_perm[j]])
+    if (is_log_std && a.mode == PPO_SYM) {   // the symmetrised log_std: 0.5f * (T[j] + T[act_perm[j]])
       const float* Pm = a.scratch + a.p_off + a.log_std_off + a.act_perm[i - pos];
       float gm = Pm[0];
       for (int c = 1; c < a.n_chunks; ++c) gm += Pm[(size_t)c * a.p_floats];
@@ -398,17 +422,18 @@ __global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_stats_kernel(PpoArgs a) 
     __syncthreads();
   }
   if (tid != 0 || !a.stats) return;
-  float sum[4];   // the columns 32 .. 35 of R over all rows: the chunks' sums in chunk order
-  for (int k = 0; k < 4; ++k) {
+  float sum[5];   // the columns 32 .. 35 of R over all rows, and 36 for the mirror loss: the chunks' sums in chunk order
+  sum[4] = 0.0f;
+  for (int k = 0; k < (a.mode == PPO_MIRROR ? 5 : 4); ++k) {
     const float* P = a.scratch + a.p_off + a.log_std_off + PPO_COL_SURR + k;
     float v = P[0];
     for (int c = 1; c < a.n_chunks; ++c) v += P[(size_t)c * a.p_floats];
     sum[k] = v;
   }
   const float* log_std = a.params + a.log_std_off;
-  double h = 0.0;   // the entropy: summed in f64, j ascending, rounded once; with act_perm: of the symmetrised log_std (f32, as the head stage forms it)
+  double h = 0.0;   // the entropy: summed in f64, j ascending, rounded once; PPO_SYM: of the symmetrised log_std (f32, as the head stage forms it)
   for (int j = 0; j < a.act_dim; ++j) {
-    const float ls = a.act_perm ? 0.5f * (log_std[j] + log_std[a.act_perm[j]]) : log_std[j];
+    const float ls = a.mode == PPO_SYM ? 0.5f * (log_std[j] + log_std[a.act_perm[j]]) : log_std[j];
     h += ((double)ls + 0.5) + 0.91893853320467274178;
   }
   a.stats[0] = sum[0] * a.inv_b;
@@ -418,12 +443,13 @@ __global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_stats_kernel(PpoArgs a) 
   a.stats[4] = sum[3] / (float)a.n_rows;   // a count over B, correctly rounded
   a.stats[5] = (float)sq[0];
   a.stats[6] = 0.0f;
-  a.stats[7] = 0.0f;
+  a.stats[7] = sum[4] * a.inv_b;   // L_m: the rows' terms already carry the 1 / A; 0 in the other modes
 }
 
 void launch_ppo(hipStream_t s, const PpoArgs& a) {
-  if (a.in_perm) hipLaunchKernelGGL(ppo_rows_kernel<true>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(ppo_rows_kernel<false>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
+  if (a.mode == PPO_SYM) hipLaunchKernelGGL(ppo_rows_kernel<PPO_SYM>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
+  else if (a.mode == PPO_MIRROR) hipLaunchKernelGGL(ppo_rows_kernel<PPO_MIRROR>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(ppo_rows_kernel<PPO_PLAIN>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(a.n_tiles, a.n_chunks), dim3(64), 0, s, a);
   hipLaunchKernelGGL(ppo_reduce_kernel, dim3(a.n_reduce_blocks), dim3(PPO_REDUCE_BLOCK), 0, s, a);
   hipLaunchKernelGGL(ppo_stats_kernel, dim3(1), dim3(PPO_REDUCE_BLOCK), 0, s, a);

@@ -115,6 +115,15 @@ class MirrorTransform:
         return a[..., self.act_perm] * self.act_sign
 
 
+def mirror_loss(actor_mean, obs: torch.Tensor, transform: MirrorTransform) -> torch.Tensor:
+    """SymmetricRL's mirror-symmetry loss, `(mirror(actor(mirror_obs)) - actor(obs)).pow(2).mean()`: the mean over rows AND actions of
+    (f(x) - M_a f(M_o x))^2, both passes carrying gradient -- what mocca_ppo_grad_mirror adds to PPO's loss, times its coef.  `actor_mean`:
+    obs [..., in_dim] -> the Gaussian's mean [..., act_dim] (the normalisation included, so that the mirror acts on the raw row);
+    `transform` in `obs`'s dtype."""
+    d = actor_mean(obs) - transform.act(actor_mean(transform.obs(obs)))
+    return d.pow(2).mean()
+
+
 class SymmetricGaussian(torch.nn.Module):
     """The symmetric policy of `DevicePolicy(symmetry=)` / the policy kernel in torch, with gradients: what the PPO update differentiates
     while the rollout acts on the device.  Built over the trainer's own `actor_seq`, `critic_seq` (torch.nn.Sequential) and `log_std`

@@ -369,6 +369,18 @@ class TorchVecEnv:
             raise NotImplementedError("update_obs_stats needs one handle (sub_batches=1)")
         self.venv.update_obs_stats(stats, rows, mean_out=mean_out, inv_std_out=inv_std_out)
 
+    def policy_mirror_tables(self, policy):
+        """this env's mirror tables for `policy`, the attached height scan's pattern included: `VecEnv.policy_mirror_tables`"""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("policy_mirror_tables needs one handle (sub_batches=1)")
+        return self.venv.policy_mirror_tables(policy)
+
+    def set_policy_mirror_loss(self, tables, coef: float = 0.0) -> None:
+        """attach the mirror-symmetry loss for `ppo_grad` / `ppo_update` (None detaches): `VecEnv.set_policy_mirror_loss`.  One handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("set_policy_mirror_loss needs one handle (sub_batches=1)")
+        self.venv.set_policy_mirror_loss(tables, coef)
+
     def ppo_grad(self, obs, action, old_logp, adv, returns, *args, **kw) -> dict:
         """PPO's minibatch loss and its gradient over the rollout storage, four launches: `VecEnv.ppo_grad` -- of the symmetric network
         where the attached policy carries mirror tables (`symmetric_policy`).  One handle only."""

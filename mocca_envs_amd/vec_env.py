@@ -280,18 +280,19 @@ class VecEnv:
 
     # ---- the trainer's own policy on the device (include/mocca.h mocca_set_policy / mocca_update_policy / mocca_act / mocca_act_step) ----
     policy = None
+    mirror_loss = None   # (tables, coef) while set_policy_mirror_loss has one attached
 
     def set_policy(self, policy) -> None:
         """Attach a `policy.DevicePolicy` (None detaches): its shapes size the kernel's image, its weights are uploaded (update_policy).
         May synchronise."""
         if policy is None:
             _lib.check(self.lib.mocca_set_policy(self.h, None, 0, 0, 0, 0.0), self.h)
-            self.policy = None
+            self.policy = self.mirror_loss = None
             return
         table = np.ascontiguousarray(policy.table(), np.int32)
         _lib.check(self.lib.mocca_set_policy(self.h, table.ctypes.data_as(C.c_void_p), table.shape[0], int(policy.in_dim), int(policy.act_dim),
                                              float(policy.clip)), self.h)
-        self.policy = policy
+        self.policy, self.mirror_loss = policy, None   # mocca_set_policy has dropped both attachments
         self.update_policy(policy)
         if getattr(policy, "symmetry", None) is not None:      # after the shapes: mocca_set_policy has dropped whatever was attached
             self.set_policy_symmetry(policy.symmetry)
@@ -312,10 +313,29 @@ class VecEnv:
         if hasattr(self.policy, "with_symmetry"):
             self.policy = self.policy.with_symmetry(tables)
 
-    def symmetric_policy(self, policy):
-        """A copy of `policy` (a `policy.DevicePolicy`) with the mirror tables of THIS env: built from get_mirror_indices() and, where the
-        policy's input is [obs | scan], the attached scan pattern (symmetry.mirror_tables).  Envs whose reference publishes no six index
-        lists raise NotImplementedError."""
+    def set_policy_mirror_loss(self, tables, coef: float = 0.0) -> None:
+        """Attach SymmetricRL's mirror-symmetry LOSS to the policy set_policy attached, for the gradient only: `tables` as in
+        set_policy_symmetry (`policy_mirror_tables(policy)` gives this env's), `coef` >= 0 the weight of
+        mean((actor(obs) - M_a actor(M_o obs))^2) in the loss (0: monitored, not trained on).  act() and act_step() keep running the plain
+        policy; ppo_grad() and ppo_update() then differentiate PPO's loss plus the term (mocca_ppo_grad_mirror) and report it in
+        stats[7].  None detaches.  Exclusive with a symmetric policy; set_policy() drops it, update_policy() leaves it alone.  May
+        synchronise."""
+        if self.policy is None:
+            raise _lib.MoccaError("set_policy_mirror_loss needs a policy (set_policy)")
+        if tables is None:
+            _lib.check(self.lib.mocca_set_policy_mirror_loss(self.h, None, None, None, None, 0.0), self.h)
+            self.mirror_loss = None
+            return
+        t = [np.ascontiguousarray(x, d) for x, d in zip(tables, (np.int32, np.float32, np.int32, np.float32))]
+        if (t[0].size, t[1].size, t[2].size, t[3].size) != (self.policy.in_dim, self.policy.in_dim, self.policy.act_dim, self.policy.act_dim):
+            raise ValueError(f"the mirror tables have {self.policy.in_dim} input and {self.policy.act_dim} action entries")
+        _lib.check(self.lib.mocca_set_policy_mirror_loss(self.h, *[x.ctypes.data_as(C.c_void_p) for x in t], float(coef)), self.h)
+        self.mirror_loss = (tuple(t), float(coef))
+
+    def policy_mirror_tables(self, policy):
+        """The mirror tables (in_perm, in_sign, act_perm, act_sign) of THIS env for `policy` (a `policy.DevicePolicy`): built from
+        get_mirror_indices() and, where the policy's input is [obs | scan], the attached scan pattern (symmetry.mirror_tables).  Envs whose
+        reference publishes no six index lists raise NotImplementedError."""
         from .symmetry import mirror_tables
         mi = self.get_mirror_indices()
         if isinstance(mi, dict):
@@ -326,7 +346,11 @@ class VecEnv:
         elif scan is None or policy.in_dim != self.obs_dim + len(scan):
             raise ValueError(f"the policy's input has {policy.in_dim} entries, the env's observation {self.obs_dim}"
                              + ("" if scan is None else f" and its height scan {len(scan)}"))
-        return policy.with_symmetry(mirror_tables(mi, self.obs_dim, policy.act_dim, scan_points=scan))
+        return mirror_tables(mi, self.obs_dim, policy.act_dim, scan_points=scan)
+
+    def symmetric_policy(self, policy):
+        """A copy of `policy` (a `policy.DevicePolicy`) with the mirror tables of THIS env (policy_mirror_tables)."""
+        return policy.with_symmetry(self.policy_mirror_tables(policy))
 
     def update_policy(self, params) -> None:
         """New weights for the attached policy, once per PPO iteration: a `DevicePolicy` of the same shapes, or a flat float32 tensor in
@@ -443,7 +467,7 @@ class VecEnv:
                                             ptr(inv_std_out), self._stream()), self.h)
         self._out()
 
-    # ---- a PPO minibatch step on the device (include/mocca.h mocca_ppo_grad / mocca_ppo_grad_sym) ----
+    # ---- a PPO minibatch step on the device (include/mocca.h mocca_ppo_grad / mocca_ppo_grad_sym / mocca_ppo_grad_mirror) ----
     def ppo_grad(self, obs: torch.Tensor, action: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor, returns: torch.Tensor,
                  idx: Optional[torch.Tensor] = None, old_value: Optional[torch.Tensor] = None, clip: float = 0.2, value_coef: float = 0.5,
                  entropy_coef: float = 0.0, value_clip: bool = False, grad: Optional[torch.Tensor] = None,
@@ -457,19 +481,22 @@ class VecEnv:
         kernel does not check; None: all R rows.  Reads the weights `update_policy` last wrote.  A policy with mirror tables attached
         (`DevicePolicy(symmetry=)`, `set_policy_symmetry`) takes the symmetric network's gradient, what autograd gives through
         `symmetry.SymmetricGaussian.evaluate_actions` (mocca_ppo_grad_sym: the same four launches on twice the columns; the entropy is the
-        symmetrised log_std's); at most 2^21 rows then, 2^22 otherwise.  `grad` / `stats`: caller-owned outputs, allocated where none is
+        symmetrised log_std's).  With a mirror loss attached (`set_policy_mirror_loss`) the loss gains coef * L_m and stats[7] is L_m
+        (mocca_ppo_grad_mirror: the plain policy, the same layout as the symmetric call).  At most 2^21 rows in either case, 2^22
+        otherwise.  `grad` / `stats`: caller-owned outputs, allocated where none is
         given.  The same inputs give the same bits on every run."""
         if self.policy is None:
             raise _lib.MoccaError("ppo_grad needs a policy (set_policy)")
         symmetric = getattr(self.policy, "symmetry", None) is not None
+        mirror = self.mirror_loss is not None
         _, stride, n_batch = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, idx, old_value, clip, value_coef,
-                                          entropy_coef, value_clip, grad, stats, symmetric=symmetric)
+                                          entropy_coef, value_clip, grad, stats, symmetric=symmetric or mirror)
         f32 = dict(dtype=torch.float32, device=self.device)
         grad = torch.empty(self.policy.n_head(), **f32) if grad is None else grad
         stats = torch.empty(8, **f32) if stats is None else stats
         ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
         self._in()
-        call = self.lib.mocca_ppo_grad_sym if symmetric else self.lib.mocca_ppo_grad
+        call = self.lib.mocca_ppo_grad_mirror if mirror else self.lib.mocca_ppo_grad_sym if symmetric else self.lib.mocca_ppo_grad
         _lib.check(call(self.h, ptr(obs), stride, ptr(action), ptr(old_logp), ptr(adv), ptr(returns), ptr(old_value), ptr(idx), n_batch, float(clip),
                         float(value_coef), float(entropy_coef), int(bool(value_clip)), ptr(grad), ptr(stats), self._stream()), self.h)
         self._out()
@@ -501,12 +528,13 @@ class VecEnv:
         M = R // minibatch_rows minibatches (the remainder is dropped), each minibatch `ppo_grad` on its rows and `adam_step` on `params`
         -- the same bits as that loop.  The storage tensors are `ppo_grad`'s, `params` / `state` / `n_params` / `lr` .. `max_grad_norm`
         `adam_step`'s; `params` must hold what `update_policy` last received.  The shuffle is keyed by `seed` and the state's step count.
-        -> {"stats": [epochs * M, 8]}: `ppo_grad`'s statistics per minibatch, [6] the clip coefficient applied (0: a skipped step);
+        -> {"stats": [epochs * M, 8]}: `ppo_grad`'s statistics per minibatch, [6] the clip coefficient applied (0: a skipped step), [7] L_m
+        with a mirror loss attached;
         `stats`: a caller-owned output.  Nothing synchronises or is read on the host; capturable after one warm call of the same shapes
         (the scalars and the seed are baked into the capture)."""
         if self.policy is None:
             raise _lib.MoccaError("ppo_update needs a policy (set_policy)")
-        symmetric = getattr(self.policy, "symmetry", None) is not None
+        symmetric = getattr(self.policy, "symmetry", None) is not None or self.mirror_loss is not None   # either halves the row bound
         n_rows, stride, _ = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, None, old_value, clip, value_coef,
                                          entropy_coef, value_clip, None, None, symmetric=symmetric)
         n_params = _ro.adam_args(self.policy, self.device, params, None, state, n_params, lr, betas, eps, max_grad_norm)

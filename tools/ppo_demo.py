@@ -5,10 +5,10 @@ that LEARNS, and what does the step kernel cost on the workload a trained policy
 Plain PPO in the pytorch-a2c-ppo-acktr mould the reference's trainers (README.md:33-39) follow -- Gaussian MLP policy 2 x 256 tanh, separate value
 net, GAE(0.95), clipped surrogate, Adam, running observation normalisation -- with everything on the device: the step kernel writes observation /
 reward / masks / bad_masks straight into the rollout storage (`step(action, into=...)`), Monitor's statistics come from `envs.episode_totals`.
-No symmetry loss, no curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it SymmetricRL's symmetric network.
+No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it SymmetricRL's symmetric network, --mirror-loss its symmetry loss.
 
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
-                           [--device-policy [--device-returns [--device-grad [--device-update]]]] [--symmetric]
+                           [--device-policy [--device-returns [--device-grad [--device-update]]]] [--symmetric | --mirror-loss COEF]
 --device-policy: collection runs through `envs.act_step(obs[t], into=...)` -- the policy kernel (normalisation, both nets, the sample, its
 log-probability, the value) and the step kernel, two launches per step and no torch op; `envs.update_policy(flat)` once per iteration hands the
 kernel the optimiser's new weights and the running observation statistics.  The noise then comes from the kernel, not from torch.randn.
@@ -27,7 +27,13 @@ and the repack --; no torch.randperm, no torch.optim.Adam, nothing read on the h
 --symmetric: the policy is the mirror-symmetric network built from the env's get_mirror_indices() (`symmetry.SymmetricGaussian` over the same
 `pi`, `vf` and `log_std`): it serves the torch update, torch collection and --verify-grad; with --device-policy the attached policy carries
 `envs.symmetric_policy(...)`'s mirror tables, and with --device-grad each minibatch is one symmetric `ppo_grad` (mocca_ppo_grad_sym).
---verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor.
+--mirror-loss COEF (not with --symmetric): SymmetricRL's mirror-symmetry loss, COEF * `symmetry.mirror_loss` = COEF * mean((pi(n(s)) -
+M_a pi(n(M_o s)))^2) over the env's get_mirror_indices(), added to the plain policy's loss; the logged lines carry `mirror_loss`, the
+iteration's mean of the term over its minibatches, and COEF 0 logs the asymmetry of an unconstrained run.  The torch update adds it through
+autograd; with --device-grad / --device-update `envs.set_policy_mirror_loss` attaches the tables and the weight, each minibatch's gradient is
+mocca_ppo_grad_mirror and the term is its stats[7].  Collection stays the plain policy's: one forward pass per step.
+--verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor; with
+--device-update, whose minibatches are drawn on the device, it takes one `envs.ppo_grad` on a torch.randperm chunk ahead of the update.
 writes <out>.jsonl (one line per logged iteration: env-steps so far, mean episode return / length of the episodes that ended since the last line,
 wall-clock env-steps/s of the whole loop incl. learning) and <out>_policy.npz (weights + observation statistics: `bench.py`'s workload
 bracket loads profiles/ppo_policy_walker3d.npz as its `ppo_policy` workload)."""
@@ -64,14 +70,17 @@ def main():
     ap.add_argument("--device-grad", action="store_true", help="with --device-returns: each minibatch's loss and gradient on the device (ppo_grad); the parameters live in one flat tensor")
     ap.add_argument("--device-update", action="store_true", help="with --device-grad: the whole update -- shuffle, gradient, clip, Adam, repack for every epoch and minibatch -- as one call (ppo_update)")
     ap.add_argument("--symmetric", action="store_true", help="SymmetricRL's symmetric network: mean, value and log_std symmetrised through the env's mirror tables")
+    ap.add_argument("--mirror-loss", type=float, default=None, metavar="COEF", help="SymmetricRL's mirror-symmetry loss with this weight (0: only logged); not with --symmetric")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args()
     if args.device_grad and not args.device_returns:
         ap.error("--device-grad requires --device-returns")
     if args.device_update and not args.device_grad:
         ap.error("--device-update requires --device-grad")
-    if args.device_update and args.verify_grad:
-        ap.error("--verify-grad checks the minibatch loop: not with --device-update")
+    if args.mirror_loss is not None and args.symmetric:
+        ap.error("--mirror-loss is not for --symmetric: a symmetric network has no mirror loss")
+    if args.mirror_loss is not None and not args.mirror_loss >= 0.0:
+        ap.error("--mirror-loss takes a weight >= 0")
     if args.verify_grad and not args.device_grad:
         ap.error("--verify-grad requires --device-grad")
     if args.device_returns and not args.device_policy:
@@ -115,6 +124,18 @@ def main():
         sym = SymmetricGaussian(pi, vf, log_std, tables).to(dev)      # shares pi, vf and log_std
         inv_std_now = lambda: inv_std if args.device_returns else 1.0 / torch.sqrt(var + 1e-8)
 
+    if args.mirror_loss is not None:
+        from mocca_envs_amd.symmetry import MirrorTransform, mirror_loss
+        mirror_tf = MirrorTransform(envs.get_mirror_indices(), od, ad, device=dev)
+        lm_sum, lm_n = torch.zeros((), device=dev), 0      # the term over the minibatches since the last logged line
+
+    def aux_loss(mb):
+        """what --mirror-loss adds to the minibatch's loss -> (COEF * L_m or 0, L_m or None); the mirror acts on the RAW rows"""
+        if args.mirror_loss is None:
+            return 0.0, None
+        l_m = mirror_loss(lambda x: pi(norm(x)), raw_all[mb], mirror_tf)
+        return args.mirror_loss * l_m, l_m
+
     def evaluate(mb):
         """(logp [b, 1], value [b, 1]) of the minibatch's stored actions under the current parameters"""
         if args.symmetric:      # the mirror acts on the RAW row
@@ -126,6 +147,8 @@ def main():
         from mocca_envs_amd.policy import DevicePolicy
         dp = DevicePolicy.from_torch(pi, vf, log_std, obs_mean=mean, obs_var=var, eps=1e-8, clip=10.0)
         envs.attach_policy(envs.symmetric_policy(dp) if args.symmetric else dp)
+        if args.mirror_loss is not None and args.device_grad:      # for the gradient only: act_step keeps running the plain policy
+            envs.set_policy_mirror_loss(envs.policy_mirror_tables(dp), args.mirror_loss)
         row_act = lambda t: dict(row(t), action=S["act"][t], logp=S["logp"][t], value=S["value"][t])
         # DevicePolicy.flat_params()'s order, built on the device: layers of pi then vf (W, b), log_std, mean, 1 / sqrt(var + eps)
         flat_params = lambda: torch.cat([q.reshape(-1) for net in (pi, vf) for m in net if isinstance(m, nn.Linear) for q in (m.weight, m.bias)]
@@ -156,7 +179,20 @@ def main():
         else:
             w_flat = flat[:n_head].requires_grad_()
             opt = torch.optim.Adam([w_flat], lr=args.lr, eps=1e-5)
-            g_buf, s_buf = torch.zeros(n_head, device=dev), torch.zeros(8, device=dev)
+        g_buf, s_buf = torch.zeros(n_head, device=dev), torch.zeros(8, device=dev)
+
+    def verify_grad(mb, it):
+        """g_buf holds ppo_grad's gradient of minibatch `mb` at the current parameters: print its largest difference from autograd"""
+        lp, v = evaluate(mb)
+        ratio = (lp - lp_all[mb]).exp()
+        surr = torch.min(ratio * adv_all[mb], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_all[mb]).mean()
+        v_loss = 0.5 * (v - ret_all[mb]).pow(2).mean()
+        auto = torch.autograd.grad(-surr + 0.5 * v_loss + aux_loss(mb)[0], head[:-1] if args.fixed_std else head)
+        worst, pos = 0.0, 0
+        for g in auto:
+            worst = max(worst, ((g_buf[pos:pos + g.numel()] - g.reshape(-1)).abs().max() / g.abs().max().clamp_min(1e-30)).item())
+            pos += g.numel()
+        print(json.dumps({"verify_grad": worst, "iter": it + 1}), flush=True)
 
     S["obs"][0].copy_(envs.reset())
     envs.episode_totals.zero_()
@@ -234,10 +270,16 @@ def main():
         o_all, a_all, lp_all = norm(S["obs"][:T]).reshape(B, od), S["act"].reshape(B, ad), S["logp"].reshape(B, 1)
         adv_all, ret_all, raw_all = adv.reshape(B, 1), ret.reshape(B, 1), S["obs"][:T].reshape(B, od)
         if args.device_update:
+            if args.verify_grad:      # the update draws its minibatches on the device: one gradient call on a chunk of our own, ahead of it
+                mb = torch.randperm(B, device=dev)[:B // args.minibatches]
+                envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf)
+                verify_grad(mb, it)
             # ppo.update() as one call: epochs x minibatches of [shuffle, ppo_grad, clip, Adam, repack]; u_stats keeps a row per minibatch
             envs.ppo_update(S["obs"][:T], S["act"], S["logp"], adv, ret, flat, adam, minibatch_rows=B // args.minibatches, epochs=args.epochs,
                             clip=args.clip, value_coef=0.5, n_params=n_head - ad if args.fixed_std else n_head, lr=args.lr, eps=1e-5,
                             max_grad_norm=0.5, seed=args.seed, stats=u_stats)
+            if args.mirror_loss is not None:
+                lm_sum += u_stats[:, 7].sum(); lm_n += u_stats.shape[0]
         for ep in range(0 if args.device_update else args.epochs):
             perm = torch.randperm(B, device=dev)
             for k, mb in enumerate(perm.chunk(args.minibatches)):
@@ -246,17 +288,10 @@ def main():
                     # the symmetric network -- the attached policy carries the mirror tables)
                     envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf)
                     if args.verify_grad and ep == 0 and k == 0:
-                        lp, v = evaluate(mb)
-                        ratio = (lp - lp_all[mb]).exp()
-                        surr = torch.min(ratio * adv_all[mb], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_all[mb]).mean()
-                        v_loss = 0.5 * (v - ret_all[mb]).pow(2).mean()
-                        auto = torch.autograd.grad(-surr + 0.5 * v_loss, head[:-1] if args.fixed_std else head)
-                        worst, pos = 0.0, 0
-                        for g in auto:
-                            worst = max(worst, ((g_buf[pos:pos + g.numel()] - g.reshape(-1)).abs().max() / g.abs().max().clamp_min(1e-30)).item())
-                            pos += g.numel()
-                        print(json.dumps({"verify_grad": worst, "iter": it + 1}), flush=True)
+                        verify_grad(mb, it)
                     with torch.no_grad():
+                        if args.mirror_loss is not None:
+                            lm_sum += s_buf[7]; lm_n += 1
                         sq = s_buf[5]
                         if args.fixed_std:      # log_std is not a parameter then: its entries leave the norm and the step
                             sq = (sq - g_buf[n_head - ad:].square().sum()).clamp(min=0.0)
@@ -270,8 +305,11 @@ def main():
                 ratio = (lp - lp_all[mb]).exp()
                 surr = torch.min(ratio * adv_all[mb], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_all[mb]).mean()
                 v_loss = 0.5 * (v - ret_all[mb]).pow(2).mean()
+                aux, l_m = aux_loss(mb)
+                if l_m is not None:
+                    lm_sum += l_m.detach(); lm_n += 1
                 opt.zero_grad(set_to_none=True)
-                (-surr + 0.5 * v_loss).backward()
+                (-surr + 0.5 * v_loss + aux).backward()
                 nn.utils.clip_grad_norm_(list(pi.parameters()) + list(vf.parameters()) + ([] if args.fixed_std else [log_std]), 0.5)
                 opt.step()
         with torch.no_grad():      # rollouts.after_update()
@@ -284,6 +322,9 @@ def main():
             line = {"iter": it + 1, "env_steps": total_steps, "wall_s": round(wall, 1), "env_steps_per_s_incl_learning": round(total_steps / wall),
                     "episodes": int(dlt[2]), "mean_return": float(dlt[0] / max(dlt[2], 1)), "mean_length": float(dlt[1] / max(dlt[2], 1)),
                     "truncated_fraction": float(dlt[3] / max(dlt[2], 1)), "log_std": float(log_std.mean().item())}
+            if args.mirror_loss is not None:      # the mean of L_m over the minibatches since the last logged line
+                line["mirror_loss"] = float(lm_sum.item() / max(lm_n, 1))
+                lm_sum.zero_(); lm_n = 0
             if "Stepper" in args.env_id:      # next_step_index of the running episodes (the step's info word): how far along the 20 planks the batch is
                 line["mean_next_step_index"] = float(envs.venv.info.float().mean().item())
             log.write(json.dumps(line) + "\n"); log.flush()

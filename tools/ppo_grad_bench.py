@@ -7,6 +7,9 @@
   python tools/ppo_grad_bench.py grad --symmetric   [--out profiles/ppo_grad_sym.json]
       the same for the mirror-symmetric policy (the env's own mirror tables): mocca_ppo_grad_sym against the minibatch through
       `symmetry.SymmetricGaussian` in torch eager, as tools/ppo_demo.py --symmetric does it; both in one process.
+  python tools/ppo_grad_bench.py grad --mirror-loss   [--out profiles/ppo_grad_mirror.json]
+      the same for the plain policy with the mirror-symmetry loss attached (the env's own mirror tables, coef 4): mocca_ppo_grad_mirror
+      against the plain minibatch plus `symmetry.mirror_loss` in torch eager, as tools/ppo_demo.py --mirror-loss does it; both in one process.
   python tools/ppo_grad_bench.py act --key NAME [--package-root DIR] [--out ...]
       `update_policy` and `act` at 4096 envs, 7 blocks of 200 warm calls, stored under "act_update"[NAME].  --package-root: the tree whose
       mocca_envs_amd (with its built library) is imported -- a checkout of the parent commit gives the A/B; run the two alternately.
@@ -58,13 +61,16 @@ def main():
     ap.add_argument("mode", choices=("grad", "act", "trace", "per-launch"))
     ap.add_argument("--out")
     ap.add_argument("--symmetric", action="store_true", help="grad: the mirror-symmetric policy (mocca_ppo_grad_sym against SymmetricGaussian)")
+    ap.add_argument("--mirror-loss", action="store_true", help="grad: the mirror-symmetry loss (mocca_ppo_grad_mirror against symmetry.mirror_loss)")
     ap.add_argument("--key", default="this")
     ap.add_argument("--package-root", default=ROOT)
     ap.add_argument("--kernel-db")
     args = ap.parse_args()
-    if args.symmetric and args.mode != "grad":
-        ap.error("--symmetric goes with the grad mode")
-    args.out = args.out or os.path.join(ROOT, "profiles", "ppo_grad_sym.json" if args.symmetric else "ppo_grad.json")
+    if (args.symmetric or args.mirror_loss) and args.mode != "grad":
+        ap.error("--symmetric and --mirror-loss go with the grad mode")
+    if args.symmetric and args.mirror_loss:
+        ap.error("--symmetric or --mirror-loss, not both")
+    args.out = args.out or os.path.join(ROOT, "profiles", "ppo_grad_sym.json" if args.symmetric else "ppo_grad_mirror.json" if args.mirror_loss else "ppo_grad.json")
     if args.mode == "per-launch":
         import sqlite3
         import statistics
@@ -104,6 +110,8 @@ def main():
     if args.symmetric:
         dp = env.symmetric_policy(dp)
     env.set_policy(dp)
+    if args.mirror_loss:
+        env.set_policy_mirror_loss(env.policy_mirror_tables(dp), 4.0)
     f = lambda *s: torch.from_numpy(rng.normal(0, 1, s).astype(np.float32)).cuda()
     obs, act, olp, adv, ret = f(ROWS, 52) * 3, f(ROWS, 21), f(ROWS) - 20, f(ROWS), f(ROWS)
     idx = torch.randperm(ROWS, device="cuda")[:B]
@@ -116,7 +124,9 @@ def main():
         env.close()
         return
     res = {"what": f"B = {B} rows gathered from {ROWS}, policy 52 -> 256 -> 256 -> {{21, 1}} tanh, HIP events, 5 blocks of 200 warm calls"}
-    name = "mocca_ppo_grad_sym" if args.symmetric else "mocca_ppo_grad"
+    name = "mocca_ppo_grad_sym" if args.symmetric else "mocca_ppo_grad_mirror" if args.mirror_loss else "mocca_ppo_grad"
+    if args.mirror_loss:
+        res["what"] += "; the plain policy with the mirror-symmetry loss of the env's mirror tables at coef 4, torch eager through symmetry.mirror_loss"
     if args.symmetric:
         res["what"] += "; the mirror-symmetric policy of the env's mirror tables, torch eager through symmetry.SymmetricGaussian"
     res[name] = timed(torch, call)
@@ -143,6 +153,19 @@ def main():
         opt.zero_grad(set_to_none=True)
         (-surr + 0.5 * v_loss).backward()
 
+    if args.mirror_loss:
+        from mocca_envs_amd.symmetry import MirrorTransform, mirror_loss
+        tf = MirrorTransform(env.get_mirror_indices(), 52, 21, device="cuda")
+
+    def eager_mirror():
+        mu = pi(o_all[idx])
+        ratio = (logprob(mu, act[idx]) - lp_all[idx]).exp()
+        surr = torch.min(ratio * adv_all[idx], ratio.clamp(0.8, 1.2) * adv_all[idx]).mean()
+        v_loss = 0.5 * (vf(o_all[idx]) - ret_all[idx]).pow(2).mean()
+        l_m = mirror_loss(lambda x: pi(x.clamp(-10, 10)), obs[idx], tf)
+        opt.zero_grad(set_to_none=True)
+        (-surr + 0.5 * v_loss + 4.0 * l_m).backward()
+
     def eager():
         mu = pi(o_all[idx])
         ratio = (logprob(mu, act[idx]) - lp_all[idx]).exp()
@@ -151,7 +174,7 @@ def main():
         opt.zero_grad(set_to_none=True)
         (-surr + 0.5 * v_loss).backward()
 
-    res["torch_eager"] = timed(torch, eager_sym if args.symmetric else eager)
+    res["torch_eager"] = timed(torch, eager_sym if args.symmetric else eager_mirror if args.mirror_loss else eager)
     res["speedup"] = round(res["torch_eager"]["us_per_call_median"] / res[name]["us_per_call_median"], 2)
     merge(args.out, "minibatch", res)
     print(json.dumps(res))
