@@ -406,9 +406,18 @@ int mocca_height_scan(mocca_handle h, float *out_dev, int row_stride, const floa
  *                       mocca_set_policy drops the attachment; mocca_update_policy leaves it alone.  A violation (an invalid table, a
  *                       negative or non-finite mirror_coef, a symmetry attached) is MOCCA_E_ARG with a message and leaves the handle as
  *                       it was.  May synchronise.
+ * mocca_set_policy_mirror_dup  attaches SymmetricRL's DUPLICATED TUPLES (every rollout tuple (s, a) is
+ *                       trained on together with its mirror image (M_o s, M_a a)) FOR THE GRADIENT ONLY: the four tables of
+ *                       mocca_set_policy_symmetry under the same validity rules.  The policy stays the plain one: while attached,
+ *                       mocca_act / mocca_act_step launch the plain instance and give the bits they give with nothing attached;
+ *                       mocca_ppo_grad_dup (below) is the gradient, mocca_ppo_update runs it, and mocca_ppo_grad / mocca_ppo_grad_sym /
+ *                       mocca_ppo_grad_mirror refuse.  The THREE attachments (symmetry, mirror loss, duplicated rows) exclude one
+ *                       another: each setter refuses while another's attachment is in place and names it, the caller detaches first.
+ *                       in_perm_host == NULL detaches; mocca_set_policy drops the attachment; mocca_update_policy leaves it alone.  A
+ *                       violation is MOCCA_E_ARG with a message and leaves the handle as it was.  May synchronise.
  * Errors (MOCCA_E_ARG, with a message): a NULL handle, any bad dimension, mocca_update_policy / mocca_act / mocca_set_policy_symmetry before
  * mocca_set_policy, mocca_act before mocca_update_policy, n_floats that fits neither form, in_stride < in_dim, mocca_act_step with act_dim other
- * than the env's, an invalid mirror table, a negative or non-finite mirror_coef, either of the two mirror attachments while the other is in place, global env ids (MOCCA_PARAM_ENV_OFFSET + n_envs) beyond 2^28 (the noise's counter holds 16 x env id
+ * than the env's, an invalid mirror table, a negative or non-finite mirror_coef, any of the three mirror attachments while another is in place, global env ids (MOCCA_PARAM_ENV_OFFSET + n_envs) beyond 2^28 (the noise's counter holds 16 x env id
  * in one 32-bit word). */
 int mocca_set_policy(mocca_handle h, const int32_t *layers_host, int n_layers_total, int in_dim, int act_dim, double clip);
 int mocca_update_policy(mocca_handle h, const float *params_dev, size_t n_floats, void *stream);
@@ -421,6 +430,8 @@ int mocca_set_policy_symmetry(mocca_handle h, const int32_t *in_perm_host, const
                               const float *act_sign_host);
 int mocca_set_policy_mirror_loss(mocca_handle h, const int32_t *in_perm_host, const float *in_sign_host, const int32_t *act_perm_host,
                                  const float *act_sign_host, double mirror_coef);
+int mocca_set_policy_mirror_dup(mocca_handle h, const int32_t *in_perm_host, const float *in_sign_host, const int32_t *act_perm_host,
+                                const float *act_sign_host);
 
 /* ---- the end of a rollout on the device (no reference counterpart: the reference's trainers run these in torch, a Python loop over the
  *      rollout's steps and a handful of reductions per iteration) ---- */
@@ -523,7 +534,8 @@ int mocca_obs_stats(mocca_handle h, const float *rows_dev, int64_t n_rows, int r
  * NULL obs_dev, action_dev, old_logp_dev, adv_dev, returns_dev or grad_dev; value_clip with old_value_dev NULL; n_rows < 1 or > 2^22;
  * obs_stride < in_dim; a non-finite or negative clip, value_coef or entropy_coef; a handle with mirror tables attached
  * (mocca_set_policy_symmetry) -- the symmetric policy's gradient is mocca_ppo_grad_sym: call that, or detach the tables first; a handle
- * with a mirror loss attached (mocca_set_policy_mirror_loss) -- that loss's gradient is mocca_ppo_grad_mirror. */
+ * with a mirror loss attached (mocca_set_policy_mirror_loss) -- that loss's gradient is mocca_ppo_grad_mirror; a handle with duplicated
+ * rows attached (mocca_set_policy_mirror_dup) -- their gradient is mocca_ppo_grad_dup. */
 int mocca_ppo_grad(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
                    const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
                    double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
@@ -564,7 +576,7 @@ int mocca_ppo_grad(mocca_handle h, const float *obs_dev, int obs_stride, const f
  *                   a mocca_update_policy made between two replays; it writes only grad_dev, stats_dev and its scratch.
  * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): those of mocca_ppo_grad with n_rows > 2^21 in place of 2^22; and a
  * policy WITHOUT mirror tables attached (mocca_set_policy_symmetry) -- the plain policy's gradient is mocca_ppo_grad; a handle with a mirror
- * loss attached (mocca_ppo_grad_mirror is its gradient). */
+ * loss attached (mocca_ppo_grad_mirror is its gradient) or with duplicated rows attached (mocca_ppo_grad_dup is theirs). */
 int mocca_ppo_grad_sym(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
                        const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
                        double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
@@ -597,10 +609,40 @@ int mocca_ppo_grad_sym(mocca_handle h, const float *obs_dev, int obs_stride, con
  *                   tables, and mirror_coef is a kernel argument, BAKED INTO a captured call: mocca_set_policy_mirror_loss and
  *                   mocca_set_policy ask for a new capture.
  * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): those of mocca_ppo_grad with n_rows > 2^21 in place of 2^22; and a
- * handle WITHOUT a mirror loss attached (mocca_set_policy_mirror_loss). */
+ * handle WITHOUT a mirror loss attached (mocca_set_policy_mirror_loss); a handle with duplicated rows attached (mocca_ppo_grad_dup is
+ * their gradient). */
 int mocca_ppo_grad_mirror(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
                           const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
                           double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
+
+/* mocca_ppo_grad_dup  mocca_ppo_grad on MIRROR-DUPLICATED rows (mocca_set_policy_mirror_dup; SymmetricRL's duplicated tuples): the PLAIN policy
+ *                   and mocca_ppo_grad's loss L, un-symmetrised and with no term added, over 2 B samples in the same four launches.  The
+ *                   argument list, the arrays, idx_dev (NOT range-checked) and grad_dev's order are mocca_ppo_grad's.  With the mirror
+ *                   (M x)[k] = sign[k] * x[perm[k]]:
+ *                       sample b      the row as given: s, a, old_logp, adv, returns, old_value
+ *                       its twin      observation M_o s -- mirrored on the RAW row and then normalised by k, exactly as
+ *                                     mocca_ppo_grad_sym stages it --; action a'[j] = a[act_perm[j]] * act_sign[j], ONE f32 operation, exact;
+ *                                     the row's OWN old_logp, adv, returns and old_value
+ *                   Every mean is over the 2 B samples: ib = 1.0f / f32(2 B).  mocca_ppo_grad's per-row lines -- logp in f64, r, the
+ *                   surrogate, g, dL/dmu, the row's log_std term, the value loss with its clamp tie rule -- apply UNCHANGED to each
+ *                   sample, one IEEE f32 operation per line, never contracted into an FMA.  log_std's gradient is the sum of g * q_j over
+ *                   all 2 B samples minus f32(entropy_coef); H is the plain one.  Actor and critic both see the twins.
+ *                   Copying old_logp to the twin is the METHOD's own assumption, that pi_old is close to mirror-symmetric: a twin's ratio
+ *                   is pi(M_a a | M_o s) / pi_old(a | s), so the twins are OFF-POLICY by the policy's asymmetry -- their ratio leaves 1
+ *                   and the clip range by as much as the policy is asymmetric --, and stats[7] below measures exactly that.  An exact
+ *                   importance ratio, pi_old(M_a a | M_o s) computed at collection, is NOT offered: it would need a second old_logp
+ *                   array through this call's and mocca_ppo_update's signature.
+ *                   stats_dev [8]: [0..5] keep mocca_ppo_grad's meanings over the 2 B samples -- [4] the count of clipped samples of both
+ *                   kinds divided by f32(2 B) --, [6] = 0, [7] = the twins' share of [3]: the sum over the B twins of old_logp - logp_twin
+ *                   (summed like the other statistics), times ib; [3] - [7] is the as-given rows' share.
+ *                   Scratch, the n_rows bound (2^21), the grow-FREES-the-old rule and the capture conditions are mocca_ppo_grad_sym's: twice
+ *                   the plain call's scratch per row, shared by all four calls; a captured call holds the attachment's device tables:
+ *                   mocca_set_policy_mirror_dup and mocca_set_policy ask for a new capture.
+ * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): those of mocca_ppo_grad with n_rows > 2^21 in place of 2^22; and a
+ * handle WITHOUT duplicated rows attached (mocca_set_policy_mirror_dup). */
+int mocca_ppo_grad_dup(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
+                       const float *adv_dev, const float *returns_dev, const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows,
+                       double clip, double value_coef, double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
 
 /* ---- PPO's optimiser step and update loop on the device (no reference counterpart: the reference's trainers run clip_grad_norm_, Adam and
  *      the minibatch loop in torch and Python) ---- */
@@ -646,7 +688,7 @@ int mocca_adam_step(mocca_handle h, float *params_dev, size_t n_floats, const fl
  *                   entropy_coef and value_clip are mocca_ppo_grad's; params_dev .. max_grad_norm are mocca_adam_step's.  Per epoch ONE
  *                   launch fills a handle-owned i64 [R] with a permutation of 0 .. R - 1; per minibatch u follow the four launches of
  *                   mocca_ppo_grad -- of mocca_ppo_grad_sym when the policy has mirror tables attached, of mocca_ppo_grad_mirror when a
- *                   mirror loss is attached: this entry point serves all three --
+ *                   mirror loss is attached, of mocca_ppo_grad_dup when duplicated rows are: this entry point serves all four --
  *                   with idx_dev = that array + u B and a handle-owned gradient [n_head], then mocca_adam_step's three launches on it.
  *                   The result is, bit for bit, what that sequence of calls gives.
  *                   The permutation is closed-form and defined in integers: w = max(2, bit_length(R - 1)) rounded up to even,
@@ -657,7 +699,7 @@ int mocca_adam_step(mocca_handle h, float *params_dev, size_t n_floats, const fl
  *                   walk returns below R and the entries are a bijection of 0 .. R - 1.  t is clock_dev[0] as the fill kernel READS IT ON
  *                   THE DEVICE when the epoch starts: a replayed graph shuffles anew, and a fresh clock with the same seed repeats a run.
  *                   stats_dev [epochs M][8] f32 or NULL: row k holds the k-th minibatch's mocca_ppo_grad statistics, with [6] overwritten
- *                   by the clip coefficient applied (0 on a skipped step) and [7] left as the gradient call wrote it (L_m with a mirror loss attached, else
+ *                   by the clip coefficient applied (0 on a skipped step) and [7] left as the gradient call wrote it (L_m with a mirror loss attached, the twins' share of [3] with duplicated rows, else
  *                   0); the trainer's `value_loss_epoch` etc. are the
  *                   rows' mean, and the rows' [3] is what a KL monitor reads.
  *                   params_dev must hold what mocca_update_policy (or mocca_adam_step) last wrote.  mocca_ppo_grad's conditions hold as
@@ -665,8 +707,8 @@ int mocca_adam_step(mocca_handle h, float *params_dev, size_t n_floats, const fl
  *                   call is a linear chain of epochs (1 + 7 M) launches on `stream`, capturable after one warm call of the same shapes,
  *                   with mocca_adam_step's scalars and `seed` baked in.
  * Errors (MOCCA_E_ARG, with a message; the handle is left as it was and nothing is launched): those of mocca_adam_step and of mocca_ppo_grad
- * (/ mocca_ppo_grad_sym / mocca_ppo_grad_mirror) but for their grad_dev and idx_dev; minibatch_rows outside 1 .. n_rollout_rows; epochs < 1; n_rollout_rows < 1 or
- * beyond mocca_ppo_grad's bound (2^22, with mirror tables or a mirror loss 2^21). */
+ * (/ mocca_ppo_grad_sym / mocca_ppo_grad_mirror / mocca_ppo_grad_dup) but for their grad_dev and idx_dev; minibatch_rows outside 1 .. n_rollout_rows; epochs < 1; n_rollout_rows < 1 or
+ * beyond mocca_ppo_grad's bound (2^22, with mirror tables, a mirror loss or duplicated rows 2^21). */
 int mocca_ppo_update(mocca_handle h, const float *obs_dev, int obs_stride, const float *action_dev, const float *old_logp_dev,
                      const float *adv_dev, const float *returns_dev, const float *old_value_dev, int64_t n_rollout_rows,
                      int64_t minibatch_rows, int epochs, double clip, double value_coef, double entropy_coef, int value_clip,

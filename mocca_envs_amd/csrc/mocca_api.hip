@@ -169,6 +169,8 @@ struct mocca_ctx {
   DevBuf<int32_t> d_pol_ml_perm;     // mocca_set_policy_mirror_loss: the same two layouts, read by mocca_ppo_grad_mirror ALONE (pol stays plain)
   DevBuf<float> d_pol_ml_sign;
   double pol_ml_coef = 0.0;          // mirror_coef; meaningful while d_pol_ml_perm is set
+  DevBuf<int32_t> d_pol_dup_perm;    // mocca_set_policy_mirror_dup: the same two layouts, read by mocca_ppo_grad_dup ALONE (pol stays plain)
+  DevBuf<float> d_pol_dup_sign;
   // scratch of mocca_gae / mocca_obs_stats (mocca_rollout.h), owned by the handle, grown on demand
   DevBuf<double> d_gae_part;         // [blocks][2]
   size_t gae_part_cap = 0;           // doubles
@@ -1077,6 +1079,11 @@ static void drop_policy_mirror_loss(mocca_handle h) {
   h->pol_ml_coef = 0.0;
 }
 
+// detach the duplicated-rows tables (mocca_set_policy_mirror_dup); as above
+static void drop_policy_mirror_dup(mocca_handle h) {
+  h->d_pol_dup_perm.reset(); h->d_pol_dup_sign.reset();
+}
+
 int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) try {
   using namespace mocca_pol;
   if (!h) return MOCCA_E_ARG;
@@ -1086,6 +1093,7 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
     h->d_pol_image.reset(); h->d_pol_layers.reset(); h->pol_filled = false;
     drop_policy_symmetry(h);
     drop_policy_mirror_loss(h);
+    drop_policy_mirror_dup(h);
     return MOCCA_OK;
   }
   auto bad = [&](const std::string& what) { h->err = "mocca_set_policy: " + what; return MOCCA_E_ARG; };
@@ -1106,6 +1114,7 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
   std::memcpy(h->pol_wt_off, im.wt_off, sizeof(im.wt_off));
   drop_policy_symmetry(h);   // the shapes may have changed
   drop_policy_mirror_loss(h);
+  drop_policy_mirror_dup(h);
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy"); }
 
@@ -1157,6 +1166,8 @@ int mocca_set_policy_symmetry(mocca_handle h, const int32_t* in_perm_host, const
   }
   if (h->d_pol_ml_perm)
     return bad("a mirror loss is attached (mocca_set_policy_mirror_loss): a symmetric network has no mirror loss, detach it first");
+  if (h->d_pol_dup_perm)
+    return bad("duplicated rows are attached (mocca_set_policy_mirror_dup): they train the plain policy, detach them first");
   DevBuf<int32_t> d_perm;
   DevBuf<float> d_sign;
   hipError_t e = hipSuccess;
@@ -1183,6 +1194,8 @@ int mocca_set_policy_mirror_loss(mocca_handle h, const int32_t* in_perm_host, co
   }
   if (h->pol.in_perm)
     return bad("the policy is mirror-symmetric (mocca_set_policy_symmetry): its mirror loss is zero by construction, detach the symmetry first");
+  if (h->d_pol_dup_perm)
+    return bad("duplicated rows are attached (mocca_set_policy_mirror_dup): one symmetry method at a time, detach them first");
   if (!std::isfinite(mirror_coef) || mirror_coef < 0.0) return bad("mirror_coef must be finite and not negative");
   DevBuf<int32_t> d_perm;
   DevBuf<float> d_sign;
@@ -1194,6 +1207,31 @@ int mocca_set_policy_mirror_loss(mocca_handle h, const int32_t* in_perm_host, co
   h->pol_ml_coef = mirror_coef;
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy_mirror_loss"); }
+
+int mocca_set_policy_mirror_dup(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
+                                const float* act_sign_host) try {
+  if (!h) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  auto bad = [&](const std::string& what) { h->err = "mocca_set_policy_mirror_dup: " + what; return MOCCA_E_ARG; };
+  if (!h->d_pol_image) return bad("needs a policy (mocca_set_policy)");
+  if (!in_perm_host) {   // detach
+    if (int rc = commit_ready(h, "mocca_set_policy_mirror_dup")) return rc;
+    drop_policy_mirror_dup(h);
+    return MOCCA_OK;
+  }
+  if (h->pol.in_perm)
+    return bad("the policy is mirror-symmetric (mocca_set_policy_symmetry): a row and its mirror image give it one gradient, detach the symmetry first");
+  if (h->d_pol_ml_perm)
+    return bad("a mirror loss is attached (mocca_set_policy_mirror_loss): one symmetry method at a time, detach it first");
+  DevBuf<int32_t> d_perm;
+  DevBuf<float> d_sign;
+  hipError_t e = hipSuccess;
+  const std::string wrong = upload_mirror_tables(h, in_perm_host, in_sign_host, act_perm_host, act_sign_host, d_perm, d_sign, &e);
+  if (!wrong.empty()) return bad(wrong);
+  if (int rc = commit_ready(h, "mocca_set_policy_mirror_dup", e)) return rc;
+  h->d_pol_dup_perm.swap(d_perm); h->d_pol_dup_sign.swap(d_sign);
+  return MOCCA_OK;
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy_mirror_dup"); }
 
 // what n_floats of a flat parameter tensor must be (mocca_update_policy, mocca_adam_step): -> "" or what is wrong
 static std::string check_n_floats(mocca_handle h, size_t n_floats) {
@@ -1336,13 +1374,13 @@ int mocca_obs_stats(mocca_handle h, const float* rows_dev, int64_t n_rows, int r
   return MOCCA_OK;
 }
 
-// what the handle's attachments make mocca_ppo_update differentiate: the mirror loss, the symmetric network, or the plain policy
+// what the handle's attachments make mocca_ppo_update differentiate: duplicated rows, the mirror loss, the symmetric network, or the plain policy
 static mocca_ppo::PpoMode ppo_mode(mocca_handle h) {
-  return h->d_pol_ml_perm ? mocca_ppo::PPO_MIRROR : h->pol.in_perm ? mocca_ppo::PPO_SYM : mocca_ppo::PPO_PLAIN;
+  return h->d_pol_dup_perm ? mocca_ppo::PPO_DUP : h->d_pol_ml_perm ? mocca_ppo::PPO_MIRROR : h->pol.in_perm ? mocca_ppo::PPO_SYM : mocca_ppo::PPO_PLAIN;
 }
 
-// mocca_ppo_grad (PPO_PLAIN), mocca_ppo_grad_sym (PPO_SYM) and mocca_ppo_grad_mirror (PPO_MIRROR): one argument list, one scratch, the same
-// four launches; the last two share the two-column scratch layout (mocca_ppo.h)
+// mocca_ppo_grad (PPO_PLAIN), mocca_ppo_grad_sym (PPO_SYM), mocca_ppo_grad_mirror (PPO_MIRROR) and mocca_ppo_grad_dup (PPO_DUP): one argument
+// list, one scratch, the same four launches; the last three share the two-column scratch layout (mocca_ppo.h)
 static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, const float* obs_dev, int obs_stride, const float* action_dev,
                     const float* old_logp_dev, const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev,
                     int64_t n_rows, double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev,
@@ -1353,6 +1391,10 @@ static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, c
   auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
   if (!h->d_pol_image || !h->pol_filled) return bad("needs a policy (mocca_set_policy, then mocca_update_policy)");
   const bool sym = mode != PPO_PLAIN;   // twice the columns
+  if (mode != PPO_DUP && h->d_pol_dup_perm)
+    return bad("duplicated rows are attached: the gradient of PPO's loss over the rows and their mirror images is mocca_ppo_grad_dup (or detach them: mocca_set_policy_mirror_dup)");
+  if (mode == PPO_DUP && !h->d_pol_dup_perm)
+    return bad("needs duplicated rows attached (mocca_set_policy_mirror_dup); the plain loss's gradient is mocca_ppo_grad");
   if (mode != PPO_MIRROR && h->d_pol_ml_perm)
     return bad("a mirror loss is attached: the gradient of PPO's loss with the mirror term is mocca_ppo_grad_mirror (or detach it: mocca_set_policy_mirror_loss)");
   if (mode == PPO_MIRROR && !h->d_pol_ml_perm)
@@ -1383,11 +1425,17 @@ static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, c
     a.in_sign = h->d_pol_ml_sign; a.act_sign = h->d_pol_ml_sign.get() + p.in_dim;
     a.mirror_k2 = (float)(2.0 * h->pol_ml_coef);
   }
+  if (mode == PPO_DUP) {
+    a.in_perm = h->d_pol_dup_perm; a.act_perm = h->d_pol_dup_perm.get() + p.in_dim;
+    a.in_sign = h->d_pol_dup_sign; a.act_sign = h->d_pol_dup_sign.get() + p.in_dim;
+  }
   a.obs = obs_dev; a.obs_stride = obs_stride; a.action = action_dev; a.old_logp = old_logp_dev; a.adv = adv_dev; a.returns = returns_dev;
   a.old_value = old_value_dev; a.idx = idx_dev;
   a.n_rows = (int)n_rows;
   a.b_pad = sym ? (int)((n_rows + PPO_SYM_TILE - 1) / PPO_SYM_TILE * 16) : (int)((n_rows + 15) / 16 * 16);   // the scratch's rows (mocca_ppo.h)
   a.clip = (float)clip; a.value_coef = (float)value_coef; a.entropy_coef = (float)entropy_coef; a.inv_b = 1.0f / (float)n_rows;
+  a.n_samples = (int)n_rows;
+  if (mode == PPO_DUP) { a.n_samples = 2 * (int)n_rows; a.inv_b = 1.0f / (float)a.n_samples; }   // every mean is over the 2 B samples
   a.value_clip = value_clip != 0;
   // the scratch (mocca_ppo.h), in floats; every piece a multiple of 4 floats, so that rows stay 16-byte aligned
   const long long bp = a.b_pad;
@@ -1434,6 +1482,13 @@ int mocca_ppo_grad_mirror(mocca_handle h, const float* obs_dev, int obs_stride, 
                           const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev, int64_t n_rows,
                           double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
   return ppo_grad(h, "mocca_ppo_grad_mirror", mocca_ppo::PPO_MIRROR, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev,
+                  idx_dev, n_rows, clip, value_coef, entropy_coef, value_clip, grad_dev, stats_dev, stream);
+}
+
+int mocca_ppo_grad_dup(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev,
+                       const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev, int64_t n_rows,
+                       double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
+  return ppo_grad(h, "mocca_ppo_grad_dup", mocca_ppo::PPO_DUP, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev,
                   idx_dev, n_rows, clip, value_coef, entropy_coef, value_clip, grad_dev, stats_dev, stream);
 }
 

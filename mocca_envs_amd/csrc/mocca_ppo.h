@@ -1,6 +1,7 @@
 // mocca_ppo.h -- the body of a PPO minibatch step up to optimizer.step() as kernels (mocca_ppo.hip): evaluate_actions, the clipped
-// surrogate, the value loss and loss.backward() for the Gaussian actor-critic of mocca_policy.h, plain, mirror-symmetric, or plain with the
-// mirror-symmetry loss added.  mocca_ppo_grad / mocca_ppo_grad_sym / mocca_ppo_grad_mirror (mocca_api.hip) check the caller's arguments, own the scratch and launch them.  The loss and the per-row formulas: include/mocca.h.
+// surrogate, the value loss and loss.backward() for the Gaussian actor-critic of mocca_policy.h, plain, mirror-symmetric, plain with the
+// mirror-symmetry loss added, or plain on mirror-duplicated rows.  mocca_ppo_grad / mocca_ppo_grad_sym / mocca_ppo_grad_mirror /
+// mocca_ppo_grad_dup (mocca_api.hip) check the caller's arguments, own the scratch and launch them.  The loss and the per-row formulas: include/mocca.h.
 //
 // Image.  The kernels read the policy image of mocca_policy.h and, behind it, a SECOND copy of every layer's weights but a net's first,
 // transposed: layer l's W[out][in] as the [in_pad / 16][out_pad / 16][64][4] fragment order of W^T (in and out swap roles and padding), so
@@ -12,7 +13,8 @@
 //   A[l]    [B_pad][out_pad_l]            layer l's output activation y
 //   dZ[l]   [B_pad][out_pad_l]            dL/d(pre-activation) of layer l; between the forward and the backward: act'(x) of layer l
 //   R       [B_pad][PPO_ROW_COLS]         per row: 0 .. 31 the log_std gradient terms, 32 surrogate, 33 value loss, 34 old_logp - logp,
-//                                         35 clipped (0 / 1), 36 the mirror term (mirror loss; else 0), 37 .. 47 zeros
+//                                         35 clipped (0 / 1), 36 the mirror term (mirror loss) or a twin's old_logp - logp (duplicated
+//                                         rows), else 0, 37 .. 47 zeros
 //   P       [n_chunks][p_floats]          chunk partials of the padded gradient: a layer's dW[out_pad][in_pad] row-major at the image's
 //                                         w_off, its db[out_pad] at b_off, the column sums of R at log_std_off
 //   Q       [reduce blocks] f64           sums of grad^2 of the reduce kernel's workgroups
@@ -53,7 +55,16 @@
 // actor column -(u * act_sign) through act_perm; the row's term goes to column 36 of R.  The critic has no mirror term: its workgroups still
 // stage 8 + 8 columns, but the mirrored ones are NOT LIVE -- zero activations and zero slopes stored, zero dA --, so their scratch rows add
 // exactly nothing to the critic's dW and db in launch 2.  Launches 3 and 4 use the plain log_std arithmetic (mode, not the tables, selects
-// it); launch 4 writes stats[7] = (column 36's sum) * ib, which the other modes leave 0.
+// it); launch 4 writes stats[7] = (column 36's sum) * ib, which the plain and symmetric modes leave 0.
+//
+// Duplicated rows (mocca_ppo_grad_dup; include/mocca.h).  The PLAIN policy and the plain loss over 2 B samples: every row and its mirror image
+// (M_o s, M_a a), which borrows the row's old_logp, adv, returns and old_value.  ppo_rows_kernel<PPO_DUP> is the symmetric instance -- its
+// staging, column layout, scratch-row ownership, B_pad, layer loop and backward loop -- with the PLAIN head stage on all 16 columns: lanes
+// 0 .. 15 each run the per-row lines on their own column's heads, a lane >= 8 reading the action as action[act_perm[j]] * act_sign[j]; each
+// writes dA for its own column alone and its R terms to its own scratch row (a mirrored column's row also old_logp - logp in column 36).
+// Actor AND critic mirrored columns are live; columns without a minibatch row stay zeros.  PpoArgs.inv_b is 1 / (2 B) and n_samples 2 B.
+// Launch 2 is unchanged; launches 3 and 4 use the plain log_std arithmetic, and launch 4 writes stats[7] from column 36 as it does for the
+// mirror loss: the twins' share of stats[3].
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,7 +75,7 @@ namespace mocca_ppo {
 
 constexpr int PPO_ROW_COLS = 48;         // floats per row of R
 constexpr int PPO_COL_SURR = 32, PPO_COL_VLOSS = 33, PPO_COL_DLOGP = 34, PPO_COL_CLIPPED = 35, PPO_COL_MIRROR = 36;
-enum PpoMode { PPO_PLAIN = 0, PPO_SYM = 1, PPO_MIRROR = 2 };   // mocca_ppo_grad, mocca_ppo_grad_sym, mocca_ppo_grad_mirror
+enum PpoMode { PPO_PLAIN = 0, PPO_SYM = 1, PPO_MIRROR = 2, PPO_DUP = 3 };   // mocca_ppo_grad, mocca_ppo_grad_sym, mocca_ppo_grad_mirror, mocca_ppo_grad_dup
 constexpr int PPO_MAX_CHUNKS = 16;       // row chunks of launch 2
 constexpr int PPO_CHUNK_MIN_ROWS = 512;  // a chunk holds at least this many rows
 constexpr int PPO_REDUCE_BLOCK = 256;
@@ -103,6 +114,7 @@ struct PpoArgs {
   int n_head, n_reduce_blocks;
   float* grad;                           // [n_head]
   float* stats;                          // [8] or null
+  int n_samples;                         // what stats[4]'s count is divided by: B, PPO_DUP: 2 B
 };
 
 // row chunks of launch 2 for a minibatch of b_pad rows: a function of B alone

@@ -1,6 +1,6 @@
 // mocca_ppo.hip -- PPO's minibatch loss and its gradient with respect to every parameter of the Gaussian actor-critic, plain (mocca_ppo_grad),
-// mirror-symmetric (mocca_ppo_grad_sym) or plain with the mirror-symmetry loss added (mocca_ppo_grad_mirror), on the device.  What each launch
-// does, the scratch and the transposed weight copy: mocca_ppo.h.
+// mirror-symmetric (mocca_ppo_grad_sym), plain with the mirror-symmetry loss added (mocca_ppo_grad_mirror) or plain on mirror-duplicated
+// rows (mocca_ppo_grad_dup), on the device.  What each launch does, the scratch and the transposed weight copy: mocca_ppo.h.
 // The loss and the per-row formulas: include/mocca.h.
 //
 // Arithmetic: the policy kernel's (mocca_policy.hip).  The layer loop below is that kernel's loop, copied -- mocca_policy.hip's kernel is left
@@ -91,17 +91,20 @@ __device__ __forceinline__ void mfma_layer(const f32x4* W, int nkg, int n_ot, co
     if (t < nt_w) epi((wave + 4 * t) * 16 + quad * 4, (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]));
 }
 
-// MODE (header: Symmetric policy, Mirror loss).  PPO_SYM and PPO_MIRROR (SYM below): the 16 MFMA columns are PPO_SYM_TILE = 8 minibatch rows x
+// MODE (header: Symmetric policy, Mirror loss, Duplicated rows).  PPO_SYM, PPO_MIRROR and PPO_DUP (SYM below): the 16 MFMA columns are PPO_SYM_TILE = 8 minibatch rows x
 // {as given, mirrored} -- policy_kernel<true>'s layout: column c is row row0 + c, column 8 + c its mirror image -- and column e's activations
 // live in scratch row 16 * tile + e.  The plain instance has one column per row and scratch row = minibatch row.
 // PPO_SYM's head stage symmetrises mean, log_std and value over the two columns; PPO_MIRROR's leaves the policy the as-given column's and
-// adds the mirror term over the actor's two columns, and its critic's mirrored columns are not live.
+// adds the mirror term over the actor's two columns, and its critic's mirrored columns are not live.  PPO_DUP's runs the plain per-row lines
+// on each of the 16 columns by itself: a mirrored column is one more sample, with the action mirrored too.
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
   __shared__ __attribute__((aligned(16))) float X[2][TILE * LDS_STRIDE];
   constexpr bool SYM = MODE != PPO_PLAIN;     // the two-column layout
   constexpr bool NET = MODE == PPO_SYM;       // the symmetric network's head stage
   constexpr bool ML = MODE == PPO_MIRROR;     // the mirror loss's head stage
+  constexpr bool DUP = MODE == PPO_DUP;       // duplicated rows: the plain head stage, one lane per COLUMN
+  constexpr bool PAIR = NET || ML;            // a head lane owns a row's two columns
   constexpr int ROWS = SYM ? PPO_SYM_TILE : TILE;   // minibatch rows of a workgroup
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row0 = blockIdx.x * ROWS, srow0 = blockIdx.x * TILE, net = blockIdx.y;
@@ -158,18 +161,21 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
     cur ^= 1;
   }
 
-  // head stage: one lane per row -> the row's loss terms (R) and dL/dhead, the backward's first dA, in the other LDS buffer.  SYM: the
+  // head stage: one lane per row -> the row's loss terms (R) and dL/dhead, the backward's first dA, in the other LDS buffer.  PAIR: the
   // row's lane reads the heads of its two columns and writes dA for both; R's terms go to the as-given column's scratch row, the lane of
-  // the mirrored column zeroes that column's R row.  ML: the critic's lane reads its as-given column alone and hands the mirrored one zeros
+  // the mirrored column zeroes that column's R row.  ML: the critic's lane reads its as-given column alone and hands the mirrored one zeros.
+  // DUP: one lane per column, each a sample of its own -- a mirrored column's lane reads the action through act_perm / act_sign and the
+  // row's own old_logp, adv, returns and old_value --, dA and R's terms go to the lane's own column and scratch row
   if (tid < TILE) {
     const int row = row0 + (SYM ? tid & (ROWS - 1) : tid);
     float* R = a.scratch + a.r_off + (size_t)(srow0 + tid) * PPO_ROW_COLS;
     const int head_pad = (a.layers + (size_t)(first + count - 1) * CTRL_LAYER_WORDS)[CL_OUT_PAD];
-    if (SYM && tid >= ROWS) {
+    if (PAIR && tid >= ROWS) {
       for (int j = 0; j < PPO_ROW_COLS; ++j)
         if ((j == PPO_COL_VLOSS) == (net == 1)) R[j] = 0.0f;
     } else {
-      const int mcol = SYM ? ROWS + tid : tid;   // SYM: the row's mirrored column
+      const int mcol = PAIR ? ROWS + tid : tid;   // PAIR: the row's mirrored column
+      const bool twin = DUP && tid >= ROWS;       // DUP: this lane's sample is a mirror image
       const float *head = &X[cur][tid * LDS_STRIDE], *mirror = &X[cur][mcol * LDS_STRIDE];
       float *dA = &X[cur ^ 1][tid * LDS_STRIDE], *dAm = &X[cur ^ 1][mcol * LDS_STRIDE];
       const long long src = row < B ? (a.idx ? (long long)a.idx[row] : row) : 0;
@@ -201,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
         R[PPO_COL_VLOSS] = vloss;
         for (int j = 0; j < head_pad; ++j) {
           dA[j] = j == 0 ? dv : 0.0f;
-          if (SYM) dAm[j] = NET && j == 0 ? dv : 0.0f;
+          if (PAIR) dAm[j] = NET && j == 0 ? dv : 0.0f;
         }
       } else {
         const float* log_std = a.params + a.log_std_off;
@@ -217,6 +223,11 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
           *ls = log_std[j];
           return head[j];
         };
+        // the sample's action j.  DUP, a mirrored column: (M_a a)[j], one f32 operation, exact
+        auto action = [&](int j) {
+          if (DUP && twin) return a.action[(size_t)src * A + a.act_perm[j]] * a.act_sign[j];
+          return a.action[(size_t)src * A + j];
+        };
         float g = 0.0f, surr = 0.0f, dlogp = 0.0f, clipped = 0.0f;
         if (row < B) {
           double lp64 = 0.0;   // the terms are f32, their sum is f64: 21 terms of size ~1 in f32 would leave ~1e-6 in the ratio
@@ -224,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
             float ls;
             const float mu = gaussian(j, &ls);
             const float s = expf(ls);
-            const float d = a.action[(size_t)src * A + j] - mu;
+            const float d = action(j) - mu;
             const float z = d / s;
             lp64 += (double)((-0.5f * z) * z - ls - 0.91893853320467274178f);
           }
@@ -245,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
             g = -g;
           }
         }
-        if (SYM)   // every act_perm[j] below is written once more (a bijection of 0 .. A - 1); the padding stays 0
+        if (PAIR)   // every act_perm[j] below is written once more (a bijection of 0 .. A - 1); the padding stays 0
           for (int j = 0; j < head_pad; ++j) dAm[j] = 0.0f;
         const float ia = 1.0f / (float)A;
         double m64 = 0.0;   // ML: the row's sum of d_j^2, the terms f32
@@ -255,7 +266,7 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
             float ls;
             const float mu = gaussian(j, &ls);
             const float s = expf(ls);
-            const float d = a.action[(size_t)src * A + j] - mu;
+            const float d = action(j) - mu;
             const float z = d / s;
             const float w = z / s;
             dmu = g * w;
@@ -284,7 +295,7 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
           if (j < POL_MAX_ACTION) R[j] = dls;
         }
         R[PPO_COL_SURR] = surr; R[PPO_COL_DLOGP] = dlogp; R[PPO_COL_CLIPPED] = clipped;
-        R[PPO_COL_MIRROR] = ML ? (float)m64 * ia : 0.0f;
+        R[PPO_COL_MIRROR] = ML ? (float)m64 * ia : DUP && twin ? dlogp : 0.0f;   // DUP: old_logp - logp of the twins alone (stats[7])
         for (int j = PPO_COL_MIRROR + 1; j < PPO_ROW_COLS; ++j) R[j] = 0.0f;
       }
     }
@@ -422,9 +433,9 @@ __global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_stats_kernel(PpoArgs a) 
     __syncthreads();
   }
   if (tid != 0 || !a.stats) return;
-  float sum[5];   // the columns 32 .. 35 of R over all rows, and 36 for the mirror loss: the chunks' sums in chunk order
+  float sum[5];   // the columns 32 .. 35 of R over all rows, and 36 for the mirror loss and the duplicated rows: the chunks' sums in chunk order
   sum[4] = 0.0f;
-  for (int k = 0; k < (a.mode == PPO_MIRROR ? 5 : 4); ++k) {
+  for (int k = 0; k < (a.mode >= PPO_MIRROR ? 5 : 4); ++k) {
     const float* P = a.scratch + a.p_off + a.log_std_off + PPO_COL_SURR + k;
     float v = P[0];
     for (int c = 1; c < a.n_chunks; ++c) v += P[(size_t)c * a.p_floats];
@@ -440,15 +451,16 @@ __global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_stats_kernel(PpoArgs a) 
   a.stats[1] = sum[1] * a.inv_b;
   a.stats[2] = (float)h;
   a.stats[3] = sum[2] * a.inv_b;
-  a.stats[4] = sum[3] / (float)a.n_rows;   // a count over B, correctly rounded
+  a.stats[4] = sum[3] / (float)a.n_samples;   // a count over B (PPO_DUP: 2 B), correctly rounded
   a.stats[5] = (float)sq[0];
   a.stats[6] = 0.0f;
-  a.stats[7] = sum[4] * a.inv_b;   // L_m: the rows' terms already carry the 1 / A; 0 in the other modes
+  a.stats[7] = sum[4] * a.inv_b;   // PPO_MIRROR: L_m, the rows' terms already carry the 1 / A; PPO_DUP: the twins' share of stats[3]; else 0
 }
 
 void launch_ppo(hipStream_t s, const PpoArgs& a) {
   if (a.mode == PPO_SYM) hipLaunchKernelGGL(ppo_rows_kernel<PPO_SYM>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   else if (a.mode == PPO_MIRROR) hipLaunchKernelGGL(ppo_rows_kernel<PPO_MIRROR>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
+  else if (a.mode == PPO_DUP) hipLaunchKernelGGL(ppo_rows_kernel<PPO_DUP>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(ppo_rows_kernel<PPO_PLAIN>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(a.n_tiles, a.n_chunks), dim3(64), 0, s, a);
   hipLaunchKernelGGL(ppo_reduce_kernel, dim3(a.n_reduce_blocks), dim3(PPO_REDUCE_BLOCK), 0, s, a);

@@ -71,11 +71,13 @@ SYMBOLS = {
     "mocca_act_step": (_i, [_vp, _vp, _i, _vp, _i] + [_vp] * 9),
     "mocca_set_policy_symmetry": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mocca_set_policy_mirror_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _d]),
+    "mocca_set_policy_mirror_dup": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mocca_gae": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _d, _d, _d, _vp, _vp, _i, _d, _vp, _vp]),
     "mocca_obs_stats": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, _d, _vp, _vp, _vp]),
     "mocca_ppo_grad": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _d, _d, _d, _i, _vp, _vp, _vp]),
     "mocca_ppo_grad_sym": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _d, _d, _d, _i, _vp, _vp, _vp]),
     "mocca_ppo_grad_mirror": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _d, _d, _d, _i, _vp, _vp, _vp]),
+    "mocca_ppo_grad_dup": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _d, _d, _d, _i, _vp, _vp, _vp]),
     "mocca_adam_step": (_i, [_vp, _vp, _sz, _vp, C.c_int64, _vp, _vp, _d, _d, _d, _d, _d, _vp]),
     "mocca_ppo_update": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _i, _d, _d, _d, _i, _vp, _sz, C.c_int64, _vp, _vp,
                               _d, _d, _d, _d, _d, _u64, _vp, _vp]),

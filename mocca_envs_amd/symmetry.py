@@ -14,7 +14,7 @@ for the PPO update.
 """
 from __future__ import annotations
 
-from typing import Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -122,6 +122,17 @@ def mirror_loss(actor_mean, obs: torch.Tensor, transform: MirrorTransform) -> to
     `transform` in `obs`'s dtype."""
     d = actor_mean(obs) - transform.act(actor_mean(transform.obs(obs)))
     return d.pow(2).mean()
+
+
+def duplicate_minibatch(obs: torch.Tensor, action: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor, returns: torch.Tensor,
+                        old_value: Optional[torch.Tensor], transform: MirrorTransform):
+    """SymmetricRL's duplicated tuples: the B rows followed by their B mirror images -- (M_o obs, M_a action) with the rows' OWN old_logp,
+    adv, returns and old_value (None stays None) -- as 2 B-row tensors, what mocca_ppo_grad_dup trains on without building them.  A
+    mirror only permutes and flips signs: the twins' entries are exact.  `transform` in `obs`'s dtype, `obs` RAW (un-normalised).
+    -> (obs, action, old_logp, adv, returns, old_value)"""
+    twice = lambda x: None if x is None else torch.cat([x, x], 0)
+    return (torch.cat([obs, transform.obs(obs)], 0), torch.cat([action, transform.act(action)], 0), twice(old_logp), twice(adv),
+            twice(returns), twice(old_value))
 
 
 class SymmetricGaussian(torch.nn.Module):

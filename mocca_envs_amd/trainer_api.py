@@ -381,6 +381,12 @@ class TorchVecEnv:
             raise NotImplementedError("set_policy_mirror_loss needs one handle (sub_batches=1)")
         self.venv.set_policy_mirror_loss(tables, coef)
 
+    def set_policy_mirror_dup(self, tables) -> None:
+        """attach the mirror-duplicated rows for `ppo_grad` / `ppo_update` (None detaches): `VecEnv.set_policy_mirror_dup`.  One handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("set_policy_mirror_dup needs one handle (sub_batches=1)")
+        self.venv.set_policy_mirror_dup(tables)
+
     def ppo_grad(self, obs, action, old_logp, adv, returns, *args, **kw) -> dict:
         """PPO's minibatch loss and its gradient over the rollout storage, four launches: `VecEnv.ppo_grad` -- of the symmetric network
         where the attached policy carries mirror tables (`symmetric_policy`).  One handle only."""

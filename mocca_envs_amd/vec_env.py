@@ -281,18 +281,19 @@ class VecEnv:
     # ---- the trainer's own policy on the device (include/mocca.h mocca_set_policy / mocca_update_policy / mocca_act / mocca_act_step) ----
     policy = None
     mirror_loss = None   # (tables, coef) while set_policy_mirror_loss has one attached
+    mirror_dup = None    # tables while set_policy_mirror_dup has them attached
 
     def set_policy(self, policy) -> None:
         """Attach a `policy.DevicePolicy` (None detaches): its shapes size the kernel's image, its weights are uploaded (update_policy).
         May synchronise."""
         if policy is None:
             _lib.check(self.lib.mocca_set_policy(self.h, None, 0, 0, 0, 0.0), self.h)
-            self.policy = self.mirror_loss = None
+            self.policy = self.mirror_loss = self.mirror_dup = None
             return
         table = np.ascontiguousarray(policy.table(), np.int32)
         _lib.check(self.lib.mocca_set_policy(self.h, table.ctypes.data_as(C.c_void_p), table.shape[0], int(policy.in_dim), int(policy.act_dim),
                                              float(policy.clip)), self.h)
-        self.policy, self.mirror_loss = policy, None   # mocca_set_policy has dropped both attachments
+        self.policy, self.mirror_loss, self.mirror_dup = policy, None, None   # mocca_set_policy has dropped every attachment
         self.update_policy(policy)
         if getattr(policy, "symmetry", None) is not None:      # after the shapes: mocca_set_policy has dropped whatever was attached
             self.set_policy_symmetry(policy.symmetry)
@@ -331,6 +332,25 @@ class VecEnv:
             raise ValueError(f"the mirror tables have {self.policy.in_dim} input and {self.policy.act_dim} action entries")
         _lib.check(self.lib.mocca_set_policy_mirror_loss(self.h, *[x.ctypes.data_as(C.c_void_p) for x in t], float(coef)), self.h)
         self.mirror_loss = (tuple(t), float(coef))
+
+    def set_policy_mirror_dup(self, tables) -> None:
+        """Attach SymmetricRL's DUPLICATED TUPLES to the policy set_policy attached, for the gradient only: `tables` as in
+        set_policy_symmetry (`policy_mirror_tables(policy)` gives this env's).  act() and act_step() keep running the plain policy;
+        ppo_grad() and ppo_update() then differentiate PPO's plain loss over every row AND its mirror image (M_o s, M_a a), 2 B samples
+        (mocca_ppo_grad_dup); a twin borrows its row's old_logp, so stats[7], the twins' share of stats[3], measures how far off-policy
+        the policy's asymmetry puts them.  None detaches.  Exclusive with a symmetric policy and with a mirror loss; set_policy() drops
+        it, update_policy() leaves it alone.  May synchronise."""
+        if self.policy is None:
+            raise _lib.MoccaError("set_policy_mirror_dup needs a policy (set_policy)")
+        if tables is None:
+            _lib.check(self.lib.mocca_set_policy_mirror_dup(self.h, None, None, None, None), self.h)
+            self.mirror_dup = None
+            return
+        t = [np.ascontiguousarray(x, d) for x, d in zip(tables, (np.int32, np.float32, np.int32, np.float32))]
+        if (t[0].size, t[1].size, t[2].size, t[3].size) != (self.policy.in_dim, self.policy.in_dim, self.policy.act_dim, self.policy.act_dim):
+            raise ValueError(f"the mirror tables have {self.policy.in_dim} input and {self.policy.act_dim} action entries")
+        _lib.check(self.lib.mocca_set_policy_mirror_dup(self.h, *[x.ctypes.data_as(C.c_void_p) for x in t]), self.h)
+        self.mirror_dup = tuple(t)
 
     def policy_mirror_tables(self, policy):
         """The mirror tables (in_perm, in_sign, act_perm, act_sign) of THIS env for `policy` (a `policy.DevicePolicy`): built from
@@ -467,7 +487,7 @@ class VecEnv:
                                             ptr(inv_std_out), self._stream()), self.h)
         self._out()
 
-    # ---- a PPO minibatch step on the device (include/mocca.h mocca_ppo_grad / mocca_ppo_grad_sym / mocca_ppo_grad_mirror) ----
+    # ---- a PPO minibatch step on the device (include/mocca.h mocca_ppo_grad / mocca_ppo_grad_sym / mocca_ppo_grad_mirror / mocca_ppo_grad_dup) ----
     def ppo_grad(self, obs: torch.Tensor, action: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor, returns: torch.Tensor,
                  idx: Optional[torch.Tensor] = None, old_value: Optional[torch.Tensor] = None, clip: float = 0.2, value_coef: float = 0.5,
                  entropy_coef: float = 0.0, value_clip: bool = False, grad: Optional[torch.Tensor] = None,
@@ -482,21 +502,23 @@ class VecEnv:
         (`DevicePolicy(symmetry=)`, `set_policy_symmetry`) takes the symmetric network's gradient, what autograd gives through
         `symmetry.SymmetricGaussian.evaluate_actions` (mocca_ppo_grad_sym: the same four launches on twice the columns; the entropy is the
         symmetrised log_std's).  With a mirror loss attached (`set_policy_mirror_loss`) the loss gains coef * L_m and stats[7] is L_m
-        (mocca_ppo_grad_mirror: the plain policy, the same layout as the symmetric call).  At most 2^21 rows in either case, 2^22
+        (mocca_ppo_grad_mirror: the plain policy, the same layout as the symmetric call).  With duplicated rows attached
+        (`set_policy_mirror_dup`) the plain loss runs over the B rows and their B mirror images, every mean over 2 B, and stats[7] is the
+        twins' share of stats[3] (mocca_ppo_grad_dup: the same layout again).  At most 2^21 rows in any of the three cases, 2^22
         otherwise.  `grad` / `stats`: caller-owned outputs, allocated where none is
         given.  The same inputs give the same bits on every run."""
         if self.policy is None:
             raise _lib.MoccaError("ppo_grad needs a policy (set_policy)")
         symmetric = getattr(self.policy, "symmetry", None) is not None
-        mirror = self.mirror_loss is not None
+        mirror, dup = self.mirror_loss is not None, self.mirror_dup is not None
         _, stride, n_batch = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, idx, old_value, clip, value_coef,
-                                          entropy_coef, value_clip, grad, stats, symmetric=symmetric or mirror)
+                                          entropy_coef, value_clip, grad, stats, symmetric=symmetric or mirror or dup)
         f32 = dict(dtype=torch.float32, device=self.device)
         grad = torch.empty(self.policy.n_head(), **f32) if grad is None else grad
         stats = torch.empty(8, **f32) if stats is None else stats
         ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
         self._in()
-        call = self.lib.mocca_ppo_grad_mirror if mirror else self.lib.mocca_ppo_grad_sym if symmetric else self.lib.mocca_ppo_grad
+        call = self.lib.mocca_ppo_grad_dup if dup else self.lib.mocca_ppo_grad_mirror if mirror else self.lib.mocca_ppo_grad_sym if symmetric else self.lib.mocca_ppo_grad
         _lib.check(call(self.h, ptr(obs), stride, ptr(action), ptr(old_logp), ptr(adv), ptr(returns), ptr(old_value), ptr(idx), n_batch, float(clip),
                         float(value_coef), float(entropy_coef), int(bool(value_clip)), ptr(grad), ptr(stats), self._stream()), self.h)
         self._out()
@@ -529,12 +551,12 @@ class VecEnv:
         -- the same bits as that loop.  The storage tensors are `ppo_grad`'s, `params` / `state` / `n_params` / `lr` .. `max_grad_norm`
         `adam_step`'s; `params` must hold what `update_policy` last received.  The shuffle is keyed by `seed` and the state's step count.
         -> {"stats": [epochs * M, 8]}: `ppo_grad`'s statistics per minibatch, [6] the clip coefficient applied (0: a skipped step), [7] L_m
-        with a mirror loss attached;
+        with a mirror loss attached, the twins' share of [3] with duplicated rows;
         `stats`: a caller-owned output.  Nothing synchronises or is read on the host; capturable after one warm call of the same shapes
         (the scalars and the seed are baked into the capture)."""
         if self.policy is None:
             raise _lib.MoccaError("ppo_update needs a policy (set_policy)")
-        symmetric = getattr(self.policy, "symmetry", None) is not None or self.mirror_loss is not None   # either halves the row bound
+        symmetric = getattr(self.policy, "symmetry", None) is not None or self.mirror_loss is not None or self.mirror_dup is not None   # each halves the row bound
         n_rows, stride, _ = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, None, old_value, clip, value_coef,
                                          entropy_coef, value_clip, None, None, symmetric=symmetric)
         n_params = _ro.adam_args(self.policy, self.device, params, None, state, n_params, lr, betas, eps, max_grad_norm)

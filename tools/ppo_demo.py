@@ -5,10 +5,11 @@ that LEARNS, and what does the step kernel cost on the workload a trained policy
 Plain PPO in the pytorch-a2c-ppo-acktr mould the reference's trainers (README.md:33-39) follow -- Gaussian MLP policy 2 x 256 tanh, separate value
 net, GAE(0.95), clipped surrogate, Adam, running observation normalisation -- with everything on the device: the step kernel writes observation /
 reward / masks / bad_masks straight into the rollout storage (`step(action, into=...)`), Monitor's statistics come from `envs.episode_totals`.
-No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it SymmetricRL's symmetric network, --mirror-loss its symmetry loss.
+No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it SymmetricRL's symmetric network, --mirror-loss its symmetry loss,
+--mirror-dup its duplicated tuples.
 
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
-                           [--device-policy [--device-returns [--device-grad [--device-update]]]] [--symmetric | --mirror-loss COEF]
+                           [--device-policy [--device-returns [--device-grad [--device-update]]]] [--symmetric | --mirror-loss COEF | --mirror-dup]
 --device-policy: collection runs through `envs.act_step(obs[t], into=...)` -- the policy kernel (normalisation, both nets, the sample, its
 log-probability, the value) and the step kernel, two launches per step and no torch op; `envs.update_policy(flat)` once per iteration hands the
 kernel the optimiser's new weights and the running observation statistics.  The noise then comes from the kernel, not from torch.randn.
@@ -32,7 +33,15 @@ M_a pi(n(M_o s)))^2) over the env's get_mirror_indices(), added to the plain pol
 iteration's mean of the term over its minibatches, and COEF 0 logs the asymmetry of an unconstrained run.  The torch update adds it through
 autograd; with --device-grad / --device-update `envs.set_policy_mirror_loss` attaches the tables and the weight, each minibatch's gradient is
 mocca_ppo_grad_mirror and the term is its stats[7].  Collection stays the plain policy's: one forward pass per step.
---verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor; with
+--mirror-dup (not with --symmetric or --mirror-loss): SymmetricRL's duplicated tuples, the plain policy trained on every minibatch row AND
+its mirror image (M_o s, M_a a) with the row's own old_logp, advantage and return -- 2 B samples per minibatch.  The torch update builds them
+with `symmetry.duplicate_minibatch`; with --device-grad / --device-update `envs.set_policy_mirror_dup` attaches the tables and each
+minibatch's gradient is mocca_ppo_grad_dup on the B rows as they lie.  The logged lines carry `mirror_loss`, `symmetry.mirror_loss` of the
+current actor on the rollout's first row of observations (computed at logged iterations only, never trained on), and `twin_dlogp`, the mean
+since the last logged line of stats[7]: the twins' share of mean(old_logp - logp), how far off-policy the policy's asymmetry puts them.
+--verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor
+(--mirror-dup: on that minibatch's rows whose ratio and whose twin's ratio lie more than 1e-4 from the clip bounds, where the surrogate's
+gradient jumps and two float32 evaluations may disagree on a sample's side; the twins' ratios are spread over the bounds); with
 --device-update, whose minibatches are drawn on the device, it takes one `envs.ppo_grad` on a torch.randperm chunk ahead of the update.
 writes <out>.jsonl (one line per logged iteration: env-steps so far, mean episode return / length of the episodes that ended since the last line,
 wall-clock env-steps/s of the whole loop incl. learning) and <out>_policy.npz (weights + observation statistics: `bench.py`'s workload
@@ -71,6 +80,7 @@ def main():
     ap.add_argument("--device-update", action="store_true", help="with --device-grad: the whole update -- shuffle, gradient, clip, Adam, repack for every epoch and minibatch -- as one call (ppo_update)")
     ap.add_argument("--symmetric", action="store_true", help="SymmetricRL's symmetric network: mean, value and log_std symmetrised through the env's mirror tables")
     ap.add_argument("--mirror-loss", type=float, default=None, metavar="COEF", help="SymmetricRL's mirror-symmetry loss with this weight (0: only logged); not with --symmetric")
+    ap.add_argument("--mirror-dup", action="store_true", help="SymmetricRL's duplicated tuples: train on every row and its mirror image; not with --symmetric or --mirror-loss")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args()
     if args.device_grad and not args.device_returns:
@@ -81,6 +91,8 @@ def main():
         ap.error("--mirror-loss is not for --symmetric: a symmetric network has no mirror loss")
     if args.mirror_loss is not None and not args.mirror_loss >= 0.0:
         ap.error("--mirror-loss takes a weight >= 0")
+    if args.mirror_dup and (args.symmetric or args.mirror_loss is not None):
+        ap.error("--mirror-dup is not for --symmetric or --mirror-loss: one symmetry method at a time")
     if args.verify_grad and not args.device_grad:
         ap.error("--verify-grad requires --device-grad")
     if args.device_returns and not args.device_policy:
@@ -129,6 +141,11 @@ def main():
         mirror_tf = MirrorTransform(envs.get_mirror_indices(), od, ad, device=dev)
         lm_sum, lm_n = torch.zeros((), device=dev), 0      # the term over the minibatches since the last logged line
 
+    if args.mirror_dup:
+        from mocca_envs_amd.symmetry import MirrorTransform, duplicate_minibatch, mirror_loss
+        mirror_tf = MirrorTransform(envs.get_mirror_indices(), od, ad, device=dev)
+        td_sum, td_n = torch.zeros((), device=dev), 0      # stats[7] over the minibatches since the last logged line
+
     def aux_loss(mb):
         """what --mirror-loss adds to the minibatch's loss -> (COEF * L_m or 0, L_m or None); the mirror acts on the RAW rows"""
         if args.mirror_loss is None:
@@ -136,8 +153,18 @@ def main():
         l_m = mirror_loss(lambda x: pi(norm(x)), raw_all[mb], mirror_tf)
         return args.mirror_loss * l_m, l_m
 
+    def minibatch(mb):
+        """(old_logp, adv, returns) of the minibatch, [b, 1] each; --mirror-dup: of its 2 b samples, the twins carrying their rows' own"""
+        if args.mirror_dup:
+            return duplicate_minibatch(raw_all[mb], a_all[mb], lp_all[mb], adv_all[mb], ret_all[mb], None, mirror_tf)[2:5]
+        return lp_all[mb], adv_all[mb], ret_all[mb]
+
     def evaluate(mb):
-        """(logp [b, 1], value [b, 1]) of the minibatch's stored actions under the current parameters"""
+        """(logp [b, 1], value [b, 1]) of the minibatch's stored actions under the current parameters; --mirror-dup: [2 b, 1], the rows then
+        their mirror images, mirrored on the RAW rows"""
+        if args.mirror_dup:
+            o2, a2 = duplicate_minibatch(raw_all[mb], a_all[mb], lp_all[mb], adv_all[mb], ret_all[mb], None, mirror_tf)[:2]
+            return logprob(pi(norm(o2)), a2), vf(norm(o2))
         if args.symmetric:      # the mirror acts on the RAW row
             lp, _, v = sym.evaluate_actions(raw_all[mb], a_all[mb], mean, inv_std_now(), 10.0)
             return lp.unsqueeze(-1), v.unsqueeze(-1)
@@ -149,6 +176,8 @@ def main():
         envs.attach_policy(envs.symmetric_policy(dp) if args.symmetric else dp)
         if args.mirror_loss is not None and args.device_grad:      # for the gradient only: act_step keeps running the plain policy
             envs.set_policy_mirror_loss(envs.policy_mirror_tables(dp), args.mirror_loss)
+        if args.mirror_dup and args.device_grad:      # likewise
+            envs.set_policy_mirror_dup(envs.policy_mirror_tables(dp))
         row_act = lambda t: dict(row(t), action=S["act"][t], logp=S["logp"][t], value=S["value"][t])
         # DevicePolicy.flat_params()'s order, built on the device: layers of pi then vf (W, b), log_std, mean, 1 / sqrt(var + eps)
         flat_params = lambda: torch.cat([q.reshape(-1) for net in (pi, vf) for m in net if isinstance(m, nn.Linear) for q in (m.weight, m.bias)]
@@ -181,12 +210,23 @@ def main():
             opt = torch.optim.Adam([w_flat], lr=args.lr, eps=1e-5)
         g_buf, s_buf = torch.zeros(n_head, device=dev), torch.zeros(8, device=dev)
 
+    def off_the_clip_bounds(mb):
+        """--mirror-dup: the rows of `mb` whose ratio and whose twin's ratio both lie more than 1e-4 from 1 - clip and 1 + clip.  The
+        surrogate's gradient jumps there, and two float32 evaluations may put a sample on either side: --verify-grad compares the two
+        gradients on the rows where the loss is differentiable, as the checkers of tests/ do by construction.  A plain minibatch's ratios
+        are all 1 +- 1e-6 at the first minibatch; the twins' are spread over the bounds by the policy's asymmetry."""
+        with torch.no_grad():
+            r = (evaluate(mb)[0] - minibatch(mb)[0]).exp().reshape(2, -1)
+            near = ((r - (1 - args.clip)).abs() < 1e-4) | ((r - (1 + args.clip)).abs() < 1e-4)
+        return mb[~near.any(0)]
+
     def verify_grad(mb, it):
         """g_buf holds ppo_grad's gradient of minibatch `mb` at the current parameters: print its largest difference from autograd"""
         lp, v = evaluate(mb)
-        ratio = (lp - lp_all[mb]).exp()
-        surr = torch.min(ratio * adv_all[mb], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_all[mb]).mean()
-        v_loss = 0.5 * (v - ret_all[mb]).pow(2).mean()
+        lp_old, adv_mb, ret_mb = minibatch(mb)
+        ratio = (lp - lp_old).exp()
+        surr = torch.min(ratio * adv_mb, ratio.clamp(1 - args.clip, 1 + args.clip) * adv_mb).mean()
+        v_loss = 0.5 * (v - ret_mb).pow(2).mean()
         auto = torch.autograd.grad(-surr + 0.5 * v_loss + aux_loss(mb)[0], head[:-1] if args.fixed_std else head)
         worst, pos = 0.0, 0
         for g in auto:
@@ -272,6 +312,8 @@ def main():
         if args.device_update:
             if args.verify_grad:      # the update draws its minibatches on the device: one gradient call on a chunk of our own, ahead of it
                 mb = torch.randperm(B, device=dev)[:B // args.minibatches]
+                if args.mirror_dup:
+                    mb = off_the_clip_bounds(mb)
                 envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf)
                 verify_grad(mb, it)
             # ppo.update() as one call: epochs x minibatches of [shuffle, ppo_grad, clip, Adam, repack]; u_stats keeps a row per minibatch
@@ -280,18 +322,26 @@ def main():
                             max_grad_norm=0.5, seed=args.seed, stats=u_stats)
             if args.mirror_loss is not None:
                 lm_sum += u_stats[:, 7].sum(); lm_n += u_stats.shape[0]
+            if args.mirror_dup:
+                td_sum += u_stats[:, 7].sum(); td_n += u_stats.shape[0]
         for ep in range(0 if args.device_update else args.epochs):
             perm = torch.randperm(B, device=dev)
             for k, mb in enumerate(perm.chunk(args.minibatches)):
                 if args.device_grad:
                     # evaluate_actions, the clipped surrogate, the value loss and backward() as one call on the raw storage (--symmetric: of
                     # the symmetric network -- the attached policy carries the mirror tables)
+                    if args.verify_grad and ep == 0 and k == 0 and args.mirror_dup:      # a call of its own on the rows off the clip bounds
+                        mb_v = off_the_clip_bounds(mb)
+                        envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb_v, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf)
+                        verify_grad(mb_v, it)
                     envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf)
-                    if args.verify_grad and ep == 0 and k == 0:
+                    if args.verify_grad and ep == 0 and k == 0 and not args.mirror_dup:
                         verify_grad(mb, it)
                     with torch.no_grad():
                         if args.mirror_loss is not None:
                             lm_sum += s_buf[7]; lm_n += 1
+                        if args.mirror_dup:
+                            td_sum += s_buf[7]; td_n += 1
                         sq = s_buf[5]
                         if args.fixed_std:      # log_std is not a parameter then: its entries leave the norm and the step
                             sq = (sq - g_buf[n_head - ad:].square().sum()).clamp(min=0.0)
@@ -302,9 +352,12 @@ def main():
                     envs.update_policy(flat)
                     continue
                 lp, v = evaluate(mb)
-                ratio = (lp - lp_all[mb]).exp()
-                surr = torch.min(ratio * adv_all[mb], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_all[mb]).mean()
-                v_loss = 0.5 * (v - ret_all[mb]).pow(2).mean()
+                lp_old, adv_mb, ret_mb = minibatch(mb)
+                ratio = (lp - lp_old).exp()
+                surr = torch.min(ratio * adv_mb, ratio.clamp(1 - args.clip, 1 + args.clip) * adv_mb).mean()
+                v_loss = 0.5 * (v - ret_mb).pow(2).mean()
+                if args.mirror_dup:      # what mocca_ppo_grad_dup reports in stats[7]: the twins' sum over the 2 b samples
+                    td_sum += (lp_old - lp.detach())[mb.numel():].sum() / (2 * mb.numel()); td_n += 1
                 aux, l_m = aux_loss(mb)
                 if l_m is not None:
                     lm_sum += l_m.detach(); lm_n += 1
@@ -325,6 +378,11 @@ def main():
             if args.mirror_loss is not None:      # the mean of L_m over the minibatches since the last logged line
                 line["mirror_loss"] = float(lm_sum.item() / max(lm_n, 1))
                 lm_sum.zero_(); lm_n = 0
+            if args.mirror_dup:
+                with torch.no_grad():      # the asymmetry of the current actor; monitored, never trained on
+                    line["mirror_loss"] = float(mirror_loss(lambda x: pi(norm(x)), S["obs"][0], mirror_tf).item())
+                line["twin_dlogp"] = float(td_sum.item() / max(td_n, 1))
+                td_sum.zero_(); td_n = 0
             if "Stepper" in args.env_id:      # next_step_index of the running episodes (the step's info word): how far along the 20 planks the batch is
                 line["mean_next_step_index"] = float(envs.venv.info.float().mean().item())
             log.write(json.dumps(line) + "\n"); log.flush()

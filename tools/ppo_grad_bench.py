@@ -10,6 +10,10 @@
   python tools/ppo_grad_bench.py grad --mirror-loss   [--out profiles/ppo_grad_mirror.json]
       the same for the plain policy with the mirror-symmetry loss attached (the env's own mirror tables, coef 4): mocca_ppo_grad_mirror
       against the plain minibatch plus `symmetry.mirror_loss` in torch eager, as tools/ppo_demo.py --mirror-loss does it; both in one process.
+  python tools/ppo_grad_bench.py grad --mirror-dup   [--out profiles/ppo_grad_dup.json]
+      the same for the plain policy with duplicated rows attached (the env's own mirror tables): mocca_ppo_grad_dup on the B rows against
+      the plain minibatch of `symmetry.duplicate_minibatch`'s 2 B rows in torch eager, as tools/ppo_demo.py --mirror-dup does it; then, in
+      the same process, mocca_ppo_grad_sym (the same layout) and the plain mocca_ppo_grad on the same rows.
   python tools/ppo_grad_bench.py act --key NAME [--package-root DIR] [--out ...]
       `update_policy` and `act` at 4096 envs, 7 blocks of 200 warm calls, stored under "act_update"[NAME].  --package-root: the tree whose
       mocca_envs_amd (with its built library) is imported -- a checkout of the parent commit gives the A/B; run the two alternately.
@@ -62,15 +66,17 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--symmetric", action="store_true", help="grad: the mirror-symmetric policy (mocca_ppo_grad_sym against SymmetricGaussian)")
     ap.add_argument("--mirror-loss", action="store_true", help="grad: the mirror-symmetry loss (mocca_ppo_grad_mirror against symmetry.mirror_loss)")
+    ap.add_argument("--mirror-dup", action="store_true", help="grad: duplicated rows (mocca_ppo_grad_dup against symmetry.duplicate_minibatch's 2 B rows)")
     ap.add_argument("--key", default="this")
     ap.add_argument("--package-root", default=ROOT)
     ap.add_argument("--kernel-db")
     args = ap.parse_args()
-    if (args.symmetric or args.mirror_loss) and args.mode != "grad":
-        ap.error("--symmetric and --mirror-loss go with the grad mode")
-    if args.symmetric and args.mirror_loss:
-        ap.error("--symmetric or --mirror-loss, not both")
-    args.out = args.out or os.path.join(ROOT, "profiles", "ppo_grad_sym.json" if args.symmetric else "ppo_grad_mirror.json" if args.mirror_loss else "ppo_grad.json")
+    if (args.symmetric or args.mirror_loss or args.mirror_dup) and args.mode != "grad":
+        ap.error("--symmetric, --mirror-loss and --mirror-dup go with the grad mode")
+    if args.symmetric + args.mirror_loss + args.mirror_dup > 1:
+        ap.error("--symmetric, --mirror-loss or --mirror-dup, one of them")
+    args.out = args.out or os.path.join(ROOT, "profiles", "ppo_grad_sym.json" if args.symmetric else "ppo_grad_mirror.json" if args.mirror_loss
+                                        else "ppo_grad_dup.json" if args.mirror_dup else "ppo_grad.json")
     if args.mode == "per-launch":
         import sqlite3
         import statistics
@@ -112,6 +118,8 @@ def main():
     env.set_policy(dp)
     if args.mirror_loss:
         env.set_policy_mirror_loss(env.policy_mirror_tables(dp), 4.0)
+    if args.mirror_dup:
+        env.set_policy_mirror_dup(env.policy_mirror_tables(dp))
     f = lambda *s: torch.from_numpy(rng.normal(0, 1, s).astype(np.float32)).cuda()
     obs, act, olp, adv, ret = f(ROWS, 52) * 3, f(ROWS, 21), f(ROWS) - 20, f(ROWS), f(ROWS)
     idx = torch.randperm(ROWS, device="cuda")[:B]
@@ -124,12 +132,21 @@ def main():
         env.close()
         return
     res = {"what": f"B = {B} rows gathered from {ROWS}, policy 52 -> 256 -> 256 -> {{21, 1}} tanh, HIP events, 5 blocks of 200 warm calls"}
-    name = "mocca_ppo_grad_sym" if args.symmetric else "mocca_ppo_grad_mirror" if args.mirror_loss else "mocca_ppo_grad"
+    name = "mocca_ppo_grad_sym" if args.symmetric else "mocca_ppo_grad_mirror" if args.mirror_loss else "mocca_ppo_grad_dup" if args.mirror_dup else "mocca_ppo_grad"
+    if args.mirror_dup:
+        res["what"] += ("; the plain policy on the B rows and their B mirror images (the env's mirror tables), torch eager on "
+                        "symmetry.duplicate_minibatch's 2 B rows; mocca_ppo_grad_sym and mocca_ppo_grad on the same B rows in the same process")
     if args.mirror_loss:
         res["what"] += "; the plain policy with the mirror-symmetry loss of the env's mirror tables at coef 4, torch eager through symmetry.mirror_loss"
     if args.symmetric:
         res["what"] += "; the mirror-symmetric policy of the env's mirror tables, torch eager through symmetry.SymmetricGaussian"
     res[name] = timed(torch, call)
+    if args.mirror_dup:      # the same layout, and the plain call, in this process
+        env.set_policy_mirror_dup(None)
+        env.set_policy_symmetry(env.policy_mirror_tables(dp))
+        res["mocca_ppo_grad_sym"] = timed(torch, call)
+        env.set_policy_symmetry(None)
+        res["mocca_ppo_grad"] = timed(torch, call)
 
     def mlp(o):
         return nn.Sequential(nn.Linear(52, 256), nn.Tanh(), nn.Linear(256, 256), nn.Tanh(), nn.Linear(256, o)).cuda()
@@ -166,6 +183,19 @@ def main():
         opt.zero_grad(set_to_none=True)
         (-surr + 0.5 * v_loss + 4.0 * l_m).backward()
 
+    if args.mirror_dup:
+        from mocca_envs_amd.symmetry import MirrorTransform, duplicate_minibatch
+        tf = MirrorTransform(env.get_mirror_indices(), 52, 21, device="cuda")
+
+    def eager_dup():
+        o2, a2, lp2, adv2, ret2, _ = duplicate_minibatch(obs[idx], act[idx], lp_all[idx], adv_all[idx], ret_all[idx], None, tf)
+        o2 = o2.clamp(-10, 10)
+        ratio = (logprob(pi(o2), a2) - lp2).exp()
+        surr = torch.min(ratio * adv2, ratio.clamp(0.8, 1.2) * adv2).mean()
+        v_loss = 0.5 * (vf(o2) - ret2).pow(2).mean()
+        opt.zero_grad(set_to_none=True)
+        (-surr + 0.5 * v_loss).backward()
+
     def eager():
         mu = pi(o_all[idx])
         ratio = (logprob(mu, act[idx]) - lp_all[idx]).exp()
@@ -174,7 +204,7 @@ def main():
         opt.zero_grad(set_to_none=True)
         (-surr + 0.5 * v_loss).backward()
 
-    res["torch_eager"] = timed(torch, eager_sym if args.symmetric else eager_mirror if args.mirror_loss else eager)
+    res["torch_eager"] = timed(torch, eager_sym if args.symmetric else eager_mirror if args.mirror_loss else eager_dup if args.mirror_dup else eager)
     res["speedup"] = round(res["torch_eager"]["us_per_call_median"] / res[name]["us_per_call_median"], 2)
     merge(args.out, "minibatch", res)
     print(json.dumps(res))
