@@ -271,6 +271,17 @@ int mocca_set_heightfield(mocca_handle h, const float *heights_host, int rows, i
  * obs_dev pointed: the controller's next input.  It is defined from the first such call after attaching. */
 int mocca_set_base_controller(mocca_handle h, const float *params_host, size_t n_floats, const int32_t *layers_host, int n_layers_total,
                               double action_scale);
+/* Observation statistics for the attached controller: what a controller trained by this project's own PPO on a Stepper id carries (the
+ * policy kernel normalises its input, mocca_set_policy above all nets; bare layers cannot express the clamp).  mean_host and inv_std_host:
+ * f32 [65] in HOST memory, copied into the handle; they apply to the controller's whole input row [robot_state(50), plan(15) x action_scale],
+ * after the scale and before both nets, entry k < 65 by the policy kernel's line in its order of operations,
+ * v = fminf(fmaxf((v - mean[k]) * inv_std[k], -clip), clip) (inv_std = 1 / sqrt(var + eps), formed by the caller in f32); the padding
+ * columns and the rows past the batch stay exact zeros.  With nothing attached mocca_plan_step gives the bits it gave without this call.
+ * Needs an attached controller.  mean_host == NULL (both NULL) detaches; mocca_set_base_controller drops the statistics on replace and on
+ * detach, as mocca_set_policy drops its attachments.  May synchronise.  Errors (MOCCA_E_ARG with a message, the handle left as it was): a
+ * NULL handle, no controller attached, exactly one of the two arrays NULL, a non-finite mean, an inv_std that is non-finite or negative, a
+ * clip that is not finite and > 0. */
+int mocca_set_base_controller_norm(mocca_handle h, const float *mean_host, const float *inv_std_host, double clip);
 /* env.step(plan) of the planner envs: the controller kernel (one launch: both nets, all envs; f32 on the matrix cores), then the step kernel on
  * its joint actions, both on `stream`; the reward carries the value term -- rew_dev, and with it Monitor's returns, totals and records
  * (mocca_set_episode_stats).  plan_dev [N][15] f32; the rest as mocca_step, and capturable in a hipGraph under the same conditions.
@@ -385,6 +396,13 @@ int mocca_height_scan(mocca_handle h, float *out_dev, int row_stride, const floa
  *                       [N] or NULL, mean_dev [N][act_dim] or NULL.  No allocation, no synchronisation, no atomics, no host state.
  * mocca_act_step        replaces `act()` followed by `envs.step(action)`: mocca_act, then mocca_step on action_dev, on the same stream; the
  *                       step's results are mocca_step's bit for bit, and the pair is capturable in a hipGraph under mocca_step's conditions.
+ * mocca_act_plan_step   replaces, in a trainer of the planner envs' high-level policy, `act()` followed by `envs.step(plan)`: mocca_act with
+ *                       plan_dev [N][15] as its action_dev, then mocca_plan_step on plan_dev, on the same stream -- three launches in a linear
+ *                       chain (policy, base controller, step).  The results are those of the two calls bit for bit (noise keying, NULL
+ *                       options, in_stride-wide rows, the reward's log(max(1, value)) / 3 term).  No allocation, no synchronisation, no
+ *                       host read: capturable in a hipGraph under mocca_step's conditions.  MOCCA_E_ARG with a message, nothing launched:
+ *                       mocca_act's and mocca_plan_step's own errors, a task other than the planner task, no base controller, an
+ *                       attached policy whose act_dim is not mocca_plan_dim(h).
  * mocca_set_policy_symmetry  replaces SymmetricRL's symmetric network (`SymmetricNet` around the actor and the critic, built from the env's
  *                       `get_mirror_indices()`): the attached policy becomes mirror-symmetric by construction,
  *                           mean_sym(s) = 1/2 (f(n(s)) + M_a f(n(M_o s)))        value_sym(s) = 1/2 (V(n(s)) + V(n(M_o s)))
@@ -426,6 +444,9 @@ int mocca_act(mocca_handle h, const float *in_dev, int in_stride, const float *e
 int mocca_act_step(mocca_handle h, const float *in_dev, int in_stride, const float *eps_dev, int deterministic, float *action_dev,
                    float *logp_dev, float *value_dev, float *mean_dev, float *obs_dev, float *rew_dev, uint8_t *done_dev, int32_t *info_dev,
                    void *stream);
+int mocca_act_plan_step(mocca_handle h, const float *in_dev, int in_stride, const float *eps_dev, int deterministic, float *plan_dev,
+                        float *logp_dev, float *value_dev, float *mean_dev, float *obs_dev, float *rew_dev, uint8_t *done_dev,
+                        int32_t *info_dev, void *stream);
 int mocca_set_policy_symmetry(mocca_handle h, const int32_t *in_perm_host, const float *in_sign_host, const int32_t *act_perm_host,
                               const float *act_sign_host);
 int mocca_set_policy_mirror_loss(mocca_handle h, const int32_t *in_perm_host, const float *in_sign_host, const int32_t *act_perm_host,

@@ -7,6 +7,10 @@ adds `log(max(1, value)) / 3` to the reward (:1101).  A `BaseController` holds t
 * `VecEnv(env_id, n, base_controller=ctrl)` / `trainer_api.make_vec_envs(..., base_controller=ctrl)` read `ctrl.actor` / `ctrl.critic` and
   run them on the device (`VecEnv.plan_step`);
 * `Walker3DPlannerEnv(base_controller=ctrl)` calls it: `ctrl(base_obs[65]) -> (value, action[21])`, float32 numpy.
+
+A controller trained by this project's own PPO (tools/ppo_demo.py on a Stepper id) also carries observation statistics: `obs_mean` /
+`obs_inv_std` over the 65 inputs and `clip`, applied as clamp((x - mean) * inv_std, -clip, clip) in front of both nets
+(`BaseController.from_policy_npz`; include/mocca.h mocca_set_base_controller_norm).
 """
 from __future__ import annotations
 
@@ -41,6 +45,11 @@ def _net(layers, in_dim, out_dim, name):
             raise ValueError(f"{name}[{i}]: hidden width {fan_in} is not a multiple of 16 up to {MAX_WIDTH}")
         net.append((w, b, act))
     return net
+
+
+def inv_std_f32(var, eps=1e-8):
+    """1 / sqrt(var + eps) in float32: what the kernels multiply by (policy.DevicePolicy and BaseController form it here, so they agree in bits)"""
+    return np.float32(1) / np.sqrt(np.array(var, dtype=np.float32).reshape(-1) + np.float32(eps))
 
 
 def _apply(net, x):
@@ -137,16 +146,53 @@ def layers_from_sequential(seq, which):
 
 
 class BaseController:
-    def __init__(self, actor, critic):
+    def __init__(self, actor, critic, obs_mean=None, obs_inv_std=None, clip=10.0):
         self.actor = _net(actor, INPUT_DIM, ACTION_DIM, "actor")
         self.critic = _net(critic, INPUT_DIM, 1, "critic")
+        self.clip = float(clip)
+        if not (np.isfinite(self.clip) and self.clip > 0):
+            raise ValueError("clip must be finite and positive")
+        if (obs_mean is None) != (obs_inv_std is None):
+            raise ValueError("obs_mean and obs_inv_std come together, or neither")
+        self.obs_mean = self.obs_inv_std = None
+        if obs_mean is not None:    # kept as float32 exactly as given
+            self.obs_mean = np.array(obs_mean, dtype=np.float32).reshape(-1)
+            self.obs_inv_std = np.array(obs_inv_std, dtype=np.float32).reshape(-1)
+            if self.obs_mean.size != INPUT_DIM or self.obs_inv_std.size != INPUT_DIM:
+                raise ValueError(f"obs_mean / obs_inv_std have {INPUT_DIM} entries")
+            if not np.isfinite(self.obs_mean).all() or not np.isfinite(self.obs_inv_std).all() or (self.obs_inv_std < 0).any():
+                raise ValueError("obs_mean must be finite, obs_inv_std finite and not negative")
 
-    from_layers = classmethod(lambda cls, actor, critic: cls(actor, critic))
+    from_layers = classmethod(lambda cls, actor, critic, **kw: cls(actor, critic, **kw))
 
     @classmethod
     def from_torch(cls, actor_seq, critic_seq):
         """from two torch.nn.Sequential of Linear / ReLU / Tanh / Softsign; any other module is a ValueError"""
         return cls(layers_from_sequential(actor_seq, "actor"), layers_from_sequential(critic_seq, "critic"))
+
+    @classmethod
+    def from_policy_npz(cls, path, eps=1e-8, clip=10.0):
+        """from tools/ppo_demo.py's <out>_policy.npz of a Stepper id (65 -> ... -> 21): `pi_<i>_weight` / `pi_<i>_bias` and `vf_*` (tanh between
+        the layers, identity heads), `obs_mean`, `obs_var`; inv_std = 1 / sqrt(var + eps) in float32 as policy.DevicePolicy forms it.  A file
+        without the critic's `vf_*` arrays is a ValueError: the critic's value is part of the planner envs' reward."""
+        with np.load(path, allow_pickle=False) as z:
+            def net(prefix):
+                idx = sorted(int(k.split("_")[1]) for k in z.files if k.startswith(prefix + "_") and k.endswith("_weight"))
+                return [(z[f"{prefix}_{i}_weight"], z[f"{prefix}_{i}_bias"], "identity" if i == idx[-1] else "tanh") for i in idx]
+            if not any(k.startswith("pi_") and k.endswith("_weight") for k in z.files):
+                raise ValueError(f"{path}: no pi_*_weight arrays: not a policy file of tools/ppo_demo.py")
+            if not any(k.startswith("vf_") and k.endswith("_weight") for k in z.files):
+                raise ValueError(f"{path}: the critic is missing (no vf_* arrays): a base controller needs the critic the policy was trained with")
+            if "obs_mean" not in z.files:
+                return cls(net("pi"), net("vf"), clip=clip)
+            return cls(net("pi"), net("vf"), obs_mean=z["obs_mean"], obs_inv_std=inv_std_f32(z["obs_var"], eps), clip=clip)
+
+    @classmethod
+    def load(cls, path, **kw):
+        """either file format, told apart by the keys: save_npz's (`actor/act`) or tools/ppo_demo.py's policy file (`pi_*`)"""
+        with np.load(path, allow_pickle=False) as z:
+            own = "actor/act" in z.files
+        return cls.from_npz(path) if own else cls.from_policy_npz(path, **kw)
 
     # ---- files: one .npz, arrays "<net>/<i>/W", "<net>/<i>/b" and the activation names "<net>/act" ----
     def save_npz(self, path):
@@ -156,19 +202,24 @@ class BaseController:
             data[which + "/act"] = np.array([act for _, _, act in net])
             for i, (w, b, _) in enumerate(net):
                 data[f"{which}/{i}/W"], data[f"{which}/{i}/b"] = w, b
+        if self.obs_mean is not None:
+            data["obs_mean"], data["obs_inv_std"], data["clip"] = self.obs_mean, self.obs_inv_std, np.float64(self.clip)
         np.savez(path, **data)
 
     @classmethod
     def from_npz(cls, path):
         with np.load(path, allow_pickle=False) as z:
             nets = [[(z[f"{which}/{i}/W"], z[f"{which}/{i}/b"], str(act)) for i, act in enumerate(z[which + "/act"])] for which in ("actor", "critic")]
-        return cls(*nets)
+            norm = dict(obs_mean=z["obs_mean"], obs_inv_std=z["obs_inv_std"], clip=float(z["clip"])) if "obs_mean" in z.files else {}
+        return cls(*nets, **norm)
 
     # ---- the callable Walker3DPlannerEnv(base_controller=...) takes ----
     def __call__(self, base_obs):
         x = np.asarray(base_obs, dtype=np.float32)
         if x.shape[-1:] != (INPUT_DIM,):
             raise ValueError(f"base_obs has {INPUT_DIM} entries: robot_state(50) and the scaled plan(15)")
+        if self.obs_mean is not None:
+            x = np.minimum(np.maximum((x - self.obs_mean) * self.obs_inv_std, np.float32(-self.clip)), np.float32(self.clip))
         return _apply(self.critic, x)[..., 0], _apply(self.actor, x)
 
     # ---- the image the controller kernel reads (csrc/mocca_controller.h); the library builds the same one from .actor / .critic ----

@@ -154,6 +154,7 @@ struct mocca_ctx {
   DevBuf<float> d_robot_state;       // [N][ROBOT_STATE_STRIDE] the controller's next input (StepArgs.robot_state)
   DevBuf<float> d_base_act;          // [N][21] the actor's output of the last mocca_plan_step
   DevBuf<float> d_base_val;          // [N] the critic's
+  DevBuf<float> d_ctrl_norm;         // mocca_set_base_controller_norm: mean [65] then inv_std [65]; ctrl.norm_mean / norm_inv_std point into it
   // a trainer's policy (mocca_set_policy), owned by the handle
   DevBuf<float> d_pol_image;         // the kernel's image (mocca_policy.h)
   DevBuf<int32_t> d_pol_layers;
@@ -672,7 +673,7 @@ int mocca_set_base_controller(mocca_handle h, const float* params_host, size_t n
   DeviceGuard guard(h->device);
   if (!params_host) {   // detach
     if (int rc = commit_ready(h, "mocca_set_base_controller")) return rc;
-    h->d_ctrl_image.reset(); h->d_ctrl_layers.reset(); h->ctrl = {};
+    h->d_ctrl_image.reset(); h->d_ctrl_layers.reset(); h->d_ctrl_norm.reset(); h->ctrl = {};
     return MOCCA_OK;
   }
   auto bad = [&](const std::string& what) { h->err = "mocca_set_base_controller: " + what; return MOCCA_E_ARG; };
@@ -709,8 +710,40 @@ int mocca_set_base_controller(mocca_handle h, const float* params_host, size_t n
   c.params = im.pa.params; c.layers = im.pa.layers; c.n_actor = count[0]; c.n_critic = count[1];
   c.robot_state = h->d_robot_state; c.action_scale = (float)action_scale;
   c.action = h->d_base_act; c.value = h->d_base_val; c.n_envs = h->n_envs;
+  h->d_ctrl_norm.reset();   // the statistics belonged to the controller that was replaced
+  c.norm_mean = c.norm_inv_std = nullptr; c.norm_clip = 0.0f;
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_base_controller"); }
+
+int mocca_set_base_controller_norm(mocca_handle h, const float* mean_host, const float* inv_std_host, double clip) {
+  using namespace mocca_ctrl;
+  if (!h) { g_err = "mocca_set_base_controller_norm: NULL handle"; return MOCCA_E_ARG; }
+  auto bad = [&](const std::string& what) { h->err = "mocca_set_base_controller_norm: " + what; return MOCCA_E_ARG; };
+  if (!h->d_ctrl_image) return bad("needs a base controller (mocca_set_base_controller)");
+  if (!mean_host != !inv_std_host) return bad("mean_host and inv_std_host must both be given, or both be NULL (detach)");
+  DeviceGuard guard(h->device);
+  if (!mean_host) {   // detach
+    if (int rc = commit_ready(h, "mocca_set_base_controller_norm")) return rc;
+    h->d_ctrl_norm.reset();
+    h->ctrl.norm_mean = h->ctrl.norm_inv_std = nullptr; h->ctrl.norm_clip = 0.0f;
+    return MOCCA_OK;
+  }
+  for (int k = 0; k < CTRL_IN; ++k) {
+    if (!std::isfinite(mean_host[k])) return bad("mean[" + std::to_string(k) + "] is not finite");
+    if (!std::isfinite(inv_std_host[k]) || inv_std_host[k] < 0.0f) return bad("inv_std[" + std::to_string(k) + "] is not finite or is negative");
+  }
+  if (!std::isfinite(clip) || !(clip > 0.0)) return bad("clip must be finite and positive");
+  float host[2 * CTRL_IN];
+  std::memcpy(host, mean_host, CTRL_IN * sizeof(float));
+  std::memcpy(host + CTRL_IN, inv_std_host, CTRL_IN * sizeof(float));
+  DevBuf<float> norm;
+  hipError_t e = norm.alloc(2 * CTRL_IN, false);
+  if (e == hipSuccess) e = hipMemcpy(norm, host, sizeof(host), hipMemcpyHostToDevice);
+  if (int rc = commit_ready(h, "mocca_set_base_controller_norm", e)) return rc;
+  h->d_ctrl_norm.swap(norm);
+  h->ctrl.norm_mean = h->d_ctrl_norm; h->ctrl.norm_inv_std = h->d_ctrl_norm.get() + CTRL_IN; h->ctrl.norm_clip = (float)clip;
+  return MOCCA_OK;
+}
 
 int mocca_task_step(mocca_handle h, const float* act_dev, const int32_t* touch_dev, const int32_t* target_dev, const int32_t* body_dev,
                     float* obs_dev, float* rew_dev, uint8_t* done_dev, int32_t* info_dev, void* stream) {
@@ -1310,6 +1343,27 @@ int mocca_act_step(mocca_handle h, const float* in_dev, int in_stride, const flo
   hipStream_t s = (hipStream_t)stream;
   if (int rc = launch_act(h, "mocca_act_step", in_dev, in_stride, eps_dev, deterministic, action_dev, logp_dev, value_dev, mean_dev, s)) return rc;
   return launch_step(h, action_dev, nullptr, obs_dev, rew_dev, done_dev, info_dev, s);
+}
+
+int mocca_act_plan_step(mocca_handle h, const float* in_dev, int in_stride, const float* eps_dev, int deterministic, float* plan_dev, float* logp_dev,
+                        float* value_dev, float* mean_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev, int32_t* info_dev, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER) { h->err = "mocca_act_plan_step: only the planner task takes plans"; return MOCCA_E_ARG; }
+  if (!obs_dev || !rew_dev || !done_dev) { h->err = "mocca_act_plan_step: obs_dev, rew_dev and done_dev must not be NULL"; return MOCCA_E_ARG; }
+  if (!h->d_ctrl_image) { h->err = "mocca_act_plan_step needs a base controller (mocca_set_base_controller)"; return MOCCA_E_ARG; }
+  if (h->d_pol_image && h->pol.act_dim != mocca_ctrl::CTRL_PLAN) {
+    h->err = "mocca_act_plan_step: the policy's act_dim (" + std::to_string(h->pol.act_dim) + ") is not the plan's (" + std::to_string(mocca_ctrl::CTRL_PLAN) + ")";
+    return MOCCA_E_ARG;
+  }
+  if (need_attachments(h) != MOCCA_OK) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = launch_act(h, "mocca_act_plan_step", in_dev, in_stride, eps_dev, deterministic, plan_dev, logp_dev, value_dev, mean_dev, s)) return rc;
+  mocca_ctrl::ControllerArgs c = h->ctrl;
+  c.plan = plan_dev;
+  mocca_ctrl::launch_controller(s, c);
+  HIP_TRY(h, hipGetLastError());
+  return launch_step(h, h->d_base_act, h->d_base_val, obs_dev, rew_dev, done_dev, info_dev, s);
 }
 
 // scratch of the rollout kernels: allocated on the first call and on one that needs more; only such a call synchronises

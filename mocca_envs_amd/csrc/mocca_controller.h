@@ -36,6 +36,11 @@ struct ControllerArgs {
   float* action;                // [N][CTRL_ACTION], not clipped (apply_action clips, robots.py:33)
   float* value;                 // [N]
   int n_envs;
+  // observation statistics of a controller trained by this project's PPO (mocca_set_base_controller_norm), or norm_mean == null: each of the
+  // 65 inputs becomes clamp((v - norm_mean[k]) * norm_inv_std[k], -norm_clip, +norm_clip) after the scale and before both nets
+  const float* norm_mean;       // device, [CTRL_IN]
+  const float* norm_inv_std;    // device, [CTRL_IN]
+  float norm_clip;
 };
 
 constexpr int CTRL_TILE = 16;        // envs per workgroup (32 and 64 measured slower at 4096 envs: profiles/HISTORY.md)

@@ -43,7 +43,10 @@ __global__ __launch_bounds__(256, 2) void controller_kernel(ControllerArgs a) {
   const int env0 = blockIdx.x * TILE, net = blockIdx.y;
   const int col = lane & 15, quad = lane >> 4;
 
-  // input: [robot_state(50), plan(15) * action_scale, zeros]; rows past the batch are zeros (their outputs are not stored)
+  // input: [robot_state(50), plan(15) * action_scale, zeros]; rows past the batch are zeros (their outputs are not stored).  With
+  // observation statistics attached (norm_mean != null: wave-uniform) the 65 entries are normalised by the policy kernel's line
+  // (mocca_policy.hip: input), the padding stays zeros
+  const bool norm = a.norm_mean != nullptr;
   for (int i = tid; i < TILE * IN_PAD; i += 256) {
     const int e = i / IN_PAD, k = i - e * IN_PAD, env = env0 + e;
     float v = 0.0f;
@@ -51,6 +54,7 @@ __global__ __launch_bounds__(256, 2) void controller_kernel(ControllerArgs a) {
       if (k < CTRL_ROBOT_STATE) v = a.robot_state[(size_t)env * CTRL_RS_STRIDE + k];
       else if (k < CTRL_IN) v = a.plan[(size_t)env * CTRL_PLAN + (k - CTRL_ROBOT_STATE)] * a.action_scale;
     }
+    if (norm && env < a.n_envs && k < CTRL_IN) v = fminf(fmaxf((v - a.norm_mean[k]) * a.norm_inv_std[k], -a.norm_clip), a.norm_clip);
     X[0][e * LDS_STRIDE + k] = v;
   }
   __syncthreads();

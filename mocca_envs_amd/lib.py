@@ -41,6 +41,7 @@ SYMBOLS = {
     "mocca_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocca_task_step": (_i, [_vp] * 10),
     "mocca_set_base_controller": (_i, [_vp, _vp, _sz, _vp, _i, _d]),
+    "mocca_set_base_controller_norm": (_i, [_vp, _vp, _vp, _d]),
     "mocca_plan_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mocca_get_base_outputs": (_i, [_vp, _vp, _vp, _vp]),
     "mocca_set_draw_tape": (_i, [_vp, _vp, _i]),
@@ -69,6 +70,7 @@ SYMBOLS = {
     "mocca_update_policy": (_i, [_vp, _vp, _sz, _vp]),
     "mocca_act": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "mocca_act_step": (_i, [_vp, _vp, _i, _vp, _i] + [_vp] * 9),
+    "mocca_act_plan_step": (_i, [_vp, _vp, _i, _vp, _i] + [_vp] * 9),
     "mocca_set_policy_symmetry": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mocca_set_policy_mirror_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _d]),
     "mocca_set_policy_mirror_dup": (_i, [_vp, _vp, _vp, _vp, _vp]),

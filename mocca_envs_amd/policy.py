@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .controller import _apply, _net, _round16, layer_table, layers_from_sequential, pack_nets, unpack_nets
+from .controller import _apply, _net, _round16, inv_std_f32, layer_table, layers_from_sequential, pack_nets, unpack_nets
 
 MAX_IN, MAX_ACTION, FLAG_WORDS = 336, 32, 4       # csrc/mocca_policy.h POL_MAX_IN / POL_MAX_ACTION / POL_FLAG_WORDS
 HALF_LOG_2PI = 0.9189385332046727
@@ -36,8 +36,8 @@ class DevicePolicy:
         self.obs_mean = self.inv_std = None
         if obs_mean is not None:
             self.obs_mean = np.array(obs_mean, dtype=np.float32).reshape(-1)
-            if inv_std is None:     # 1 / sqrt(var + eps) in float32: what the kernel multiplies by
-                inv_std = np.float32(1) / np.sqrt(np.array(obs_var, dtype=np.float32).reshape(-1) + np.float32(eps))
+            if inv_std is None:
+                inv_std = inv_std_f32(obs_var, eps)
             self.inv_std = np.array(inv_std, dtype=np.float32).reshape(-1)
             if self.obs_mean.size != self.in_dim or self.inv_std.size != self.in_dim:
                 raise ValueError(f"obs_mean / obs_var have {self.in_dim} entries")

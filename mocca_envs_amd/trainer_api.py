@@ -333,14 +333,15 @@ class TorchVecEnv:
     # ---- the trainer's own policy on the device (VecEnv.set_policy / act_step, include/mocca.h mocca_act_step) ----
     def attach_policy(self, policy) -> None:
         """Attach a `policy.DevicePolicy` whose input is this env's observation row ([obs | scan] with a height scan) and whose actions are
-        the env's; `update_policy(policy_or_flat_tensor)` refreshes its weights once per PPO iteration.  One handle only.  A policy with
-        mirror tables (`symmetric_policy(p)`, `DevicePolicy(symmetry=)`) acts as the symmetric network: the tables cover the whole row."""
+        the env's -- on a planner env with its base controller the 15-number plans, and act_step() goes policy -> base controller -> step
+        (VecEnv.act_plan_step); `update_policy(policy_or_flat_tensor)` refreshes its weights once per PPO iteration.  One handle only.  A
+        policy with mirror tables (`symmetric_policy(p)`, `DevicePolicy(symmetry=)`) acts as the symmetric network: the tables cover the
+        whole row."""
         if not hasattr(self.venv, "lib"):
             raise NotImplementedError("a device policy needs one handle (sub_batches=1)")
-        if self._plan:
-            raise NotImplementedError("a device policy acts with joint actions: not on a planner env that steps through its base controller")
-        if policy is not None and (policy.in_dim != self.observation_space.shape[0] or policy.act_dim != self.venv.act_dim):
-            raise ValueError(f"the policy maps {policy.in_dim} -> {policy.act_dim}, the env {self.observation_space.shape[0]} -> {self.venv.act_dim}")
+        act_dim = self.venv.plan_dim if self._plan else self.venv.act_dim
+        if policy is not None and (policy.in_dim != self.observation_space.shape[0] or policy.act_dim != act_dim):
+            raise ValueError(f"the policy maps {policy.in_dim} -> {policy.act_dim}, the env {self.observation_space.shape[0]} -> {act_dim}")
         self.venv.set_policy(policy)
         n, f32 = self.num_envs, dict(dtype=torch.float32, device=self.device)
         self._pol_bufs = None if policy is None else {"action": torch.zeros(n, policy.act_dim, **f32), "logp": torch.zeros(n, 1, **f32),
@@ -413,6 +414,8 @@ class TorchVecEnv:
             raise _lib.MoccaError("act_step needs a device policy (attach_policy)")
         out = {k: (into or {}).get(k, self._pol_bufs[k]) for k in ("action", "logp", "value")}
         self.last_act = out
+        if self._plan:       # a planner env: the action is the plan, the base controller runs between the policy and the step
+            return lambda row, **kw: self.venv.act_plan_step(row, plan_out=out["action"], logp_out=out["logp"], value_out=out["value"], **kw)
         return lambda row, **kw: self.venv.act_step(row, action_out=out["action"], logp_out=out["logp"], value_out=out["value"], **kw)
 
     def act_step(self, obs: Optional[torch.Tensor] = None, into: Optional[dict] = None):
@@ -441,7 +444,8 @@ class TorchVecEnv:
         `terminal_observation=True`: the graph's launches all write their finished envs' final observations into ONE buffer of their own,
         `envs.rollout_terminal_obs` [N, obs_dim] (apart from the record slots of `step()`; rows of envs that did not finish keep older
         content), which is also `envs.venv.terminal_obs` while `sink` runs -- a sink that wants them copies them at step t.
-        `policy=None`: the attached device policy (attach_policy) acts -- every step of the graph is act_step's two launches; `into(t)` may
+        `policy=None`: the attached device policy (attach_policy) acts -- every step of the graph is act_step's two launches (three on a
+        planner env: act_plan_step); `into(t)` may
         carry "action" / "logp" / "value" rows, and `sink`'s `action` is the tensor the policy wrote.  `update_policy` between replays
         changes what the graph computes: no recapture."""
         if not hasattr(self.venv, "lib"):

@@ -243,11 +243,15 @@ class VecEnv:
         of ACTIVATIONS -- actor 65 -> ... -> 21, critic 65 -> ... -> 1, hidden widths multiples of 16 up to 256, at most 8 layers per net.
         `action_scale` multiplies the plan (Walker3DPlannerEnv.action_scale = 2).  From the next reset() / step() / observe() on the handle
         keeps `robot_state` (the first 50 floats of the last observation) as the controller's input: attach before reset(), or call
-        observe() after attaching."""
+        observe() after attaching.  A `ctrl` that carries `obs_mean` / `obs_inv_std` (and `clip`) has them attached too
+        (set_base_controller_norm); one without the attributes runs on the raw input."""
         if ctrl is None:
             _lib.check(self.lib.mocca_set_base_controller(self.h, None, 0, None, 0, 0.0), self.h)
             self.base_controller = None
             return
+        mean, inv_std = getattr(ctrl, "obs_mean", None), getattr(ctrl, "obs_inv_std", None)
+        if (mean is None) != (inv_std is None):
+            raise ValueError("a controller carries obs_mean and obs_inv_std together, or neither")
         actor, critic = (ctrl.actor, ctrl.critic) if hasattr(ctrl, "actor") else ctrl
         layers = [(np.asarray(w, np.float32), np.asarray(b, np.float32), act) for w, b, act in list(actor) + list(critic)]
         if any(w.ndim != 2 or b.size != w.shape[0] or act not in ACTIVATIONS for w, b, act in layers):    # the widths are the library's to refuse
@@ -256,9 +260,26 @@ class VecEnv:
         table = layer_table(actor, critic, "flat")
         _lib.check(self.lib.mocca_set_base_controller(self.h, params.ctypes.data_as(C.c_void_p), params.size, table.ctypes.data_as(C.c_void_p),
                                                       table.shape[0], float(action_scale)), self.h)
-        self.base_controller = ctrl
+        self.base_controller = ctrl     # (the library dropped the statistics of the controller this one replaces)
+        if mean is not None:
+            self.set_base_controller_norm(mean, inv_std, getattr(ctrl, "clip", 10.0))
         f32 = dict(dtype=torch.float32, device=self.device)
         self._base_action, self._base_value = torch.zeros(self.n_envs, self.act_dim, **f32), torch.zeros(self.n_envs, **f32)
+
+    def set_base_controller_norm(self, mean, inv_std, clip: float = 10.0):
+        """Observation statistics of the attached base controller (include/mocca.h mocca_set_base_controller_norm; mean None detaches):
+        float32 [65] each, over the controller's input row [robot_state(50), plan(15) * action_scale]; the kernel applies
+        clamp((x - mean) * inv_std, -clip, clip) in front of both nets.  set_base_controller(ctrl) calls this for a `ctrl` that carries
+        `obs_mean` / `obs_inv_std`, and drops the statistics of the controller it replaces."""
+        if self.base_controller is None:
+            raise _lib.MoccaError("set_base_controller_norm needs a base controller (set_base_controller)")
+        if mean is None:
+            _lib.check(self.lib.mocca_set_base_controller_norm(self.h, None, None, float(clip)), self.h)
+            return
+        mean, inv_std = np.ascontiguousarray(mean, np.float32).reshape(-1), np.ascontiguousarray(inv_std, np.float32).reshape(-1)
+        if mean.size != 65 or inv_std.size != 65:
+            raise ValueError("the statistics of a base controller have 65 entries: robot_state(50) and the scaled plan(15)")
+        _lib.check(self.lib.mocca_set_base_controller_norm(self.h, mean.ctypes.data_as(C.c_void_p), inv_std.ctypes.data_as(C.c_void_p), float(clip)), self.h)
 
     def plan_step(self, plans: torch.Tensor, obs_out: Optional[torch.Tensor] = None,
                   rew_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -430,6 +451,20 @@ class VecEnv:
         """act(obs) and step(action) as two launches of one C call (include/mocca.h mocca_act_step): the action, its log-probability and the
         value go to `action_out` / `logp_out` / `value_out` (logp and value only where given; the action to a buffer of this object
         otherwise: `self.last_action`), the step's results are step()'s, bit for bit.  Same contract as step() otherwise."""
+        return self._launch_act_step(self.lib.mocca_act_step, obs, eps, deterministic, action_out, logp_out, value_out, obs_out, rew_out)
+
+    def act_plan_step(self, obs: torch.Tensor, eps: Optional[torch.Tensor] = None, deterministic: bool = False, plan_out: Optional[torch.Tensor] = None,
+                      logp_out: Optional[torch.Tensor] = None, value_out: Optional[torch.Tensor] = None, obs_out: Optional[torch.Tensor] = None,
+                      rew_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """act_step()'s twin on a planner env (include/mocca.h mocca_act_plan_step): the attached policy's action is the 15-number plan, and
+        act(obs), the base controller and the step kernel are three launches of one C call.  The plan goes to `plan_out` (or
+        `self.last_action`); the results are those of act() followed by plan_step(plan), bit for bit."""
+        if not self.plan_dim:
+            raise ValueError("act_plan_step: planner envs only")
+        return self._launch_act_step(self.lib.mocca_act_plan_step, obs, eps, deterministic, plan_out, logp_out, value_out, obs_out, rew_out)
+
+    def _launch_act_step(self, entry, obs, eps, deterministic, action_out, logp_out, value_out, obs_out, rew_out):
+        """act_step() / act_plan_step(): check the tensors, launch `entry` (mocca_act_step or mocca_act_plan_step: same argument list)"""
         given = {k: v for k, v in (("action", action_out), ("logp", logp_out), ("value", value_out)) if v is not None}
         if "action" not in given and self.policy is not None:
             if getattr(self, "_pol_action", None) is None or self._pol_action.shape[1] != self.policy.act_dim:
@@ -442,8 +477,8 @@ class VecEnv:
             if obs_o.shape != (self.n_envs, self.obs_dim) or rew.numel() != self.n_envs or obs_o.dtype != torch.float32 or rew.dtype != torch.float32 \
                     or not obs_o.is_contiguous() or not rew.is_contiguous() or obs_o.device != self.device or rew.device != self.device:
                 raise ValueError("obs_out / rew_out must be contiguous float32 [n_envs, obs_dim] / [n_envs] tensors on the env's device")
-        _lib.check(self.lib.mocca_act_step(self.h, *args, C.c_void_p(obs_o.data_ptr()), C.c_void_p(rew.data_ptr()), C.c_void_p(self.done.data_ptr()),
-                                           C.c_void_p(self.info.data_ptr()), self._stream()), self.h)
+        _lib.check(entry(self.h, *args, C.c_void_p(obs_o.data_ptr()), C.c_void_p(rew.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                         C.c_void_p(self.info.data_ptr()), self._stream()), self.h)
         return obs_o, rew, self.done, self.info
 
     # ---- the end of a rollout on the device (include/mocca.h mocca_gae / mocca_obs_stats) ----

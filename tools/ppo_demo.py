@@ -10,6 +10,13 @@ No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it Symme
 
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
                            [--device-policy [--device-returns [--device-grad [--device-update]]]] [--symmetric | --mirror-loss COEF | --mirror-dup]
+                           [--base-controller FILE] [--height-scan NX,NY]
+--base-controller FILE (required for the planner ids, Walker3DPlannerEnv-v0 / MikePlannerEnv-v0): ALLSTEPS's second step.  FILE is a
+`BaseController.save_npz` file or the <out>_policy.npz of an earlier run of this script on a Stepper id (told apart by the keys; the latter
+brings its observation statistics along); it is frozen as the env's base controller and the policy trained here emits 15-number plans.
+Every --device-* flag works: collection is then `act_plan_step`, policy -> base controller -> step, three launches per step.
+--height-scan NX,NY: the observation row becomes [obs | scan], a `perception.scan_grid` of NX x NY terrain heights over 0 .. 2 m ahead and
+-0.5 .. 0.5 m sideways, through `make_vec_envs(height_scan=...)`: a planner that cannot see the height field has nothing to plan on.
 --device-policy: collection runs through `envs.act_step(obs[t], into=...)` -- the policy kernel (normalisation, both nets, the sample, its
 log-probability, the value) and the step kernel, two launches per step and no torch op; `envs.update_policy(flat)` once per iteration hands the
 kernel the optimiser's new weights and the running observation statistics.  The noise then comes from the kernel, not from torch.randn.
@@ -81,6 +88,8 @@ def main():
     ap.add_argument("--symmetric", action="store_true", help="SymmetricRL's symmetric network: mean, value and log_std symmetrised through the env's mirror tables")
     ap.add_argument("--mirror-loss", type=float, default=None, metavar="COEF", help="SymmetricRL's mirror-symmetry loss with this weight (0: only logged); not with --symmetric")
     ap.add_argument("--mirror-dup", action="store_true", help="SymmetricRL's duplicated tuples: train on every row and its mirror image; not with --symmetric or --mirror-loss")
+    ap.add_argument("--base-controller", default=None, metavar="FILE", help="the planner ids' frozen base controller: a BaseController.save_npz file or this script's policy file of a Stepper run")
+    ap.add_argument("--height-scan", default=None, metavar="NX,NY", help="append a scan_grid of NX x NY terrain heights (0 .. 2 m ahead, -0.5 .. 0.5 m sideways) to the observation row")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args()
     if args.device_grad and not args.device_returns:
@@ -99,11 +108,24 @@ def main():
         ap.error("--device-returns requires --device-policy")
     if args.verify_returns and not args.device_returns:
         ap.error("--verify-returns requires --device-returns")
+    planner = "Planner" in args.env_id
+    if planner != (args.base_controller is not None):
+        ap.error("--base-controller is required for the planner ids, and only for them")
+    if planner and (args.symmetric or args.mirror_loss is not None or args.mirror_dup):
+        ap.error("the planner ids publish no mirror indices for plans: no --symmetric / --mirror-loss / --mirror-dup")
     import torch
     import torch.nn as nn
     from mocca_envs_amd.trainer_api import make_vec_envs
     torch.manual_seed(args.seed)
-    envs = make_vec_envs(args.env_id, seed=args.seed, num_processes=args.envs, record_events=False)
+    extra = {}
+    if args.base_controller is not None:
+        from mocca_envs_amd.controller import BaseController
+        extra["base_controller"] = BaseController.load(args.base_controller)
+    if args.height_scan is not None:
+        from mocca_envs_amd.perception import scan_grid
+        nx, ny = (int(v) for v in args.height_scan.split(","))
+        extra["height_scan"] = dict(points=scan_grid((0.0, 2.0), (-0.5, 0.5), nx, ny))
+    envs = make_vec_envs(args.env_id, seed=args.seed, num_processes=args.envs, record_events=False, **extra)
     dev, N, T = envs.device, args.envs, args.steps
     od, ad = envs.observation_space.shape[0], envs.action_space.shape[0]
 
