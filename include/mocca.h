@@ -82,7 +82,12 @@ enum {
                                         a two-waves-per-SIMD register budget: Bullet caps neither rows nor contacts, and this instance exists to
                                         measure what the product's caps change).  1 forces the 48-row instance for a blob that would run the
                                         compact one, 2 forces the 64-row instance for any blob (A/B runs), 0 = automatic.  The instances execute
-                                        the same arithmetic in the same order: on the same blob results are bit-identical. */
+                                        the same arithmetic in the same order: on the same blob results are bit-identical.
+                                        Bit 2 (add 4 to any of the above): the step kernel builds the Delassus matrix A = J X^T with the VALU
+                                        dot products for every row count.  Without it a substep of a tree without loop closures that holds 8 to
+                                        32 rows (8 to 16 in the compact instance; not the 48-row planner kernel) builds A with
+                                        v_mfma_f32_16x16x4_f32, which evaluates the same fma chain in the same order: results are
+                                        bit-identical with and without the bit (A/B runs).  Values: 0, 1, 2, 4, 5, 6. */
   MOCCA_PARAM_ORDER_EVERY = 12,      /* TIMING ONLY.  K > 0: every K-th mocca_step first sorts the envs by the constraint-row count their last step
                                         ended with and the step kernel starts the heaviest first (a launch of more envs than the chip holds at
                                         once ends with the waves it started last: they should be the light ones); 0: index order.  Envs never

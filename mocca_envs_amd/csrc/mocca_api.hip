@@ -112,7 +112,8 @@ struct mocca_ctx {
   float gain = 1.0f;
   bool compact = false;        // the blob fits the compact step-kernel instance (compact_ok); MOCCA_PARAM_KERNEL_VARIANT = 1 overrides
   bool wide = false;           // the blob's caps exceed 48 rows / 12 contacts: the 64-row accuracy instance (mocca_r64.hip)
-  int force_full = 0;          // MOCCA_PARAM_KERNEL_VARIANT: 1 forces the 48-row instance, 2 the 64-row one
+  int force_full = 0;          // MOCCA_PARAM_KERNEL_VARIANT, bits 0..1: 1 forces the 48-row instance, 2 the 64-row one
+  bool delassus_valu = false;  // MOCCA_PARAM_KERNEL_VARIANT, bit 2: the step kernel builds the Delassus matrix on the VALU for every row count
   int persist_warm = 0;        // MOCCA_PARAM_PERSIST_IMPULSES
   int pace = -18;              // MOCCA_PARAM_PACE_TICKS: self-calibrating pace priorities, 18/16 of the previous launch's mean wave time (profiles/archive/r04_pace_*.jsonl)
   DevBuf<unsigned long long> d_pace_acc;     // self-calibration samples of the pace, one packed word (StepArgs.pace_acc), owned by the handle
@@ -540,7 +541,7 @@ static StepArgs make_args(mocca_handle h) {
   a.gain_v = h->pvec_on[2] ? h->d_pvec[2].get() : nullptr;
   a.gain = h->gain;
   a.dbg = h->dbg;
-  a.prio = h->prio;
+  a.prio = h->prio | (h->delassus_valu ? PRIO_DELASSUS_VALU : 0);   // (the thresholds take 18 bits)
   a.traj = h->d_traj; a.traj_n = h->traj_n; a.traj_tmax = h->traj_tmax; a.traj_cstep = h->traj_cstep;
   a.final_obs = h->final_obs;
   a.persist_warm = h->persist_warm;
@@ -976,10 +977,12 @@ int mocca_set_param(mocca_handle h, int param_id, double value) {
         HIP_TRY(h, h->d_order.alloc((size_t)h->n_envs, false));
       }
       break;
-    case MOCCA_PARAM_KERNEL_VARIANT:
-      if (value != 0 && value != 1 && value != 2) { h->err = "MOCCA_PARAM_KERNEL_VARIANT is 0 (automatic), 1 (force the 48-row instance) or 2 (force the 64-row instance)"; return MOCCA_E_ARG; }
-      if (value == 1 && h->wide) { h->err = "MOCCA_PARAM_KERNEL_VARIANT = 1: this blob needs the 64-row instance (caps beyond 48 rows / 12 contacts, or sweep_alternate)"; return MOCCA_E_ARG; }
-      h->force_full = (int)value; break;
+    case MOCCA_PARAM_KERNEL_VARIANT: {
+      if (value != (double)(int)value || value < 0 || value > 7 || ((int)value & 3) == 3) { h->err = "MOCCA_PARAM_KERNEL_VARIANT is 0 (automatic), 1 (force the 48-row instance) or 2 (force the 64-row instance), plus 4 to build the Delassus matrix on the VALU"; return MOCCA_E_ARG; }
+      const int inst = (int)value & 3;
+      if (inst == 1 && h->wide) { h->err = "MOCCA_PARAM_KERNEL_VARIANT = 1: this blob needs the 64-row instance (caps beyond 48 rows / 12 contacts, or sweep_alternate)"; return MOCCA_E_ARG; }
+      h->force_full = inst; h->delassus_valu = ((int)value & 4) != 0; break;
+    }
     default: h->err = "unknown parameter id"; return MOCCA_E_ARG;
   }
   return MOCCA_OK;

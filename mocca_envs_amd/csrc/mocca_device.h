@@ -1493,6 +1493,93 @@ DI void delassus_store(float* L, int c, int nr, int tmax, const float* v) {  // 
   }
 }
 
+// The same matrix on the matrix pipe (topologies without closures, nr <= DELASSUS_MFMA_ROWS): v_mfma_f32_16x16x4_f32 is bit for bit the
+// k-ordered fmaf chain `s = fma(J[d], X[d], s)`, d ascending, that delassus_dots evaluates (one rounding per product, no wider accumulator,
+// subnormals kept), and the chain of delassus_dots starts as an fma onto +0 (v_fma_f32 .., 0 in its ISA): the accumulators start at +0.0f.
+// The lanes park their X next to the J rows ([nr][28] at L_DX: the head of the A region, dead between the sweeps and the first A store), a
+// 16 x 16 tile of J X^T is seven MFMAs chained through the accumulator (k = 4 kk + (lane >> 4) of row lane & 15 on both operands), and every
+// element goes where delassus_store leaves it.  Float 27 of a J row is +0 and that of an X row is written as +0: fma(0, 0, s) == s.
+// Rows and columns at or beyond nr read whatever LDS holds there; MFMA outputs are element-wise independent and those are never stored.
+// What delassus_store leaves in A[i][j], i != j, d = (i - j) mod nr: lane j's step d stores J_i . X_j there (first store) when d <= nr / 2,
+// lane i's step nr - d stores J_j . X_i there (second store) when nr - d <= nr / 2; for even nr and d == nr / 2 both happen and the second
+// store -- later in the wave's program order -- wins, so A[i][j] and A[j][i] hold DIFFERENT products there.  In terms of the product
+// D[r][c] = J_r . X_c a lane holds (e = (r - c) mod nr): it goes to A[r][c] when 2 e < nr and to A[c][r] when 2 e <= nr; every element of
+// A has exactly one writer.  The diagonal (e == 0) is parked in A[c][c], where the row's own lane picks it up before it stores the zero.
+constexpr int DELASSUS_MFMA_ROWS = COMPACT ? 16 : 32;   // one tile where X has 488 floats before L_J, four where it has 960 or more
+#ifndef MOCCA_DELASSUS_MFMA_MIN
+#define MOCCA_DELASSUS_MFMA_MIN 8   // fewest rows that take the matrix pipe.  Below, the VALU build is a few short steps and the fixed cost of this path
+                                    // (X store, three wave barriers, 7 x 40 cycles of dependent MFMA latency) is the larger: headline launch, five
+                                    // interleaved blocks each, parent 99.82 us, threshold 1: 98.73, 4: 98.40, 8: 98.12, 12: 98.34 (profiles/delassus_mfma.json)
+#endif
+constexpr int PRIO_DELASSUS_VALU = 1 << 18;   // StepArgs.prio, above the three 6-bit thresholds: MOCCA_PARAM_KERNEL_VARIANT's bit 2
+enum : int { L_DX = L_V };
+static_assert(L_DX + 28 * DELASSUS_MFMA_ROWS <= L_J && MAXR >= DELASSUS_MFMA_ROWS, "the X rows of the matrix-pipe Delassus build end before the J rows");
+template <int R, int C>
+DI void delassus_tile_store(float* L, const f4_t& acc, int nr, int li, int lk) {
+  const int c = 16 * C + li;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int r = 16 * R + 4 * lk + j;
+    int e = r - c;
+    if (e < 0) e += nr;
+    const bool in = r < nr && c < nr;
+    if (in && 2 * e <= nr) L[L_A + __mul24(MAXR, c) + r] = acc[j];
+    if (in && 2 * e < nr) L[L_A + __mul24(MAXR, r) + c] = acc[j];
+  }
+}
+template <class T>
+DI float delassus_mfma(float* L, const float* X, int cc, bool has_row, int nr, int lane) {
+  if (has_row) {
+    // The row offset is laundered so that its 16-byte alignment stays unknown: the stores pair up as ds_write2_b32, which take any two
+    // registers.  As ds_write_b128 they tie X into seven 4-register tuples from the sweeps to the apply phase (compact planner instance:
+    // 41 spilled registers with the wide stores, 12 with the pairs).
+    int xo = 28 * cc;
+    asm volatile("" : "+v"(xo));
+    float* xr = L + L_DX + xo;
+#pragma unroll
+    for (int d = 0; d < 28; ++d) xr[d] = d < T::ND ? X[d < T::ND ? d : 0] : 0.0f;
+  }
+  wsync();
+  // the lane number is laundered: the tile coordinates and the addresses derived from them are invariants of the substep loop and must not be
+  // hoisted out of it (registers live across the whole substep, in kernels that sit at their budget)
+  asm volatile("" : "+v"(lane));
+  const int li = lane & 15, lk = lane >> 4;
+  const float* Jl = L + L_J + 28 * li + lk;
+  const float* Xl = L + L_DX + 28 * li + lk;
+  f4_t d00 = {0.0f, 0.0f, 0.0f, 0.0f};
+  bool four = false;
+  if constexpr (DELASSUS_MFMA_ROWS > 16) four = nr > 16;   // wave-uniform
+  if (!four) {
+#pragma unroll
+    for (int kk = 0; kk < 7; ++kk) d00 = __builtin_amdgcn_mfma_f32_16x16x4f32(Jl[4 * kk], Xl[4 * kk], d00, 0, 0, 0);
+    wsync();  // every J and X row has been read: A may overwrite them
+    delassus_tile_store<0, 0>(L, d00, nr, li, lk);
+  } else {
+    // four tiles: their chains interleaved, two or more independent accumulators keep the matrix pipe at its issue rate
+    f4_t d01 = d00, d10 = d00, d11 = d00;
+#pragma unroll
+    for (int kk = 0; kk < 7; ++kk) {
+      const float j0 = Jl[4 * kk], j1 = Jl[28 * 16 + 4 * kk], x0 = Xl[4 * kk], x1 = Xl[28 * 16 + 4 * kk];
+      d00 = __builtin_amdgcn_mfma_f32_16x16x4f32(j0, x0, d00, 0, 0, 0);
+      d01 = __builtin_amdgcn_mfma_f32_16x16x4f32(j0, x1, d01, 0, 0, 0);
+      d10 = __builtin_amdgcn_mfma_f32_16x16x4f32(j1, x0, d10, 0, 0, 0);
+      d11 = __builtin_amdgcn_mfma_f32_16x16x4f32(j1, x1, d11, 0, 0, 0);
+    }
+    wsync();
+    delassus_tile_store<0, 0>(L, d00, nr, li, lk);
+    delassus_tile_store<0, 1>(L, d01, nr, li, lk);
+    delassus_tile_store<1, 0>(L, d10, nr, li, lk);
+    delassus_tile_store<1, 1>(L, d11, nr, li, lk);
+  }
+  wsync();  // the diagonal came from other lanes
+  float diag = 1.0f;
+  if (has_row) {
+    diag = L[L_A + (MAXR + 1) * cc];
+    L[L_A + (MAXR + 1) * cc] = 0.0f;  // the solver works on a zero diagonal (see solve_constraints)
+  }
+  return diag;
+}
+
 // One PGS visit of fixed-bound row RR, then the next (compile-time recursion = guaranteed full unrolling with a
 // wave-uniform early exit; the optimiser keeps a `#pragma unroll` loop with a break rolled).  With RR an immediate, the
 // readlane / writelane index and the LDS offset are constants and the A entry of the next visit is fetched one visit
@@ -1679,7 +1766,7 @@ DI void set_issue_priority(int nr, int prio) {
 #define MOCCA_PACE_SHIFT 4   // width of the priority bands around the pace: 2^-4
 #endif
 constexpr int PACE_TICK_SHIFT = 6;   // elapsed ticks and the pace are compared in units of 64 ticks
-enum : int { L_T0 = L_BASE + 13, L_PACE = L_BASE + 14, L_KEEPWARM = L_BASE + 15 /* StepArgs.persist_warm or a warm-starting blob: same reason */ };
+enum : int { L_T0 = L_BASE + 13, L_PACE = L_BASE + 14, L_KEEPWARM = L_BASE + 15 /* bit 0: StepArgs.persist_warm or a warm-starting blob; bit 1: StepArgs.prio & PRIO_DELASSUS_VALU: same reason */ };
 constexpr unsigned PACE_CNT_BITS = 24, PACE_WINDOW = 128;
 DI void pace_start(const StepArgs& a, float* L, int lane, int pace) {
   if (lane == 0) {
@@ -1726,9 +1813,12 @@ DI void dbg_fold_step(int32_t* dbg, int lane) {
     dbg[16] = (int32_t)(unsigned)h; dbg[17] = (int32_t)(unsigned)(h >> 32); dbg[18] += 1;
   }
 }
-template <class T>
+template <class T, bool MATRIX_PIPE>
 DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wanted, unsigned long long ppk, int32_t* dbg, const float* Afac, int prio, int& rows_out) {
-  const bool keep_warm = uni(__float_as_int(L[L_KEEPWARM])) != 0;   // (wave-uniform) the slots' normal impulses are wanted after the substep (warm start / diagnostic)
+  // (wave-uniform) bit 0: the slots' normal impulses are wanted after the substep (warm start / diagnostic); bit 1: the Delassus matrix is built on
+  // the VALU whatever the row count (StepArgs.prio & PRIO_DELASSUS_VALU).  One scalar for both: it is live to the end of the substep anyway
+  const int wave_flags = uni(__float_as_int(L[L_KEEPWARM]));
+  const bool keep_warm = (wave_flags & 1) != 0;
   STAMP_BEGIN;
   // wave-uniform scalars live in SGPRs: loop control becomes s_cmp/s_cbranch instead of exec-mask bookkeeping
   const float dt = unif(M->dt), idt = rcp(dt);
@@ -1999,7 +2089,13 @@ DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wan
   // column would do) instead of branching around each access
   const int lc = has_row ? dense : MAXR - 1;
   float diag;
-  {
+  // wave-uniform: the matrix pipe builds it where the rows fit its tiles (delassus_mfma; bit-identical); closure topologies (Cassie's two-chain
+  // sum is not one fma chain), more rows and MOCCA_PARAM_KERNEL_VARIANT's bit 2 take the VALU build
+  bool on_mfma = false;
+  if constexpr (T::NCLOS == 0 && MATRIX_PIPE) on_mfma = nr >= MOCCA_DELASSUS_MFMA_MIN && nr <= DELASSUS_MFMA_ROWS && !(wave_flags & 2);
+  if (on_mfma) {
+    diag = delassus_mfma<T>(L, X, has_row ? dense : 0, has_row, nr, lane);
+  } else {
     float av[MAXR / 2 + 1];
     const int cc = has_row ? dense : 0, tmax = nr >> 1;
     delassus_dots<T, 0>(L, X, 28 * cc, 28 * nr, tmax, av);
@@ -2277,7 +2373,10 @@ DI ContactFlags substep(ModelP M, float* L, int lane, const float* ter, int next
   STAMP(2);
   pace_checkpoint(L, done0 + 36, total);
 #ifndef MOCCA_SKIP_SOLVE
-  solve_constraints<T>(M, L, lane, nc, nc_wanted, ppk, dbg, Afac, prio, rows_out);
+  // The planner instance of the 48-row kernel sits at its 128-register budget: with the matrix-pipe build compiled in, the deepest step of its VALU
+  // build spills two 4-register tuples to scratch (whatever the new path holds: X store, operand reads, MFMAs or tile stores alone).  It keeps the
+  // VALU build for every row count until that instance has room.
+  solve_constraints<T, (COMPACT || MAXR != 48 || TASK != MOCCA_TASK_WALKER3D_PLANNER)>(M, L, lane, nc, nc_wanted, ppk, dbg, Afac, prio, rows_out);
 #endif
   if (dbg) { __builtin_amdgcn_s_waitcnt(0); dbg_fold_step(dbg, lane); }   // (lane 0 wrote the twelve words above; it reads them back itself)
   STAMP(3);

@@ -284,7 +284,7 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
   if (dbg && lane == 0) { dbg[16] = 0; dbg[17] = 0; dbg[18] = 0; }   // step signature: restarted by every mocca_step
   load_dyn(st, L, lane, T::NJ, T::NSLOT, warm_ld);
   pace_start(a, L, lane, INJECT ? 0 : a.pace);
-  if (lane == 0) L[L_KEEPWARM] = __int_as_float(warm_st ? 1 : 0);
+  if (lane == 0) L[L_KEEPWARM] = __int_as_float((warm_st ? 1 : 0) | ((a.prio & PRIO_DELASSUS_VALU) ? 2 : 0));   // (solve_constraints: wave_flags)
   // the lane's root->body path, packed 5 bits per step; the only lane-derived value kept across the substeps
   const unsigned long long ppk = T::path_packed(lane < T::NB ? lane : 0);
   ContactFlags fl = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
   wsync();
   flush_obs(L, obs_out, lane, a.obs_dim);
   if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) keep_robot_state<T>(a, L, env, lane);
-  store_dyn(st, L, lane, T::NJ, T::NSLOT, uni(__float_as_int(L[L_KEEPWARM])) != 0);
+  store_dyn(st, L, lane, T::NJ, T::NSLOT, (uni(__float_as_int(L[L_KEEPWARM])) & 1) != 0);
   if (lane == 0) store_task<T, TASK, true>(tk, t);
   if (!INJECT) pace_finish(a, L, lane, a.pace);
   STAMP(25);  // reset (if any) + write-back done
