@@ -146,6 +146,8 @@ enum : int {
   L_A = L_V,                          // [MAXR][MAXR] Delassus matrix, row = updated row, column = lane
   L_J = L_V + 488,                    // [MAXR + 1][28] Jacobian rows (+ one dummy row for lanes that own no row)
   L_XL = L_V,                         // [MAXR][28] M^-1 J^T lambda, after the iterations
+  L_MID = L_CAND + (MOCCA_MAX_PAIRS + 1) / 2,   // [NG][4] geom_points -> collide: the two end points of every geom added up, one 16-byte record per geom
+  L_LGAP = L_ABA_END - MAXR,          // [MAXR] solve_constraints: the gaps of the compacted limit-row candidates (behind the J rows; the link inertias are dead by then)
   L_SOLVER_END = (L_J + 28 * (MAXR + 1) > L_A + MAXR * MAXR ? L_J + 28 * (MAXR + 1) : L_A + MAXR * MAXR),
   L_TOTAL = (L_ABA_END > L_SOLVER_END ? L_ABA_END : L_SOLVER_END) + MOCCA_LDS_PAD,
 #else
@@ -168,6 +170,8 @@ enum : int {
   L_A = L_V,            // [MAXR][MAXR] Delassus matrix, row = updated row, column = lane
   L_J = (L_V + 960 > L_RT ? L_V + 960 : L_RT),   // [MAXR][28] Jacobian rows (tail of the A region; never below the body frames, see the assert)
   L_XL = L_V,           // [MAXR][28] M^-1 J^T lambda, after the iterations
+  L_MID = L_CAND + (MOCCA_MAX_PAIRS + 1) / 2,   // [NG][4] geom_points -> collide: the two end points of every geom added up, one 16-byte record per geom
+  L_LGAP = L_GP,        // [MAXR] solve_constraints: the gaps of the compacted limit-row candidates (the geom points are dead after the collision pass)
   L_TOTAL = L_V + MAXR * MAXR + 28 + MOCCA_LDS_PAD,  // + one dummy J row for lanes that own no row (A-row prefetches clamp to row MAXR - 1)
 #endif
 };
@@ -186,6 +190,20 @@ static_assert(L_TOTAL * 4 <= 10240 || MOCCA_LDS_PAD > 0 || MAXR > 48, "more than
 static_assert(MAXR != 48 || (L_ROWD == L_V + 848 && L_RT == L_V + 896 && L_M == L_V + 1160 && L_P == L_V + 1952 && L_ABA_END == L_V + 2084 && L_J == L_V + 960), "the product's layout is unchanged");
 static_assert(COMPACT || L_CAND + (MOCCA_MAX_PAIRS + 1) / 2 <= L_TOTAL, "candidate list behind the ABA view");
 static_assert(L_J >= L_RT, "J rows may be written while S, U, 1/D, the factor of IA0 and the contacts are still being read");
+static_assert(L_LGAP + MAXR <= L_CT && L_J >= L_CT, "limit gaps: written after the collision pass, read before the first J row or A entry is stored");
+#endif
+#if MOCCA_COMPACT
+static_assert(L_LGAP >= L_J + 28 * (MAXR + 1) && L_LGAP >= L_A + MAXR * MAXR && L_LGAP >= L_M && L_LGAP + MAXR <= L_TOTAL, "limit gaps: behind the solver view, in the dead link inertias");
+#endif
+static_assert(L_MID % 4 == 0 && L_MID >= L_CAND + (MOCCA_MAX_PAIRS + 1) / 2, "midpoint records: 16-byte aligned, behind the candidate list");
+// Which topologies keep midpoint records (collide's broad phase): those with self-collision pairs whose records fit the slack behind the
+// candidate list -- under the link inertias in the compact layout, behind the ABA view otherwise; the others keep the broad phase that adds
+// the end points up per pair.  MOCCA_NO_TRIM_<n>: A/B builds without one of the step kernel's trims (tools/ab.sh), never the product.
+template <class T>
+#ifdef MOCCA_NO_TRIM_1
+constexpr bool MID_RECORDS = false;
+#else
+constexpr bool MID_RECORDS = T::NPAIR > 0 && 6 * T::NG <= GP_FLOATS && L_MID + 4 * T::NG <= (COMPACT ? (int)L_ABA_END : (int)L_TOTAL);
 #endif
 
 // contact record fields
@@ -687,7 +705,8 @@ DI void chol6_solve(const float* F, const float* b, float* x) {
 // ABA inward pass (lane = body of the current level) + base solve + outward pass (lane = body).
 // Leaves S, V = U / D, 1/D, u / D in LDS and the factor of IA0 in Afac (scalar registers) for the row sweeps, and the new generalised
 // velocity in L_NU.
-template <class T>
+// FACTOR_ACROSS_LANES: the base's 6x6 factor is formed once across lanes (below); false keeps the per-lane chol6_factor (same bits).
+template <class T, bool FACTOR_ACROSS_LANES>
 DI void aba_passes(ModelP M, float* L, int lane, unsigned long long ppk, float* Afac) {
   STAMP_BEGIN;
   // ---- inward pass, one tree level at a time.  8 lanes per body (lane i < 6 owns row i of the 6x6
@@ -842,22 +861,51 @@ DI void aba_passes(ModelP M, float* L, int lane, unsigned long long ppk, float* 
       dst[1] = make_float4(rowb[4], rowb[5], pb_, 0.0f);
     }
     wsync();
-    float IA[21], pA[6];
+    float a0[6];
+#ifdef MOCCA_NO_TRIM_3
+    constexpr bool across = false;
+#else
+    constexpr bool across = FACTOR_ACROSS_LANES;
+#endif
+    // The factor is formed ONCE, across lanes, not once per lane: lane i < 6 owns row i of the Cholesky factor (own[k] = L_ik).  Column j is,
+    // on every lane at once, chol6_factor's own chain for the element (lane, j) -- t = A_ij - sum_k L_ik L_jk with k ascending, the row's
+    // entries L_jk as the scalars the row sweeps want anyway (Afac) -- then one v_rsq (lane j's t is the pivot), one multiply, and the lane
+    // reads that used to follow the factor (unif) taken as the values appear: 27 VALU instead of 56, every entry by the same operations in the
+    // same order, so Afac is bit-identical.  A_ij, i >= j, is the element the upper-triangle storage names: row j, column i of the block.
+    if constexpr (across) {
+      const int li = lane < 6 ? lane : 0;   // (the other lanes repeat row 0; nothing reads them)
+      float colA[6], pA[6], own[6];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const float4 lo = *reinterpret_cast<const float4*>(L + L_B0 + 8 * i), hi = *reinterpret_cast<const float4*>(L + L_B0 + 8 * i + 4);
-      const float rr_[6] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y};
+      for (int j = 0; j < 6; ++j) { colA[j] = L[L_B0 + 8 * j + li]; pA[j] = L[L_B0 + 8 * j + 6]; }
 #pragma unroll
-      for (int j = i; j < 6; ++j) IA[sym(i, j)] = rr_[j];
-      pA[i] = hi.z;
+      for (int j = 0; j < 6; ++j) {
+        float t = colA[j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) t -= own[k] * Afac[sym(j, k)];
+        Afac[sym(j, j)] = readlane(rsq(t), j);
+        own[j] = t * Afac[sym(j, j)];
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) Afac[sym(i, j)] = readlane(own[j], i);
+      }
+      chol6_solve(Afac, pA, a0);   // (every lane, as before: the base acceleration needs no LDS round trip)
+    } else {
+      float IA[21], pA[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const float4 lo = *reinterpret_cast<const float4*>(L + L_B0 + 8 * i), hi = *reinterpret_cast<const float4*>(L + L_B0 + 8 * i + 4);
+        const float rr_[6] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y};
+#pragma unroll
+        for (int j = i; j < 6; ++j) IA[sym(i, j)] = rr_[j];
+        pA[i] = hi.z;
+      }
+      float Ai[21];
+      chol6_factor(IA, Ai);
+      chol6_solve(Ai, pA, a0);
+      // every lane solved the same system: the base acceleration needs no LDS round trip, and the factor travels to the row sweeps in
+      // scalar registers (uniform by construction; it used to cost six 16-byte LDS writes, a barrier and six reads per substep)
+#pragma unroll
+      for (int i = 0; i < 21; ++i) Afac[i] = unif(Ai[i]);
     }
-    float Ai[21], a0[6];
-    chol6_factor(IA, Ai);
-    chol6_solve(Ai, pA, a0);
-    // every lane solved the same system: the base acceleration needs no LDS round trip, and the factor travels to the row sweeps in
-    // scalar registers (uniform by construction; it used to cost six 16-byte LDS writes, a barrier and six reads per substep)
-#pragma unroll
-    for (int i = 0; i < 21; ++i) Afac[i] = unif(Ai[i]);
 #pragma unroll
     for (int i = 0; i < 6; ++i) abase[i] = -a0[i];
   }
@@ -1137,10 +1185,25 @@ DI void geom_points(ModelP M, float* L, int lane) {
     const f4_t t = *(CF4P)(M->gp_tab[lane]);  // point (body frame) + body id, one load
     const int b = __float_as_int(t.w);
     const float pl[3] = {t.x, t.y, t.z};
+    float pw[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const float4 fr = *reinterpret_cast<const float4*>(L + L_RT + 12 * b + 4 * i);   // row i of the rotation, origin component i
-      L[L_GP + 3 * lane + i] = fr.x * pl[0] + fr.y * pl[1] + fr.z * pl[2] + fr.w;
+      pw[i] = fr.x * pl[0] + fr.y * pl[1] + fr.z * pl[2] + fr.w;
+      L[L_GP + 3 * lane + i] = pw[i];
+    }
+    if constexpr (MID_RECORDS<T>) {
+      // The self-collision broad phase compares (a1 + a2) - (b1 + b2) of a pair's two geoms: a1 + a2 is formed HERE, once per geom -- the lane
+      // of end 1 adds its neighbour's end 2 (one DPP add per component; both lanes are below 2 NG) -- instead of once per pair and lane
+      // (141 pairs: three batches a substep).  The same single add of the same two floats: the broad phase's decisions are unchanged.
+      // (as v_add_f32_dpp by hand, like group8_sum2: the optimiser keeps the lane swap as a v_mov_b32_dpp of its own per component)
+      float m0, m1, m2;
+      asm("s_nop 1\n\t"
+          "v_add_f32_dpp %0, %3, %3 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+          "v_add_f32_dpp %1, %4, %4 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+          "v_add_f32_dpp %2, %5, %5 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+          : "=&v"(m0), "=&v"(m1), "=&v"(m2) : "v"(pw[0]), "v"(pw[1]), "v"(pw[2]));
+      if (!(lane & 1)) *reinterpret_cast<float4*>(L + L_MID + 2 * lane) = make_float4(m0, m1, m2, 0.0f);   // record of geom lane / 2
     }
   }
 }
@@ -1355,9 +1418,14 @@ DI ContactFlags collide(ModelP M, float* L, int lane, const float* ter, int next
       const int ids = __float_as_int(pt.x);   // geom_a | geom_b << 5 | body_a << 10 | body_b << 15 | margin code << 20
       const int ga = ids & 31, gb = (ids >> 5) & 31;
       float dm[3];  // distance of the two segment midpoints (x2); the segments' half lengths and radii are constants of the pair (pt.w)
+      if constexpr (MID_RECORDS<T>) {   // the sums of the end points come from geom_points: two 16-byte reads
+        const float4 sa_ = *reinterpret_cast<const float4*>(L + L_MID + 4 * ga), sb_ = *reinterpret_cast<const float4*>(L + L_MID + 4 * gb);
+        dm[0] = sa_.x - sb_.x; dm[1] = sa_.y - sb_.y; dm[2] = sa_.z - sb_.z;
+      } else {
 #pragma unroll
-      for (int i = 0; i < 3; ++i)
-        dm[i] = (L[L_GP + 6 * ga + i] + L[L_GP + 6 * ga + 3 + i]) - (L[L_GP + 6 * gb + i] + L[L_GP + 6 * gb + 3 + i]);
+        for (int i = 0; i < 3; ++i)
+          dm[i] = (L[L_GP + 6 * ga + i] + L[L_GP + 6 * ga + 3 + i]) - (L[L_GP + 6 * gb + i] + L[L_GP + 6 * gb + 3 + i]);
+      }
       const float reach = 2.0f * (pt.w + (float)((ids >> 20) & 0xFF) * (1.0f / 8192.0f));   // + the pair's margin (= pair_margin[k])
       near = dot3(dm, dm) < reach * reach;
     }
@@ -1826,16 +1894,22 @@ DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wan
   int nl;
   {
     bool act = false;
+    float gap = 0.0f;
     if (lane < 2 * T::NJ) {
       const int b = 1 + (lane >> 1), side = lane & 1;
       const float q = L[L_Q + b];
-      const float gap = side == 0 ? q - M->jlo[b] : M->jhi[b] - q;
+      gap = side == 0 ? q - M->jlo[b] : M->jhi[b] - q;
       const float vel = (side == 0 ? 1.0f : -1.0f) * L[L_NU + 5 + b];
       act = M->limit_at_violation ? !(gap > 0.0f) : gap + dt * vel < M->limit_slack;
     }
     const unsigned long long lm = __ballot(act);
     const int rk = lane_rank(lm);
-    if (act && rk < maxr) reinterpret_cast<int*>(L)[L_ROWD + rk] = lane;
+    if (act && rk < maxr) {
+      reinterpret_cast<int*>(L)[L_ROWD + rk] = lane;
+#ifndef MOCCA_NO_TRIM_2
+      L[L_LGAP + rk] = gap;   // the row build takes the candidate's gap from here: the same float, without loading jlo / jhi a second time behind the candidate read
+#endif
+    }
     nl = uni(__popcll(lm));
     if (dbg && lane == 0) {
       dbg[5] = (int32_t)(unsigned)lm; dbg[6] = (int32_t)(unsigned)(lm >> 32);
@@ -1887,8 +1961,12 @@ DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wan
   if (r < nl) {
     const int c = reinterpret_cast<int*>(L)[L_ROWD + r];
     const int b = 1 + (c >> 1), side = c & 1;
+#ifndef MOCCA_NO_TRIM_2
+    const float gap = L[L_LGAP + r];
+#else
     const float q = L[L_Q + b];
     const float gap = side == 0 ? q - M->jlo[b] : M->jhi[b] - q;
+#endif
     kind = 0; jl = b; ba = b; sgn = side == 0 ? 1.0f : -1.0f;
     bias = gap < 0 ? M->erp_noncontact * (-gap) * idt : -gap * idt;
   } else if (T::NCLOS > 0 && r < nl + NCL) {
@@ -2367,8 +2445,11 @@ DI ContactFlags substep(ModelP M, float* L, int lane, const float* ter, int next
   }
   STAMP(1);
   pace_checkpoint(L, done0 + 20, total);
+  // The planner instance of the 48-row kernel sits at its 128-register budget (see below): the factor across lanes spills five registers there
+  // (24 B of scratch), so that instance keeps the per-lane factor.
+  constexpr bool PLANNER48 = !COMPACT && MAXR == 48 && TASK == MOCCA_TASK_WALKER3D_PLANNER;
 #ifndef MOCCA_SKIP_ABA
-  aba_passes<T>(M, L, lane, ppk, Afac);
+  aba_passes<T, !PLANNER48>(M, L, lane, ppk, Afac);
 #endif
   STAMP(2);
   pace_checkpoint(L, done0 + 36, total);
@@ -2376,7 +2457,7 @@ DI ContactFlags substep(ModelP M, float* L, int lane, const float* ter, int next
   // The planner instance of the 48-row kernel sits at its 128-register budget: with the matrix-pipe build compiled in, the deepest step of its VALU
   // build spills two 4-register tuples to scratch (whatever the new path holds: X store, operand reads, MFMAs or tile stores alone).  It keeps the
   // VALU build for every row count until that instance has room.
-  solve_constraints<T, (COMPACT || MAXR != 48 || TASK != MOCCA_TASK_WALKER3D_PLANNER)>(M, L, lane, nc, nc_wanted, ppk, dbg, Afac, prio, rows_out);
+  solve_constraints<T, !PLANNER48>(M, L, lane, nc, nc_wanted, ppk, dbg, Afac, prio, rows_out);
 #endif
   if (dbg) { __builtin_amdgcn_s_waitcnt(0); dbg_fold_step(dbg, lane); }   // (lane 0 wrote the twelve words above; it reads them back itself)
   STAMP(3);
