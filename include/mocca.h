@@ -258,9 +258,47 @@ int mocca_set_trajectory(mocca_handle h, const float *table_host, int n_frames, 
  * triangle among the 2 W x 2 W cells around the grid point nearest to its centre, W = ceil((radius + contact margin) x scale + 1/2) -- every
  * cell it can reach (W = 1 for feet and limbs at 4 points per metre, 2 for the walker's 14 cm pelvis and Mike's 23 cm waist sphere, mike.xml:20,
  * whose contact ends MikePlannerEnv's episode; a grid on which a sphere would span more than 4 cells each way is refused);
- * outside the grid there is no ground.  One grid shared by all envs of the handle
- * (the reference loads the same file for every env).  Required before reset / step / observe with MOCCA_TASK_WALKER3D_PLANNER. */
+ * outside the grid there is no ground.  By default one grid is shared by all envs of the handle
+ * (the reference loads the same file for every env): this call is mocca_set_heightfield_bank with n_fields = 1.
+ * A grid is required before reset / step / observe with MOCCA_TASK_WALKER3D_PLANNER. */
 int mocca_set_heightfield(mocca_handle h, const float *heights_host, int rows, int cols, double scale);
+
+/* The terrain BANK of the planner envs: n_fields height fields of one shape in device memory, every env standing on one of them -- what
+ * `HeightField.reload(data=None)` (bullet_objects.py:355-441) gives one env at a time, a fresh random terrain, for a whole batch.  Physics,
+ * the reset's target height, mocca_height_scan and mocca_render read the env's OWN field.
+ *   mocca_set_heightfield_bank: heights_host [n_fields][rows][cols] f32 (HOST memory, copied), or NULL for a bank of zeros to be generated into;
+ *     n_fields 1 .. MOCCA_HF_MAX_FIELDS.  The checks of mocca_set_heightfield (at least 2 x 2, positive scale, a grid that is not too fine
+ *     for the robot); waits for the launches in flight; planner task only.  The range [zmin, zmax] of every field is kept on the device beside
+ *     the bank (the ray caster clips to it).  Every env is put on field 0 and redraw-at-reset is switched off.  NULL with n_fields == 0 detaches.
+ *   mocca_generate_heightfields: fills fields first .. first + count - 1 with the reference's generator (get_random_height_field,
+ *     bullet_objects.py:395-441: n_peaks super-Gaussian peaks / scale + Perlin noise of 4 x 4 and 8 x 8 lattice cells, minus the mean of the
+ *     5 x 5 corner platform the robot starts over, which is flattened to exactly 0) in f32, times `gain` (finite, > 0: the difficulty knob),
+ *     and writes their ranges.  Asynchronous on `stream`: no allocation, no host read, no atomics -- the caller orders it against the step
+ *     launches on the same stream.  n_peaks 1 .. MOCCA_HF_MAX_PEAKS; rows and cols must be multiples of 8 (the lattices divide them).
+ *     The draws: uniform (w >> 8) 2^-24 of word d & 3 of philox4x32(d >> 2, block, field index in the bank, 3, seed low, seed high).  Block 0,
+ *     d = 256 a + k: parameter k of array a, in the reference's order -- height 0.1 + 2.9 u, centre along the first axis and along the
+ *     second (-half + 2 half u, half = size / scale / 2), the two spreads 1 + 15 u, the two exponents 2 (1 + int(5 u)); the stride is 256
+ *     whatever n_peaks is, so fewer peaks are a prefix.  Block 1, d = 0 .. 24: the gradient angles 2 pi u of the 5 x 5 lattice, row-major; block
+ *     2, d = 0 .. 80: those of the 9 x 9 lattice.  The first grid axis is the ROW index (the reference's quirk).  The field's index in the bank
+ *     keys it: every handle that generates the same bank with the same seed holds the same fields.
+ *   mocca_set_env_fields: field_dev int32 [n_envs] (DEVICE memory), the field of every env; NULL puts all envs on field 0.  The values are
+ *     checked against the bank on the host after waiting for `stream` (it may synchronise, as mocca_render does for its env ids).
+ *     redraw_at_reset != 0: every reset of env e -- mocca_reset and the auto-reset inside mocca_step / mocca_plan_step / mocca_act_plan_step --
+ *     first draws field = (uint64(w) * n_fields) >> 32, w = word 0 of philox4x32(0, episode, global env id, 2, seed low, seed high) with the
+ *     reset's seed, BEFORE the walk target's height is looked up.  Counter word 3 = 2 is a domain of its own and the episode's draw counter
+ *     is not touched: every other draw keeps its value.  The index lives in an array of the handle, not in the task record: a snapshot of a
+ *     bank run is state + task + env fields.
+ *   mocca_get_env_fields / mocca_get_heightfields: the readbacks, asynchronous on `stream`: int32 [n_envs], f32 [count][rows][cols]
+ *     (DEVICE memory).
+ * MOCCA_E_ARG, the handle unchanged: not the planner task, n_fields outside its range, no bank attached, first / count outside the bank,
+ * rows or cols no multiple of 8 (generate), n_peaks outside 1 .. 256, a gain that is not finite and positive, an env field outside the bank. */
+#define MOCCA_HF_MAX_FIELDS 1024
+#define MOCCA_HF_MAX_PEAKS 256
+int mocca_set_heightfield_bank(mocca_handle h, const float *heights_host, int n_fields, int rows, int cols, double scale);
+int mocca_generate_heightfields(mocca_handle h, int first, int count, uint64_t seed, int n_peaks, double gain, void *stream);
+int mocca_set_env_fields(mocca_handle h, const int32_t *field_dev, int redraw_at_reset, void *stream);
+int mocca_get_env_fields(mocca_handle h, int32_t *field_dev, void *stream);
+int mocca_get_heightfields(mocca_handle h, int first, int count, float *out_dev, void *stream);
 
 /* The base controller of the planner envs (env_locomotion.py:1029-1040): the agent's action is a 15-number plan; inside step() an actor-critic
  * pair of MLPs turns [robot_state(50), plan x action_scale] (65 floats, :1093) into the 21 joint actions, and the critic's value is part of the

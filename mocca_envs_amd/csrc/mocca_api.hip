@@ -19,6 +19,7 @@
 #include "mocca_render.h"
 #include "mocca_rollout.h"
 #include "mocca_scan.h"
+#include "mocca_terrain.h"
 
 using namespace mocca;
 
@@ -139,10 +140,14 @@ struct mocca_ctx {
   DevBuf<float> d_traj;         // Cassie mocap / phase envs: the motion table (mocca_set_trajectory), owned by the handle
   int traj_n = 0;
   double traj_tmax = 0.0, traj_cstep = 0.0;
-  DevBuf<float> d_hf;           // planner envs: the height field (mocca_set_heightfield), owned by the handle
-  int hf_rows = 0, hf_cols = 0;
+  // planner envs: the terrain bank (mocca_set_heightfield_bank; mocca_set_heightfield attaches a bank of one), all owned by the handle
+  DevBuf<float> d_hf;           // [hf_n_fields][hf_planes][rows][cols]: a field's heights, then its max-pooled copies (windows 2 .. hf_planes)
+  int hf_rows = 0, hf_cols = 0, hf_n_fields = 0, hf_planes = 1;
   float hf_scale = 0.0f;
-  float hf_zmin = 0.0f, hf_zmax = 0.0f;   // range of the heights (mocca_render clips its rays to it)
+  DevBuf<float> d_hf_range;     // [hf_n_fields][2] range of each field's heights (mocca_render clips its rays to it)
+  DevBuf<float> d_hf_part;      // [hf_n_fields][blocks][2] scratch of mocca_generate_heightfields' range reduction
+  DevBuf<int32_t> d_hf_field;   // [N] the field each env stands on (mocca_set_env_fields)
+  int hf_redraw = 0;            // every reset draws the env's field anew
   DevBuf<float> d_scenes;       // mocca_render: world-space primitives of each view, owned by the handle, grown on demand
   int scenes_cap = 0;           // views it holds
   DevBuf<float> d_scan_pts;     // mocca_set_height_scan: the pattern [scan_n][2] in the heading frame, owned by the handle
@@ -549,6 +554,9 @@ static StepArgs make_args(mocca_handle h) {
   a.pace_acc = h->d_pace_acc;
   a.ep_ret = h->d_ep_ret; a.ep_masks = h->ep_masks; a.ep_bad = h->ep_bad; a.ep_totals = h->ep_totals;   // (ep_rec / ep_serial: mocca_step only)
   a.hf = h->d_hf; a.hf_rows = h->hf_rows; a.hf_cols = h->hf_cols; a.hf_scale = h->hf_scale;
+  if (h->hf_n_fields > 1) {   // (a bank of one is the shared grid: the kernels take the path they always took)
+    a.hf_field = h->d_hf_field; a.hf_stride = h->hf_planes * h->hf_rows * h->hf_cols; a.hf_n_fields = h->hf_n_fields; a.hf_redraw = h->hf_redraw;
+  }
   a.robot_state = h->d_ctrl_image ? h->d_robot_state.get() : nullptr;   // (base_value: mocca_plan_step only)
   return a;
 }
@@ -568,9 +576,10 @@ static int need_heightfield(mocca_handle h, const char* who, const char* when) {
   return MOCCA_E_ARG;
 }
 // ... and this is what the ray caster and the height scan read of it; the other tasks have no grid
-static mocca_rdr::HeightField heightfield_record(mocca_handle h) {
-  if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER) return mocca_rdr::HeightField{nullptr, 0, 0, 0.0f, 0.0f, 0.0f};
-  return mocca_rdr::HeightField{h->d_hf, h->hf_rows, h->hf_cols, h->hf_scale, h->hf_zmin, h->hf_zmax};
+static mocca_rdr::HeightFieldBank heightfield_record(mocca_handle h) {
+  if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER) return mocca_rdr::HeightFieldBank{nullptr, 0, 0, 0.0f, nullptr, nullptr, 0};
+  return mocca_rdr::HeightFieldBank{h->d_hf, h->hf_rows, h->hf_cols, h->hf_scale, h->d_hf_range, h->hf_n_fields > 1 ? h->d_hf_field.get() : nullptr,
+                                    (size_t)h->hf_planes * h->hf_rows * h->hf_cols};
 }
 // what reset / step / observe cannot run without: the mocap / phase envs read their targets, reset poses and reward references from the
 // motion table, the planner envs their ground from the height field
@@ -830,9 +839,9 @@ int mocca_set_trajectory(mocca_handle h, const float* table_host, int n_frames, 
   return MOCCA_OK;
 }
 
-int mocca_set_heightfield(mocca_handle h, const float* heights_host, int rows, int cols, double scale) try {
-  if (!h) return MOCCA_E_ARG;
-  if (!heights_host || rows < 2 || cols < 2 || !(scale > 0.0)) { h->err = "mocca_set_heightfield: needs at least 2 x 2 heights and a positive scale"; return MOCCA_E_ARG; }
+// Attach a terrain bank (mocca_set_heightfield: a bank of one; `who`: the entry point's name).  heights_host == nullptr: a bank of zeros.
+static int attach_bank(mocca_handle h, const std::string& who, const float* heights_host, int n_fields, int rows, int cols, double scale) {
+  if (rows < 2 || cols < 2 || !(scale > 0.0)) { h->err = who + ": needs at least 2 x 2 heights and a positive scale"; return MOCCA_E_ARG; }
   // Search window of every terrain contact slot: a sphere of reach rho = radius + margin around a centre that is at most half a cell from
   // its nearest grid point touches only cells within W = ceil(rho scale + 1/2) of that point (1e-6: a reach of exactly half a cell is W = 1).
   // W - 1 travels in bits 30..31 of the slot record; a grid so fine that a sphere spans more than 4 cells each way is refused.
@@ -843,49 +852,161 @@ int mocca_set_heightfield(mocca_handle h, const float* heights_host, int rows, i
     const double reach = (double)h->model.slot_tab[sl][0] + (double)((ids >> 17) & 0xFFu) / 8192.0;
     int w = (int)std::ceil(reach * scale + 0.5 - 1e-6);
     if (w < 1) w = 1;
-    if (w > 4 && ((ids >> 25) & 1u)) { h->err = "mocca_set_heightfield: the grid is too fine for this robot (a contact sphere would span more than 4 cells each way)"; return MOCCA_E_ARG; }
+    if (w > 4 && ((ids >> 25) & 1u)) { h->err = who + ": the grid is too fine for this robot (a contact sphere would span more than 4 cells each way)"; return MOCCA_E_ARG; }
     if (w > 4) w = 4;
     wbits[sl] = (ids & 0x3FFFFFFFu) | ((uint32_t)(w - 1) << 30);
     if (((ids >> 25) & 1u) && w > wmax) wmax = w;
   }
+  const size_t cells = (size_t)rows * cols, stride = cells * wmax;
+  if (stride > ((size_t)1 << 26) || stride * n_fields > ((size_t)1 << 30)) { h->err = who + ": the bank is larger than 2^30 heights (pooled copies included)"; return MOCCA_E_ARG; }
   DeviceGuard guard(h->device);
-  // the heights, followed by one max-pooled copy per window 2 .. wmax (copy k: the highest point within k + 1 cells of each grid point): what a
-  // wide sphere's search is pruned by with one load
-  const size_t cells = (size_t)rows * cols;
-  std::vector<float> host(cells * wmax);
-  std::memcpy(host.data(), heights_host, cells * sizeof(float));
-  for (int w = 2; w <= wmax; ++w) {
-    float* out = host.data() + cells * (w - 1);
-    for (int j = 0; j < rows; ++j)
-      for (int i = 0; i < cols; ++i) {
-        float m = -1e30f;
-        for (int jj = (j - w < 0 ? 0 : j - w); jj <= (j + w > rows - 1 ? rows - 1 : j + w); ++jj)
-          for (int ii = (i - w < 0 ? 0 : i - w); ii <= (i + w > cols - 1 ? cols - 1 : i + w); ++ii)
-            m = heights_host[(size_t)jj * cols + ii] > m ? heights_host[(size_t)jj * cols + ii] : m;
-        out[(size_t)j * cols + i] = m;
+  // every field: the heights, followed by one max-pooled copy per window 2 .. wmax (copy k: the highest point within k + 1 cells of each grid
+  // point): what a wide sphere's search is pruned by with one load.  Beside the bank, each field's range.
+  std::vector<float> host, range((size_t)n_fields * 2, 0.0f);
+  if (heights_host) {
+    host.resize(stride * n_fields);
+    for (int f = 0; f < n_fields; ++f) {
+      const float* in = heights_host + cells * f;
+      float* field = host.data() + stride * f;
+      std::memcpy(field, in, cells * sizeof(float));
+      for (int w = 2; w <= wmax; ++w) {
+        float* out = field + cells * (w - 1);
+        for (int j = 0; j < rows; ++j)
+          for (int i = 0; i < cols; ++i) {
+            float m = -1e30f;
+            for (int jj = (j - w < 0 ? 0 : j - w); jj <= (j + w > rows - 1 ? rows - 1 : j + w); ++jj)
+              for (int ii = (i - w < 0 ? 0 : i - w); ii <= (i + w > cols - 1 ? cols - 1 : i + w); ++ii)
+                m = in[(size_t)jj * cols + ii] > m ? in[(size_t)jj * cols + ii] : m;
+            out[(size_t)j * cols + i] = m;
+          }
       }
+      float zmin = in[0], zmax = in[0];
+      for (size_t k = 1; k < cells; ++k) {
+        zmin = in[k] < zmin ? in[k] : zmin;
+        zmax = in[k] > zmax ? in[k] : zmax;
+      }
+      range[2 * (size_t)f] = zmin; range[2 * (size_t)f + 1] = zmax;
+    }
   }
   // the window bits go into a COPY of the model; the handle's host image takes them only once the device has them
   auto next = std::make_unique<MoccaModel>(h->model);
   for (int sl = 0; sl < next->n_slots; ++sl) std::memcpy(&next->slot_tab[sl][2], &wbits[sl], 4);
-  DevBuf<float> hf;
-  hipError_t e = hf.alloc(host.size(), false);
-  if (e == hipSuccess) e = hipMemcpy(hf, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (int rc = commit_ready(h, "mocca_set_heightfield", e)) return rc;   // no launch in flight still reads the old grid or the old slot records
+  DevBuf<float> hf, rng, part;
+  DevBuf<int32_t> field;
+  hipError_t e = hf.alloc(stride * n_fields, !heights_host);
+  if (e == hipSuccess && heights_host) e = hipMemcpy(hf, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = rng.alloc(range.size(), false);
+  if (e == hipSuccess) e = hipMemcpy(rng, range.data(), range.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = part.alloc((size_t)n_fields * mocca_terrain::terrain_blocks(rows, cols) * 2, true);
+  if (e == hipSuccess) e = field.alloc((size_t)h->n_envs, true);
+  if (int rc = commit_ready(h, who.c_str(), e)) return rc;   // no launch in flight still reads the old bank or the old slot records
   // the device model is rewritten in place: the last step that can fail, and one that fails leaves host and device records as they were
   if ((e = hipMemcpy(h->d_model, next.get(), sizeof(MoccaModel), hipMemcpyHostToDevice)) != hipSuccess) {
     h->err = std::string("hipMemcpy(model): ") + hipGetErrorString(e); return MOCCA_E_HIP;
   }
   h->model = *next;
-  h->d_hf.swap(hf);
+  h->d_hf.swap(hf); h->d_hf_range.swap(rng); h->d_hf_part.swap(part); h->d_hf_field.swap(field);
   h->hf_rows = rows; h->hf_cols = cols; h->hf_scale = (float)scale;
-  h->hf_zmin = h->hf_zmax = heights_host[0];
-  for (size_t k = 1; k < cells; ++k) {
-    h->hf_zmin = heights_host[k] < h->hf_zmin ? heights_host[k] : h->hf_zmin;
-    h->hf_zmax = heights_host[k] > h->hf_zmax ? heights_host[k] : h->hf_zmax;
+  h->hf_n_fields = n_fields; h->hf_planes = wmax; h->hf_redraw = 0;
+  return MOCCA_OK;
+}
+
+int mocca_set_heightfield(mocca_handle h, const float* heights_host, int rows, int cols, double scale) try {
+  if (!h) return MOCCA_E_ARG;
+  if (!heights_host) { h->err = "mocca_set_heightfield: needs at least 2 x 2 heights and a positive scale"; return MOCCA_E_ARG; }
+  return attach_bank(h, "mocca_set_heightfield", heights_host, 1, rows, cols, scale);
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_heightfield"); }
+
+int mocca_set_heightfield_bank(mocca_handle h, const float* heights_host, int n_fields, int rows, int cols, double scale) try {
+  if (!h) return MOCCA_E_ARG;
+  const std::string who = "mocca_set_heightfield_bank";
+  if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER) { h->err = who + ": only the planner task (Walker3DPlannerEnv, MikePlannerEnv) stands on height fields"; return MOCCA_E_ARG; }
+  if (!heights_host && n_fields == 0) {   // detach
+    DeviceGuard guard(h->device);
+    if (int rc = commit_ready(h, who.c_str())) return rc;
+    h->d_hf.reset(); h->d_hf_range.reset(); h->d_hf_part.reset(); h->d_hf_field.reset();
+    h->hf_rows = h->hf_cols = h->hf_n_fields = h->hf_redraw = 0; h->hf_planes = 1; h->hf_scale = 0.0f;
+    return MOCCA_OK;
+  }
+  if (n_fields < 1 || n_fields > MOCCA_HF_MAX_FIELDS) { h->err = who + ": n_fields must be 1 .. " + std::to_string(MOCCA_HF_MAX_FIELDS); return MOCCA_E_ARG; }
+  return attach_bank(h, who, heights_host, n_fields, rows, cols, scale);
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_heightfield_bank"); }
+
+// what the bank calls below share: a planner handle with a bank, and fields first .. first + count - 1 inside it
+static int need_bank(mocca_handle h, const std::string& who, int first, int count) {
+  if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER || !h->d_hf) { h->err = who + ": no terrain bank (mocca_set_heightfield_bank)"; return MOCCA_E_ARG; }
+  if (first < 0 || count < 1 || first > h->hf_n_fields - count) {
+    h->err = who + ": fields " + std::to_string(first) + " .. " + std::to_string((long long)first + count - 1) + " are not inside the bank of " + std::to_string(h->hf_n_fields);
+    return MOCCA_E_ARG;
   }
   return MOCCA_OK;
-} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_heightfield"); }
+}
+
+int mocca_generate_heightfields(mocca_handle h, int first, int count, uint64_t seed, int n_peaks, double gain, void* stream) try {
+  if (!h) return MOCCA_E_ARG;
+  const std::string who = "mocca_generate_heightfields";
+  if (int rc = need_bank(h, who, first, count)) return rc;
+  if ((h->hf_rows & 7) || (h->hf_cols & 7)) { h->err = who + ": rows and cols must be multiples of 8 (the noise lattices of 4 and 8 cells divide them)"; return MOCCA_E_ARG; }
+  if (n_peaks < 1 || n_peaks > MOCCA_HF_MAX_PEAKS) { h->err = who + ": n_peaks must be 1 .. " + std::to_string(MOCCA_HF_MAX_PEAKS); return MOCCA_E_ARG; }
+  if (!std::isfinite(gain) || !(gain > 0.0)) { h->err = who + ": gain must be finite and > 0"; return MOCCA_E_ARG; }
+  DeviceGuard guard(h->device);
+  mocca_terrain::TerrainArgs a{};
+  a.bank = h->d_hf; a.range = h->d_hf_range; a.part = h->d_hf_part;
+  a.rows = h->hf_rows; a.cols = h->hf_cols; a.planes = h->hf_planes; a.stride = (size_t)h->hf_planes * h->hf_rows * h->hf_cols;
+  a.scale = h->hf_scale; a.gain = (float)gain;
+  a.first = first; a.count = count; a.n_peaks = n_peaks;
+  a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+  mocca_terrain::launch_generate((hipStream_t)stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_generate_heightfields"); }
+
+int mocca_set_env_fields(mocca_handle h, const int32_t* field_dev, int redraw_at_reset, void* stream) try {
+  if (!h) return MOCCA_E_ARG;
+  const std::string who = "mocca_set_env_fields";
+  if (int rc = need_bank(h, who, 0, 1)) return rc;
+  DeviceGuard guard(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t bytes = (size_t)h->n_envs * sizeof(int32_t);
+  if (field_dev) {
+    std::vector<int32_t> ids((size_t)h->n_envs);
+    HIP_TRY(h, hipMemcpyAsync(ids.data(), field_dev, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (int e = 0; e < h->n_envs; ++e)
+      if (ids[e] < 0 || ids[e] >= h->hf_n_fields) {
+        h->err = who + ": field " + std::to_string(ids[e]) + " (env " + std::to_string(e) + ") is outside 0 .. " + std::to_string(h->hf_n_fields - 1);
+        return MOCCA_E_ARG;
+      }
+    HIP_TRY(h, hipMemcpyAsync(h->d_hf_field, field_dev, bytes, hipMemcpyDeviceToDevice, s));
+  } else {
+    HIP_TRY(h, hipMemsetAsync(h->d_hf_field, 0, bytes, s));
+  }
+  h->hf_redraw = redraw_at_reset != 0;
+  return MOCCA_OK;
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_env_fields"); }
+
+int mocca_get_env_fields(mocca_handle h, int32_t* field_dev, void* stream) try {
+  if (!h) return MOCCA_E_ARG;
+  if (!field_dev) { h->err = "mocca_get_env_fields: field_dev must not be NULL"; return MOCCA_E_ARG; }
+  if (int rc = need_bank(h, "mocca_get_env_fields", 0, 1)) return rc;
+  DeviceGuard guard(h->device);
+  HIP_TRY(h, hipMemcpyAsync(field_dev, h->d_hf_field, (size_t)h->n_envs * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return MOCCA_OK;
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_get_env_fields"); }
+
+int mocca_get_heightfields(mocca_handle h, int first, int count, float* out_dev, void* stream) try {
+  if (!h) return MOCCA_E_ARG;
+  if (!out_dev) { h->err = "mocca_get_heightfields: out_dev must not be NULL"; return MOCCA_E_ARG; }
+  if (int rc = need_bank(h, "mocca_get_heightfields", first, count)) return rc;
+  DeviceGuard guard(h->device);
+  const size_t cells = (size_t)h->hf_rows * h->hf_cols, w = cells * sizeof(float);   // the heights of each field, without its pooled copies
+  const float* src = h->d_hf.get() + cells * h->hf_planes * first;
+  if (h->hf_planes == 1) HIP_TRY(h, hipMemcpyAsync(out_dev, src, w * count, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  else
+    for (int f = 0; f < count; ++f)
+      HIP_TRY(h, hipMemcpyAsync(out_dev + cells * f, src + cells * h->hf_planes * f, w, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return MOCCA_OK;
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_get_heightfields"); }
 
 int mocca_observe(mocca_handle h, float* obs_dev, void* stream) {
   if (!h || !obs_dev) return MOCCA_E_ARG;
@@ -1052,7 +1173,7 @@ int mocca_render(mocca_handle h, const int32_t* env_ids_dev, int n_views, const 
   mocca_rdr::launch_scene(s, scene_args(h), env_ids_dev, h->n_envs, n_views, h->d_scenes);
   HIP_TRY(h, hipGetLastError());
   mocca_rdr::launch_raycast(s, h->d_scenes, cameras_dev, n_views, width, height, h->task_id, h->model.plank_shape, h->model.plank_half,
-                            heightfield_record(h), rgb_dev, depth_dev, id_dev);
+                            heightfield_record(h), env_ids_dev, rgb_dev, depth_dev, id_dev);
   HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_render"); }

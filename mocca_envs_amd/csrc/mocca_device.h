@@ -289,6 +289,11 @@ struct StepArgs {
   // only): the critic's estimate, whose term log(max(1, v)) / 3 the step kernel adds to the reward (:1101)
   float* robot_state;
   const float* base_value;
+  // planner envs on a terrain bank of more than one field (mocca_set_heightfield_bank), null otherwise: hf_field [N], the field env e stands
+  // on -- its grid starts at hf + hf_field[e] * hf_stride --, handle-owned and outside the task record; hf_redraw: every reset draws it anew
+  // from the hf_n_fields of the bank (mocca_set_env_fields).  Last in the record: the arguments in front keep their offsets.
+  int32_t* hf_field;
+  int hf_stride, hf_n_fields, hf_redraw;
 };
 constexpr int ROBOT_STATE_STRIDE = 64;   // = mocca_ctrl::CTRL_RS_STRIDE (mocca_controller.h; checked in mocca_api.hip)
 
@@ -1147,6 +1152,17 @@ DI float hf_height_at(const float* hf, int rows, int cols, float sc, float x, fl
   ix = ix < 0 ? 0 : (ix > cols - 1 ? cols - 1 : ix);
   iy = iy < 0 ? 0 : (iy > rows - 1 ? rows - 1 : iy);
   return hf[iy * cols + ix];
+}
+// the grid env `e` (index in this handle) stands on: the shared one, or its field of the bank -- one wave-uniform load per env
+DI const float* env_heightfield(const StepArgs& a, int e) {
+  return a.hf_field ? a.hf + (size_t)uni(a.hf_field[e]) * (size_t)a.hf_stride : a.hf;
+}
+// Field of global env `env` in episode `episode` under redraw-at-reset (mocca_set_env_fields): word 0 of the Philox block (0, episode, env,
+// 2) -- counter word 3 is 0 for the envs' own draws and 1 for the policy's noise, so no other draw moves -- scaled to 0 .. n_fields - 1
+DI int draw_env_field(const StepArgs& a, int env, int episode) {
+  uint32_t o[4];
+  philox4x32(0u, (uint32_t)episode, (uint32_t)env, 2u, a.seed_lo, a.seed_hi, o);
+  return (int)(((uint64_t)o[0] * (uint64_t)(uint32_t)a.hf_n_fields) >> 32);
 }
 
 DI float clamp01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }
@@ -2797,7 +2813,17 @@ DI void reset_env(const StepArgs& a, ModelP M, float* L, float* ter, int env, in
     t.draw += 2;
     t.wt[0] = -R + 2.0f * R * ux;
     t.wt[1] = -R + 2.0f * R * uy;
-    t.wt[2] = hf_height_at(a.hf, a.hf_rows, a.hf_cols, a.hf_scale, t.wt[0], t.wt[1]);
+    const float* hf = a.hf;
+    if (a.hf_field) {   // a terrain bank: the new episode's field first (redrawn, or the one the env keeps), then the target's height ON it
+      if (a.hf_redraw) {
+        const int f = draw_env_field(a, env, t.episode);
+        if (lane == 0) a.hf_field[env - a.env_offset] = f;
+        hf += (size_t)f * (size_t)a.hf_stride;
+      } else {
+        hf = env_heightfield(a, env - a.env_offset);
+      }
+    }
+    t.wt[2] = hf_height_at(hf, a.hf_rows, a.hf_cols, a.hf_scale, t.wt[0], t.wt[1]);
     calc_potential(M, L, t, ro, &dist, &cd, &sd);
     if (lane == 0) softsign_tail(sd, cd, obs + ROBOT_OBS<T>);
   } else if (TASK == MOCCA_TASK_WALKER3D_CUSTOM) {

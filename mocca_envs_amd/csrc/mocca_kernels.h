@@ -356,6 +356,8 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
     // a heavy env is almost always still heavy, and more than half of a substep runs before its own count is known
     int last_rows = uni((int)tk[MOCCA_TW_LAST_ROWS]);
     if (!INJECT && a.pace == 0) set_issue_priority(last_rows, a.prio);
+    const float* hfp = a.hf;   // planner envs: the env's own grid of the terrain bank, read once per env
+    if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) hfp = env_heightfield(a, env);
 #pragma unroll 1
     for (int s = 0; s < nsub; ++s) {
       // launder the model pointer: keeps LICM from hoisting dozens of loop-invariant model loads out of the
@@ -364,7 +366,7 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
       int ln = lane;  // same for lane-derived offsets and predicates (recomputing them costs a few instructions)
       unsigned long long pk = ppk;  // laundered too: otherwise every (ppk >> 5k) & 31 and the addresses derived from it
       asm volatile("" : "+s"(Ms), "+v"(ln), "+v"(pk));  // are hoisted out of the loop and spilled
-      fl = substep<T, TASK>(Ms, L, ln, ter, nsi0, pk, dbg, a.prio, last_rows, HeightFieldArgs{a.hf, a.hf_rows, a.hf_cols, a.hf_scale}, s, nsub, &cover);
+      fl = substep<T, TASK>(Ms, L, ln, ter, nsi0, pk, dbg, a.prio, last_rows, HeightFieldArgs{hfp, a.hf_rows, a.hf_cols, a.hf_scale}, s, nsub, &cover);
     }
     if constexpr (INJECT) {  // getContactPoints results handed in by the caller (robots.py:74-86, env_locomotion.py:634-650, :880-890)
       const int32_t* tc = a.inj_touch + (size_t)env * T::NFEET;

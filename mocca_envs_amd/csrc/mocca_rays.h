@@ -24,6 +24,14 @@ struct SceneArgs {
   int dyn_stride, terrain_stride, task_id;
 };
 struct HeightField { const float* data; int rows, cols; float scale, zmin, zmax; };   // data == nullptr: none
+// The planner handle's terrain bank (mocca_set_heightfield_bank): field f at data + f * stride, its range at range[2 f], range[2 f + 1] (device
+// memory: mocca_generate_heightfields writes it without telling the host); env e stands on field[e], or on field 0 where field == nullptr.
+struct HeightFieldBank { const float* data; int rows, cols; float scale; const float* range; const int32_t* field; size_t stride; };
+DI HeightField env_heightfield(const HeightFieldBank& b, int env) {
+  if (!b.data) return HeightField{nullptr, 0, 0, 0.0f, 0.0f, 0.0f};
+  const int f = b.field ? b.field[env] : 0;
+  return HeightField{b.data + (size_t)f * b.stride, b.rows, b.cols, b.scale, b.range[2 * f], b.range[2 * f + 1]};
+}
 
 DI void euler_to_mat(float roll, float pitch, float yaw, float* R) {
   const float cr = cosf(roll), sr = sinf(roll), cp = cosf(pitch), sp = sinf(pitch), cy = cosf(yaw), sy = sinf(yaw);

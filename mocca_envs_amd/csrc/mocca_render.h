@@ -20,7 +20,8 @@ static_assert(SCENE_WORDS * 4 <= 2048, "the scene of one env stays under 2 KB of
 void launch_link_frames(hipStream_t s, const SceneArgs& a, int n, float* frames);
 // scenes [n_views][SCENE_WORDS] of the listed envs (ids are clamped to 0 .. n_envs - 1)
 void launch_scene(hipStream_t s, const SceneArgs& a, const int32_t* env_ids, int n_envs, int n_views, float* scenes);
+// (bank.data != nullptr: view v sees the grid of env env_ids[v])
 void launch_raycast(hipStream_t s, const float* scenes, const float* cameras, int n_views, int width, int height, int task_id, int plank_shape,
-                    const float* plank_half, HeightField hf, uint8_t* rgb, float* depth, int32_t* id);
+                    const float* plank_half, HeightFieldBank bank, const int32_t* env_ids, uint8_t* rgb, float* depth, int32_t* id);
 
 }  // namespace mocca_rdr

@@ -278,11 +278,12 @@ DI float hit_heightfield(const HeightField hf, const float* o, const float* d, f
 }
 
 __global__ __launch_bounds__(TILE * TILE) void raycast_kernel(const float* scenes, const float* cameras, int width, int height, int task_id,
-                                                              int plank_shape, float ph0, float ph1, float ph2, HeightField hf, uint8_t* rgb,
-                                                              float* depth, int32_t* idout) {
+                                                              int plank_shape, float ph0, float ph1, float ph2, HeightFieldBank bank,
+                                                              const int32_t* env_ids, uint8_t* rgb, float* depth, int32_t* idout) {
   __shared__ float S[SCENE_WORDS];
   __shared__ float CAM[MOCCA_CAMERA_FLOATS];
   const int view = blockIdx.z, tid = threadIdx.y * TILE + threadIdx.x;
+  const HeightField hf = env_heightfield(bank, bank.data ? env_ids[view] : 0);   // the grid and range of the view's env
   const float* sc = scenes + (size_t)view * SCENE_WORDS;
   for (int k = tid; k < SCENE_WORDS; k += TILE * TILE) S[k] = sc[k];
   if (tid < MOCCA_CAMERA_FLOATS) CAM[tid] = cameras[(size_t)view * MOCCA_CAMERA_FLOATS + tid];
@@ -415,10 +416,10 @@ void launch_scene(hipStream_t s, const SceneArgs& a, const int32_t* env_ids, int
   hipLaunchKernelGGL(scene_kernel, dim3(n_views), dim3(64), 0, s, a, env_ids, n_envs, scenes);
 }
 void launch_raycast(hipStream_t s, const float* scenes, const float* cameras, int n_views, int width, int height, int task_id, int plank_shape,
-                    const float* plank_half, HeightField hf, uint8_t* rgb, float* depth, int32_t* id) {
+                    const float* plank_half, HeightFieldBank bank, const int32_t* env_ids, uint8_t* rgb, float* depth, int32_t* id) {
   const dim3 grid((width + TILE - 1) / TILE, (height + TILE - 1) / TILE, n_views);
   hipLaunchKernelGGL(raycast_kernel, grid, dim3(TILE, TILE), 0, s, scenes, cameras, width, height, task_id, plank_shape, plank_half[0],
-                     plank_half[1], plank_half[2], hf, rgb, depth, id);
+                     plank_half[1], plank_half[2], bank, env_ids, rgb, depth, id);
 }
 
 }  // namespace mocca_rdr

@@ -6,7 +6,7 @@ namespace mocca_scan {
 
 struct ScanArgs {
   mocca_rdr::SceneArgs scene;      // the handle's records; read only
-  mocca_rdr::HeightField hf;       // planner task: the grid; data == nullptr otherwise
+  mocca_rdr::HeightFieldBank hf;   // planner task: the bank, env e on its own grid; data == nullptr otherwise
   const float* points;             // [n_points][2] in the heading frame, device memory owned by the handle
   int n_points;
   float z_above, max_drop;

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(64) void scan_kernel(ScanArgs a) {
   const bool ground = task == MOCCA_TASK_WALKER3D_CUSTOM || task == MOCCA_TASK_CASSIE;
   const bool cylinder = M->plank_shape == MOCCA_PLANK_CYLINDER;
   const float ph[3] = {M->plank_half[0], M->plank_half[1], M->plank_half[2]};
-  const HeightField hf = a.hf;
+  const HeightField hf = env_heightfield(a.hf, e);
   for (int p = lane; p < a.n_points; p += 64) {
     const float px = a.points[2 * p], py = a.points[2 * p + 1];
     const float x = bx + (cy * px - sy * py), y = by + (sy * px + cy * py);

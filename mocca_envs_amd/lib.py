@@ -23,6 +23,7 @@ DEBUG_WORDS = 20
 CAMERA_FLOATS = 16   # MOCCA_CAMERA_FLOATS
 RENDER_MAX_SIZE = 4096   # MOCCA_RENDER_MAX_SIZE
 SCAN_MAX_POINTS = 256   # MOCCA_SCAN_MAX_POINTS
+HF_MAX_FIELDS, HF_MAX_PEAKS = 1024, 256   # MOCCA_HF_MAX_FIELDS, MOCCA_HF_MAX_PEAKS
 RENDER_ID_NONE, RENDER_ID_GROUND, RENDER_ID_PLANK0, RENDER_ID_HEIGHTFIELD, RENDER_ID_TARGET, RENDER_ID_LINK0 = -1, 32, 33, 37, 38, 64   # MOCCA_RENDER_ID_*
 
 # every symbol include/mocca.h declares: (name, restype, argtypes)
@@ -61,6 +62,11 @@ SYMBOLS = {
     "mocca_episode_serial": (C.c_uint32, [_vp]),
     "mocca_set_trajectory": (_i, [_vp, _vp, _i, _d, _d]),
     "mocca_set_heightfield": (_i, [_vp, _vp, _i, _i, _d]),
+    "mocca_set_heightfield_bank": (_i, [_vp, _vp, _i, _i, _i, _d]),
+    "mocca_generate_heightfields": (_i, [_vp, _i, _i, _u64, _i, _d, _vp]),
+    "mocca_set_env_fields": (_i, [_vp, _vp, _i, _vp]),
+    "mocca_get_env_fields": (_i, [_vp, _vp, _vp]),
+    "mocca_get_heightfields": (_i, [_vp, _i, _i, _vp, _vp]),
     "mocca_get_link_frames": (_i, [_vp, _vp, _vp]),
     "mocca_render": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mocca_set_height_scan": (_i, [_vp, _vp, _i, _d, _d]),

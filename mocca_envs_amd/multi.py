@@ -166,6 +166,25 @@ class _Parts:
             return rgb
         return tuple(x for x, on in ((rgb, True), (dep, depth), (idt, ids)) if on)
 
+    # ---- the terrain bank lives in ONE handle's device memory ----
+    def _one_handle(self, what: str):
+        raise NotImplementedError(f"{what} needs one handle (one device, sub_batches=1)")
+
+    def set_heightfield_bank(self, *a, **k):
+        self._one_handle("set_heightfield_bank")
+
+    def generate_heightfields(self, *a, **k):
+        self._one_handle("generate_heightfields")
+
+    def set_env_fields(self, *a, **k):
+        self._one_handle("set_env_fields")
+
+    def env_fields(self):
+        self._one_handle("env_fields")
+
+    def height_fields(self, *a, **k):
+        self._one_handle("height_fields")
+
     def set_state(self, st) -> None:
         st = torch.as_tensor(st, dtype=torch.float32).reshape(self.n_envs, self.state_dim)
         for e, sl in zip(self.parts, self.slices):

@@ -193,11 +193,15 @@ class TorchVecEnv:
     every observation: `observation_space` grows by P, and reset() / step() / step(into=...) / capture_rollout return and fill rows
     [obs | scan] -- the step kernel's launch, then ONE more (include/mocca.h mocca_height_scan, which copies the observation into the wide row
     itself): no torch.cat, no copy or synchronise on the host.  Under auto-reset the scan, like the observation, belongs to the new episode's
-    first state."""
+    first state.
+    `terrain_bank=dict(n_fields=K, seed=S, n_peaks=256, gain=1.0, redraw_at_reset=True)` (planner ids): a bank of K random height fields of
+    the shipped shape (128 x 128 points, 4 per metre) generated on the device before the first reset (include/mocca.h
+    mocca_generate_heightfields), every env on one of them -- with `redraw_at_reset` another one in every episode; refresh_terrain(seed)
+    regenerates the bank in place.  Without it the envs stand on the shipped map, as ever."""
 
     def __init__(self, env_id: str, num_envs: int, seed: int = 0, device: Optional[int] = None, sub_batches: int = 1,
                  terminal_observation: bool = False, record_slots: int = 8, eager_done: bool = False, record_events: bool = True,
-                 height_scan: Optional[dict] = None, **kw):
+                 height_scan: Optional[dict] = None, terrain_bank: Optional[dict] = None, **kw):
         if height_scan is not None and terminal_observation:
             raise NotImplementedError("height_scan with terminal_observation=True: the scan runs after the step's launch, when an env that finished "
                                       "already holds its next episode's first state -- the terminal state is gone, so no scan can be appended to "
@@ -208,6 +212,19 @@ class TorchVecEnv:
                                  **({"device": device} if device is not None else {}), **kw)
         self.env_id, self.num_envs = env_id, int(num_envs)
         self.device = self.venv.device
+        self._terrain = None
+        if terrain_bank is not None:
+            if not hasattr(self.venv, "lib"):
+                raise NotImplementedError("terrain_bank needs one handle (one device, sub_batches=1)")
+            from . import host_logic as H
+            tb = dict(terrain_bank)
+            unknown = set(tb) - {"n_fields", "seed", "n_peaks", "gain", "redraw_at_reset"}
+            if unknown or "n_fields" not in tb:
+                raise ValueError(f"terrain_bank takes n_fields, seed, n_peaks, gain, redraw_at_reset (got {sorted(tb)})")
+            self._terrain = dict(n_peaks=int(tb.get("n_peaks", 256)), gain=float(tb.get("gain", 1.0)))
+            self.venv.set_heightfield_bank(int(tb["n_fields"]), H.HEIGHT_FIELD_SCALE, rows=H.HEIGHT_FIELD_SIZE[0], cols=H.HEIGHT_FIELD_SIZE[1])
+            self.refresh_terrain(int(tb.get("seed", 0)))
+            self.venv.set_env_fields(None, redraw_at_reset=bool(tb.get("redraw_at_reset", True)))
         self._scan, self._wide = 0, None
         if height_scan is not None:
             if not hasattr(self.venv, "lib"):
@@ -248,6 +265,13 @@ class TorchVecEnv:
         self._eager = bool(eager_done)
         from . import model as M
         self._stepper = self.venv.task_id == M.TASK_WALKER3D_STEPPER
+
+    def refresh_terrain(self, seed: int) -> None:
+        """Regenerate the whole terrain bank in place from `seed` (asynchronous, on the current stream, ordered against the steps around it):
+        the envs keep their field indices and walk on the new fields from their next step on."""
+        if self._terrain is None:
+            raise _lib.MoccaError("refresh_terrain needs terrain_bank=dict(...) at construction")
+        self.venv.generate_heightfields(int(seed), **self._terrain)
 
     def _attach_terminal(self, buf: torch.Tensor):
         """Attach `buf` [N, obs_dim] as the terminal-observation buffer of the handle(s) (each sub-batch its rows) and return the

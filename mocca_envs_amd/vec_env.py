@@ -166,6 +166,7 @@ class VecEnv:
             self.keep_terminal_obs(True)
         self.ep = None        # episode_stats(): Monitor / TimeLimitMask inside the launch
         self.height_field = None
+        self.terrain_bank = None   # set_heightfield_bank(): n_fields, rows, cols, scale
         if self.task_id == M.TASK_WALKER3D_PLANNER:
             from .terrain import load_height_field   # self.terrain.reload(data="height_field_map_0.npy"), env_locomotion.py:1015-1021
             self.set_heightfield(*load_height_field())
@@ -235,6 +236,90 @@ class VecEnv:
             raise ValueError("heights must be a [rows][cols] grid")
         _lib.check(self.lib.mocca_set_heightfield(self.h, hf.ctypes.data_as(C.c_void_p), hf.shape[0], hf.shape[1], float(scale)), self.h)
         self.height_field = (hf, float(scale))
+        self.terrain_bank = None
+
+    # ---- the planner envs' terrain bank (include/mocca.h mocca_set_heightfield_bank) ----
+    def _need_bank(self, who: str):
+        if getattr(self, "terrain_bank", None) is None:
+            raise _lib.MoccaError(f"{who} needs a terrain bank (set_heightfield_bank)")
+        return self.terrain_bank
+
+    def set_heightfield_bank(self, fields_or_count, scale: float, rows: Optional[int] = None, cols: Optional[int] = None) -> None:
+        """Attach a bank of height fields of one shape, every env on one of them (field 0 until set_env_fields says otherwise).
+        `fields_or_count`: heights [K][rows][cols], copied into the handle, or an int K with `rows` and `cols` for a bank of zeros
+        that generate_heightfields() fills on the device; K = 1 .. 1024.  None detaches.  May synchronise."""
+        if fields_or_count is None:
+            _lib.check(self.lib.mocca_set_heightfield_bank(self.h, None, 0, 0, 0, 0.0), self.h)
+            self.terrain_bank = self.height_field = None
+            return
+        if isinstance(fields_or_count, (int, np.integer)):
+            if rows is None or cols is None:
+                raise ValueError("a bank to be generated into needs rows and cols")
+            k, rows, cols, ptr = int(fields_or_count), int(rows), int(cols), None
+        else:
+            hf = np.ascontiguousarray(fields_or_count, np.float32)
+            if hf.ndim != 3:
+                raise ValueError("fields must be [K][rows][cols] grids")
+            if (rows is not None and int(rows) != hf.shape[1]) or (cols is not None and int(cols) != hf.shape[2]):
+                raise ValueError("rows / cols differ from the shape of the fields")
+            k, rows, cols = hf.shape
+            ptr = hf.ctypes.data_as(C.c_void_p)
+        if not 1 <= k <= _lib.HF_MAX_FIELDS:
+            raise ValueError(f"a terrain bank holds 1 .. {_lib.HF_MAX_FIELDS} fields")
+        _lib.check(self.lib.mocca_set_heightfield_bank(self.h, ptr, k, rows, cols, float(scale)), self.h)
+        self.terrain_bank = dict(n_fields=k, rows=rows, cols=cols, scale=float(scale))
+        self.height_field = None       # (the fields live on the device: height_fields() reads them back)
+
+    def generate_heightfields(self, seed: int, first: int = 0, count: Optional[int] = None, n_peaks: int = 256, gain: float = 1.0) -> None:
+        """Fill fields first .. first + count - 1 (default: to the end of the bank) with random terrain on the device: the reference's
+        generator (`HeightField.reload(data=None)`), `n_peaks` peaks, the finished field times `gain`.  Asynchronous; nothing synchronises."""
+        bank = self._need_bank("generate_heightfields")
+        first = int(first)
+        count = bank["n_fields"] - first if count is None else int(count)
+        if not 1 <= int(n_peaks) <= _lib.HF_MAX_PEAKS:
+            raise ValueError(f"n_peaks must be 1 .. {_lib.HF_MAX_PEAKS}")
+        if not (np.isfinite(gain) and gain > 0):
+            raise ValueError("gain must be finite and > 0")
+        if first < 0 or count < 1 or first + count > bank["n_fields"]:
+            raise ValueError(f"fields {first} .. {first + count - 1} are not inside the bank of {bank['n_fields']}")
+        self._in()
+        _lib.check(self.lib.mocca_generate_heightfields(self.h, first, count, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_peaks), float(gain), self._stream()), self.h)
+        self._out()
+
+    def set_env_fields(self, ids=None, redraw_at_reset: bool = False) -> None:
+        """Put env e on field ids[e] of the bank (None: every env on field 0).  `redraw_at_reset`: every reset, auto-reset included, draws
+        the env's field anew (keyed by seed, episode and global env id).  May synchronise: the ids are checked on the host."""
+        self._need_bank("set_env_fields")
+        ev = None
+        if ids is not None:
+            ev = torch.as_tensor(ids, dtype=torch.int32).reshape(-1).to(self.device).contiguous()
+            if ev.numel() != self.n_envs:
+                raise ValueError("set_env_fields: one field index per env")
+        self._in()
+        _lib.check(self.lib.mocca_set_env_fields(self.h, None if ev is None else C.c_void_p(ev.data_ptr()), 1 if redraw_at_reset else 0, self._stream()), self.h)
+        self._out()
+
+    def env_fields(self) -> torch.Tensor:
+        """The field every env stands on: int32 [N] on the device."""
+        self._need_bank("env_fields")
+        out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        self._in()
+        _lib.check(self.lib.mocca_get_env_fields(self.h, C.c_void_p(out.data_ptr()), self._stream()), self.h)
+        self._out()
+        return out
+
+    def height_fields(self, first: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """Fields first .. first + count - 1 of the bank as they are on the device: float32 [count][rows][cols]."""
+        bank = self._need_bank("height_fields")
+        first = int(first)
+        count = bank["n_fields"] - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > bank["n_fields"]:
+            raise ValueError(f"fields {first} .. {first + count - 1} are not inside the bank of {bank['n_fields']}")
+        out = torch.empty(count, bank["rows"], bank["cols"], dtype=torch.float32, device=self.device)
+        self._in()
+        _lib.check(self.lib.mocca_get_heightfields(self.h, first, count, C.c_void_p(out.data_ptr()), self._stream()), self.h)
+        self._out()
+        return out
 
     # ---- the planner envs' base controller (env_locomotion.py:1029-1040, :1091-1101) ----
     def set_base_controller(self, ctrl, action_scale: float = 2.0):

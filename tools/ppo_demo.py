@@ -90,6 +90,10 @@ def main():
     ap.add_argument("--mirror-dup", action="store_true", help="SymmetricRL's duplicated tuples: train on every row and its mirror image; not with --symmetric or --mirror-loss")
     ap.add_argument("--base-controller", default=None, metavar="FILE", help="the planner ids' frozen base controller: a BaseController.save_npz file or this script's policy file of a Stepper run")
     ap.add_argument("--height-scan", default=None, metavar="NX,NY", help="append a scan_grid of NX x NY terrain heights (0 .. 2 m ahead, -0.5 .. 0.5 m sideways) to the observation row")
+    ap.add_argument("--terrain-bank", type=int, default=0, metavar="K", help="planner ids: train on a bank of K random height fields generated on the device, another one in every episode (0: the shipped map)")
+    ap.add_argument("--terrain-seed", type=int, default=0, metavar="S", help="seed of the terrain bank")
+    ap.add_argument("--terrain-refresh", type=int, default=0, metavar="M", help="regenerate the bank every M iterations with seed S + iteration (0: never)")
+    ap.add_argument("--terrain-gain", type=float, default=1.0, metavar="G", help="the generated fields are multiplied by G: the difficulty knob")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args()
     if args.device_grad and not args.device_returns:
@@ -113,6 +117,10 @@ def main():
         ap.error("--base-controller is required for the planner ids, and only for them")
     if planner and (args.symmetric or args.mirror_loss is not None or args.mirror_dup):
         ap.error("the planner ids publish no mirror indices for plans: no --symmetric / --mirror-loss / --mirror-dup")
+    if args.terrain_bank and not planner:
+        ap.error("--terrain-bank is for the planner ids: the other tasks have no height field")
+    if args.terrain_refresh and not args.terrain_bank:
+        ap.error("--terrain-refresh requires --terrain-bank")
     import torch
     import torch.nn as nn
     from mocca_envs_amd.trainer_api import make_vec_envs
@@ -125,6 +133,8 @@ def main():
         from mocca_envs_amd.perception import scan_grid
         nx, ny = (int(v) for v in args.height_scan.split(","))
         extra["height_scan"] = dict(points=scan_grid((0.0, 2.0), (-0.5, 0.5), nx, ny))
+    if args.terrain_bank:
+        extra["terrain_bank"] = dict(n_fields=args.terrain_bank, seed=args.terrain_seed, gain=args.terrain_gain, redraw_at_reset=True)
     envs = make_vec_envs(args.env_id, seed=args.seed, num_processes=args.envs, record_events=False, **extra)
     dev, N, T = envs.device, args.envs, args.steps
     od, ad = envs.observation_space.shape[0], envs.action_space.shape[0]
@@ -261,6 +271,8 @@ def main():
     log = open(args.out + ".jsonl", "w")
     t_start, total_steps, last_tot = time.perf_counter(), 0, torch.zeros(4, device=dev)
     for it in range(args.iters):
+        if args.terrain_refresh and it and it % args.terrain_refresh == 0:
+            envs.refresh_terrain(args.terrain_seed + it)     # on the stream of the steps around it: no synchronise
         # ---- collect
         if args.device_returns:
             with torch.no_grad():
