@@ -171,13 +171,15 @@ struct mocca_ctx {
   int pol_tail_row = 0;              // pol_repack's row of the flags; the rows of mean and inv_std follow it
   std::vector<int32_t> pol_table;    // host copy of d_pol_layers (offsets into the image)
   int pol_wt_off[mocca_ppo::PPO_MAX_TABLE] = {};   // the layers' transposed copies in the image (mocca_ppo.h), -1: none
-  DevBuf<int32_t> d_pol_sym_perm;    // mocca_set_policy_symmetry: in_perm [in_dim] then act_perm [act_dim]; pol.in_perm / act_perm point into it
-  DevBuf<float> d_pol_sym_sign;      // in_sign [in_dim] then act_sign [act_dim]
-  DevBuf<int32_t> d_pol_ml_perm;     // mocca_set_policy_mirror_loss: the same two layouts, read by mocca_ppo_grad_mirror ALONE (pol stays plain)
-  DevBuf<float> d_pol_ml_sign;
-  double pol_ml_coef = 0.0;          // mirror_coef; meaningful while d_pol_ml_perm is set
-  DevBuf<int32_t> d_pol_dup_perm;    // mocca_set_policy_mirror_dup: the same two layouts, read by mocca_ppo_grad_dup ALONE (pol stays plain)
-  DevBuf<float> d_pol_dup_sign;
+  // the policy's ONE mirror attachment (set_policy_mirror): the setters refuse a second kind, so the tables are held once
+  struct {
+    mocca_ppo::PpoMode method = mocca_ppo::PPO_PLAIN;   // PPO_PLAIN: nothing attached.  PPO_SYM (mocca_set_policy_symmetry): pol.in_perm and its
+                                     // kin point into the tables; PPO_MIRROR (.._mirror_loss) and PPO_DUP (.._mirror_dup): mocca_ppo_grad_mirror /
+                                     // _dup ALONE read them, pol stays plain
+    DevBuf<int32_t> perm;            // in_perm [in_dim] then act_perm [act_dim]
+    DevBuf<float> sign;              // in_sign [in_dim] then act_sign [act_dim]
+    double coef = 0.0;               // PPO_MIRROR: mirror_coef
+  } pol_mirror;
   // scratch of mocca_gae / mocca_obs_stats (mocca_rollout.h), owned by the handle, grown on demand
   DevBuf<double> d_gae_part;         // [blocks][2]
   size_t gae_part_cap = 0;           // doubles
@@ -1223,22 +1225,12 @@ int mocca_height_scan(mocca_handle h, float* out_dev, int row_stride, const floa
   return MOCCA_OK;
 }
 
-// detach the mirror tables of the policy (mocca_set_policy_symmetry); the caller has made sure that no launch in flight reads them
-static void drop_policy_symmetry(mocca_handle h) {
-  h->d_pol_sym_perm.reset(); h->d_pol_sym_sign.reset();
+// detach the policy's mirror attachment, whichever kind it is; the caller has made sure that no launch in flight reads the tables
+static void drop_policy_mirror(mocca_handle h) {
+  h->pol_mirror.perm.reset(); h->pol_mirror.sign.reset();
+  h->pol_mirror.method = mocca_ppo::PPO_PLAIN; h->pol_mirror.coef = 0.0;
   h->pol.in_perm = h->pol.act_perm = nullptr;
   h->pol.in_sign = h->pol.act_sign = nullptr;
-}
-
-// detach the mirror loss (mocca_set_policy_mirror_loss); as above
-static void drop_policy_mirror_loss(mocca_handle h) {
-  h->d_pol_ml_perm.reset(); h->d_pol_ml_sign.reset();
-  h->pol_ml_coef = 0.0;
-}
-
-// detach the duplicated-rows tables (mocca_set_policy_mirror_dup); as above
-static void drop_policy_mirror_dup(mocca_handle h) {
-  h->d_pol_dup_perm.reset(); h->d_pol_dup_sign.reset();
 }
 
 int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) try {
@@ -1248,9 +1240,7 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
   if (!layers_host) {   // detach
     if (int rc = commit_ready(h, "mocca_set_policy")) return rc;
     h->d_pol_image.reset(); h->d_pol_layers.reset(); h->pol_filled = false;
-    drop_policy_symmetry(h);
-    drop_policy_mirror_loss(h);
-    drop_policy_mirror_dup(h);
+    drop_policy_mirror(h);
     return MOCCA_OK;
   }
   auto bad = [&](const std::string& what) { h->err = "mocca_set_policy: " + what; return MOCCA_E_ARG; };
@@ -1269,9 +1259,7 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
   h->pol_repack = im.rp; h->pol_n_base = im.n_src; h->pol_filled = false;
   h->pol_tail_row = im.tail_row; h->pol_table.swap(im.table);
   std::memcpy(h->pol_wt_off, im.wt_off, sizeof(im.wt_off));
-  drop_policy_symmetry(h);   // the shapes may have changed
-  drop_policy_mirror_loss(h);
-  drop_policy_mirror_dup(h);
+  drop_policy_mirror(h);   // the shapes may have changed
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy"); }
 
@@ -1310,85 +1298,62 @@ static std::string upload_mirror_tables(mocca_handle h, const int32_t* in_perm_h
   return "";
 }
 
-int mocca_set_policy_symmetry(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
-                              const float* act_sign_host) try {
+// mocca_set_policy_symmetry (PPO_SYM), mocca_set_policy_mirror_loss (PPO_MIRROR) and mocca_set_policy_mirror_dup (PPO_DUP): attach `method`'s
+// tables, replace them, or (in_perm_host NULL) detach them.  One kind at a time: a second kind is refused, and detaching a kind that is not the
+// attached one leaves the attached one alone.  A table error or a failed upload leaves the handle as it was.
+static int set_policy_mirror(mocca_handle h, const char* name, mocca_ppo::PpoMode method, const int32_t* in_perm_host, const float* in_sign_host,
+                             const int32_t* act_perm_host, const float* act_sign_host, double mirror_coef) try {
+  using namespace mocca_ppo;
   if (!h) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
-  auto bad = [&](const std::string& what) { h->err = "mocca_set_policy_symmetry: " + what; return MOCCA_E_ARG; };
+  auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
   if (!h->d_pol_image) return bad("needs a policy (mocca_set_policy)");
   if (!in_perm_host) {   // detach
-    if (int rc = commit_ready(h, "mocca_set_policy_symmetry")) return rc;
-    drop_policy_symmetry(h);
+    if (int rc = commit_ready(h, name)) return rc;
+    if (h->pol_mirror.method == method) drop_policy_mirror(h);
     return MOCCA_OK;
   }
-  if (h->d_pol_ml_perm)
-    return bad("a mirror loss is attached (mocca_set_policy_mirror_loss): a symmetric network has no mirror loss, detach it first");
-  if (h->d_pol_dup_perm)
-    return bad("duplicated rows are attached (mocca_set_policy_mirror_dup): they train the plain policy, detach them first");
-  DevBuf<int32_t> d_perm;
-  DevBuf<float> d_sign;
-  hipError_t e = hipSuccess;
-  const std::string wrong = upload_mirror_tables(h, in_perm_host, in_sign_host, act_perm_host, act_sign_host, d_perm, d_sign, &e);
-  if (!wrong.empty()) return bad(wrong);
-  if (int rc = commit_ready(h, "mocca_set_policy_symmetry", e)) return rc;
-  const int in_dim = h->pol.in_dim;
-  h->d_pol_sym_perm.swap(d_perm); h->d_pol_sym_sign.swap(d_sign);
-  h->pol.in_perm = h->d_pol_sym_perm; h->pol.act_perm = h->d_pol_sym_perm.get() + in_dim;
-  h->pol.in_sign = h->d_pol_sym_sign; h->pol.act_sign = h->d_pol_sym_sign.get() + in_dim;
-  return MOCCA_OK;
-} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy_symmetry"); }
-
-int mocca_set_policy_mirror_loss(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
-                                 const float* act_sign_host, double mirror_coef) try {
-  if (!h) return MOCCA_E_ARG;
-  DeviceGuard guard(h->device);
-  auto bad = [&](const std::string& what) { h->err = "mocca_set_policy_mirror_loss: " + what; return MOCCA_E_ARG; };
-  if (!h->d_pol_image) return bad("needs a policy (mocca_set_policy)");
-  if (!in_perm_host) {   // detach
-    if (int rc = commit_ready(h, "mocca_set_policy_mirror_loss")) return rc;
-    drop_policy_mirror_loss(h);
-    return MOCCA_OK;
-  }
-  if (h->pol.in_perm)
-    return bad("the policy is mirror-symmetric (mocca_set_policy_symmetry): its mirror loss is zero by construction, detach the symmetry first");
-  if (h->d_pol_dup_perm)
-    return bad("duplicated rows are attached (mocca_set_policy_mirror_dup): one symmetry method at a time, detach them first");
+  static const char* const refusal[4][4] = {   // [method][the attached kind]
+      {},
+      {nullptr, nullptr, "a mirror loss is attached (mocca_set_policy_mirror_loss): a symmetric network has no mirror loss, detach it first",
+       "duplicated rows are attached (mocca_set_policy_mirror_dup): they train the plain policy, detach them first"},
+      {nullptr, "the policy is mirror-symmetric (mocca_set_policy_symmetry): its mirror loss is zero by construction, detach the symmetry first", nullptr,
+       "duplicated rows are attached (mocca_set_policy_mirror_dup): one symmetry method at a time, detach them first"},
+      {nullptr, "the policy is mirror-symmetric (mocca_set_policy_symmetry): a row and its mirror image give it one gradient, detach the symmetry first",
+       "a mirror loss is attached (mocca_set_policy_mirror_loss): one symmetry method at a time, detach it first", nullptr}};
+  static_assert(PPO_PLAIN == 0 && PPO_SYM == 1 && PPO_MIRROR == 2 && PPO_DUP == 3, "refusal[][]'s rows and columns");
+  if (const char* why = refusal[method][h->pol_mirror.method]) return bad(why);
   if (!std::isfinite(mirror_coef) || mirror_coef < 0.0) return bad("mirror_coef must be finite and not negative");
   DevBuf<int32_t> d_perm;
   DevBuf<float> d_sign;
   hipError_t e = hipSuccess;
   const std::string wrong = upload_mirror_tables(h, in_perm_host, in_sign_host, act_perm_host, act_sign_host, d_perm, d_sign, &e);
   if (!wrong.empty()) return bad(wrong);
-  if (int rc = commit_ready(h, "mocca_set_policy_mirror_loss", e)) return rc;
-  h->d_pol_ml_perm.swap(d_perm); h->d_pol_ml_sign.swap(d_sign);
-  h->pol_ml_coef = mirror_coef;
+  if (int rc = commit_ready(h, name, e)) return rc;
+  h->pol_mirror.perm.swap(d_perm); h->pol_mirror.sign.swap(d_sign);
+  h->pol_mirror.method = method; h->pol_mirror.coef = mirror_coef;
+  if (method == PPO_SYM) {   // the policy kernel's symmetric instance runs from here on (launch_policy)
+    const int in_dim = h->pol.in_dim;
+    h->pol.in_perm = h->pol_mirror.perm; h->pol.act_perm = h->pol_mirror.perm.get() + in_dim;
+    h->pol.in_sign = h->pol_mirror.sign; h->pol.act_sign = h->pol_mirror.sign.get() + in_dim;
+  }
   return MOCCA_OK;
-} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy_mirror_loss"); }
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, name); }
+
+int mocca_set_policy_symmetry(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
+                              const float* act_sign_host) {
+  return set_policy_mirror(h, "mocca_set_policy_symmetry", mocca_ppo::PPO_SYM, in_perm_host, in_sign_host, act_perm_host, act_sign_host, 0.0);
+}
+
+int mocca_set_policy_mirror_loss(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
+                                 const float* act_sign_host, double mirror_coef) {
+  return set_policy_mirror(h, "mocca_set_policy_mirror_loss", mocca_ppo::PPO_MIRROR, in_perm_host, in_sign_host, act_perm_host, act_sign_host, mirror_coef);
+}
 
 int mocca_set_policy_mirror_dup(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
-                                const float* act_sign_host) try {
-  if (!h) return MOCCA_E_ARG;
-  DeviceGuard guard(h->device);
-  auto bad = [&](const std::string& what) { h->err = "mocca_set_policy_mirror_dup: " + what; return MOCCA_E_ARG; };
-  if (!h->d_pol_image) return bad("needs a policy (mocca_set_policy)");
-  if (!in_perm_host) {   // detach
-    if (int rc = commit_ready(h, "mocca_set_policy_mirror_dup")) return rc;
-    drop_policy_mirror_dup(h);
-    return MOCCA_OK;
-  }
-  if (h->pol.in_perm)
-    return bad("the policy is mirror-symmetric (mocca_set_policy_symmetry): a row and its mirror image give it one gradient, detach the symmetry first");
-  if (h->d_pol_ml_perm)
-    return bad("a mirror loss is attached (mocca_set_policy_mirror_loss): one symmetry method at a time, detach it first");
-  DevBuf<int32_t> d_perm;
-  DevBuf<float> d_sign;
-  hipError_t e = hipSuccess;
-  const std::string wrong = upload_mirror_tables(h, in_perm_host, in_sign_host, act_perm_host, act_sign_host, d_perm, d_sign, &e);
-  if (!wrong.empty()) return bad(wrong);
-  if (int rc = commit_ready(h, "mocca_set_policy_mirror_dup", e)) return rc;
-  h->d_pol_dup_perm.swap(d_perm); h->d_pol_dup_sign.swap(d_sign);
-  return MOCCA_OK;
-} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy_mirror_dup"); }
+                                const float* act_sign_host) {
+  return set_policy_mirror(h, "mocca_set_policy_mirror_dup", mocca_ppo::PPO_DUP, in_perm_host, in_sign_host, act_perm_host, act_sign_host, 0.0);
+}
 
 // what n_floats of a flat parameter tensor must be (mocca_update_policy, mocca_adam_step): -> "" or what is wrong
 static std::string check_n_floats(mocca_handle h, size_t n_floats) {
@@ -1552,10 +1517,8 @@ int mocca_obs_stats(mocca_handle h, const float* rows_dev, int64_t n_rows, int r
   return MOCCA_OK;
 }
 
-// what the handle's attachments make mocca_ppo_update differentiate: duplicated rows, the mirror loss, the symmetric network, or the plain policy
-static mocca_ppo::PpoMode ppo_mode(mocca_handle h) {
-  return h->d_pol_dup_perm ? mocca_ppo::PPO_DUP : h->d_pol_ml_perm ? mocca_ppo::PPO_MIRROR : h->pol.in_perm ? mocca_ppo::PPO_SYM : mocca_ppo::PPO_PLAIN;
-}
+// what the handle's attachment makes mocca_ppo_update differentiate: duplicated rows, the mirror loss, the symmetric network, or the plain policy
+static mocca_ppo::PpoMode ppo_mode(mocca_handle h) { return h->pol_mirror.method; }
 
 // mocca_ppo_grad (PPO_PLAIN), mocca_ppo_grad_sym (PPO_SYM), mocca_ppo_grad_mirror (PPO_MIRROR) and mocca_ppo_grad_dup (PPO_DUP): one argument
 // list, one scratch, the same four launches; the last three share the two-column scratch layout (mocca_ppo.h)
@@ -1569,17 +1532,17 @@ static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, c
   auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
   if (!h->d_pol_image || !h->pol_filled) return bad("needs a policy (mocca_set_policy, then mocca_update_policy)");
   const bool sym = mode != PPO_PLAIN;   // twice the columns
-  if (mode != PPO_DUP && h->d_pol_dup_perm)
-    return bad("duplicated rows are attached: the gradient of PPO's loss over the rows and their mirror images is mocca_ppo_grad_dup (or detach them: mocca_set_policy_mirror_dup)");
-  if (mode == PPO_DUP && !h->d_pol_dup_perm)
-    return bad("needs duplicated rows attached (mocca_set_policy_mirror_dup); the plain loss's gradient is mocca_ppo_grad");
-  if (mode != PPO_MIRROR && h->d_pol_ml_perm)
-    return bad("a mirror loss is attached: the gradient of PPO's loss with the mirror term is mocca_ppo_grad_mirror (or detach it: mocca_set_policy_mirror_loss)");
-  if (mode == PPO_MIRROR && !h->d_pol_ml_perm)
-    return bad("needs a mirror loss attached (mocca_set_policy_mirror_loss); the plain loss's gradient is mocca_ppo_grad");
-  if (mode == PPO_PLAIN && h->pol.in_perm)
-    return bad("the policy has mirror tables attached: the symmetric policy's gradient is mocca_ppo_grad_sym (or detach the tables: mocca_set_policy_symmetry)");
-  if (mode == PPO_SYM && !h->pol.in_perm) return bad("needs a policy with mirror tables attached (mocca_set_policy_symmetry); the plain policy's gradient is mocca_ppo_grad");
+  if (const PpoMode attached = ppo_mode(h); mode != attached) {   // the first of these that holds names the entry point to call instead
+    if (attached == PPO_DUP)
+      return bad("duplicated rows are attached: the gradient of PPO's loss over the rows and their mirror images is mocca_ppo_grad_dup (or detach them: mocca_set_policy_mirror_dup)");
+    if (mode == PPO_DUP) return bad("needs duplicated rows attached (mocca_set_policy_mirror_dup); the plain loss's gradient is mocca_ppo_grad");
+    if (attached == PPO_MIRROR)
+      return bad("a mirror loss is attached: the gradient of PPO's loss with the mirror term is mocca_ppo_grad_mirror (or detach it: mocca_set_policy_mirror_loss)");
+    if (mode == PPO_MIRROR) return bad("needs a mirror loss attached (mocca_set_policy_mirror_loss); the plain loss's gradient is mocca_ppo_grad");
+    if (mode == PPO_PLAIN)
+      return bad("the policy has mirror tables attached: the symmetric policy's gradient is mocca_ppo_grad_sym (or detach the tables: mocca_set_policy_symmetry)");
+    return bad("needs a policy with mirror tables attached (mocca_set_policy_symmetry); the plain policy's gradient is mocca_ppo_grad");
+  }
   if (!obs_dev || !action_dev || !old_logp_dev || !adv_dev || !returns_dev || !grad_dev)
     return bad("obs_dev, action_dev, old_logp_dev, adv_dev, returns_dev and grad_dev must not be NULL");
   if (value_clip && !old_value_dev) return bad("value_clip needs old_value_dev");
@@ -1597,15 +1560,10 @@ static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, c
   a.in_dim = p.in_dim; a.in_pad = p.in_pad; a.act_dim = p.act_dim; a.norm_clip = p.clip;
   std::memcpy(a.wt_off, h->pol_wt_off, sizeof(a.wt_off));
   a.mode = mode;
-  if (mode == PPO_SYM) { a.in_perm = p.in_perm; a.in_sign = p.in_sign; a.act_perm = p.act_perm; a.act_sign = p.act_sign; }
-  if (mode == PPO_MIRROR) {
-    a.in_perm = h->d_pol_ml_perm; a.act_perm = h->d_pol_ml_perm.get() + p.in_dim;
-    a.in_sign = h->d_pol_ml_sign; a.act_sign = h->d_pol_ml_sign.get() + p.in_dim;
-    a.mirror_k2 = (float)(2.0 * h->pol_ml_coef);
-  }
-  if (mode == PPO_DUP) {
-    a.in_perm = h->d_pol_dup_perm; a.act_perm = h->d_pol_dup_perm.get() + p.in_dim;
-    a.in_sign = h->d_pol_dup_sign; a.act_sign = h->d_pol_dup_sign.get() + p.in_dim;
+  if (mode != PPO_PLAIN) {
+    a.in_perm = h->pol_mirror.perm; a.act_perm = h->pol_mirror.perm.get() + p.in_dim;
+    a.in_sign = h->pol_mirror.sign; a.act_sign = h->pol_mirror.sign.get() + p.in_dim;
+    a.mirror_k2 = (float)(2.0 * h->pol_mirror.coef);
   }
   a.obs = obs_dev; a.obs_stride = obs_stride; a.action = action_dev; a.old_logp = old_logp_dev; a.adv = adv_dev; a.returns = returns_dev;
   a.old_value = old_value_dev; a.idx = idx_dev;

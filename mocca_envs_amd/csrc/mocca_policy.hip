@@ -4,9 +4,9 @@
 //
 // Arithmetic: the controller kernel's contract (mocca_controller.hip).  f32 in, f32 accumulate on the matrix cores
 // (v_mfma_f32_16x16x4_f32); an output is the sum of FOUR partial sums, one accumulator per MFMA j of a 16-wide k-group (the k with
-// k mod 4 = j), each in ascending k, added as (p0 + p1) + (p2 + p3) ahead of the bias and the activation.  The layer loop below is that
-// kernel's, restated over a wider LDS row (the input may be [obs | scan], up to 336 floats): mocca_controller.hip itself is left as it is
-// (profiles/kernel_resources_policy.md).
+// k mod 4 = j), each in ascending k, added as (p0 + p1) + (p2 + p3) ahead of the bias and the activation.  The layer loop is the one that
+// kernel and mocca_ppo.hip run too (mocca_mlp.h: mfma_layer), here over a wider LDS row than the controller's (the input may be
+// [obs | scan], up to 336 floats).
 //
 // A workgroup of four waves owns POL_TILE envs of ONE net (blockIdx.y: 0 actor, 1 critic).  The activations of the tile stay in LDS from the
 // normalised input to the head, X[env][feature], two buffers; the weights stream from L2 in fragment order.  The head's outputs go to LDS
@@ -21,31 +21,20 @@
 // stage's lane folds the two columns of its env into one mean (or value).
 #include <hip/hip_runtime.h>
 
+#include "mocca_mlp.h"
 #include "mocca_philox.h"
 #include "mocca_policy.h"
 
 namespace mocca_pol {
 
 using namespace mocca_ctrl;   // CL_*, CTRL_ACT_*
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace mocca_mlp;   // f32x4, mfma_layer, activate, normalise
 
 constexpr int LDS_STRIDE = POL_MAX_IN + 4;   // floats per env row: 16-byte aligned rows, rows 0..7 start on different bank groups (340 = 20 mod 32)
-constexpr int NP = 4;                        // partial sums per output
-constexpr int NT = 4;                        // output tiles per wave: 16 tiles of 16 rows (width 256) over 4 waves
 constexpr int TILE = POL_TILE;          // MFMA columns of a workgroup: 16 envs, or (SYM) POL_SYM_TILE envs and their mirror images
 static_assert(TILE == 16, "one 16-env MFMA sub-tile per workgroup; the noise stage deals 16 envs x 16 Philox blocks to 256 lanes");
 static_assert(2 * POL_SYM_TILE == TILE, "the symmetric instance: column c the env as given, column POL_SYM_TILE + c its mirror image");
 static_assert(POL_MAX_WIDTH <= POL_MAX_IN && POL_MAX_ACTION <= 32, "LDS rows hold the widest layer; 16 Philox blocks give 32 normals");
-
-__device__ __forceinline__ float activate(float x, int act) {
-  switch (act) {
-    case CTRL_ACT_RELU: return fmaxf(x, 0.0f);
-    case CTRL_ACT_TANH: return tanhf(x);
-    case CTRL_ACT_SOFTSIGN: return x / (1.0f + fabsf(x));
-    default: return x;
-  }
-}
 
 template <bool SYM>
 __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
@@ -54,7 +43,7 @@ __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
   __shared__ float Z[ENVS * POL_MAX_ACTION];   // the tile's noise, Z[env][j]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int env0 = blockIdx.x * ENVS, net = blockIdx.y;
-  const int col = lane & 15, quad = lane >> 4;
+  const int col = lane & 15;
 
   // input: the first in_dim floats of the env's row, normalised, zeros up to in_pad; rows past the batch are zeros (nothing of them is stored).
   // SYM: column e >= ENVS is the mirror image of env e - ENVS, formed from the RAW row (the statistics are not symmetric) and normalised by k
@@ -67,7 +56,7 @@ __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
       if (env < a.n_envs && k < a.in_dim) {
         if (SYM && e >= ENVS) v = a.in[(size_t)env * a.in_stride + a.in_perm[k]] * a.in_sign[k];
         else v = a.in[(size_t)env * a.in_stride + k];
-        if (norm) v = fminf(fmaxf((v - mu[k]) * is[k], -a.clip), a.clip);
+        if (norm) v = normalise(v, mu[k], is[k], a.clip);
       }
       X[0][e * LDS_STRIDE + k] = v;
     }
@@ -92,66 +81,17 @@ __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
 #pragma unroll 1
   for (int li = 0; li < count; ++li) {
     const int32_t* lr = a.layers + (size_t)(first + li) * CTRL_LAYER_WORDS;
-    const int nkg = lr[CL_IN_PAD] >> 4, n_ot = lr[CL_OUT_PAD] >> 4, act = lr[CL_ACT];
-    const f32x4* W = (const f32x4*)(a.params + lr[CL_W_OFF]);
+    const int act = lr[CL_ACT];
     const float* B = a.params + lr[CL_B_OFF];
-    const int nt_w = wave < n_ot ? (n_ot - wave + 3) >> 2 : 0;   // output tiles of this wave (wave-uniform)
-    const float* Xin = X[cur];
     float* Xout = X[cur ^ 1];
-
-    f32x4 acc[NT][NP];   // [..][j]: the partial sum fed by MFMA j of every k-group
+    // epilogue: bias, activation, then LDS (the next layer, or the head stage)
+    mfma_layer<LDS_STRIDE>((const f32x4*)(a.params + lr[CL_W_OFF]), lr[CL_IN_PAD] >> 4, lr[CL_OUT_PAD] >> 4, X[cur], wave, lane, [&](int o, f32x4 sum) {
+      const f32x4 bias = *(const f32x4*)(B + o);
+      f32x4 y;
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int j = 0; j < NP; ++j) acc[t][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-
-    if (nt_w > 0) {
-      // weight fragments of this wave's tiles at k-group kg (tiles past the wave's last re-read that one: loaded, never multiplied)
-      const f32x4* wp[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int ot = wave + 4 * (t < nt_w ? t : nt_w - 1);
-        wp[t] = W + (size_t)ot * nkg * 64 + lane;
-      }
-      // the weights come from L2: the fragments of k-groups kg + 1 and kg + 2 are in flight while kg multiplies
-      f32x4 w0[NT], w1[NT], w2[NT];
-      auto load = [&](f32x4 (&w)[NT], int kg) {
-        const int kc = kg < nkg ? kg : nkg - 1;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) w[t] = wp[t][(size_t)kc * 64];
-      };
-      auto multiply = [&](const f32x4 (&w)[NT], int kg) {
-        const f32x4 b = *(const f32x4*)&Xin[col * LDS_STRIDE + kg * 16 + quad * 4];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          if (t < nt_w) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][j], b[j], acc[t][j], 0, 0, 0);
-          }
-      };
-      // three k-groups per trip: the three fragment sets rotate by name, not by register moves
-      load(w0, 0); load(w1, 1);
-#pragma unroll 1
-      for (int kg = 0; kg < nkg; kg += 3) {
-        load(w2, kg + 2); multiply(w0, kg);
-        if (kg + 1 >= nkg) break;
-        load(w0, kg + 3); multiply(w1, kg + 1);
-        if (kg + 2 >= nkg) break;
-        load(w1, kg + 4); multiply(w2, kg + 2);
-      }
-      // epilogue: lane holds rows 16 ot + 4 quad + 0..3 of env column `col`; bias, activation, then LDS (the next layer, or the head stage)
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        if (t < nt_w) {
-          const int o = (wave + 4 * t) * 16 + quad * 4;
-          const f32x4 bias = *(const f32x4*)(B + o);
-          const f32x4 sum = (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]);
-          f32x4 y;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) y[r] = activate(sum[r] + bias[r], act);
-          *(f32x4*)&Xout[col * LDS_STRIDE + o] = y;
-        }
-    }
+      for (int r = 0; r < 4; ++r) y[r] = activate(sum[r] + bias[r], act);
+      *(f32x4*)&Xout[col * LDS_STRIDE + o] = y;
+    });
     __syncthreads();
     cur ^= 1;
   }

@@ -3,11 +3,12 @@
 // rows (mocca_ppo_grad_dup), on the device.  What each launch does, the scratch and the transposed weight copy: mocca_ppo.h.
 // The loss and the per-row formulas: include/mocca.h.
 //
-// Arithmetic: the policy kernel's (mocca_policy.hip).  The layer loop below is that kernel's loop, copied -- mocca_policy.hip's kernel is left
-// as it is -- with the epilogue as a parameter: the forward adds the bias, activates and also stores the output to scratch; the backward
-// (the same loop over the transposed copy) stores dA to LDS only.
+// Arithmetic: the policy kernel's (mocca_policy.hip), on the layer loop both share (mocca_mlp.h: mfma_layer, the epilogue a parameter): the
+// forward adds the bias, activates and also stores the output to scratch; the backward (the same loop over the transposed copy) stores dA
+// to LDS only.  The forward's activation is this file's own, activate_once: tanh rounded once, where the policy kernel's is tanhf.
 #include <hip/hip_runtime.h>
 
+#include "mocca_mlp.h"
 #include "mocca_ppo.h"
 
 // every f32 / f64 operation written below is that IEEE operation: a * b + c stays two roundings (include/mocca.h names each of them)
@@ -17,15 +18,17 @@ namespace mocca_ppo {
 
 using namespace mocca_ctrl;   // CL_*, CTRL_ACT_*
 using namespace mocca_pol;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using mocca_mlp::f32x4;
+using mocca_mlp::mfma_layer;
+using mocca_mlp::NP;
 
 constexpr int LDS_STRIDE = POL_MAX_IN + 4;   // the policy kernel's LDS row
-constexpr int NP = 4, NT = 4, TILE = POL_TILE;
+constexpr int TILE = POL_TILE;
 static_assert(TILE == 16, "one 16-row MFMA sub-tile per workgroup");
 static_assert(2 * PPO_SYM_TILE == TILE, "the symmetric instance: column c the row as given, column PPO_SYM_TILE + c its mirror image");
 
-__device__ __forceinline__ float activate(float x, int act) {
+// NOT mocca_mlp::activate (tanhf), and named apart from it so that neither can stand in for the other
+__device__ __forceinline__ float activate_once(float x, int act) {
   switch (act) {
     case CTRL_ACT_RELU: return fmaxf(x, 0.0f);
     case CTRL_ACT_TANH: return (float)tanh((double)x);   // rounded once: the stored activations feed dW, and tanhf's 2 ulp showed in small nets
@@ -42,53 +45,6 @@ __device__ __forceinline__ float activate_slope(float x, int act) {
     case CTRL_ACT_SOFTSIGN: { const float u = 1.0f / (1.0f + fabsf(x)); return u * u; }
     default: return 1.0f;
   }
-}
-
-// out[o][col] = sum_k W[o][k] Xin[col][k] for the 16 columns of the workgroup: W in fragment order [n_ot][nkg][64][4]; epi(o, sum) receives
-// rows o .. o + 3 of column `col` (lane & 15), sum = (p0 + p1) + (p2 + p3).  mocca_policy.hip's loop.
-template <class Epi>
-__device__ __forceinline__ void mfma_layer(const f32x4* W, int nkg, int n_ot, const float* Xin, int wave, int lane, Epi epi) {
-  const int col = lane & 15, quad = lane >> 4;
-  const int nt_w = wave < n_ot ? (n_ot - wave + 3) >> 2 : 0;   // output tiles of this wave (wave-uniform)
-  if (nt_w == 0) return;
-  f32x4 acc[NT][NP];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int j = 0; j < NP; ++j) acc[t][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  const f32x4* wp[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int ot = wave + 4 * (t < nt_w ? t : nt_w - 1);
-    wp[t] = W + (size_t)ot * nkg * 64 + lane;
-  }
-  f32x4 w0[NT], w1[NT], w2[NT];
-  auto load = [&](f32x4 (&w)[NT], int kg) {
-    const int kc = kg < nkg ? kg : nkg - 1;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) w[t] = wp[t][(size_t)kc * 64];
-  };
-  auto multiply = [&](const f32x4 (&w)[NT], int kg) {
-    const f32x4 b = *(const f32x4*)&Xin[col * LDS_STRIDE + kg * 16 + quad * 4];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-      if (t < nt_w) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][j], b[j], acc[t][j], 0, 0, 0);
-      }
-  };
-  load(w0, 0); load(w1, 1);
-#pragma unroll 1
-  for (int kg = 0; kg < nkg; kg += 3) {
-    load(w2, kg + 2); multiply(w0, kg);
-    if (kg + 1 >= nkg) break;
-    load(w0, kg + 3); multiply(w1, kg + 1);
-    if (kg + 2 >= nkg) break;
-    load(w1, kg + 4); multiply(w2, kg + 2);
-  }
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-    if (t < nt_w) epi((wave + 4 * t) * 16 + quad * 4, (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]));
 }
 
 // MODE (header: Symmetric policy, Mirror loss, Duplicated rows).  PPO_SYM, PPO_MIRROR and PPO_DUP (SYM below): the 16 MFMA columns are PPO_SYM_TILE = 8 minibatch rows x
@@ -144,13 +100,13 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
     float* Xout = X[cur ^ 1];
     float* Y = a.scratch + a.a_off[first + li] + (size_t)(srow0 + col) * out_pad;
     float* S = a.scratch + a.dz_off[first + li] + (size_t)(srow0 + col) * out_pad;
-    mfma_layer((const f32x4*)(a.params + lr[CL_W_OFF]), lr[CL_IN_PAD] >> 4, out_pad >> 4, X[cur], wave, lane, [&](int o, f32x4 sum) {
+    mfma_layer<LDS_STRIDE>((const f32x4*)(a.params + lr[CL_W_OFF]), lr[CL_IN_PAD] >> 4, out_pad >> 4, X[cur], wave, lane, [&](int o, f32x4 sum) {
       const f32x4 bias = *(const f32x4*)(Bias + o);
       f32x4 y, slope;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float x = sum[r] + bias[r];
-        y[r] = activate(x, act);
+        y[r] = activate_once(x, act);
         slope[r] = live ? activate_slope(x, act) : 0.0f;
       }
       *(f32x4*)(S + o) = slope;   // act'(x) waits in dZ's place until the backward multiplies it by dA
@@ -319,7 +275,7 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
     if (li == 0) break;
     __syncthreads();
     float* Xout = X[cur ^ 1];
-    mfma_layer((const f32x4*)(a.params + a.wt_off[first + li]), out_pad >> 4, lr[CL_IN_PAD] >> 4, Xd, wave, lane,
+    mfma_layer<LDS_STRIDE>((const f32x4*)(a.params + a.wt_off[first + li]), out_pad >> 4, lr[CL_IN_PAD] >> 4, Xd, wave, lane,
                [&](int o, f32x4 sum) { *(f32x4*)&Xout[col * LDS_STRIDE + o] = sum; });
     __syncthreads();
     cur ^= 1;

@@ -404,19 +404,25 @@ class VecEnv:
         if getattr(policy, "symmetry", None) is not None:      # after the shapes: mocca_set_policy has dropped whatever was attached
             self.set_policy_symmetry(policy.symmetry)
 
+    def _set_policy_mirror(self, name: str, tables, *extra):
+        """What the three setters below share: mocca_<name>(tables, *extra) -> the tables as the library took them, or None (detached)."""
+        if self.policy is None:
+            raise _lib.MoccaError(f"{name} needs a policy (set_policy)")
+        fn = getattr(self.lib, "mocca_" + name)
+        if tables is None:
+            _lib.check(fn(self.h, None, None, None, None, *extra), self.h)   # (a detach reads nothing of `extra`)
+            return None
+        t = [np.ascontiguousarray(x, d) for x, d in zip(tables, (np.int32, np.float32, np.int32, np.float32))]
+        if (t[0].size, t[1].size, t[2].size, t[3].size) != (self.policy.in_dim, self.policy.in_dim, self.policy.act_dim, self.policy.act_dim):
+            raise ValueError(f"the mirror tables have {self.policy.in_dim} input and {self.policy.act_dim} action entries")
+        _lib.check(fn(self.h, *[x.ctypes.data_as(C.c_void_p) for x in t], *extra), self.h)
+        return tuple(t)
+
     def set_policy_symmetry(self, tables) -> None:
         """Attach mirror tables (symmetry.mirror_tables: in_perm, in_sign, act_perm, act_sign) to the policy set_policy attached: act() and
         act_step() then run the symmetric policy (csrc/mocca_policy.h: Symmetry), still one launch.  None detaches.  set_policy() with a
         `DevicePolicy(symmetry=)` calls this; update_policy() leaves the symmetry alone.  May synchronise."""
-        if self.policy is None:
-            raise _lib.MoccaError("set_policy_symmetry needs a policy (set_policy)")
-        if tables is None:
-            _lib.check(self.lib.mocca_set_policy_symmetry(self.h, None, None, None, None), self.h)
-        else:
-            t = [np.ascontiguousarray(x, d) for x, d in zip(tables, (np.int32, np.float32, np.int32, np.float32))]
-            if (t[0].size, t[1].size, t[2].size, t[3].size) != (self.policy.in_dim, self.policy.in_dim, self.policy.act_dim, self.policy.act_dim):
-                raise ValueError(f"the mirror tables have {self.policy.in_dim} input and {self.policy.act_dim} action entries")
-            _lib.check(self.lib.mocca_set_policy_symmetry(self.h, *[x.ctypes.data_as(C.c_void_p) for x in t]), self.h)
+        self._set_policy_mirror("set_policy_symmetry", tables)
         if hasattr(self.policy, "with_symmetry"):
             self.policy = self.policy.with_symmetry(tables)
 
@@ -427,17 +433,8 @@ class VecEnv:
         policy; ppo_grad() and ppo_update() then differentiate PPO's loss plus the term (mocca_ppo_grad_mirror) and report it in
         stats[7].  None detaches.  Exclusive with a symmetric policy; set_policy() drops it, update_policy() leaves it alone.  May
         synchronise."""
-        if self.policy is None:
-            raise _lib.MoccaError("set_policy_mirror_loss needs a policy (set_policy)")
-        if tables is None:
-            _lib.check(self.lib.mocca_set_policy_mirror_loss(self.h, None, None, None, None, 0.0), self.h)
-            self.mirror_loss = None
-            return
-        t = [np.ascontiguousarray(x, d) for x, d in zip(tables, (np.int32, np.float32, np.int32, np.float32))]
-        if (t[0].size, t[1].size, t[2].size, t[3].size) != (self.policy.in_dim, self.policy.in_dim, self.policy.act_dim, self.policy.act_dim):
-            raise ValueError(f"the mirror tables have {self.policy.in_dim} input and {self.policy.act_dim} action entries")
-        _lib.check(self.lib.mocca_set_policy_mirror_loss(self.h, *[x.ctypes.data_as(C.c_void_p) for x in t], float(coef)), self.h)
-        self.mirror_loss = (tuple(t), float(coef))
+        t = self._set_policy_mirror("set_policy_mirror_loss", tables, float(coef))
+        self.mirror_loss = None if t is None else (t, float(coef))
 
     def set_policy_mirror_dup(self, tables) -> None:
         """Attach SymmetricRL's DUPLICATED TUPLES to the policy set_policy attached, for the gradient only: `tables` as in
@@ -446,17 +443,7 @@ class VecEnv:
         (mocca_ppo_grad_dup); a twin borrows its row's old_logp, so stats[7], the twins' share of stats[3], measures how far off-policy
         the policy's asymmetry puts them.  None detaches.  Exclusive with a symmetric policy and with a mirror loss; set_policy() drops
         it, update_policy() leaves it alone.  May synchronise."""
-        if self.policy is None:
-            raise _lib.MoccaError("set_policy_mirror_dup needs a policy (set_policy)")
-        if tables is None:
-            _lib.check(self.lib.mocca_set_policy_mirror_dup(self.h, None, None, None, None), self.h)
-            self.mirror_dup = None
-            return
-        t = [np.ascontiguousarray(x, d) for x, d in zip(tables, (np.int32, np.float32, np.int32, np.float32))]
-        if (t[0].size, t[1].size, t[2].size, t[3].size) != (self.policy.in_dim, self.policy.in_dim, self.policy.act_dim, self.policy.act_dim):
-            raise ValueError(f"the mirror tables have {self.policy.in_dim} input and {self.policy.act_dim} action entries")
-        _lib.check(self.lib.mocca_set_policy_mirror_dup(self.h, *[x.ctypes.data_as(C.c_void_p) for x in t]), self.h)
-        self.mirror_dup = tuple(t)
+        self.mirror_dup = self._set_policy_mirror("set_policy_mirror_dup", tables)
 
     def policy_mirror_tables(self, policy):
         """The mirror tables (in_perm, in_sign, act_perm, act_sign) of THIS env for `policy` (a `policy.DevicePolicy`): built from
