@@ -205,6 +205,13 @@ constexpr bool MID_RECORDS = false;
 #else
 constexpr bool MID_RECORDS = T::NPAIR > 0 && 6 * T::NG <= GP_FLOATS && L_MID + 4 * T::NG <= (COMPACT ? (int)L_ABA_END : (int)L_TOTAL);
 #endif
+// does body b have a child?  (T::cchild: the compile-time child table of the generated topo_*.h)
+template <class T>
+constexpr bool has_child(int b) {
+  for (int k = 0; k < T::MAXCH; ++k)
+    if (T::cchild(b, k) >= 0) return true;
+  return false;
+}
 
 // contact record fields
 enum : int { C_BA = 0, C_BB = 1, C_SLOT = 2, C_P = 3, C_N = 6, C_DEPTH = 9, C_MU = 10, C_ERP = 11, C_CFM = 12, C_MA = 13, C_MB = 14 };
@@ -296,6 +303,32 @@ struct StepArgs {
   int hf_stride, hf_n_fields, hf_redraw;
 };
 constexpr int ROBOT_STATE_STRIDE = 64;   // = mocca_ctrl::CTRL_RS_STRIDE (mocca_controller.h; checked in mocca_api.hip)
+
+// The LATE VIEW of a step kernel's arguments: a copy of the StepArgs record read again from the kernarg segment, at the point of the
+// call.  The compiler loads every kernel argument at entry; the forty-odd that only the epilogue uses (outputs, episode statistics, reset
+// parameters, seeds) do not fit the scalar registers across the substep loop, are parked in lanes of a vector register (v_writelane)
+// and fetched back one v_readlane each.  Reading them where they are used is a scalar load and costs no vector slot.  The pointer is
+// laundered, so the loads can neither merge with those at entry nor move above this point; only the fields the caller reads are loaded.
+// Valid only in a kernel whose ONE parameter is the StepArgs record (offset 0 of the segment).  LATE = false: nothing is read (the caller uses its parameter).
+DI void read_kernargs(StepArgs& la) {
+  auto p = __builtin_amdgcn_kernarg_segment_ptr();   // (constant address space: scalar loads)
+  asm volatile("" : "+s"(p));
+  __builtin_memcpy(&la, p, sizeof(StepArgs));
+}
+template <bool LATE>
+DI void late_args(StepArgs& la) {
+  if constexpr (LATE) read_kernargs(la);
+}
+// Which step-kernel instances read the late view: all but the walker's physics instances at their register budget, which keep the arguments
+// of the entry.  With the late view the substep loop, scheduled around the freed scalar registers, spilled in the 48-row Stepper and Planner
+// instances (20 / 36 B of scratch where there was none) and spilled more in the compact ones (Custom 27 -> 34 registers, Stepper and Planner
+// 4 / 24 B of scratch more); the 48-row Custom instance, the headline, goes from 124 to 127 of its 128 registers and spills nothing.
+template <class T, int TASK, bool INJECT>
+#ifdef MOCCA_NO_TRIM_7
+constexpr bool LATE_ARGS = false;
+#else
+constexpr bool LATE_ARGS = INJECT || MAXR > 48 || !__is_base_of(TopoWalker3D, T) || (!COMPACT && TASK == MOCCA_TASK_WALKER3D_CUSTOM);
+#endif
 
 // ------------------------------------------------------------------ helpers
 DI void wsync() {
@@ -498,9 +531,16 @@ DI void walk_consts(ModelP M, int b, WalkConsts& k) {
     k.ms = M->mass[b]; k.jarm = M->jarm[b]; k.jdamp = M->jdamp[b];
   }
 }
-// ---- phase 1: body frames (L_RT) and world joint axes (L_SV + SVS b + 0..2)
-template <class T>
+// ---- phase 1: body frames (L_RT) and, with AXES, world joint axes (L_SV + SVS b + 0..2).  Only the FULL second phase reads the axes: the
+// walks that precede an observation (step epilogue, reset, observe kernel) leave them out, and stage_joints leaves out the float4 they come from
+#ifdef MOCCA_NO_TRIM_6
+template <class T, bool AXES_ = true>
 DI void walk_phase1(float* L, int lane, unsigned long long ppk) {
+  constexpr bool AXES = true;
+#else
+template <class T, bool AXES = true>
+DI void walk_phase1(float* L, int lane, unsigned long long ppk) {
+#endif
   static_assert(3 * (T::NB - 1) <= 63, "three lanes per body must fit the wave (lane 63 writes the base)");
   {
     const int g = (lane * 43) >> 7;          // lane / 3 for lane < 64
@@ -529,9 +569,9 @@ DI void walk_phase1(float* L, int lane, unsigned long long ppk) {
       row[0] = n0; row[1] = n1; row[2] = n2;
     }
     if (bg > 0) {
-      const float4 r3 = reinterpret_cast<const float4*>(L + L_SV + SVS * bg)[3];
+      const float4 r3 = AXES ? reinterpret_cast<const float4*>(L + L_SV + SVS * bg)[3] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
       *reinterpret_cast<float4*>(L + L_RT + 12 * bg + 4 * ri) = make_float4(row[0], row[1], row[2], rr);
-      L[L_SV + SVS * bg + ri] = row[0] * r3.x + row[1] * r3.y + row[2] * r3.z;  // world axis: Rot(axis, q) leaves the axis in place
+      if constexpr (AXES) L[L_SV + SVS * bg + ri] = row[0] * r3.x + row[1] * r3.y + row[2] * r3.z;  // world axis: Rot(axis, q) leaves the axis in place
     }
     if (lane == 63) {
 #pragma unroll
@@ -661,7 +701,7 @@ DI void walk_kinematics(ModelP M, float* L, int lane, unsigned long long ppk) {
   const int b = lane < T::NB ? lane : 0;
   WalkConsts wk;
   walk_consts<FULL>(M, b, wk);   // fetched before the walk so that their latency hides behind it
-  walk_phase1<T>(L, lane, ppk);
+  walk_phase1<T, FULL>(L, lane, ppk);
   wsync();
   walk_phase2<T, FULL>(M, L, lane, b, ppk, wk);
 }
@@ -2129,10 +2169,14 @@ DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wan
       pub[k] = uu * L[L_SV + SVS * jj + SV_INVD];
       pin6(pb); pin1(pub[k]); pin1(w);
     }
-  } else {
+  }
+#ifdef MOCCA_NO_TRIM_5
+  else {
 #pragma unroll
     for (int k = 0; k < T::MAXD; ++k) pub[k] = 0.0f;
   }
+#endif
+  // (without a second path pub stays unwritten: the outward sweep reads it under the same wave-uniform two_paths)
   // Launder the LDS pointer: otherwise the compiler keeps all 21 bodies' S/U loads of the inward sweep live
   // for the outward sweep (273 VGPRs); re-reading 13 broadcast floats per body costs far less than the occupancy.
   STAMP(19);
@@ -2162,18 +2206,29 @@ DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wan
 #pragma unroll
     for (int b = 1; b < T::NB; ++b) {
       const int p = T::parent(b);
-      float S[6], U[6];
+      // a body without children: nothing reads its acceleration, so neither that nor its S is formed (T::cchild, compile time;
+      // the walker's bodies 8, 13, 17 and 21)
+#ifdef MOCCA_NO_TRIM_4
+      constexpr bool inner = true;
+#else
+      const bool inner = has_child<T>(b);   // (folds after unrolling)
+#endif
+      float U[6];
 #pragma unroll
-      for (int i = 0; i < 6; ++i) { S[i] = L2[L_SV + SVS * b + i]; U[i] = L2[L_SV + SVS * b + SV_V + i]; }   // U = V = IA S / D
+      for (int i = 0; i < 6; ++i) U[i] = L2[L_SV + SVS * b + SV_V + i];   // U = V = IA S / D
       const int dpos = T::depth(b) - 1;  // (folds after unrolling) the body's position on every path that holds it
       // pu[dpos] where the row's path holds b, else 0: bit b of the ancestor mask, sign-extended, ANDs the value (v_bfe_i32 + v_and)
       float ub = __uint_as_float(__float_as_uint(pu[dpos]) & (unsigned)__builtin_amdgcn_sbfe((int)ma, b, 1));
       if (two_paths) ub += __uint_as_float(__float_as_uint(pub[dpos]) & (unsigned)__builtin_amdgcn_sbfe((int)mb, b, 1));
       const float qdd = ub - dot6(U, acc[p]);   // u / D - (IA S / D) . a_parent
       X[5 + b] = qdd;
+      if (inner) {
+        float S[6];
 #pragma unroll
-      for (int i = 0; i < 6; ++i) acc[b][i] = acc[p][i] + S[i] * qdd;
-      pin6(acc[b]); pin1(X[5 + b]);
+        for (int i = 0; i < 6; ++i) { S[i] = L2[L_SV + SVS * b + i]; acc[b][i] = acc[p][i] + S[i] * qdd; }
+        pin6(acc[b]);
+      }
+      pin1(X[5 + b]);
     }
   }
   STAMP(6);
@@ -2387,8 +2442,15 @@ DI void fast_sincos(float q, float* s, float* c) {
 // lane = joint: sin/cos of the joint angle and everything a path walk needs about the joint, as one 16-float LDS
 // record (layout at L_JR0).  Every lane of a walk visits up to MAXD joints; staging keeps the model's global loads and the
 // Rodrigues formula out of that loop (they were re-done per (lane, path step), with the load latency on the chain).
-template <class T>
+// AXES = false (a walk that precedes an observation, walk_kinematics<T, false>): the fourth float4, axis and speed, has no reader and is not written
+#ifdef MOCCA_NO_TRIM_6
+template <class T, bool AXES_ = true>
 DI void stage_joints(ModelP M, float* L, int lane) {
+  constexpr bool AXES = true;
+#else
+template <class T, bool AXES = true>
+DI void stage_joints(ModelP M, float* L, int lane) {
+#endif
   if (lane < T::NB) {   // lane 0 stages the identity (blob joint 0, q[0] = 0)
     const int j = lane;
     float s, cq;
@@ -2407,7 +2469,7 @@ DI void stage_joints(ModelP M, float* L, int lane) {
     rec[0] = make_float4(Tl[0], Tl[1], Tl[2], Tl[3]);
     rec[1] = make_float4(Tl[4], Tl[5], Tl[6], Tl[7]);
     rec[2] = make_float4(Tl[8], M->jpos[j][0], M->jpos[j][1], M->jpos[j][2]);
-    rec[3] = make_float4(ax[0], ax[1], ax[2], L[L_QD + j]);
+    if constexpr (AXES) rec[3] = make_float4(ax[0], ax[1], ax[2], L[L_QD + j]);
   }
   wsync();
 }
@@ -2735,7 +2797,7 @@ DI float reset_base_pose(ModelP M, float* L, int lane) {
   if (lane < MOCCA_MAX_SLOTS) L[L_WARM + lane] = 0.0f;
   wsync();
   const float z0 = L[L_BASE + 2];
-  stage_joints<T>(M, L, lane);
+  stage_joints<T, false>(M, L, lane);
   walk_kinematics<T, false>(M, L, lane, T::path_packed(lane < T::NB ? lane : 0));
   wsync();
   return z0;

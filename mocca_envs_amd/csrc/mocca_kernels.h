@@ -239,7 +239,7 @@ DI StepResult cassie_step(const StepArgs& __restrict__ a, ModelP M, float* L, ui
     jv = (L[L_Q + M->ordered_body[lane]] - L[L_Q0 + lane]) / M->control_dt;
     tk[MOCCA_TW_JVEL + lane] = __float_as_uint(jv);
   }
-  stage_joints<T>(M, L, lane);
+  stage_joints<T, false>(M, L, lane);
   walk_kinematics<T, false>(M, L, lane, ppk);
   wsync();
   t.t += 1;
@@ -289,6 +289,11 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
   const unsigned long long ppk = T::path_packed(lane < T::NB ? lane : 0);
   ContactFlags fl = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   int cover = 0;   // Stepper: cover mask of the last substep's contacts (mocca_device.h cover_targets)
+  // the arguments as everything behind the substeps reads them: the late view (late_args), which is not carried across the loop, in
+  // the instances that take it (LATE_ARGS), the kernel's own parameter in the others
+  constexpr bool LATE = LATE_ARGS<T, TASK, INJECT>;
+  StepArgs late, late_reset;
+  const StepArgs& al = LATE ? late : a;
   if constexpr (TASK == MOCCA_TASK_CASSIE) {
     // ---- CassieEnv.step (env_cassie.py:433-479): 50 x { filter joint speeds, PD torques, one physics step }
     const int no = M->n_ordered, nctl = M->n_ctrl, mode = M->cassie_mode;
@@ -333,6 +338,7 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
       wsync();
       substep<T, TASK>(Ms, L, ln, nullptr, 0, pk, dbg, a.prio, last_rows, HeightFieldArgs{nullptr, 0, 0, 0.0f}, it, nllc);
     }
+    late_args<LATE>(late);
     if (!INJECT && lane == 0) tk[MOCCA_TW_LAST_ROWS] = (uint32_t)last_rows;
   } else {
     // apply_action, robots.py:31-40.  Only the two task words the physics needs are read before the substeps;
@@ -368,12 +374,13 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
       asm volatile("" : "+s"(Ms), "+v"(ln), "+v"(pk));  // are hoisted out of the loop and spilled
       fl = substep<T, TASK>(Ms, L, ln, ter, nsi0, pk, dbg, a.prio, last_rows, HeightFieldArgs{hfp, a.hf_rows, a.hf_cols, a.hf_scale}, s, nsub, &cover);
     }
+    late_args<LATE>(late);
     if constexpr (INJECT) {  // getContactPoints results handed in by the caller (robots.py:74-86, env_locomotion.py:634-650, :880-890)
-      const int32_t* tc = a.inj_touch + (size_t)env * T::NFEET;
+      const int32_t* tc = al.inj_touch + (size_t)env * T::NFEET;
       fl.touch0 = tc[0] != 0; fl.touch1 = tc[1] != 0;
       if constexpr (T::NFEET > 2) { fl.touch2 = tc[2] != 0; fl.touch3 = tc[3] != 0; }
-      if (a.inj_target) {   // per foot: 1 = on the cover of the target plank (plank next_step_index mod n_planks at the step's start), 2 = of the plank after it
-        const int32_t* tg = a.inj_target + (size_t)env * T::NFEET;
+      if (al.inj_target) {   // per foot: 1 = on the cover of the target plank (plank next_step_index mod n_planks at the step's start), 2 = of the plank after it
+        const int32_t* tg = al.inj_target + (size_t)env * T::NFEET;
         const int npl = TASK == MOCCA_TASK_WALKER3D_STEPPER ? M->n_planks : 1;
 #pragma unroll
         for (int f = 0; f < T::NFEET; ++f)
@@ -381,53 +388,56 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
         fl.target0 = tg[0] == 1; fl.target1 = tg[1] == 1;
         if constexpr (T::NFEET > 2) { fl.target2 = tg[2] == 1; fl.target3 = tg[3] == 1; }
       }
-      if (a.inj_body) fl.body_touch = a.inj_body[env] != 0;
+      if (al.inj_body) fl.body_touch = al.inj_body[env] != 0;
     }
     if (!INJECT && lane == 0) tk[MOCCA_TW_LAST_ROWS] = (uint32_t)last_rows;
     STAMP(27);  // substeps done
   }
   TaskRegs t = load_task<T, TASK>(tk);
-  const float ep_ret0 = a.ep_ret ? a.ep_ret[env] : 0.0f;
+  const float ep_ret0 = al.ep_ret ? al.ep_ret[env] : 0.0f;
   StepResult r;
-  if constexpr (TASK == MOCCA_TASK_CASSIE) r = cassie_step<T>(a, M, L, tk, lane, ppk, t, obs);
+  if constexpr (TASK == MOCCA_TASK_CASSIE) r = cassie_step<T>(al, M, L, tk, lane, ppk, t, obs);
   else {
     // the raw (unclipped) action enters the energy penalty (env_locomotion.py:185-188): re-read, not held in a register across the substeps
-    const float act_raw = lane < T::NJ ? a.act[(size_t)env * T::NJ + lane] : 0.0f;
+    const float act_raw = lane < T::NJ ? al.act[(size_t)env * T::NJ + lane] : 0.0f;
     {
       int lo = lane;  // laundered: the walk's lane-derived body index would otherwise be kept (spilled) from kernel entry
       asm volatile("" : "+v"(lo));
-      stage_joints<T>(M, L, lo);
+      stage_joints<T, false>(M, L, lo);
       walk_kinematics<T, false>(M, L, lo, ppk);
     }
     wsync();
     t.t += 1;
-    if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) r = planner_step<T>(M, L, lane, t, fl, obs, a.base_value ? a.base_value + env : nullptr);
-    else if constexpr (TASK == MOCCA_TASK_WALKER3D_CUSTOM) r = custom_step<T, INJECT>(a, M, L, env, lane, t, fl, act_raw, obs);
-    else r = stepper_step<T, INJECT>(a, M, L, ter, tk, env, lane, t, fl, cover, act_raw, obs);
+    if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) r = planner_step<T>(M, L, lane, t, fl, obs, al.base_value ? al.base_value + env : nullptr);
+    else if constexpr (TASK == MOCCA_TASK_WALKER3D_CUSTOM) r = custom_step<T, INJECT>(al, M, L, env, lane, t, fl, act_raw, obs);
+    else r = stepper_step<T, INJECT>(al, M, L, ter, tk, env, lane, t, fl, cover, act_raw, obs);
     t.prevx = L[L_BASE];
   }
   const int timeout = t.t >= M->max_episode_steps;
   const int dflag = (t.done ? 1 : 0) | (timeout ? 2 : 0);
   if (lane == 0) {
-    a.rew[env] = r.rew;
-    a.done[env] = (uint8_t)dflag;
-    if (a.info) a.info[env] = r.info;
-    if (a.ep_ret) monitor_emit(a, env, ep_ret0, r.rew, dflag, t.t, r.info);
+    al.rew[env] = r.rew;
+    al.done[env] = (uint8_t)dflag;
+    if (al.info) al.info[env] = r.info;
+    if (al.ep_ret) monitor_emit(al, env, ep_ret0, r.rew, dflag, t.t, r.info);
   }
   STAMP(26);  // observation + reward done
-  if (a.auto_reset && dflag) {
-    keep_terminal_obs(a, L, env, lane);
-    reset_task<T, TASK, INJECT>(a, M, L, ter, tk, env + a.env_offset, lane, t, obs);
+  if (al.auto_reset && dflag) {
+    late_args<LATE>(late_reset);   // the reset's arguments (seeds, curriculum, gains, the terminal-observation buffer): read by the waves that reset, where they reset
+    const StepArgs& ar = LATE ? late_reset : a;
+    keep_terminal_obs(ar, L, env, lane);
+    reset_task<T, TASK, INJECT>(ar, M, L, ter, tk, env + ar.env_offset, lane, t, obs);
   }
   wsync();
-  flush_obs(L, obs_out, lane, a.obs_dim);
-  if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) keep_robot_state<T>(a, L, env, lane);
+  late_args<LATE>(late);   // and the write-back's: read behind the reset, not held across it
+  flush_obs(L, LATE ? al.obs + (size_t)env * al.obs_dim : obs_out, lane, al.obs_dim);
+  if constexpr (TASK == MOCCA_TASK_WALKER3D_PLANNER) keep_robot_state<T>(al, L, env, lane);
   store_dyn(st, L, lane, T::NJ, T::NSLOT, (uni(__float_as_int(L[L_KEEPWARM])) & 1) != 0);
   if (lane == 0) store_task<T, TASK, true>(tk, t);
-  if (!INJECT) pace_finish(a, L, lane, a.pace);
+  if (!INJECT) pace_finish(al, L, lane, al.pace);
   STAMP(25);  // reset (if any) + write-back done
 #ifdef MOCCA_STAMPS
-  if (lane == 0 && blockIdx.x < STAMP_WAVES) g_stamps[blockIdx.x * STAMP_SLOTS + 24] = (unsigned long long)(a.auto_reset && dflag);
+  if (lane == 0 && blockIdx.x < STAMP_WAVES) g_stamps[blockIdx.x * STAMP_SLOTS + 24] = (unsigned long long)(al.auto_reset && dflag);
 #endif
 }
 
@@ -466,7 +476,7 @@ __global__ __launch_bounds__(64) void mocca_observe_kernel(StepArgs a) {
   TaskRegs t = load_task<T, TASK>(tk);
   if (lane == 0) { L[L_Q] = 0.0f; L[L_QD] = 0.0f; }
   wsync();
-  stage_joints<T>(M, L, lane);
+  stage_joints<T, false>(M, L, lane);
   walk_kinematics<T, false>(M, L, lane, T::path_packed(lane < T::NB ? lane : 0));
   wsync();
   if constexpr (TASK == MOCCA_TASK_CASSIE) {
