@@ -413,6 +413,41 @@ int mocca_set_height_scan(mocca_handle h, const float *points_host, int n_points
 int mocca_scan_dim(mocca_handle h);
 int mocca_height_scan(mocca_handle h, float *out_dev, int row_stride, const float *obs_dev, void *stream);
 
+/* The egocentric depth camera: a small depth image per env from a pinhole that rides on one of the robot's links, cast with mocca_render's
+ * geometry -- the same pixel centres, rays and depth (t along the view axis) -- but for all N envs in one launch on the training path.
+ * Mount: mount_host [6] f32 (HOST memory) is the eye's offset (3) in `body`'s frame, then roll, pitch, yaw in radians.  The camera's axes
+ * in the MOUNT frame are the columns of R_z(yaw) R_y(pitch) R_x(roll) (the planks' Euler order): forward = column 0, up = column 2,
+ * right = forward x up.  With all angles zero the camera looks along the mount's +x with +z up; a POSITIVE pitch looks down.  The mount
+ * frame is `body`'s R of mocca_get_link_frames (a rigid mount), or with MOCCA_DEPTH_STABILISED R_z(yaw) of the base's heading, from the
+ * (cos yaw, sin yaw) mocca_height_scan uses.  In both modes the eye is origin_body + R_body offset.
+ * Seen: the plane z = 0 (Custom and Cassie tasks), the live planks, the env's own height field from the bank and, with
+ * MOCCA_DEPTH_SEE_ROBOT, the robot as mocca_render draws it (its geoms, or its skeleton).  The walk target is never seen: it is visual only.
+ *   mocca_set_depth_camera  body 0 .. n_bodies - 1; 1 <= width, height <= 64, width * height <= MOCCA_DEPTH_MAX_PIXELS; 0 < fov_y < pi
+ *                           (radians); 0 < near < far; flags a sum of MOCCA_DEPTH_*.  mount_host == NULL detaches.  Allocates nothing.
+ *   mocca_depth_dim         width * height, 0 when no camera is attached.
+ *   mocca_depth_camera      obs_dev == NULL: row e is out_dev[e * row_stride .. + width * height).  obs_dev [N][obs_dim] f32: row e is
+ *                           [obs (obs_dim) | depth] -- the same launch copies the observation, as mocca_height_scan does.  Entry
+ *                           j * width + i of the image is the depth in metres of pixel (column i, row j), row 0 on top; exactly `far`
+ *                           where nothing is entered in [near, far).  Floats of a row beyond what is written are left untouched; out_dev
+ *                           must not overlap obs_dev.  cameras_dev [N][MOCCA_CAMERA_FLOATS] f32 or NULL: the camera records the rays were
+ *                           cast from (pass them to mocca_render to watch what the robot sees); bit for bit the same with and without
+ *                           MOCCA_DEPTH_SEE_ROBOT.  One kernel, one wave per env, asynchronous on `stream`: no allocation, no host read,
+ *                           no synchronisation, no atomics -- capturable in a hipGraph together with mocca_step / mocca_plan_step /
+ *                           mocca_act_step.  Reads the state, task and terrain records and writes none of them; a non-finite pose
+ *                           leaves finite depths in [near, far], `far` along every ray that is not finite.  An [obs | scan | depth] row: mocca_height_scan with obs_dev, then this call with out_dev
+ *                           advanced by obs_dim + scan_dim and obs_dev == NULL.
+ * Errors (MOCCA_E_ARG, with a message; the handle is unchanged and nothing is launched): body outside 0 .. n_bodies - 1, width or height
+ * outside 1 .. 64 or their product above MOCCA_DEPTH_MAX_PIXELS, a non-finite mount, fov_y outside (0, pi), near <= 0, far <= near, a
+ * non-finite near or far, unknown flag bits, mocca_depth_camera before mocca_set_depth_camera, row_stride smaller than the row, out_dev
+ * NULL, a planner handle before mocca_set_heightfield. */
+#define MOCCA_DEPTH_MAX_PIXELS 256
+#define MOCCA_DEPTH_STABILISED 1   /* orientation from the base's heading only */
+#define MOCCA_DEPTH_SEE_ROBOT  2   /* the robot's own geoms (or its skeleton) occlude */
+int mocca_set_depth_camera(mocca_handle h, int body, const float *mount_host /* [6] */, int width, int height, double fov_y, double near,
+                           double far, int flags);
+int mocca_depth_dim(mocca_handle h);
+int mocca_depth_camera(mocca_handle h, float *out_dev, int row_stride, const float *obs_dev, float *cameras_dev, void *stream);
+
 /* ---- the trainer's own policy on the device (no reference counterpart: the reference's trainers, README.md:33-39, run their
  *      pytorch-a2c-ppo-acktr `actor_critic.act()` in torch, four small kernels and a sampler per step) ---- */
 

@@ -19,6 +19,7 @@
 #include "mocca_render.h"
 #include "mocca_rollout.h"
 #include "mocca_scan.h"
+#include "mocca_depth.h"
 #include "mocca_terrain.h"
 
 using namespace mocca;
@@ -153,6 +154,8 @@ struct mocca_ctx {
   DevBuf<float> d_scan_pts;     // mocca_set_height_scan: the pattern [scan_n][2] in the heading frame, owned by the handle
   int scan_n = 0;
   float scan_above = 0.0f, scan_drop = 0.0f;
+  bool depth_on = false;        // mocca_set_depth_camera: the camera, passed to the kernel by value (out, obs and the records apart)
+  mocca_depth::DepthArgs depth{};
   // planner envs: the base controller (mocca_set_base_controller), all owned by the handle
   DevBuf<float> d_ctrl_image;        // the kernel's image (mocca_controller.h; the tail of mocca_policy.h's image is there and not read)
   DevBuf<int32_t> d_ctrl_layers;
@@ -1221,6 +1224,53 @@ int mocca_height_scan(mocca_handle h, float* out_dev, int row_stride, const floa
   a.points = h->d_scan_pts; a.n_points = h->scan_n; a.z_above = h->scan_above; a.max_drop = h->scan_drop;
   a.out = out_dev; a.row_stride = row_stride; a.obs = obs_dev; a.obs_dim = obs_dev ? h->obs_dim : 0;
   mocca_scan::launch_height_scan((hipStream_t)stream, a, h->n_envs);
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
+}
+
+int mocca_set_depth_camera(mocca_handle h, int body, const float* mount_host, int width, int height, double fov_y, double near, double far, int flags) {
+  if (!h) return MOCCA_E_ARG;
+  if (!mount_host) {   // detach
+    h->depth_on = false;
+    return MOCCA_OK;
+  }
+  auto bad = [&](const std::string& what) { h->err = "mocca_set_depth_camera: " + what; return MOCCA_E_ARG; };
+  if (body < 0 || body >= h->model.n_bodies) return bad("body " + std::to_string(body) + " is outside 0 .. " + std::to_string(h->model.n_bodies - 1));
+  if (width < 1 || width > 64 || height < 1 || height > 64 || width * height > MOCCA_DEPTH_MAX_PIXELS)
+    return bad("width and height must be 1 .. 64 and their product at most " + std::to_string(MOCCA_DEPTH_MAX_PIXELS));
+  for (int k = 0; k < 6; ++k)
+    if (!std::isfinite(mount_host[k])) return bad("mount entry " + std::to_string(k) + " is not finite");
+  if (!(fov_y > 0.0 && fov_y < 3.14159265358979323846)) return bad("fov_y must lie in (0, pi) radians");
+  if (!std::isfinite(near) || !std::isfinite(far) || !(near > 0.0) || !(far > near)) return bad("needs finite 0 < near < far");
+  if (flags & ~(MOCCA_DEPTH_STABILISED | MOCCA_DEPTH_SEE_ROBOT)) return bad("unknown flag bits " + std::to_string(flags & ~(MOCCA_DEPTH_STABILISED | MOCCA_DEPTH_SEE_ROBOT)));
+  mocca_depth::DepthArgs a{};
+  a.body = body; a.width = width; a.height = height; a.flags = flags;
+  for (int k = 0; k < 3; ++k) a.offset[k] = mount_host[k];
+  mocca_rdr::euler_to_mat(mount_host[3], mount_host[4], mount_host[5], a.axes);
+  a.tan_half_fov = (float)std::tan(0.5 * fov_y); a.near = (float)near; a.far = (float)far;
+  if (!std::isfinite(a.tan_half_fov) || !(a.near > 0.0f) || !(a.far > a.near)) return bad("fov_y, near and far must stay distinct and finite in float32");
+  h->depth = a; h->depth_on = true;
+  return MOCCA_OK;
+}
+
+int mocca_depth_dim(mocca_handle h) { return h ? (h->depth_on ? h->depth.width * h->depth.height : 0) : MOCCA_E_ARG; }
+
+int mocca_depth_camera(mocca_handle h, float* out_dev, int row_stride, const float* obs_dev, float* cameras_dev, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (!h->depth_on) { h->err = "mocca_depth_camera: no camera (mocca_set_depth_camera)"; return MOCCA_E_ARG; }
+  if (!out_dev) { h->err = "mocca_depth_camera: out_dev must not be NULL"; return MOCCA_E_ARG; }
+  const int width = h->depth.width * h->depth.height + (obs_dev ? h->obs_dim : 0);
+  if (row_stride < width) {
+    h->err = "mocca_depth_camera: row_stride " + std::to_string(row_stride) + " is smaller than the row (" + std::to_string(width) + " floats)";
+    return MOCCA_E_ARG;
+  }
+  if (need_heightfield(h, "mocca_depth_camera: ", "first") != MOCCA_OK) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  mocca_depth::DepthArgs a = h->depth;
+  a.scene = scene_args(h);
+  a.hf = heightfield_record(h);
+  a.out = out_dev; a.row_stride = row_stride; a.obs = obs_dev; a.obs_dim = obs_dev ? h->obs_dim : 0; a.cameras = cameras_dev;
+  mocca_depth::launch_depth_camera((hipStream_t)stream, a, h->n_envs);
   HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
 }

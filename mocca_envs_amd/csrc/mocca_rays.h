@@ -33,7 +33,7 @@ DI HeightField env_heightfield(const HeightFieldBank& b, int env) {
   return HeightField{b.data + (size_t)f * b.stride, b.rows, b.cols, b.scale, b.range[2 * f], b.range[2 * f + 1]};
 }
 
-DI void euler_to_mat(float roll, float pitch, float yaw, float* R) {
+__host__ DI void euler_to_mat(float roll, float pitch, float yaw, float* R) {   // (on the host too: mocca_set_depth_camera's mount)
   const float cr = cosf(roll), sr = sinf(roll), cp = cosf(pitch), sp = sinf(pitch), cy = cosf(yaw), sy = sinf(yaw);
   R[0] = cy * cp; R[1] = cy * sp * sr - sy * cr; R[2] = cy * sp * cr + sy * sr;
   R[3] = sy * cp; R[4] = sy * sp * sr + cy * cr; R[5] = sy * sp * cr - cy * sr;

@@ -5,13 +5,11 @@
 #include <cstdint>
 
 #include "mocca.h"
-#include "mocca_rays.h"
+#include "mocca_scene.h"
 
 namespace mocca_rdr {
 
 constexpr int TILE = 16;                               // a 16 x 16 pixel tile per workgroup: four waves
-constexpr int MAX_PRIMS = MOCCA_MAX_GEOMS + 1;         // the robot's geoms and the walk target
-constexpr int PRIM_WORDS = 12;                         // p1 (3), radius, p2 (3), id, colour (3), kind
 // one view's scene as the assembly kernel leaves it: [MAX_PRIMS][PRIM_WORDS] then [MOCCA_MAX_PLANKS][PLANK_WORDS] then {n_prims, n_planks, 0, 0}
 constexpr int SCENE_WORDS = MAX_PRIMS * PRIM_WORDS + MOCCA_MAX_PLANKS * PLANK_WORDS + 4;
 static_assert(SCENE_WORDS * 4 <= 2048, "the scene of one env stays under 2 KB of LDS");

@@ -128,6 +128,18 @@ class EnvBase(gym.Env):
             self._vec.set_height_scan(points, z_above, max_drop)
         return self._vec.height_scan()[0].cpu().numpy()
 
+    def depth_image(self, camera=None):
+        """What the robot sees (VecEnv.depth_camera), np.float32 [H][W] metres along the view axis, `far` where nothing is in range:
+        `camera` a perception.DepthCamera that becomes the env's camera; None keeps the camera set before, or a 16 x 12 forward camera on
+        the base pitched 35 degrees down if there is none yet.  The sibling of height_scan()."""
+        if camera is None and self._vec.depth_dim == 0:
+            from .perception import DepthCamera
+            camera = DepthCamera(offset=(0.15, 0.0, 0.10), pitch=-35.0, fov_y=90.0, near=0.05, far=6.0)
+        if camera is not None:
+            self._vec.set_depth_camera(camera)
+        h, w = self._vec.depth_shape
+        return self._vec.depth_camera()[0].reshape(h, w).cpu().numpy()
+
     def _camera_follow(self, lookat=False):
         """reset: camera.lookat(robot.body_xyz) (env_locomotion.py:97,503,1065); step: camera.track(...) (:133,554,1105)"""
         if self.is_rendered:

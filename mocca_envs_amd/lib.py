@@ -23,6 +23,7 @@ DEBUG_WORDS = 20
 CAMERA_FLOATS = 16   # MOCCA_CAMERA_FLOATS
 RENDER_MAX_SIZE = 4096   # MOCCA_RENDER_MAX_SIZE
 SCAN_MAX_POINTS = 256   # MOCCA_SCAN_MAX_POINTS
+DEPTH_MAX_PIXELS, DEPTH_STABILISED, DEPTH_SEE_ROBOT = 256, 1, 2   # MOCCA_DEPTH_*
 HF_MAX_FIELDS, HF_MAX_PEAKS = 1024, 256   # MOCCA_HF_MAX_FIELDS, MOCCA_HF_MAX_PEAKS
 RENDER_ID_NONE, RENDER_ID_GROUND, RENDER_ID_PLANK0, RENDER_ID_HEIGHTFIELD, RENDER_ID_TARGET, RENDER_ID_LINK0 = -1, 32, 33, 37, 38, 64   # MOCCA_RENDER_ID_*
 
@@ -72,6 +73,9 @@ SYMBOLS = {
     "mocca_set_height_scan": (_i, [_vp, _vp, _i, _d, _d]),
     "mocca_scan_dim": (_i, [_vp]),
     "mocca_height_scan": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "mocca_set_depth_camera": (_i, [_vp, _i, _vp, _i, _i, _d, _d, _d, _i]),
+    "mocca_depth_dim": (_i, [_vp]),
+    "mocca_depth_camera": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "mocca_set_policy": (_i, [_vp, _vp, _i, _i, _i, _d]),
     "mocca_update_policy": (_i, [_vp, _vp, _sz, _vp]),
     "mocca_act": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

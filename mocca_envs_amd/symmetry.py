@@ -35,12 +35,14 @@ def _table(dim, neg, right, left, what):
     return perm, sign
 
 
-def mirror_tables(mirror_indices, obs_dim: int, act_dim: int, scan_points=None):
+def mirror_tables(mirror_indices, obs_dim: int, act_dim: int, scan_points=None, depth_shape=None):
     """-> (in_perm int32 [in_dim], in_sign float32 [in_dim], act_perm int32 [act_dim], act_sign float32 [act_dim]) in `MirrorTransform`'s
     convention, (M x)[k] = sign[k] * x[perm[k]]: perm swaps the right and left sets, sign is -1 on the neg set.  `mirror_indices`: the six
     lists of `get_mirror_indices()`.  With `scan_points` [n, 2] (a perception pattern: x ahead, y to the left) the input is [obs | scan],
     in_dim = obs_dim + n: scan entry p maps to the point at (px, -py) with sign +1, a point with py == 0 to itself; a point whose reflection
-    is not in the pattern (to 1e-6 m) is a ValueError.  The tables are checked (check_tables)."""
+    is not in the pattern (to 1e-6 m) is a ValueError.  With `depth_shape` (H, W) (a perception.DepthCamera in the robot's sagittal plane)
+    an H x W depth image follows, [obs | scan | depth]: entry (j, i), at j * W + i of the block, maps to (j, W - 1 - i) with sign +1.  The
+    tables are checked (check_tables)."""
     if isinstance(mirror_indices, dict) or len(mirror_indices) != 6:
         raise ValueError("mirror_indices must be the six lists (neg_obs, right_obs, left_obs, neg_act, right_act, left_act) of get_mirror_indices()")
     neg_obs, right_obs, left_obs, neg_act, right_act, left_act = mirror_indices
@@ -61,6 +63,13 @@ def mirror_tables(mirror_indices, obs_dim: int, act_dim: int, scan_points=None):
             raise ValueError(f"scan point {p} ({pts[p, 0]:g}, {pts[p, 1]:g}) has no reflection ({pts[p, 0]:g}, {-pts[p, 1]:g}) in the pattern")
         in_perm = np.concatenate([in_perm, (int(obs_dim) + scan_perm).astype(np.int32)])
         in_sign = np.concatenate([in_sign, np.ones(len(pts), np.float32)])
+    if depth_shape is not None:
+        if len(tuple(depth_shape)) != 2 or any(int(v) != v or int(v) < 1 for v in depth_shape):
+            raise ValueError("depth_shape must be (height, width), both at least 1")
+        H, W = (int(v) for v in depth_shape)
+        flip = (np.arange(H)[:, None] * W + (W - 1 - np.arange(W))[None, :]).reshape(-1)
+        in_perm = np.concatenate([in_perm, (len(in_perm) + flip).astype(np.int32)])
+        in_sign = np.concatenate([in_sign, np.ones(H * W, np.float32)])
     return check_tables((in_perm, in_sign, act_perm, act_sign))
 
 

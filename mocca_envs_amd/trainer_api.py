@@ -194,6 +194,9 @@ class TorchVecEnv:
     [obs | scan] -- the step kernel's launch, then ONE more (include/mocca.h mocca_height_scan, which copies the observation into the wide row
     itself): no torch.cat, no copy or synchronise on the host.  Under auto-reset the scan, like the observation, belongs to the new episode's
     first state.
+    `depth_camera=perception.DepthCamera(...)` appends the egocentric depth image (include/mocca.h mocca_depth_camera) the same way:
+    `observation_space` grows by width * height, rows are [obs | depth] -- or [obs | scan | depth] with a height scan too, one more launch
+    each -- in reset() / step() / step(into=...) / capture_rollout and as act_step()'s input rows.
     `terrain_bank=dict(n_fields=K, seed=S, n_peaks=256, gain=1.0, redraw_at_reset=True)` (planner ids): a bank of K random height fields of
     the shipped shape (128 x 128 points, 4 per metre) generated on the device before the first reset (include/mocca.h
     mocca_generate_heightfields), every env on one of them -- with `redraw_at_reset` another one in every episode; refresh_terrain(seed)
@@ -201,7 +204,13 @@ class TorchVecEnv:
 
     def __init__(self, env_id: str, num_envs: int, seed: int = 0, device: Optional[int] = None, sub_batches: int = 1,
                  terminal_observation: bool = False, record_slots: int = 8, eager_done: bool = False, record_events: bool = True,
-                 height_scan: Optional[dict] = None, terrain_bank: Optional[dict] = None, **kw):
+                 height_scan: Optional[dict] = None, terrain_bank: Optional[dict] = None, depth_camera=None, **kw):
+        if depth_camera is not None and terminal_observation:
+            raise NotImplementedError("depth_camera with terminal_observation=True: the camera runs after the step's launch, when an env that "
+                                      "finished already holds its next episode's first state -- the terminal state is gone, so no image can be "
+                                      "appended to the terminal observation")
+        if depth_camera is not None and sub_batches > 1:
+            raise NotImplementedError("depth_camera needs one handle (sub_batches=1)")
         if height_scan is not None and terminal_observation:
             raise NotImplementedError("height_scan with terminal_observation=True: the scan runs after the step's launch, when an env that finished "
                                       "already holds its next episode's first state -- the terminal state is gone, so no scan can be appended to "
@@ -231,8 +240,15 @@ class TorchVecEnv:
                 raise NotImplementedError("height_scan needs one handle (one device, sub_batches=1)")
             self.venv.set_height_scan(**height_scan)
             self._scan = self.venv.scan_dim
-            self._wide = torch.zeros(self.num_envs, self.venv.obs_dim + self._scan, dtype=torch.float32, device=self.device)
-        high = np.inf * np.ones(self.venv.obs_dim + self._scan, dtype=np.float32)
+        self._depth = 0
+        if depth_camera is not None:
+            if not hasattr(self.venv, "lib"):
+                raise NotImplementedError("depth_camera needs one handle (one device, sub_batches=1)")
+            self.venv.set_depth_camera(depth_camera)
+            self._depth = self.venv.depth_dim
+        if self._scan or self._depth:
+            self._wide = torch.zeros(self.num_envs, self.venv.obs_dim + self._scan + self._depth, dtype=torch.float32, device=self.device)
+        high = np.inf * np.ones(self.venv.obs_dim + self._scan + self._depth, dtype=np.float32)
         self.observation_space = gym_shim.Box(-high, high, dtype=np.float32)                      # robots.py:18-29, env_locomotion.py:58-60
         self.action_space = gym_shim.Box(-np.ones(self.venv.act_dim, np.float32), np.ones(self.venv.act_dim, np.float32), dtype=np.float32)
         # a planner env with its base controller attached (base_controller=...): the action is the 15-number plan (unbounded box,
@@ -299,22 +315,32 @@ class TorchVecEnv:
     # ---- the VecPyTorch surface ----
     def reset(self) -> torch.Tensor:
         obs = self.venv.reset()        # (the reset kernel zeroes the envs' running returns: Monitor.reset)
-        return self.venv.height_scan(out=self._wide, obs=obs) if self._scan else obs
+        return obs if self._wide is None else self._widen(obs, self._wide)
+
+    def _widen(self, obs, wide):
+        """the wide row [obs | scan | depth] into `wide`: one launch per sensor, the first of them copies the observation"""
+        if self._scan:
+            self.venv.height_scan(out=wide, obs=obs)
+            if self._depth:
+                self.venv.depth_camera(out=wide[:, self.venv.obs_dim + self._scan:])
+        else:
+            self.venv.depth_camera(out=wide, obs=obs)
+        return wide
 
     def _step_obs(self, actions, obs_out=None, rew_out=None, launch=None):
-        """the step's launch and, with a height scan, the launch that writes the wide row [obs | scan] (into `obs_out` or this object's own
-        buffer; the step's own observation stays in the handle's buffer) -> (obs, reward).  `launch`: what steps instead of step() /
+        """the step's launch and, with a height scan or a depth camera, the launches that write the wide row [obs | scan | depth] (into
+        `obs_out` or this object's own buffer; the step's own observation stays in the handle's buffer) -> (obs, reward).  `launch`: what steps instead of step() /
         plan_step() (act_step: `actions` is then the policy's input row)"""
         launch = launch or self._venv_step
-        if not self._scan:
+        if self._wide is None:
             if obs_out is None and rew_out is None:      # (the sub-batched step takes the actions only)
                 return launch(actions)[:2]
             return launch(actions, obs_out=obs_out, rew_out=rew_out)[:2]
         wide = self._wide if obs_out is None else obs_out
         if wide.shape != self._wide.shape or not wide.is_contiguous():
-            raise ValueError("with a height scan the observation rows are contiguous float32 [n_envs, obs_dim + scan_dim]")
+            raise ValueError("with a height scan or a depth camera the observation rows are contiguous float32 [n_envs, obs_dim + scan_dim + depth_dim]")
         o, r = launch(actions, rew_out=rew_out)[:2]
-        return self.venv.height_scan(out=wide, obs=o), r
+        return self._widen(o, wide), r
 
     def step(self, actions: torch.Tensor, into: Optional[dict] = None):
         """`into` (one handle only): {"obs": [N, obs_dim], "reward": [N, 1], "masks": [N, 1], "bad_masks": [N, 1]} -- any subset -- tensors of the
@@ -356,7 +382,7 @@ class TorchVecEnv:
 
     # ---- the trainer's own policy on the device (VecEnv.set_policy / act_step, include/mocca.h mocca_act_step) ----
     def attach_policy(self, policy) -> None:
-        """Attach a `policy.DevicePolicy` whose input is this env's observation row ([obs | scan] with a height scan) and whose actions are
+        """Attach a `policy.DevicePolicy` whose input is this env's observation row ([obs | scan | depth] with a height scan / a depth camera) and whose actions are
         the env's -- on a planner env with its base controller the 15-number plans, and act_step() goes policy -> base controller -> step
         (VecEnv.act_plan_step); `update_policy(policy_or_flat_tensor)` refreshes its weights once per PPO iteration.  One handle only.  A
         policy with mirror tables (`symmetric_policy(p)`, `DevicePolicy(symmetry=)`) acts as the symmetric network: the tables cover the
@@ -450,7 +476,7 @@ class TorchVecEnv:
         step()'s.  The noise comes from the kernel (seed, env, the env's step and episode counters)."""
         launch = self._act_launch(into)
         if obs is None:
-            obs = self._wide if self._scan else self.venv.obs
+            obs = self.venv.obs if self._wide is None else self._wide
         return self._step(obs, into, launch)
 
     def capture_rollout(self, policy=None, num_steps: int = 1, sink=None, warmup: int = 2, into=None):
@@ -479,7 +505,7 @@ class TorchVecEnv:
             if self.rollout_terminal_obs is None:
                 self.rollout_terminal_obs = torch.zeros_like(self._term_bufs[0])
             self._attach_terminal(self.rollout_terminal_obs)
-        obs, rew = (self._wide if self._scan else venv.obs), self._rew2
+        obs, rew = (venv.obs if self._wide is None else self._wide), self._rew2
         if policy is None:
             act_of = None
         elif len(inspect.signature(policy).parameters) >= 2:        # policy(obs, t): e.g. to write its action into the storage's row t

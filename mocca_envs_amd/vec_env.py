@@ -447,19 +447,31 @@ class VecEnv:
 
     def policy_mirror_tables(self, policy):
         """The mirror tables (in_perm, in_sign, act_perm, act_sign) of THIS env for `policy` (a `policy.DevicePolicy`): built from
-        get_mirror_indices() and, where the policy's input is [obs | scan], the attached scan pattern (symmetry.mirror_tables).  Envs whose
+        get_mirror_indices() and, where the policy's input is [obs | scan], [obs | depth] or [obs | scan | depth], the attached scan pattern and
+        the attached depth camera's shape (symmetry.mirror_tables; ValueError for a camera outside the robot's sagittal plane).  Envs whose
         reference publishes no six index lists raise NotImplementedError."""
         from .symmetry import mirror_tables
         mi = self.get_mirror_indices()
         if isinstance(mi, dict):
             raise NotImplementedError("the Cassie mocap envs publish a dict of index lists (env_cassie.py:554-571), not get_mirror_indices()'s six")
-        scan = getattr(self, "_scan_points", None)
-        if policy.in_dim == self.obs_dim:
+        scan, cam = getattr(self, "_scan_points", None), getattr(self, "_depth_cam", None)
+        ns, nd = (0 if scan is None else len(scan)), (0 if cam is None else cam.width * cam.height)
+        if policy.in_dim == self.obs_dim:                                       # [obs]
+            scan = cam = None
+        elif scan is not None and cam is not None and ns == nd and policy.in_dim == self.obs_dim + ns:
+            raise ValueError(f"the policy's input has {policy.in_dim} entries: [obs | scan] and [obs | depth] are both {self.obs_dim} + {ns} wide here; "
+                             "detach the sensor the policy does not read (set_height_scan(None) / set_depth_camera(None))")
+        elif scan is not None and policy.in_dim == self.obs_dim + ns:           # [obs | scan]
+            cam = None
+        elif cam is not None and policy.in_dim == self.obs_dim + nd:            # [obs | depth]
             scan = None
-        elif scan is None or policy.in_dim != self.obs_dim + len(scan):
+        elif cam is None or policy.in_dim != self.obs_dim + ns + nd:            # [obs | scan | depth]
             raise ValueError(f"the policy's input has {policy.in_dim} entries, the env's observation {self.obs_dim}"
-                             + ("" if scan is None else f" and its height scan {len(scan)}"))
-        return mirror_tables(mi, self.obs_dim, policy.act_dim, scan_points=scan)
+                             + ("" if scan is None else f", its height scan {ns}") + ("" if cam is None else f", its depth image {nd}"))
+        if cam is not None and not cam.sagittal:
+            raise ValueError("the depth camera does not lie in the robot's sagittal plane (body 0, offset[1] == 0, yaw == roll == 0): "
+                             "the mirrored robot does not see the column-flipped image")
+        return mirror_tables(mi, self.obs_dim, policy.act_dim, scan_points=scan, depth_shape=None if cam is None else cam.shape)
 
     def symmetric_policy(self, policy):
         """A copy of `policy` (a `policy.DevicePolicy`) with the mirror tables of THIS env (policy_mirror_tables)."""
@@ -1063,6 +1075,58 @@ class VecEnv:
         self._in()
         _lib.check(self.lib.mocca_height_scan(self.h, C.c_void_p(out.data_ptr()), int(stride), None if obs is None else C.c_void_p(obs.data_ptr()),
                                               self._stream()), self.h)
+        self._out()
+        return out if out.shape[1] == width else out[:, :width]
+
+    # ---- the egocentric depth camera (include/mocca.h mocca_set_depth_camera / mocca_depth_camera) ----
+    @property
+    def depth_dim(self) -> int:
+        """pixels of the attached depth camera, 0 when there is none"""
+        return int(self.lib.mocca_depth_dim(self.h))
+
+    @property
+    def depth_shape(self):
+        """(height, width) of the attached depth camera, None when there is none"""
+        cam = getattr(self, "_depth_cam", None)
+        return None if cam is None else cam.shape
+
+    def set_depth_camera(self, cam) -> None:
+        """Attach a `perception.DepthCamera` (None detaches).  Nothing is allocated and nothing synchronises."""
+        if cam is None:
+            _lib.check(self.lib.mocca_set_depth_camera(self.h, 0, None, 0, 0, 0.0, 0.0, 0.0, 0), self.h)
+            self._depth_cam = None
+            return
+        a = cam.pack()
+        mount = np.ascontiguousarray(a["mount"], np.float32)
+        _lib.check(self.lib.mocca_set_depth_camera(self.h, a["body"], mount.ctypes.data_as(C.c_void_p), a["width"], a["height"], a["fov_y"],
+                                                   a["near"], a["far"], a["flags"]), self.h)
+        self._depth_cam = cam                # symmetric_policy() mirrors the image
+
+    def depth_camera(self, out: Optional[torch.Tensor] = None, obs: Optional[torch.Tensor] = None,
+                     cameras_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The depth image of the state the handle holds: float32 [N, H * W] on the device (row e reshapes to depth_shape), one launch,
+        nothing synchronises.  `out` and `obs` as in height_scan(): with `obs` the rows are [obs | depth].  `cameras_out`: a contiguous
+        float32 [N, CAMERA_FLOATS] tensor on the device that receives the camera records the rays were cast from (render() takes them)."""
+        p = self.depth_dim
+        if p == 0:
+            raise _lib.MoccaError("depth_camera needs a camera (set_depth_camera)")
+        width = p
+        if obs is not None:
+            if obs.shape != (self.n_envs, self.obs_dim) or obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device:
+                raise ValueError("obs must be a contiguous float32 [n_envs, obs_dim] tensor on the env's device")
+            width += self.obs_dim
+        if out is None:
+            out = torch.empty(self.n_envs, width, dtype=torch.float32, device=self.device)
+        elif out.dim() != 2 or out.shape[0] != self.n_envs or out.shape[1] < width or out.dtype != torch.float32 or out.device != self.device \
+                or out.stride(1) != 1 or (self.n_envs > 1 and out.stride(0) < out.shape[1]):
+            raise ValueError(f"out must be a float32 [n_envs, >= {width}] tensor on the env's device with contiguous rows")
+        if cameras_out is not None and (tuple(cameras_out.shape) != (self.n_envs, _lib.CAMERA_FLOATS) or cameras_out.dtype != torch.float32
+                                        or not cameras_out.is_contiguous() or cameras_out.device != self.device):
+            raise ValueError(f"cameras_out must be a contiguous float32 [n_envs, {_lib.CAMERA_FLOATS}] tensor on the env's device")
+        stride = out.stride(0) if self.n_envs > 1 else max(out.stride(0), width)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        self._in()
+        _lib.check(self.lib.mocca_depth_camera(self.h, ptr(out), int(stride), ptr(obs), ptr(cameras_out), self._stream()), self.h)
         self._out()
         return out if out.shape[1] == width else out[:, :width]
 

@@ -10,13 +10,16 @@ No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it Symme
 
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
                            [--device-policy [--device-returns [--device-grad [--device-update]]]] [--symmetric | --mirror-loss COEF | --mirror-dup]
-                           [--base-controller FILE] [--height-scan NX,NY]
+                           [--base-controller FILE] [--height-scan NX,NY] [--depth-camera W,H]
 --base-controller FILE (required for the planner ids, Walker3DPlannerEnv-v0 / MikePlannerEnv-v0): ALLSTEPS's second step.  FILE is a
 `BaseController.save_npz` file or the <out>_policy.npz of an earlier run of this script on a Stepper id (told apart by the keys; the latter
 brings its observation statistics along); it is frozen as the env's base controller and the policy trained here emits 15-number plans.
 Every --device-* flag works: collection is then `act_plan_step`, policy -> base controller -> step, three launches per step.
 --height-scan NX,NY: the observation row becomes [obs | scan], a `perception.scan_grid` of NX x NY terrain heights over 0 .. 2 m ahead and
 -0.5 .. 0.5 m sideways, through `make_vec_envs(height_scan=...)`: a planner that cannot see the height field has nothing to plan on.
+--depth-camera W,H: an egocentric depth image of W x H pixels is appended, [obs | depth] or [obs | scan | depth]: a `perception.DepthCamera` on
+the base, 0.15 m ahead of and 0.10 m above its origin, pitched 35 degrees down, 90 degrees of vertical field, 0.05 .. 6 m, rigidly mounted and
+blind to the robot's own links, through `make_vec_envs(depth_camera=...)`.  Rows wider than the device policy's 336 inputs are refused.
 --device-policy: collection runs through `envs.act_step(obs[t], into=...)` -- the policy kernel (normalisation, both nets, the sample, its
 log-probability, the value) and the step kernel, two launches per step and no torch op; `envs.update_policy(flat)` once per iteration hands the
 kernel the optimiser's new weights and the running observation statistics.  The noise then comes from the kernel, not from torch.randn.
@@ -90,6 +93,7 @@ def main():
     ap.add_argument("--mirror-dup", action="store_true", help="SymmetricRL's duplicated tuples: train on every row and its mirror image; not with --symmetric or --mirror-loss")
     ap.add_argument("--base-controller", default=None, metavar="FILE", help="the planner ids' frozen base controller: a BaseController.save_npz file or this script's policy file of a Stepper run")
     ap.add_argument("--height-scan", default=None, metavar="NX,NY", help="append a scan_grid of NX x NY terrain heights (0 .. 2 m ahead, -0.5 .. 0.5 m sideways) to the observation row")
+    ap.add_argument("--depth-camera", default=None, metavar="W,H", help="append a W x H depth image from a forward camera on the base, pitched 35 degrees down, to the observation row")
     ap.add_argument("--terrain-bank", type=int, default=0, metavar="K", help="planner ids: train on a bank of K random height fields generated on the device, another one in every episode (0: the shipped map)")
     ap.add_argument("--terrain-seed", type=int, default=0, metavar="S", help="seed of the terrain bank")
     ap.add_argument("--terrain-refresh", type=int, default=0, metavar="M", help="regenerate the bank every M iterations with seed S + iteration (0: never)")
@@ -133,11 +137,17 @@ def main():
         from mocca_envs_amd.perception import scan_grid
         nx, ny = (int(v) for v in args.height_scan.split(","))
         extra["height_scan"] = dict(points=scan_grid((0.0, 2.0), (-0.5, 0.5), nx, ny))
+    if args.depth_camera is not None:
+        from mocca_envs_amd.perception import DepthCamera
+        cw, ch = (int(v) for v in args.depth_camera.split(","))
+        extra["depth_camera"] = DepthCamera(offset=(0.15, 0.0, 0.10), pitch=-35.0, fov_y=90.0, near=0.05, far=6.0, width=cw, height=ch)
     if args.terrain_bank:
         extra["terrain_bank"] = dict(n_fields=args.terrain_bank, seed=args.terrain_seed, gain=args.terrain_gain, redraw_at_reset=True)
     envs = make_vec_envs(args.env_id, seed=args.seed, num_processes=args.envs, record_events=False, **extra)
     dev, N, T = envs.device, args.envs, args.steps
     od, ad = envs.observation_space.shape[0], envs.action_space.shape[0]
+    if args.depth_camera is not None and od > 336:
+        raise SystemExit(f"--depth-camera {args.depth_camera}: the observation row would have {od} entries, the policy kernel takes at most 336")
 
     def mlp(i, o, gain):
         net = nn.Sequential(nn.Linear(i, 256), nn.Tanh(), nn.Linear(256, 256), nn.Tanh(), nn.Linear(256, o)).to(dev)
