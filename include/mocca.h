@@ -814,6 +814,69 @@ int mocca_ppo_update(mocca_handle h, const float *obs_dev, int obs_stride, const
                      float *params_dev, size_t n_floats, int64_t n_params, float *moments_dev, double *clock_dev, double lr,
                      double beta1, double beta2, double eps, double max_grad_norm, uint64_t seed, float *stats_dev, void *stream);
 
+/* mocca_distill_grad  a regression (behaviour-cloning / DAgger) minibatch step on mocca_ppo_grad's machinery: the loss
+ *                       L = distill_coef 1/(B A) sum_rows sum_j (mu_j - t_j)^2 + value_coef 0.5 mean_rows (v - vt)^2
+ *                   -- torch's `distill_coef * (mean - target).pow(2).mean() + value_coef * 0.5 * (v - vt).pow(2).mean()` -- and its gradient
+ *                   with respect to every parameter of the PLAIN policy, in the same four launches.  obs_dev, obs_stride, idx_dev (NOT
+ *                   range-checked), n_rows = B, grad_dev's order and the forward (tanh rounded once) are mocca_ppo_grad's.  target_dev
+ *                   [R][act_dim] f32: the actions to regress the actor's mean mu onto (a teacher's means, a controller's outputs);
+ *                   value_target_dev [R] f32 or NULL: what the critic regresses onto.  Per row, each line ONE IEEE f32 operation in this
+ *                   order, never contracted into an FMA (A = act_dim, t the row's targets):
+ *                       ib = 1.0f / f32(B);  ia = 1.0f / f32(A);  k2 = f32(2 * distill_coef)   (the product in double)
+ *                       for j ascending:   d = mu[j] - t[j];  q = d * d;  m = m + f64(q)
+ *                                          u = d * ib;  u = u * ia;  dL/dmu[j] = u * k2
+ *                       the row's distillation term = f32(m) * ia
+ *                       value_target given:  e = v - vt;  l = e * e;  value loss = 0.5f * l;  dv = f32(value_coef) * e;  dL/dv = dv * ib
+ *                       value_target NULL:   value loss = 0, dL/dv = 0: every entry of the critic's gradient is then exactly +0
+ *                   log_std takes no gradient: its entries of grad_dev are exactly +0.0f.  Through the layers and in the sums the
+ *                   arithmetic is mocca_ppo_grad's.  grad_dev [n_head] is fully overwritten.  stats_dev [8] f32 or NULL: 0, L_v, H as
+ *                   mocca_ppo_grad forms it, 0, 0, the sum of grad_dev^2, 0, L_d = mean_rows mean_j (mu_j - t_j)^2 (the rows' terms
+ *                   summed in f64 within a row chunk, the chunks' sums added in chunk order, times ib).
+ *                   The scratch is mocca_ppo_grad's own (one buffer in the handle serves both calls; the same size for the same B), the
+ *                   bound on n_rows 2^22, and mocca_ppo_grad's conditions hold as they stand: a call that grows the scratch FREES the old
+ *                   one and may synchronise; every other call is asynchronous on `stream` and capturable after one warm call with the
+ *                   same B; it reads the image mocca_update_policy last wrote and writes only grad_dev, stats_dev and its scratch.
+ * Errors (MOCCA_E_ARG, with a message; the handle is left as it was): a NULL handle; called before mocca_set_policy / mocca_update_policy; a
+ * NULL obs_dev, target_dev or grad_dev; n_rows < 1 or > 2^22; obs_stride < in_dim; a non-finite or negative distill_coef or value_coef; a
+ * handle with ANY mirror attachment (mocca_set_policy_symmetry, mocca_set_policy_mirror_loss, mocca_set_policy_mirror_dup) -- detach it:
+ * distilling into a symmetric network is not provided. */
+int mocca_distill_grad(mocca_handle h, const float *obs_dev, int obs_stride, const float *target_dev, const float *value_target_dev,
+                       const int64_t *idx_dev, int64_t n_rows, double distill_coef, double value_coef, float *grad_dev, float *stats_dev,
+                       void *stream);
+
+/* mocca_distill_update  mocca_ppo_update's loop around mocca_distill_grad: `epochs` passes over R = n_rollout_rows stored rows, each a fresh
+ *                   shuffle (the same Feistel permutation, keyed by `seed` and clock_dev[0] read on the device) cut into M = R / B
+ *                   minibatches of B = minibatch_rows rows, the remainder dropped; per minibatch the four launches of mocca_distill_grad
+ *                   with idx_dev = the permutation + u B and a handle-owned gradient, then mocca_adam_step's three launches.  Bit for
+ *                   bit what that sequence of calls gives.  obs_dev .. value_target_dev, distill_coef and value_coef are
+ *                   mocca_distill_grad's; params_dev .. max_grad_norm are mocca_adam_step's.  stats_dev [epochs M][8] f32 or NULL: row k
+ *                   holds the k-th minibatch's mocca_distill_grad statistics with [6] overwritten by the clip coefficient applied.
+ *                   mocca_ppo_update's conditions hold as they stand: a linear chain of epochs (1 + 7 M) launches, capturable after one
+ *                   warm call of the same shapes.
+ * Errors (MOCCA_E_ARG, with a message; the handle is left as it was and nothing is launched): those of mocca_adam_step and of
+ * mocca_distill_grad but for their grad_dev and idx_dev; minibatch_rows outside 1 .. n_rollout_rows; epochs < 1; n_rollout_rows < 1 or > 2^22. */
+int mocca_distill_update(mocca_handle h, const float *obs_dev, int obs_stride, const float *target_dev, const float *value_target_dev,
+                         int64_t n_rollout_rows, int64_t minibatch_rows, int epochs, double distill_coef, double value_coef,
+                         float *params_dev, size_t n_floats, int64_t n_params, float *moments_dev, double *clock_dev, double lr,
+                         double beta1, double beta2, double eps, double max_grad_norm, uint64_t seed, float *stats_dev, void *stream);
+
+/* mocca_set_teacher   a SECOND, independent policy image in the handle: a frozen teacher that labels the rows a student visits.  The layer
+ *                   table, in_dim, act_dim, clip and every shape check are mocca_set_policy's; layers_host NULL detaches.  The teacher may
+ *                   differ from the policy of mocca_set_policy in in_dim and in layers.  It takes no mirror attachment, and nothing done to
+ *                   it touches that policy, its mirror attachment, mocca_act's results or the gradient calls'.  May synchronise.
+ * mocca_update_teacher  the teacher's weights, as mocca_update_policy takes the policy's: params_dev of either length (with or without
+ *                   mean / inv_std), one repack launch on `stream`, nothing synchronises.
+ * mocca_teacher_act   the teacher's actor mean and value on n_rows rows in ONE launch of the policy kernel's plain instance, deterministic:
+ *                   the arithmetic of mocca_act with deterministic = 1 (with the same weights, the same bits).  in_dev [n_rows][in_stride]
+ *                   f32, the first in_dim floats of a row are read; n_rows is any count >= 1 (at most 2^22), not tied to n_envs: the
+ *                   deterministic path reads no env record.  mean_dev [n_rows][act_dim]; value_dev [n_rows] or NULL (the critic is then
+ *                   not run).  No allocation, no synchronisation, no host read: capturable.
+ * Errors (MOCCA_E_ARG, with a message): mocca_set_teacher / mocca_update_teacher: those of mocca_set_policy / mocca_update_policy.
+ * mocca_teacher_act: called before mocca_set_teacher and mocca_update_teacher; a NULL in_dev or mean_dev; in_stride < in_dim; n_rows < 1. */
+int mocca_set_teacher(mocca_handle h, const int32_t *layers_host, int n_layers_total, int in_dim, int act_dim, double clip);
+int mocca_update_teacher(mocca_handle h, const float *params_dev, size_t n_floats, void *stream);
+int mocca_teacher_act(mocca_handle h, const float *in_dev, int in_stride, int64_t n_rows, float *mean_dev, float *value_dev, void *stream);
+
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */
 int mocca_kernel_info(mocca_handle h, int *vgprs, int *sgprs, int *lds_bytes, int *scratch_bytes, int *max_blocks_per_cu);

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <new>
 #include <string>
@@ -164,17 +165,20 @@ struct mocca_ctx {
   DevBuf<float> d_base_act;          // [N][21] the actor's output of the last mocca_plan_step
   DevBuf<float> d_base_val;          // [N] the critic's
   DevBuf<float> d_ctrl_norm;         // mocca_set_base_controller_norm: mean [65] then inv_std [65]; ctrl.norm_mean / norm_inv_std point into it
-  // a trainer's policy (mocca_set_policy), owned by the handle
-  DevBuf<float> d_pol_image;         // the kernel's image (mocca_policy.h)
-  DevBuf<int32_t> d_pol_layers;
-  mocca_pol::PolicyArgs pol{};       // shapes and image offsets; the per-call pointers are filled by mocca_act
-  mocca_pol::RepackArgs pol_repack{};   // rows of the repack kernel; src offsets in the caller's flat parameters
-  size_t pol_n_base = 0;             // floats of mocca_update_policy's params_dev without the normalisation arrays
-  bool pol_filled = false;           // mocca_update_policy has run since mocca_set_policy
-  int pol_tail_row = 0;              // pol_repack's row of the flags; the rows of mean and inv_std follow it
-  std::vector<int32_t> pol_table;    // host copy of d_pol_layers (offsets into the image)
-  int pol_wt_off[mocca_ppo::PPO_MAX_TABLE] = {};   // the layers' transposed copies in the image (mocca_ppo.h), -1: none
-  // the policy's ONE mirror attachment (set_policy_mirror): the setters refuse a second kind, so the tables are held once
+  // a policy image and what describes it, owned by the handle.  Two slots: `student`, the trainer's policy (mocca_set_policy: mocca_act, the
+  // gradient and the optimiser calls), and `teacher`, a frozen second policy that only mocca_teacher_act evaluates (mocca_set_teacher)
+  struct PolicySlot {
+    DevBuf<float> d_pol_image;         // the kernel's image (mocca_policy.h)
+    DevBuf<int32_t> d_pol_layers;
+    mocca_pol::PolicyArgs pol{};       // shapes and image offsets; the per-call pointers are filled by mocca_act / mocca_teacher_act
+    mocca_pol::RepackArgs pol_repack{};   // rows of the repack kernel; src offsets in the caller's flat parameters
+    size_t pol_n_base = 0;             // floats of mocca_update_policy's params_dev without the normalisation arrays
+    bool pol_filled = false;           // mocca_update_policy / mocca_update_teacher has run since the slot was set
+    int pol_tail_row = 0;              // pol_repack's row of the flags; the rows of mean and inv_std follow it
+    std::vector<int32_t> pol_table;    // host copy of d_pol_layers (offsets into the image)
+    int pol_wt_off[mocca_ppo::PPO_MAX_TABLE] = {};   // the layers' transposed copies in the image (mocca_ppo.h), -1: none
+  } student, teacher;
+  // the student's ONE mirror attachment (set_policy_mirror): the setters refuse a second kind, so the tables are held once
   struct {
     mocca_ppo::PpoMode method = mocca_ppo::PPO_PLAIN;   // PPO_PLAIN: nothing attached.  PPO_SYM (mocca_set_policy_symmetry): pol.in_perm and its
                                      // kin point into the tables; PPO_MIRROR (.._mirror_loss) and PPO_DUP (.._mirror_dup): mocca_ppo_grad_mirror /
@@ -1279,21 +1283,25 @@ int mocca_depth_camera(mocca_handle h, float* out_dev, int row_stride, const flo
 static void drop_policy_mirror(mocca_handle h) {
   h->pol_mirror.perm.reset(); h->pol_mirror.sign.reset();
   h->pol_mirror.method = mocca_ppo::PPO_PLAIN; h->pol_mirror.coef = 0.0;
-  h->pol.in_perm = h->pol.act_perm = nullptr;
-  h->pol.in_sign = h->pol.act_sign = nullptr;
+  h->student.pol.in_perm = h->student.pol.act_perm = nullptr;
+  h->student.pol.in_sign = h->student.pol.act_sign = nullptr;
 }
 
-int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) try {
+// mocca_set_policy (the student's slot: the mirror attachment goes with the old shapes) and mocca_set_teacher (the teacher's): attach,
+// replace or (layers_host NULL) detach the slot's policy image.  A refused call leaves the handle as it was.
+static int set_policy_slot(mocca_handle h, const char* name, bool student, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim,
+                           double clip) try {
   using namespace mocca_pol;
   if (!h) return MOCCA_E_ARG;
+  mocca_ctx::PolicySlot& slot = student ? h->student : h->teacher;
   DeviceGuard guard(h->device);
   if (!layers_host) {   // detach
-    if (int rc = commit_ready(h, "mocca_set_policy")) return rc;
-    h->d_pol_image.reset(); h->d_pol_layers.reset(); h->pol_filled = false;
-    drop_policy_mirror(h);
+    if (int rc = commit_ready(h, name)) return rc;
+    slot.d_pol_image.reset(); slot.d_pol_layers.reset(); slot.pol_filled = false;
+    if (student) drop_policy_mirror(h);
     return MOCCA_OK;
   }
-  auto bad = [&](const std::string& what) { h->err = "mocca_set_policy: " + what; return MOCCA_E_ARG; };
+  auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
   if (in_dim < 1 || in_dim > POL_MAX_IN) return bad("in_dim must be 1 .. " + std::to_string(POL_MAX_IN));
   if (act_dim < 1 || act_dim > POL_MAX_ACTION) return bad("act_dim must be 1 .. " + std::to_string(POL_MAX_ACTION));
   if (!std::isfinite(clip) || !(clip > 0.0)) return bad("clip must be finite and positive");
@@ -1303,15 +1311,23 @@ int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_to
                                               "the actor ends in act_dim = " + std::to_string(act_dim) + " outputs, the critic in 1", count);
   if (!wrong.empty()) return bad(wrong);
   NetImage im;
-  if (int rc = commit_ready(h, "mocca_set_policy", build_image(im, layers_host, n_layers_total, count, in_dim, act_dim, true))) return rc;
-  h->d_pol_image.swap(im.image); h->d_pol_layers.swap(im.layers);
-  h->pol = im.pa; h->pol.clip = (float)clip;
-  h->pol_repack = im.rp; h->pol_n_base = im.n_src; h->pol_filled = false;
-  h->pol_tail_row = im.tail_row; h->pol_table.swap(im.table);
-  std::memcpy(h->pol_wt_off, im.wt_off, sizeof(im.wt_off));
-  drop_policy_mirror(h);   // the shapes may have changed
+  if (int rc = commit_ready(h, name, build_image(im, layers_host, n_layers_total, count, in_dim, act_dim, true))) return rc;
+  slot.d_pol_image.swap(im.image); slot.d_pol_layers.swap(im.layers);
+  slot.pol = im.pa; slot.pol.clip = (float)clip;
+  slot.pol_repack = im.rp; slot.pol_n_base = im.n_src; slot.pol_filled = false;
+  slot.pol_tail_row = im.tail_row; slot.pol_table.swap(im.table);
+  std::memcpy(slot.pol_wt_off, im.wt_off, sizeof(im.wt_off));
+  if (student) drop_policy_mirror(h);   // the shapes may have changed
   return MOCCA_OK;
-} catch (const std::bad_alloc&) { return out_of_host_memory(h, "mocca_set_policy"); }
+} catch (const std::bad_alloc&) { return out_of_host_memory(h, name); }
+
+int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) {
+  return set_policy_slot(h, "mocca_set_policy", true, layers_host, n_layers_total, in_dim, act_dim, clip);
+}
+
+int mocca_set_teacher(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) {
+  return set_policy_slot(h, "mocca_set_teacher", false, layers_host, n_layers_total, in_dim, act_dim, clip);
+}
 
 // The rules of one mirror table (mocca_policy.h: Symmetry): -> "" or what is wrong with the first entry that breaks one.
 static std::string check_mirror_table(const int32_t* perm, const float* sign, int dim, const char* perm_name, const char* sign_name) {
@@ -1333,7 +1349,7 @@ static std::string check_mirror_table(const int32_t* perm, const float* sign, in
 static std::string upload_mirror_tables(mocca_handle h, const int32_t* in_perm_host, const float* in_sign_host, const int32_t* act_perm_host,
                                         const float* act_sign_host, DevBuf<int32_t>& d_perm, DevBuf<float>& d_sign, hipError_t* e) {
   if (!in_sign_host || !act_perm_host || !act_sign_host) return "in_sign_host, act_perm_host and act_sign_host must not be NULL";
-  const int in_dim = h->pol.in_dim, act_dim = h->pol.act_dim;
+  const int in_dim = h->student.pol.in_dim, act_dim = h->student.pol.act_dim;
   std::string wrong = check_mirror_table(in_perm_host, in_sign_host, in_dim, "in_perm", "in_sign");
   if (wrong.empty()) wrong = check_mirror_table(act_perm_host, act_sign_host, act_dim, "act_perm", "act_sign");
   if (!wrong.empty()) return wrong;
@@ -1357,7 +1373,7 @@ static int set_policy_mirror(mocca_handle h, const char* name, mocca_ppo::PpoMod
   if (!h) return MOCCA_E_ARG;
   DeviceGuard guard(h->device);
   auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
-  if (!h->d_pol_image) return bad("needs a policy (mocca_set_policy)");
+  if (!h->student.d_pol_image) return bad("needs a policy (mocca_set_policy)");
   if (!in_perm_host) {   // detach
     if (int rc = commit_ready(h, name)) return rc;
     if (h->pol_mirror.method == method) drop_policy_mirror(h);
@@ -1383,9 +1399,9 @@ static int set_policy_mirror(mocca_handle h, const char* name, mocca_ppo::PpoMod
   h->pol_mirror.perm.swap(d_perm); h->pol_mirror.sign.swap(d_sign);
   h->pol_mirror.method = method; h->pol_mirror.coef = mirror_coef;
   if (method == PPO_SYM) {   // the policy kernel's symmetric instance runs from here on (launch_policy)
-    const int in_dim = h->pol.in_dim;
-    h->pol.in_perm = h->pol_mirror.perm; h->pol.act_perm = h->pol_mirror.perm.get() + in_dim;
-    h->pol.in_sign = h->pol_mirror.sign; h->pol.act_sign = h->pol_mirror.sign.get() + in_dim;
+    const int in_dim = h->student.pol.in_dim;
+    h->student.pol.in_perm = h->pol_mirror.perm; h->student.pol.act_perm = h->pol_mirror.perm.get() + in_dim;
+    h->student.pol.in_sign = h->pol_mirror.sign; h->student.pol.act_sign = h->pol_mirror.sign.get() + in_dim;
   }
   return MOCCA_OK;
 } catch (const std::bad_alloc&) { return out_of_host_memory(h, name); }
@@ -1405,54 +1421,85 @@ int mocca_set_policy_mirror_dup(mocca_handle h, const int32_t* in_perm_host, con
   return set_policy_mirror(h, "mocca_set_policy_mirror_dup", mocca_ppo::PPO_DUP, in_perm_host, in_sign_host, act_perm_host, act_sign_host, 0.0);
 }
 
-// what n_floats of a flat parameter tensor must be (mocca_update_policy, mocca_adam_step): -> "" or what is wrong
-static std::string check_n_floats(mocca_handle h, size_t n_floats) {
-  const size_t base = h->pol_n_base, in_dim = (size_t)h->pol.in_dim;
+// what n_floats of a flat parameter tensor must be (mocca_update_policy, mocca_update_teacher, mocca_adam_step): -> "" or what is wrong
+static std::string check_n_floats(const mocca_ctx::PolicySlot& slot, size_t n_floats) {
+  const size_t base = slot.pol_n_base, in_dim = (size_t)slot.pol.in_dim;
   if (n_floats == base || n_floats == base + 2 * in_dim) return "";
   return "this policy takes " + std::to_string(base) + " floats (layers, log_std), or " + std::to_string(base + 2 * in_dim) +
          " with mean and inv_std, not " + std::to_string(n_floats);
 }
 
-// the repack launch of mocca_update_policy; n_floats has been checked, the handle's device is current
-static void repack_policy(mocca_handle h, const float* params_dev, size_t n_floats, hipStream_t s) {
-  const size_t base = h->pol_n_base, in_dim = (size_t)h->pol.in_dim;
-  mocca_pol::RepackArgs rp = h->pol_repack;
+// the repack launch of mocca_update_policy / mocca_update_teacher; n_floats has been checked, the handle's device is current
+static void repack_policy(const mocca_ctx::PolicySlot& slot, const float* params_dev, size_t n_floats, hipStream_t s) {
+  const size_t base = slot.pol_n_base, in_dim = (size_t)slot.pol.in_dim;
+  mocca_pol::RepackArgs rp = slot.pol_repack;
   rp.src = params_dev;
   const bool norm = n_floats != base;
-  rp.rows[h->pol_tail_row].fill = norm ? 1.0f : 0.0f;
-  rp.rows[h->pol_tail_row + 1].src = norm ? (int32_t)base : -1;
-  rp.rows[h->pol_tail_row + 2].src = norm ? (int32_t)(base + in_dim) : -1;
+  rp.rows[slot.pol_tail_row].fill = norm ? 1.0f : 0.0f;
+  rp.rows[slot.pol_tail_row + 1].src = norm ? (int32_t)base : -1;
+  rp.rows[slot.pol_tail_row + 2].src = norm ? (int32_t)(base + in_dim) : -1;
   mocca_pol::launch_repack(s, rp);
 }
 
-int mocca_update_policy(mocca_handle h, const float* params_dev, size_t n_floats, void* stream) {
+// mocca_update_policy and mocca_update_teacher: new weights for the slot's image, one repack launch
+static int update_policy_slot(mocca_handle h, const char* name, const char* setter, bool student, const float* params_dev, size_t n_floats,
+                              void* stream) {
   if (!h) return MOCCA_E_ARG;
-  if (!h->d_pol_image) { h->err = "mocca_update_policy needs a policy (mocca_set_policy)"; return MOCCA_E_ARG; }
-  if (!params_dev) { h->err = "mocca_update_policy: params_dev must not be NULL"; return MOCCA_E_ARG; }
-  const std::string wrong = check_n_floats(h, n_floats);
-  if (!wrong.empty()) { h->err = "mocca_update_policy: " + wrong; return MOCCA_E_ARG; }
+  mocca_ctx::PolicySlot& slot = student ? h->student : h->teacher;
+  if (!slot.d_pol_image) { h->err = std::string(name) + " needs a policy (" + setter + ")"; return MOCCA_E_ARG; }
+  if (!params_dev) { h->err = std::string(name) + ": params_dev must not be NULL"; return MOCCA_E_ARG; }
+  const std::string wrong = check_n_floats(slot, n_floats);
+  if (!wrong.empty()) { h->err = std::string(name) + ": " + wrong; return MOCCA_E_ARG; }
   DeviceGuard guard(h->device);
-  repack_policy(h, params_dev, n_floats, (hipStream_t)stream);
+  repack_policy(slot, params_dev, n_floats, (hipStream_t)stream);
   HIP_TRY(h, hipGetLastError());
-  h->pol_filled = true;
+  slot.pol_filled = true;
+  return MOCCA_OK;
+}
+
+int mocca_update_policy(mocca_handle h, const float* params_dev, size_t n_floats, void* stream) {
+  return update_policy_slot(h, "mocca_update_policy", "mocca_set_policy", true, params_dev, n_floats, stream);
+}
+
+int mocca_update_teacher(mocca_handle h, const float* params_dev, size_t n_floats, void* stream) {
+  return update_policy_slot(h, "mocca_update_teacher", "mocca_set_teacher", false, params_dev, n_floats, stream);
+}
+
+// mocca_teacher_act: the teacher's slot through the policy kernel's plain instance, deterministic, over n_rows rows.  That path of the kernel
+// reads no env record and no noise; the mean IS the deterministic action, so mean_dev stands in the kernel's action output.
+int mocca_teacher_act(mocca_handle h, const float* in_dev, int in_stride, int64_t n_rows, float* mean_dev, float* value_dev, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  auto bad = [&](const std::string& what) { h->err = "mocca_teacher_act: " + what; return MOCCA_E_ARG; };
+  const mocca_ctx::PolicySlot& slot = h->teacher;
+  if (!slot.d_pol_image || !slot.pol_filled) return bad("needs a teacher (mocca_set_teacher, then mocca_update_teacher)");
+  if (!in_dev || !mean_dev) return bad("in_dev and mean_dev must not be NULL");
+  if (in_stride < slot.pol.in_dim)
+    return bad("in_stride " + std::to_string(in_stride) + " is smaller than the teacher's in_dim (" + std::to_string(slot.pol.in_dim) + ")");
+  if (n_rows < 1 || n_rows > mocca_ppo::PPO_MAX_ROWS) return bad("n_rows must be 1 .. 2^22, not " + std::to_string(n_rows));
+  DeviceGuard guard(h->device);
+  mocca_pol::PolicyArgs a = slot.pol;   // (a teacher has no mirror tables: the plain instance)
+  a.in = in_dev; a.in_stride = in_stride; a.eps = nullptr; a.deterministic = 1;
+  a.action = mean_dev; a.logp = nullptr; a.value = value_dev; a.mean = nullptr; a.n_envs = (int)n_rows;
+  mocca_pol::launch_policy((hipStream_t)stream, a);
+  HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
 }
 
 // the policy kernel's launch of mocca_act / mocca_act_step; the handle's device is current
 static int launch_act(mocca_handle h, const char* who, const float* in_dev, int in_stride, const float* eps_dev, int deterministic, float* action_dev,
                       float* logp_dev, float* value_dev, float* mean_dev, hipStream_t s) {
-  if (!h->d_pol_image || !h->pol_filled) {
+  if (!h->student.d_pol_image || !h->student.pol_filled) {
     h->err = std::string(who) + " needs a policy (mocca_set_policy, then mocca_update_policy)"; return MOCCA_E_ARG;
   }
   if (!in_dev || !action_dev) { h->err = std::string(who) + ": in_dev and action_dev must not be NULL"; return MOCCA_E_ARG; }
-  if (in_stride < h->pol.in_dim) {
-    h->err = std::string(who) + ": in_stride " + std::to_string(in_stride) + " is smaller than the policy's in_dim (" + std::to_string(h->pol.in_dim) + ")";
+  if (in_stride < h->student.pol.in_dim) {
+    h->err = std::string(who) + ": in_stride " + std::to_string(in_stride) + " is smaller than the policy's in_dim (" + std::to_string(h->student.pol.in_dim) + ")";
     return MOCCA_E_ARG;
   }
   if ((long long)h->env_offset + h->n_envs > (1ll << 28) || h->env_offset < 0) {
     h->err = std::string(who) + ": the noise is keyed by global env ids below 2^28 (MOCCA_PARAM_ENV_OFFSET + n_envs)"; return MOCCA_E_ARG;
   }
-  mocca_pol::PolicyArgs a = h->pol;
+  mocca_pol::PolicyArgs a = h->student.pol;
   a.in = in_dev; a.in_stride = in_stride; a.eps = eps_dev; a.deterministic = deterministic != 0;
   a.task = h->d_task; a.task_words = MOCCA_TASK_WORDS; a.tw_t = MOCCA_TW_T; a.tw_episode = MOCCA_TW_EPISODE;
   a.env_offset = h->env_offset; a.seed_lo = (uint32_t)h->seed; a.seed_hi = (uint32_t)(h->seed >> 32);
@@ -1473,8 +1520,8 @@ int mocca_act_step(mocca_handle h, const float* in_dev, int in_stride, const flo
                    float* value_dev, float* mean_dev, float* obs_dev, float* rew_dev, uint8_t* done_dev, int32_t* info_dev, void* stream) {
   if (!h) return MOCCA_E_ARG;
   if (!obs_dev || !rew_dev || !done_dev) { h->err = "mocca_act_step: obs_dev, rew_dev and done_dev must not be NULL"; return MOCCA_E_ARG; }
-  if (h->d_pol_image && h->pol.act_dim != mocca_act_dim(h)) {
-    h->err = "mocca_act_step: the policy's act_dim (" + std::to_string(h->pol.act_dim) + ") is not the env's (" + std::to_string(mocca_act_dim(h)) + ")";
+  if (h->student.d_pol_image && h->student.pol.act_dim != mocca_act_dim(h)) {
+    h->err = "mocca_act_step: the policy's act_dim (" + std::to_string(h->student.pol.act_dim) + ") is not the env's (" + std::to_string(mocca_act_dim(h)) + ")";
     return MOCCA_E_ARG;
   }
   if (need_attachments(h) != MOCCA_OK) return MOCCA_E_ARG;
@@ -1490,8 +1537,8 @@ int mocca_act_plan_step(mocca_handle h, const float* in_dev, int in_stride, cons
   if (h->task_id != MOCCA_TASK_WALKER3D_PLANNER) { h->err = "mocca_act_plan_step: only the planner task takes plans"; return MOCCA_E_ARG; }
   if (!obs_dev || !rew_dev || !done_dev) { h->err = "mocca_act_plan_step: obs_dev, rew_dev and done_dev must not be NULL"; return MOCCA_E_ARG; }
   if (!h->d_ctrl_image) { h->err = "mocca_act_plan_step needs a base controller (mocca_set_base_controller)"; return MOCCA_E_ARG; }
-  if (h->d_pol_image && h->pol.act_dim != mocca_ctrl::CTRL_PLAN) {
-    h->err = "mocca_act_plan_step: the policy's act_dim (" + std::to_string(h->pol.act_dim) + ") is not the plan's (" + std::to_string(mocca_ctrl::CTRL_PLAN) + ")";
+  if (h->student.d_pol_image && h->student.pol.act_dim != mocca_ctrl::CTRL_PLAN) {
+    h->err = "mocca_act_plan_step: the policy's act_dim (" + std::to_string(h->student.pol.act_dim) + ") is not the plan's (" + std::to_string(mocca_ctrl::CTRL_PLAN) + ")";
     return MOCCA_E_ARG;
   }
   if (need_attachments(h) != MOCCA_OK) return MOCCA_E_ARG;
@@ -1571,7 +1618,9 @@ int mocca_obs_stats(mocca_handle h, const float* rows_dev, int64_t n_rows, int r
 static mocca_ppo::PpoMode ppo_mode(mocca_handle h) { return h->pol_mirror.method; }
 
 // mocca_ppo_grad (PPO_PLAIN), mocca_ppo_grad_sym (PPO_SYM), mocca_ppo_grad_mirror (PPO_MIRROR) and mocca_ppo_grad_dup (PPO_DUP): one argument
-// list, one scratch, the same four launches; the last three share the two-column scratch layout (mocca_ppo.h)
+// list, one scratch, the same four launches; the last three share the two-column scratch layout (mocca_ppo.h).  mocca_distill_grad (PPO_DISTIL) is
+// the plain call with another head stage: action_dev carries the targets, returns_dev the value targets (or NULL) and `clip` distill_coef;
+// old_logp_dev, adv_dev and old_value_dev are not read.
 static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, const float* obs_dev, int obs_stride, const float* action_dev,
                     const float* old_logp_dev, const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev,
                     int64_t n_rows, double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev,
@@ -1580,9 +1629,14 @@ static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, c
   using namespace mocca_ppo;
   if (!h) { g_err = std::string(name) + ": NULL handle"; return MOCCA_E_ARG; }
   auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
-  if (!h->d_pol_image || !h->pol_filled) return bad("needs a policy (mocca_set_policy, then mocca_update_policy)");
-  const bool sym = mode != PPO_PLAIN;   // twice the columns
-  if (const PpoMode attached = ppo_mode(h); mode != attached) {   // the first of these that holds names the entry point to call instead
+  if (!h->student.d_pol_image || !h->student.pol_filled) return bad("needs a policy (mocca_set_policy, then mocca_update_policy)");
+  const bool distil = mode == PPO_DISTIL;
+  const bool sym = mode != PPO_PLAIN && !distil;   // twice the columns
+  if (const PpoMode attached = ppo_mode(h); distil) {
+    if (attached != PPO_PLAIN)
+      return bad(std::string("a mirror attachment is in place (") + (attached == PPO_SYM ? "mocca_set_policy_symmetry" : attached == PPO_MIRROR ? "mocca_set_policy_mirror_loss" : "mocca_set_policy_mirror_dup") +
+                 "): the regression gradient is the plain policy's, detach it first");
+  } else if (mode != attached) {   // the first of these that holds names the entry point to call instead
     if (attached == PPO_DUP)
       return bad("duplicated rows are attached: the gradient of PPO's loss over the rows and their mirror images is mocca_ppo_grad_dup (or detach them: mocca_set_policy_mirror_dup)");
     if (mode == PPO_DUP) return bad("needs duplicated rows attached (mocca_set_policy_mirror_dup); the plain loss's gradient is mocca_ppo_grad");
@@ -1593,24 +1647,26 @@ static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, c
       return bad("the policy has mirror tables attached: the symmetric policy's gradient is mocca_ppo_grad_sym (or detach the tables: mocca_set_policy_symmetry)");
     return bad("needs a policy with mirror tables attached (mocca_set_policy_symmetry); the plain policy's gradient is mocca_ppo_grad");
   }
-  if (!obs_dev || !action_dev || !old_logp_dev || !adv_dev || !returns_dev || !grad_dev)
+  if (distil && (!obs_dev || !action_dev || !grad_dev)) return bad("obs_dev, target_dev and grad_dev must not be NULL");
+  if (!distil && (!obs_dev || !action_dev || !old_logp_dev || !adv_dev || !returns_dev || !grad_dev))
     return bad("obs_dev, action_dev, old_logp_dev, adv_dev, returns_dev and grad_dev must not be NULL");
   if (value_clip && !old_value_dev) return bad("value_clip needs old_value_dev");
   if (n_rows < 1 || n_rows > (sym ? PPO_MAX_ROWS_SYM : PPO_MAX_ROWS)) return bad(std::string("n_rows must be 1 .. ") + (sym ? "2^21" : "2^22") + ", not " + std::to_string(n_rows));
-  if (obs_stride < h->pol.in_dim)
-    return bad("obs_stride " + std::to_string(obs_stride) + " is smaller than the policy's in_dim (" + std::to_string(h->pol.in_dim) + ")");
+  if (obs_stride < h->student.pol.in_dim)
+    return bad("obs_stride " + std::to_string(obs_stride) + " is smaller than the policy's in_dim (" + std::to_string(h->student.pol.in_dim) + ")");
   if (!std::isfinite(clip) || clip < 0.0 || !std::isfinite(value_coef) || value_coef < 0.0 || !std::isfinite(entropy_coef) || entropy_coef < 0.0)
-    return bad("clip, value_coef and entropy_coef must be finite and not negative");
+    return bad(distil ? "distill_coef and value_coef must be finite and not negative" : "clip, value_coef and entropy_coef must be finite and not negative");
   if (check_only) return MOCCA_OK;
   DeviceGuard guard(h->device);
   PpoArgs a{};
-  const mocca_pol::PolicyArgs& p = h->pol;
+  const mocca_pol::PolicyArgs& p = h->student.pol;
   a.params = p.params; a.layers = p.layers; a.n_actor = p.n_actor; a.n_critic = p.n_critic;
   a.log_std_off = p.log_std_off; a.flags_off = p.flags_off; a.mean_off = p.mean_off; a.inv_std_off = p.inv_std_off;
   a.in_dim = p.in_dim; a.in_pad = p.in_pad; a.act_dim = p.act_dim; a.norm_clip = p.clip;
-  std::memcpy(a.wt_off, h->pol_wt_off, sizeof(a.wt_off));
+  std::memcpy(a.wt_off, h->student.pol_wt_off, sizeof(a.wt_off));
   a.mode = mode;
-  if (mode != PPO_PLAIN) {
+  if (distil) a.mirror_k2 = (float)(2.0 * clip);   // f32(2 distill_coef), the product in double
+  if (sym) {
     a.in_perm = h->pol_mirror.perm; a.act_perm = h->pol_mirror.perm.get() + p.in_dim;
     a.in_sign = h->pol_mirror.sign; a.act_sign = h->pol_mirror.sign.get() + p.in_dim;
     a.mirror_k2 = (float)(2.0 * h->pol_mirror.coef);
@@ -1630,7 +1686,7 @@ static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, c
   int n_tiles = PPO_ROW_COLS / 16, n_head = p.act_dim;
   a.a0_off = pos; pos += bp * p.in_pad;
   for (int i = 0; i < n_layers; ++i) {
-    const int32_t* r = &h->pol_table[(size_t)i * CTRL_LAYER_WORDS];
+    const int32_t* r = &h->student.pol_table[(size_t)i * CTRL_LAYER_WORDS];
     a.a_off[i] = pos; pos += bp * r[CL_OUT_PAD];
     a.dz_off[i] = pos; pos += bp * r[CL_OUT_PAD];
     n_tiles += (r[CL_OUT_PAD] / 16) * (r[CL_IN_PAD] / 16) + r[CL_OUT_PAD] / 16;
@@ -1684,13 +1740,13 @@ static int adam_check(mocca_handle h, const char* name, const float* params_dev,
                       double max_grad_norm) {
   if (!h) { g_err = std::string(name) + ": NULL handle"; return MOCCA_E_ARG; }
   auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
-  if (!h->d_pol_image) return bad("needs a policy (mocca_set_policy)");
+  if (!h->student.d_pol_image) return bad("needs a policy (mocca_set_policy)");
   if (!params_dev || (need_grad && !grad_dev) || !moments_dev || !clock_dev)
     return bad(std::string("params_dev, ") + (need_grad ? "grad_dev, " : "") + "moments_dev and clock_dev must not be NULL");
-  const std::string wrong = check_n_floats(h, n_floats);
+  const std::string wrong = check_n_floats(h->student, n_floats);
   if (!wrong.empty()) return bad(wrong);
-  if (n_params < 1 || n_params > (int64_t)h->pol_n_base)
-    return bad("n_params must be 1 .. " + std::to_string(h->pol_n_base) + " (the floats ahead of mean / inv_std), not " + std::to_string(n_params));
+  if (n_params < 1 || n_params > (int64_t)h->student.pol_n_base)
+    return bad("n_params must be 1 .. " + std::to_string(h->student.pol_n_base) + " (the floats ahead of mean / inv_std), not " + std::to_string(n_params));
   if (!std::isfinite(lr) || lr < 0.0 || !std::isfinite(eps) || eps < 0.0) return bad("lr and eps must be finite and not negative");
   if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return bad("beta1 and beta2 must lie in [0, 1)");
   if (std::isnan(max_grad_norm) || max_grad_norm < 0.0) return bad("max_grad_norm must not be NaN or negative (0: no clip)");
@@ -1698,18 +1754,18 @@ static int adam_check(mocca_handle h, const char* name, const float* params_dev,
 }
 
 // f64 words of d_optim ahead of the permutation (mocca_optim.h: Scratch)
-static size_t optim_head_words(mocca_handle h) { return mocca_optim::OPT_REC_WORDS + (h->pol_n_base + 1) / 2; }
+static size_t optim_head_words(mocca_handle h) { return mocca_optim::OPT_REC_WORDS + (h->student.pol_n_base + 1) / 2; }
 
 // launches A, B and C of mocca_adam_step; the arguments have been checked, d_optim holds the record, the handle's device is current
 static void adam_launch(mocca_handle h, float* params_dev, size_t n_floats, const float* grad_dev, int64_t n_params, float* moments_dev,
                         double* clock_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm, float* stats_row, hipStream_t s) {
   mocca_optim::AdamArgs a{};
   a.params = params_dev; a.grad = grad_dev; a.n_params = (int)n_params;
-  a.m = moments_dev; a.v = moments_dev + h->pol_n_base; a.clock = clock_dev;
+  a.m = moments_dev; a.v = moments_dev + h->student.pol_n_base; a.clock = clock_dev;
   a.rec = (mocca_optim::AdamRecord*)h->d_optim.get();
   a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_grad_norm = max_grad_norm; a.stats = stats_row;
   mocca_optim::launch_adam(s, a);
-  repack_policy(h, params_dev, n_floats, s);
+  repack_policy(h->student, params_dev, n_floats, s);
 }
 
 int mocca_adam_step(mocca_handle h, float* params_dev, size_t n_floats, const float* grad_dev, int64_t n_params, float* moments_dev,
@@ -1720,21 +1776,25 @@ int mocca_adam_step(mocca_handle h, float* params_dev, size_t n_floats, const fl
   if (int rc = grow_scratch(h, "mocca_adam_step", h->d_optim, &h->optim_cap, optim_head_words(h))) return rc;
   adam_launch(h, params_dev, n_floats, grad_dev, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm, nullptr, (hipStream_t)stream);
   HIP_TRY(h, hipGetLastError());
-  h->pol_filled = true;
+  h->student.pol_filled = true;
   return MOCCA_OK;
 }
 
-int mocca_ppo_update(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev,
-                     const float* adv_dev, const float* returns_dev, const float* old_value_dev, int64_t n_rollout_rows,
-                     int64_t minibatch_rows, int epochs, double clip, double value_coef, double entropy_coef, int value_clip,
-                     float* params_dev, size_t n_floats, int64_t n_params, float* moments_dev, double* clock_dev, double lr,
-                     double beta1, double beta2, double eps, double max_grad_norm, uint64_t seed, float* stats_dev, void* stream) {
-  const char* name = "mocca_ppo_update";
-  if (int rc = adam_check(h, name, params_dev, n_floats, nullptr, false, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm))
-    return rc;
+int mocca_distill_grad(mocca_handle h, const float* obs_dev, int obs_stride, const float* target_dev, const float* value_target_dev,
+                       const int64_t* idx_dev, int64_t n_rows, double distill_coef, double value_coef, float* grad_dev, float* stats_dev,
+                       void* stream) {
+  return ppo_grad(h, "mocca_distill_grad", mocca_ppo::PPO_DISTIL, obs_dev, obs_stride, target_dev, nullptr, nullptr, value_target_dev, nullptr, idx_dev,
+                  n_rows, distill_coef, value_coef, 0.0, 0, grad_dev, stats_dev, stream);
+}
+
+// The body of mocca_ppo_update and mocca_distill_update: epochs x (n_rollout_rows / minibatch_rows) minibatches of [shuffle once per epoch,
+// the gradient, launches A .. C of mocca_adam_step].  `grad_of(idx, grad, stats_row, check_only)` is the gradient call on minibatch_rows rows;
+// asked with check_only it only refuses.  `sym`: the gradient call's scratch has two rows per minibatch row, which halves the row bound.
+using UpdateGrad = std::function<int(const int64_t* idx, float* grad, float* stats_row, bool check_only)>;
+static int update_loop(mocca_handle h, const char* name, bool sym, int64_t n_rollout_rows, int64_t minibatch_rows, int epochs, float* params_dev,
+                       size_t n_floats, int64_t n_params, float* moments_dev, double* clock_dev, double lr, double beta1, double beta2, double eps,
+                       double max_grad_norm, uint64_t seed, float* stats_dev, void* stream, const UpdateGrad& grad_of) {
   auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
-  const mocca_ppo::PpoMode mode = ppo_mode(h);   // one entry point: the handle's attachments decide, as VecEnv.ppo_grad does
-  const bool sym = mode != mocca_ppo::PPO_PLAIN;
   const long long most = sym ? mocca_ppo::PPO_MAX_ROWS_SYM : mocca_ppo::PPO_MAX_ROWS;
   if (n_rollout_rows < 1 || n_rollout_rows > most)
     return bad(std::string("n_rollout_rows must be 1 .. ") + (sym ? "2^21" : "2^22") + ", not " + std::to_string(n_rollout_rows));
@@ -1742,8 +1802,7 @@ int mocca_ppo_update(mocca_handle h, const float* obs_dev, int obs_stride, const
     return bad("minibatch_rows must be 1 .. n_rollout_rows (" + std::to_string(n_rollout_rows) + "), not " + std::to_string(minibatch_rows));
   if (epochs < 1) return bad("epochs must be at least 1, not " + std::to_string(epochs));
   float* const unset = params_dev;   // stands for grad_dev in the check: the gradient buffer is the handle's
-  if (int rc = ppo_grad(h, name, mode, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, nullptr, minibatch_rows,
-                        clip, value_coef, entropy_coef, value_clip, unset, nullptr, stream, true)) return rc;
+  if (int rc = grad_of(nullptr, unset, nullptr, true)) return rc;
   DeviceGuard guard(h->device);
   const size_t head = optim_head_words(h);
   if (int rc = grow_scratch(h, name, h->d_optim, &h->optim_cap, head + (size_t)n_rollout_rows)) return rc;
@@ -1757,13 +1816,44 @@ int mocca_ppo_update(mocca_handle h, const float* obs_dev, int obs_stride, const
     mocca_optim::launch_shuffle((hipStream_t)stream, sh);
     for (int64_t u = 0; u < per_epoch; ++u) {
       float* const row = stats_dev ? stats_dev + 8 * ((size_t)ep * per_epoch + u) : nullptr;
-      if (int rc = ppo_grad(h, name, mode, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev,
-                            perm + u * minibatch_rows, minibatch_rows, clip, value_coef, entropy_coef, value_clip, grad, row, stream)) return rc;
+      if (int rc = grad_of(perm + u * minibatch_rows, grad, row, false)) return rc;
       adam_launch(h, params_dev, n_floats, grad, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm, row, (hipStream_t)stream);
     }
   }
   HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
+}
+
+int mocca_ppo_update(mocca_handle h, const float* obs_dev, int obs_stride, const float* action_dev, const float* old_logp_dev,
+                     const float* adv_dev, const float* returns_dev, const float* old_value_dev, int64_t n_rollout_rows,
+                     int64_t minibatch_rows, int epochs, double clip, double value_coef, double entropy_coef, int value_clip,
+                     float* params_dev, size_t n_floats, int64_t n_params, float* moments_dev, double* clock_dev, double lr,
+                     double beta1, double beta2, double eps, double max_grad_norm, uint64_t seed, float* stats_dev, void* stream) {
+  const char* name = "mocca_ppo_update";
+  if (int rc = adam_check(h, name, params_dev, n_floats, nullptr, false, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm))
+    return rc;
+  const mocca_ppo::PpoMode mode = ppo_mode(h);   // one entry point: the handle's attachments decide, as VecEnv.ppo_grad does
+  return update_loop(h, name, mode != mocca_ppo::PPO_PLAIN, n_rollout_rows, minibatch_rows, epochs, params_dev, n_floats, n_params, moments_dev,
+                     clock_dev, lr, beta1, beta2, eps, max_grad_norm, seed, stats_dev, stream,
+                     [&](const int64_t* idx, float* grad, float* stats_row, bool check_only) {
+                       return ppo_grad(h, name, mode, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, idx,
+                                       minibatch_rows, clip, value_coef, entropy_coef, value_clip, grad, stats_row, stream, check_only);
+                     });
+}
+
+int mocca_distill_update(mocca_handle h, const float* obs_dev, int obs_stride, const float* target_dev, const float* value_target_dev,
+                         int64_t n_rollout_rows, int64_t minibatch_rows, int epochs, double distill_coef, double value_coef, float* params_dev,
+                         size_t n_floats, int64_t n_params, float* moments_dev, double* clock_dev, double lr, double beta1, double beta2, double eps,
+                         double max_grad_norm, uint64_t seed, float* stats_dev, void* stream) {
+  const char* name = "mocca_distill_update";
+  if (int rc = adam_check(h, name, params_dev, n_floats, nullptr, false, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm))
+    return rc;
+  return update_loop(h, name, false, n_rollout_rows, minibatch_rows, epochs, params_dev, n_floats, n_params, moments_dev, clock_dev, lr, beta1,
+                     beta2, eps, max_grad_norm, seed, stats_dev, stream,
+                     [&](const int64_t* idx, float* grad, float* stats_row, bool check_only) {
+                       return ppo_grad(h, name, mocca_ppo::PPO_DISTIL, obs_dev, obs_stride, target_dev, nullptr, nullptr, value_target_dev, nullptr,
+                                       idx, minibatch_rows, distill_coef, value_coef, 0.0, 0, grad, stats_row, stream, check_only);
+                     });
 }
 
 #ifdef MOCCA_STAMPS

@@ -65,6 +65,15 @@
 // Actor AND critic mirrored columns are live; columns without a minibatch row stay zeros.  PpoArgs.inv_b is 1 / (2 B) and n_samples 2 B.
 // Launch 2 is unchanged; launches 3 and 4 use the plain log_std arithmetic, and launch 4 writes stats[7] from column 36 as it does for the
 // mirror loss: the twins' share of stats[3].
+//
+// Distillation (mocca_distill_grad; include/mocca.h).  A supervised head on the same machinery: the loss is distill_coef mean_rows mean_j
+// (mean_j - target_j)^2 + value_coef 0.5 mean (v - value_target)^2.  ppo_rows_kernel<PPO_DISTIL> is the PLAIN instance -- one column per row, its
+// staging with idx and the normalisation, its layer loop with activate_once, activations and slopes to scratch, its backward -- and only the head
+// stage differs: the actor's lane forms d = mean - target per action, hands u = ((d * ib) * ia) * k2 to the backward, writes +0 to the row's
+// log_std terms and the row's sum of d^2 (f64) times ia to column 36 of R; the critic's lane forms the squared error against value_target, or
+// zeros where that is NULL.  PpoArgs carries the targets in `action`, the value targets in `returns` and k2 = f32(2 distill_coef) in `mirror_k2`;
+// old_logp, adv and old_value are not read, entropy_coef is 0.  Launches 2 to 4 are unchanged (launch 4 writes stats[7] from column 36, as for
+// the mirror loss); the scratch is the plain call's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,7 +84,7 @@ namespace mocca_ppo {
 
 constexpr int PPO_ROW_COLS = 48;         // floats per row of R
 constexpr int PPO_COL_SURR = 32, PPO_COL_VLOSS = 33, PPO_COL_DLOGP = 34, PPO_COL_CLIPPED = 35, PPO_COL_MIRROR = 36;
-enum PpoMode { PPO_PLAIN = 0, PPO_SYM = 1, PPO_MIRROR = 2, PPO_DUP = 3 };   // mocca_ppo_grad, mocca_ppo_grad_sym, mocca_ppo_grad_mirror, mocca_ppo_grad_dup
+enum PpoMode { PPO_PLAIN = 0, PPO_SYM = 1, PPO_MIRROR = 2, PPO_DUP = 3, PPO_DISTIL = 4 };   // mocca_ppo_grad, _sym, _mirror, _dup; mocca_distill_grad
 constexpr int PPO_MAX_CHUNKS = 16;       // row chunks of launch 2
 constexpr int PPO_CHUNK_MIN_ROWS = 512;  // a chunk holds at least this many rows
 constexpr int PPO_REDUCE_BLOCK = 256;
@@ -97,11 +106,11 @@ struct PpoArgs {
   const int32_t *in_perm, *act_perm;     // [in_dim], [act_dim]
   const float *in_sign, *act_sign;
   int mode;                              // PpoMode
-  float mirror_k2;                       // PPO_MIRROR: f32(2 mirror_coef)
+  float mirror_k2;                       // PPO_MIRROR: f32(2 mirror_coef); PPO_DISTIL: f32(2 distill_coef)
   // the minibatch
   const float* obs; int obs_stride;
   const float *action, *old_logp, *adv, *returns, *old_value;
-  const int64_t* idx;                    // [B] or null: rows 0 .. B - 1
+  const int64_t* idx;                    // [B] or null: rows 0 .. B - 1.  PPO_DISTIL: action = the target rows [R][act_dim], returns = value_target or null
   int n_rows, b_pad;                     // B; the scratch's rows: B rounded up to 16, symmetric: 16 ceil(B / 8)
   float clip, value_coef, entropy_coef, inv_b;
   int value_clip;

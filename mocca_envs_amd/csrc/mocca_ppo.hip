@@ -53,10 +53,12 @@ __device__ __forceinline__ float activate_slope(float x, int act) {
 // PPO_SYM's head stage symmetrises mean, log_std and value over the two columns; PPO_MIRROR's leaves the policy the as-given column's and
 // adds the mirror term over the actor's two columns, and its critic's mirrored columns are not live.  PPO_DUP's runs the plain per-row lines
 // on each of the 16 columns by itself: a mirrored column is one more sample, with the action mirrored too.
+// PPO_DISTIL (header: Distillation): the plain instance -- one column per row, its staging, layer loop and backward -- with the regression head stage.
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
   __shared__ __attribute__((aligned(16))) float X[2][TILE * LDS_STRIDE];
-  constexpr bool SYM = MODE != PPO_PLAIN;     // the two-column layout
+  constexpr bool DISTIL = MODE == PPO_DISTIL; // the regression head stage on the plain layout
+  constexpr bool SYM = MODE != PPO_PLAIN && !DISTIL;   // the two-column layout
   constexpr bool NET = MODE == PPO_SYM;       // the symmetric network's head stage
   constexpr bool ML = MODE == PPO_MIRROR;     // the mirror loss's head stage
   constexpr bool DUP = MODE == PPO_DUP;       // duplicated rows: the plain head stage, one lane per COLUMN
@@ -135,7 +137,40 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
       const float *head = &X[cur][tid * LDS_STRIDE], *mirror = &X[cur][mcol * LDS_STRIDE];
       float *dA = &X[cur ^ 1][tid * LDS_STRIDE], *dAm = &X[cur ^ 1][mcol * LDS_STRIDE];
       const long long src = row < B ? (a.idx ? (long long)a.idx[row] : row) : 0;
-      if (net == 1) {
+      if constexpr (DISTIL) {   // include/mocca.h, mocca_distill_grad: one f32 operation per line of it, in that order; action is the target
+        if (net == 1) {         // row, returns the value target or null
+          float dv = 0.0f, vloss = 0.0f;
+          if (row < B && a.returns) {
+            const float e = head[0] - a.returns[src];
+            const float l = e * e;
+            vloss = 0.5f * l;
+            dv = a.value_coef * e;
+            dv = dv * a.inv_b;
+          }
+          R[PPO_COL_VLOSS] = vloss;
+          for (int j = 0; j < head_pad; ++j) dA[j] = j == 0 ? dv : 0.0f;
+        } else {
+          const int A = a.act_dim;
+          const float ia = 1.0f / (float)A;
+          double m64 = 0.0;   // the row's sum of d_j^2, the terms f32
+          for (int j = 0; j < head_pad || j < POL_MAX_ACTION; ++j) {
+            float dmu = 0.0f;
+            if (row < B && j < A) {
+              const float d = head[j] - a.action[(size_t)src * A + j];
+              const float q = d * d;
+              m64 += (double)q;
+              float u = d * a.inv_b;
+              u = u * ia;
+              dmu = u * a.mirror_k2;
+            }
+            if (j < head_pad) dA[j] = dmu;
+            if (j < POL_MAX_ACTION) R[j] = 0.0f;   // log_std takes no gradient
+          }
+          R[PPO_COL_SURR] = 0.0f; R[PPO_COL_DLOGP] = 0.0f; R[PPO_COL_CLIPPED] = 0.0f;
+          R[PPO_COL_MIRROR] = (float)m64 * ia;   // the row's distillation term (stats[7])
+          for (int j = PPO_COL_MIRROR + 1; j < PPO_ROW_COLS; ++j) R[j] = 0.0f;
+        }
+      } else if (net == 1) {
         float dv = 0.0f, vloss = 0.0f;
         if (row < B) {   // include/mocca.h: one f32 operation per line of it, in that order
           const float v = NET ? 0.5f * (head[0] + mirror[0]) : head[0], ret = a.returns[src];
@@ -410,13 +445,14 @@ __global__ __launch_bounds__(PPO_REDUCE_BLOCK) void ppo_stats_kernel(PpoArgs a) 
   a.stats[4] = sum[3] / (float)a.n_samples;   // a count over B (PPO_DUP: 2 B), correctly rounded
   a.stats[5] = (float)sq[0];
   a.stats[6] = 0.0f;
-  a.stats[7] = sum[4] * a.inv_b;   // PPO_MIRROR: L_m, the rows' terms already carry the 1 / A; PPO_DUP: the twins' share of stats[3]; else 0
+  a.stats[7] = sum[4] * a.inv_b;   // PPO_MIRROR: L_m, the rows' terms already carry the 1 / A; PPO_DUP: the twins' share of stats[3]; PPO_DISTIL: L_d; else 0
 }
 
 void launch_ppo(hipStream_t s, const PpoArgs& a) {
   if (a.mode == PPO_SYM) hipLaunchKernelGGL(ppo_rows_kernel<PPO_SYM>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   else if (a.mode == PPO_MIRROR) hipLaunchKernelGGL(ppo_rows_kernel<PPO_MIRROR>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   else if (a.mode == PPO_DUP) hipLaunchKernelGGL(ppo_rows_kernel<PPO_DUP>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
+  else if (a.mode == PPO_DISTIL) hipLaunchKernelGGL(ppo_rows_kernel<PPO_DISTIL>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(ppo_rows_kernel<PPO_PLAIN>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(a.n_tiles, a.n_chunks), dim3(64), 0, s, a);
   hipLaunchKernelGGL(ppo_reduce_kernel, dim3(a.n_reduce_blocks), dim3(PPO_REDUCE_BLOCK), 0, s, a);

@@ -93,6 +93,12 @@ SYMBOLS = {
     "mocca_adam_step": (_i, [_vp, _vp, _sz, _vp, C.c_int64, _vp, _vp, _d, _d, _d, _d, _d, _vp]),
     "mocca_ppo_update": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _i, _d, _d, _d, _i, _vp, _sz, C.c_int64, _vp, _vp,
                               _d, _d, _d, _d, _d, _u64, _vp, _vp]),
+    "mocca_distill_grad": (_i, [_vp, _vp, _i, _vp, _vp, _vp, C.c_int64, _d, _d, _vp, _vp, _vp]),
+    "mocca_distill_update": (_i, [_vp, _vp, _i, _vp, _vp, C.c_int64, C.c_int64, _i, _d, _d, _vp, _sz, C.c_int64, _vp, _vp,
+                                  _d, _d, _d, _d, _d, _u64, _vp, _vp]),
+    "mocca_set_teacher": (_i, [_vp, _vp, _i, _i, _i, _d]),
+    "mocca_update_teacher": (_i, [_vp, _vp, _sz, _vp]),
+    "mocca_teacher_act": (_i, [_vp, _vp, _i, C.c_int64, _vp, _vp, _vp]),
     "mocca_is_diagnostic_build": (_i, []),
     "mocca_kernel_info": (_i, [_vp] + [C.POINTER(_i)] * 5),
     "mocca_last_error": (C.c_char_p, [_vp]),

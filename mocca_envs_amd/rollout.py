@@ -180,6 +180,36 @@ def ppo_args(policy, device, obs, action, old_logp, adv, returns, idx, old_value
     return n_rows, stride, n_batch
 
 
+def distill_args(policy, device, obs, target, value_target, idx, distill_coef, value_coef, grad, stats):
+    """check the tensors and numbers of distill_grad -> (R stored rows, obs row stride, B minibatch rows); ValueError otherwise"""
+    import torch
+    if not isinstance(obs, torch.Tensor) or obs.device != device:
+        raise ValueError("obs must be a float32 tensor on the env's device")
+    n_rows, stride = rows_2d(obs, policy.in_dim)
+    a = policy.act_dim
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.float32 or target.device != device or not target.is_contiguous() \
+            or target.dim() < 1 or target.shape[-1] != a or target.numel() != n_rows * a:
+        raise ValueError(f"target must be a contiguous float32 [..., {a}] tensor of {n_rows} rows on the env's device")
+    t = value_target
+    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != device or not t.is_contiguous()
+                          or t.numel() != n_rows):
+        raise ValueError(f"value_target must be a contiguous float32 tensor of {n_rows} elements (one per row of obs) on the env's device")
+    if idx is None:
+        n_batch = n_rows
+    else:
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.device != device or idx.dim() != 1 or not idx.is_contiguous():
+            raise ValueError("idx must be a contiguous int64 [B] tensor on the env's device (a chunk of torch.randperm)")
+        n_batch = int(idx.numel())
+    if not 1 <= n_batch <= MAX_MINIBATCH:
+        raise ValueError(f"the minibatch must have 1 .. {MAX_MINIBATCH} rows")
+    for name, x in (("distill_coef", distill_coef), ("value_coef", value_coef)):
+        if not (np.isfinite(float(x)) and float(x) >= 0.0):
+            raise ValueError(f"{name} must be finite and not negative")
+    stats_out("grad", grad, policy.n_head(), device)
+    stats_out("stats", stats, 8, device)
+    return n_rows, stride, n_batch
+
+
 class AdamState:
     """Adam's state for the flat parameter tensor of `update_policy`, on the device (include/mocca.h mocca_adam_step): `moments` float32
     [2, n_head] -- m, then v -- and `clock` float64 [4] = {t, beta1^t, beta2^t, skipped steps}.  `n_head`: `DevicePolicy.n_head()`."""

@@ -200,11 +200,24 @@ class TorchVecEnv:
     `terrain_bank=dict(n_fields=K, seed=S, n_peaks=256, gain=1.0, redraw_at_reset=True)` (planner ids): a bank of K random height fields of
     the shipped shape (128 x 128 points, 4 per metre) generated on the device before the first reset (include/mocca.h
     mocca_generate_heightfields), every env on one of them -- with `redraw_at_reset` another one in every episode; refresh_terrain(seed)
-    regenerates the bank in place.  Without it the envs stand on the shipped map, as ever."""
+    regenerates the bank in place.  Without it the envs stand on the shipped map, as ever.
+    `privileged_scan=dict(points=[P, 2], z_above=1.0, max_drop=2.0)` (teacher-student distillation; not together with `height_scan=`): the
+    scan is attached to the handle but NOT appended to the observation row -- rows stay [obs] or [obs | depth] -- and `envs.privileged`
+    [N, obs_dim + P] holds [obs | scan], the row a teacher trained with `height_scan=` saw, refreshed by one more height-scan launch after
+    every reset and step, on the step's stream.  `attach_teacher(policy)` / `teacher_targets(mean_out, value_out)` evaluate a frozen
+    teacher on it."""
 
     def __init__(self, env_id: str, num_envs: int, seed: int = 0, device: Optional[int] = None, sub_batches: int = 1,
                  terminal_observation: bool = False, record_slots: int = 8, eager_done: bool = False, record_events: bool = True,
-                 height_scan: Optional[dict] = None, terrain_bank: Optional[dict] = None, depth_camera=None, **kw):
+                 height_scan: Optional[dict] = None, terrain_bank: Optional[dict] = None, depth_camera=None,
+                 privileged_scan: Optional[dict] = None, **kw):
+        if height_scan is not None and privileged_scan is not None:
+            raise ValueError("height_scan= puts the scan into the observation row, privileged_scan= keeps it out of it: one of the two")
+        if privileged_scan is not None and terminal_observation:
+            raise NotImplementedError("privileged_scan with terminal_observation=True: the scan runs after the step's launch, when an env that "
+                                      "finished already holds its next episode's first state")
+        if privileged_scan is not None and sub_batches > 1:
+            raise NotImplementedError("privileged_scan needs one handle (sub_batches=1)")
         if depth_camera is not None and terminal_observation:
             raise NotImplementedError("depth_camera with terminal_observation=True: the camera runs after the step's launch, when an env that "
                                       "finished already holds its next episode's first state -- the terminal state is gone, so no image can be "
@@ -240,6 +253,12 @@ class TorchVecEnv:
                 raise NotImplementedError("height_scan needs one handle (one device, sub_batches=1)")
             self.venv.set_height_scan(**height_scan)
             self._scan = self.venv.scan_dim
+        self.privileged = None
+        if privileged_scan is not None:
+            if not hasattr(self.venv, "lib"):
+                raise NotImplementedError("privileged_scan needs one handle (one device, sub_batches=1)")
+            self.venv.set_height_scan(**privileged_scan)
+            self.privileged = torch.zeros(self.num_envs, self.venv.obs_dim + self.venv.scan_dim, dtype=torch.float32, device=self.device)
         self._depth = 0
         if depth_camera is not None:
             if not hasattr(self.venv, "lib"):
@@ -315,7 +334,13 @@ class TorchVecEnv:
     # ---- the VecPyTorch surface ----
     def reset(self) -> torch.Tensor:
         obs = self.venv.reset()        # (the reset kernel zeroes the envs' running returns: Monitor.reset)
+        self._refresh_privileged(obs)
         return obs if self._wide is None else self._widen(obs, self._wide)
+
+    def _refresh_privileged(self, obs):
+        """privileged_scan=: the row [obs | scan] of the state the envs are in now into `self.privileged`, one launch on the step's stream"""
+        if self.privileged is not None:
+            self.venv.height_scan(out=self.privileged, obs=obs)
 
     def _widen(self, obs, wide):
         """the wide row [obs | scan | depth] into `wide`: one launch per sensor, the first of them copies the observation"""
@@ -334,12 +359,16 @@ class TorchVecEnv:
         launch = launch or self._venv_step
         if self._wide is None:
             if obs_out is None and rew_out is None:      # (the sub-batched step takes the actions only)
-                return launch(actions)[:2]
-            return launch(actions, obs_out=obs_out, rew_out=rew_out)[:2]
+                o, r = launch(actions)[:2]
+            else:
+                o, r = launch(actions, obs_out=obs_out, rew_out=rew_out)[:2]
+            self._refresh_privileged(o)
+            return o, r
         wide = self._wide if obs_out is None else obs_out
         if wide.shape != self._wide.shape or not wide.is_contiguous():
             raise ValueError("with a height scan or a depth camera the observation rows are contiguous float32 [n_envs, obs_dim + scan_dim + depth_dim]")
         o, r = launch(actions, rew_out=rew_out)[:2]
+        self._refresh_privileged(o)
         return self._widen(o, wide), r
 
     def step(self, actions: torch.Tensor, into: Optional[dict] = None):
@@ -399,6 +428,42 @@ class TorchVecEnv:
 
     def update_policy(self, params) -> None:
         self.venv.update_policy(params)
+
+    # ---- teacher-student distillation (VecEnv.set_teacher / teacher_act / distill_grad / distill_update) ----
+    def attach_teacher(self, policy) -> None:
+        """Attach a frozen `policy.DevicePolicy` as the teacher (None detaches): it reads `envs.privileged` ([obs | scan], with
+        `privileged_scan=`) or, without one, the env's observation row, and labels the states the student visits (teacher_targets).  One
+        handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("a teacher needs one handle (sub_batches=1)")
+        rows = self._teacher_rows()
+        if policy is not None and policy.in_dim != rows.shape[1]:
+            raise ValueError(f"the teacher reads {policy.in_dim} inputs, its rows here have {rows.shape[1]}"
+                             + (" ([obs | scan])" if self.privileged is not None else " (the observation row; privileged_scan= gives [obs | scan])"))
+        self.venv.set_teacher(policy)
+
+    def _teacher_rows(self):
+        if self.privileged is not None:
+            return self.privileged
+        return self.venv.obs if self._wide is None else self._wide
+
+    def teacher_targets(self, mean_out: Optional[torch.Tensor] = None, value_out: Optional[torch.Tensor] = None) -> dict:
+        """The teacher's actor mean [N, A] and value [N] (or [N, 1]) of the state the envs are in now -- after the last reset() / step() /
+        act_step() -- into `mean_out` / `value_out` (rows of the trainer's storage; allocated where none is given): one launch on the
+        step's stream, capturable behind act_step and the sensors in one graph.  -> {"mean", "value"}"""
+        return self.venv.teacher_act(self._teacher_rows(), mean=mean_out, value=value_out)
+
+    def distill_grad(self, obs, target, *args, **kw) -> dict:
+        """the regression gradient over stored rows and their targets, four launches: `VecEnv.distill_grad`.  One handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("distill_grad needs one handle (sub_batches=1)")
+        return self.venv.distill_grad(obs, target, *args, **kw)
+
+    def distill_update(self, obs, target, params, state, minibatch_rows, epochs, **kw) -> dict:
+        """epochs x minibatches of [shuffle, distill_grad, adam_step] over the stored rows as one call: `VecEnv.distill_update`.  One handle only."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError("distill_update needs one handle (sub_batches=1)")
+        return self.venv.distill_update(obs, target, params, state, minibatch_rows, epochs, **kw)
 
     def symmetric_policy(self, policy):
         """a copy of `policy` with this env's mirror tables, the attached height scan's pattern included: `VecEnv.symmetric_policy`"""

@@ -692,6 +692,108 @@ class VecEnv:
         self._out()
         return {"stats": stats.view(int(epochs) * per_epoch, 8)}
 
+    # ---- teacher-student distillation on the device (include/mocca.h mocca_distill_grad / mocca_distill_update / mocca_set_teacher ..) ----
+    teacher = None
+
+    def _no_mirror(self, name: str) -> None:
+        if self.policy is None:
+            raise _lib.MoccaError(f"{name} needs a policy (set_policy)")
+        if getattr(self.policy, "symmetry", None) is not None or self.mirror_loss is not None or self.mirror_dup is not None:
+            raise _lib.MoccaError(f"{name}: the policy has a mirror attachment (symmetry, mirror loss or duplicated rows): detach it first")
+
+    def distill_grad(self, obs: torch.Tensor, target: torch.Tensor, value_target: Optional[torch.Tensor] = None,
+                     idx: Optional[torch.Tensor] = None, distill_coef: float = 1.0, value_coef: float = 0.5,
+                     grad: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None) -> dict:
+        """A regression minibatch step (behaviour cloning, DAgger) as `ppo_grad`'s four launches: the gradient of
+        `distill_coef * (mean - target).pow(2).mean() + value_coef * 0.5 * (value - value_target).pow(2).mean()` with respect to every
+        parameter of the attached PLAIN policy -> {"grad" [policy.n_head()], "stats" [8]: 0, value loss, entropy, 0, 0, sum of grad^2, 0,
+        L_d = mean squared error of the actor's mean}.  `obs` and `idx` as in `ppo_grad`; `target` [.., act_dim] and `value_target` ([..] or
+        [.., 1], None: the critic gets no gradient) contiguous float32 of the same R rows.  log_std's gradient is exactly 0.  The same
+        inputs give the same bits on every run."""
+        self._no_mirror("distill_grad")
+        _, stride, n_batch = _ro.distill_args(self.policy, self.device, obs, target, value_target, idx, distill_coef, value_coef, grad, stats)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        grad = torch.empty(self.policy.n_head(), **f32) if grad is None else grad
+        stats = torch.empty(8, **f32) if stats is None else stats
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        self._in()
+        _lib.check(self.lib.mocca_distill_grad(self.h, ptr(obs), stride, ptr(target), ptr(value_target), ptr(idx), n_batch, float(distill_coef),
+                                               float(value_coef), ptr(grad), ptr(stats), self._stream()), self.h)
+        self._out()
+        return {"grad": grad, "stats": stats}
+
+    def distill_update(self, obs: torch.Tensor, target: torch.Tensor, params: torch.Tensor, state, minibatch_rows: int, epochs: int,
+                       value_target: Optional[torch.Tensor] = None, distill_coef: float = 1.0, value_coef: float = 0.5,
+                       n_params: Optional[int] = None, lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5,
+                       max_grad_norm: float = 0.5, seed: int = 0, stats: Optional[torch.Tensor] = None) -> dict:
+        """`ppo_update`'s loop around `distill_grad`: `epochs` passes over the R stored rows, each a fresh shuffle cut into
+        M = R // minibatch_rows minibatches (the remainder is dropped), each minibatch `distill_grad` on its rows and `adam_step` on
+        `params` -- the same bits as that loop.  -> {"stats": [epochs * M, 8]}: `distill_grad`'s statistics per minibatch, [6] the clip
+        coefficient applied.  Nothing synchronises or is read on the host; capturable after one warm call of the same shapes."""
+        self._no_mirror("distill_update")
+        n_rows, stride, _ = _ro.distill_args(self.policy, self.device, obs, target, value_target, None, distill_coef, value_coef, None, None)
+        n_params = _ro.adam_args(self.policy, self.device, params, None, state, n_params, lr, betas, eps, max_grad_norm)
+        per_epoch = _ro.update_args(n_rows, minibatch_rows, epochs, seed, stats, self.device)
+        if stats is None:
+            stats = torch.empty(int(epochs) * per_epoch, 8, dtype=torch.float32, device=self.device)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        self._in()
+        _lib.check(self.lib.mocca_distill_update(self.h, ptr(obs), stride, ptr(target), ptr(value_target), n_rows, int(minibatch_rows), int(epochs),
+                                                 float(distill_coef), float(value_coef), ptr(params), params.numel(), n_params,
+                                                 ptr(state.moments), ptr(state.clock), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                                 float(max_grad_norm), int(seed), ptr(stats), self._stream()), self.h)
+        self._out()
+        return {"stats": stats.view(int(epochs) * per_epoch, 8)}
+
+    def set_teacher(self, policy) -> None:
+        """Attach a frozen `policy.DevicePolicy` as the TEACHER (None detaches): a second image beside the policy of set_policy, which it
+        may differ from in in_dim and layers; its weights are uploaded (update_teacher).  A policy carrying `symmetry` is refused.  The
+        attached policy, its mirror attachment, act() and the gradient calls are untouched.  May synchronise."""
+        if policy is None:
+            _lib.check(self.lib.mocca_set_teacher(self.h, None, 0, 0, 0, 0.0), self.h)
+            self.teacher = None
+            return
+        if getattr(policy, "symmetry", None) is not None:
+            raise ValueError("set_teacher: the teacher is a plain policy; one carrying `symmetry` is not supported")
+        table = np.ascontiguousarray(policy.table(), np.int32)
+        _lib.check(self.lib.mocca_set_teacher(self.h, table.ctypes.data_as(C.c_void_p), table.shape[0], int(policy.in_dim), int(policy.act_dim),
+                                              float(policy.clip)), self.h)
+        self.teacher = policy
+        self.update_teacher(policy)
+
+    def update_teacher(self, params) -> None:
+        """New weights for the teacher: a `DevicePolicy` of the same shapes or a flat float32 tensor, as `update_policy` takes them."""
+        if self.teacher is None:
+            raise _lib.MoccaError("update_teacher needs a teacher (set_teacher)")
+        flat = torch.from_numpy(params.flat_params()) if hasattr(params, "flat_params") else params
+        flat = flat.detach().to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
+        self._in()
+        _lib.check(self.lib.mocca_update_teacher(self.h, C.c_void_p(flat.data_ptr()), flat.numel(), self._stream()), self.h)
+        self._out()
+
+    def teacher_act(self, rows: torch.Tensor, mean: Optional[torch.Tensor] = None, value: Optional[torch.Tensor] = None) -> dict:
+        """The teacher's actor mean and value on `rows` [n, >= teacher.in_dim] (float32 on the env's device, contiguous last dimension; any
+        n >= 1) in one launch -> {"mean" [n, act_dim], "value" [n]}.  `mean` / `value`: caller-owned outputs (rows of a storage);
+        allocated where none is given.  Nothing synchronises."""
+        t = self.teacher
+        if t is None:
+            raise _lib.MoccaError("teacher_act needs a teacher (set_teacher)")
+        if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[0] < 1 or rows.shape[1] < t.in_dim or rows.dtype != torch.float32 \
+                or rows.device != self.device or rows.stride(1) != 1:
+            raise ValueError(f"the teacher's input must be a float32 [n, >= {t.in_dim}] tensor on the env's device with contiguous rows")
+        n = rows.shape[0]
+        f32 = dict(dtype=torch.float32, device=self.device)
+        mean = torch.empty(n, t.act_dim, **f32) if mean is None else mean
+        value = torch.empty(n, **f32) if value is None else value
+        _ro.stats_out("mean", mean, n * t.act_dim, self.device)
+        _ro.stats_out("value", value, n, self.device)
+        stride = rows.stride(0) if n > 1 else max(rows.stride(0), rows.shape[1])
+        self._in()
+        _lib.check(self.lib.mocca_teacher_act(self.h, C.c_void_p(rows.data_ptr()), int(stride), n, C.c_void_p(mean.data_ptr()),
+                                              C.c_void_p(value.data_ptr()), self._stream()), self.h)
+        self._out()
+        return {"mean": mean, "value": value}
+
     # ---- the reference's env-level setters, batched (env_base.py:103-118, env_locomotion.py:76-77,224-282) ----
     def set_env_params(self, params_dict):
         """`set_env_params({"curriculum": k})`: one value for all envs or one per env (takes effect at each env's next reset; the

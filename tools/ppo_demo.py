@@ -11,6 +11,7 @@ No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it Symme
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
                            [--device-policy [--device-returns [--device-grad [--device-update]]]] [--symmetric | --mirror-loss COEF | --mirror-dup]
                            [--base-controller FILE] [--height-scan NX,NY] [--depth-camera W,H]
+                           [--distill-from TEACHER.npz --privileged-scan NX,NY]
 --base-controller FILE (required for the planner ids, Walker3DPlannerEnv-v0 / MikePlannerEnv-v0): ALLSTEPS's second step.  FILE is a
 `BaseController.save_npz` file or the <out>_policy.npz of an earlier run of this script on a Stepper id (told apart by the keys; the latter
 brings its observation statistics along); it is frozen as the env's base controller and the policy trained here emits 15-number plans.
@@ -49,6 +50,14 @@ with `symmetry.duplicate_minibatch`; with --device-grad / --device-update `envs.
 minibatch's gradient is mocca_ppo_grad_dup on the B rows as they lie.  The logged lines carry `mirror_loss`, `symmetry.mirror_loss` of the
 current actor on the rollout's first row of observations (computed at logged iterations only, never trained on), and `twin_dlogp`, the mean
 since the last logged line of stats[7]: the twins' share of mean(old_logp - logp), how far off-policy the policy's asymmetry puts them.
+--distill-from TEACHER.npz --privileged-scan NX,NY (with --device-update; used with --depth-camera W,H): teacher-student distillation
+(DAgger) in place of PPO.  TEACHER.npz is the <out>_policy.npz of a run with --height-scan NX,NY: it is frozen in the handle's teacher slot
+(`envs.attach_teacher`) and reads `envs.privileged`, the row [obs | scan] that `make_vec_envs(privileged_scan=...)` keeps beside the student's
+own row, which stays [obs | depth].  The student collects with its own noise through `act_step`; after every step `envs.teacher_targets` stores
+the teacher's mean and value of the state reached beside the row, one more launch; the iteration's learning is ONE `envs.distill_update` --
+the regression of the student's mean onto the teacher's, with the teacher's value as the critic's target -- and the logged lines carry `L_d`,
+the mean squared error of the actor's mean over the iteration's minibatches.  log_std takes no gradient from the regression: it starts at the
+teacher's and stays there.
 --verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor
 (--mirror-dup: on that minibatch's rows whose ratio and whose twin's ratio lie more than 1e-4 from the clip bounds, where the surrogate's
 gradient jumps and two float32 evaluations may disagree on a sample's side; the twins' ratios are spread over the bounds); with
@@ -65,7 +74,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--env-id", default="Walker3DCustomEnv-v0")
     ap.add_argument("--envs", type=int, default=4096)
@@ -98,8 +107,10 @@ def main():
     ap.add_argument("--terrain-seed", type=int, default=0, metavar="S", help="seed of the terrain bank")
     ap.add_argument("--terrain-refresh", type=int, default=0, metavar="M", help="regenerate the bank every M iterations with seed S + iteration (0: never)")
     ap.add_argument("--terrain-gain", type=float, default=1.0, metavar="G", help="the generated fields are multiplied by G: the difficulty knob")
+    ap.add_argument("--distill-from", default=None, metavar="TEACHER.npz", help="with --device-update: distil this frozen teacher (the policy file of a --height-scan run) into the student instead of PPO")
+    ap.add_argument("--privileged-scan", default=None, metavar="NX,NY", help="with --distill-from: the teacher's scan_grid, kept beside the observation row (envs.privileged), never in it")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.device_grad and not args.device_returns:
         ap.error("--device-grad requires --device-returns")
     if args.device_update and not args.device_grad:
@@ -125,6 +136,12 @@ def main():
         ap.error("--terrain-bank is for the planner ids: the other tasks have no height field")
     if args.terrain_refresh and not args.terrain_bank:
         ap.error("--terrain-refresh requires --terrain-bank")
+    if args.distill_from is not None and not args.device_update:
+        ap.error("--distill-from requires --device-update")
+    if args.distill_from is not None and (args.symmetric or args.mirror_loss is not None or args.mirror_dup or args.verify_grad):
+        ap.error("--distill-from is not for --symmetric / --mirror-loss / --mirror-dup / --verify-grad: the regression gradient is the plain policy's")
+    if args.privileged_scan is not None and (args.distill_from is None or args.height_scan is not None):
+        ap.error("--privileged-scan goes with --distill-from and not with --height-scan")
     import torch
     import torch.nn as nn
     from mocca_envs_amd.trainer_api import make_vec_envs
@@ -137,6 +154,10 @@ def main():
         from mocca_envs_amd.perception import scan_grid
         nx, ny = (int(v) for v in args.height_scan.split(","))
         extra["height_scan"] = dict(points=scan_grid((0.0, 2.0), (-0.5, 0.5), nx, ny))
+    if args.privileged_scan is not None:
+        from mocca_envs_amd.perception import scan_grid
+        nx, ny = (int(v) for v in args.privileged_scan.split(","))
+        extra["privileged_scan"] = dict(points=scan_grid((0.0, 2.0), (-0.5, 0.5), nx, ny))
     if args.depth_camera is not None:
         from mocca_envs_amd.perception import DepthCamera
         cw, ch = (int(v) for v in args.depth_camera.split(","))
@@ -159,6 +180,10 @@ def main():
 
     pi, vf = mlp(od, ad, 0.01), mlp(od, 1, 1.0)
     log_std = nn.Parameter(torch.full((ad,), args.log_std, device=dev), requires_grad=not args.fixed_std)
+    if args.distill_from is not None:      # the regression gives log_std no gradient: the student explores with the teacher's noise throughout
+        import numpy as np
+        with np.load(args.distill_from, allow_pickle=False) as z:
+            log_std.data.copy_(torch.from_numpy(z["log_std"]).to(dev))
     opt = torch.optim.Adam(list(pi.parameters()) + list(vf.parameters()) + ([] if args.fixed_std else [log_std]), lr=args.lr, eps=1e-5)
     # rollout storage, a2c-ppo-acktr's layout; the step kernel writes rows t + 1 / t of obs, rewards, masks, bad_masks itself
     S = {"obs": torch.zeros(T + 1, N, od, device=dev), "reward": torch.zeros(T, N, 1, device=dev), "masks": torch.ones(T + 1, N, 1, device=dev),
@@ -221,6 +246,10 @@ def main():
         if args.mirror_dup and args.device_grad:      # likewise
             envs.set_policy_mirror_dup(envs.policy_mirror_tables(dp))
         row_act = lambda t: dict(row(t), action=S["act"][t], logp=S["logp"][t], value=S["value"][t])
+        if args.distill_from is not None:      # the frozen teacher; its labels of the state in obs[t] lie in row t beside it
+            envs.attach_teacher(DevicePolicy.from_npz(args.distill_from))
+            S["t_mean"], S["t_value"] = torch.zeros(T + 1, N, ad, device=dev), torch.zeros(T + 1, N, 1, device=dev)
+            ld_sum, ld_n = torch.zeros((), device=dev), 0      # L_d over the minibatches since the last logged line
         # DevicePolicy.flat_params()'s order, built on the device: layers of pi then vf (W, b), log_std, mean, 1 / sqrt(var + eps)
         flat_params = lambda: torch.cat([q.reshape(-1) for net in (pi, vf) for m in net if isinstance(m, nn.Linear) for q in (m.weight, m.bias)]
                                         + [log_std, mean, 1.0 / torch.sqrt(var + 1e-8)])
@@ -277,6 +306,8 @@ def main():
         print(json.dumps({"verify_grad": worst, "iter": it + 1}), flush=True)
 
     S["obs"][0].copy_(envs.reset())
+    if args.distill_from is not None:
+        envs.teacher_targets(S["t_mean"][0], S["t_value"][0])
     envs.episode_totals.zero_()
     log = open(args.out + ".jsonl", "w")
     t_start, total_steps, last_tot = time.perf_counter(), 0, torch.zeros(4, device=dev)
@@ -293,6 +324,8 @@ def main():
                 envs.update_policy(flat)
                 for t in range(T):
                     envs.act_step(S["obs"][t], into=row_act(t))
+                    if args.distill_from is not None:      # the teacher labels the state the student has just reached
+                        envs.teacher_targets(S["t_mean"][t + 1], S["t_value"][t + 1])
                 envs.venv.act(S["obs"][T], deterministic=True, out={"value": S["value"][T]})
                 if args.verify_returns:
                     raw = envs.finish_rollout(S["reward"], S["value"], S["masks"], S["bad_masks"], args.gamma, args.lam, args.reward_scale, normalise=False)
@@ -353,7 +386,13 @@ def main():
         B = N * T
         o_all, a_all, lp_all = norm(S["obs"][:T]).reshape(B, od), S["act"].reshape(B, ad), S["logp"].reshape(B, 1)
         adv_all, ret_all, raw_all = adv.reshape(B, 1), ret.reshape(B, 1), S["obs"][:T].reshape(B, od)
-        if args.device_update:
+        if args.distill_from is not None:
+            # DAgger's regression as one call: epochs x minibatches of [shuffle, distill_grad, clip, Adam, repack] on the rows the student visited
+            envs.distill_update(S["obs"][:T], S["t_mean"][:T], flat, adam, minibatch_rows=B // args.minibatches, epochs=args.epochs,
+                                value_target=S["t_value"][:T], distill_coef=1.0, value_coef=0.5, n_params=n_head - ad if args.fixed_std else n_head,
+                                lr=args.lr, eps=1e-5, max_grad_norm=0.5, seed=args.seed, stats=u_stats)
+            ld_sum += u_stats[:, 7].sum(); ld_n += u_stats.shape[0]
+        elif args.device_update:
             if args.verify_grad:      # the update draws its minibatches on the device: one gradient call on a chunk of our own, ahead of it
                 mb = torch.randperm(B, device=dev)[:B // args.minibatches]
                 if args.mirror_dup:
@@ -411,6 +450,8 @@ def main():
                 opt.step()
         with torch.no_grad():      # rollouts.after_update()
             S["obs"][0].copy_(S["obs"][T]); S["masks"][0].copy_(S["masks"][T]); S["bad_masks"][0].copy_(S["bad_masks"][T])
+            if args.distill_from is not None:
+                S["t_mean"][0].copy_(S["t_mean"][T]); S["t_value"][0].copy_(S["t_value"][T])
         if it % 10 == 9 or it == 0:
             tot_now = envs.episode_totals.clone()
             dlt = (tot_now - last_tot).cpu().numpy()
@@ -427,6 +468,9 @@ def main():
                     line["mirror_loss"] = float(mirror_loss(lambda x: pi(norm(x)), S["obs"][0], mirror_tf).item())
                 line["twin_dlogp"] = float(td_sum.item() / max(td_n, 1))
                 td_sum.zero_(); td_n = 0
+            if args.distill_from is not None:      # the mean of L_d over the minibatches since the last logged line
+                line["L_d"] = float(ld_sum.item() / max(ld_n, 1))
+                ld_sum.zero_(); ld_n = 0
             if "Stepper" in args.env_id:      # next_step_index of the running episodes (the step's info word): how far along the 20 planks the batch is
                 line["mean_next_step_index"] = float(envs.venv.info.float().mean().item())
             log.write(json.dumps(line) + "\n"); log.flush()
