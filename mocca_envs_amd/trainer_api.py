@@ -213,31 +213,23 @@ class TorchVecEnv:
                  privileged_scan: Optional[dict] = None, **kw):
         if height_scan is not None and privileged_scan is not None:
             raise ValueError("height_scan= puts the scan into the observation row, privileged_scan= keeps it out of it: one of the two")
-        if privileged_scan is not None and terminal_observation:
-            raise NotImplementedError("privileged_scan with terminal_observation=True: the scan runs after the step's launch, when an env that "
-                                      "finished already holds its next episode's first state")
-        if privileged_scan is not None and sub_batches > 1:
-            raise NotImplementedError("privileged_scan needs one handle (sub_batches=1)")
-        if depth_camera is not None and terminal_observation:
-            raise NotImplementedError("depth_camera with terminal_observation=True: the camera runs after the step's launch, when an env that "
-                                      "finished already holds its next episode's first state -- the terminal state is gone, so no image can be "
-                                      "appended to the terminal observation")
-        if depth_camera is not None and sub_batches > 1:
-            raise NotImplementedError("depth_camera needs one handle (sub_batches=1)")
-        if height_scan is not None and terminal_observation:
-            raise NotImplementedError("height_scan with terminal_observation=True: the scan runs after the step's launch, when an env that finished "
-                                      "already holds its next episode's first state -- the terminal state is gone, so no scan can be appended to "
-                                      "the terminal observation")
-        if height_scan is not None and sub_batches > 1:
-            raise NotImplementedError("height_scan needs one handle (sub_batches=1)")
+        sensors = [name for name, arg in (("privileged_scan", privileged_scan), ("depth_camera", depth_camera), ("height_scan", height_scan))
+                   if arg is not None]
+        for name in sensors:             # refused before anything touches a device
+            if terminal_observation:
+                raise NotImplementedError(f"{name} with terminal_observation=True: the sensor runs after the step's launch, when an env that "
+                                          "finished already holds its next episode's first state -- the terminal state is gone, so nothing of it "
+                                          "can be appended to the terminal observation")
+            if sub_batches > 1:
+                raise NotImplementedError(f"{name} needs one handle (sub_batches=1)")
         self.venv = make_vec_env(env_id, num_envs, sub_batches=sub_batches, seed=seed, auto_reset=True,
                                  **({"device": device} if device is not None else {}), **kw)
         self.env_id, self.num_envs = env_id, int(num_envs)
         self.device = self.venv.device
+        for name in sensors + (["terrain_bank"] if terrain_bank is not None else []):    # (several devices are no single handle either)
+            self._one(name)
         self._terrain = None
         if terrain_bank is not None:
-            if not hasattr(self.venv, "lib"):
-                raise NotImplementedError("terrain_bank needs one handle (one device, sub_batches=1)")
             from . import host_logic as H
             tb = dict(terrain_bank)
             unknown = set(tb) - {"n_fields", "seed", "n_peaks", "gain", "redraw_at_reset"}
@@ -249,20 +241,14 @@ class TorchVecEnv:
             self.venv.set_env_fields(None, redraw_at_reset=bool(tb.get("redraw_at_reset", True)))
         self._scan, self._wide = 0, None
         if height_scan is not None:
-            if not hasattr(self.venv, "lib"):
-                raise NotImplementedError("height_scan needs one handle (one device, sub_batches=1)")
             self.venv.set_height_scan(**height_scan)
             self._scan = self.venv.scan_dim
         self.privileged = None
         if privileged_scan is not None:
-            if not hasattr(self.venv, "lib"):
-                raise NotImplementedError("privileged_scan needs one handle (one device, sub_batches=1)")
             self.venv.set_height_scan(**privileged_scan)
             self.privileged = torch.zeros(self.num_envs, self.venv.obs_dim + self.venv.scan_dim, dtype=torch.float32, device=self.device)
         self._depth = 0
         if depth_camera is not None:
-            if not hasattr(self.venv, "lib"):
-                raise NotImplementedError("depth_camera needs one handle (one device, sub_batches=1)")
             self.venv.set_depth_camera(depth_camera)
             self._depth = self.venv.depth_dim
         if self._scan or self._depth:
@@ -307,6 +293,19 @@ class TorchVecEnv:
         if self._terrain is None:
             raise _lib.MoccaError("refresh_terrain needs terrain_bank=dict(...) at construction")
         self.venv.generate_heightfields(int(seed), **self._terrain)
+
+    def _one(self, name: str):
+        """The one `VecEnv` behind this object, for `name`, which needs it: sub-batches and shards are handles of their own, each with
+        its streams, its policy slots and its sensors."""
+        if not hasattr(self.venv, "lib"):
+            raise NotImplementedError(f"{name} needs one handle (sub_batches=1)")
+        return self.venv
+
+    def _masks_into(self, into: dict) -> None:
+        """step(into=) / capture_rollout(into=): the kernel's `masks` / `bad_masks` columns into the caller's tensors, from the next launch on"""
+        if "masks" in into or "bad_masks" in into:
+            self.masks, self.bad_masks = into.get("masks", self.masks), into.get("bad_masks", self.bad_masks)
+            self.venv.episode_masks_into(self.masks, self.bad_masks)
 
     def _attach_terminal(self, buf: torch.Tensor):
         """Attach `buf` [N, obs_dim] as the terminal-observation buffer of the handle(s) (each sub-batch its rows) and return the
@@ -393,11 +392,8 @@ class TorchVecEnv:
             self._use_terminal(slot)
         rew = self._rew2
         if into:
-            if not hasattr(self.venv, "lib"):
-                raise NotImplementedError("step(into=...) needs one handle (sub_batches=1)")
-            if "masks" in into or "bad_masks" in into:
-                self.masks, self.bad_masks = into.get("masks", self.masks), into.get("bad_masks", self.bad_masks)
-                self.venv.episode_masks_into(self.masks, self.bad_masks)
+            self._one("step(into=...)")
+            self._masks_into(into)
             rew = into.get("reward", rew)
             obs = self._step_obs(actions, obs_out=into.get("obs"), rew_out=into.get("reward"), launch=launch)[0]
         else:
@@ -416,8 +412,7 @@ class TorchVecEnv:
         (VecEnv.act_plan_step); `update_policy(policy_or_flat_tensor)` refreshes its weights once per PPO iteration.  One handle only.  A
         policy with mirror tables (`symmetric_policy(p)`, `DevicePolicy(symmetry=)`) acts as the symmetric network: the tables cover the
         whole row."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("a device policy needs one handle (sub_batches=1)")
+        self._one("attach_policy")
         act_dim = self.venv.plan_dim if self._plan else self.venv.act_dim
         if policy is not None and (policy.in_dim != self.observation_space.shape[0] or policy.act_dim != act_dim):
             raise ValueError(f"the policy maps {policy.in_dim} -> {policy.act_dim}, the env {self.observation_space.shape[0]} -> {act_dim}")
@@ -434,8 +429,7 @@ class TorchVecEnv:
         """Attach a frozen `policy.DevicePolicy` as the teacher (None detaches): it reads `envs.privileged` ([obs | scan], with
         `privileged_scan=`) or, without one, the env's observation row, and labels the states the student visits (teacher_targets).  One
         handle only."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("a teacher needs one handle (sub_batches=1)")
+        self._one("attach_teacher")
         rows = self._teacher_rows()
         if policy is not None and policy.in_dim != rows.shape[1]:
             raise ValueError(f"the teacher reads {policy.in_dim} inputs, its rows here have {rows.shape[1]}"
@@ -453,74 +447,8 @@ class TorchVecEnv:
         step's stream, capturable behind act_step and the sensors in one graph.  -> {"mean", "value"}"""
         return self.venv.teacher_act(self._teacher_rows(), mean=mean_out, value=value_out)
 
-    def distill_grad(self, obs, target, *args, **kw) -> dict:
-        """the regression gradient over stored rows and their targets, four launches: `VecEnv.distill_grad`.  One handle only."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("distill_grad needs one handle (sub_batches=1)")
-        return self.venv.distill_grad(obs, target, *args, **kw)
-
-    def distill_update(self, obs, target, params, state, minibatch_rows, epochs, **kw) -> dict:
-        """epochs x minibatches of [shuffle, distill_grad, adam_step] over the stored rows as one call: `VecEnv.distill_update`.  One handle only."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("distill_update needs one handle (sub_batches=1)")
-        return self.venv.distill_update(obs, target, params, state, minibatch_rows, epochs, **kw)
-
-    def symmetric_policy(self, policy):
-        """a copy of `policy` with this env's mirror tables, the attached height scan's pattern included: `VecEnv.symmetric_policy`"""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("a device policy needs one handle (sub_batches=1)")
-        return self.venv.symmetric_policy(policy)
-
-    # ---- the end of a rollout on the device (VecEnv.finish_rollout / update_obs_stats, include/mocca.h mocca_gae / mocca_obs_stats) ----
-    def finish_rollout(self, reward, value, masks, bad_masks, *args, **kw) -> dict:
-        """returns, advantages (normalised by default) and their moments from the rollout storage, two launches: `VecEnv.finish_rollout`.
-        One handle only."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("finish_rollout needs one handle (sub_batches=1)")
-        return self.venv.finish_rollout(reward, value, masks, bad_masks, *args, **kw)
-
-    def update_obs_stats(self, stats, rows, mean_out=None, inv_std_out=None) -> None:
-        """merge a rollout's observation rows into a `rollout.ObsStats`, two launches: `VecEnv.update_obs_stats`.  One handle only."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("update_obs_stats needs one handle (sub_batches=1)")
-        self.venv.update_obs_stats(stats, rows, mean_out=mean_out, inv_std_out=inv_std_out)
-
-    def policy_mirror_tables(self, policy):
-        """this env's mirror tables for `policy`, the attached height scan's pattern included: `VecEnv.policy_mirror_tables`"""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("policy_mirror_tables needs one handle (sub_batches=1)")
-        return self.venv.policy_mirror_tables(policy)
-
-    def set_policy_mirror_loss(self, tables, coef: float = 0.0) -> None:
-        """attach the mirror-symmetry loss for `ppo_grad` / `ppo_update` (None detaches): `VecEnv.set_policy_mirror_loss`.  One handle only."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("set_policy_mirror_loss needs one handle (sub_batches=1)")
-        self.venv.set_policy_mirror_loss(tables, coef)
-
-    def set_policy_mirror_dup(self, tables) -> None:
-        """attach the mirror-duplicated rows for `ppo_grad` / `ppo_update` (None detaches): `VecEnv.set_policy_mirror_dup`.  One handle only."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("set_policy_mirror_dup needs one handle (sub_batches=1)")
-        self.venv.set_policy_mirror_dup(tables)
-
-    def ppo_grad(self, obs, action, old_logp, adv, returns, *args, **kw) -> dict:
-        """PPO's minibatch loss and its gradient over the rollout storage, four launches: `VecEnv.ppo_grad` -- of the symmetric network
-        where the attached policy carries mirror tables (`symmetric_policy`).  One handle only."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("ppo_grad needs one handle (sub_batches=1)")
-        return self.venv.ppo_grad(obs, action, old_logp, adv, returns, *args, **kw)
-
-    def adam_step(self, params, grad, state, **kw) -> None:
-        """clip_grad_norm_, Adam's step and update_policy on the flat parameter tensor, three launches: `VecEnv.adam_step`.  One handle only."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("adam_step needs one handle (sub_batches=1)")
-        self.venv.adam_step(params, grad, state, **kw)
-
-    def ppo_update(self, obs, action, old_logp, adv, returns, params, state, minibatch_rows, epochs, **kw) -> dict:
-        """a2c-ppo-acktr's `agent.update(rollouts)` over the rollout storage as one call: `VecEnv.ppo_update`.  One handle only."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("ppo_update needs one handle (sub_batches=1)")
-        return self.venv.ppo_update(obs, action, old_logp, adv, returns, params, state, minibatch_rows, epochs, **kw)
+    # (distill_grad, distill_update, finish_rollout, update_obs_stats, ppo_grad, adam_step, ppo_update, symmetric_policy, policy_mirror_tables,
+    # set_policy_mirror_loss and set_policy_mirror_dup are the one handle's: _FORWARDED, below the class)
 
     def _act_launch(self, into):
         """the launcher _step_obs() calls: act_step with the policy's outputs going to `into`'s "action" / "logp" / "value" (this object's
@@ -563,9 +491,7 @@ class TorchVecEnv:
         planner env: act_plan_step); `into(t)` may
         carry "action" / "logp" / "value" rows, and `sink`'s `action` is the tensor the policy wrote.  `update_policy` between replays
         changes what the graph computes: no recapture."""
-        if not hasattr(self.venv, "lib"):
-            raise NotImplementedError("capture_rollout needs one handle (sub_batches=1): sub-batches step on streams of their own")
-        venv, dev = self.venv, self.device
+        venv, dev = self._one("capture_rollout"), self.device       # (sub-batches step on streams of their own)
         if self._want_terminal:          # the graph bakes the buffer's address into its launches: a fixed one, not a record slot of step()
             if self.rollout_terminal_obs is None:
                 self.rollout_terminal_obs = torch.zeros_like(self._term_bufs[0])
@@ -579,31 +505,18 @@ class TorchVecEnv:
             act_of = lambda o, t: policy(o)
 
         def body(t):
-            if act_of is None:       # the device policy: its input row is where the last step wrote its observation
-                d = {} if into is None else into(t)
-                launch = self._act_launch(d)
-                if "masks" in d or "bad_masks" in d:
-                    self.masks, self.bad_masks = d.get("masks", self.masks), d.get("bad_masks", self.bad_masks)
-                    venv.episode_masks_into(self.masks, self.bad_masks)
-                o, r = self._step_obs(obs if into is None else into(t - 1)["obs"], obs_out=d.get("obs"), rew_out=d.get("reward"), launch=launch)[:2]
-                if into is None:
-                    o, r = obs, rew
-                if sink is not None:
-                    sink(t, o, r, self.masks, self.bad_masks, self.last_act["action"])
-                return
+            d = {} if into is None else into(t)
+            row = obs if into is None else into(t - 1)["obs"]        # the policy's input: where the last step wrote its observation
+            if act_of is None:       # the device policy reads the row itself: the step is act_step's launches
+                x, launch = row, self._act_launch(d)
+            else:                    # a torch policy has produced the action: the step is step()'s launch
+                x, launch = act_of(row, t), None
+            self._masks_into(d)
+            o, r = self._step_obs(x, obs_out=d.get("obs"), rew_out=d.get("reward"), launch=launch)[:2]
             if into is None:
-                action = act_of(obs, t)
-                self._step_obs(action)
                 o, r = obs, rew
-            else:
-                action = act_of(into(t - 1)["obs"], t)
-                d = into(t)
-                if "masks" in d or "bad_masks" in d:
-                    self.masks, self.bad_masks = d.get("masks", self.masks), d.get("bad_masks", self.bad_masks)
-                    venv.episode_masks_into(self.masks, self.bad_masks)
-                o, r = self._step_obs(action, obs_out=d.get("obs"), rew_out=d.get("reward"))[:2]
             if sink is not None:
-                sink(t, o, r, self.masks, self.bad_masks, action)
+                sink(t, o, r, self.masks, self.bad_masks, self.last_act["action"] if act_of is None else x)
 
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -652,6 +565,35 @@ class TorchVecEnv:
 
     def evaluation_mode(self, on=True):
         self.venv.evaluation_mode(on)
+
+
+# Methods of the one handle that the trainer calls on `envs` unchanged: name -> what the call is (the arguments and the rest: VecEnv's docstring)
+_FORWARDED = {
+    "distill_grad": "the regression gradient over stored rows and their targets, four launches",
+    "distill_update": "epochs x minibatches of [shuffle, distill_grad, adam_step] over the stored rows as one call",
+    "finish_rollout": "returns, advantages (normalised by default) and their moments from the rollout storage, two launches",
+    "update_obs_stats": "merge a rollout's observation rows into a `rollout.ObsStats`, two launches",
+    "ppo_grad": "PPO's minibatch loss and its gradient over the rollout storage, four launches -- of the symmetric network where the attached "
+                "policy carries mirror tables (`symmetric_policy`)",
+    "adam_step": "clip_grad_norm_, Adam's step and update_policy on the flat parameter tensor, three launches",
+    "ppo_update": "a2c-ppo-acktr's `agent.update(rollouts)` over the rollout storage as one call",
+    "symmetric_policy": "a copy of `policy` with this env's mirror tables, the attached height scan's pattern included",
+    "policy_mirror_tables": "this env's mirror tables for `policy`, the attached height scan's pattern included",
+    "set_policy_mirror_loss": "attach the mirror-symmetry loss for `ppo_grad` / `ppo_update` (None detaches)",
+    "set_policy_mirror_dup": "attach the mirror-duplicated rows for `ppo_grad` / `ppo_update` (None detaches)",
+}
+
+
+def _forwarder(name: str, what: str):
+    def method(self, *args, **kw):
+        return getattr(self._one(name), name)(*args, **kw)
+    method.__name__, method.__qualname__ = name, f"TorchVecEnv.{name}"
+    method.__doc__ = f"{what}: `VecEnv.{name}`.  One handle only."
+    return method
+
+
+for _name, _what in _FORWARDED.items():
+    setattr(TorchVecEnv, _name, _forwarder(_name, _what))
 
 
 def make_vec_envs(env_name: str, seed: int, num_processes: int, log_dir=None, device=None, **kw) -> TorchVecEnv:

@@ -92,6 +92,11 @@ def compile_model_for(env_or_task, **kw) -> M.MoccaModel:
     return _MODELS[env_id](**kw)
 
 
+def _ptr(x):
+    """a tensor's device pointer as the library takes it; None stays None"""
+    return None if x is None else C.c_void_p(x.data_ptr())
+
+
 class VecEnv:
     """N independent copies of a registered env id, stepped together.
 
@@ -189,7 +194,8 @@ class VecEnv:
     # .contiguous(), the caller's reads of what a getter returns) run on torch's CURRENT stream.  Every method except step() orders the
     # two, stream against stream, never through the host: _in() before a call that consumes caller tensors, _out() after a call whose
     # result the caller will read.  step() is the hot path and stays unordered on a pinned stream: the caller orders it (SubBatchedVecEnv's
-    # step_async / wait do), or passes ready, contiguous float32 device tensors and reads the outputs after a synchronize.
+    # step_async / wait do), or passes ready, contiguous float32 device tensors and reads the outputs after a synchronize.  The bracket is
+    # written once, in _call(): every entry point that takes a stream goes through it, except the two launchers of the hot path.
     def _in(self):
         if self.stream is not None:
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -200,6 +206,19 @@ class VecEnv:
 
     def _sync(self):
         (self.stream if self.stream is not None else torch.cuda.current_stream(self.device)).synchronize()
+
+    def _call(self, fn, *args, wait: bool = True, then: Optional[str] = "out") -> None:
+        """The bracket above around one library call that takes a stream: _in() (unless `wait` is False: a call that reads nothing of the
+        caller's), `fn(handle, *args, stream)` with every tensor passed as its device pointer (None stays None), then _out(), _sync()
+        (`then="sync"`: the caller's temporaries must outlive the launch) or nothing (`then=None`: another call follows).  `args` keeps the
+        tensors alive across the call."""
+        if wait:
+            self._in()
+        _lib.check(fn(self.h, *[C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args], self._stream()), self.h)
+        if then == "out":
+            self._out()
+        elif then == "sync":
+            self._sync()
 
     def close(self):
         if getattr(self, "h", None):
@@ -282,9 +301,7 @@ class VecEnv:
             raise ValueError("gain must be finite and > 0")
         if first < 0 or count < 1 or first + count > bank["n_fields"]:
             raise ValueError(f"fields {first} .. {first + count - 1} are not inside the bank of {bank['n_fields']}")
-        self._in()
-        _lib.check(self.lib.mocca_generate_heightfields(self.h, first, count, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_peaks), float(gain), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_generate_heightfields, first, count, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_peaks), float(gain))
 
     def set_env_fields(self, ids=None, redraw_at_reset: bool = False) -> None:
         """Put env e on field ids[e] of the bank (None: every env on field 0).  `redraw_at_reset`: every reset, auto-reset included, draws
@@ -295,17 +312,13 @@ class VecEnv:
             ev = torch.as_tensor(ids, dtype=torch.int32).reshape(-1).to(self.device).contiguous()
             if ev.numel() != self.n_envs:
                 raise ValueError("set_env_fields: one field index per env")
-        self._in()
-        _lib.check(self.lib.mocca_set_env_fields(self.h, None if ev is None else C.c_void_p(ev.data_ptr()), 1 if redraw_at_reset else 0, self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_set_env_fields, ev, 1 if redraw_at_reset else 0)
 
     def env_fields(self) -> torch.Tensor:
         """The field every env stands on: int32 [N] on the device."""
         self._need_bank("env_fields")
         out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
-        self._in()
-        _lib.check(self.lib.mocca_get_env_fields(self.h, C.c_void_p(out.data_ptr()), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_get_env_fields, out)
         return out
 
     def height_fields(self, first: int = 0, count: Optional[int] = None) -> torch.Tensor:
@@ -316,9 +329,7 @@ class VecEnv:
         if first < 0 or count < 1 or first + count > bank["n_fields"]:
             raise ValueError(f"fields {first} .. {first + count - 1} are not inside the bank of {bank['n_fields']}")
         out = torch.empty(count, bank["rows"], bank["cols"], dtype=torch.float32, device=self.device)
-        self._in()
-        _lib.check(self.lib.mocca_get_heightfields(self.h, first, count, C.c_void_p(out.data_ptr()), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_get_heightfields, first, count, out)
         return out
 
     # ---- the planner envs' base controller (env_locomotion.py:1029-1040, :1091-1101) ----
@@ -379,27 +390,45 @@ class VecEnv:
         """(action [N, 21] before apply_action's clip, value [N]) of the controller in the last plan_step(): copies, on the device."""
         if self.base_controller is None:
             raise _lib.MoccaError("base_outputs needs a base controller (set_base_controller)")
-        _lib.check(self.lib.mocca_get_base_outputs(self.h, C.c_void_p(self._base_action.data_ptr()), C.c_void_p(self._base_value.data_ptr()),
-                                                   self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_get_base_outputs, self._base_action, self._base_value, wait=False)   # (buffers of this object's: nothing to wait for)
         return self._base_action.clone(), self._base_value.clone()
 
     # ---- the trainer's own policy on the device (include/mocca.h mocca_set_policy / mocca_update_policy / mocca_act / mocca_act_step) ----
     policy = None
     mirror_loss = None   # (tables, coef) while set_policy_mirror_loss has one attached
     mirror_dup = None    # tables while set_policy_mirror_dup has them attached
+    teacher = None
+    _pol_action = None   # act_step()'s own action buffer, made on first use
+    _scan_points = None  # the pattern set_height_scan attached
+    _depth_cam = None    # the camera set_depth_camera attached
+    _host_np = None      # host_mirror()'s numpy views, made on first use
+
+    def _set_slot(self, fn, policy) -> None:
+        """set_policy() / set_teacher(): the layer table and shapes of `policy` (None: detach) to `fn`, mocca_set_policy or mocca_set_teacher"""
+        if policy is None:
+            _lib.check(fn(self.h, None, 0, 0, 0, 0.0), self.h)
+            return
+        table = np.ascontiguousarray(policy.table(), np.int32)
+        _lib.check(fn(self.h, table.ctypes.data_as(C.c_void_p), table.shape[0], int(policy.in_dim), int(policy.act_dim), float(policy.clip)), self.h)
+
+    def _update_slot(self, fn, params) -> None:
+        """update_policy() / update_teacher(): a `DevicePolicy`'s or a flat tensor's weights to `fn`, mocca_update_policy or mocca_update_teacher"""
+        flat = torch.from_numpy(params.flat_params()) if hasattr(params, "flat_params") else params
+        flat = flat.detach().to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
+        self._call(fn, flat, flat.numel())       # `flat` may be freed (and its memory reused on the current stream) as soon as this returns
+
+    @property
+    def _mirrored(self) -> bool:
+        """does the attached policy carry a mirror attachment: symmetry, a mirror loss or duplicated rows"""
+        return getattr(self.policy, "symmetry", None) is not None or self.mirror_loss is not None or self.mirror_dup is not None
 
     def set_policy(self, policy) -> None:
         """Attach a `policy.DevicePolicy` (None detaches): its shapes size the kernel's image, its weights are uploaded (update_policy).
         May synchronise."""
-        if policy is None:
-            _lib.check(self.lib.mocca_set_policy(self.h, None, 0, 0, 0, 0.0), self.h)
-            self.policy = self.mirror_loss = self.mirror_dup = None
-            return
-        table = np.ascontiguousarray(policy.table(), np.int32)
-        _lib.check(self.lib.mocca_set_policy(self.h, table.ctypes.data_as(C.c_void_p), table.shape[0], int(policy.in_dim), int(policy.act_dim),
-                                             float(policy.clip)), self.h)
+        self._set_slot(self.lib.mocca_set_policy, policy)
         self.policy, self.mirror_loss, self.mirror_dup = policy, None, None   # mocca_set_policy has dropped every attachment
+        if policy is None:
+            return
         self.update_policy(policy)
         if getattr(policy, "symmetry", None) is not None:      # after the shapes: mocca_set_policy has dropped whatever was attached
             self.set_policy_symmetry(policy.symmetry)
@@ -454,7 +483,7 @@ class VecEnv:
         mi = self.get_mirror_indices()
         if isinstance(mi, dict):
             raise NotImplementedError("the Cassie mocap envs publish a dict of index lists (env_cassie.py:554-571), not get_mirror_indices()'s six")
-        scan, cam = getattr(self, "_scan_points", None), getattr(self, "_depth_cam", None)
+        scan, cam = self._scan_points, self._depth_cam
         ns, nd = (0 if scan is None else len(scan)), (0 if cam is None else cam.width * cam.height)
         if policy.in_dim == self.obs_dim:                                       # [obs]
             scan = cam = None
@@ -483,11 +512,7 @@ class VecEnv:
         log_std and observation statistics).  One repack kernel on the stream; nothing synchronises."""
         if self.policy is None:
             raise _lib.MoccaError("update_policy needs a policy (set_policy)")
-        flat = torch.from_numpy(params.flat_params()) if hasattr(params, "flat_params") else params
-        flat = flat.detach().to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
-        self._in()
-        _lib.check(self.lib.mocca_update_policy(self.h, C.c_void_p(flat.data_ptr()), flat.numel(), self._stream()), self.h)
-        self._out()       # `flat` may be freed (and its memory reused on the current stream) as soon as this returns
+        self._update_slot(self.lib.mocca_update_policy, params)
 
     def _act_args(self, obs, eps, deterministic, out, logp, value):
         """check the tensors of act() / act_step() -> (ctypes arguments in_dev .. mean_dev, the output dict)"""
@@ -512,10 +537,9 @@ class VecEnv:
             t = out.get(k)
             if t is not None and (t.numel() != numel or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()):
                 raise ValueError(f"out[{k!r}] must be a contiguous float32 tensor of {numel} elements on the env's device")
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
         stride = obs.stride(0) if n > 1 else max(obs.stride(0), obs.shape[1])
-        return (ptr(obs), int(stride), ptr(eps), int(bool(deterministic)), ptr(out["action"]), ptr(out.get("logp")), ptr(out.get("value")),
-                ptr(out.get("mean"))), out
+        return (_ptr(obs), int(stride), _ptr(eps), int(bool(deterministic)), _ptr(out["action"]), _ptr(out.get("logp")), _ptr(out.get("value")),
+                _ptr(out.get("mean"))), out
 
     def act(self, obs: torch.Tensor, eps: Optional[torch.Tensor] = None, deterministic: bool = False, out: Optional[dict] = None) -> dict:
         """`actor_critic.act(obs)` as one launch: -> {"action" [N, A], "logp" [N], "value" [N]} (and "mean" [N, A] when `out` has that key),
@@ -524,9 +548,7 @@ class VecEnv:
         episode counters) -- two calls without a step() in between draw the same noise.  `out`: any of the output tensors, caller-owned
         (rows of a trainer's rollout storage; "logp" / "value" may be [N, 1])."""
         args, out = self._act_args(obs, eps, deterministic, out, True, True)
-        self._in()
-        _lib.check(self.lib.mocca_act(self.h, *args, self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_act, *args)
         return out
 
     def act_step(self, obs: torch.Tensor, eps: Optional[torch.Tensor] = None, deterministic: bool = False, action_out: Optional[torch.Tensor] = None,
@@ -551,7 +573,7 @@ class VecEnv:
         """act_step() / act_plan_step(): check the tensors, launch `entry` (mocca_act_step or mocca_act_plan_step: same argument list)"""
         given = {k: v for k, v in (("action", action_out), ("logp", logp_out), ("value", value_out)) if v is not None}
         if "action" not in given and self.policy is not None:
-            if getattr(self, "_pol_action", None) is None or self._pol_action.shape[1] != self.policy.act_dim:
+            if self._pol_action is None or self._pol_action.shape[1] != self.policy.act_dim:
                 self._pol_action = torch.zeros(self.n_envs, self.policy.act_dim, dtype=torch.float32, device=self.device)
             given["action"] = self._pol_action
         args, out = self._act_args(obs, eps, deterministic, given, False, False)
@@ -581,11 +603,8 @@ class VecEnv:
         returns = torch.empty(reward.shape, **f32) if returns is None else returns
         adv = torch.empty(reward.shape, **f32) if adv is None else adv
         moments = torch.empty(2, **f32) if moments is None else moments
-        ptr = lambda x: C.c_void_p(x.data_ptr())
-        self._in()
-        _lib.check(self.lib.mocca_gae(self.h, ptr(reward), ptr(value), ptr(masks), ptr(bad_masks), T, float(gamma), float(lam), float(reward_scale),
-                                      ptr(returns), ptr(adv), int(bool(normalise)), float(adv_eps), ptr(moments), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_gae, reward, value, masks, bad_masks, T, float(gamma), float(lam), float(reward_scale), returns, adv,
+                   int(bool(normalise)), float(adv_eps), moments)
         return {"returns": returns, "adv": adv, "moments": moments}
 
     def update_obs_stats(self, stats, rows: torch.Tensor, mean_out: Optional[torch.Tensor] = None, inv_std_out: Optional[torch.Tensor] = None) -> None:
@@ -600,11 +619,7 @@ class VecEnv:
         n_rows, stride = _ro.rows_2d(rows, stats.dim)
         _ro.stats_out("mean_out", mean_out, stats.dim, self.device)
         _ro.stats_out("inv_std_out", inv_std_out, stats.dim, self.device)
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        self._in()
-        _lib.check(self.lib.mocca_obs_stats(self.h, ptr(rows), n_rows, stride, stats.dim, ptr(stats.state), float(stats.eps), ptr(mean_out),
-                                            ptr(inv_std_out), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_obs_stats, rows, n_rows, stride, stats.dim, stats.state, float(stats.eps), mean_out, inv_std_out)
 
     # ---- a PPO minibatch step on the device (include/mocca.h mocca_ppo_grad / mocca_ppo_grad_sym / mocca_ppo_grad_mirror / mocca_ppo_grad_dup) ----
     def ppo_grad(self, obs: torch.Tensor, action: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor, returns: torch.Tensor,
@@ -631,17 +646,17 @@ class VecEnv:
         symmetric = getattr(self.policy, "symmetry", None) is not None
         mirror, dup = self.mirror_loss is not None, self.mirror_dup is not None
         _, stride, n_batch = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, idx, old_value, clip, value_coef,
-                                          entropy_coef, value_clip, grad, stats, symmetric=symmetric or mirror or dup)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        grad = torch.empty(self.policy.n_head(), **f32) if grad is None else grad
-        stats = torch.empty(8, **f32) if stats is None else stats
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        self._in()
+                                          entropy_coef, value_clip, grad, stats, symmetric=self._mirrored)
+        out = self._grad_out(grad, stats)
         call = self.lib.mocca_ppo_grad_dup if dup else self.lib.mocca_ppo_grad_mirror if mirror else self.lib.mocca_ppo_grad_sym if symmetric else self.lib.mocca_ppo_grad
-        _lib.check(call(self.h, ptr(obs), stride, ptr(action), ptr(old_logp), ptr(adv), ptr(returns), ptr(old_value), ptr(idx), n_batch, float(clip),
-                        float(value_coef), float(entropy_coef), int(bool(value_clip)), ptr(grad), ptr(stats), self._stream()), self.h)
-        self._out()
-        return {"grad": grad, "stats": stats}
+        self._call(call, obs, stride, action, old_logp, adv, returns, old_value, idx, n_batch, float(clip), float(value_coef), float(entropy_coef),
+                   int(bool(value_clip)), out["grad"], out["stats"])
+        return out
+
+    def _grad_out(self, grad, stats) -> dict:
+        """what ppo_grad() / distill_grad() write and return: the caller's `grad` / `stats`, allocated where none is given"""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        return {"grad": torch.empty(self.policy.n_head(), **f32) if grad is None else grad, "stats": torch.empty(8, **f32) if stats is None else stats}
 
     # ---- the optimiser step and the whole update on the device (include/mocca.h mocca_adam_step / mocca_ppo_update) ----
     def adam_step(self, params: torch.Tensor, grad: torch.Tensor, state, n_params: Optional[int] = None, lr: float = 3e-4,
@@ -654,11 +669,8 @@ class VecEnv:
         if self.policy is None:
             raise _lib.MoccaError("adam_step needs a policy (set_policy)")
         n_params = _ro.adam_args(self.policy, self.device, params, grad, state, n_params, lr, betas, eps, max_grad_norm)
-        ptr = lambda x: C.c_void_p(x.data_ptr())
-        self._in()
-        _lib.check(self.lib.mocca_adam_step(self.h, ptr(params), params.numel(), ptr(grad), n_params, ptr(state.moments), ptr(state.clock), float(lr),
-                                            float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_adam_step, params, params.numel(), grad, n_params, state.moments, state.clock, float(lr), float(betas[0]),
+                   float(betas[1]), float(eps), float(max_grad_norm))
 
     def ppo_update(self, obs: torch.Tensor, action: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor, returns: torch.Tensor,
                    params: torch.Tensor, state, minibatch_rows: int, epochs: int, old_value: Optional[torch.Tensor] = None, clip: float = 0.2,
@@ -675,30 +687,30 @@ class VecEnv:
         (the scalars and the seed are baked into the capture)."""
         if self.policy is None:
             raise _lib.MoccaError("ppo_update needs a policy (set_policy)")
-        symmetric = getattr(self.policy, "symmetry", None) is not None or self.mirror_loss is not None or self.mirror_dup is not None   # each halves the row bound
+        symmetric = self._mirrored       # each attachment halves the row bound
         n_rows, stride, _ = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, None, old_value, clip, value_coef,
                                          entropy_coef, value_clip, None, None, symmetric=symmetric)
+        return self._update_loop(self.lib.mocca_ppo_update, (obs, stride, action, old_logp, adv, returns, old_value), n_rows, minibatch_rows, epochs,
+                                 (float(clip), float(value_coef), float(entropy_coef), int(bool(value_clip))), params, state, n_params, lr, betas,
+                                 eps, max_grad_norm, seed, stats, symmetric)
+
+    def _update_loop(self, fn, data, n_rows, minibatch_rows, epochs, coefs, params, state, n_params, lr, betas, eps, max_grad_norm, seed, stats,
+                     symmetric=False) -> dict:
+        """ppo_update() / distill_update() behind the check of their storage: the optimiser's and the loop's own checks, the statistics
+        [epochs * M, 8] and the call `fn(*data, n_rows, minibatch_rows, epochs, *coefs, adam_step's arguments, seed, stats)`"""
         n_params = _ro.adam_args(self.policy, self.device, params, None, state, n_params, lr, betas, eps, max_grad_norm)
         per_epoch = _ro.update_args(n_rows, minibatch_rows, epochs, seed, stats, self.device, symmetric=symmetric)
         if stats is None:
             stats = torch.empty(int(epochs) * per_epoch, 8, dtype=torch.float32, device=self.device)
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        self._in()
-        _lib.check(self.lib.mocca_ppo_update(self.h, ptr(obs), stride, ptr(action), ptr(old_logp), ptr(adv), ptr(returns), ptr(old_value), n_rows,
-                                             int(minibatch_rows), int(epochs), float(clip), float(value_coef), float(entropy_coef),
-                                             int(bool(value_clip)), ptr(params), params.numel(), n_params, ptr(state.moments), ptr(state.clock),
-                                             float(lr), float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm), int(seed), ptr(stats),
-                                             self._stream()), self.h)
-        self._out()
+        self._call(fn, *data, n_rows, int(minibatch_rows), int(epochs), *coefs, params, params.numel(), n_params, state.moments, state.clock,
+                   float(lr), float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm), int(seed), stats)
         return {"stats": stats.view(int(epochs) * per_epoch, 8)}
 
     # ---- teacher-student distillation on the device (include/mocca.h mocca_distill_grad / mocca_distill_update / mocca_set_teacher ..) ----
-    teacher = None
-
     def _no_mirror(self, name: str) -> None:
         if self.policy is None:
             raise _lib.MoccaError(f"{name} needs a policy (set_policy)")
-        if getattr(self.policy, "symmetry", None) is not None or self.mirror_loss is not None or self.mirror_dup is not None:
+        if self._mirrored:
             raise _lib.MoccaError(f"{name}: the policy has a mirror attachment (symmetry, mirror loss or duplicated rows): detach it first")
 
     def distill_grad(self, obs: torch.Tensor, target: torch.Tensor, value_target: Optional[torch.Tensor] = None,
@@ -712,15 +724,10 @@ class VecEnv:
         inputs give the same bits on every run."""
         self._no_mirror("distill_grad")
         _, stride, n_batch = _ro.distill_args(self.policy, self.device, obs, target, value_target, idx, distill_coef, value_coef, grad, stats)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        grad = torch.empty(self.policy.n_head(), **f32) if grad is None else grad
-        stats = torch.empty(8, **f32) if stats is None else stats
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        self._in()
-        _lib.check(self.lib.mocca_distill_grad(self.h, ptr(obs), stride, ptr(target), ptr(value_target), ptr(idx), n_batch, float(distill_coef),
-                                               float(value_coef), ptr(grad), ptr(stats), self._stream()), self.h)
-        self._out()
-        return {"grad": grad, "stats": stats}
+        out = self._grad_out(grad, stats)
+        self._call(self.lib.mocca_distill_grad, obs, stride, target, value_target, idx, n_batch, float(distill_coef), float(value_coef),
+                   out["grad"], out["stats"])
+        return out
 
     def distill_update(self, obs: torch.Tensor, target: torch.Tensor, params: torch.Tensor, state, minibatch_rows: int, epochs: int,
                        value_target: Optional[torch.Tensor] = None, distill_coef: float = 1.0, value_coef: float = 0.5,
@@ -732,44 +739,25 @@ class VecEnv:
         coefficient applied.  Nothing synchronises or is read on the host; capturable after one warm call of the same shapes."""
         self._no_mirror("distill_update")
         n_rows, stride, _ = _ro.distill_args(self.policy, self.device, obs, target, value_target, None, distill_coef, value_coef, None, None)
-        n_params = _ro.adam_args(self.policy, self.device, params, None, state, n_params, lr, betas, eps, max_grad_norm)
-        per_epoch = _ro.update_args(n_rows, minibatch_rows, epochs, seed, stats, self.device)
-        if stats is None:
-            stats = torch.empty(int(epochs) * per_epoch, 8, dtype=torch.float32, device=self.device)
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        self._in()
-        _lib.check(self.lib.mocca_distill_update(self.h, ptr(obs), stride, ptr(target), ptr(value_target), n_rows, int(minibatch_rows), int(epochs),
-                                                 float(distill_coef), float(value_coef), ptr(params), params.numel(), n_params,
-                                                 ptr(state.moments), ptr(state.clock), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                                 float(max_grad_norm), int(seed), ptr(stats), self._stream()), self.h)
-        self._out()
-        return {"stats": stats.view(int(epochs) * per_epoch, 8)}
+        return self._update_loop(self.lib.mocca_distill_update, (obs, stride, target, value_target), n_rows, minibatch_rows, epochs,
+                                 (float(distill_coef), float(value_coef)), params, state, n_params, lr, betas, eps, max_grad_norm, seed, stats)
 
     def set_teacher(self, policy) -> None:
         """Attach a frozen `policy.DevicePolicy` as the TEACHER (None detaches): a second image beside the policy of set_policy, which it
         may differ from in in_dim and layers; its weights are uploaded (update_teacher).  A policy carrying `symmetry` is refused.  The
         attached policy, its mirror attachment, act() and the gradient calls are untouched.  May synchronise."""
-        if policy is None:
-            _lib.check(self.lib.mocca_set_teacher(self.h, None, 0, 0, 0, 0.0), self.h)
-            self.teacher = None
-            return
         if getattr(policy, "symmetry", None) is not None:
             raise ValueError("set_teacher: the teacher is a plain policy; one carrying `symmetry` is not supported")
-        table = np.ascontiguousarray(policy.table(), np.int32)
-        _lib.check(self.lib.mocca_set_teacher(self.h, table.ctypes.data_as(C.c_void_p), table.shape[0], int(policy.in_dim), int(policy.act_dim),
-                                              float(policy.clip)), self.h)
+        self._set_slot(self.lib.mocca_set_teacher, policy)
         self.teacher = policy
-        self.update_teacher(policy)
+        if policy is not None:
+            self.update_teacher(policy)
 
     def update_teacher(self, params) -> None:
         """New weights for the teacher: a `DevicePolicy` of the same shapes or a flat float32 tensor, as `update_policy` takes them."""
         if self.teacher is None:
             raise _lib.MoccaError("update_teacher needs a teacher (set_teacher)")
-        flat = torch.from_numpy(params.flat_params()) if hasattr(params, "flat_params") else params
-        flat = flat.detach().to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
-        self._in()
-        _lib.check(self.lib.mocca_update_teacher(self.h, C.c_void_p(flat.data_ptr()), flat.numel(), self._stream()), self.h)
-        self._out()
+        self._update_slot(self.lib.mocca_update_teacher, params)
 
     def teacher_act(self, rows: torch.Tensor, mean: Optional[torch.Tensor] = None, value: Optional[torch.Tensor] = None) -> dict:
         """The teacher's actor mean and value on `rows` [n, >= teacher.in_dim] (float32 on the env's device, contiguous last dimension; any
@@ -788,10 +776,7 @@ class VecEnv:
         _ro.stats_out("mean", mean, n * t.act_dim, self.device)
         _ro.stats_out("value", value, n, self.device)
         stride = rows.stride(0) if n > 1 else max(rows.stride(0), rows.shape[1])
-        self._in()
-        _lib.check(self.lib.mocca_teacher_act(self.h, C.c_void_p(rows.data_ptr()), int(stride), n, C.c_void_p(mean.data_ptr()),
-                                              C.c_void_p(value.data_ptr()), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_teacher_act, rows, int(stride), n, mean, value)
         return {"mean": mean, "value": value}
 
     # ---- the reference's env-level setters, batched (env_base.py:103-118, env_locomotion.py:76-77,224-282) ----
@@ -842,9 +827,7 @@ class VecEnv:
         v = torch.as_tensor(values, dtype=torch.float32).to(self.device).contiguous().reshape(-1)
         if v.numel() != (1 if broadcast else self.n_envs):
             raise ValueError("values must hold one float per env (or one float with broadcast=True)")
-        self._in()
-        _lib.check(self.lib.mocca_set_param_v(self.h, pid, C.c_void_p(v.data_ptr()), int(broadcast), self._stream()), self.h)
-        self._out()       # `v` may be freed (and its memory reused on the current stream) as soon as this returns
+        self._call(self.lib.mocca_set_param_v, pid, v, int(broadcast))       # `v` may be freed (and its memory reused on the current stream) as soon as this returns
 
     def seed(self, seed: int, rewind: bool = True):
         """Philox key of the in-kernel draws (gym's env.seed(s), env_base.py:164-166).  With rewind (default) the per-env episode
@@ -925,22 +908,14 @@ class VecEnv:
         actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
         i32 = lambda x: None if x is None else torch.as_tensor(x, dtype=torch.int32).to(self.device).contiguous()
         touch, target, body = i32(touch), i32(target), i32(body)
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        self._in()
-        _lib.check(self.lib.mocca_task_step(self.h, C.c_void_p(actions.data_ptr()), ptr(touch), ptr(target), ptr(body),
-                                            C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.rew.data_ptr()),
-                                            C.c_void_p(self.done.data_ptr()), C.c_void_p(self.info.data_ptr()), self._stream()), self.h)
-        self._sync()   # the int32 temporaries above must outlive the launch
+        self._call(self.lib.mocca_task_step, actions, touch, target, body, self.obs, self.rew, self.done, self.info,
+                   then="sync")   # the int32 temporaries above must outlive the launch
         return self.obs, self.rew, self.done, self.info
 
     def reset(self, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        mp = None
         if mask is not None:
             mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            mp = C.c_void_p(mask.data_ptr())
-        self._in()
-        _lib.check(self.lib.mocca_reset(self.h, mp, self.seed_value, C.c_void_p(self.obs.data_ptr()), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_reset, mask, self.seed_value, self.obs)
         return self.obs
 
     def step(self, actions: torch.Tensor, obs_out: Optional[torch.Tensor] = None,
@@ -986,7 +961,7 @@ class VecEnv:
         """Lay obs / rew / info / state / task / done out in ONE device buffer with ONE pinned host image, so that a caller on the host
         pays one upload, one download and one synchronize per step (`step_host`) instead of one blocking copy per quantity.  The
         tensors `obs`, `rew`, `done`, `info` become views into that buffer.  Returns the numpy views of the host image."""
-        if getattr(self, "_host_np", None) is not None:
+        if self._host_np is not None:
             return self._host_np
         n = self.n_envs
         parts = [("obs", n * self.obs_dim, torch.float32, np.float32, (n, self.obs_dim)), ("rew", n, torch.float32, np.float32, (n,)),
@@ -1013,9 +988,8 @@ class VecEnv:
 
     def _download(self) -> dict:
         d = self._dev_views
-        _lib.check(self.lib.mocca_get_state(self.h, C.c_void_p(d["state"].data_ptr()), self._stream()), self.h)
-        _lib.check(self.lib.mocca_get_task(self.h, C.c_void_p(d["task"].data_ptr()), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_get_state, d["state"], wait=False, then=None)    # (behind the step / reset / observe that the caller issued)
+        self._call(self.lib.mocca_get_task, d["task"], wait=False)
         self._pack_host.copy_(self._pack, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         return self._host_np
@@ -1042,50 +1016,36 @@ class VecEnv:
 
     def observe(self) -> torch.Tensor:
         """calc_state() + observation tail of the current state, no stepping (include/mocca.h mocca_observe)."""
-        self._in()
-        _lib.check(self.lib.mocca_observe(self.h, C.c_void_p(self.obs.data_ptr()), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_observe, self.obs)
         return self.obs
 
     # ---- snapshots (saveState/restoreState role; used by the parity tests) ----
     def get_state(self) -> torch.Tensor:
         st = torch.empty(self.n_envs, self.state_dim, dtype=torch.float32, device=self.device)
-        self._in()      # (st's memory may have been in use on the current stream a moment ago)
-        _lib.check(self.lib.mocca_get_state(self.h, C.c_void_p(st.data_ptr()), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_get_state, st)      # (waits first: st's memory may have been in use on the current stream a moment ago)
         return st
 
     def set_state(self, st) -> None:
         st = torch.as_tensor(st, dtype=torch.float32).to(self.device).contiguous().reshape(self.n_envs, self.state_dim)
-        self._in()
-        _lib.check(self.lib.mocca_set_state(self.h, C.c_void_p(st.data_ptr()), self._stream()), self.h)
-        self._sync()
+        self._call(self.lib.mocca_set_state, st, then="sync")
 
     def get_task(self) -> torch.Tensor:
         t = torch.empty(self.n_envs, M.TASK_WORDS, dtype=torch.int32, device=self.device)
-        self._in()
-        _lib.check(self.lib.mocca_get_task(self.h, C.c_void_p(t.data_ptr()), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_get_task, t)
         return t
 
     def set_task(self, t: torch.Tensor) -> None:
         t = t.to(device=self.device, dtype=torch.int32).contiguous().reshape(self.n_envs, M.TASK_WORDS)
-        self._in()
-        _lib.check(self.lib.mocca_set_task(self.h, C.c_void_p(t.data_ptr()), self._stream()), self.h)
-        self._sync()
+        self._call(self.lib.mocca_set_task, t, then="sync")
 
     def get_terrain(self) -> torch.Tensor:
         t = torch.empty(self.n_envs, 128, dtype=torch.float32, device=self.device)
-        self._in()
-        _lib.check(self.lib.mocca_get_terrain(self.h, C.c_void_p(t.data_ptr()), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_get_terrain, t)
         return t
 
     def set_terrain(self, t) -> None:
         t = torch.as_tensor(t, dtype=torch.float32).to(self.device).contiguous().reshape(self.n_envs, 128)
-        self._in()
-        _lib.check(self.lib.mocca_set_terrain(self.h, C.c_void_p(t.data_ptr()), self._stream()), self.h)
-        self._sync()
+        self._call(self.lib.mocca_set_terrain, t, then="sync")
 
     # ---- where the links are, what an env looks like (include/mocca.h mocca_get_link_frames / mocca_render) ----
     def link_frames(self, envs=None) -> torch.Tensor:
@@ -1093,9 +1053,7 @@ class VecEnv:
         world <- body), origin in world (3), centre of mass in world (3) -- the order of the oracle's link_frames.  One small kernel;
         nothing synchronises."""
         fr = torch.empty(self.n_envs, int(self.model.n_bodies), 15, dtype=torch.float32, device=self.device)
-        self._in()
-        _lib.check(self.lib.mocca_get_link_frames(self.h, C.c_void_p(fr.data_ptr()), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_get_link_frames, fr)
         if envs is None:
             return fr
         return fr[torch.as_tensor(envs, dtype=torch.long).to(self.device)]
@@ -1126,10 +1084,7 @@ class VecEnv:
         rgb = torch.empty(k, height, width, 3, dtype=torch.uint8, device=self.device)
         dep = torch.empty(k, height, width, dtype=torch.float32, device=self.device) if depth else None
         idt = torch.empty(k, height, width, dtype=torch.int32, device=self.device) if ids else None
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        self._in()
-        _lib.check(self.lib.mocca_render(self.h, ptr(ev), k, ptr(cams), int(width), int(height), ptr(rgb), ptr(dep), ptr(idt), self._stream()), self.h)
-        self._out()
+        self._call(self.lib.mocca_render, ev, k, cams, int(width), int(height), rgb, dep, idt)
         if not depth and not ids:
             return rgb
         return tuple(x for x in (rgb, dep, idt) if x is not None)
@@ -1163,7 +1118,11 @@ class VecEnv:
         p = self.scan_dim
         if p == 0:
             raise _lib.MoccaError("height_scan needs a pattern (set_height_scan)")
-        width = p
+        return self._sensor_rows(self.lib.mocca_height_scan, p, out, obs)
+
+    def _sensor_rows(self, fn, width: int, out, obs, *extra) -> torch.Tensor:
+        """height_scan() / depth_camera(): check `obs` and `out` (allocated where none is given) for a sensor of `width` floats, launch
+        `fn(out, row stride, obs, *extra)` -> `out`, narrowed to the width written"""
         if obs is not None:
             if obs.shape != (self.n_envs, self.obs_dim) or obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device:
                 raise ValueError("obs must be a contiguous float32 [n_envs, obs_dim] tensor on the env's device")
@@ -1174,10 +1133,7 @@ class VecEnv:
                 or out.stride(1) != 1 or (self.n_envs > 1 and out.stride(0) < out.shape[1]):
             raise ValueError(f"out must be a float32 [n_envs, >= {width}] tensor on the env's device with contiguous rows")
         stride = out.stride(0) if self.n_envs > 1 else max(out.stride(0), width)
-        self._in()
-        _lib.check(self.lib.mocca_height_scan(self.h, C.c_void_p(out.data_ptr()), int(stride), None if obs is None else C.c_void_p(obs.data_ptr()),
-                                              self._stream()), self.h)
-        self._out()
+        self._call(fn, out, int(stride), obs, *extra)
         return out if out.shape[1] == width else out[:, :width]
 
     # ---- the egocentric depth camera (include/mocca.h mocca_set_depth_camera / mocca_depth_camera) ----
@@ -1189,8 +1145,7 @@ class VecEnv:
     @property
     def depth_shape(self):
         """(height, width) of the attached depth camera, None when there is none"""
-        cam = getattr(self, "_depth_cam", None)
-        return None if cam is None else cam.shape
+        return None if self._depth_cam is None else self._depth_cam.shape
 
     def set_depth_camera(self, cam) -> None:
         """Attach a `perception.DepthCamera` (None detaches).  Nothing is allocated and nothing synchronises."""
@@ -1212,25 +1167,10 @@ class VecEnv:
         p = self.depth_dim
         if p == 0:
             raise _lib.MoccaError("depth_camera needs a camera (set_depth_camera)")
-        width = p
-        if obs is not None:
-            if obs.shape != (self.n_envs, self.obs_dim) or obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device:
-                raise ValueError("obs must be a contiguous float32 [n_envs, obs_dim] tensor on the env's device")
-            width += self.obs_dim
-        if out is None:
-            out = torch.empty(self.n_envs, width, dtype=torch.float32, device=self.device)
-        elif out.dim() != 2 or out.shape[0] != self.n_envs or out.shape[1] < width or out.dtype != torch.float32 or out.device != self.device \
-                or out.stride(1) != 1 or (self.n_envs > 1 and out.stride(0) < out.shape[1]):
-            raise ValueError(f"out must be a float32 [n_envs, >= {width}] tensor on the env's device with contiguous rows")
         if cameras_out is not None and (tuple(cameras_out.shape) != (self.n_envs, _lib.CAMERA_FLOATS) or cameras_out.dtype != torch.float32
                                         or not cameras_out.is_contiguous() or cameras_out.device != self.device):
             raise ValueError(f"cameras_out must be a contiguous float32 [n_envs, {_lib.CAMERA_FLOATS}] tensor on the env's device")
-        stride = out.stride(0) if self.n_envs > 1 else max(out.stride(0), width)
-        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        self._in()
-        _lib.check(self.lib.mocca_depth_camera(self.h, ptr(out), int(stride), ptr(obs), ptr(cameras_out), self._stream()), self.h)
-        self._out()
-        return out if out.shape[1] == width else out[:, :width]
+        return self._sensor_rows(self.lib.mocca_depth_camera, p, out, obs, cameras_out)
 
     def kernel_info(self) -> dict:
         v = [C.c_int() for _ in range(5)]
