@@ -7,6 +7,7 @@ from types import SimpleNamespace
 import numpy as np
 
 import ppo_reference as R
+from ppo_reference import gather  # noqa: F401  (re-exported for the tests)
 
 HALF_LOG_2PI = R.HALF_LOG_2PI
 MUTATIONS = ("no_inv_a", "no_factor_2", "flipped_sign", "rolled_targets", "value_leaks_into_actor", "entropy_on_log_std")
@@ -28,21 +29,10 @@ def make_storage(name, p, n_rows, seed=0):
         obs = obs[keep][:n_rows]
         assert obs.shape[0] == n_rows, "too few candidate rows"
     labeller = R.make_policy(name, norm=p.obs_mean is not None, seed=seed + 100)
-    x = _normalise(labeller, np.asarray(obs, np.float64))
+    x = R.normalise64(labeller, obs)
     mu, v = R._forward64(labeller.actor, x)[-1], R._forward64(labeller.critic, x)[-1][:, 0]
     return dict(obs=obs, target=(mu + rng.normal(0, 0.1, mu.shape)).astype(np.float32),
                 value_target=(v + rng.normal(0, 0.1, v.shape)).astype(np.float32))
-
-
-def gather(storage, idx=None, n=None):
-    """the minibatch's rows: storage[idx], or the first n rows"""
-    return {k: (v[:n] if idx is None else v[np.asarray(idx)]) for k, v in storage.items()}
-
-
-def _normalise(p, x):
-    if p.obs_mean is None:
-        return x
-    return np.clip((x - np.asarray(p.obs_mean, np.float64)) * np.asarray(p.inv_std, np.float64), -p.clip, p.clip)
 
 
 def loss_autograd(p, batch, dtype="float64", distill_coef=1.0, value_coef=0.5, use_value=True, mutation=None):
@@ -96,7 +86,7 @@ def loss_autograd(p, batch, dtype="float64", distill_coef=1.0, value_coef=0.5, u
 def grad_by_hand(p, batch, distill_coef=1.0, value_coef=0.5, use_value=True):
     """the per-row lines of include/mocca.h (mocca_distill_grad) in float64 numpy -> the flat gradient"""
     f = lambda k: np.asarray(batch[k], np.float64)
-    x = _normalise(p, f("obs"))
+    x = R.normalise64(p, f("obs"))
     n, a = x.shape[0], p.log_std.size
     za, zc = [], []
     ya, yc = R._forward64(p.actor, x, za), R._forward64(p.critic, x, zc)

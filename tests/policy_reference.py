@@ -9,6 +9,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from controller_reference import act64, error_units, net64, triple  # noqa: F401  (re-exported for the tests)
+from ppo_reference import normalise64  # noqa: F401
 
 HALF_LOG_2PI = 0.5 * np.log(2.0 * np.pi)
 NOISE_SEED = 2024            # the seed of the noise-moment tests, CPU and GPU (test_policy.py checks that the reference holds both bounds at it)
@@ -45,13 +46,6 @@ def random_policy(kind="ppo", in_dim=52, act_dim=21, norm=True, seed=0):
 
 def plausible_inputs(n, in_dim, seed=0):
     return np.random.default_rng([seed, 77]).normal(0, 3.0, (n, in_dim)).astype(np.float32)
-
-
-def normalise64(p, x):
-    x = np.asarray(x, np.float64)
-    if p.obs_mean is None:
-        return x
-    return np.clip((x - np.asarray(p.obs_mean, np.float64)) * np.asarray(p.inv_std, np.float64), -p.clip, p.clip)
 
 
 def forward64(p, x):

@@ -13,7 +13,7 @@ import numpy as np
 
 import ppo_reference as R
 from policy_symmetry_reference import mirror, random_tables  # noqa: F401  (re-exported for the tests)
-from ppo_reference import CLIP, HALF_LOG_2PI
+from ppo_reference import CLIP, HALF_LOG_2PI, critic_slices  # noqa: F401
 from ppo_symmetry_reference import identity_tables  # noqa: F401
 
 MUTATIONS = ("action_not_mirrored",   # the twin keeps the row's action
@@ -27,6 +27,7 @@ MUTATIONS = ("action_not_mirrored",   # the twin keeps the row's action
 HEAD_SCALE = 0.1
 
 
+# not ppo_reference.make_policy under another name: the actor's output layer is scaled by HEAD_SCALE
 def make_policy(name, norm=True, seed=0, acts=None):
     """ppo_reference.make_policy with the actor's output layer scaled by HEAD_SCALE: a policy that is CLOSE TO mirror-symmetric, which is
     what the method assumes of pi_old (a twin borrows its row's old_logp) and what a trainer's small-gain initialisation of that layer
@@ -116,13 +117,6 @@ def loss_autograd_dup(p, tables, batch, dtype="float64", clip=CLIP, value_coef=0
     return SimpleNamespace(grad=grad, stats=stats, logp=logp.detach().numpy(), value=v.detach().numpy(), pre=pre)
 
 
-def _normalise64(p, x):
-    x = np.asarray(x, np.float64)
-    if p.obs_mean is None:
-        return x
-    return np.clip((x - np.asarray(p.obs_mean, np.float64)) * np.asarray(p.inv_std, np.float64), -p.clip, p.clip)
-
-
 def grad_by_hand_dup(p, tables, batch, clip=CLIP, value_coef=0.5, entropy_coef=0.0, value_clip=False):
     """the per-row lines of include/mocca.h in float64 numpy, once per KIND of sample with ib = 1 / (2 B) -> (the flat gradient, the
     twins' share of mean(old_logp - logp)): every weight's, bias's and log_std's gradient is the sum over both kinds"""
@@ -134,7 +128,7 @@ def grad_by_hand_dup(p, tables, batch, clip=CLIP, value_coef=0.5, entropy_coef=0
     adv, ret, olp = f("adv"), f("returns"), f("old_logp")
     parts, share = None, 0.0
     for twin in (False, True):
-        x = _normalise64(p, mirror(f("obs"), in_perm, in_sign) if twin else f("obs"))
+        x = R.normalise64(p, mirror(f("obs"), in_perm, in_sign) if twin else f("obs"))
         a = f("action")[:, act_perm] * act_sign.astype(np.float64) if twin else f("action")
         za, zc = [], []
         ya, yc = R._forward64(p.actor, x, za), R._forward64(p.critic, x, zc)
@@ -177,7 +171,7 @@ def make_storage_dup(p, tables, n_rows, seed=0, clip=CLIP):
     n_c = 6 * n_rows + 256
     obs = rng.normal(0, 3.0, (n_c, in_dim)).astype(np.float32)
     m_obs = obs[:, in_perm] * in_sign.astype(np.float32)
-    x1, x2 = _normalise64(p, obs), _normalise64(p, m_obs)
+    x1, x2 = R.normalise64(p, obs), R.normalise64(p, m_obs)
     pre = []
     mu1, mu2 = R._forward64(p.actor, x1, pre)[-1], R._forward64(p.actor, x2, pre)[-1]
     v1, v2 = R._forward64(p.critic, x1, pre)[-1][:, 0], R._forward64(p.critic, x2, pre)[-1][:, 0]
@@ -220,8 +214,3 @@ def make_storage_dup(p, tables, n_rows, seed=0, clip=CLIP):
     assert keep.size == n_rows, f"too few candidate rows: {int(ok.sum())} of {n_c} for {n_rows}"
     return {k: np.ascontiguousarray(v[keep]) for k, v in dict(obs=obs, action=action, old_logp=old_logp, adv=adv, returns=returns,
                                                               old_value=old_value).items()}
-
-
-def critic_slices(p):
-    """[(start, stop)] of the critic's parameter tensors in flat_params' order"""
-    return R.tensor_slices(p)[2 * len(p.actor):2 * (len(p.actor) + len(p.critic))]

@@ -14,7 +14,7 @@ import numpy as np
 
 import ppo_reference as R
 from policy_symmetry_reference import mirror, random_tables  # noqa: F401  (re-exported for the tests)
-from ppo_reference import CLIP, HALF_LOG_2PI
+from ppo_reference import CLIP, HALF_LOG_2PI, critic_slices  # noqa: F401
 from ppo_symmetry_reference import identity_tables, mirror_storage  # noqa: F401
 
 MUTATIONS = ("mirror_detached",   # f2 is a constant: the mirrored pass gets no gradient
@@ -126,8 +126,3 @@ def grad_by_hand_mirror(p, tables, coef, batch, clip=CLIP, value_coef=0.5, entro
     actor = [a + b for a, b in zip(R._backward64(p.actor, ya1, za1, d_f1), R._backward64(p.actor, ya2, za2, d_f2))]
     parts = actor + R._backward64(p.critic, yc, zc, d_v) + [d_ls]
     return np.concatenate([np.asarray(q).reshape(-1) for q in parts]), float((d * d).sum(-1).mean() / n_act)
-
-
-def critic_slices(p):
-    """[(start, stop)] of the critic's parameter tensors in flat_params' order"""
-    return R.tensor_slices(p)[2 * len(p.actor):2 * (len(p.actor) + len(p.critic))]

@@ -56,6 +56,18 @@ def tensor_slices(p):
     return out
 
 
+def critic_slices(p):
+    """[(start, stop)] of the critic's parameter tensors in flat_params' order"""
+    return tensor_slices(p)[2 * len(p.actor):2 * (len(p.actor) + len(p.critic))]
+
+
+def normalise64(p, x):
+    x = np.asarray(x, np.float64)
+    if p.obs_mean is None:
+        return x
+    return np.clip((x - np.asarray(p.obs_mean, np.float64)) * np.asarray(p.inv_std, np.float64), -p.clip, p.clip)
+
+
 def _activate(torch, x, act):
     return {"identity": lambda v: v, "relu": torch.relu, "tanh": torch.tanh, "softsign": lambda v: v / (1 + v.abs())}[act](x)
 

@@ -2,19 +2,19 @@
 as the yardstick, and the call's contract -- fixed bits, overwritten outputs, graph capture, a scratch shared with mocca_ppo_grad, a
 read-only image, the argument errors.  The checker is tests/distill_reference.py."""
 import ctypes as C
-import json
-import os
+import functools
 
 import numpy as np
 import pytest
 
-import distill_reference as D
+import ppo_grad_cases as G
 import ppo_reference as R
+from ppo_grad_cases import bits as _bits, device_policy as _dp, to_device as _device
 
 pytestmark = pytest.mark.gpu
-BATCHES = (1, 16, 17, 100, 1100)     # one row, the 16-row tile, one past it, several workgroups, three row chunks of launch 2
-KW = dict(distill_coef=0.7, value_coef=0.5)
-STATS = [1, 2, 7]                    # L_v, H, L_d
+MODE = G.MODES["distill"]
+KW = MODE.kw
+_storage = functools.partial(G.storage, MODE)
 
 
 @pytest.fixture(scope="module")
@@ -25,146 +25,21 @@ def env():
     e.close()
 
 
-def _dp(p):
-    from mocca_envs_amd.policy import DevicePolicy
-    return DevicePolicy(p.actor, p.critic, p.log_std, obs_mean=p.obs_mean, inv_std=p.inv_std, clip=p.clip)
-
-
-def _bits(x):
-    return np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "cpu") else x).reshape(-1).view(np.uint8)
-
-
-def _record(section, key, value):
-    out = os.environ.get("MOCCA_TEST_OUT")     # a directory: measured figures are collected there (profiles/distill_parity.json)
-    if not out:
-        return
-    path = os.path.join(out, "distill_parity.json")
-    doc = json.load(open(path)) if os.path.exists(path) else {
-        "what": "tests/test_gpu_distill.py: gradient errors per parameter tensor relative to that tensor's largest |g_f64|, pooled over the "
-                "tensors whose f64 gradient is not identically zero, as [median, p99, max], kernel and float32 autograd yardstick; stats: "
-                "errors of stats[1], stats[2], stats[7] in units of 1e-6 (1 + |x|)", "grad": {}, "stats": {}}
-    doc[section][key] = value
-    with open(path, "w") as f:
-        json.dump(doc, f, indent=1, sort_keys=True)
-        f.write("\n")
-
-
-_STORAGE = {}
-
-
-def _storage(name, norm, n_rows):
-    key = (name, norm, n_rows)
-    if key not in _STORAGE:
-        p = R.make_policy(name, norm=norm, seed=1)
-        _STORAGE[key] = (p, D.make_storage(name, p, n_rows, seed=2))
-    return _STORAGE[key]
-
-
-def _device(st, strided=False):
-    """the storage on the device; strided: obs is a view of wider rows whose other floats are NaN"""
-    import torch
-    d = {k: torch.from_numpy(v).cuda() for k, v in st.items()}
-    if strided:
-        wide = torch.full((st["obs"].shape[0], st["obs"].shape[1] + 13), float("nan"), device="cuda")
-        wide[:, :st["obs"].shape[1]] = d["obs"]
-        d["obs"] = wide[:, :st["obs"].shape[1]]
-    return d
-
-
 def _call(env, d, idx=None, use_value=True, **kw):
-    import torch
-    out = env.distill_grad(d["obs"], d["target"], d["value_target"] if use_value else None,
-                           idx=None if idx is None else torch.from_numpy(idx).cuda(), **{**KW, **kw})
-    torch.cuda.synchronize()
-    return out["grad"].cpu().numpy(), out["stats"].cpu().numpy()
-
-
-def _configs():
-    """(B, idx form, norm, value targets given, strided): every batch size with both index forms and the normalisation on and off; the
-    value targets and the strided obs cycle with periods 3 and 5, so that over the 20 configurations each meets both index forms and both
-    normalisations"""
-    n = 0
-    for b in BATCHES:
-        for form in ("null", "perm"):
-            for norm in (True, False):
-                yield b, form, norm, n % 3 != 1, n % 5 < 2
-                n += 1
+    return G.call(MODE, env, d, idx, use_value, **kw)
 
 
 @pytest.mark.parametrize("name", sorted(R.NETS))
 def test_gradient_and_stats_parity(env, name):
-    """The project's rule (tests/test_gpu_ppo.py).  Per parameter tensor the error against the float64 gradient over that tensor's largest
-    |g_f64|, pooled over the tensors of a configuration (configurations of fewer than 1000 elements are pooled with the next ones of the
-    net); the kernel stays within 3 x float32 autograd at the median, the 99th percentile and the maximum.  A tensor whose f64 gradient
-    is identically zero -- log_std's always, the critic's without value targets -- is not pooled: it must be all +0.0f bits.  stats[1],
-    stats[2] and stats[7] by the same rule in units of 1e-6 (1 + |x|), pooled over the net's configurations; stats[5] within 1e-5 of the
-    f64 sum over grad_dev; stats[0, 3, 4, 6] exactly 0."""
-    failures, pool_got, pool_yard, pool_keys, s_got, s_yard = [], [], [], [], [], []
-
-    def flush():
-        got, yard = R.triple(np.concatenate(pool_got)), R.triple(np.concatenate(pool_yard))
-        key = "+".join(pool_keys)
-        print(f"{name} {key}: kernel {got}, f32 autograd {yard}")
-        _record("grad", f"{name}:{key}", {"kernel_vs_f64": got, "f32_autograd_vs_f64": yard, "elements": int(sum(map(len, pool_got)))})
-        if not R.within(got, yard):
-            failures.append((key, got, yard))
-        pool_got.clear(), pool_yard.clear(), pool_keys.clear()
-
-    configs = list(_configs())
-    for i, (b, form, norm, use_value, strided) in enumerate(configs):
-        n_rows = b if form == "null" else b + 7
-        p, st = _storage(name, norm, n_rows)
-        env.set_policy(_dp(p))
-        idx = None
-        if form == "perm":      # a slice of a permutation, with one row repeated
-            idx = np.random.default_rng(b).permutation(n_rows)[:b].astype(np.int64)
-            idx[-1] = idx[0]
-        grad, stats = _call(env, _device(st, strided), idx=idx, use_value=use_value)
-        batch = D.gather(st, idx, b)
-        ref = D.loss_autograd(p, batch, "float64", use_value=use_value, **KW)
-        f32 = D.loss_autograd(p, batch, "float32", use_value=use_value, **KW)
-        pool_got.append(D.pooled_errors(p, grad, ref.grad)), pool_yard.append(D.pooled_errors(p, f32.grad, ref.grad))
-        pool_keys.append(f"B{b}-{form}-{'norm' if norm else 'raw'}{'' if use_value else '-novalue'}")
-        if not D.zero_bits_ok(p, grad, ref.grad):
-            failures.append((pool_keys[-1], "a tensor with an identically zero gradient is not all +0.0f bits"))
-        if len(D.zero_tensors(p, ref.grad)) != (1 if use_value else 1 + 2 * len(p.critic)):
-            failures.append((pool_keys[-1], "the reference's zero tensors"))
-        s_got.append(R.stat_units(stats[STATS], ref.stats[STATS])), s_yard.append(R.stat_units(f32.stats[STATS], ref.stats[STATS]))
-        sq = float((grad.astype(np.float64) ** 2).sum())
-        if abs(float(stats[5]) - sq) > 1e-5 * sq:
-            failures.append((pool_keys[-1], "sum of grad^2", float(stats[5]), sq))
-        if stats[[0, 3, 4, 6]].view(np.uint32).any():
-            failures.append((pool_keys[-1], "stats[0, 3, 4, 6]", stats.tolist()))
-        rest = sum(ref.grad.size for _ in configs[i + 1:])
-        if sum(map(len, pool_got)) >= 1000 and (rest >= 1000 or rest == 0):
-            flush()
-    if pool_got:
-        flush()
-    got, yard = R.triple(np.concatenate(s_got)), R.triple(np.concatenate(s_yard))
-    print(f"{name} stats: kernel {got}, f32 autograd {yard}")
-    _record("stats", name, {"kernel_vs_f64": got, "f32_autograd_vs_f64": yard})
-    if not R.within(got, yard):
-        failures.append(("stats", got, yard))
-    assert not failures, failures
+    assert not (f := G.parity(MODE, name, G.gpu_compute(MODE, env))), f
 
 
 def test_same_bits_whatever_the_outputs_held_and_identity_idx(env):
-    """two calls on the same inputs give the same bits; grad / stats pre-filled with NaN are fully overwritten; idx = arange(B) is idx NULL"""
-    import torch
-    p, st = _storage("mixed", True, 100)
-    env.set_policy(_dp(p))
-    d = _device(st)
-    first = _call(env, d)
-    grad, stats = torch.full((env.policy.n_head(),), float("nan"), device="cuda"), torch.full((8,), float("nan"), device="cuda")
-    env.distill_grad(d["obs"], d["target"], d["value_target"], grad=grad, stats=stats, **KW)
-    ident = _call(env, d, idx=np.arange(100, dtype=np.int64))
-    for other in ((grad, stats), ident):
-        assert np.array_equal(_bits(first[0]), _bits(other[0])) and np.array_equal(_bits(first[1]), _bits(other[1]))
-    assert np.isfinite(first[0]).all() and np.isfinite(first[1]).all()
+    G.same_bits_contract(MODE, env)
 
 
 def test_no_coefficient_and_no_value_targets_give_all_zero_bits(env):
-    p, st = _storage("ppo", True, 100)
+    p, _, st = _storage("ppo", True, 100)
     env.set_policy(_dp(p))
     grad, stats = _call(env, _device(st), use_value=False, distill_coef=0.0)
     assert not grad.view(np.uint32).any()
@@ -172,30 +47,7 @@ def test_no_coefficient_and_no_value_targets_give_all_zero_bits(env):
 
 
 def test_graph_replay_sees_an_update(env):
-    """a graph captured after a warm call replays to the eager bits, before and after an update_policy made between the replays"""
-    import torch
-    p, st = _storage("ppo", True, 100)
-    q = R.make_policy("ppo", norm=True, seed=9)
-    env.set_policy(_dp(p))
-    d = _device(st)
-    grad, stats = torch.empty(env.policy.n_head(), device="cuda"), torch.empty(8, device="cuda")
-    call = lambda g, s: env.distill_grad(d["obs"], d["target"], d["value_target"], grad=g, stats=s, **KW)
-    call(grad, stats)      # warm: the scratch is allocated
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        call(grad, stats)
-    for pol in (p, q):
-        env.update_policy(_dp(pol))
-        grad.fill_(float("nan"))
-        graph.replay()
-        eager_g, eager_s = torch.empty_like(grad), torch.empty_like(stats)
-        call(eager_g, eager_s)
-        torch.cuda.synchronize()
-        assert np.array_equal(_bits(grad), _bits(eager_g)) and np.array_equal(_bits(stats), _bits(eager_s))
-        if pol is p:
-            first = grad.clone()
-    assert not np.array_equal(_bits(first), _bits(grad))
+    G.graph_replay_contract(MODE, env)
 
 
 def test_ppo_grad_and_act_are_untouched(env):
@@ -203,7 +55,7 @@ def test_ppo_grad_and_act_are_untouched(env):
     so does act"""
     import torch
     p = R.make_policy("ppo", norm=True, seed=1)
-    ppo_st, st = R.make_storage(p, 100, seed=2), _storage("ppo", True, 100)[1]
+    ppo_st, st = R.make_storage(p, 100, seed=2), _storage("ppo", True, 100)[2]
     env.set_policy(_dp(p))
     pd, d = {k: torch.from_numpy(v).cuda() for k, v in ppo_st.items()}, _device(st)
     obs4 = d["obs"][:4].contiguous()
@@ -223,7 +75,7 @@ def test_argument_errors(env):
     import torch
     from mocca_envs_amd import lib as L
     from mocca_envs_amd.vec_env import VecEnv
-    p, st = _storage("tiny", True, 17)
+    p, _, st = _storage("tiny", True, 17)
     d = _device(st)
     ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     grad, stats = torch.full((_dp(p).n_head(),), 7.0, device="cuda"), torch.full((8,), 7.0, device="cuda")

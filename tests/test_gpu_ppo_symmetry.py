@@ -2,6 +2,7 @@
 autograd as the yardstick, the mirrored minibatch, the call's contract -- fixed bits, overwritten outputs, graph capture, a read-only
 image, the plain call left as it was --, the argument errors and a whole training run.  The checker is tests/ppo_symmetry_reference.py."""
 import ctypes as C
+import functools
 import json
 import os
 import subprocess
@@ -11,13 +12,16 @@ import numpy as np
 import pytest
 
 import policy_symmetry_reference as S
+import ppo_grad_cases as G
 import ppo_reference as R
 import ppo_symmetry_reference as PS
+from ppo_grad_cases import bits as _bits, device_policy as _dp, to_device as _device
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BATCHES = (1, 8, 9, 17, 100, 1100)   # one row, the 8-row tile, one past it, across the 16-row scratch tile, several workgroups, several row chunks of launch 2
-KW = dict(clip=R.CLIP, value_coef=0.5, entropy_coef=0.01)
+MODE = G.MODES["sym"]
+KW = MODE.kw
+_storage, _record = functools.partial(G.storage, MODE), functools.partial(G.record, MODE)
 
 
 @pytest.fixture(scope="module")
@@ -28,124 +32,13 @@ def env():
     e.close()
 
 
-def _dp(p, tables=None):
-    from mocca_envs_amd.policy import DevicePolicy
-    return DevicePolicy(p.actor, p.critic, p.log_std, obs_mean=p.obs_mean, inv_std=p.inv_std, clip=p.clip, symmetry=tables)
-
-
-def _bits(x):
-    return np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "cpu") else x).reshape(-1).view(np.uint8)
-
-
-def _record(section, key, value):
-    out = os.environ.get("MOCCA_TEST_OUT")     # a directory: measured figures are collected there (profiles/ppo_grad_sym_parity.json)
-    if not out:
-        return
-    path = os.path.join(out, "ppo_grad_sym_parity.json")
-    doc = json.load(open(path)) if os.path.exists(path) else {
-        "what": "tests/test_gpu_ppo_symmetry.py: gradient errors per parameter tensor relative to that tensor's largest |g_f64|, pooled, as "
-                "[median, p99, max], kernel and float32 autograd yardstick; stats: errors of stats[0..3] in units of 1e-6 (1 + |x|); mirror: the "
-                "kernel on the mirrored minibatch against the original minibatch's float64 gradient", "grad": {}, "stats": {}, "mirror": {},
-        "adam": {}, "demo": {}}
-    doc[section][key] = value
-    with open(path, "w") as f:
-        json.dump(doc, f, indent=1, sort_keys=True)
-        f.write("\n")
-
-
-_STORAGE = {}
-
-
-def _storage(name, norm, n_rows):
-    """(policy, tables, storage), computed once and left unchanged"""
-    key = (name, norm, n_rows)
-    if key not in _STORAGE:
-        p = R.make_policy(name, norm=norm, seed=1)
-        tables = PS.random_tables(R.NETS[name][0], 3, R.NETS[name][1])
-        _STORAGE[key] = (p, tables, PS.make_storage_sym(p, tables, n_rows, seed=2))
-    return _STORAGE[key]
-
-
-def _device(st, strided):
-    """the storage on the device; strided: obs is a view of wider rows whose other floats are NaN"""
-    import torch
-    d = {k: torch.from_numpy(v).cuda() for k, v in st.items()}
-    if strided:
-        wide = torch.full((st["obs"].shape[0], st["obs"].shape[1] + 13), float("nan"), device="cuda")
-        wide[:, :st["obs"].shape[1]] = d["obs"]
-        d["obs"] = wide[:, :st["obs"].shape[1]]
-    return d
-
-
 def _call(env, d, idx=None, value_clip=False, **kw):
-    import torch
-    out = env.ppo_grad(d["obs"], d["action"], d["old_logp"], d["adv"], d["returns"], idx=None if idx is None else torch.from_numpy(idx).cuda(),
-                       old_value=d["old_value"] if value_clip else None, value_clip=value_clip, **{**KW, **kw})
-    torch.cuda.synchronize()
-    return out["grad"].cpu().numpy(), out["stats"].cpu().numpy()
-
-
-def _configs():
-    """(B, idx form, norm, value_clip, strided): every batch size with both index forms and the normalisation on and off; value_clip and
-    the strided obs cycle with periods 3 and 5, as in test_gpu_ppo.py"""
-    n = 0
-    for b in BATCHES:
-        for form in ("null", "perm"):
-            for norm in (True, False):
-                yield b, form, norm, n % 3 == 0, n % 5 < 2
-                n += 1
+    return G.call(MODE, env, d, idx, value_clip, **kw)
 
 
 @pytest.mark.parametrize("name", sorted(R.NETS))
 def test_gradient_and_stats_parity(env, name):
-    """The project's rule, as test_gpu_ppo.py applies it to the plain call.  Per parameter tensor the error against the float64 gradient
-    over that tensor's largest |g_f64|, pooled over the tensors of a configuration (configurations of fewer than 1000 elements are pooled
-    with the next ones of the net); the kernel stays within 3 x float32 autograd at the median, the 99th percentile and the maximum.
-    stats[0..3] by the same rule in units of 1e-6 (1 + |x|), pooled over the net's configurations; stats[4] exact; stats[5] within 1e-5 of
-    the f64 sum over grad_dev.  No row is left out (ppo_symmetry_reference.make_storage_sym)."""
-    failures, pool_got, pool_yard, pool_keys, s_got, s_yard = [], [], [], [], [], []
-
-    def flush():
-        got, yard = R.triple(np.concatenate(pool_got)), R.triple(np.concatenate(pool_yard))
-        key = "+".join(pool_keys)
-        print(f"{name} {key}: kernel {got}, f32 autograd {yard}")
-        _record("grad", f"{name}:{key}", {"kernel_vs_f64": got, "f32_autograd_vs_f64": yard, "elements": int(sum(map(len, pool_got)))})
-        if not R.within(got, yard):
-            failures.append((key, got, yard))
-        pool_got.clear(), pool_yard.clear(), pool_keys.clear()
-
-    configs = list(_configs())
-    for i, (b, form, norm, value_clip, strided) in enumerate(configs):
-        n_rows = b if form == "null" else b + 7
-        p, tables, st = _storage(name, norm, n_rows)
-        env.set_policy(_dp(p, tables))
-        idx = None
-        if form == "perm":      # a slice of a permutation, with one row repeated
-            idx = np.random.default_rng(b).permutation(n_rows)[:b].astype(np.int64)
-            idx[-1] = idx[0]
-        grad, stats = _call(env, _device(st, strided), idx=idx, value_clip=value_clip)
-        batch = R.gather(st, idx, b)
-        ref = PS.loss_autograd_sym(p, tables, batch, "float64", value_clip=value_clip, **KW)
-        f32 = PS.loss_autograd_sym(p, tables, batch, "float32", value_clip=value_clip, **KW)
-        pool_got.append(R.tensor_errors(p, grad, ref.grad)), pool_yard.append(R.tensor_errors(p, f32.grad, ref.grad))
-        pool_keys.append(f"B{b}-{form}-{'norm' if norm else 'raw'}{'-vclip' if value_clip else ''}")
-        s_got.append(R.stat_units(stats[:4], ref.stats[:4])), s_yard.append(R.stat_units(f32.stats[:4], ref.stats[:4]))
-        if stats[4] != np.float32(round(ref.stats[4] * b)) / np.float32(b):
-            failures.append((pool_keys[-1], "clip fraction", float(stats[4]), ref.stats[4]))
-        sq = float((grad.astype(np.float64) ** 2).sum())
-        if abs(float(stats[5]) - sq) > 1e-5 * sq or stats[6] != 0 or stats[7] != 0:
-            failures.append((pool_keys[-1], "sum of grad^2", float(stats[5]), sq))
-        rest = sum(ref.grad.size for _ in configs[i + 1:])
-        if sum(map(len, pool_got)) >= 1000 and (rest >= 1000 or rest == 0):
-            flush()
-    if pool_got:
-        flush()
-    got, yard = R.triple(np.concatenate(s_got)), R.triple(np.concatenate(s_yard))
-    print(f"{name} stats: kernel {got}, f32 autograd {yard}")
-    _record("stats", name, {"kernel_vs_f64": got, "f32_autograd_vs_f64": yard})
-    if not R.within(got, yard):
-        failures.append(("stats", got, yard))
-    assert not failures, failures
+    assert not (f := G.parity(MODE, name, G.gpu_compute(MODE, env))), f
 
 
 @pytest.mark.parametrize("name", ["mixed", "ppo"])
@@ -167,52 +60,11 @@ def test_mirrored_minibatch_gives_the_original_gradient(env, name):
 
 
 def test_same_bits_whatever_the_outputs_held_and_identity_idx(env):
-    """two calls on the same inputs give the same bits; grad / stats pre-filled with NaN are fully overwritten; idx = identity is idx NULL"""
-    import torch
-    p, tables, st = _storage("mixed", True, 100)
-    env.set_policy(_dp(p, tables))
-    d = _device(st, False)
-    first = _call(env, d, value_clip=True)
-    again = _call(env, d, value_clip=True)
-    grad, stats = torch.full((env.policy.n_head(),), float("nan"), device="cuda"), torch.full((8,), float("nan"), device="cuda")
-    env.ppo_grad(d["obs"], d["action"], d["old_logp"], d["adv"], d["returns"], old_value=d["old_value"], value_clip=True, grad=grad, stats=stats, **KW)
-    ident = _call(env, d, idx=np.arange(100, dtype=np.int64), value_clip=True)
-    for other in (again, (grad, stats), ident):
-        assert np.array_equal(_bits(first[0]), _bits(other[0])) and np.array_equal(_bits(first[1]), _bits(other[1]))
-    assert np.isfinite(first[0]).all() and np.isfinite(first[1]).all()
+    G.same_bits_contract(MODE, env)
 
 
 def test_graph_replay_sees_an_update_and_act_is_untouched(env):
-    """a graph captured after a warm call replays to the eager bits, before and after an update_policy made between the replays; mocca_act's
-    outputs after ppo_grad calls equal those before: the image is only read"""
-    import torch
-    p, tables, st = _storage("ppo", True, 100)
-    q = R.make_policy("ppo", norm=True, seed=9)
-    env.set_policy(_dp(p, tables))
-    d = _device(st, False)
-    obs4 = d["obs"][:4].contiguous()
-    before = env.act(obs4, deterministic=True)
-    before = {k: v.clone() for k, v in before.items()}
-    grad, stats = torch.empty(env.policy.n_head(), device="cuda"), torch.empty(8, device="cuda")
-    call = lambda g, s: env.ppo_grad(d["obs"], d["action"], d["old_logp"], d["adv"], d["returns"], grad=g, stats=s, **KW)
-    call(grad, stats)      # warm: the scratch is allocated
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        call(grad, stats)
-    for pol in (p, q):
-        env.update_policy(_dp(pol))
-        grad.fill_(float("nan"))
-        graph.replay()
-        eager_g, eager_s = torch.empty_like(grad), torch.empty_like(stats)
-        call(eager_g, eager_s)
-        torch.cuda.synchronize()
-        assert np.array_equal(_bits(grad), _bits(eager_g)) and np.array_equal(_bits(stats), _bits(eager_s))
-        if pol is p:
-            after = env.act(obs4, deterministic=True)
-            assert all(np.array_equal(_bits(before[k]), _bits(after[k])) for k in before)
-            first = grad.clone()
-    assert not np.array_equal(_bits(first), _bits(grad))
+    G.graph_replay_contract(MODE, env)
 
 
 def test_plain_call_is_untouched_by_a_symmetric_call_on_the_same_handle(env):
