@@ -16,7 +16,8 @@
 // Lane roles per phase (see DESIGN.md "Kernel anatomy"):
 //   kinematics walk  lane = body       root->body walk, no cross-lane traffic
 //   ABA inward pass  lane = body of the current tree level (<= 4 busy lanes)
-//   ABA outward pass lane = body       root->body walk
+//   ABA outward pass lane = body of a root->leaf chain laid along a DPP row: a level per round
+//                    (closure trees, compact instances: lane = body, root->body walk)
 //   collision        lane = terrain contact slot / self-collision pair (strided)
 //   rows             lane = constraint row: unit-impulse response (O(n) sweep),
 //                    Delassus column in registers, PGS with one readlane per row
@@ -319,6 +320,17 @@ template <bool LATE>
 DI void late_args(StepArgs& la) {
   if constexpr (LATE) read_kernargs(la);
 }
+// Which step-kernel instances run the ABA outward pass level by level over DPP (aba_passes): those whose generated header lays their chains
+// out in the wave's rows (topo_*.h OUTWARD_DPP), but for the compact instances: at their 96-register budget the walker's spill already, and
+// the rounds' 31 live values cost its Custom and Planner instances 8 / 20 B of scratch more (22 -> 27 and 12 -> 41 spilled registers), the
+// per-lane word the quadruped's Custom instance 20 B.  They, the trees without a layout (loop closures) and MOCCA_NO_TRIM_8 keep the
+// root->body walk and compile to the instructions they had.
+template <class T>
+#ifdef MOCCA_NO_TRIM_8
+constexpr bool OUTWARD_ROUNDS = false;
+#else
+constexpr bool OUTWARD_ROUNDS = T::OUTWARD_DPP && !COMPACT;
+#endif
 // Which step-kernel instances read the late view: all but the walker's physics instances at their register budget, which keep the arguments
 // of the entry.  With the late view the substep loop, scheduled around the freed scalar registers, spilled in the 48-row Stepper and Planner
 // instances (20 / 36 B of scratch where there was none) and spilled more in the compact ones (Custom 27 -> 34 registers, Stepper and Planner
@@ -951,31 +963,83 @@ DI void aba_passes(ModelP M, float* L, int lane, unsigned long long ppk, float* 
 #pragma unroll
       for (int i = 0; i < 21; ++i) Afac[i] = unif(Ai[i]);
     }
+    // (with the rounds below the negation's only reader is an add, and the optimiser carries it back through the whole substitution; that
+    // is the same number wherever it is finite and another NaN sign where an infinite state makes one: the solve ends here, as in the walk's build)
+    if constexpr (OUTWARD_ROUNDS<T>) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) pin1(a0[i]);
+    }
 #pragma unroll
     for (int i = 0; i < 6; ++i) abase[i] = -a0[i];
   }
   STAMP(11);
-  // outward pass: lane = body, walk from the root accumulating the spatial acceleration
+  // outward pass: every body's joint acceleration from its parent's spatial acceleration, root to leaves
   {
-    const int b = lane < T::NB ? lane : 0;
     float a[6], qdd = 0;
+    int b;        // the lane's body ...
+    bool store;   // ... and whether this lane stores its new joint speed
 #pragma unroll
     for (int i = 0; i < 6; ++i) a[i] = abase[i];
+    if constexpr (OUTWARD_ROUNDS<T>) {
+      // Level by level: body b's acceleration is a function of its parent's alone -- t = a_parent + c_b, qdd_b = (u / D)_b - V_b . t,
+      // a_b = t + S_b qdd_b -- and the parent's lane holds a_parent, bit for bit what a walk down b's own path recomputes.  Every root->leaf
+      // chain sits on consecutive lanes from the start of a DPP row (topo_*.h out_body), so each lane reads its own record once and then
+      // applies its own step MAXD times to what its left neighbour holds: after round k every body of depth <= k is final and stays final,
+      // whatever the deeper lanes held before (nothing of a lane's own earlier value enters its step).  No LDS access inside the rounds.
+      const int ol = T::out_lane(ppk);    // (the top bits of the lane's packed word: no table access in the substep)
+      b = ol & 31;                        // (idle lanes run body 0's record: finite or not, nothing reads what they compute)
+      store = (unsigned)(ol - 1) < 31u;   // the body's primary lane: a trunk that two chains share is computed in both rows, stored from one
+      static_assert(SV_V == 6 && SV_C == 12 && SV_UU == 18 && SVS % 4 == 0 && L_SV % 4 == 0, "the body record as five 16-byte reads");
+      const float4* rec = reinterpret_cast<const float4*>(L + L_SV + SVS * b);
+      const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3], r4 = rec[4];
+      const float S[6] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y}, V[6] = {r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
+      const float c[6] = {r3.x, r3.y, r3.z, r3.w, r4.x, r4.y}, uu = r4.z;
+      float t[6], ab[6];
+      // a chain's head hangs on the base: the one add the walk starts with.  The other lanes overwrite it in the first shifted round.
+      // (a pinned and the add spelled out: the walk adds c TO the base's acceleration, a value of its own -- neither fused with the solve's
+      // last multiply nor commuted, which two NaNs of different sign would tell)
 #pragma unroll
-    for (int k = 0; k < T::MAXD; ++k) {
-      const int j = (int)((ppk >> (5 * k)) & 31ull);
-      if (j != 0) {
-        float U[6], S[6];
+      for (int i = 0; i < 6; ++i) { pin1(a[i]); asm("v_add_f32_e32 %0, %1, %2" : "=v"(t[i]) : "v"(a[i]), "v"(c[i])); }
 #pragma unroll
-        for (int i = 0; i < 6; ++i) { a[i] += L[L_SV + SVS * j + SV_C + i]; U[i] = L[L_SV + SVS * j + SV_V + i]; S[i] = L[L_SV + SVS * j + i]; }
-        qdd = L[L_SV + SVS * j + SV_UU] - dot6(U, a);   // u / D - (U / D) . a
+      for (int k = 0; k < T::MAXD; ++k) {
+        if (k > 0) {
+          // t = a(lane - 1) + c as six v_add_f32_dpp, row_shr:1 without bound_ctrl: the first lane of a row has no source and is not written,
+          // so the heads keep their t.  (Left to the optimiser the shift is a v_mov_b32_dpp of its own per component; the block pays the
+          // DPP read hazard -- two wait states behind the FMAs that wrote the neighbour's value -- once.)
+          asm("s_nop 1\n\t"
+              "v_add_f32_dpp %0, %6, %12 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+              "v_add_f32_dpp %1, %7, %13 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+              "v_add_f32_dpp %2, %8, %14 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+              "v_add_f32_dpp %3, %9, %15 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+              "v_add_f32_dpp %4, %10, %16 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+              "v_add_f32_dpp %5, %11, %17 row_shr:1 row_mask:0xf bank_mask:0xf"
+              : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5])
+              : "v"(ab[0]), "v"(ab[1]), "v"(ab[2]), "v"(ab[3]), "v"(ab[4]), "v"(ab[5]), "v"(c[0]), "v"(c[1]), "v"(c[2]), "v"(c[3]), "v"(c[4]), "v"(c[5]));
+        }
+        qdd = uu - dot6(V, t);   // u / D - (U / D) . a
 #pragma unroll
-        for (int i = 0; i < 6; ++i) a[i] += S[i] * qdd;
+        for (int i = 0; i < 6; ++i) ab[i] = t[i] + S[i] * qdd;
+      }
+    } else {
+      // lane = body: walk from the root accumulating the spatial acceleration
+      b = lane < T::NB ? lane : 0;
+      store = lane >= 1 && lane < T::NB;
+#pragma unroll
+      for (int k = 0; k < T::MAXD; ++k) {
+        const int j = (int)((ppk >> (5 * k)) & 31ull);
+        if (j != 0) {
+          float U[6], S[6];
+#pragma unroll
+          for (int i = 0; i < 6; ++i) { a[i] += L[L_SV + SVS * j + SV_C + i]; U[i] = L[L_SV + SVS * j + SV_V + i]; S[i] = L[L_SV + SVS * j + i]; }
+          qdd = L[L_SV + SVS * j + SV_UU] - dot6(U, a);   // u / D - (U / D) . a
+#pragma unroll
+          for (int i = 0; i < 6; ++i) a[i] += S[i] * qdd;
+        }
       }
     }
     const float dt = M->dt;
-    if (lane >= 1 && lane < T::NB) L[L_NU + 5 + b] = L[L_QD + b] + dt * qdd;
-    if (lane == 0) {
+    if (store) L[L_NU + 5 + b] = L[L_QD + b] + dt * qdd;
+    if (lane == 0) {   // (a: the base's own acceleration -- lane 0 walks no path, and the rounds leave a alone)
       float om[3] = {L[L_BASE + 10], L[L_BASE + 11], L[L_BASE + 12]}, vl[3] = {L[L_BASE + 7], L[L_BASE + 8], L[L_BASE + 9]}, wxv[3];
       cross3(om, vl, wxv);
 #pragma unroll

@@ -285,8 +285,9 @@ __global__ __launch_bounds__(64, MOCCA_WAVES_PER_EU) void mocca_step_kernel(Step
   load_dyn(st, L, lane, T::NJ, T::NSLOT, warm_ld);
   pace_start(a, L, lane, INJECT ? 0 : a.pace);
   if (lane == 0) L[L_KEEPWARM] = __int_as_float((warm_st ? 1 : 0) | ((a.prio & PRIO_DELASSUS_VALU) ? 2 : 0));   // (solve_constraints: wave_flags)
-  // the lane's root->body path, packed 5 bits per step; the only lane-derived value kept across the substeps
-  const unsigned long long ppk = T::path_packed(lane < T::NB ? lane : 0);
+  // the lane's root->body path, packed 5 bits per step; the only lane-derived value kept across the substeps.  The instances that run the ABA
+  // outward pass level by level read the word that holds, above the path, the lane's body in that pass (topo_*.h kLanePk)
+  const unsigned long long ppk = OUTWARD_ROUNDS<T> ? T::lane_packed(lane) : T::path_packed(lane < T::NB ? lane : 0);
   ContactFlags fl = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   int cover = 0;   // Stepper: cover mask of the last substep's contacts (mocca_device.h cover_targets)
   // the arguments as everything behind the substeps reads them: the late view (late_args), which is not carried across the loop, in

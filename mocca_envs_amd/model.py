@@ -1179,6 +1179,34 @@ def joint_limits(m: MoccaModel) -> Tuple[np.ndarray, np.ndarray]:
 # --------------------------------------------------------------------------
 # compile-time topology for the HIP kernels
 # --------------------------------------------------------------------------
+OUTWARD_ROWS, OUTWARD_ROW_LANES = 4, 16   # a wave's DPP rows
+OUTWARD_SHIFT = 58                          # topo_*.h kLanePk: the outward pass's lane bits sit above the packed path
+
+
+def outward_layout(parent: List[int], n_closures: int = 0) -> Tuple[bool, List[int]]:
+    """Lane layout of the ABA outward pass that goes level by level (mocca_device.h, aba_passes): (OUTWARD_DPP, body of each of the 64 lanes).
+
+    Every root->leaf chain of the tree, leaves in ascending order, takes consecutive lanes from the start of one 16-lane DPP row, so that a
+    body's parent sits on the lane to its left and its acceleration arrives by a row shift.  A trunk that several chains share is repeated
+    in each of their rows (the same arithmetic on the same values); the lowest lane that hosts a body is its primary lane, the one that
+    stores.  Idle lanes hold -1.  The pass is taken (OUTWARD_DPP) when the tree has at most four leaf chains of at most 16 bodies and no loop
+    closures; a tree whose chains do not fit has no layout (every lane -1)."""
+    nb = len(parent)
+    lanes = [-1] * (OUTWARD_ROWS * OUTWARD_ROW_LANES)
+    chains = []
+    for leaf in (b for b in range(1, nb) if b not in parent[1:]):
+        c, cur = [], leaf
+        while cur > 0:
+            c.append(cur)
+            cur = parent[cur]
+        chains.append(c[::-1])
+    if len(chains) > OUTWARD_ROWS or any(len(c) > OUTWARD_ROW_LANES for c in chains):
+        return False, lanes
+    for r, c in enumerate(chains):
+        lanes[OUTWARD_ROW_LANES * r:OUTWARD_ROW_LANES * r + len(c)] = c
+    return n_closures == 0, lanes
+
+
 def topology_header(m: MoccaModel, name: str = "Walker3D") -> str:
     """C++ header with the tree as constexpr tables (mocca_envs_amd/csrc/topo_*.h).
 
@@ -1221,6 +1249,11 @@ def topology_header(m: MoccaModel, name: str = "Walker3D") -> str:
             cur = parent[cur]
         p = p[::-1]
         path.append(p + [-1] * (maxd - len(p)))
+    outward_dpp, out_lanes = outward_layout(parent, m.n_closures)
+    out_primary = [b >= 0 and out_lanes.index(b) == l for l, b in enumerate(out_lanes)]
+    out_lane_bits = [0 if b < 0 else b + (0 if p else 32) for b, p in zip(out_lanes, out_primary)]
+    pathpk = [sum(((path[b][k] if path[b][k] >= 0 else 0) << (5 * k)) for k in range(maxd)) for b in range(nb)]
+    assert 5 * maxd <= OUTWARD_SHIFT and nb <= 32, "the packed path and the outward pass's lane bits share one 64-bit word"
 
     def arr(vals):
         return "{" + ", ".join(str(v) for v in vals) + "}"
@@ -1241,7 +1274,11 @@ def topology_header(m: MoccaModel, name: str = "Walker3D") -> str:
     lines += [
         "};",
         "__device__ static const unsigned long long kPathPk%s[%d] = %s;" % (
-            name, nb, arr(["0x%xull" % sum(((path[b][k] if path[b][k] >= 0 else 0) << (5 * k)) for k in range(maxd)) for b in range(nb)])),
+            name, nb, arr(["0x%xull" % v for v in pathpk])),
+        "// per LANE: the packed path of the lane's body in the lane = body layout (kPathPk of body `lane`, 0 behind the last body) and, in the top six",
+        "// bits, the lane's body in the level-by-level ABA outward pass (model.py outward_layout): + 32 on a lane that repeats a shared trunk, 0 idle",
+        "__device__ static const unsigned long long kLanePk%s[%d] = %s;" % (
+            name, len(out_lanes), arr(["0x%xull" % ((pathpk[l] if l < nb else 0) | (ol << OUTWARD_SHIFT)) for l, ol in enumerate(out_lane_bits)])),
         "struct Topo%s {" % name,
         "  static constexpr int NB = %d;        // bodies incl. floating base" % nb,
         "  static constexpr int NJ = %d;        // hinges" % (nb - 1),
@@ -1277,6 +1314,16 @@ def topology_header(m: MoccaModel, name: str = "Walker3D") -> str:
         "  // the lane's own root->body path, 5 bits per step (0 = past the end: joints are numbered from 1): loaded once per kernel, two VGPRs, then",
         "  // every path step is a v_bfe -- no table access inside the walks",
         "  static __device__ __forceinline__ unsigned long long path_packed(int b) { return kPathPk%s[b]; }" % name,
+        "  // ABA outward pass, level by level: every root->leaf chain on consecutive lanes from the start of a 16-lane DPP row, so a body's parent is",
+        "  // the lane to its left (model.py outward_layout).  out_body: the lane's body, -1 idle; out_primary: the one lane of a body that stores",
+        "  // (a trunk that chains share is repeated in their rows); OUTWARD_DPP: at most four chains of at most 16 bodies and no loop closures",
+        "  static constexpr bool OUTWARD_DPP = %s;" % ("true" if outward_dpp else "false"),
+        "  static constexpr int out_body(int lane) { constexpr int t[%d] = %s; return t[lane]; }" % (len(out_lanes), arr(out_lanes)),
+        "  static constexpr bool out_primary(int lane) { constexpr bool t[%d] = %s; return t[lane]; }"
+        % (len(out_lanes), arr(["true" if p else "false" for p in out_primary])),
+        "  // what the step kernel keeps per lane across the substeps: path_packed of body `lane` (0 behind the last body), out_lane above it",
+        "  static __device__ __forceinline__ unsigned long long lane_packed(int lane) { return kLanePk%s[lane]; }" % name,
+        "  static __device__ __forceinline__ int out_lane(unsigned long long lane_pk) { return (int)(lane_pk >> %d); }" % OUTWARD_SHIFT,
         "};",
         "",
     ]
