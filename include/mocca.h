@@ -877,6 +877,65 @@ int mocca_set_teacher(mocca_handle h, const int32_t *layers_host, int n_layers_t
 int mocca_update_teacher(mocca_handle h, const float *params_dev, size_t n_floats, void *stream);
 int mocca_teacher_act(mocca_handle h, const float *in_dev, int in_stride, int64_t n_rows, float *mean_dev, float *value_dev, void *stream);
 
+/* ---- PPO with a privileged critic (an asymmetric actor-critic; no reference counterpart: the reference's trainers give both nets one
+ *      observation) ---- */
+
+/* The critic is a training-time device and is thrown away at deployment, so it may read what the robot will never have: the simulator's
+ * exact geometry (TorchVecEnv's `envs.privileged`, [obs | scan]).  The actor keeps reading what the robot really has.  PPO's loss separates
+ * -- the surrogate and the entropy depend on the actor and log_std alone, the value term on the critic alone -- and every sum's order is a
+ * function of B and the shapes alone, so each output below is, BIT FOR BIT, an output of the existing calls on a suitable plain policy:
+ * action, logp, mean and the actor's / log_std's gradient those of a plain policy with the same actor on the actor's rows; the value and the
+ * critic's gradient those of a plain policy of in_dim = critic_in_dim with the same critic on the critic's rows; likewise stats[0..4] and
+ * [7].  stats[5], the sum of grad_dev^2, is the only statistic of the gradient call that mixes both nets (and, in the update's rows, [6],
+ * the clip coefficient formed from it).  Arithmetic and layout: csrc/mocca_policy.h and csrc/mocca_ppo.h, Privileged critic.
+ *
+ * mocca_set_policy_priv   mocca_set_policy with the critic's FIRST layer taking critic_in_dim inputs (1 .. 336; it may equal in_dim, be
+ *                       smaller or larger): the same table, the same rules, the actor's first layer takes in_dim.  The image gains the
+ *                       critic's statistics, and the parameter vector of mocca_update_policy / mocca_adam_step is: the layers, log_std,
+ *                       then optionally mean[in_dim], inv_std[in_dim], critic_mean[critic_in_dim], critic_inv_std[critic_in_dim] -- ALL
+ *                       FOUR OR NONE: n_floats is n_head or n_head + 2 in_dim + 2 critic_in_dim.  One device flag word switches the
+ *                       normalisation of both nets; the critic's is clamp((x - critic_mean[k]) * critic_inv_std[k], -clip, +clip), the
+ *                       same f32 operations in the same order with the same clip.  layers_host == NULL detaches.  mocca_set_policy on
+ *                       the same handle returns it to a plain policy; either call drops the binding of mocca_set_critic_rows.  May
+ *                       synchronise.
+ *                       NOT PROVIDED with a privileged critic: the three mirror attachments (mirror tables for the critic's row are a
+ *                       later addition) -- mocca_set_policy_symmetry / _mirror_loss / _mirror_dup refuse on such a policy and
+ *                       mocca_set_policy_priv refuses while one of them is attached, each with a message, the caller detaches first --;
+ *                       distillation INTO such a policy (mocca_distill_grad / mocca_distill_update refuse).  mocca_set_teacher,
+ *                       mocca_update_teacher and mocca_teacher_act are untouched: a teacher is a plain policy.
+ * mocca_set_critic_rows   binds the rows the critic's workgroups of mocca_act / mocca_act_step / mocca_act_plan_step read: rows_dev
+ *                       [n_envs][row_stride] f32, CALLER-owned (`envs.privileged`), the first critic_in_dim floats of row i belong to env
+ *                       i.  A fixed address, read at every launch: the three calls stay capturable (mocca_set_terminal_obs_buffer is
+ *                       the precedent).  rows_dev == NULL detaches.  With value_dev NULL the critic is not run and no binding is needed.
+ * mocca_ppo_grad_priv     mocca_ppo_grad for such a policy: its argument list with critic_obs_dev [R][critic_stride] f32 added, the
+ *                       storage's critic rows, RAW, gathered through the same idx_dev (NOT range-checked); the four launches, the per-row
+ *                       lines, grad_dev's order (the critic's first W is [out][critic_in_dim]) and stats_dev are mocca_ppo_grad's.
+ *                       Scratch: mocca_ppo_grad's plus 4 B critic_in_pad bytes (the critic's normalised input), the handle's one
+ *                       buffer: the grow-FREES-the-old rule and the capture conditions hold as they stand.  n_rows 1 .. 2^22.
+ * mocca_ppo_update_priv   mocca_ppo_update for such a policy: its argument list with critic_obs_dev, critic_stride added; bit for bit the
+ *                       sequence mocca_ppo_grad_priv + mocca_adam_step per minibatch, under the same shuffle.
+ * Errors (MOCCA_E_ARG, with a message; the handle and every output are left as they were, nothing is launched): mocca_set_policy_priv:
+ * those of mocca_set_policy, critic_in_dim outside 1 .. 336, a critic whose first layer does not take critic_in_dim, a mirror attachment
+ * in place.  mocca_set_critic_rows: a NULL handle, a policy without a privileged critic (or none), row_stride < critic_in_dim.  mocca_act /
+ * mocca_act_step / mocca_act_plan_step: value_dev asked for on such a policy with no rows bound.  mocca_set_policy_symmetry /
+ * _mirror_loss / _mirror_dup: a policy with a privileged critic.  mocca_ppo_grad_priv / mocca_ppo_update_priv: those of mocca_ppo_grad /
+ * mocca_ppo_update, a NULL critic_obs_dev, critic_stride < critic_in_dim, a policy WITHOUT a privileged critic (mocca_ppo_grad /
+ * mocca_ppo_update are its calls).  mocca_ppo_grad / _sym / _mirror / _dup, mocca_ppo_update, mocca_distill_grad and mocca_distill_update on
+ * a policy WITH one: the message names mocca_ppo_grad_priv / mocca_ppo_update_priv; distillation into such a policy is not provided. */
+int mocca_set_policy_priv(mocca_handle h, const int32_t *layers_host, int n_layers_total, int in_dim, int critic_in_dim, int act_dim,
+                          double clip);
+int mocca_set_critic_rows(mocca_handle h, const float *rows_dev, int row_stride);
+int mocca_ppo_grad_priv(mocca_handle h, const float *obs_dev, int obs_stride, const float *critic_obs_dev, int critic_stride,
+                        const float *action_dev, const float *old_logp_dev, const float *adv_dev, const float *returns_dev,
+                        const float *old_value_dev, const int64_t *idx_dev, int64_t n_rows, double clip, double value_coef,
+                        double entropy_coef, int value_clip, float *grad_dev, float *stats_dev, void *stream);
+int mocca_ppo_update_priv(mocca_handle h, const float *obs_dev, int obs_stride, const float *critic_obs_dev, int critic_stride,
+                          const float *action_dev, const float *old_logp_dev, const float *adv_dev, const float *returns_dev,
+                          const float *old_value_dev, int64_t n_rollout_rows, int64_t minibatch_rows, int epochs, double clip,
+                          double value_coef, double entropy_coef, int value_clip, float *params_dev, size_t n_floats, int64_t n_params,
+                          float *moments_dev, double *clock_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm,
+                          uint64_t seed, float *stats_dev, void *stream);
+
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */
 int mocca_kernel_info(mocca_handle h, int *vgprs, int *sgprs, int *lds_bytes, int *scratch_bytes, int *max_blocks_per_cu);

@@ -187,6 +187,9 @@ struct mocca_ctx {
     DevBuf<float> sign;              // in_sign [in_dim] then act_sign [act_dim]
     double coef = 0.0;               // PPO_MIRROR: mirror_coef
   } pol_mirror;
+  // the student's privileged critic (mocca_set_policy_priv: student.pol.critic_in_dim != 0): the rows its workgroups of mocca_act read
+  const float* critic_rows = nullptr;   // caller-owned [n_envs][critic_stride] (mocca_set_critic_rows)
+  int critic_stride = 0;
   // scratch of mocca_gae / mocca_obs_stats (mocca_rollout.h), owned by the handle, grown on demand
   DevBuf<double> d_gae_part;         // [blocks][2]
   size_t gae_part_cap = 0;           // doubles
@@ -234,7 +237,7 @@ static int commit_ready(mocca_handle h, const char* who, hipError_t e = hipSucce
 // the previous layer's output, so it needs no bound of its own.
 constexpr size_t NO_OFFSETS = ~(size_t)0;
 static std::string check_layer_table(const int32_t* layers, int n_layers_total, int in_dim, int head, size_t n_params, const std::string& first_takes,
-                                     const std::string& ends_in, int count[2]) {
+                                     const std::string& ends_in, int count[2], int critic_in_dim = 0) {   // critic_in_dim != 0: what the CRITIC's first layer takes
   using namespace mocca_ctrl;
   if (!layers || n_layers_total < 2 || n_layers_total > 2 * CTRL_MAX_LAYERS) return "needs 1 .. 8 layers for each of the two nets";
   count[0] = count[1] = 0;
@@ -248,7 +251,7 @@ static std::string check_layer_table(const int32_t* layers, int n_layers_total, 
     const bool first = count[net] == 0;
     if (++count[net] > CTRL_MAX_LAYERS) return at + "more than 8 layers in one net";
     const int in = r[CL_IN], out = r[CL_OUT];
-    if (first && in != in_dim) {
+    if (first && in != (net == 1 && critic_in_dim ? critic_in_dim : in_dim)) {
       std::string what = first_takes;
       const size_t k = what.find("%d");
       return at + (k == std::string::npos ? what : what.replace(k, 2, std::to_string(in)));
@@ -284,7 +287,8 @@ struct NetImage {
   std::vector<int32_t> table;
   int wt_off[mocca_ppo::PPO_MAX_TABLE];
 };
-static hipError_t build_image(NetImage& im, const int32_t* layers_host, int n_layers_total, const int count[2], int in_dim, int act_dim, bool packed) {
+static hipError_t build_image(NetImage& im, const int32_t* layers_host, int n_layers_total, const int count[2], int in_dim, int act_dim, bool packed,
+                              int critic_in_dim = 0) {   // != 0: a privileged critic -- two more tail rows, critic_mean and critic_inv_std (tail_row + 3, + 4)
   using namespace mocca_ctrl;
   using namespace mocca_pol;
   std::vector<int32_t>& table = im.table;
@@ -312,6 +316,11 @@ static hipError_t build_image(NetImage& im, const int32_t* layers_host, int n_la
   pa.flags_off = row(POL_FLAG_WORDS, -1, 0, 1, 0);
   pa.mean_off = row(in_pad, -1, 0, in_dim, 0);
   pa.inv_std_off = row(in_pad, -1, 0, in_dim, 0);
+  if (critic_in_dim) {   // a plain policy's image has neither: its offsets do not move
+    pa.critic_in_dim = critic_in_dim; pa.critic_in_pad = (critic_in_dim + 15) / 16 * 16;
+    pa.critic_mean_off = row(pa.critic_in_pad, -1, 0, critic_in_dim, 0);
+    pa.critic_inv_std_off = row(pa.critic_in_pad, -1, 0, critic_in_dim, 0);
+  }
   for (int i = 0, s = 0; i < n_layers_total; ++i) {   // W^T of a layer: in and out swap roles and padding
     const int32_t* r = &table[(size_t)i * CTRL_LAYER_WORDS];
     im.wt_off[i] = -1;
@@ -1289,29 +1298,39 @@ static void drop_policy_mirror(mocca_handle h) {
 
 // mocca_set_policy (the student's slot: the mirror attachment goes with the old shapes) and mocca_set_teacher (the teacher's): attach,
 // replace or (layers_host NULL) detach the slot's policy image.  A refused call leaves the handle as it was.
+// `priv` (mocca_set_policy_priv, the student's slot): the critic's first layer takes critic_in_dim inputs and the image carries its statistics.
+// Either student call drops the critic-row binding (mocca_set_critic_rows): its stride was checked against the old shapes.
 static int set_policy_slot(mocca_handle h, const char* name, bool student, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim,
-                           double clip) try {
+                           double clip, bool priv = false, int critic_in_dim = 0) try {
   using namespace mocca_pol;
   if (!h) return MOCCA_E_ARG;
   mocca_ctx::PolicySlot& slot = student ? h->student : h->teacher;
   DeviceGuard guard(h->device);
+  auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
+  if (priv && h->pol_mirror.method != mocca_ppo::PPO_PLAIN)   // also for a detach: the caller says what goes first
+    return bad(std::string("a mirror attachment is in place (") + (h->pol_mirror.method == mocca_ppo::PPO_SYM ? "mocca_set_policy_symmetry" : h->pol_mirror.method == mocca_ppo::PPO_MIRROR ? "mocca_set_policy_mirror_loss" : "mocca_set_policy_mirror_dup") +
+               "): mirror tables for the critic's row are not provided, detach it first");
   if (!layers_host) {   // detach
     if (int rc = commit_ready(h, name)) return rc;
     slot.d_pol_image.reset(); slot.d_pol_layers.reset(); slot.pol_filled = false;
-    if (student) drop_policy_mirror(h);
+    if (student) { drop_policy_mirror(h); h->critic_rows = nullptr; h->critic_stride = 0; slot.pol.critic_in_dim = 0; }
     return MOCCA_OK;
   }
-  auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
   if (in_dim < 1 || in_dim > POL_MAX_IN) return bad("in_dim must be 1 .. " + std::to_string(POL_MAX_IN));
+  if (priv && (critic_in_dim < 1 || critic_in_dim > POL_MAX_IN)) return bad("critic_in_dim must be 1 .. " + std::to_string(POL_MAX_IN));
   if (act_dim < 1 || act_dim > POL_MAX_ACTION) return bad("act_dim must be 1 .. " + std::to_string(POL_MAX_ACTION));
   if (!std::isfinite(clip) || !(clip > 0.0)) return bad("clip must be finite and positive");
   int count[2];
-  const std::string wrong = check_layer_table(layers_host, n_layers_total, in_dim, act_dim, NO_OFFSETS,
-                                              "a net's first layer takes in_dim = " + std::to_string(in_dim) + " inputs, not %d",
-                                              "the actor ends in act_dim = " + std::to_string(act_dim) + " outputs, the critic in 1", count);
+  const std::string takes = priv ? "the actor's first layer takes in_dim = " + std::to_string(in_dim) + " inputs and the critic's critic_in_dim = " +
+                                       std::to_string(critic_in_dim) + ", not %d"
+                                 : "a net's first layer takes in_dim = " + std::to_string(in_dim) + " inputs, not %d";
+  const std::string wrong = check_layer_table(layers_host, n_layers_total, in_dim, act_dim, NO_OFFSETS, takes,
+                                              "the actor ends in act_dim = " + std::to_string(act_dim) + " outputs, the critic in 1", count,
+                                              priv ? critic_in_dim : 0);
   if (!wrong.empty()) return bad(wrong);
   NetImage im;
-  if (int rc = commit_ready(h, name, build_image(im, layers_host, n_layers_total, count, in_dim, act_dim, true))) return rc;
+  if (int rc = commit_ready(h, name, build_image(im, layers_host, n_layers_total, count, in_dim, act_dim, true, priv ? critic_in_dim : 0))) return rc;
+  if (student) { h->critic_rows = nullptr; h->critic_stride = 0; }
   slot.d_pol_image.swap(im.image); slot.d_pol_layers.swap(im.layers);
   slot.pol = im.pa; slot.pol.clip = (float)clip;
   slot.pol_repack = im.rp; slot.pol_n_base = im.n_src; slot.pol_filled = false;
@@ -1323,6 +1342,23 @@ static int set_policy_slot(mocca_handle h, const char* name, bool student, const
 
 int mocca_set_policy(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) {
   return set_policy_slot(h, "mocca_set_policy", true, layers_host, n_layers_total, in_dim, act_dim, clip);
+}
+
+int mocca_set_policy_priv(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int critic_in_dim, int act_dim, double clip) {
+  return set_policy_slot(h, "mocca_set_policy_priv", true, layers_host, n_layers_total, in_dim, act_dim, clip, true, critic_in_dim);
+}
+
+int mocca_set_critic_rows(mocca_handle h, const float* rows_dev, int row_stride) {
+  if (!h) return MOCCA_E_ARG;
+  auto bad = [&](const std::string& what) { h->err = "mocca_set_critic_rows: " + what; return MOCCA_E_ARG; };
+  if (!rows_dev) { h->critic_rows = nullptr; h->critic_stride = 0; return MOCCA_OK; }   // detach
+  const mocca_pol::PolicyArgs& p = h->student.pol;
+  if (!h->student.d_pol_image || !p.critic_in_dim)
+    return bad("needs a policy with a privileged critic (mocca_set_policy_priv): the plain policy's critic reads mocca_act's in_dev");
+  if (row_stride < p.critic_in_dim)
+    return bad("row_stride " + std::to_string(row_stride) + " is smaller than the policy's critic_in_dim (" + std::to_string(p.critic_in_dim) + ")");
+  h->critic_rows = rows_dev; h->critic_stride = row_stride;
+  return MOCCA_OK;
 }
 
 int mocca_set_teacher(mocca_handle h, const int32_t* layers_host, int n_layers_total, int in_dim, int act_dim, double clip) {
@@ -1374,6 +1410,8 @@ static int set_policy_mirror(mocca_handle h, const char* name, mocca_ppo::PpoMod
   DeviceGuard guard(h->device);
   auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
   if (!h->student.d_pol_image) return bad("needs a policy (mocca_set_policy)");
+  if (in_perm_host && h->student.pol.critic_in_dim)
+    return bad("the policy has a privileged critic (mocca_set_policy_priv): mirror tables for the critic's row are not provided, set a plain policy first (mocca_set_policy)");
   if (!in_perm_host) {   // detach
     if (int rc = commit_ready(h, name)) return rc;
     if (h->pol_mirror.method == method) drop_policy_mirror(h);
@@ -1423,10 +1461,10 @@ int mocca_set_policy_mirror_dup(mocca_handle h, const int32_t* in_perm_host, con
 
 // what n_floats of a flat parameter tensor must be (mocca_update_policy, mocca_update_teacher, mocca_adam_step): -> "" or what is wrong
 static std::string check_n_floats(const mocca_ctx::PolicySlot& slot, size_t n_floats) {
-  const size_t base = slot.pol_n_base, in_dim = (size_t)slot.pol.in_dim;
-  if (n_floats == base || n_floats == base + 2 * in_dim) return "";
-  return "this policy takes " + std::to_string(base) + " floats (layers, log_std), or " + std::to_string(base + 2 * in_dim) +
-         " with mean and inv_std, not " + std::to_string(n_floats);
+  const size_t base = slot.pol_n_base, in_dim = (size_t)slot.pol.in_dim, critic_in = (size_t)slot.pol.critic_in_dim;
+  if (n_floats == base || n_floats == base + 2 * in_dim + 2 * critic_in) return "";
+  return "this policy takes " + std::to_string(base) + " floats (layers, log_std), or " + std::to_string(base + 2 * in_dim + 2 * critic_in) +
+         (critic_in ? " with mean, inv_std, critic_mean and critic_inv_std, not " : " with mean and inv_std, not ") + std::to_string(n_floats);
 }
 
 // the repack launch of mocca_update_policy / mocca_update_teacher; n_floats has been checked, the handle's device is current
@@ -1438,6 +1476,10 @@ static void repack_policy(const mocca_ctx::PolicySlot& slot, const float* params
   rp.rows[slot.pol_tail_row].fill = norm ? 1.0f : 0.0f;
   rp.rows[slot.pol_tail_row + 1].src = norm ? (int32_t)base : -1;
   rp.rows[slot.pol_tail_row + 2].src = norm ? (int32_t)(base + in_dim) : -1;
+  if (const size_t critic_in = (size_t)slot.pol.critic_in_dim) {   // a privileged critic: its statistics follow, all four or none
+    rp.rows[slot.pol_tail_row + 3].src = norm ? (int32_t)(base + 2 * in_dim) : -1;
+    rp.rows[slot.pol_tail_row + 4].src = norm ? (int32_t)(base + 2 * in_dim + critic_in) : -1;
+  }
   mocca_pol::launch_repack(s, rp);
 }
 
@@ -1499,7 +1541,11 @@ static int launch_act(mocca_handle h, const char* who, const float* in_dev, int 
   if ((long long)h->env_offset + h->n_envs > (1ll << 28) || h->env_offset < 0) {
     h->err = std::string(who) + ": the noise is keyed by global env ids below 2^28 (MOCCA_PARAM_ENV_OFFSET + n_envs)"; return MOCCA_E_ARG;
   }
+  if (h->student.pol.critic_in_dim && value_dev && !h->critic_rows) {
+    h->err = std::string(who) + ": the policy's critic reads rows of its own: bind them (mocca_set_critic_rows), or pass value_dev NULL"; return MOCCA_E_ARG;
+  }
   mocca_pol::PolicyArgs a = h->student.pol;
+  a.critic_in = h->critic_rows; a.critic_stride = h->critic_stride;
   a.in = in_dev; a.in_stride = in_stride; a.eps = eps_dev; a.deterministic = deterministic != 0;
   a.task = h->d_task; a.task_words = MOCCA_TASK_WORDS; a.tw_t = MOCCA_TW_T; a.tw_episode = MOCCA_TW_EPISODE;
   a.env_offset = h->env_offset; a.seed_lo = (uint32_t)h->seed; a.seed_hi = (uint32_t)(h->seed >> 32);
@@ -1624,15 +1670,26 @@ static mocca_ppo::PpoMode ppo_mode(mocca_handle h) { return h->pol_mirror.method
 static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, const float* obs_dev, int obs_stride, const float* action_dev,
                     const float* old_logp_dev, const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev,
                     int64_t n_rows, double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev,
-                    void* stream, bool check_only = false) {   // check_only: the refusals alone (mocca_ppo_update asks before its first launch)
+                    void* stream, bool check_only = false,   // check_only: the refusals alone (mocca_ppo_update asks before its first launch)
+                    const float* critic_obs_dev = nullptr, int critic_stride = 0) {   // PPO_PRIV (mocca_ppo_grad_priv): the storage's critic rows
   using namespace mocca_ctrl;
   using namespace mocca_ppo;
   if (!h) { g_err = std::string(name) + ": NULL handle"; return MOCCA_E_ARG; }
   auto bad = [&](const std::string& what) { h->err = std::string(name) + ": " + what; return MOCCA_E_ARG; };
   if (!h->student.d_pol_image || !h->student.pol_filled) return bad("needs a policy (mocca_set_policy, then mocca_update_policy)");
   const bool distil = mode == PPO_DISTIL;
-  const bool sym = mode != PPO_PLAIN && !distil;   // twice the columns
-  if (const PpoMode attached = ppo_mode(h); distil) {
+  const bool priv = mode == PPO_PRIV;
+  const bool sym = mode != PPO_PLAIN && !distil && !priv;   // twice the columns
+  if (const bool has = h->student.pol.critic_in_dim != 0; has != priv) {   // (a privileged critic and a mirror attachment exclude each other)
+    if (has && distil) return bad("the policy has a privileged critic (mocca_set_policy_priv): distilling into an asymmetric student is not provided");
+    if (has) return bad("the policy has a privileged critic (mocca_set_policy_priv): its gradient is mocca_ppo_grad_priv, its update mocca_ppo_update_priv");
+    return bad("needs a policy with a privileged critic (mocca_set_policy_priv); the plain policy's gradient is mocca_ppo_grad, its update mocca_ppo_update");
+  }
+  if (priv) {
+    if (!critic_obs_dev) return bad("critic_obs_dev must not be NULL");
+    if (critic_stride < h->student.pol.critic_in_dim)
+      return bad("critic_stride " + std::to_string(critic_stride) + " is smaller than the policy's critic_in_dim (" + std::to_string(h->student.pol.critic_in_dim) + ")");
+  } else if (const PpoMode attached = ppo_mode(h); distil) {
     if (attached != PPO_PLAIN)
       return bad(std::string("a mirror attachment is in place (") + (attached == PPO_SYM ? "mocca_set_policy_symmetry" : attached == PPO_MIRROR ? "mocca_set_policy_mirror_loss" : "mocca_set_policy_mirror_dup") +
                  "): the regression gradient is the plain policy's, detach it first");
@@ -1685,6 +1742,12 @@ static int ppo_grad(mocca_handle h, const char* name, mocca_ppo::PpoMode mode, c
   long long pos = 0;
   int n_tiles = PPO_ROW_COLS / 16, n_head = p.act_dim;
   a.a0_off = pos; pos += bp * p.in_pad;
+  a.a0c_off = a.a0_off;
+  if (priv) {   // A0c (mocca_ppo.h: Privileged critic)
+    a.critic_obs = critic_obs_dev; a.critic_stride = critic_stride; a.critic_in_dim = p.critic_in_dim; a.critic_in_pad = p.critic_in_pad;
+    a.critic_mean_off = p.critic_mean_off; a.critic_inv_std_off = p.critic_inv_std_off;
+    a.a0c_off = pos; pos += bp * p.critic_in_pad;
+  }
   for (int i = 0; i < n_layers; ++i) {
     const int32_t* r = &h->student.pol_table[(size_t)i * CTRL_LAYER_WORDS];
     a.a_off[i] = pos; pos += bp * r[CL_OUT_PAD];
@@ -1732,6 +1795,14 @@ int mocca_ppo_grad_dup(mocca_handle h, const float* obs_dev, int obs_stride, con
                        double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev, void* stream) {
   return ppo_grad(h, "mocca_ppo_grad_dup", mocca_ppo::PPO_DUP, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev,
                   idx_dev, n_rows, clip, value_coef, entropy_coef, value_clip, grad_dev, stats_dev, stream);
+}
+
+int mocca_ppo_grad_priv(mocca_handle h, const float* obs_dev, int obs_stride, const float* critic_obs_dev, int critic_stride, const float* action_dev,
+                        const float* old_logp_dev, const float* adv_dev, const float* returns_dev, const float* old_value_dev, const int64_t* idx_dev,
+                        int64_t n_rows, double clip, double value_coef, double entropy_coef, int value_clip, float* grad_dev, float* stats_dev,
+                        void* stream) {
+  return ppo_grad(h, "mocca_ppo_grad_priv", mocca_ppo::PPO_PRIV, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev,
+                  idx_dev, n_rows, clip, value_coef, entropy_coef, value_clip, grad_dev, stats_dev, stream, false, critic_obs_dev, critic_stride);
 }
 
 // the refusals of mocca_adam_step's arguments (mocca_ppo_update shares them): -> MOCCA_OK, or MOCCA_E_ARG with the message set
@@ -1838,6 +1909,24 @@ int mocca_ppo_update(mocca_handle h, const float* obs_dev, int obs_stride, const
                      [&](const int64_t* idx, float* grad, float* stats_row, bool check_only) {
                        return ppo_grad(h, name, mode, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev, idx,
                                        minibatch_rows, clip, value_coef, entropy_coef, value_clip, grad, stats_row, stream, check_only);
+                     });
+}
+
+int mocca_ppo_update_priv(mocca_handle h, const float* obs_dev, int obs_stride, const float* critic_obs_dev, int critic_stride,
+                          const float* action_dev, const float* old_logp_dev, const float* adv_dev, const float* returns_dev,
+                          const float* old_value_dev, int64_t n_rollout_rows, int64_t minibatch_rows, int epochs, double clip, double value_coef,
+                          double entropy_coef, int value_clip, float* params_dev, size_t n_floats, int64_t n_params, float* moments_dev,
+                          double* clock_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm, uint64_t seed,
+                          float* stats_dev, void* stream) {
+  const char* name = "mocca_ppo_update_priv";
+  if (int rc = adam_check(h, name, params_dev, n_floats, nullptr, false, n_params, moments_dev, clock_dev, lr, beta1, beta2, eps, max_grad_norm))
+    return rc;
+  return update_loop(h, name, false, n_rollout_rows, minibatch_rows, epochs, params_dev, n_floats, n_params, moments_dev, clock_dev, lr, beta1,
+                     beta2, eps, max_grad_norm, seed, stats_dev, stream,
+                     [&](const int64_t* idx, float* grad, float* stats_row, bool check_only) {
+                       return ppo_grad(h, name, mocca_ppo::PPO_PRIV, obs_dev, obs_stride, action_dev, old_logp_dev, adv_dev, returns_dev, old_value_dev,
+                                       idx, minibatch_rows, clip, value_coef, entropy_coef, value_clip, grad, stats_row, stream, check_only,
+                                       critic_obs_dev, critic_stride);
                      });
 }
 

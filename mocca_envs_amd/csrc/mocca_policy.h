@@ -14,6 +14,8 @@
 //               DEVICE word, so that an update between two replays of a captured launch switches it without a recapture)
 //   mean        [in_pad], zeros past in_dim
 //   inv_std     [in_pad], zeros past in_dim        x = clamp((x - mean[k]) * inv_std[k], -clip, +clip), f32, in that operation order
+//   critic_mean, critic_inv_std   [critic_in_pad] each, zeros past critic_in_dim: ONLY in the image of a policy with a privileged critic
+//               (below); a plain policy's image has neither and its offsets are what they were
 //   transposed  behind everything above (the policy kernel reads none of it): the weights of every layer but a net's first once more,
 //               transposed, for mocca_ppo_grad's backward (mocca_ppo.h: Image)
 //
@@ -47,6 +49,15 @@
 // mean_dev receives `mean`; deterministic: action = mean bit for bit.  The noise is the plain instance's: same keying, each env's normals drawn
 // once, so for the same seed, env and counters both instances see the same eps.  CONSEQUENCE: act(M_o s) = M_a act(s) and value(M_o s) =
 // value(s) hold numerically (==; a sum that cancels may come out as -0 on one side and +0 on the other): the combine is commutative.
+//
+// Privileged critic (mocca_set_policy_priv: an asymmetric actor-critic).  The critic has an input of its own: critic_in_dim floats per row
+// (1 .. POL_MAX_IN: the LDS row is the same) from a second buffer `critic_in` with its own stride, and its own statistics critic_mean /
+// critic_inv_std behind inv_std in the image.  policy_kernel<false, true> is the plain instance with the staging of the critic's workgroups
+// (net == 1, uniform over the workgroup) reading feature k < critic_in_dim of critic_in[env * critic_stride + k], normalised as
+// clamp((x - critic_mean[k]) * critic_inv_std[k], -clip, +clip) -- the same f32 operations in the same order, the same clip and the same flag
+// word as the actor's -- and padded with zeros to critic_in_pad.  The actor's workgroups, the layer loop and the head stage are the plain
+// instance's: action, logp and mean are the bits of a plain policy with the same actor, the value those of a plain policy of in_dim =
+// critic_in_dim with the same critic on the critic's rows.  No mirror tables: the symmetric instance has no such twin.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -87,9 +98,14 @@ struct PolicyArgs {
   const float* in_sign;         // [in_dim]
   const int32_t* act_perm;      // [act_dim]
   const float* act_sign;        // [act_dim]
+  // the privileged critic (header: Privileged critic); critic_in_dim 0: both nets read `in`.  At the END: the members above keep their offsets
+  const float* critic_in;       // [N][critic_stride], the first critic_in_dim floats of a row are read by the critic's workgroups
+  int critic_stride, critic_in_dim, critic_in_pad;
+  int critic_mean_off, critic_inv_std_off;   // float offsets into the image
 };
 
-// one row of the repack kernel's table, one per layer and one per tail array (log_std, mean, inv_std: out = 1 row, no fragment order)
+// one row of the repack kernel's table, one per layer and one per tail array (log_std, mean, inv_std, critic_mean, critic_inv_std: out = 1 row,
+// no fragment order)
 struct RepackRow {
   int32_t dst, dst_end;         // image range [dst, dst_end)
   int32_t src;                  // offset in the caller's parameters, < 0: the first `out` floats are `fill`, the rest zeros
@@ -97,7 +113,7 @@ struct RepackRow {
   float fill;
   int32_t transposed;           // weights: != 0: the row's matrix [out][in] is the transpose of the source's W[in][out] (mocca_ppo.h: Image)
 };
-constexpr int POL_MAX_REPACK_ROWS = 6 * POL_MAX_LAYERS + 4;   // weights + bias of 16 layers, log_std, flags, mean, inv_std; 16 transposed copies
+constexpr int POL_MAX_REPACK_ROWS = 6 * POL_MAX_LAYERS + 6;   // weights + bias of 16 layers, log_std, flags, mean, inv_std, critic_mean, critic_inv_std; 16 transposed copies
 struct RepackArgs {
   const float* src;
   float* image;

@@ -36,8 +36,10 @@ static_assert(TILE == 16, "one 16-env MFMA sub-tile per workgroup; the noise sta
 static_assert(2 * POL_SYM_TILE == TILE, "the symmetric instance: column c the env as given, column POL_SYM_TILE + c its mirror image");
 static_assert(POL_MAX_WIDTH <= POL_MAX_IN && POL_MAX_ACTION <= 32, "LDS rows hold the widest layer; 16 Philox blocks give 32 normals");
 
-template <bool SYM>
+// PRIV (header: Privileged critic): the plain layout with the critic's workgroups staging their own rows under their own statistics
+template <bool SYM, bool PRIV = false>
 __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
+  static_assert(!(SYM && PRIV), "the privileged critic has no mirror tables");
   constexpr int ENVS = SYM ? POL_SYM_TILE : TILE;   // envs of a workgroup
   __shared__ __attribute__((aligned(16))) float X[2][TILE * LDS_STRIDE];
   __shared__ float Z[ENVS * POL_MAX_ACTION];   // the tile's noise, Z[env][j]
@@ -47,7 +49,21 @@ __global__ __launch_bounds__(256, 2) void policy_kernel(PolicyArgs a) {
 
   // input: the first in_dim floats of the env's row, normalised, zeros up to in_pad; rows past the batch are zeros (nothing of them is stored).
   // SYM: column e >= ENVS is the mirror image of env e - ENVS, formed from the RAW row (the statistics are not symmetric) and normalised by k
-  {
+  // PRIV: a second copy of the loop, not one loop over parameters -- folded into one lambda the two moved instructions in both existing
+  // instances, which are held to the instruction streams they had (profiles/kernel_resources_priv_critic.md)
+  if (PRIV && net == 1) {   // the critic's own rows and statistics: the loop below, field for field
+    const bool norm = a.params[a.flags_off] != 0.0f;
+    const float *mu = a.params + a.critic_mean_off, *is = a.params + a.critic_inv_std_off;
+    for (int i = tid; i < TILE * a.critic_in_pad; i += 256) {
+      const int e = i / a.critic_in_pad, k = i - e * a.critic_in_pad, env = env0 + e;
+      float v = 0.0f;
+      if (env < a.n_envs && k < a.critic_in_dim) {
+        v = a.critic_in[(size_t)env * a.critic_stride + k];
+        if (norm) v = normalise(v, mu[k], is[k], a.clip);
+      }
+      X[0][e * LDS_STRIDE + k] = v;
+    }
+  } else {
     const bool norm = a.params[a.flags_off] != 0.0f;
     const float *mu = a.params + a.mean_off, *is = a.params + a.inv_std_off;
     for (int i = tid; i < TILE * a.in_pad; i += 256) {
@@ -155,8 +171,9 @@ __global__ __launch_bounds__(256) void repack_kernel(RepackArgs a) {
 }
 
 void launch_policy(hipStream_t s, const PolicyArgs& a) {
-  if (a.in_perm) hipLaunchKernelGGL(policy_kernel<true>, dim3((a.n_envs + POL_SYM_TILE - 1) / POL_SYM_TILE, a.value ? 2 : 1), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(policy_kernel<false>, dim3((a.n_envs + TILE - 1) / TILE, a.value ? 2 : 1), dim3(256), 0, s, a);
+  if (a.in_perm) hipLaunchKernelGGL((policy_kernel<true>), dim3((a.n_envs + POL_SYM_TILE - 1) / POL_SYM_TILE, a.value ? 2 : 1), dim3(256), 0, s, a);
+  else if (a.critic_in_dim) hipLaunchKernelGGL((policy_kernel<false, true>), dim3((a.n_envs + TILE - 1) / TILE, a.value ? 2 : 1), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((policy_kernel<false>), dim3((a.n_envs + TILE - 1) / TILE, a.value ? 2 : 1), dim3(256), 0, s, a);
 }
 
 void launch_repack(hipStream_t s, const RepackArgs& a) {

@@ -74,6 +74,17 @@
 // zeros where that is NULL.  PpoArgs carries the targets in `action`, the value targets in `returns` and k2 = f32(2 distill_coef) in `mirror_k2`;
 // old_logp, adv and old_value are not read, entropy_coef is 0.  Launches 2 to 4 are unchanged (launch 4 writes stats[7] from column 36, as for
 // the mirror loss); the scratch is the plain call's.
+//
+// Privileged critic (mocca_ppo_grad_priv; mocca_policy.h: Privileged critic).  PPO's loss separates: the surrogate and the entropy depend on the
+// actor and log_std alone, the value term on the critic alone.  ppo_rows_kernel<PPO_PRIV> is the PLAIN instance -- one column per row, its layer
+// loop, head stage and backward -- with the staging of the critic's workgroups (net == 1, uniform over the workgroup) reading feature k <
+// critic_in_dim of critic_obs[src * critic_stride + k] under critic_mean / critic_inv_std (the same f32 operations, clip and flag word), padded
+// with zeros to critic_in_pad, and writing the tile to a second scratch array
+//   A0c     [B_pad][critic_in_pad]        the critic's normalised input (written by the CRITIC's workgroups; rows past B zeros)
+// which launch 2 reads as the input of the critic's first layer: PpoArgs.a0c_off, equal to a0_off in every other mode.  That layer's dW tiles
+// cover critic_in_pad (the table's own in_pad), and n_head follows the table's own in.  Launches 3 and 4 are the plain ones (column 36 of R
+// is zeros: stats[7] = 0).  Every sum's order is the plain call's, so the actor's and log_std's gradients are the bits of mocca_ppo_grad on
+// a plain policy with the same actor, the critic's those of a plain policy of in_dim = critic_in_dim with the same critic on the critic's rows.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,7 +95,7 @@ namespace mocca_ppo {
 
 constexpr int PPO_ROW_COLS = 48;         // floats per row of R
 constexpr int PPO_COL_SURR = 32, PPO_COL_VLOSS = 33, PPO_COL_DLOGP = 34, PPO_COL_CLIPPED = 35, PPO_COL_MIRROR = 36;
-enum PpoMode { PPO_PLAIN = 0, PPO_SYM = 1, PPO_MIRROR = 2, PPO_DUP = 3, PPO_DISTIL = 4 };   // mocca_ppo_grad, _sym, _mirror, _dup; mocca_distill_grad
+enum PpoMode { PPO_PLAIN = 0, PPO_SYM = 1, PPO_MIRROR = 2, PPO_DUP = 3, PPO_DISTIL = 4, PPO_PRIV = 5 };   // mocca_ppo_grad, _sym, _mirror, _dup; mocca_distill_grad; mocca_ppo_grad_priv
 constexpr int PPO_MAX_CHUNKS = 16;       // row chunks of launch 2
 constexpr int PPO_CHUNK_MIN_ROWS = 512;  // a chunk holds at least this many rows
 constexpr int PPO_REDUCE_BLOCK = 256;
@@ -124,6 +135,11 @@ struct PpoArgs {
   float* grad;                           // [n_head]
   float* stats;                          // [8] or null
   int n_samples;                         // what stats[4]'s count is divided by: B, PPO_DUP: 2 B
+  // the privileged critic (header: Privileged critic), read by PPO_PRIV alone.  At the END: the members above keep their offsets
+  const float* critic_obs; int critic_stride;   // the storage's critic rows [R][critic_stride], gathered through the same idx
+  int critic_in_dim, critic_in_pad;
+  int critic_mean_off, critic_inv_std_off;
+  long long a0c_off;                     // A0c: what launch 2 reads as the input of the critic's FIRST layer; every other mode: a0_off
 };
 
 // row chunks of launch 2 for a minibatch of b_pad rows: a function of B alone

@@ -54,11 +54,13 @@ __device__ __forceinline__ float activate_slope(float x, int act) {
 // adds the mirror term over the actor's two columns, and its critic's mirrored columns are not live.  PPO_DUP's runs the plain per-row lines
 // on each of the 16 columns by itself: a mirrored column is one more sample, with the action mirrored too.
 // PPO_DISTIL (header: Distillation): the plain instance -- one column per row, its staging, layer loop and backward -- with the regression head stage.
+// PPO_PRIV (header: Privileged critic): the plain instance with the critic's workgroups staging the critic's own rows, to A0c.
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
   __shared__ __attribute__((aligned(16))) float X[2][TILE * LDS_STRIDE];
   constexpr bool DISTIL = MODE == PPO_DISTIL; // the regression head stage on the plain layout
-  constexpr bool SYM = MODE != PPO_PLAIN && !DISTIL;   // the two-column layout
+  constexpr bool PRIV = MODE == PPO_PRIV;     // the critic's own staging on the plain layout (header: Privileged critic)
+  constexpr bool SYM = MODE != PPO_PLAIN && !DISTIL && !PRIV;   // the two-column layout
   constexpr bool NET = MODE == PPO_SYM;       // the symmetric network's head stage
   constexpr bool ML = MODE == PPO_MIRROR;     // the mirror loss's head stage
   constexpr bool DUP = MODE == PPO_DUP;       // duplicated rows: the plain head stage, one lane per COLUMN
@@ -71,7 +73,24 @@ __global__ __launch_bounds__(256, 2) void ppo_rows_kernel(PpoArgs a) {
 
   // input: the policy kernel's staging, the rows gathered through idx; the normalised tile also goes to A0.  SYM: column e >= ROWS is the
   // mirror image of row e - ROWS, formed from the RAW row through in_perm / in_sign and normalised by k
-  {
+  // PRIV: a second copy of the loop, not one loop over parameters -- folded into one lambda the two made the compiler move instructions in all
+  // five existing instances, which are held to the instruction streams they had (profiles/kernel_resources_priv_critic.md)
+  if (PRIV && net == 1) {   // the critic's own rows and statistics, the tile to A0c: the loop below, field for field
+    const bool norm = a.params[a.flags_off] != 0.0f;
+    const float *mu = a.params + a.critic_mean_off, *is = a.params + a.critic_inv_std_off;
+    float* A0c = a.scratch + a.a0c_off;
+    for (int i = tid; i < TILE * a.critic_in_pad; i += 256) {
+      const int e = i / a.critic_in_pad, k = i - e * a.critic_in_pad, row = row0 + e;
+      float v = 0.0f;
+      if (row < B && k < a.critic_in_dim) {
+        const long long src = a.idx ? (long long)a.idx[row] : row;
+        v = a.critic_obs[(size_t)src * a.critic_stride + k];
+        if (norm) v = fminf(fmaxf((v - mu[k]) * is[k], -a.norm_clip), a.norm_clip);
+      }
+      X[0][e * LDS_STRIDE + k] = v;
+      A0c[(size_t)(srow0 + e) * a.critic_in_pad + k] = v;
+    }
+  } else {
     const bool norm = a.params[a.flags_off] != 0.0f;
     const float *mu = a.params + a.mean_off, *is = a.params + a.inv_std_off;
     float* A0 = a.scratch + a.a0_off;
@@ -336,7 +355,7 @@ __global__ __launch_bounds__(64) void ppo_wgrad_kernel(PpoArgs a) {
     if (t < n_ot * n_kt) {
       const int ot = t / n_kt, kt = t - ot * n_kt;
       const bool first = gl == 0 || gl == a.n_actor;
-      const float* Ap = a.scratch + (first ? a.a0_off : a.a_off[gl - 1]);   // the layer's input [b_pad][in_pad]
+      const float* Ap = a.scratch + (first ? (gl == 0 ? a.a0_off : a.a0c_off) : a.a_off[gl - 1]);   // the layer's input [b_pad][in_pad]; a0c_off: A0, PPO_PRIV: A0c
       const float* pz = dZ + (size_t)(r_begin + quad) * out_pad + 16 * ot + col;
       const float* pa = Ap + (size_t)(r_begin + quad) * in_pad + 16 * kt + col;
       f32x4 acc[NP];
@@ -453,6 +472,7 @@ void launch_ppo(hipStream_t s, const PpoArgs& a) {
   else if (a.mode == PPO_MIRROR) hipLaunchKernelGGL(ppo_rows_kernel<PPO_MIRROR>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   else if (a.mode == PPO_DUP) hipLaunchKernelGGL(ppo_rows_kernel<PPO_DUP>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   else if (a.mode == PPO_DISTIL) hipLaunchKernelGGL(ppo_rows_kernel<PPO_DISTIL>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
+  else if (a.mode == PPO_PRIV) hipLaunchKernelGGL(ppo_rows_kernel<PPO_PRIV>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(ppo_rows_kernel<PPO_PLAIN>, dim3(a.b_pad / TILE, 2), dim3(256), 0, s, a);
   hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(a.n_tiles, a.n_chunks), dim3(64), 0, s, a);
   hipLaunchKernelGGL(ppo_reduce_kernel, dim3(a.n_reduce_blocks), dim3(PPO_REDUCE_BLOCK), 0, s, a);

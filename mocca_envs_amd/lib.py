@@ -99,6 +99,11 @@ SYMBOLS = {
     "mocca_set_teacher": (_i, [_vp, _vp, _i, _i, _i, _d]),
     "mocca_update_teacher": (_i, [_vp, _vp, _sz, _vp]),
     "mocca_teacher_act": (_i, [_vp, _vp, _i, C.c_int64, _vp, _vp, _vp]),
+    "mocca_set_policy_priv": (_i, [_vp, _vp, _i, _i, _i, _i, _d]),
+    "mocca_set_critic_rows": (_i, [_vp, _vp, _i]),
+    "mocca_ppo_grad_priv": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _d, _d, _d, _i, _vp, _vp, _vp]),
+    "mocca_ppo_update_priv": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _i, _d, _d, _d, _i, _vp, _sz, C.c_int64,
+                                   _vp, _vp, _d, _d, _d, _d, _d, _u64, _vp, _vp]),
     "mocca_is_diagnostic_build": (_i, []),
     "mocca_kernel_info": (_i, [_vp] + [C.POINTER(_i)] * 5),
     "mocca_last_error": (C.c_char_p, [_vp]),

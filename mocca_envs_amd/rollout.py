@@ -249,9 +249,10 @@ def adam_args(policy, device, params, grad, state, n_params, lr, betas, eps, max
     """check the tensors and numbers of adam_step (`grad` None: ppo_update, which owns its gradient) -> n_params; ValueError otherwise"""
     import torch
     n_head = policy.n_head()
+    n_tail = policy.n_tail() if hasattr(policy, "n_tail") else 2 * policy.in_dim   # an asymmetric policy: + the critic's statistics
     if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.device != device or params.dim() != 1 \
-            or not params.is_contiguous() or params.numel() not in (n_head, n_head + 2 * policy.in_dim):
-        raise ValueError(f"params must be a contiguous float32 [{n_head}] or [{n_head + 2 * policy.in_dim}] tensor on the env's device "
+            or not params.is_contiguous() or params.numel() not in (n_head, n_head + n_tail):
+        raise ValueError(f"params must be a contiguous float32 [{n_head}] or [{n_head + n_tail}] tensor on the env's device "
                          "(DevicePolicy.flat_params()'s order); it is updated in place")
     n_params = n_head if n_params is None else int(n_params)
     if not 1 <= n_params <= n_head:

@@ -411,12 +411,20 @@ class TorchVecEnv:
         the env's -- on a planner env with its base controller the 15-number plans, and act_step() goes policy -> base controller -> step
         (VecEnv.act_plan_step); `update_policy(policy_or_flat_tensor)` refreshes its weights once per PPO iteration.  One handle only.  A
         policy with mirror tables (`symmetric_policy(p)`, `DevicePolicy(symmetry=)`) acts as the symmetric network: the tables cover the
-        whole row."""
+        whole row.  An `asymmetric` policy (a privileged critic) needs `privileged_scan=`: its critic reads `envs.privileged` ([obs | scan]),
+        which this call binds (VecEnv.set_critic_rows), so act_step()'s value is the privileged critic's; the actor reads the observation
+        row as ever."""
         self._one("attach_policy")
         act_dim = self.venv.plan_dim if self._plan else self.venv.act_dim
         if policy is not None and (policy.in_dim != self.observation_space.shape[0] or policy.act_dim != act_dim):
             raise ValueError(f"the policy maps {policy.in_dim} -> {policy.act_dim}, the env {self.observation_space.shape[0]} -> {act_dim}")
+        asym = getattr(policy, "asymmetric", False)
+        if asym and (self.privileged is None or policy.critic_in_dim != self.privileged.shape[1]):
+            raise ValueError(f"the policy's critic reads {policy.critic_in_dim} inputs of its own: " + (
+                "that takes privileged_scan= ([obs | scan])" if self.privileged is None else f"envs.privileged has {self.privileged.shape[1]} ([obs | scan])"))
         self.venv.set_policy(policy)
+        if asym:
+            self.venv.set_critic_rows(self.privileged)
         n, f32 = self.num_envs, dict(dtype=torch.float32, device=self.device)
         self._pol_bufs = None if policy is None else {"action": torch.zeros(n, policy.act_dim, **f32), "logp": torch.zeros(n, 1, **f32),
                                                       "value": torch.zeros(n, 1, **f32)}

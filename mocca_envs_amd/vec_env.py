@@ -398,6 +398,7 @@ class VecEnv:
     mirror_loss = None   # (tables, coef) while set_policy_mirror_loss has one attached
     mirror_dup = None    # tables while set_policy_mirror_dup has them attached
     teacher = None
+    critic_rows = None   # the rows set_critic_rows bound (an asymmetric policy's critic reads them)
     _pol_action = None   # act_step()'s own action buffer, made on first use
     _scan_points = None  # the pattern set_height_scan attached
     _depth_cam = None    # the camera set_depth_camera attached
@@ -409,6 +410,12 @@ class VecEnv:
             _lib.check(fn(self.h, None, 0, 0, 0, 0.0), self.h)
             return
         table = np.ascontiguousarray(policy.table(), np.int32)
+        if getattr(policy, "asymmetric", False):      # a privileged critic: the student's slot alone takes one
+            if fn is not self.lib.mocca_set_policy:
+                raise ValueError("set_teacher: the teacher is a plain policy; one with a privileged critic is not supported")
+            _lib.check(self.lib.mocca_set_policy_priv(self.h, table.ctypes.data_as(C.c_void_p), table.shape[0], int(policy.in_dim),
+                                                      int(policy.critic_in_dim), int(policy.act_dim), float(policy.clip)), self.h)
+            return
         _lib.check(fn(self.h, table.ctypes.data_as(C.c_void_p), table.shape[0], int(policy.in_dim), int(policy.act_dim), float(policy.clip)), self.h)
 
     def _update_slot(self, fn, params) -> None:
@@ -424,14 +431,35 @@ class VecEnv:
 
     def set_policy(self, policy) -> None:
         """Attach a `policy.DevicePolicy` (None detaches): its shapes size the kernel's image, its weights are uploaded (update_policy).
-        May synchronise."""
+        An `asymmetric` policy (a privileged critic: another `critic_in_dim`, or critic statistics) goes through mocca_set_policy_priv:
+        bind the critic's rows with set_critic_rows() before act() is asked for a value; the mirror attachments, distill_grad() and
+        distill_update() are not provided for it.  May synchronise."""
         self._set_slot(self.lib.mocca_set_policy, policy)
         self.policy, self.mirror_loss, self.mirror_dup = policy, None, None   # mocca_set_policy has dropped every attachment
+        self.critic_rows = None                                               # and the critic-row binding
         if policy is None:
             return
         self.update_policy(policy)
         if getattr(policy, "symmetry", None) is not None:      # after the shapes: mocca_set_policy has dropped whatever was attached
             self.set_policy_symmetry(policy.symmetry)
+
+    def set_critic_rows(self, rows: Optional[torch.Tensor]) -> None:
+        """Bind the rows an asymmetric policy's critic reads in act() / act_step() / act_plan_step(): `rows` float32 [n_envs, >= critic_in_dim]
+        on the env's device with contiguous rows, caller-owned and read AT EVERY LAUNCH from this fixed address (`TorchVecEnv.privileged`), so
+        the calls stay capturable; this object keeps a reference.  None detaches.  set_policy() drops the binding."""
+        if rows is None:
+            _lib.check(self.lib.mocca_set_critic_rows(self.h, None, 0), self.h)
+            self.critic_rows = None
+            return
+        p = self.policy
+        if p is None or not getattr(p, "asymmetric", False):
+            raise _lib.MoccaError("set_critic_rows needs a policy with a privileged critic (set_policy with an asymmetric DevicePolicy)")
+        if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[0] != self.n_envs or rows.shape[1] < p.critic_in_dim \
+                or rows.dtype != torch.float32 or rows.device != self.device or rows.stride(1) != 1:
+            raise ValueError(f"the critic's rows must be a float32 [n_envs, >= {p.critic_in_dim}] tensor on the env's device with contiguous rows")
+        stride = rows.stride(0) if self.n_envs > 1 else max(rows.stride(0), rows.shape[1])
+        _lib.check(self.lib.mocca_set_critic_rows(self.h, C.c_void_p(rows.data_ptr()), int(stride)), self.h)
+        self.critic_rows = rows
 
     def _set_policy_mirror(self, name: str, tables, *extra):
         """What the three setters below share: mocca_<name>(tables, *extra) -> the tables as the library took them, or None (detached)."""
@@ -625,7 +653,7 @@ class VecEnv:
     def ppo_grad(self, obs: torch.Tensor, action: torch.Tensor, old_logp: torch.Tensor, adv: torch.Tensor, returns: torch.Tensor,
                  idx: Optional[torch.Tensor] = None, old_value: Optional[torch.Tensor] = None, clip: float = 0.2, value_coef: float = 0.5,
                  entropy_coef: float = 0.0, value_clip: bool = False, grad: Optional[torch.Tensor] = None,
-                 stats: Optional[torch.Tensor] = None) -> dict:
+                 stats: Optional[torch.Tensor] = None, critic_obs: Optional[torch.Tensor] = None) -> dict:
         """The body of `ppo.update`'s minibatch loop up to `optimizer.step()` -- `evaluate_actions`, the clipped surrogate, the value loss,
         `loss.backward()` -- as four launches: -> {"grad" [policy.n_head()] in `DevicePolicy.flat_params()`'s order (`split_grad` gives
         per-layer views), "stats" [8]: mean surrogate, value loss, entropy, mean(old_logp - logp), clip fraction, sum of grad^2, 0, 0}.
@@ -640,18 +668,38 @@ class VecEnv:
         (`set_policy_mirror_dup`) the plain loss runs over the B rows and their B mirror images, every mean over 2 B, and stats[7] is the
         twins' share of stats[3] (mocca_ppo_grad_dup: the same layout again).  At most 2^21 rows in any of the three cases, 2^22
         otherwise.  `grad` / `stats`: caller-owned outputs, allocated where none is
-        given.  The same inputs give the same bits on every run."""
+        given.  The same inputs give the same bits on every run.  An asymmetric policy (a privileged critic) takes `critic_obs`
+        [R, >= critic_in_dim] or [T, N, >= critic_in_dim], the storage's RAW critic rows of the same R rows, gathered through the same
+        `idx` (mocca_ppo_grad_priv); a plain policy refuses it."""
         if self.policy is None:
             raise _lib.MoccaError("ppo_grad needs a policy (set_policy)")
+        priv = self._critic_args(obs, critic_obs)
         symmetric = getattr(self.policy, "symmetry", None) is not None
         mirror, dup = self.mirror_loss is not None, self.mirror_dup is not None
         _, stride, n_batch = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, idx, old_value, clip, value_coef,
                                           entropy_coef, value_clip, grad, stats, symmetric=self._mirrored)
         out = self._grad_out(grad, stats)
         call = self.lib.mocca_ppo_grad_dup if dup else self.lib.mocca_ppo_grad_mirror if mirror else self.lib.mocca_ppo_grad_sym if symmetric else self.lib.mocca_ppo_grad
-        self._call(call, obs, stride, action, old_logp, adv, returns, old_value, idx, n_batch, float(clip), float(value_coef), float(entropy_coef),
+        if priv:
+            call = self.lib.mocca_ppo_grad_priv
+        self._call(call, obs, stride, *priv, action, old_logp, adv, returns, old_value, idx, n_batch, float(clip), float(value_coef), float(entropy_coef),
                    int(bool(value_clip)), out["grad"], out["stats"])
         return out
+
+    def _critic_args(self, obs, critic_obs) -> tuple:
+        """ppo_grad() / ppo_update(): `critic_obs` against the attached policy -> (critic_obs, its row stride) for an asymmetric policy, ()
+        for a plain one; a ValueError where the two do not go together or the rows are not `obs`' rows"""
+        asym = getattr(self.policy, "asymmetric", False)
+        if not asym:
+            if critic_obs is not None:
+                raise ValueError("critic_obs goes with an asymmetric policy (a privileged critic); the attached policy's critic reads obs")
+            return ()
+        if not isinstance(critic_obs, torch.Tensor) or critic_obs.device != self.device:
+            raise ValueError("the attached policy has a privileged critic: critic_obs must be a float32 tensor on the env's device")
+        n_rows, stride = _ro.rows_2d(critic_obs, self.policy.critic_in_dim)
+        if isinstance(obs, torch.Tensor) and obs.dim() >= 1 and n_rows != _ro.rows_2d(obs, self.policy.in_dim)[0]:
+            raise ValueError("critic_obs must hold one row per row of obs")
+        return (critic_obs, stride)
 
     def _grad_out(self, grad, stats) -> dict:
         """what ppo_grad() / distill_grad() write and return: the caller's `grad` / `stats`, allocated where none is given"""
@@ -676,7 +724,7 @@ class VecEnv:
                    params: torch.Tensor, state, minibatch_rows: int, epochs: int, old_value: Optional[torch.Tensor] = None, clip: float = 0.2,
                    value_coef: float = 0.5, entropy_coef: float = 0.0, value_clip: bool = False, n_params: Optional[int] = None, lr: float = 3e-4,
                    betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-5, max_grad_norm: float = 0.5, seed: int = 0,
-                   stats: Optional[torch.Tensor] = None) -> dict:
+                   stats: Optional[torch.Tensor] = None, critic_obs: Optional[torch.Tensor] = None) -> dict:
         """a2c-ppo-acktr's `agent.update(rollouts)` as one call: `epochs` passes over the R rollout rows, each a fresh shuffle cut into
         M = R // minibatch_rows minibatches (the remainder is dropped), each minibatch `ppo_grad` on its rows and `adam_step` on `params`
         -- the same bits as that loop.  The storage tensors are `ppo_grad`'s, `params` / `state` / `n_params` / `lr` .. `max_grad_norm`
@@ -684,13 +732,16 @@ class VecEnv:
         -> {"stats": [epochs * M, 8]}: `ppo_grad`'s statistics per minibatch, [6] the clip coefficient applied (0: a skipped step), [7] L_m
         with a mirror loss attached, the twins' share of [3] with duplicated rows;
         `stats`: a caller-owned output.  Nothing synchronises or is read on the host; capturable after one warm call of the same shapes
-        (the scalars and the seed are baked into the capture)."""
+        (the scalars and the seed are baked into the capture).  `critic_obs`: an asymmetric policy's critic rows, as in `ppo_grad`
+        (mocca_ppo_update_priv)."""
         if self.policy is None:
             raise _lib.MoccaError("ppo_update needs a policy (set_policy)")
+        priv = self._critic_args(obs, critic_obs)
         symmetric = self._mirrored       # each attachment halves the row bound
         n_rows, stride, _ = _ro.ppo_args(self.policy, self.device, obs, action, old_logp, adv, returns, None, old_value, clip, value_coef,
                                          entropy_coef, value_clip, None, None, symmetric=symmetric)
-        return self._update_loop(self.lib.mocca_ppo_update, (obs, stride, action, old_logp, adv, returns, old_value), n_rows, minibatch_rows, epochs,
+        return self._update_loop(self.lib.mocca_ppo_update_priv if priv else self.lib.mocca_ppo_update,
+                                 (obs, stride, *priv, action, old_logp, adv, returns, old_value), n_rows, minibatch_rows, epochs,
                                  (float(clip), float(value_coef), float(entropy_coef), int(bool(value_clip))), params, state, n_params, lr, betas,
                                  eps, max_grad_norm, seed, stats, symmetric)
 
@@ -712,6 +763,8 @@ class VecEnv:
             raise _lib.MoccaError(f"{name} needs a policy (set_policy)")
         if self._mirrored:
             raise _lib.MoccaError(f"{name}: the policy has a mirror attachment (symmetry, mirror loss or duplicated rows): detach it first")
+        if getattr(self.policy, "asymmetric", False):
+            raise _lib.MoccaError(f"{name}: the policy has a privileged critic: distilling into an asymmetric student is not provided")
 
     def distill_grad(self, obs: torch.Tensor, target: torch.Tensor, value_target: Optional[torch.Tensor] = None,
                      idx: Optional[torch.Tensor] = None, distill_coef: float = 1.0, value_coef: float = 0.5,

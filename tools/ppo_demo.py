@@ -11,7 +11,7 @@ No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it Symme
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
                            [--device-policy [--device-returns [--device-grad [--device-update]]]] [--symmetric | --mirror-loss COEF | --mirror-dup]
                            [--base-controller FILE] [--height-scan NX,NY] [--depth-camera W,H]
-                           [--distill-from TEACHER.npz --privileged-scan NX,NY]
+                           [--distill-from TEACHER.npz --privileged-scan NX,NY] [--privileged-critic --privileged-scan NX,NY]
 --base-controller FILE (required for the planner ids, Walker3DPlannerEnv-v0 / MikePlannerEnv-v0): ALLSTEPS's second step.  FILE is a
 `BaseController.save_npz` file or the <out>_policy.npz of an earlier run of this script on a Stepper id (told apart by the keys; the latter
 brings its observation statistics along); it is frozen as the env's base controller and the policy trained here emits 15-number plans.
@@ -58,6 +58,14 @@ the teacher's mean and value of the state reached beside the row, one more launc
 the regression of the student's mean onto the teacher's, with the teacher's value as the critic's target -- and the logged lines carry `L_d`,
 the mean squared error of the actor's mean over the iteration's minibatches.  log_std takes no gradient from the regression: it starts at the
 teacher's and stays there.
+--privileged-critic --privileged-scan NX,NY (not with --distill-from or a symmetry method): PPO with an asymmetric actor-critic.  The actor
+reads the observation row as ever ([obs | depth] with --depth-camera W,H); the critic reads `envs.privileged`, the row [obs | scan] that
+`make_vec_envs(privileged_scan=...)` keeps beside it, under running statistics of its own.  The critic only exists while training, so nothing
+privileged reaches the policy that is saved.  The rollout storage gains `critic_obs` [T + 1][N][obs + scan], one copy per step from
+`envs.privileged` (counted in the reported rate).  Every arm builds the critic on those rows: the torch update and --verify-grad evaluate
+`vf` on them, --device-policy attaches an asymmetric `DevicePolicy` (`attach_policy` binds `envs.privileged` for the critic's workgroups),
+--device-returns keeps a second `ObsStats` that writes into the longer tail of the flat tensor, and --device-grad / --device-update pass
+`critic_obs=` (mocca_ppo_grad_priv / mocca_ppo_update_priv).  <out>_policy.npz also holds `critic_obs_mean` / `critic_obs_var`.
 --verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor
 (--mirror-dup: on that minibatch's rows whose ratio and whose twin's ratio lie more than 1e-4 from the clip bounds, where the surrogate's
 gradient jumps and two float32 evaluations may disagree on a sample's side; the twins' ratios are spread over the bounds); with
@@ -109,6 +117,7 @@ def main(argv=None):
     ap.add_argument("--terrain-gain", type=float, default=1.0, metavar="G", help="the generated fields are multiplied by G: the difficulty knob")
     ap.add_argument("--distill-from", default=None, metavar="TEACHER.npz", help="with --device-update: distil this frozen teacher (the policy file of a --height-scan run) into the student instead of PPO")
     ap.add_argument("--privileged-scan", default=None, metavar="NX,NY", help="with --distill-from: the teacher's scan_grid, kept beside the observation row (envs.privileged), never in it")
+    ap.add_argument("--privileged-critic", action="store_true", help="with --privileged-scan: PPO whose critic reads envs.privileged ([obs | scan]) while the actor reads the observation row")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args(argv)
     if args.device_grad and not args.device_returns:
@@ -140,8 +149,11 @@ def main(argv=None):
         ap.error("--distill-from requires --device-update")
     if args.distill_from is not None and (args.symmetric or args.mirror_loss is not None or args.mirror_dup or args.verify_grad):
         ap.error("--distill-from is not for --symmetric / --mirror-loss / --mirror-dup / --verify-grad: the regression gradient is the plain policy's")
-    if args.privileged_scan is not None and (args.distill_from is None or args.height_scan is not None):
-        ap.error("--privileged-scan goes with --distill-from and not with --height-scan")
+    if args.privileged_scan is not None and ((args.distill_from is None and not args.privileged_critic) or args.height_scan is not None):
+        ap.error("--privileged-scan goes with --distill-from or --privileged-critic and not with --height-scan")
+    if args.privileged_critic and (args.privileged_scan is None or args.distill_from is not None or args.symmetric or args.mirror_loss is not None
+                                   or args.mirror_dup):
+        ap.error("--privileged-critic requires --privileged-scan and is not for --distill-from / --symmetric / --mirror-loss / --mirror-dup")
     import torch
     import torch.nn as nn
     from mocca_envs_amd.trainer_api import make_vec_envs
@@ -178,7 +190,9 @@ def main(argv=None):
         nn.init.orthogonal_(net[-1].weight, gain)
         return net
 
-    pi, vf = mlp(od, ad, 0.01), mlp(od, 1, 1.0)
+    PC = args.privileged_critic
+    oc = envs.privileged.shape[1] if PC else od      # what the critic reads: [obs | scan], or the actor's row
+    pi, vf = mlp(od, ad, 0.01), mlp(oc, 1, 1.0)
     log_std = nn.Parameter(torch.full((ad,), args.log_std, device=dev), requires_grad=not args.fixed_std)
     if args.distill_from is not None:      # the regression gives log_std no gradient: the student explores with the teacher's noise throughout
         import numpy as np
@@ -192,6 +206,12 @@ def main(argv=None):
     row = lambda t: {"obs": S["obs"][t + 1], "reward": S["reward"][t], "masks": S["masks"][t + 1], "bad_masks": S["bad_masks"][t + 1]}
     mean, var, count = torch.zeros(od, device=dev), torch.ones(od, device=dev), 1e-4
     norm = lambda o: ((o - mean) / torch.sqrt(var + 1e-8)).clamp(-10.0, 10.0)
+    cnorm = norm      # the critic's normalisation; --privileged-critic: of its own rows, under its own statistics
+    if PC:
+        S["critic_obs"] = torch.zeros(T + 1, N, oc, device=dev)
+        cmean, cvar = torch.zeros(oc, device=dev), torch.ones(oc, device=dev)
+        cnorm = lambda o: ((o - cmean) / torch.sqrt(cvar + 1e-8)).clamp(-10.0, 10.0)
+    ckw = lambda: {"critic_obs": S["critic_obs"][:T]} if PC else {}      # what ppo_grad / ppo_update take beside the storage
 
     def logprob(mu, a):
         return (-0.5 * ((a - mu) / log_std.exp()) ** 2 - log_std - 0.9189385332046727).sum(-1, keepdim=True)
@@ -235,11 +255,12 @@ def main(argv=None):
         if args.symmetric:      # the mirror acts on the RAW row
             lp, _, v = sym.evaluate_actions(raw_all[mb], a_all[mb], mean, inv_std_now(), 10.0)
             return lp.unsqueeze(-1), v.unsqueeze(-1)
-        return logprob(pi(o_all[mb]), a_all[mb]), vf(o_all[mb])
+        return logprob(pi(o_all[mb]), a_all[mb]), vf(c_all[mb])
 
     if args.device_policy:
         from mocca_envs_amd.policy import DevicePolicy
-        dp = DevicePolicy.from_torch(pi, vf, log_std, obs_mean=mean, obs_var=var, eps=1e-8, clip=10.0)
+        dp = DevicePolicy.from_torch(pi, vf, log_std, obs_mean=mean, obs_var=var, eps=1e-8, clip=10.0,
+                                     **(dict(critic_obs_mean=cmean, critic_obs_var=cvar) if PC else {}))
         envs.attach_policy(envs.symmetric_policy(dp) if args.symmetric else dp)
         if args.mirror_loss is not None and args.device_grad:      # for the gradient only: act_step keeps running the plain policy
             envs.set_policy_mirror_loss(envs.policy_mirror_tables(dp), args.mirror_loss)
@@ -252,16 +273,21 @@ def main(argv=None):
             ld_sum, ld_n = torch.zeros((), device=dev), 0      # L_d over the minibatches since the last logged line
         # DevicePolicy.flat_params()'s order, built on the device: layers of pi then vf (W, b), log_std, mean, 1 / sqrt(var + eps)
         flat_params = lambda: torch.cat([q.reshape(-1) for net in (pi, vf) for m in net if isinstance(m, nn.Linear) for q in (m.weight, m.bias)]
-                                        + [log_std, mean, 1.0 / torch.sqrt(var + 1e-8)])
+                                        + [log_std, mean, 1.0 / torch.sqrt(var + 1e-8)] + ([cmean, 1.0 / torch.sqrt(cvar + 1e-8)] if PC else []))
 
     if args.device_returns:
         from mocca_envs_amd.rollout import ObsStats
         stats = ObsStats(od, dev, eps=1e-8)
         head = [q for net in (pi, vf) for m in net if isinstance(m, nn.Linear) for q in (m.weight, m.bias)] + [log_std]
         n_head = sum(q.numel() for q in head)
-        flat = torch.zeros(n_head + 2 * od, device=dev)      # DevicePolicy.flat_params()'s order; allocated once
-        mean, inv_std = flat[n_head:n_head + od], flat[n_head + od:]      # the statistics tail: update_obs_stats writes it
+        flat = torch.zeros(n_head + 2 * od + (2 * oc if PC else 0), device=dev)      # DevicePolicy.flat_params()'s order; allocated once
+        mean, inv_std = flat[n_head:n_head + od], flat[n_head + od:n_head + 2 * od]      # the statistics tail: update_obs_stats writes it
         norm = lambda o: ((o - mean) * inv_std).clamp(-10.0, 10.0)       # the policy kernel's formula
+        cnorm = norm
+        if PC:      # the critic's statistics: a second ObsStats over the privileged rows, into the longer tail
+            stats_c = ObsStats(oc, dev, eps=1e-8)
+            cmean, cinv_std = flat[n_head + 2 * od:n_head + 2 * od + oc], flat[n_head + 2 * od + oc:]
+            cnorm = lambda o: ((o - cmean) * cinv_std).clamp(-10.0, 10.0)
         adv_buf, ret_buf = torch.zeros(T, N, 1, device=dev), torch.zeros(T, N, 1, device=dev)
 
     if args.device_grad:
@@ -298,7 +324,7 @@ def main(argv=None):
         ratio = (lp - lp_old).exp()
         surr = torch.min(ratio * adv_mb, ratio.clamp(1 - args.clip, 1 + args.clip) * adv_mb).mean()
         v_loss = 0.5 * (v - ret_mb).pow(2).mean()
-        auto = torch.autograd.grad(-surr + 0.5 * v_loss + aux_loss(mb)[0], head[:-1] if args.fixed_std else head)
+        auto = torch.autograd.grad(-surr + 0.5 * v_loss + aux_loss(mb)[0], head[:-1] if args.fixed_std else head)      # (vf on the critic's rows: evaluate)
         worst, pos = 0.0, 0
         for g in auto:
             worst = max(worst, ((g_buf[pos:pos + g.numel()] - g.reshape(-1)).abs().max() / g.abs().max().clamp_min(1e-30)).item())
@@ -306,6 +332,8 @@ def main(argv=None):
         print(json.dumps({"verify_grad": worst, "iter": it + 1}), flush=True)
 
     S["obs"][0].copy_(envs.reset())
+    if PC:
+        S["critic_obs"][0].copy_(envs.privileged)
     if args.distill_from is not None:
         envs.teacher_targets(S["t_mean"][0], S["t_value"][0])
     envs.episode_totals.zero_()
@@ -319,11 +347,15 @@ def main(argv=None):
             with torch.no_grad():
                 # the statistics see every observation collected so far: the reset row first, then rows 1 .. T of the previous rollout
                 envs.update_obs_stats(stats, S["obs"][1:] if it else S["obs"][:1], mean_out=mean, inv_std_out=inv_std)
+                if PC:
+                    envs.update_obs_stats(stats_c, S["critic_obs"][1:] if it else S["critic_obs"][:1], mean_out=cmean, inv_std_out=cinv_std)
                 if not args.device_grad:
                     torch.cat([q.reshape(-1) for q in head], out=flat[:n_head])
                 envs.update_policy(flat)
                 for t in range(T):
-                    envs.act_step(S["obs"][t], into=row_act(t))
+                    envs.act_step(S["obs"][t], into=row_act(t))      # (--privileged-critic: the value is the critic's on envs.privileged)
+                    if PC:      # the critic's row of the state just reached, beside the actor's
+                        S["critic_obs"][t + 1].copy_(envs.privileged)
                     if args.distill_from is not None:      # the teacher labels the state the student has just reached
                         envs.teacher_targets(S["t_mean"][t + 1], S["t_value"][t + 1])
                 envs.venv.act(S["obs"][T], deterministic=True, out={"value": S["value"][T]})
@@ -351,12 +383,18 @@ def main(argv=None):
                 tot = count + bn
                 mean = mean + d * bn / tot
                 var = (var * count + bv * bn + d * d * count * bn / tot) / tot
+                if PC:      # the same merge over the critic's rows
+                    c0 = S["critic_obs"][0]
+                    dc = c0.mean(0) - cmean
+                    cmean, cvar = cmean + dc * bn / tot, (cvar * count + c0.var(0, unbiased=False) * bn + dc * dc * count * bn / tot) / tot
                 count = tot
                 if args.device_policy:
                     envs.update_policy(flat_params())
                 for t in range(T):
                     if args.device_policy:
                         envs.act_step(S["obs"][t], into=row_act(t))
+                        if PC:
+                            S["critic_obs"][t + 1].copy_(envs.privileged)
                         continue
                     if args.symmetric:
                         mu, ls, v = sym(S["obs"][t], mean, inv_std_now(), 10.0)
@@ -368,9 +406,12 @@ def main(argv=None):
                     o = norm(S["obs"][t])
                     mu = pi(o)
                     a = mu + log_std.exp() * torch.randn_like(mu)
-                    S["act"][t].copy_(a); S["logp"][t].copy_(logprob(mu, a)); S["value"][t].copy_(vf(o))
+                    S["act"][t].copy_(a); S["logp"][t].copy_(logprob(mu, a)); S["value"][t].copy_(vf(cnorm(S["critic_obs"][t])) if PC else vf(o))
                     envs.step(S["act"][t], into=row(t))
-                S["value"][T].copy_(sym(S["obs"][T], mean, inv_std_now(), 10.0)[2].unsqueeze(-1) if args.symmetric else vf(norm(S["obs"][T])))
+                    if PC:
+                        S["critic_obs"][t + 1].copy_(envs.privileged)
+                S["value"][T].copy_(sym(S["obs"][T], mean, inv_std_now(), 10.0)[2].unsqueeze(-1) if args.symmetric
+                                    else vf(cnorm(S["critic_obs"][T])) if PC else vf(norm(S["obs"][T])))
                 # GAE; an episode cut by the TimeLimit (bad_masks = 0) is not bootstrapped through: its advantage stops there (a2c-ppo-acktr's use_proper_time_limits)
                 adv = torch.zeros(T, N, 1, device=dev)
                 gae = torch.zeros(N, 1, device=dev)
@@ -386,6 +427,7 @@ def main(argv=None):
         B = N * T
         o_all, a_all, lp_all = norm(S["obs"][:T]).reshape(B, od), S["act"].reshape(B, ad), S["logp"].reshape(B, 1)
         adv_all, ret_all, raw_all = adv.reshape(B, 1), ret.reshape(B, 1), S["obs"][:T].reshape(B, od)
+        c_all = cnorm(S["critic_obs"][:T]).reshape(B, oc) if PC else o_all      # what vf reads in the torch arms
         if args.distill_from is not None:
             # DAgger's regression as one call: epochs x minibatches of [shuffle, distill_grad, clip, Adam, repack] on the rows the student visited
             envs.distill_update(S["obs"][:T], S["t_mean"][:T], flat, adam, minibatch_rows=B // args.minibatches, epochs=args.epochs,
@@ -397,12 +439,12 @@ def main(argv=None):
                 mb = torch.randperm(B, device=dev)[:B // args.minibatches]
                 if args.mirror_dup:
                     mb = off_the_clip_bounds(mb)
-                envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf)
+                envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf, **ckw())
                 verify_grad(mb, it)
             # ppo.update() as one call: epochs x minibatches of [shuffle, ppo_grad, clip, Adam, repack]; u_stats keeps a row per minibatch
             envs.ppo_update(S["obs"][:T], S["act"], S["logp"], adv, ret, flat, adam, minibatch_rows=B // args.minibatches, epochs=args.epochs,
                             clip=args.clip, value_coef=0.5, n_params=n_head - ad if args.fixed_std else n_head, lr=args.lr, eps=1e-5,
-                            max_grad_norm=0.5, seed=args.seed, stats=u_stats)
+                            max_grad_norm=0.5, seed=args.seed, stats=u_stats, **ckw())
             if args.mirror_loss is not None:
                 lm_sum += u_stats[:, 7].sum(); lm_n += u_stats.shape[0]
             if args.mirror_dup:
@@ -417,7 +459,7 @@ def main(argv=None):
                         mb_v = off_the_clip_bounds(mb)
                         envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb_v, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf)
                         verify_grad(mb_v, it)
-                    envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf)
+                    envs.ppo_grad(S["obs"][:T], S["act"], S["logp"], adv, ret, idx=mb, clip=args.clip, value_coef=0.5, grad=g_buf, stats=s_buf, **ckw())
                     if args.verify_grad and ep == 0 and k == 0 and not args.mirror_dup:
                         verify_grad(mb, it)
                     with torch.no_grad():
@@ -450,6 +492,8 @@ def main(argv=None):
                 opt.step()
         with torch.no_grad():      # rollouts.after_update()
             S["obs"][0].copy_(S["obs"][T]); S["masks"][0].copy_(S["masks"][T]); S["bad_masks"][0].copy_(S["bad_masks"][T])
+            if PC:
+                S["critic_obs"][0].copy_(S["critic_obs"][T])
             if args.distill_from is not None:
                 S["t_mean"][0].copy_(S["t_mean"][T]); S["t_value"][0].copy_(S["t_value"][T])
         if it % 10 == 9 or it == 0:
@@ -480,10 +524,13 @@ def main(argv=None):
     import numpy as np
     if args.device_returns:
         mean, var = stats.mean.float(), stats.var.float()
+        if PC:
+            cmean, cvar = stats_c.mean.float(), stats_c.var.float()
+    extra_stats = dict(critic_obs_mean=cmean.cpu().numpy(), critic_obs_var=cvar.cpu().numpy()) if PC else {}
     np.savez(args.out + "_policy.npz", obs_mean=mean.cpu().numpy(), obs_var=var.cpu().numpy(), log_std=log_std.detach().cpu().numpy(),
              **{f"pi_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in pi.state_dict().items()},
              **{f"vf_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in vf.state_dict().items()},
-             env_id=np.array(args.env_id), env_steps=np.array(total_steps))
+             env_id=np.array(args.env_id), env_steps=np.array(total_steps), **extra_stats)
     envs.close()
 
 
