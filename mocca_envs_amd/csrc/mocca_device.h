@@ -331,6 +331,22 @@ constexpr bool OUTWARD_ROUNDS = false;
 #else
 constexpr bool OUTWARD_ROUNDS = T::OUTWARD_DPP && !COMPACT;
 #endif
+// Which step-kernel instances form the body velocities of the kinematics walk level by level over DPP (walk_phase2<T, true>): the ones that
+// run the outward pass that way -- the same lane layout, the same per-lane word.  The others and MOCCA_NO_TRIM_9 keep lane = body and the sum
+// along the path, and compile to the instructions they had.
+template <class T>
+#ifdef MOCCA_NO_TRIM_9
+constexpr bool WALK_LEVELS = false;
+#else
+constexpr bool WALK_LEVELS = OUTWARD_ROUNDS<T>;
+#endif
+// the lane that hosts the base body (0) in that layout: the last lane without a body (-1: none, and no WALK_LEVELS)
+template <class T>
+constexpr int walk_base_lane() {
+  for (int l = 63; l >= 0; --l)
+    if (T::out_body(l) < 0) return l;
+  return -1;
+}
 // Which step-kernel instances read the late view: all but the walker's physics instances at their register budget, which keep the arguments
 // of the entry.  With the late view the substep loop, scheduled around the freed scalar registers, spilled in the 48-row Stepper and Planner
 // instances (20 / 36 B of scratch where there was none) and spilled more in the compact ones (Custom 27 -> 34 registers, Stepper and Planner
@@ -527,6 +543,8 @@ DI float draw_u(const StepArgs& a, int env, int episode, int d) {  // env = glob
 //     Each group also leaves its joint's world axis a = R_body * axis (component i on lane i).
 //  2. lane = body: joint motion vector S = (a, r x a), then -- FULL only -- the spatial velocity as a plain sum of
 //     S_j qd_j along the path (no rotation chain any more), the velocity-product acceleration, link inertia, bias force.
+//     Where the ABA outward pass goes level by level (WALK_LEVELS) the FULL phase runs on that pass's lanes and takes the velocity
+//     from the parent's lane, v_b = v_parent + S_b qd_b, instead of summing along the path (walk_phase2).
 // One lane per body for everything cost ~90 VALU per path step; this costs ~20 + ~12.
 // the body's own constants of the walk's second phase
 struct WalkConsts { float cl[3], inl[6], ms, jarm, jdamp; };
@@ -591,10 +609,51 @@ DI void walk_phase1(float* L, int lane, unsigned long long ppk) {
     }
   }
 }
+// ---- the velocity chain of phase 2 where it goes level by level (WALK_LEVELS).  The operations are the ones the sum along the path compiles
+// to, spelled out so that the choice is in the source: a CHILD adds its ancestor's term as fma(qd_j, S_j, v), the body adds its OWN as
+// fma(S, qd, v) -- the same number, but with two NaN operands the order decides whose sign and payload come out.
+// cross3 as the sum along the path compiles it: each component one product and one FMA that subtracts it, the left vector's component first
+DI float fms_pinned(float p, float q, float r, float s) {   // p q - r s
+  float o;
+  asm("v_mul_f32_e32 %0, %3, %4\n\t"
+      "v_fma_f32 %0, %1, %2, -%0" : "=&v"(o) : "v"(p), "v"(q), "v"(r), "v"(s));
+  return o;
+}
+DI void cross3_pinned(const float* a, const float* b, float* o) {
+  o[0] = fms_pinned(a[1], b[2], a[2], b[1]); o[1] = fms_pinned(a[2], b[0], a[0], b[2]); o[2] = fms_pinned(a[0], b[1], a[1], b[0]);
+}
+// link = fma(qd, S, t): what the lane's right neighbour takes as its parent's velocity
+DI void walk_link(float* link, float qd, const float* S, const float* t) {
+  asm volatile("v_fma_f32 %0, %6, %7, %13\n\t"
+               "v_fma_f32 %1, %6, %8, %14\n\t"
+               "v_fma_f32 %2, %6, %9, %15\n\t"
+               "v_fma_f32 %3, %6, %10, %16\n\t"
+               "v_fma_f32 %4, %6, %11, %17\n\t"
+               "v_fma_f32 %5, %6, %12, %18"
+               : "=&v"(link[0]), "=&v"(link[1]), "=&v"(link[2]), "=&v"(link[3]), "=&v"(link[4]), "=&v"(link[5])
+               : "v"(qd), "v"(S[0]), "v"(S[1]), "v"(S[2]), "v"(S[3]), "v"(S[4]), "v"(S[5]), "v"(t[0]), "v"(t[1]), "v"(t[2]), "v"(t[3]), "v"(t[4]), "v"(t[5]));
+}
+// t = the left neighbour's link: six v_mov_b32_dpp row_shr:1 without bound_ctrl -- the first lane of a row has no source and is not written,
+// so a chain's head keeps the base's velocity.  (s_nop 1: the DPP read hazard, two wait states behind whatever wrote link last)
+DI void walk_shift(float* t, const float* link) {
+  asm volatile("s_nop 1\n\t"
+               "v_mov_b32_dpp %0, %6 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+               "v_mov_b32_dpp %1, %7 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+               "v_mov_b32_dpp %2, %8 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+               "v_mov_b32_dpp %3, %9 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+               "v_mov_b32_dpp %4, %10 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+               "v_mov_b32_dpp %5, %11 row_shr:1 row_mask:0xf bank_mask:0xf"
+               : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5])
+               : "v"(link[0]), "v"(link[1]), "v"(link[2]), "v"(link[3]), "v"(link[4]), "v"(link[5]));
+}
 // ---- phase 2: lane = body (see above); in the compact layout the link inertias it writes overlay the body frames, the geom points and
-// the candidate list: every lane holds its frame in registers before the first store (wave barrier inside `if (FULL)`)
+// the candidate list: every lane holds its frame in registers before the first store (wave barrier inside `if (FULL)`).
+// WALK_LEVELS (FULL only): the lanes are the outward pass's instead -- b = T::out_body(lane), the caller's, from the top bits of the per-lane
+// word; every root->leaf chain on consecutive lanes from the start of a DPP row, the walker's trunk (1, 2, 3) in two rows: both compute,
+// the primary lane stores; the base on the last lane without a body.  Everything but the velocity is indexed by b through LDS as before.
 template <class T, bool FULL>
 DI void walk_phase2(ModelP M, float* L, int lane, int b, unsigned long long ppk, const WalkConsts& wk) {
+  constexpr bool LEVELS = FULL && WALK_LEVELS<T>;
   const float cl[3] = {wk.cl[0], wk.cl[1], wk.cl[2]};
   const float inl[6] = {wk.inl[0], wk.inl[1], wk.inl[2], wk.inl[3], wk.inl[4], wk.inl[5]};
   const float ms = wk.ms, jarm = wk.jarm, jdamp = wk.jdamp;
@@ -604,7 +663,50 @@ DI void walk_phase2(ModelP M, float* L, int lane, int b, unsigned long long ppk,
     const float4 t = *reinterpret_cast<const float4*>(L + L_RT + 12 * b + 4 * i);
     R[3 * i] = t.x; R[3 * i + 1] = t.y; R[3 * i + 2] = t.z; r[i] = t.w;
   }
-  if (FULL) {
+  bool stores = lane < T::NB;   // the lane that stores body b's results
+  if constexpr (LEVELS) {
+    static_assert(walk_base_lane<T>() >= 0, "the base needs a lane without a body");
+    // v_b = v_parent(b) + S_b qd_b, and the parent's lane is the left neighbour: every lane starts from the base's velocity, forms its link
+    // from what it holds and takes its neighbour's, MAXD - 1 times.  After k shifts every body of depth <= k + 1 holds its parent's final
+    // velocity and from then on forms the same link from it; nothing of what a lane held before enters (the link is a function of t alone),
+    // so the argument asks nothing of the values, finite or not.  No LDS access and no mask inside: the lanes without a body (the base's
+    // among them) stay out and keep the base's velocity, and no lane with a body reads one of them.
+    const int ol = T::out_lane(ppk);
+    const bool primary = (unsigned)(ol - 1) < 31u;
+    stores = primary || lane == walk_base_lane<T>();
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { v[k] = L[L_BASE + 10 + k]; v[3 + k] = L[L_BASE + 7 + k]; }
+    if (b != 0) {
+      float a[3] = {L[L_SV + SVS * b], L[L_SV + SVS * b + 1], L[L_SV + SVS * b + 2]}, ra[3], link[6], vJ[6];
+      cross3(r, a, ra);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { S[i] = a[i]; S[3 + i] = ra[i]; }
+      if (primary) {   // (the ABA reads it)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) L[L_SV + SVS * b + 3 + i] = ra[i];
+      }
+      const float qd = L[L_QD + b];
+#pragma unroll
+      for (int k = 1; k < T::MAXD; ++k) {
+        walk_link(link, qd, S, v);
+        walk_shift(v, link);
+      }
+      // v: the parent's velocity.  The body's own joint, as in the sum along the path: vJ = S qd, c = crm(v, vJ), v += vJ as an FMA.  Spelled
+      // out as well: with v arriving from the rounds the optimiser commuted crm's products (vJ x v), which a NaN on both sides tells
+#pragma unroll
+      for (int i = 0; i < 6; ++i) asm("v_mul_f32_e32 %0, %1, %2" : "=v"(vJ[i]) : "v"(S[i]), "v"(qd));
+      {
+        float cb[3], cc[3];
+        cross3_pinned(v, vJ, c); cross3_pinned(v, vJ + 3, cb); cross3_pinned(v + 3, vJ, cc);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) asm("v_add_f32_e32 %0, %1, %2" : "=v"(c[3 + i]) : "v"(cc[i]), "v"(cb[i]));
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) asm("v_fma_f32 %0, %1, %2, %3" : "=v"(link[i]) : "v"(S[i]), "v"(qd), "v"(v[i]));
+#pragma unroll
+      for (int i = 0; i < 6; ++i) v[i] = link[i];
+    }
+  } else if (FULL) {
     if (lane >= 1 && lane < T::NB) {
       float a[3] = {L[L_SV + SVS * b], L[L_SV + SVS * b + 1], L[L_SV + SVS * b + 2]}, ra[3];
       cross3(r, a, ra);
@@ -633,7 +735,7 @@ DI void walk_phase2(ModelP M, float* L, int lane, int b, unsigned long long ppk,
       for (int i = 0; i < 6; ++i) v[i] += vJ[i];
     }
   }
-  if (lane < T::NB) {
+  if (stores) {
     float cw[3];
     matvec3(R, cl, cw);
 #pragma unroll
@@ -710,7 +812,8 @@ DI void walk_phase2(ModelP M, float* L, int lane, int b, unsigned long long ppk,
 template <class T, bool FULL>
 DI void walk_kinematics(ModelP M, float* L, int lane, unsigned long long ppk) {
   asm volatile("" : "+v"(lane));  // lane-derived indices are recomputed per walk: CSE across walks kept them live from kernel entry (spilled)
-  const int b = lane < T::NB ? lane : 0;
+  int b = lane < T::NB ? lane : 0;
+  if constexpr (FULL && WALK_LEVELS<T>) b = T::out_lane(ppk) & 31;   // phase 2's body in the outward pass's layout (0: the base's lane and the idle ones)
   WalkConsts wk;
   walk_consts<FULL>(M, b, wk);   // fetched before the walk so that their latency hides behind it
   walk_phase1<T, FULL>(L, lane, ppk);
