@@ -936,6 +936,74 @@ int mocca_ppo_update_priv(mocca_handle h, const float *obs_dev, int obs_stride, 
                           float *moments_dev, double *clock_dev, double lr, double beta1, double beta2, double eps, double max_grad_norm,
                           uint64_t seed, float *stats_dev, void *stream);
 
+/* ---- domain randomisation on the device: motor strength, action latency, pushes, sensor noise (no reference counterpart: the reference's
+ *      robot has the same dynamics in every env and every episode) ---- */
+
+/* These entry points are ADDITIVE: MOCCA_ABI_VERSION stays 8, and a handle that calls none of them launches and computes exactly what it
+ * did before.  Nothing here touches the step kernel: everything acts on its inputs and outputs -- the action buffer it reads, the state
+ * record it loads, the observation row it wrote.  Arithmetic, keying and kernel layout: mocca_envs_amd/csrc/mocca_randomise.h.
+ *
+ * Keying.  Every draw is Philox4x32-10 under the handle's seed key (MOCCA_PARAM_SEED / mocca_reset), with the counter (g, c1, E, c3):
+ * g = MOCCA_PARAM_ENV_OFFSET + env, the GLOBAL env id; E the env's episode counter (task word MOCCA_TW_EPISODE); c1 = 0 or the env's step
+ * counter T (task word MOCCA_TW_T); both counters READ FROM THE TASK RECORD WHEN THE KERNEL RUNS.  Nothing is kept on the host: every launch
+ * below can be captured in a hipGraph, a shard reproduces the rows it owns, and a restored task record (mocca_set_task) restores the draws.
+ * c3 = domain + 256 b with the domains 4 and 5 (0 .. 3 are the envs' own draws, policy noise, the field choice and the terrain generator:
+ * no other draw moves) and a block index b.  A uniform is u = (w >> 8) 2^-24, a signed uniform s = 2 u - 1.
+ *     episode parameters  (g, 0, E, 4):          strength = fmaf(u0, strength_hi - strength_lo, strength_lo)
+ *                                                 delay = delay_min + (w1 >> 8) % (delay_max - delay_min + 1)
+ *                                                 phase = (w2 >> 8) % push_interval
+ *     the push of step T  (g, T, E, 4 + 256):    dvx = push_max s0, dvy = push_max s1
+ *     noise of column k   (g, T, E, 5 + 256 (k / 4)), word k % 4:  out[k] = fmaf(scale[k], s, row[k])
+ *
+ * mocca_set_randomisation  attaches (cfg == NULL: detaches) the randomisation of the PLANT.  From then on every launch of the step kernel --
+ *                   mocca_step, mocca_plan_step, mocca_act_step, mocca_act_plan_step -- is preceded, on the same stream, by ONE small launch
+ *                   that reads the action buffer the step kernel would have read (the caller's, the policy's output or the base
+ *                   controller's) and writes a handle-owned effective-action buffer [N][act_dim], which the step kernel reads instead.
+ *                   Nothing is launched without an attachment.  Per env:
+ *                     motor strength   v = strength * clip(a, -1, 1), the clip as the step kernel spells it (a NaN passes through).  The
+ *                                      step computes gain * applied_gain * clip(.), so v scales the torque; the step's energy penalty, which
+ *                                      reads the same buffer, sees v as well.  MOCCA_TASK_CASSIE takes the range [1, 1] ALONE: its action
+ *                                      is a PD target, not a torque (the clip to [-1, 1] applies there too).
+ *                     latency          a handle-owned ring [N][delay_max + 1][act_dim]: slot T % (delay_max + 1) receives v, and the
+ *                                      effective action is the v stored at step T - delay when T >= delay, else 0.  Indexed by T: a reset --
+ *                                      mocca_reset or the auto-reset inside the step kernel -- needs no clearing pass.  THE RING IS NOT
+ *                                      PART OF THE mocca_get_state / mocca_get_task SNAPSHOT: a restored snapshot with delay > 0 reads, for
+ *                                      its first `delay` steps, whatever the ring held; mocca_task_step advances T without writing it.
+ *                     pushes           push_interval > 0, T > 0 and (T + phase) % push_interval == 0: dvx and dvy are added to words 7 and
+ *                                      8 of the env's state record, the base's linear velocity in the world frame.  The Walker2D and Crab2D
+ *                                      topologies and blobs with planar != 0 take dvx alone (the draw is taken, word 8 is not written).
+ *                                      The planner's base controller reads the robot state the previous step left: IT SEES A PUSH ONE
+ *                                      STEP LATE.
+ *                   May allocate and synchronise; no step ever does.  mocca_task_step has no physics and is not perturbed.  One handle:
+ *                   the multi-handle wrappers of the Python layer do not offer it.
+ * mocca_get_effective_action  out_dev [N][act_dim] <- what the last step's kernel read; one copy on `stream`.
+ * mocca_set_sensor_noise   scale_host [dim] f32, dim = obs_dim, copied into the handle (NULL detaches); may synchronise.
+ * mocca_sensor_noise       out_dev[e][k] = fmaf(scale[k], s, rows_dev[e][k]) for k < dim, rows in_stride / out_stride floats apart; in place is
+ *                   allowed (out_dev == rows_dev with equal strides), columns at or beyond dim are not written.  T and E are the env's
+ *                   counters NOW -- after the step that wrote the row --, so two calls without a step in between give the same rows.
+ * mocca_randomisation_record  out_dev[e][0 .. 3] <- strength, delay, steps until the env's next push (0: the next step is pushed; -1: no
+ *                   pushes), 0 -- a pure function of the task record's E and T, so the row describes the episode the env is in now, also
+ *                   right after an auto-reset.  Rows row_stride floats apart (the tail of a privileged critic's row).
+ * The three launches allocate nothing, read nothing on the host, use no atomics and do not synchronise.
+ * Errors (MOCCA_E_ARG, with a message, before any launch; the handle and every output are left as they were): mocca_set_randomisation: a
+ * strength range outside (0, 1] or reversed; one other than [1, 1] on MOCCA_TASK_CASSIE; negative or reversed delays, delay_max >
+ * MOCCA_RAND_MAX_DELAY; a negative or non-finite push_max; push_interval outside 0 .. 65536.  mocca_set_sensor_noise: dim != obs_dim, a
+ * negative or non-finite scale.  mocca_sensor_noise before mocca_set_sensor_noise, mocca_randomisation_record / mocca_get_effective_action
+ * before mocca_set_randomisation; a NULL pointer; in_stride or out_stride < obs_dim, row_stride < MOCCA_RAND_WORDS. */
+#define MOCCA_RAND_WORDS 4
+#define MOCCA_RAND_MAX_DELAY 7
+typedef struct mocca_randomisation {
+  float strength_lo, strength_hi; /* per-episode motor strength, 0 < lo <= hi <= 1 */
+  int32_t delay_min, delay_max;   /* per-episode action latency in steps, 0 <= min <= max <= MOCCA_RAND_MAX_DELAY */
+  int32_t push_interval;          /* steps between pushes, 0 (none) .. 65536; each episode draws its phase */
+  float push_max;                 /* largest |dvx|, |dvy| of a push, m/s */
+} mocca_randomisation;
+int mocca_set_randomisation(mocca_handle h, const mocca_randomisation *cfg);
+int mocca_get_effective_action(mocca_handle h, float *out_dev, void *stream);
+int mocca_set_sensor_noise(mocca_handle h, const float *scale_host, int dim);
+int mocca_sensor_noise(mocca_handle h, const float *rows_dev, int in_stride, float *out_dev, int out_stride, void *stream);
+int mocca_randomisation_record(mocca_handle h, float *out_dev, int row_stride, void *stream);
+
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */
 int mocca_kernel_info(mocca_handle h, int *vgprs, int *sgprs, int *lds_bytes, int *scratch_bytes, int *max_blocks_per_cu);

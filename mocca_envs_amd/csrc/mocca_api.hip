@@ -22,6 +22,7 @@
 #include "mocca_scan.h"
 #include "mocca_depth.h"
 #include "mocca_terrain.h"
+#include "mocca_randomise.h"
 
 using namespace mocca;
 
@@ -199,6 +200,12 @@ struct mocca_ctx {
   size_t ppo_cap = 0;
   DevBuf<double> d_optim;            // scratch of mocca_adam_step / mocca_ppo_update (mocca_optim.h): the record, the gradient, the permutation
   size_t optim_cap = 0;
+  // domain randomisation (mocca_randomise.h), all owned by the handle
+  bool rand_on = false;              // mocca_set_randomisation: launch_step runs the perturb kernel and the step kernel reads d_rand_eff
+  mocca_rand::RandConfig rand_cfg{};
+  DevBuf<float> d_rand_eff;          // [N][act_dim] the effective action of the last step
+  DevBuf<float> d_rand_ring;         // [N][delay_max + 1][act_dim] the stored actions of the last delay_max + 1 steps; NOT part of a snapshot
+  DevBuf<float> d_noise_scale;       // [obs_dim] mocca_set_sensor_noise
   std::string err;
 };
 static_assert(ROBOT_STATE_STRIDE == mocca_ctrl::CTRL_RS_STRIDE, "the step kernels and the controller kernel share the robot_state buffer");
@@ -628,6 +635,12 @@ int mocca_reset(mocca_handle h, const uint8_t* mask_dev, uint64_t seed, float* o
   return MOCCA_OK;
 }
 
+// what the randomisation kernels key their draws by (mocca_randomise.h)
+static mocca_rand::RandKeys rand_keys(mocca_handle h) {
+  return mocca_rand::RandKeys{h->d_task, MOCCA_TASK_WORDS, MOCCA_TW_T, MOCCA_TW_EPISODE, h->env_offset, h->n_envs, (uint32_t)h->seed,
+                              (uint32_t)(h->seed >> 32)};
+}
+
 // the step-kernel launch of mocca_step / mocca_plan_step (base_value: the controller's value estimates, or null); the handle's device is current
 static int launch_step(mocca_handle h, const float* act_dev, const float* base_value, float* obs_dev, float* rew_dev, uint8_t* done_dev,
                        int32_t* info_dev, hipStream_t s) {
@@ -635,6 +648,12 @@ static int launch_step(mocca_handle h, const float* act_dev, const float* base_v
   a.act = act_dev; a.obs = obs_dev; a.rew = rew_dev; a.done = done_dev; a.info = info_dev;
   a.base_value = base_value;
   if (int rc = flush_pending(h, s)) return rc;
+  if (h->rand_on) {   // strength, latency and pushes act on what the step kernel reads: one small launch in front of it, nothing without an attachment
+    mocca_rand::PerturbArgs p{rand_keys(h), h->rand_cfg, act_dev, h->d_rand_eff, h->d_rand_ring, h->d_dyn, DYN_STRIDE, mocca_act_dim(h)};
+    mocca_rand::launch_perturb(s, p);
+    HIP_TRY(h, hipGetLastError());
+    a.act = h->d_rand_eff;
+  }
   // mocca_step never allocates and never synchronises, and the pace calibrates itself on the device: the launch can be captured in a
   // hipGraph.  Two optional features keep HOST state per launch that a capture bakes into the kernel arguments: the episode-record ring
   // (slot and serial below: a replayed launch keeps writing one slot under one serial -- read ep_masks / ep_totals instead) and the
@@ -682,6 +701,100 @@ int mocca_plan_step(mocca_handle h, const float* plan_dev, float* obs_dev, float
   mocca_ctrl::launch_controller(s, c);
   HIP_TRY(h, hipGetLastError());
   return launch_step(h, h->d_base_act, h->d_base_val, obs_dev, rew_dev, done_dev, info_dev, s);
+}
+
+// ---- domain randomisation (mocca_randomise.h) ----
+int mocca_set_randomisation(mocca_handle h, const mocca_randomisation* cfg) {
+  if (!h) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  if (!cfg) {   // detach: the next step reads the caller's actions again
+    if (int rc = commit_ready(h, "mocca_set_randomisation")) return rc;
+    h->rand_on = false; h->d_rand_eff.reset(); h->d_rand_ring.reset();
+    return MOCCA_OK;
+  }
+  auto refuse = [&](const std::string& what) { h->err = "mocca_set_randomisation: " + what; return MOCCA_E_ARG; };
+  const float lo = (float)cfg->strength_lo, hi = (float)cfg->strength_hi, pm = (float)cfg->push_max;
+  if (!(lo > 0.0f) || !(hi <= 1.0f) || !(lo <= hi)) return refuse("the strength range must satisfy 0 < strength_lo <= strength_hi <= 1");
+  if (h->task_id == MOCCA_TASK_CASSIE && (lo != 1.0f || hi != 1.0f))
+    return refuse("MOCCA_TASK_CASSIE takes the strength range [1, 1] alone: its action is a PD target, not a torque");
+  if (cfg->delay_min < 0 || cfg->delay_max < cfg->delay_min || cfg->delay_max > MOCCA_RAND_MAX_DELAY)
+    return refuse("the delays must satisfy 0 <= delay_min <= delay_max <= " + std::to_string(MOCCA_RAND_MAX_DELAY));
+  if (!std::isfinite(pm) || pm < 0.0f) return refuse("push_max must be finite and not negative");
+  if (cfg->push_interval < 0 || cfg->push_interval > mocca_rand::RAND_MAX_INTERVAL)
+    return refuse("push_interval must be 0 (no pushes) .. " + std::to_string(mocca_rand::RAND_MAX_INTERVAL));
+  const int ad = mocca_act_dim(h);
+  const size_t n_eff = (size_t)h->n_envs * ad, n_ring = n_eff * (cfg->delay_max + 1);
+  if (n_eff >= ((size_t)1 << 31) || (long long)h->env_offset + h->n_envs > (1ll << 32) || h->env_offset < 0)
+    return refuse("n_envs x act_dim must stay below 2^31 and the global env ids below 2^32");
+  DevBuf<float> eff, ring;
+  hipError_t e = eff.alloc(n_eff, true);
+  if (e == hipSuccess) e = ring.alloc(n_ring, true);
+  if (int rc = commit_ready(h, "mocca_set_randomisation", e)) return rc;
+  h->d_rand_eff.swap(eff); h->d_rand_ring.swap(ring);
+  const int planar = h->topo == TOPO_WALKER2D || h->topo == TOPO_CRAB2D || h->model.planar != 0;
+  h->rand_cfg = mocca_rand::RandConfig{lo, hi, cfg->delay_min, cfg->delay_max, cfg->push_interval, pm, planar};
+  h->rand_on = true;
+  return MOCCA_OK;
+}
+
+int mocca_get_effective_action(mocca_handle h, float* out_dev, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (!h->rand_on) { h->err = "mocca_get_effective_action needs a randomisation (mocca_set_randomisation)"; return MOCCA_E_ARG; }
+  if (!out_dev) { h->err = "mocca_get_effective_action: out_dev is NULL"; return MOCCA_E_ARG; }
+  DeviceGuard guard(h->device);
+  HIP_TRY(h, hipMemcpyAsync(out_dev, h->d_rand_eff, (size_t)h->n_envs * mocca_act_dim(h) * sizeof(float), hipMemcpyDeviceToDevice,
+                            (hipStream_t)stream));
+  return MOCCA_OK;
+}
+
+int mocca_set_sensor_noise(mocca_handle h, const float* scale_host, int dim) {
+  if (!h) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  if (!scale_host) {
+    if (int rc = commit_ready(h, "mocca_set_sensor_noise")) return rc;
+    h->d_noise_scale.reset();
+    return MOCCA_OK;
+  }
+  if (dim != h->obs_dim) { h->err = "mocca_set_sensor_noise: dim must be obs_dim (" + std::to_string(h->obs_dim) + ")"; return MOCCA_E_ARG; }
+  for (int k = 0; k < dim; ++k)
+    if (!std::isfinite(scale_host[k]) || scale_host[k] < 0.0f) {
+      h->err = "mocca_set_sensor_noise: scale " + std::to_string(k) + " must be finite and not negative"; return MOCCA_E_ARG;
+    }
+  if ((size_t)h->n_envs * dim >= ((size_t)1 << 31)) { h->err = "mocca_set_sensor_noise: n_envs x dim must stay below 2^31"; return MOCCA_E_ARG; }
+  DevBuf<float> sc;
+  hipError_t e = sc.alloc(dim, false);
+  if (e == hipSuccess) e = hipMemcpy(sc, scale_host, (size_t)dim * sizeof(float), hipMemcpyHostToDevice);
+  if (int rc = commit_ready(h, "mocca_set_sensor_noise", e)) return rc;
+  h->d_noise_scale.swap(sc);
+  return MOCCA_OK;
+}
+
+int mocca_sensor_noise(mocca_handle h, const float* rows_dev, int in_stride, float* out_dev, int out_stride, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (!h->d_noise_scale) { h->err = "mocca_sensor_noise needs the scales (mocca_set_sensor_noise)"; return MOCCA_E_ARG; }
+  if (!rows_dev || !out_dev) { h->err = "mocca_sensor_noise: rows_dev or out_dev is NULL"; return MOCCA_E_ARG; }
+  if (in_stride < h->obs_dim || out_stride < h->obs_dim) {
+    h->err = "mocca_sensor_noise: in_stride and out_stride must be at least obs_dim (" + std::to_string(h->obs_dim) + ")"; return MOCCA_E_ARG;
+  }
+  DeviceGuard guard(h->device);
+  mocca_rand::NoiseArgs a{rand_keys(h), h->d_noise_scale, rows_dev, out_dev, in_stride, out_stride, h->obs_dim};
+  mocca_rand::launch_noise((hipStream_t)stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
+}
+
+int mocca_randomisation_record(mocca_handle h, float* out_dev, int row_stride, void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  if (!h->rand_on) { h->err = "mocca_randomisation_record needs a randomisation (mocca_set_randomisation)"; return MOCCA_E_ARG; }
+  if (!out_dev) { h->err = "mocca_randomisation_record: out_dev is NULL"; return MOCCA_E_ARG; }
+  if (row_stride < MOCCA_RAND_WORDS) {
+    h->err = "mocca_randomisation_record: row_stride must be at least MOCCA_RAND_WORDS (" + std::to_string(MOCCA_RAND_WORDS) + ")"; return MOCCA_E_ARG;
+  }
+  DeviceGuard guard(h->device);
+  mocca_rand::RecordArgs a{rand_keys(h), h->rand_cfg, out_dev, row_stride};
+  mocca_rand::launch_record((hipStream_t)stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
 }
 
 int mocca_get_base_outputs(mocca_handle h, float* action_dev, float* value_dev, void* stream) {

@@ -25,6 +25,7 @@ RENDER_MAX_SIZE = 4096   # MOCCA_RENDER_MAX_SIZE
 SCAN_MAX_POINTS = 256   # MOCCA_SCAN_MAX_POINTS
 DEPTH_MAX_PIXELS, DEPTH_STABILISED, DEPTH_SEE_ROBOT = 256, 1, 2   # MOCCA_DEPTH_*
 HF_MAX_FIELDS, HF_MAX_PEAKS = 1024, 256   # MOCCA_HF_MAX_FIELDS, MOCCA_HF_MAX_PEAKS
+RAND_WORDS, RAND_MAX_DELAY, RAND_MAX_INTERVAL = 4, 7, 65536   # MOCCA_RAND_WORDS, MOCCA_RAND_MAX_DELAY, the bound of push_interval
 RENDER_ID_NONE, RENDER_ID_GROUND, RENDER_ID_PLANK0, RENDER_ID_HEIGHTFIELD, RENDER_ID_TARGET, RENDER_ID_LINK0 = -1, 32, 33, 37, 38, 64   # MOCCA_RENDER_ID_*
 
 # every symbol include/mocca.h declares: (name, restype, argtypes)
@@ -104,10 +105,23 @@ SYMBOLS = {
     "mocca_ppo_grad_priv": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _d, _d, _d, _i, _vp, _vp, _vp]),
     "mocca_ppo_update_priv": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _i, _d, _d, _d, _i, _vp, _sz, C.c_int64,
                                    _vp, _vp, _d, _d, _d, _d, _d, _u64, _vp, _vp]),
+    "mocca_set_randomisation": (_i, [_vp, _vp]),
+    "mocca_get_effective_action": (_i, [_vp, _vp, _vp]),
+    "mocca_set_sensor_noise": (_i, [_vp, _vp, _i]),
+    "mocca_sensor_noise": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    "mocca_randomisation_record": (_i, [_vp, _vp, _i, _vp]),
     "mocca_is_diagnostic_build": (_i, []),
     "mocca_kernel_info": (_i, [_vp] + [C.POINTER(_i)] * 5),
     "mocca_last_error": (C.c_char_p, [_vp]),
 }
+
+
+
+class RandomisationConfig(C.Structure):
+    """`mocca_randomisation` of include/mocca.h"""
+    _fields_ = [("strength_lo", C.c_float), ("strength_hi", C.c_float), ("delay_min", C.c_int32), ("delay_max", C.c_int32),
+                ("push_interval", C.c_int32), ("push_max", C.c_float)]
+
 
 _lib = None
 

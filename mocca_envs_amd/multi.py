@@ -185,6 +185,22 @@ class _Parts:
     def height_fields(self, *a, **k):
         self._one_handle("height_fields")
 
+    # ---- ... and so do the randomisation's effective actions, its ring and its scales ----
+    def set_randomisation(self, *a, **k):
+        self._one_handle("set_randomisation")
+
+    def effective_action(self):
+        self._one_handle("effective_action")
+
+    def set_sensor_noise(self, *a, **k):
+        self._one_handle("set_sensor_noise")
+
+    def sensor_noise(self, *a, **k):
+        self._one_handle("sensor_noise")
+
+    def randomisation_record(self, *a, **k):
+        self._one_handle("randomisation_record")
+
     def set_state(self, st) -> None:
         st = torch.as_tensor(st, dtype=torch.float32).reshape(self.n_envs, self.state_dim)
         for e, sl in zip(self.parts, self.slices):

@@ -205,12 +205,24 @@ class TorchVecEnv:
     scan is attached to the handle but NOT appended to the observation row -- rows stay [obs] or [obs | depth] -- and `envs.privileged`
     [N, obs_dim + P] holds [obs | scan], the row a teacher trained with `height_scan=` saw, refreshed by one more height-scan launch after
     every reset and step, on the step's stream.  `attach_teacher(policy)` / `teacher_targets(mean_out, value_out)` evaluate a frozen
-    teacher on it."""
+    teacher on it.
+    `randomisation=randomisation.Randomisation(...)` (one handle): domain randomisation on the device (include/mocca.h
+    mocca_set_randomisation) -- per-episode motor strength and action latency and random pushes act in front of every step (one more small
+    launch), `envs.effective_action()` tells what the step read; `envs.randomisation` [N, 4] is the record of every env's plant (strength,
+    delay, steps until the next push, 0), refreshed after every reset and step.  With `obs_noise` the POLICY's row -- this object's buffer or
+    the `into=` row of the trainer's storage -- gets uniform noise added in place to its first obs_dim columns, one launch BEHIND the sensor
+    launches, which stay in their order: `envs.privileged` is refreshed first, from the clean observation.  With `privileged=True` (needs
+    `privileged_scan=`) the privileged row is [obs | scan | record] and `envs.randomisation` is its tail: a privileged critic or a teacher
+    knows the plant, the actor does not."""
 
     def __init__(self, env_id: str, num_envs: int, seed: int = 0, device: Optional[int] = None, sub_batches: int = 1,
                  terminal_observation: bool = False, record_slots: int = 8, eager_done: bool = False, record_events: bool = True,
                  height_scan: Optional[dict] = None, terrain_bank: Optional[dict] = None, depth_camera=None,
-                 privileged_scan: Optional[dict] = None, **kw):
+                 privileged_scan: Optional[dict] = None, randomisation=None, **kw):
+        if randomisation is not None and randomisation.privileged and privileged_scan is None:
+            raise ValueError("Randomisation(privileged=True) puts the plant's record behind [obs | scan]: that takes privileged_scan=")
+        if randomisation is not None and sub_batches > 1:
+            raise NotImplementedError("randomisation needs one handle (sub_batches=1)")
         if height_scan is not None and privileged_scan is not None:
             raise ValueError("height_scan= puts the scan into the observation row, privileged_scan= keeps it out of it: one of the two")
         sensors = [name for name, arg in (("privileged_scan", privileged_scan), ("depth_camera", depth_camera), ("height_scan", height_scan))
@@ -226,7 +238,7 @@ class TorchVecEnv:
                                  **({"device": device} if device is not None else {}), **kw)
         self.env_id, self.num_envs = env_id, int(num_envs)
         self.device = self.venv.device
-        for name in sensors + (["terrain_bank"] if terrain_bank is not None else []):    # (several devices are no single handle either)
+        for name in sensors + (["terrain_bank"] if terrain_bank is not None else []) + (["randomisation"] if randomisation is not None else []):    # (several devices are no single handle either)
             self._one(name)
         self._terrain = None
         if terrain_bank is not None:
@@ -247,6 +259,15 @@ class TorchVecEnv:
         if privileged_scan is not None:
             self.venv.set_height_scan(**privileged_scan)
             self.privileged = torch.zeros(self.num_envs, self.venv.obs_dim + self.venv.scan_dim, dtype=torch.float32, device=self.device)
+        self.randomisation, self._noisy = None, False
+        if randomisation is not None:
+            self.venv.set_randomisation(randomisation)
+            self._noisy = randomisation.obs_noise is not None
+            if randomisation.privileged:     # [obs | scan | record]: the record call writes the tail
+                self.privileged = torch.zeros(self.num_envs, self.privileged.shape[1] + _lib.RAND_WORDS, dtype=torch.float32, device=self.device)
+                self.randomisation = self.privileged[:, -_lib.RAND_WORDS:]
+            else:
+                self.randomisation = torch.zeros(self.num_envs, _lib.RAND_WORDS, dtype=torch.float32, device=self.device)
         self._depth = 0
         if depth_camera is not None:
             self.venv.set_depth_camera(depth_camera)
@@ -334,12 +355,23 @@ class TorchVecEnv:
     def reset(self) -> torch.Tensor:
         obs = self.venv.reset()        # (the reset kernel zeroes the envs' running returns: Monitor.reset)
         self._refresh_privileged(obs)
-        return obs if self._wide is None else self._widen(obs, self._wide)
+        return self._noise(obs if self._wide is None else self._widen(obs, self._wide))
 
     def _refresh_privileged(self, obs):
-        """privileged_scan=: the row [obs | scan] of the state the envs are in now into `self.privileged`, one launch on the step's stream"""
+        """privileged_scan=: the row [obs | scan] of the state the envs are in now into `self.privileged`, one launch on the step's stream;
+        randomisation=: the plant's record into `self.randomisation` (the tail of the privileged row with privileged=True), one more"""
         if self.privileged is not None:
             self.venv.height_scan(out=self.privileged, obs=obs)
+        if self.randomisation is not None:
+            self.venv.randomisation_record(out=self.randomisation)
+
+    def effective_action(self) -> torch.Tensor:
+        """randomisation=: what the last step's kernel read in place of the action, [N, act_dim]: `VecEnv.effective_action`.  One handle only."""
+        return self._one("effective_action").effective_action()
+
+    def _noise(self, row):
+        """randomisation= with obs_noise: the sensor noise onto the head of the policy's row, in place, behind every sensor launch"""
+        return self.venv.sensor_noise(row) if self._noisy else row
 
     def _widen(self, obs, wide):
         """the wide row [obs | scan | depth] into `wide`: one launch per sensor, the first of them copies the observation"""
@@ -362,13 +394,13 @@ class TorchVecEnv:
             else:
                 o, r = launch(actions, obs_out=obs_out, rew_out=rew_out)[:2]
             self._refresh_privileged(o)
-            return o, r
+            return self._noise(o), r
         wide = self._wide if obs_out is None else obs_out
         if wide.shape != self._wide.shape or not wide.is_contiguous():
             raise ValueError("with a height scan or a depth camera the observation rows are contiguous float32 [n_envs, obs_dim + scan_dim + depth_dim]")
         o, r = launch(actions, rew_out=rew_out)[:2]
         self._refresh_privileged(o)
-        return self._widen(o, wide), r
+        return self._noise(self._widen(o, wide)), r
 
     def step(self, actions: torch.Tensor, into: Optional[dict] = None):
         """`into` (one handle only): {"obs": [N, obs_dim], "reward": [N, 1], "masks": [N, 1], "bad_masks": [N, 1]} -- any subset -- tensors of the
@@ -421,7 +453,8 @@ class TorchVecEnv:
         asym = getattr(policy, "asymmetric", False)
         if asym and (self.privileged is None or policy.critic_in_dim != self.privileged.shape[1]):
             raise ValueError(f"the policy's critic reads {policy.critic_in_dim} inputs of its own: " + (
-                "that takes privileged_scan= ([obs | scan])" if self.privileged is None else f"envs.privileged has {self.privileged.shape[1]} ([obs | scan])"))
+                "that takes privileged_scan= ([obs | scan])" if self.privileged is None
+                else f"envs.privileged has {self.privileged.shape[1]} ([obs | scan], with Randomisation(privileged=True) [obs | scan | record])"))
         self.venv.set_policy(policy)
         if asym:
             self.venv.set_critic_rows(self.privileged)
@@ -441,7 +474,7 @@ class TorchVecEnv:
         rows = self._teacher_rows()
         if policy is not None and policy.in_dim != rows.shape[1]:
             raise ValueError(f"the teacher reads {policy.in_dim} inputs, its rows here have {rows.shape[1]}"
-                             + (" ([obs | scan])" if self.privileged is not None else " (the observation row; privileged_scan= gives [obs | scan])"))
+                             + (" ([obs | scan], with Randomisation(privileged=True) [obs | scan | record])" if self.privileged is not None else " (the observation row; privileged_scan= gives [obs | scan])"))
         self.venv.set_teacher(policy)
 
     def _teacher_rows(self):

@@ -110,6 +110,8 @@ class VecEnv:
     not finish in this step keep their old content.
     """
 
+    randomisation = None    # set_randomisation(): the attached randomisation.Randomisation
+
     def __init__(self, env_id: str = "Walker3DCustomEnv-v0", n_envs: int = 1, device: Optional[int] = None,
                  auto_reset: bool = True, seed: int = 0, model_blob: Optional[bytes] = None, env_offset: int = 0,
                  terminal_obs: bool = False, max_rows: Optional[int] = None, max_contacts: Optional[int] = None, base_controller=None,
@@ -1224,6 +1226,62 @@ class VecEnv:
                                         or not cameras_out.is_contiguous() or cameras_out.device != self.device):
             raise ValueError(f"cameras_out must be a contiguous float32 [n_envs, {_lib.CAMERA_FLOATS}] tensor on the env's device")
         return self._sensor_rows(self.lib.mocca_depth_camera, p, out, obs, cameras_out)
+
+    # ---- domain randomisation (include/mocca.h mocca_set_randomisation .. mocca_randomisation_record; randomisation.Randomisation) ----
+    def set_randomisation(self, rand) -> None:
+        """Attach a `randomisation.Randomisation` (None detaches both parts): its strength, latency and pushes act in front of every step
+        from the next one on (step, plan_step, act_step, act_plan_step: one more small launch each), its `obs_noise` becomes the scales of
+        sensor_noise().  May allocate and synchronise; no step does."""
+        if rand is None:
+            _lib.check(self.lib.mocca_set_randomisation(self.h, None), self.h)
+            _lib.check(self.lib.mocca_set_sensor_noise(self.h, None, 0), self.h)
+            self.randomisation = None
+            return
+        scales = rand.noise_scales(self.obs_dim)      # (refused before the handle changes)
+        cfg = rand.config()
+        _lib.check(self.lib.mocca_set_randomisation(self.h, C.byref(cfg)), self.h)
+        self.set_sensor_noise(scales)
+        self.randomisation = rand
+
+    def effective_action(self) -> torch.Tensor:
+        """what the last step's kernel read in place of the action: float32 [N, act_dim] (the clipped action times the episode's strength,
+        `delay` steps late)"""
+        out = torch.empty(self.n_envs, self.act_dim, dtype=torch.float32, device=self.device)
+        self._call(self.lib.mocca_get_effective_action, out)
+        return out
+
+    def set_sensor_noise(self, scales) -> None:
+        """the scales of sensor_noise(): one per observation column, float32 [obs_dim] >= 0, copied into the handle; None detaches"""
+        if scales is None:
+            _lib.check(self.lib.mocca_set_sensor_noise(self.h, None, 0), self.h)
+            return
+        s = np.ascontiguousarray(scales.detach().cpu().numpy() if isinstance(scales, torch.Tensor) else scales, np.float32).reshape(-1)
+        _lib.check(self.lib.mocca_set_sensor_noise(self.h, s.ctypes.data_as(C.c_void_p), int(s.size)), self.h)
+
+    def sensor_noise(self, rows: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`rows` [N, >= obs_dim] with uniform noise of the attached scales added to the first obs_dim columns, one launch, nothing
+        synchronises: into `out` (float32 [N, >= obs_dim] with contiguous rows; columns beyond obs_dim are left untouched), or IN PLACE
+        without one.  The noise is keyed by the envs' step and episode counters: two calls without a step in between add the same noise."""
+        out = rows if out is None else out
+        for name, t in (("rows", rows), ("out", out)):
+            if t.dim() != 2 or t.shape[0] != self.n_envs or t.shape[1] < self.obs_dim or t.dtype != torch.float32 or t.device != self.device \
+                    or t.stride(1) != 1 or (self.n_envs > 1 and t.stride(0) < self.obs_dim):
+                raise ValueError(f"{name} must be a float32 [n_envs, >= {self.obs_dim}] tensor on the env's device with contiguous rows")
+        stride = lambda t: int(t.stride(0) if self.n_envs > 1 else max(t.stride(0), self.obs_dim))
+        self._call(self.lib.mocca_sensor_noise, rows, stride(rows), out, stride(out))
+        return out
+
+    def randomisation_record(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The plant each env has in the episode it is in now: float32 [N, 4] -- strength, delay, steps until the next push (-1: none),
+        0 --, one launch.  `out`: a float32 [N, >= 4] tensor with contiguous rows (the tail of a privileged row); returned narrowed to 4."""
+        w = _lib.RAND_WORDS
+        if out is None:
+            out = torch.empty(self.n_envs, w, dtype=torch.float32, device=self.device)
+        elif out.dim() != 2 or out.shape[0] != self.n_envs or out.shape[1] < w or out.dtype != torch.float32 or out.device != self.device \
+                or out.stride(1) != 1 or (self.n_envs > 1 and out.stride(0) < w):
+            raise ValueError(f"out must be a float32 [n_envs, >= {w}] tensor on the env's device with contiguous rows")
+        self._call(self.lib.mocca_randomisation_record, out, int(out.stride(0) if self.n_envs > 1 else max(out.stride(0), w)))
+        return out if out.shape[1] == w else out[:, :w]
 
     def kernel_info(self) -> dict:
         v = [C.c_int() for _ in range(5)]

@@ -12,6 +12,7 @@ No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it Symme
                            [--device-policy [--device-returns [--device-grad [--device-update]]]] [--symmetric | --mirror-loss COEF | --mirror-dup]
                            [--base-controller FILE] [--height-scan NX,NY] [--depth-camera W,H]
                            [--distill-from TEACHER.npz --privileged-scan NX,NY] [--privileged-critic --privileged-scan NX,NY]
+                           [--rand-strength LO,HI] [--rand-latency LO,HI] [--rand-push INTERVAL,MAX] [--obs-noise SCALE] [--rand-privileged]
 --base-controller FILE (required for the planner ids, Walker3DPlannerEnv-v0 / MikePlannerEnv-v0): ALLSTEPS's second step.  FILE is a
 `BaseController.save_npz` file or the <out>_policy.npz of an earlier run of this script on a Stepper id (told apart by the keys; the latter
 brings its observation statistics along); it is frozen as the env's base controller and the policy trained here emits 15-number plans.
@@ -66,6 +67,12 @@ privileged reaches the policy that is saved.  The rollout storage gains `critic_
 `vf` on them, --device-policy attaches an asymmetric `DevicePolicy` (`attach_policy` binds `envs.privileged` for the critic's workgroups),
 --device-returns keeps a second `ObsStats` that writes into the longer tail of the flat tensor, and --device-grad / --device-update pass
 `critic_obs=` (mocca_ppo_grad_priv / mocca_ppo_update_priv).  <out>_policy.npz also holds `critic_obs_mean` / `critic_obs_var`.
+--rand-strength LO,HI / --rand-latency LO,HI / --rand-push INTERVAL,MAX / --obs-noise SCALE: domain randomisation on the device through
+`make_vec_envs(randomisation=Randomisation(...))` -- every episode draws its motor strength in [LO, HI] and its action latency of LO .. HI
+steps, every INTERVAL steps the base is pushed by up to MAX m/s, and uniform noise of half-width SCALE is added to the policy's row (the
+critic's privileged row stays clean).  Every arm works: the randomisation acts on what the step kernel reads and writes, whoever produced the
+action.  --rand-privileged (with --privileged-critic): the privileged row becomes [obs | scan | record], the critic knows the plant.
+<out>_policy.npz records the randomisation the policy was trained under (`randomisation`, a JSON string).
 --verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor
 (--mirror-dup: on that minibatch's rows whose ratio and whose twin's ratio lie more than 1e-4 from the clip bounds, where the surrogate's
 gradient jumps and two float32 evaluations may disagree on a sample's side; the twins' ratios are spread over the bounds); with
@@ -118,6 +125,11 @@ def main(argv=None):
     ap.add_argument("--distill-from", default=None, metavar="TEACHER.npz", help="with --device-update: distil this frozen teacher (the policy file of a --height-scan run) into the student instead of PPO")
     ap.add_argument("--privileged-scan", default=None, metavar="NX,NY", help="with --distill-from: the teacher's scan_grid, kept beside the observation row (envs.privileged), never in it")
     ap.add_argument("--privileged-critic", action="store_true", help="with --privileged-scan: PPO whose critic reads envs.privileged ([obs | scan]) while the actor reads the observation row")
+    ap.add_argument("--rand-strength", default=None, metavar="LO,HI", help="each episode draws its motor strength in [LO, HI], 0 < LO <= HI <= 1")
+    ap.add_argument("--rand-latency", default=None, metavar="LO,HI", help="each episode draws its action latency of LO .. HI steps (at most 7)")
+    ap.add_argument("--rand-push", default=None, metavar="INTERVAL,MAX", help="every INTERVAL steps the base's velocity jumps by up to MAX m/s along x and y")
+    ap.add_argument("--obs-noise", type=float, default=None, metavar="SCALE", help="uniform noise of this half-width on every column of the policy's observation row")
+    ap.add_argument("--rand-privileged", action="store_true", help="with --privileged-critic: the plant's record joins the critic's row, [obs | scan | record]")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args(argv)
     if args.device_grad and not args.device_returns:
@@ -154,11 +166,20 @@ def main(argv=None):
     if args.privileged_critic and (args.privileged_scan is None or args.distill_from is not None or args.symmetric or args.mirror_loss is not None
                                    or args.mirror_dup):
         ap.error("--privileged-critic requires --privileged-scan and is not for --distill-from / --symmetric / --mirror-loss / --mirror-dup")
+    if args.rand_privileged and not args.privileged_critic:
+        ap.error("--rand-privileged requires --privileged-critic: the record is the tail of the critic's row")
     import torch
     import torch.nn as nn
     from mocca_envs_amd.trainer_api import make_vec_envs
     torch.manual_seed(args.seed)
     extra = {}
+    rand = None
+    if any(v is not None for v in (args.rand_strength, args.rand_latency, args.rand_push, args.obs_noise)) or args.rand_privileged:
+        from mocca_envs_amd.randomisation import Randomisation
+        pair = lambda text, kind, default: default if text is None else tuple(k(v) for k, v in zip(kind, text.split(",")))
+        rand = Randomisation(strength=pair(args.rand_strength, (float, float), (1.0, 1.0)), latency=pair(args.rand_latency, (int, int), (0, 0)),
+                             push=pair(args.rand_push, (int, float), (0, 0.0)), obs_noise=args.obs_noise, privileged=args.rand_privileged)
+        extra["randomisation"] = rand
     if args.base_controller is not None:
         from mocca_envs_amd.controller import BaseController
         extra["base_controller"] = BaseController.load(args.base_controller)
@@ -530,7 +551,8 @@ def main(argv=None):
     np.savez(args.out + "_policy.npz", obs_mean=mean.cpu().numpy(), obs_var=var.cpu().numpy(), log_std=log_std.detach().cpu().numpy(),
              **{f"pi_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in pi.state_dict().items()},
              **{f"vf_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in vf.state_dict().items()},
-             env_id=np.array(args.env_id), env_steps=np.array(total_steps), **extra_stats)
+             env_id=np.array(args.env_id), env_steps=np.array(total_steps), **extra_stats,
+             **({} if rand is None else dict(randomisation=np.array(json.dumps(rand.as_dict())))))
     envs.close()
 
 
