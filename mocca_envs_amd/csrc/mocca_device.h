@@ -197,6 +197,9 @@ static_assert(L_LGAP + MAXR <= L_CT && L_J >= L_CT, "limit gaps: written after t
 static_assert(L_LGAP >= L_J + 28 * (MAXR + 1) && L_LGAP >= L_A + MAXR * MAXR && L_LGAP >= L_M && L_LGAP + MAXR <= L_TOTAL, "limit gaps: behind the solver view, in the dead link inertias");
 #endif
 static_assert(L_MID % 4 == 0 && L_MID >= L_CAND + (MOCCA_MAX_PAIRS + 1) / 2, "midpoint records: 16-byte aligned, behind the candidate list");
+// The rows' inward sweep fetches the next path position's S, V, 1/D and velocity entry BEFORE it stores this position's Jacobian entry: no
+// J row, the dummy row included, may overlap a body record or the velocity (48-row, 64-row and compact layouts alike)
+static_assert(L_J >= L_SV + 22 * SVS && L_NU + 28 <= L_V && L_V <= L_SV, "J rows lie behind the body records and the new velocity");
 // Which topologies keep midpoint records (collide's broad phase): those with self-collision pairs whose records fit the slack behind the
 // candidate list -- under the link inertias in the compact layout, behind the ABA view otherwise; the others keep the broad phase that adds
 // the end points up per pair.  MOCCA_NO_TRIM_<n>: A/B builds without one of the step kernel's trims (tools/ab.sh), never the product.
@@ -339,6 +342,32 @@ template <class T>
 constexpr bool WALK_LEVELS = false;
 #else
 constexpr bool WALK_LEVELS = OUTWARD_ROUNDS<T>;
+#endif
+// Which step-kernel instances read LDS operands whose addresses are known in advance a step ahead of the arithmetic that waits for them
+// (the same operations in the same order: only the place of the reads changes): the constraint rows' outward sweep (the next body's V | S,
+// 12 registers), their inward sweep (the next path position's S, V, 1/D and velocity entry, 14 registers, both paths) and the ABA inward
+// levels (the next level's own-link operands, up to 22 registers).  An instance that would spill or leave its register budget keeps the
+// parent's order for that item (profiles/kernel_resources_parity.md), as does every instance under MOCCA_NO_TRIM_10 / _11 / _12: the
+// compact instances keep it for all three (at their 96-register budget six of the eight gained 8 .. 40 B of scratch), and the walker's
+// 48-row Stepper and Planner instances for the inward sweep (with all three they spilled four registers, 20 B of scratch, where there
+// was none; with the outward sweep and the levels alone they do not).
+template <class T, int TASK>
+#ifdef MOCCA_NO_TRIM_10
+constexpr bool AHEAD_OUTWARD = false;
+#else
+constexpr bool AHEAD_OUTWARD = !COMPACT;
+#endif
+template <class T, int TASK>
+#ifdef MOCCA_NO_TRIM_11
+constexpr bool AHEAD_INWARD = false;
+#else
+constexpr bool AHEAD_INWARD = !COMPACT && !(MAXR == 48 && __is_base_of(TopoWalker3D, T) && (TASK == MOCCA_TASK_WALKER3D_STEPPER || TASK == MOCCA_TASK_WALKER3D_PLANNER));
+#endif
+template <class T, int TASK>
+#ifdef MOCCA_NO_TRIM_12
+constexpr bool AHEAD_LEVELS = false;
+#else
+constexpr bool AHEAD_LEVELS = !COMPACT;
 #endif
 // the lane that hosts the base body (0) in that layout: the last lane without a body (-1: none, and no WALK_LEVELS)
 template <class T>
@@ -866,7 +895,8 @@ DI void chol6_solve(const float* F, const float* b, float* x) {
 // Leaves S, V = U / D, 1/D, u / D in LDS and the factor of IA0 in Afac (scalar registers) for the row sweeps, and the new generalised
 // velocity in L_NU.
 // FACTOR_ACROSS_LANES: the base's 6x6 factor is formed once across lanes (below); false keeps the per-lane chol6_factor (same bits).
-template <class T, bool FACTOR_ACROSS_LANES>
+// AHEAD: the inward levels request the next level's own-link operands a level ahead (AHEAD_LEVELS); false keeps the reads where they were (same bits).
+template <class T, bool FACTOR_ACROSS_LANES, bool AHEAD>
 DI void aba_passes(ModelP M, float* L, int lane, unsigned long long ppk, float* Afac) {
   STAMP_BEGIN;
   // ---- inward pass, one tree level at a time.  8 lanes per body (lane i < 6 owns row i of the 6x6
@@ -877,35 +907,72 @@ DI void aba_passes(ModelP M, float* L, int lane, unsigned long long ppk, float* 
   const int s = lane >> 3, i = lane & 7;
   const int ii = i < 6 ? i : 0;
   // A body sits in the slot of its "carried" child (topo_*.h: clevel / ccarry), so along a serial chain the articulated
-  // inertia row and bias of the child stay in registers (crow, cpA) and a level costs no LDS round trip: the level's
-  // own link data has static addresses and nothing on the chain waits for it.  Only children in another slot (the
-  // second leg at the pelvis, the limbs at the base) travel through LDS.
+  // inertia row and bias of the child stay in registers (crow, cpA); only children in another slot (the second leg at the
+  // pelvis, the limbs at the base) travel through LDS.  The level's own link data has static addresses, but left to itself the
+  // compiler requests it behind the previous level's stores and waits for it within some seven vector instructions (31 waits in
+  // the pass): a level did cost an LDS round trip.  With AHEAD (below) the requests go out a level earlier.
   float crow[6] = {0, 0, 0, 0, 0, 0}, cpA = 0.0f;
   // LDS offsets of the slot's body, carried from level to level: along a chain the body index drops by one per level, so most
   // levels update the four offsets with one subtraction each instead of rebuilding them from a per-slot select (12 integer
   // instructions per level).  Lanes of an empty slot point at body d (any existing body; they never store).
   int bb = 0, o6i = 0, o36 = 0, osv = 0, osvi = 0;
+  // bodies of a level and their children are compile-time constants selected by the lane's slot
+#define MOCCA_CONT(d, sl) (T::clevel(d, sl) < 0 || ((d) < T::MAXD && T::clevel((d) + 1 <= T::MAXD ? (d) + 1 : (d), sl) == T::clevel(d, sl) + 1))
+  // the offsets of level d's bodies from those of level d + 1 (a macro, not a lambda: with the offsets captured by reference the levels came out longer)
+#define MOCCA_LEVEL_OFFSETS(d) \
+  if ((d) < T::MAXD && MOCCA_CONT(d, 0) && MOCCA_CONT(d, 1) && MOCCA_CONT(d, 2) && MOCCA_CONT(d, 3)) {  /* compile-time: every body of the level continues its slot's chain */ \
+    bb -= 1; o6i -= 6; o36 -= 36; osv -= SVS; osvi -= SVS; \
+  } else { \
+    const int b = s == 0 ? T::clevel(d, 0) : s == 1 ? T::clevel(d, 1) : s == 2 ? T::clevel(d, 2) : s == 3 ? T::clevel(d, 3) : -1; \
+    bb = b >= 0 ? b : (d); \
+    o6i = 6 * bb + ii; o36 = 36 * bb + 6 * ii; osv = SVS * bb; osvi = osv + ii; \
+  }
+  // a level that holds only massless links (the intermediate links of the multi-hinge joints: two of the walker's eight levels)
+  // has nothing to read: its link inertias and bias forces are zero (mocca_create() checks the blob against T::massless)
+#define MOCCA_NOMASS(d, sl) (T::clevel(d, sl) < 0 || T::massless(T::clevel(d, sl)))
+#define MOCCA_NOMASS_LEVEL(d) (MOCCA_NOMASS(d, 0) && MOCCA_NOMASS(d, 1) && MOCCA_NOMASS(d, 2) && MOCCA_NOMASS(d, 3))   // compile-time
+  // AHEAD: level d - 1's OWN-LINK operands -- S, c, its row of the link inertia and its bias component where the level is not massless,
+  // the lane's component of S, the armature and the net joint torque -- are requested before level d's arithmetic, into a second register set.
+  // The walk staged them and nothing inside this pass writes them before their own level has read them: a level stores SV_V, SV_INVD and
+  // SV_UU (and, where it is consumed through LDS, its L_M row and L_P entry) of ITS OWN bodies only, after it has taken their armature and
+  // torque from the registers requested a level earlier, and no body sits on two levels.  Children that arrive through LDS are real
+  // dependencies and are read where they were, behind the wsync() of the level that stored them.
+  float nS[6], nc[6], nM[6] = {0, 0, 0, 0, 0, 0}, nP = 0.0f, nSi = 0.0f, narm = 0.0f, nunet = 0.0f;
+#define MOCCA_LEVEL_FETCH(d) \
+  _Pragma("unroll") for (int j = 0; j < 6; ++j) { nS[j] = L[L_SV + osv + j]; nc[j] = L[L_SV + osv + SV_C + j]; } \
+  if (!MOCCA_NOMASS_LEVEL(d)) { \
+    _Pragma("unroll") for (int j = 0; j < 6; ++j) nM[j] = L[L_M + o36 + j]; \
+    nP = L[L_P + o6i]; \
+  } \
+  nSi = i < 6 ? L[L_SV + osvi] : 0.0f; \
+  narm = L[L_SV + osv + SV_INVD]; nunet = L[L_SV + osv + SV_UU];
+  if constexpr (AHEAD) { MOCCA_LEVEL_OFFSETS(T::MAXD) MOCCA_LEVEL_FETCH(T::MAXD) }
 #pragma unroll
   for (int d = T::MAXD; d >= 1; --d) {
-    // bodies of this level and their children are compile-time constants selected by the lane's slot
-#define MOCCA_CONT(sl) (T::clevel(d, sl) < 0 || (d < T::MAXD && T::clevel(d + 1 <= T::MAXD ? d + 1 : d, sl) == T::clevel(d, sl) + 1))
     const bool sv = s == 0 ? T::clevel(d, 0) >= 0 : s == 1 ? T::clevel(d, 1) >= 0 : s == 2 ? T::clevel(d, 2) >= 0 : s == 3 ? T::clevel(d, 3) >= 0 : false;
     const bool valid = sv && i < 6;
-    if (d < T::MAXD && MOCCA_CONT(0) && MOCCA_CONT(1) && MOCCA_CONT(2) && MOCCA_CONT(3)) {  // compile-time: every body of the level continues its slot's chain
-      bb -= 1; o6i -= 6; o36 -= 36; osv -= SVS; osvi -= SVS;
-    } else {
-      const int b = s == 0 ? T::clevel(d, 0) : s == 1 ? T::clevel(d, 1) : s == 2 ? T::clevel(d, 2) : s == 3 ? T::clevel(d, 3) : -1;
-      bb = b >= 0 ? b : d;
-      o6i = 6 * bb + ii; o36 = 36 * bb + 6 * ii; osv = SVS * bb; osvi = osv + ii;
-    }
-#undef MOCCA_CONT
+    if constexpr (!AHEAD) { MOCCA_LEVEL_OFFSETS(d) }
+    const int c6i = o6i, c36 = o36, csv = osv, csvi = osvi;   // this level's offsets (AHEAD moves the carried ones on to level d - 1 below)
     float row[6], S[6], c[6], pAi;
+    float Si_, arm_, unet_;
+    if constexpr (AHEAD) {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) { S[j] = nS[j]; c[j] = nc[j]; }
+      if (MOCCA_NOMASS_LEVEL(d)) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) row[j] = crow[j];
+        pAi = cpA;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) row[j] = nM[j] + crow[j];
+        pAi = nP + cpA;
+      }
+      Si_ = nSi; arm_ = narm; unet_ = nunet;
+      if (d > 1) { MOCCA_LEVEL_OFFSETS(d - 1) MOCCA_LEVEL_FETCH(d - 1) }
+    } else {
 #pragma unroll
     for (int j = 0; j < 6; ++j) { S[j] = L[L_SV + osv + j]; c[j] = L[L_SV + osv + SV_C + j]; }
-    // a level that holds only massless links (the intermediate links of the multi-hinge joints: two of the walker's eight levels)
-    // has nothing to read: its link inertias and bias forces are zero (mocca_create() checks the blob against T::massless)
-#define MOCCA_NOMASS(sl) (T::clevel(d, sl) < 0 || T::massless(T::clevel(d, sl)))
-    if (MOCCA_NOMASS(0) && MOCCA_NOMASS(1) && MOCCA_NOMASS(2) && MOCCA_NOMASS(3)) {   // compile-time
+    if (MOCCA_NOMASS_LEVEL(d)) {
 #pragma unroll
       for (int j = 0; j < 6; ++j) row[j] = crow[j];
       pAi = cpA;
@@ -914,7 +981,7 @@ DI void aba_passes(ModelP M, float* L, int lane, unsigned long long ppk, float* 
       for (int j = 0; j < 6; ++j) row[j] = L[L_M + o36 + j] + crow[j];
       pAi = L[L_P + o6i] + cpA;
     }
-#undef MOCCA_NOMASS
+    }
 #pragma unroll
     for (int k = 0; k < T::MAXCH; ++k) {
       // the k-th child of the slot's body, unless it is the carried one
@@ -932,11 +999,13 @@ DI void aba_passes(ModelP M, float* L, int lane, unsigned long long ppk, float* 
     // Branch-free on purpose: idle lanes (rows 6, 7 of a group, empty slots) run the same arithmetic on harmless data
     // and are kept out of the sums / the stores only.  Under `valid ? ... : 0` the compiler sank the LDS reads into
     // conditional blocks, each with its own wait, and nothing of the next level could be fetched ahead.
-    const float Si = i < 6 ? L[L_SV + osvi] : 0.0f;  // the lane's own component of S (0 for the two idle lanes)
+    if constexpr (!AHEAD) Si_ = i < 6 ? L[L_SV + osvi] : 0.0f;
+    const float Si = Si_;  // the lane's own component of S (0 for the two idle lanes)
     const float Ui = dot6(row, S);
     float dsum = Si * Ui, psum = Si * pAi;
     group8_sum2(dsum, psum);
-    float arm = L[L_SV + osv + SV_INVD], unet = L[L_SV + osv + SV_UU];  // staged by the walk: joint armature, net joint torque
+    if constexpr (!AHEAD) { arm_ = L[L_SV + osv + SV_INVD]; unet_ = L[L_SV + osv + SV_UU]; }
+    float arm = arm_, unet = unet_;                  // staged by the walk: joint armature, net joint torque
     pin1(arm); pin1(unet);                           // fetched with the level's other reads, not inside the store branch
     const float id = rcp(dsum + arm);
     const float u = unet - psum;
@@ -972,11 +1041,11 @@ DI void aba_passes(ModelP M, float* L, int lane, unsigned long long ppk, float* 
     if (valid) {
       if (store_m) {
 #pragma unroll
-        for (int j = 0; j < 6; ++j) L[L_M + o36 + j] = row[j];
-        L[L_P + o6i] = pOut;
+        for (int j = 0; j < 6; ++j) L[L_M + c36 + j] = row[j];
+        L[L_P + c6i] = pOut;
       }
-      L[L_SV + osvi + SV_V] = uid;   // V_i = U_i / D: what the outward passes and the row sweeps multiply by
-      if (i == 0) { L[L_SV + osv + SV_INVD] = id; L[L_SV + osv + SV_UU] = u * id; }
+      L[L_SV + csvi + SV_V] = uid;   // V_i = U_i / D: what the outward passes and the row sweeps multiply by
+      if (i == 0) { L[L_SV + csv + SV_INVD] = id; L[L_SV + csv + SV_UU] = u * id; }
     }
     // What the slot hands to the next level in registers: its result.  Only a slot whose NEXT-level body does not continue this
     // level's chain (a chain that starts there, or this level's body is consumed through LDS) must hand over zeros, and which
@@ -997,6 +1066,11 @@ DI void aba_passes(ModelP M, float* L, int lane, unsigned long long ppk, float* 
 #undef MOCCA_VIA_LDS
     if (store_m) wsync();
   }
+#undef MOCCA_LEVEL_FETCH
+#undef MOCCA_LEVEL_OFFSETS
+#undef MOCCA_NOMASS_LEVEL
+#undef MOCCA_NOMASS
+#undef MOCCA_CONT
   STAMP(10);
   // base: the six lanes of the first group each add up ONE ROW of the base's articulated inertia (own link + the children, which all
   // arrive through LDS) and its bias component, park row + bias as eight floats, and every lane reads the 6 x 8 block back for the
@@ -2104,7 +2178,15 @@ DI void dbg_fold_step(int32_t* dbg, int lane) {
     dbg[16] = (int32_t)(unsigned)h; dbg[17] = (int32_t)(unsigned)(h >> 32); dbg[18] += 1;
   }
 }
-template <class T, bool MATRIX_PIPE>
+// What the rows' inward sweep reads at one position of a packed path: S and V = IA S / D of the body there, its entry of the new velocity, 1 / D
+struct PathOps { float S[6], U[6], nu, invd; };
+DI void path_ops(const float* L, unsigned long long pk, int k, PathOps& o) {
+  const int j = (int)((pk >> (5 * k)) & 31ull);   // 0 past the end of the path: body 0's record, which the sweep's selects discard
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { o.S[i] = L[L_SV + SVS * j + i]; o.U[i] = L[L_SV + SVS * j + SV_V + i]; }
+  o.nu = L[L_NU + 5 + j]; o.invd = L[L_SV + SVS * j + SV_INVD];
+}
+template <class T, bool MATRIX_PIPE, bool AHEAD_OUT, bool AHEAD_IN>
 DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wanted, unsigned long long ppk, int32_t* dbg, const float* Afac, int prio, int& rows_out) {
   // (wave-uniform) bit 0: the slots' normal impulses are wanted after the substep (warm start / diagnostic); bit 1: the Delassus matrix is built on
   // the VALU whatever the row count (StepArgs.prio & PRIO_DELASSUS_VALU).  One scalar for both: it is live to the end of the substep anyway
@@ -2295,14 +2377,27 @@ DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wan
     for (int i = 1; i < 7; ++i) jz[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
   float pu[T::MAXD], pub[T::MAXD];
+  // AHEAD_IN: a position's S, V, 1/D and velocity entry (addresses from the packed path, known before the loop) are requested one position
+  // ahead, before this position's arithmetic and its J store, into a second register set (14 registers); position MAXD - 1 before the
+  // loop, position 0 requests nothing.  In the parent's order every position waited for its record after the previous position's store and
+  // for 1/D and the velocity entry after its own.  The J rows overlap neither the records nor L_NU (asserted at the layout).
+  PathOps nx;
+  if constexpr (AHEAD_IN) path_ops(L, pka, T::MAXD - 1, nx);
 #pragma unroll
   for (int k = T::MAXD - 1; k >= 0; --k) {
     const int j = (int)((pka >> (5 * k)) & 31ull);
     const bool valid = j != 0;   // 0: past the end of the path (body 0's record is read, the selects below discard it)
     const int jj = j;
-    float S[6], U[6];
+    float S[6], U[6], nu, invd;
+    if constexpr (AHEAD_IN) {
 #pragma unroll
-    for (int i = 0; i < 6; ++i) { S[i] = L[L_SV + SVS * jj + i]; U[i] = L[L_SV + SVS * jj + SV_V + i]; }
+      for (int i = 0; i < 6; ++i) { S[i] = nx.S[i]; U[i] = nx.U[i]; }
+      nu = nx.nu; invd = nx.invd;
+      if (k > 0) path_ops(L, pka, k - 1, nx);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) { S[i] = L[L_SV + SVS * jj + i]; U[i] = L[L_SV + SVS * jj + SV_V + i]; }
+    }
     float jb = dot6(S, F);
     if (jj == jl) jb = sgn;
     jb = valid ? jb : 0.0f;
@@ -2311,29 +2406,42 @@ DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wan
 #pragma unroll
     for (int i = 0; i < 6; ++i) pa[i] += U[i] * uu;  // U holds V = IA S / D; uu == 0 past the end of the path
     if (valid) Jrow[5 + jj] = jb;
-    w += jb * L[L_NU + 5 + jj];
-    pu[k] = uu * L[L_SV + SVS * jj + SV_INVD];   // what the outward sweep starts from: u / D
+    if constexpr (!AHEAD_IN) nu = L[L_NU + 5 + jj];
+    w += jb * nu;
+    if constexpr (!AHEAD_IN) invd = L[L_SV + SVS * jj + SV_INVD];
+    pu[k] = uu * invd;   // what the outward sweep starts from: u / D
     pin6(pa); pin1(pu[k]); pin1(w);
   }
   if (two_paths) {
     const int bq = bb >= 0 ? bb : 0;
     const unsigned long long pkb = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(ppk >> 32), bq, 64) << 32) |
                                    (unsigned long long)(unsigned)__shfl((int)(unsigned)ppk, bq, 64);
+    // (the second path's first request sits inside the branch: in front of it, waves without a second path would pay five reads for nothing)
+    if constexpr (AHEAD_IN) path_ops(L, pkb, T::MAXD - 1, nx);
 #pragma unroll
     for (int k = T::MAXD - 1; k >= 0; --k) {
       const int j = (int)((pkb >> (5 * k)) & 31ull);
       const bool valid = j != 0;
       const int jj = j;
-      float S[6], U[6];
+      float S[6], U[6], nu, invd;
+      if constexpr (AHEAD_IN) {
 #pragma unroll
-      for (int i = 0; i < 6; ++i) { S[i] = L[L_SV + SVS * jj + i]; U[i] = L[L_SV + SVS * jj + SV_V + i]; }
+        for (int i = 0; i < 6; ++i) { S[i] = nx.S[i]; U[i] = nx.U[i]; }
+        nu = nx.nu; invd = nx.invd;
+        if (k > 0) path_ops(L, pkb, k - 1, nx);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { S[i] = L[L_SV + SVS * jj + i]; U[i] = L[L_SV + SVS * jj + SV_V + i]; }
+      }
       const float jb = valid ? -dot6(S, F2) : 0.0f;   // the force on the second body is -F2
       const float uu = valid ? (k == T::MAXD - 1 ? jb : jb - dot6(S, pb)) : 0.0f;
 #pragma unroll
       for (int i = 0; i < 6; ++i) pb[i] += U[i] * uu;
       if (valid) Jrow[5 + jj] += jb;                  // common ancestors carry both paths' entries
-      w += jb * L[L_NU + 5 + jj];
-      pub[k] = uu * L[L_SV + SVS * jj + SV_INVD];
+      if constexpr (!AHEAD_IN) nu = L[L_NU + 5 + jj];
+      w += jb * nu;
+      if constexpr (!AHEAD_IN) invd = L[L_SV + SVS * jj + SV_INVD];
+      pub[k] = uu * invd;
       pin6(pb); pin1(pub[k]); pin1(w);
     }
   }
@@ -2370,19 +2478,46 @@ DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wan
     float acc[T::NB][6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) acc[0][i] = a0[i];
+    // AHEAD_OUT: body b + 1's V | S (static addresses, the same on every lane) are requested before body b's arithmetic, into a second
+    // register set, so a body no longer starts with a full LDS round trip: the pins below are volatile statements, which every memory
+    // operation is ordered against, and nothing crossed them on its own.  Body 1 is requested before the loop, the last body requests
+    // nothing: no address outside [1, NB) is formed.  Still through L2, so the inward sweep's values are not kept live.
+    // a body without children: nothing reads its acceleration, so neither that nor its S is formed (T::cchild, compile time;
+    // the walker's bodies 8, 13, 17 and 21)
+#ifdef MOCCA_NO_TRIM_4
+#define MOCCA_INNER(b) true
+#else
+#define MOCCA_INNER(b) has_child<T>(b)   // (folds after unrolling)
+#endif
+    float Un[6], Sn[6];
+    if constexpr (AHEAD_OUT && T::NB > 1) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) Un[i] = L2[L_SV + SVS * 1 + SV_V + i];
+      if (MOCCA_INNER(1)) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) Sn[i] = L2[L_SV + SVS * 1 + i];
+      }
+    }
 #pragma unroll
     for (int b = 1; b < T::NB; ++b) {
       const int p = T::parent(b);
-      // a body without children: nothing reads its acceleration, so neither that nor its S is formed (T::cchild, compile time;
-      // the walker's bodies 8, 13, 17 and 21)
-#ifdef MOCCA_NO_TRIM_4
-      constexpr bool inner = true;
-#else
-      const bool inner = has_child<T>(b);   // (folds after unrolling)
-#endif
-      float U[6];
+      const bool inner = MOCCA_INNER(b);
+      float U[6], S[6];
+      if constexpr (AHEAD_OUT) {
 #pragma unroll
-      for (int i = 0; i < 6; ++i) U[i] = L2[L_SV + SVS * b + SV_V + i];   // U = V = IA S / D
+        for (int i = 0; i < 6; ++i) { U[i] = Un[i]; S[i] = inner ? Sn[i] : 0.0f; }   // (a body without children: S has no reader)
+        if (b + 1 < T::NB) {
+#pragma unroll
+          for (int i = 0; i < 6; ++i) Un[i] = L2[L_SV + SVS * (b + 1) + SV_V + i];
+          if (MOCCA_INNER(b + 1)) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) Sn[i] = L2[L_SV + SVS * (b + 1) + i];
+          }
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) U[i] = L2[L_SV + SVS * b + SV_V + i];   // U = V = IA S / D
+      }
       const int dpos = T::depth(b) - 1;  // (folds after unrolling) the body's position on every path that holds it
       // pu[dpos] where the row's path holds b, else 0: bit b of the ancestor mask, sign-extended, ANDs the value (v_bfe_i32 + v_and)
       float ub = __uint_as_float(__float_as_uint(pu[dpos]) & (unsigned)__builtin_amdgcn_sbfe((int)ma, b, 1));
@@ -2390,13 +2525,17 @@ DI void solve_constraints(ModelP M, float* L, int lane, int nc_found, int nc_wan
       const float qdd = ub - dot6(U, acc[p]);   // u / D - (IA S / D) . a_parent
       X[5 + b] = qdd;
       if (inner) {
-        float S[6];
+        if constexpr (!AHEAD_OUT) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) { S[i] = L2[L_SV + SVS * b + i]; acc[b][i] = acc[p][i] + S[i] * qdd; }
+          for (int i = 0; i < 6; ++i) S[i] = L2[L_SV + SVS * b + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) acc[b][i] = acc[p][i] + S[i] * qdd;
         pin6(acc[b]);
       }
       pin1(X[5 + b]);
     }
+#undef MOCCA_INNER
   }
   STAMP(6);
   wsync();  // all lanes are done with the ABA view: the A matrix may overwrite it
@@ -2694,7 +2833,7 @@ DI ContactFlags substep(ModelP M, float* L, int lane, const float* ter, int next
   // (24 B of scratch), so that instance keeps the per-lane factor.
   constexpr bool PLANNER48 = !COMPACT && MAXR == 48 && TASK == MOCCA_TASK_WALKER3D_PLANNER;
 #ifndef MOCCA_SKIP_ABA
-  aba_passes<T, !PLANNER48>(M, L, lane, ppk, Afac);
+  aba_passes<T, !PLANNER48, AHEAD_LEVELS<T, TASK>>(M, L, lane, ppk, Afac);
 #endif
   STAMP(2);
   pace_checkpoint(L, done0 + 36, total);
@@ -2702,7 +2841,7 @@ DI ContactFlags substep(ModelP M, float* L, int lane, const float* ter, int next
   // The planner instance of the 48-row kernel sits at its 128-register budget: with the matrix-pipe build compiled in, the deepest step of its VALU
   // build spills two 4-register tuples to scratch (whatever the new path holds: X store, operand reads, MFMAs or tile stores alone).  It keeps the
   // VALU build for every row count until that instance has room.
-  solve_constraints<T, !PLANNER48>(M, L, lane, nc, nc_wanted, ppk, dbg, Afac, prio, rows_out);
+  solve_constraints<T, !PLANNER48, AHEAD_OUTWARD<T, TASK>, AHEAD_INWARD<T, TASK>>(M, L, lane, nc, nc_wanted, ppk, dbg, Afac, prio, rows_out);
 #endif
   if (dbg) { __builtin_amdgcn_s_waitcnt(0); dbg_fold_step(dbg, lane); }   // (lane 0 wrote the twelve words above; it reads them back itself)
   STAMP(3);
