@@ -1004,6 +1004,56 @@ int mocca_set_sensor_noise(mocca_handle h, const float *scale_host, int dim);
 int mocca_sensor_noise(mocca_handle h, const float *rows_dev, int in_stride, float *out_dev, int out_stride, void *stream);
 int mocca_randomisation_record(mocca_handle h, float *out_dev, int row_stride, void *stream);
 
+/* ---- observation-action history on the training path (no reference counterpart) ---- */
+
+/* These entry points are ADDITIVE: MOCCA_ABI_VERSION stays 8, and a handle that calls none of them launches exactly what it launched before.
+ * Nothing here touches the step kernel.  A feed-forward actor on the current row cannot tell which plant it has (mocca_set_randomisation):
+ * strength and delay show only in what was commanded against what happened over the last few steps.  mocca_history writes that -- past
+ * observations and past actions -- as the tail of the policy's row, one launch, capturable.  Index rules, race argument and kernel layout:
+ * mocca_envs_amd/csrc/mocca_history.h.
+ *
+ * The rule.  Configuration: K = steps, 1 .. MOCCA_HIST_MAX_STEPS; s = stride, 1 .. MOCCA_HIST_MAX_STRIDE; an ordered list of C distinct
+ * observation columns cols[0 .. C), 0 <= C <= obs_dim; an action width A, 0 .. 32; C + A >= 1; block width K (C + A) <= MOCCA_HIST_MAX_DIM.
+ * Per env the handle owns a ring of R = K s + 1 slots of C + A floats and a tag of two uint32 per slot.  At attach time the ring is zeroed
+ * and every tag is set to a value no episode holds (t = 0xFFFFFFFF).  mocca_history is ONE launch; per env, with t the task word MOCCA_TW_T
+ * and E the task word MOCCA_TW_EPISODE, both READ FROM THE TASK RECORD WHEN THE KERNEL RUNS (nothing is kept on the host), it
+ *   1. stores the current frame: in slot t % R the observation part takes rows[e][cols[0 .. C)], the action part +0.0, the tag (E, t);
+ *   2. completes the previous frame: if t >= 1, act_dev != NULL and the tag of slot (t - 1) % R equals (E, t - 1), the action part of that
+ *      slot takes act[e][0 .. A);
+ *   3. emits the block, NEWEST FIRST: pair j = 1 .. K sits at offset (j - 1)(C + A) and is [o_u[cols] | a_u] with u = t - j s -- the
+ *      observation the policy read j s steps ago and the action it then output.  A pair is valid iff t >= j s and the tag of slot u % R
+ *      equals (E, u); an invalid pair is C + A words of +0.0.  A valid pair comes from the ring, except the action part when j s == 1: it is
+ *      taken from act[e] directly (+0.0 when act_dev == NULL).
+ * No thread reads a ring word that another thread of the same launch writes: the launch writes slot t % R and the action part of slot
+ * (t - 1) % R; step 3 reads slots of u = t - j s with 1 <= j s <= R - 1, never slot t % R; of slot (t - 1) % R it reads the tag and the
+ * observation part, which an earlier launch wrote, and takes the action part -- the one word being written -- from act[e] instead.
+ * Consequences: the ring is indexed by T and tagged by (E, T), so mocca_reset, the step kernel's auto-reset and a mocca_set_task that moves T
+ * need no clearing pass: an episode only ever reads what it wrote itself.  A call that was skipped shows up as a zero pair, never as
+ * another episode's data.  Two calls without a step in between write and emit the same words.  Everything is a copy or a zero.
+ * Limits: THE RING IS NOT PART OF THE mocca_get_state / mocca_get_task SNAPSHOT -- a restored task record that returns to an (E, T) the ring
+ * has already seen reads those frames; mocca_task_step advances T without a history call.
+ *
+ * mocca_set_history  attaches (steps == 0: detaches; the other arguments are then not read) the history: cols_host [n_cols] int32 is copied
+ *                   into the handle, act_dim is A (the env's action width, the plan's on a planner env, or 0).  May allocate and
+ *                   synchronise.  One handle: the multi-handle wrappers of the Python layer do not offer it.
+ * mocca_history_dim  steps * (n_cols + act_dim).
+ * mocca_history      rows_dev: the policy's rows, row_stride floats apart, columns 0 .. obs_dim - 1 read; act_dev: the action the policy output
+ *                   on the PREVIOUS row (what the step that led here ran on), act_stride floats apart, or NULL (after a reset); out_dev: the
+ *                   block's first float, rows out_stride floats apart.  rows_dev and out_dev may lie in the same row (in place: head columns
+ *                   are read, tail columns written; the block must not overlap the columns read).  Floats of a row outside the block are
+ *                   never written.  Allocates nothing, reads nothing on the host, uses no atomics and does not synchronise.
+ * Errors (MOCCA_E_ARG, with a message, before any launch; the handle and every output are left as they were): mocca_set_history: a column
+ * outside 0 .. obs_dim - 1 or repeated; steps, stride, act_dim or the block width out of range; n_cols + act_dim == 0.  mocca_history and
+ * mocca_history_dim without an attachment; mocca_history: a NULL rows_dev or out_dev, row_stride < obs_dim, out_stride <
+ * mocca_history_dim, act_stride < act_dim with a non-NULL act_dev. */
+#define MOCCA_HIST_MAX_STEPS 16
+#define MOCCA_HIST_MAX_STRIDE 8
+#define MOCCA_HIST_MAX_DIM 1024
+int mocca_set_history(mocca_handle h, const int32_t *cols_host, int n_cols, int act_dim, int steps, int stride); /* steps == 0 detaches */
+int mocca_history_dim(mocca_handle h);   /* steps * (n_cols + act_dim); MOCCA_E_ARG without an attachment */
+int mocca_history(mocca_handle h, const float *rows_dev, int row_stride, const float *act_dev /* may be NULL */, int act_stride,
+                  float *out_dev, int out_stride, void *stream);
+
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */
 int mocca_kernel_info(mocca_handle h, int *vgprs, int *sgprs, int *lds_bytes, int *scratch_bytes, int *max_blocks_per_cu);

@@ -23,6 +23,7 @@
 #include "mocca_depth.h"
 #include "mocca_terrain.h"
 #include "mocca_randomise.h"
+#include "mocca_history.h"
 
 using namespace mocca;
 
@@ -206,6 +207,11 @@ struct mocca_ctx {
   DevBuf<float> d_rand_eff;          // [N][act_dim] the effective action of the last step
   DevBuf<float> d_rand_ring;         // [N][delay_max + 1][act_dim] the stored actions of the last delay_max + 1 steps; NOT part of a snapshot
   DevBuf<float> d_noise_scale;       // [obs_dim] mocca_set_sensor_noise
+  // the observation-action history (mocca_history.h), all owned by the handle; hist_cfg.steps == 0: none attached
+  mocca_hist::HistConfig hist_cfg{};
+  DevBuf<int32_t> d_hist_cols;       // [n_cols] the observation columns of a frame
+  DevBuf<float> d_hist_ring;         // [N][steps * stride + 1][n_cols + act_dim] the frames; NOT part of a snapshot
+  DevBuf<uint32_t> d_hist_tags;      // [N][steps * stride + 1][2] (episode, step) of the frame a slot holds
   std::string err;
 };
 static_assert(ROBOT_STATE_STRIDE == mocca_ctrl::CTRL_RS_STRIDE, "the step kernels and the controller kernel share the robot_state buffer");
@@ -793,6 +799,76 @@ int mocca_randomisation_record(mocca_handle h, float* out_dev, int row_stride, v
   DeviceGuard guard(h->device);
   mocca_rand::RecordArgs a{rand_keys(h), h->rand_cfg, out_dev, row_stride};
   mocca_rand::launch_record((hipStream_t)stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return MOCCA_OK;
+}
+
+// ---- the observation-action history (mocca_history.h) ----
+int mocca_set_history(mocca_handle h, const int32_t* cols_host, int n_cols, int act_dim, int steps, int stride) {
+  if (!h) return MOCCA_E_ARG;
+  DeviceGuard guard(h->device);
+  if (steps == 0) {   // detach
+    if (int rc = commit_ready(h, "mocca_set_history")) return rc;
+    h->hist_cfg = mocca_hist::HistConfig{}; h->d_hist_cols.reset(); h->d_hist_ring.reset(); h->d_hist_tags.reset();
+    return MOCCA_OK;
+  }
+  auto refuse = [&](const std::string& what) { h->err = "mocca_set_history: " + what; return MOCCA_E_ARG; };
+  if (steps < 1 || steps > MOCCA_HIST_MAX_STEPS) return refuse("steps must be 1 .. " + std::to_string(MOCCA_HIST_MAX_STEPS) + " (0 detaches)");
+  if (stride < 1 || stride > MOCCA_HIST_MAX_STRIDE) return refuse("stride must be 1 .. " + std::to_string(MOCCA_HIST_MAX_STRIDE));
+  if (act_dim < 0 || act_dim > mocca_hist::HIST_MAX_ACT) return refuse("act_dim must be 0 .. " + std::to_string(mocca_hist::HIST_MAX_ACT));
+  if (n_cols < 0 || n_cols > h->obs_dim || (n_cols > 0 && !cols_host))
+    return refuse("n_cols must be 0 .. obs_dim (" + std::to_string(h->obs_dim) + "), with that many columns");
+  if (n_cols + act_dim == 0) return refuse("a frame needs at least one observation column or one action entry");
+  std::vector<char> seen((size_t)h->obs_dim, 0);
+  for (int k = 0; k < n_cols; ++k) {
+    const int c = cols_host[k];
+    if (c < 0 || c >= h->obs_dim) return refuse("column " + std::to_string(c) + " is outside 0 .. " + std::to_string(h->obs_dim - 1));
+    if (seen[c]) return refuse("column " + std::to_string(c) + " is repeated");
+    seen[c] = 1;
+  }
+  const mocca_hist::HistConfig cfg{steps, stride, n_cols, act_dim};
+  if (mocca_hist::hist_dim(cfg) > MOCCA_HIST_MAX_DIM)
+    return refuse("the block has steps x (n_cols + act_dim) = " + std::to_string(mocca_hist::hist_dim(cfg)) + " floats, at most " +
+                  std::to_string(MOCCA_HIST_MAX_DIM));
+  const size_t n_slots = (size_t)h->n_envs * mocca_hist::hist_slots(cfg);
+  if ((size_t)h->n_envs * mocca_hist::hist_dim(cfg) >= ((size_t)1 << 31)) return refuse("n_envs x the block width must stay below 2^31");
+  DevBuf<int32_t> cols;
+  DevBuf<float> ring;
+  DevBuf<uint32_t> tags;
+  hipError_t e = cols.alloc((size_t)(n_cols > 0 ? n_cols : 1), true);
+  if (e == hipSuccess && n_cols > 0) e = hipMemcpy(cols, cols_host, (size_t)n_cols * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = ring.alloc(n_slots * mocca_hist::hist_width(cfg), true);
+  if (e == hipSuccess) e = tags.alloc(n_slots * 2, false);
+  if (e == hipSuccess) e = hipMemset(tags, 0xFF, n_slots * 2 * sizeof(uint32_t));   // every tag word HIST_NO_T: a frame no episode holds
+  if (int rc = commit_ready(h, "mocca_set_history", e)) return rc;
+  h->d_hist_cols.swap(cols); h->d_hist_ring.swap(ring); h->d_hist_tags.swap(tags);
+  h->hist_cfg = cfg;
+  return MOCCA_OK;
+}
+
+int mocca_history_dim(mocca_handle h) {
+  if (!h) return MOCCA_E_ARG;
+  if (h->hist_cfg.steps == 0) { h->err = "mocca_history_dim needs a history (mocca_set_history)"; return MOCCA_E_ARG; }
+  return mocca_hist::hist_dim(h->hist_cfg);
+}
+
+int mocca_history(mocca_handle h, const float* rows_dev, int row_stride, const float* act_dev, int act_stride, float* out_dev, int out_stride,
+                  void* stream) {
+  if (!h) return MOCCA_E_ARG;
+  const mocca_hist::HistConfig& cfg = h->hist_cfg;
+  if (cfg.steps == 0) { h->err = "mocca_history needs a history (mocca_set_history)"; return MOCCA_E_ARG; }
+  if (!rows_dev || !out_dev) { h->err = "mocca_history: rows_dev or out_dev is NULL"; return MOCCA_E_ARG; }
+  if (row_stride < h->obs_dim) { h->err = "mocca_history: row_stride must be at least obs_dim (" + std::to_string(h->obs_dim) + ")"; return MOCCA_E_ARG; }
+  if (out_stride < mocca_hist::hist_dim(cfg)) {
+    h->err = "mocca_history: out_stride must be at least the block width (" + std::to_string(mocca_hist::hist_dim(cfg)) + ")"; return MOCCA_E_ARG;
+  }
+  if (act_dev && act_stride < cfg.act_dim) {
+    h->err = "mocca_history: act_stride must be at least the history's act_dim (" + std::to_string(cfg.act_dim) + ")"; return MOCCA_E_ARG;
+  }
+  DeviceGuard guard(h->device);
+  mocca_hist::HistArgs a{cfg, h->d_task, MOCCA_TASK_WORDS, MOCCA_TW_T, MOCCA_TW_EPISODE, h->n_envs, h->d_hist_cols, h->d_hist_ring, h->d_hist_tags,
+                         rows_dev, act_dev, out_dev, row_stride, act_stride, out_stride};
+  mocca_hist::launch_history((hipStream_t)stream, a);
   HIP_TRY(h, hipGetLastError());
   return MOCCA_OK;
 }

@@ -201,6 +201,13 @@ class _Parts:
     def randomisation_record(self, *a, **k):
         self._one_handle("randomisation_record")
 
+    # ---- ... and the history's ring ----
+    def set_history(self, *a, **k):
+        self._one_handle("set_history")
+
+    def history(self, *a, **k):
+        self._one_handle("history")
+
     def set_state(self, st) -> None:
         st = torch.as_tensor(st, dtype=torch.float32).reshape(self.n_envs, self.state_dim)
         for e, sl in zip(self.parts, self.slices):

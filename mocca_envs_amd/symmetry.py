@@ -35,13 +35,17 @@ def _table(dim, neg, right, left, what):
     return perm, sign
 
 
-def mirror_tables(mirror_indices, obs_dim: int, act_dim: int, scan_points=None, depth_shape=None):
+def mirror_tables(mirror_indices, obs_dim: int, act_dim: int, scan_points=None, depth_shape=None, history=None):
     """-> (in_perm int32 [in_dim], in_sign float32 [in_dim], act_perm int32 [act_dim], act_sign float32 [act_dim]) in `MirrorTransform`'s
     convention, (M x)[k] = sign[k] * x[perm[k]]: perm swaps the right and left sets, sign is -1 on the neg set.  `mirror_indices`: the six
     lists of `get_mirror_indices()`.  With `scan_points` [n, 2] (a perception pattern: x ahead, y to the left) the input is [obs | scan],
     in_dim = obs_dim + n: scan entry p maps to the point at (px, -py) with sign +1, a point with py == 0 to itself; a point whose reflection
     is not in the pattern (to 1e-6 m) is a ValueError.  With `depth_shape` (H, W) (a perception.DepthCamera in the robot's sagittal plane)
     an H x W depth image follows, [obs | scan | depth]: entry (j, i), at j * W + i of the block, maps to (j, W - 1 - i) with sign +1.  The
+    With `history` = (columns, hist_act_dim, steps) (a history.History as the env resolved it) the block of `steps` pairs
+    [obs[columns] | action] follows, [obs | scan | depth | hist]: in every pair, observation entry p (column columns[p]) maps to the
+    position in `columns` of in_perm[columns[p]], with that column's sign -- a ValueError, naming the column, if the set of columns is not
+    closed under the mirror --; the action entries map through act_perm / act_sign (`hist_act_dim` must be 0 or `act_dim`).  The
     tables are checked (check_tables)."""
     if isinstance(mirror_indices, dict) or len(mirror_indices) != 6:
         raise ValueError("mirror_indices must be the six lists (neg_obs, right_obs, left_obs, neg_act, right_act, left_act) of get_mirror_indices()")
@@ -70,6 +74,28 @@ def mirror_tables(mirror_indices, obs_dim: int, act_dim: int, scan_points=None, 
         flip = (np.arange(H)[:, None] * W + (W - 1 - np.arange(W))[None, :]).reshape(-1)
         in_perm = np.concatenate([in_perm, (len(in_perm) + flip).astype(np.int32)])
         in_sign = np.concatenate([in_sign, np.ones(H * W, np.float32)])
+    if history is not None:
+        cols, hist_act, steps = history
+        cols, hist_act, steps = [int(c) for c in np.asarray(cols).reshape(-1)], int(hist_act), int(steps)
+        if hist_act not in (0, int(act_dim)):
+            raise ValueError(f"the history holds {hist_act} action entries per frame: the mirror needs 0 or the policy's act_dim ({int(act_dim)})")
+        where = {c: p for p, c in enumerate(cols)}
+        pair_perm, pair_sign = [], []
+        for c in cols:
+            if not 0 <= c < int(obs_dim):
+                raise ValueError(f"history column {c} is outside 0 .. {int(obs_dim) - 1}")
+            if int(in_perm[c]) not in where:
+                raise ValueError(f"history column {c} mirrors to column {int(in_perm[c])}, which the history does not hold: "
+                                 "the columns are not closed under the mirror")
+            pair_perm.append(where[int(in_perm[c])])
+            pair_sign.append(in_sign[c])
+        if hist_act:
+            pair_perm += [len(cols) + int(a) for a in act_perm]
+            pair_sign += list(act_sign)
+        pair_perm, width = np.asarray(pair_perm, np.int64), len(cols) + hist_act
+        base = len(in_perm) + width * np.arange(steps)[:, None]
+        in_perm = np.concatenate([in_perm, (base + pair_perm[None, :]).reshape(-1).astype(np.int32)])
+        in_sign = np.concatenate([in_sign, np.tile(np.asarray(pair_sign, np.float32), steps)])
     return check_tables((in_perm, in_sign, act_perm, act_sign))
 
 

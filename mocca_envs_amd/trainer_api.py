@@ -213,12 +213,19 @@ class TorchVecEnv:
     the `into=` row of the trainer's storage -- gets uniform noise added in place to its first obs_dim columns, one launch BEHIND the sensor
     launches, which stay in their order: `envs.privileged` is refreshed first, from the clean observation.  With `privileged=True` (needs
     `privileged_scan=`) the privileged row is [obs | scan | record] and `envs.randomisation` is its tail: a privileged critic or a teacher
-    knows the plant, the actor does not."""
+    knows the plant, the actor does not.
+    `history=history.History(steps, stride, columns, actions)` (one handle): the observation-action history (include/mocca.h mocca_history)
+    becomes the tail of the row, [obs | scan | depth | hist]: `observation_space` grows by `envs.venv.history_dim`, and reset() / step() /
+    step(into=...) / act_step() / capture_rollout fill it.  The history launch is the LAST one of a reset or step, behind the sensors and
+    behind the sensor noise, on the policy's row itself: its frames hold what the policy actually saw (noisy with `obs_noise`;
+    `envs.privileged` is not changed).  The action of a frame is what the policy output on it: reset() passes none, step(actions) the tensor it
+    handed to the launch, act_step() the policy's action output (`into["action"]` or this object's own buffer).  Without a scan or a camera
+    the observation reaches the wide row through the sensor-noise launch where there is one, else through one device copy."""
 
     def __init__(self, env_id: str, num_envs: int, seed: int = 0, device: Optional[int] = None, sub_batches: int = 1,
                  terminal_observation: bool = False, record_slots: int = 8, eager_done: bool = False, record_events: bool = True,
                  height_scan: Optional[dict] = None, terrain_bank: Optional[dict] = None, depth_camera=None,
-                 privileged_scan: Optional[dict] = None, randomisation=None, **kw):
+                 privileged_scan: Optional[dict] = None, randomisation=None, history=None, **kw):
         if randomisation is not None and randomisation.privileged and privileged_scan is None:
             raise ValueError("Randomisation(privileged=True) puts the plant's record behind [obs | scan]: that takes privileged_scan=")
         if randomisation is not None and sub_batches > 1:
@@ -227,7 +234,7 @@ class TorchVecEnv:
             raise ValueError("height_scan= puts the scan into the observation row, privileged_scan= keeps it out of it: one of the two")
         sensors = [name for name, arg in (("privileged_scan", privileged_scan), ("depth_camera", depth_camera), ("height_scan", height_scan))
                    if arg is not None]
-        for name in sensors:             # refused before anything touches a device
+        for name in sensors + (["history"] if history is not None else []):             # refused before anything touches a device
             if terminal_observation:
                 raise NotImplementedError(f"{name} with terminal_observation=True: the sensor runs after the step's launch, when an env that "
                                           "finished already holds its next episode's first state -- the terminal state is gone, so nothing of it "
@@ -238,7 +245,7 @@ class TorchVecEnv:
                                  **({"device": device} if device is not None else {}), **kw)
         self.env_id, self.num_envs = env_id, int(num_envs)
         self.device = self.venv.device
-        for name in sensors + (["terrain_bank"] if terrain_bank is not None else []) + (["randomisation"] if randomisation is not None else []):    # (several devices are no single handle either)
+        for name in sensors + (["terrain_bank"] if terrain_bank is not None else []) + (["randomisation"] if randomisation is not None else []) + (["history"] if history is not None else []):    # (several devices are no single handle either)
             self._one(name)
         self._terrain = None
         if terrain_bank is not None:
@@ -272,9 +279,13 @@ class TorchVecEnv:
         if depth_camera is not None:
             self.venv.set_depth_camera(depth_camera)
             self._depth = self.venv.depth_dim
-        if self._scan or self._depth:
-            self._wide = torch.zeros(self.num_envs, self.venv.obs_dim + self._scan + self._depth, dtype=torch.float32, device=self.device)
-        high = np.inf * np.ones(self.venv.obs_dim + self._scan + self._depth, dtype=np.float32)
+        self._hist = 0
+        if history is not None:
+            self.venv.set_history(history)
+            self._hist = self.venv.history_dim
+        if self._scan or self._depth or self._hist:
+            self._wide = torch.zeros(self.num_envs, self.venv.obs_dim + self._scan + self._depth + self._hist, dtype=torch.float32, device=self.device)
+        high = np.inf * np.ones(self.venv.obs_dim + self._scan + self._depth + self._hist, dtype=np.float32)
         self.observation_space = gym_shim.Box(-high, high, dtype=np.float32)                      # robots.py:18-29, env_locomotion.py:58-60
         self.action_space = gym_shim.Box(-np.ones(self.venv.act_dim, np.float32), np.ones(self.venv.act_dim, np.float32), dtype=np.float32)
         # a planner env with its base controller attached (base_controller=...): the action is the 15-number plan (unbounded box,
@@ -355,7 +366,7 @@ class TorchVecEnv:
     def reset(self) -> torch.Tensor:
         obs = self.venv.reset()        # (the reset kernel zeroes the envs' running returns: Monitor.reset)
         self._refresh_privileged(obs)
-        return self._noise(obs if self._wide is None else self._widen(obs, self._wide))
+        return self._noise(obs) if self._wide is None else self._row(obs, self._wide, None)
 
     def _refresh_privileged(self, obs):
         """privileged_scan=: the row [obs | scan] of the state the envs are in now into `self.privileged`, one launch on the step's stream;
@@ -373,8 +384,21 @@ class TorchVecEnv:
         """randomisation= with obs_noise: the sensor noise onto the head of the policy's row, in place, behind every sensor launch"""
         return self.venv.sensor_noise(row) if self._noisy else row
 
+    def _row(self, obs, wide, act):
+        """the policy's wide row [obs | scan | depth | hist] into `wide`: the sensors, the sensor noise on the row's head, then -- last, on what
+        the policy will read -- the history, whose previous frame takes `act` (None: a reset)"""
+        if self._scan or self._depth:
+            self._noise(self._widen(obs, wide))
+        elif self._noisy:              # no sensor copies the observation: the noise launch writes the noisy head straight into the row
+            self.venv.sensor_noise(obs, out=wide)
+        else:
+            wide[:, :self.venv.obs_dim].copy_(obs)
+        if self._hist:
+            self.venv.history(wide, act, out=wide[:, wide.shape[1] - self._hist:])
+        return wide
+
     def _widen(self, obs, wide):
-        """the wide row [obs | scan | depth] into `wide`: one launch per sensor, the first of them copies the observation"""
+        """the sensors' part [obs | scan | depth] of the wide row into `wide`: one launch per sensor, the first of them copies the observation"""
         if self._scan:
             self.venv.height_scan(out=wide, obs=obs)
             if self._depth:
@@ -384,10 +408,10 @@ class TorchVecEnv:
         return wide
 
     def _step_obs(self, actions, obs_out=None, rew_out=None, launch=None):
-        """the step's launch and, with a height scan or a depth camera, the launches that write the wide row [obs | scan | depth] (into
+        """the step's launch and, with a height scan, a depth camera or a history, the launches that write the wide row [obs | scan | depth | hist] (into
         `obs_out` or this object's own buffer; the step's own observation stays in the handle's buffer) -> (obs, reward).  `launch`: what steps instead of step() /
         plan_step() (act_step: `actions` is then the policy's input row)"""
-        launch = launch or self._venv_step
+        act_launch, launch = launch, launch or self._venv_step
         if self._wide is None:
             if obs_out is None and rew_out is None:      # (the sub-batched step takes the actions only)
                 o, r = launch(actions)[:2]
@@ -397,10 +421,12 @@ class TorchVecEnv:
             return self._noise(o), r
         wide = self._wide if obs_out is None else obs_out
         if wide.shape != self._wide.shape or not wide.is_contiguous():
-            raise ValueError("with a height scan or a depth camera the observation rows are contiguous float32 [n_envs, obs_dim + scan_dim + depth_dim]")
+            raise ValueError("with a height scan, a depth camera or a history the observation rows are contiguous float32 "
+                             "[n_envs, obs_dim + scan_dim + depth_dim + history_dim]")
         o, r = launch(actions, rew_out=rew_out)[:2]
         self._refresh_privileged(o)
-        return self._noise(self._widen(o, wide)), r
+        # the action of the frame the policy acted on: step()'s tensor, or what act_step's policy launch wrote
+        return self._row(o, wide, (actions if act_launch is None else self.last_act["action"]) if self._hist else None), r
 
     def step(self, actions: torch.Tensor, into: Optional[dict] = None):
         """`into` (one handle only): {"obs": [N, obs_dim], "reward": [N, 1], "masks": [N, 1], "bad_masks": [N, 1]} -- any subset -- tensors of the

@@ -111,6 +111,8 @@ class VecEnv:
     """
 
     randomisation = None    # set_randomisation(): the attached randomisation.Randomisation
+    hist = None             # set_history(): the attached history.History, and what it resolved to on this env
+    _hist_cols, _hist_act = None, 0
 
     def __init__(self, env_id: str = "Walker3DCustomEnv-v0", n_envs: int = 1, device: Optional[int] = None,
                  auto_reset: bool = True, seed: int = 0, model_blob: Optional[bytes] = None, env_offset: int = 0,
@@ -507,15 +509,22 @@ class VecEnv:
     def policy_mirror_tables(self, policy):
         """The mirror tables (in_perm, in_sign, act_perm, act_sign) of THIS env for `policy` (a `policy.DevicePolicy`): built from
         get_mirror_indices() and, where the policy's input is [obs | scan], [obs | depth] or [obs | scan | depth], the attached scan pattern and
-        the attached depth camera's shape (symmetry.mirror_tables; ValueError for a camera outside the robot's sagittal plane).  Envs whose
-        reference publishes no six index lists raise NotImplementedError."""
+        the attached depth camera's shape (symmetry.mirror_tables; ValueError for a camera outside the robot's sagittal plane).  With a
+        history attached (set_history) the policy's input must be the FULL row [obs | scan | depth | hist] of whatever is attached, and the
+        tables cover the history block too.  Envs whose reference publishes no six index lists raise NotImplementedError."""
         from .symmetry import mirror_tables
         mi = self.get_mirror_indices()
         if isinstance(mi, dict):
             raise NotImplementedError("the Cassie mocap envs publish a dict of index lists (env_cassie.py:554-571), not get_mirror_indices()'s six")
         scan, cam = self._scan_points, self._depth_cam
         ns, nd = (0 if scan is None else len(scan)), (0 if cam is None else cam.width * cam.height)
-        if policy.in_dim == self.obs_dim:                                       # [obs]
+        hist = None if self.hist is None else (self._hist_cols, self._hist_act, self.hist.steps)
+        if hist is not None:                                                    # [obs | scan | depth | hist]: the full row, nothing else
+            if policy.in_dim != self.obs_dim + ns + nd + self.history_dim:
+                raise ValueError(f"the policy's input has {policy.in_dim} entries: with a history attached it must be the full row, the env's "
+                                 f"observation {self.obs_dim}" + ("" if scan is None else f", its height scan {ns}")
+                                 + ("" if cam is None else f", its depth image {nd}") + f" and its history {self.history_dim}")
+        elif policy.in_dim == self.obs_dim:                                     # [obs]
             scan = cam = None
         elif scan is not None and cam is not None and ns == nd and policy.in_dim == self.obs_dim + ns:
             raise ValueError(f"the policy's input has {policy.in_dim} entries: [obs | scan] and [obs | depth] are both {self.obs_dim} + {ns} wide here; "
@@ -530,7 +539,7 @@ class VecEnv:
         if cam is not None and not cam.sagittal:
             raise ValueError("the depth camera does not lie in the robot's sagittal plane (body 0, offset[1] == 0, yaw == roll == 0): "
                              "the mirrored robot does not see the column-flipped image")
-        return mirror_tables(mi, self.obs_dim, policy.act_dim, scan_points=scan, depth_shape=None if cam is None else cam.shape)
+        return mirror_tables(mi, self.obs_dim, policy.act_dim, scan_points=scan, depth_shape=None if cam is None else cam.shape, history=hist)
 
     def symmetric_policy(self, policy):
         """A copy of `policy` (a `policy.DevicePolicy`) with the mirror tables of THIS env (policy_mirror_tables)."""
@@ -1281,6 +1290,44 @@ class VecEnv:
                 or out.stride(1) != 1 or (self.n_envs > 1 and out.stride(0) < w):
             raise ValueError(f"out must be a float32 [n_envs, >= {w}] tensor on the env's device with contiguous rows")
         self._call(self.lib.mocca_randomisation_record, out, int(out.stride(0) if self.n_envs > 1 else max(out.stride(0), w)))
+        return out if out.shape[1] == w else out[:, :w]
+
+    # ---- the observation-action history (include/mocca.h mocca_set_history / mocca_history; history.History) ----
+    def set_history(self, hist) -> None:
+        """Attach a `history.History` (None detaches): history() then writes the last `steps` pairs [obs[columns] | action] of every env,
+        newest first.  `actions=True` takes this env's action width -- the plan's on a planner env with its base controller.  May allocate
+        and synchronise; history() never does."""
+        if hist is None:
+            _lib.check(self.lib.mocca_set_history(self.h, None, 0, 0, 0, 0), self.h)
+            self.hist, self._hist_cols, self._hist_act = None, None, 0
+            return
+        plan = getattr(self, "base_controller", None) is not None
+        cols, a = hist.resolve(self.obs_dim, self.plan_dim if plan else self.act_dim)      # (refused before the handle changes)
+        _lib.check(self.lib.mocca_set_history(self.h, cols.ctypes.data_as(C.c_void_p), int(cols.size), a, hist.steps, hist.stride), self.h)
+        self.hist, self._hist_cols, self._hist_act = hist, cols, a
+
+    @property
+    def history_dim(self) -> int:
+        """floats of the attached history's block, steps * (columns + actions); 0 when there is none"""
+        return 0 if self.hist is None else int(self.lib.mocca_history_dim(self.h))
+
+    def history(self, rows: torch.Tensor, act: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Store the frame of `rows` (float32 [N, >= obs_dim] with contiguous rows: what the policy reads NOW), complete the previous frame
+        with `act` (float32 [N, >= the history's action width]: the action the policy output on the previous row; None after a reset) and
+        write the block [N, history_dim], newest pair first, one launch, nothing synchronises: into `out` (float32 [N, >= history_dim] with
+        contiguous rows -- a view of the tail of `rows` itself will do; floats beyond the block are left untouched), or into a new tensor.
+        Keyed by the envs' step and episode counters: two calls without a step in between write and return the same words."""
+        if self.hist is None:
+            raise _lib.MoccaError("history needs a History (set_history)")
+        w, n = self.history_dim, self.n_envs
+        if out is None:
+            out = torch.empty(n, w, dtype=torch.float32, device=self.device)
+        for name, t, least in (("rows", rows, self.obs_dim), ("act", act, self._hist_act), ("out", out, w)):
+            if t is not None and (t.dim() != 2 or t.shape[0] != n or t.shape[1] < least or t.dtype != torch.float32 or t.device != self.device
+                                  or (t.shape[1] > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < t.shape[1])):
+                raise ValueError(f"{name} must be a float32 [n_envs, >= {least}] tensor on the env's device with contiguous rows")
+        stride = lambda t: int(t.stride(0) if n > 1 else max(t.stride(0), t.shape[1]))
+        self._call(self.lib.mocca_history, rows, stride(rows), act, 0 if act is None else stride(act), out, stride(out))
         return out if out.shape[1] == w else out[:, :w]
 
     def kernel_info(self) -> dict:

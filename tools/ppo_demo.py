@@ -13,6 +13,7 @@ No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it Symme
                            [--base-controller FILE] [--height-scan NX,NY] [--depth-camera W,H]
                            [--distill-from TEACHER.npz --privileged-scan NX,NY] [--privileged-critic --privileged-scan NX,NY]
                            [--rand-strength LO,HI] [--rand-latency LO,HI] [--rand-push INTERVAL,MAX] [--obs-noise SCALE] [--rand-privileged]
+                           [--history K[,S]]
 --base-controller FILE (required for the planner ids, Walker3DPlannerEnv-v0 / MikePlannerEnv-v0): ALLSTEPS's second step.  FILE is a
 `BaseController.save_npz` file or the <out>_policy.npz of an earlier run of this script on a Stepper id (told apart by the keys; the latter
 brings its observation statistics along); it is frozen as the env's base controller and the policy trained here emits 15-number plans.
@@ -73,6 +74,11 @@ steps, every INTERVAL steps the base is pushed by up to MAX m/s, and uniform noi
 critic's privileged row stays clean).  Every arm works: the randomisation acts on what the step kernel reads and writes, whoever produced the
 action.  --rand-privileged (with --privileged-critic): the privileged row becomes [obs | scan | record], the critic knows the plant.
 <out>_policy.npz records the randomisation the policy was trained under (`randomisation`, a JSON string).
+--history K[,S]: the observation-action history through `make_vec_envs(history=History(K, S))`, all observation columns plus the actions: the
+policy's row ends in the K pairs [obs | action] it read and output S, 2 S, .. K S steps ago (newest first; include/mocca.h mocca_history), so
+that the actor can tell the plant it has from what its commands did.  Every arm works (the row is just wider; --symmetric takes the env's
+extended mirror tables); not with --mirror-loss / --mirror-dup, whose torch side mirrors with get_mirror_indices() alone.
+<out>_policy.npz records the history (`history`, a JSON string): tools/randomisation_eval.py rebuilds the env with it.
 --verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor
 (--mirror-dup: on that minibatch's rows whose ratio and whose twin's ratio lie more than 1e-4 from the clip bounds, where the surrogate's
 gradient jumps and two float32 evaluations may disagree on a sample's side; the twins' ratios are spread over the bounds); with
@@ -130,6 +136,7 @@ def main(argv=None):
     ap.add_argument("--rand-push", default=None, metavar="INTERVAL,MAX", help="every INTERVAL steps the base's velocity jumps by up to MAX m/s along x and y")
     ap.add_argument("--obs-noise", type=float, default=None, metavar="SCALE", help="uniform noise of this half-width on every column of the policy's observation row")
     ap.add_argument("--rand-privileged", action="store_true", help="with --privileged-critic: the plant's record joins the critic's row, [obs | scan | record]")
+    ap.add_argument("--history", default=None, metavar="K[,S]", help="append the last K (observation, action) pairs, S steps apart (default 1), to the policy's row")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args(argv)
     if args.device_grad and not args.device_returns:
@@ -180,6 +187,13 @@ def main(argv=None):
         rand = Randomisation(strength=pair(args.rand_strength, (float, float), (1.0, 1.0)), latency=pair(args.rand_latency, (int, int), (0, 0)),
                              push=pair(args.rand_push, (int, float), (0, 0.0)), obs_noise=args.obs_noise, privileged=args.rand_privileged)
         extra["randomisation"] = rand
+    hist = None
+    if args.history is not None:
+        if args.mirror_loss is not None or args.mirror_dup:
+            ap.error("--history is not for --mirror-loss / --mirror-dup: their torch side mirrors with get_mirror_indices() alone")
+        from mocca_envs_amd.history import History
+        hist = History(*(int(v) for v in args.history.split(",")))
+        extra["history"] = hist
     if args.base_controller is not None:
         from mocca_envs_amd.controller import BaseController
         extra["base_controller"] = BaseController.load(args.base_controller)
@@ -200,8 +214,8 @@ def main(argv=None):
     envs = make_vec_envs(args.env_id, seed=args.seed, num_processes=args.envs, record_events=False, **extra)
     dev, N, T = envs.device, args.envs, args.steps
     od, ad = envs.observation_space.shape[0], envs.action_space.shape[0]
-    if args.depth_camera is not None and od > 336:
-        raise SystemExit(f"--depth-camera {args.depth_camera}: the observation row would have {od} entries, the policy kernel takes at most 336")
+    if (args.depth_camera is not None or hist is not None) and od > 336:
+        raise SystemExit(f"--depth-camera {args.depth_camera} / --history {args.history}: the observation row would have {od} entries, the policy kernel takes at most 336")
 
     def mlp(i, o, gain):
         net = nn.Sequential(nn.Linear(i, 256), nn.Tanh(), nn.Linear(256, 256), nn.Tanh(), nn.Linear(256, o)).to(dev)
@@ -552,7 +566,8 @@ def main(argv=None):
              **{f"pi_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in pi.state_dict().items()},
              **{f"vf_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in vf.state_dict().items()},
              env_id=np.array(args.env_id), env_steps=np.array(total_steps), **extra_stats,
-             **({} if rand is None else dict(randomisation=np.array(json.dumps(rand.as_dict())))))
+             **({} if rand is None else dict(randomisation=np.array(json.dumps(rand.as_dict())))),
+             **({} if hist is None else dict(history=np.array(json.dumps(hist.as_dict())))))
     envs.close()
 
 

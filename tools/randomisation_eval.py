@@ -8,7 +8,8 @@ sensors -- or none, the plain plant.
 
 Per policy every env plays ONE episode with the mean action (no action noise; the sensor noise of the condition is applied): mean return and
 mean length over the envs, one JSON line per policy, appended to --out, with the condition and the randomisation the policy's file says it
-was trained under.  Reported, not gated.
+was trained under.  A policy trained with an observation-action history (ppo_demo.py --history; its file records the `History`) plays on
+an env rebuilt with the same history: its rows are [obs | hist] again.  Reported, not gated.
 """
 from __future__ import annotations
 
@@ -57,7 +58,12 @@ def main(argv=None):
             x = torch.tanh(x @ w["pi_0_weight"].T + w["pi_0_bias"])
             x = torch.tanh(x @ w["pi_2_weight"].T + w["pi_2_bias"])
             return x @ w["pi_4_weight"].T + w["pi_4_bias"]
-        envs = make_vec_envs(args.env_id, seed=args.seed, num_processes=n, record_events=False, **({} if rand is None else dict(randomisation=rand)))
+        hist = None
+        if "history" in z.files:     # the sensor setting stored beside the policy
+            from mocca_envs_amd.history import History
+            hist = History.from_dict(json.loads(str(z["history"])))
+        envs = make_vec_envs(args.env_id, seed=args.seed, num_processes=n, record_events=False, **({} if rand is None else dict(randomisation=rand)),
+                             **({} if hist is None else dict(history=hist)))
         obs = envs.reset()
         alive = torch.ones(n, device=dev)
         ret, length = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
@@ -72,7 +78,8 @@ def main(argv=None):
         line = {"policy": name, "condition": condition, "envs": n, "mean_return": float(ret.mean()), "mean_length": float(length.mean()),
                 "unfinished": int(alive.sum()), "trained_env_steps": int(z["env_steps"]),
                 "evaluated_under": None if rand is None else rand.as_dict(),
-                "trained_under": json.loads(str(z["randomisation"])) if "randomisation" in z.files else None}
+                "trained_under": json.loads(str(z["randomisation"])) if "randomisation" in z.files else None,
+                "history": None if hist is None else hist.as_dict()}
         print(json.dumps(line), flush=True)
         if args.out:
             with open(args.out, "a") as f:
