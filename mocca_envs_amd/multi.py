@@ -166,47 +166,11 @@ class _Parts:
             return rgb
         return tuple(x for x, on in ((rgb, True), (dep, depth), (idt, ids)) if on)
 
-    # ---- the terrain bank lives in ONE handle's device memory ----
-    def _one_handle(self, what: str):
-        raise NotImplementedError(f"{what} needs one handle (one device, sub_batches=1)")
-
-    def set_heightfield_bank(self, *a, **k):
-        self._one_handle("set_heightfield_bank")
-
-    def generate_heightfields(self, *a, **k):
-        self._one_handle("generate_heightfields")
-
-    def set_env_fields(self, *a, **k):
-        self._one_handle("set_env_fields")
-
-    def env_fields(self):
-        self._one_handle("env_fields")
-
-    def height_fields(self, *a, **k):
-        self._one_handle("height_fields")
-
-    # ---- ... and so do the randomisation's effective actions, its ring and its scales ----
-    def set_randomisation(self, *a, **k):
-        self._one_handle("set_randomisation")
-
-    def effective_action(self):
-        self._one_handle("effective_action")
-
-    def set_sensor_noise(self, *a, **k):
-        self._one_handle("set_sensor_noise")
-
-    def sensor_noise(self, *a, **k):
-        self._one_handle("sensor_noise")
-
-    def randomisation_record(self, *a, **k):
-        self._one_handle("randomisation_record")
-
-    # ---- ... and the history's ring ----
-    def set_history(self, *a, **k):
-        self._one_handle("set_history")
-
-    def history(self, *a, **k):
-        self._one_handle("history")
+    # What lives in ONE handle's device memory -- the terrain bank; the randomisation's effective actions, its ring and its scales; the
+    # history's ring -- is refused here: the stubs are made from this list, below the class
+    ONE_HANDLE = ("set_heightfield_bank", "generate_heightfields", "set_env_fields", "env_fields", "height_fields",
+                  "set_randomisation", "effective_action", "set_sensor_noise", "sensor_noise", "randomisation_record",
+                  "set_history", "history")
 
     def set_state(self, st) -> None:
         st = torch.as_tensor(st, dtype=torch.float32).reshape(self.n_envs, self.state_dim)
@@ -216,6 +180,18 @@ class _Parts:
     def set_task(self, t: torch.Tensor) -> None:
         for e, sl in zip(self.parts, self.slices):
             e.set_task(t[sl])
+
+
+def _refusal(name: str):
+    def method(self, *a, **k):
+        raise NotImplementedError(f"{name} needs one handle (one device, sub_batches=1)")
+    method.__name__, method.__qualname__ = name, f"_Parts.{name}"
+    method.__doc__ = f"`VecEnv.{name}` needs one handle: refused."
+    return method
+
+
+for _name in _Parts.ONE_HANDLE:
+    setattr(_Parts, _name, _refusal(_name))
 
 
 class SubBatchedVecEnv(_Parts):

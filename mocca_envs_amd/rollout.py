@@ -121,6 +121,14 @@ def gae_args(n_envs, device, reward, value, masks, bad_masks, gamma, lam, reward
     return T
 
 
+def _row_stride(n: int, stride: int, cols: int):
+    """THE row-stride rule, for `n` rows of `cols` floats, `stride` floats apart -> the stride to hand to a kernel, None where rows
+    overlap.  One row's stride never indexes anything, but the C side checks stride >= width: it is the row's own length at least."""
+    if n == 1:
+        return max(stride, cols)
+    return stride if stride >= cols else None
+
+
 def rows_2d(rows, dim: int):
     """rows [..., >= dim] with contiguous last dimension and one stride between consecutive rows -> (n_rows, row_stride in floats)"""
     import torch
@@ -130,16 +138,29 @@ def rows_2d(rows, dim: int):
     lead = [(int(n), int(s)) for n, s in zip(rows.shape[:-1], rows.stride()[:-1]) if n != 1]
     if any(n == 0 for n, _ in lead):
         raise ValueError("rows must hold at least one row")
-    stride = lead[-1][1] if lead else int(rows.shape[-1])
     for (n0, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
         if s0 != n1 * s1:
             raise ValueError("rows must have one uniform stride between consecutive rows (a slice of contiguous storage along the first axis will do)")
-    if stride < dim:
-        raise ValueError(f"the row stride ({stride}) is smaller than dim ({dim})")
     n_rows = 1
     for n, _ in lead:
         n_rows *= n
+    stride = _row_stride(n_rows, lead[-1][1] if lead else 0, int(rows.shape[-1]))
+    if stride is None:
+        raise ValueError(f"the row stride ({lead[-1][1]}) is smaller than the rows ({rows.shape[-1]}): they overlap")
     return n_rows, stride
+
+
+def row_view(name: str, t, width: int, n_rows, device) -> int:
+    """THE rule for "a float32 [n, >= width] tensor on `device` with contiguous rows" (a view of wider storage will do), for every call
+    that hands such rows to a kernel: two dimensions, `n_rows` rows (None: any n >= 1), stride(1) == 1 unless there is one column, no
+    overlapping rows -> the row stride in floats (_row_stride).  `name`: what the ValueError calls the tensor."""
+    import torch
+    if isinstance(t, torch.Tensor) and t.dim() == 2 and t.dtype == torch.float32 and t.device == device:
+        (n, cols), (s0, s1) = t.shape, t.stride()
+        stride = _row_stride(n, s0, cols)
+        if (n == n_rows if n_rows else n >= 1) and cols >= width and (cols <= 1 or s1 == 1) and stride is not None:
+            return stride
+    raise ValueError(f"{name} must be a float32 [{'n_envs' if n_rows else 'n'}, >= {width}] tensor on the env's device with contiguous rows")
 
 
 MAX_MINIBATCH = 1 << 22   # include/mocca.h mocca_ppo_grad

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import inspect
 import weakref
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -180,6 +181,21 @@ class _Infos:
         return self._finished().items()
 
 
+# What TorchVecEnv's constructor decides once about its rows: `policy` and `privileged`, the blocks of the two rows in order as
+# {name: (offset, width)} (empty: no such row), and `launches`, the calls (o, row, act) that follow a reset's or a step's launch, in order
+_RowPlan = namedtuple("_RowPlan", "policy privileged launches")
+
+
+def _blocks(*named) -> dict:
+    """(name, width) pairs laid end to end -> {name: (offset, width)}, in order, without the empty ones"""
+    out, at = {}, 0
+    for name, width in named:
+        if width:
+            out[name] = (at, width)
+            at += width
+    return out
+
+
 class TorchVecEnv:
     """`VecPyTorch`-shaped env batch on one MI355X (module docstring).  kwargs go to the env class (`plank_class=...`) / `VecEnv`
     (`max_rows=...`); `sub_batches=k` steps the batch as k sub-batches on their own HIP streams (`multi.SubBatchedVecEnv`).
@@ -189,38 +205,40 @@ class TorchVecEnv:
     drops the per-step event (for loops that read `masks` / `episode_totals` only).  `terminal_observation=True` gives every record slot
     terminal-observation rows of its own (launch k writes slot k % record_slots), so `infos[i]["terminal_observation"]` is the final
     observation of THAT step's episode however late it is read.
-    `height_scan=dict(points=[P, 2], z_above=1.0, max_drop=2.0)` (perception.scan_grid builds patterns) appends the terrain height scan to
-    every observation: `observation_space` grows by P, and reset() / step() / step(into=...) / capture_rollout return and fill rows
-    [obs | scan] -- the step kernel's launch, then ONE more (include/mocca.h mocca_height_scan, which copies the observation into the wide row
-    itself): no torch.cat, no copy or synchronise on the host.  Under auto-reset the scan, like the observation, belongs to the new episode's
-    first state.
-    `depth_camera=perception.DepthCamera(...)` appends the egocentric depth image (include/mocca.h mocca_depth_camera) the same way:
-    `observation_space` grows by width * height, rows are [obs | depth] -- or [obs | scan | depth] with a height scan too, one more launch
-    each -- in reset() / step() / step(into=...) / capture_rollout and as act_step()'s input rows.
     `terrain_bank=dict(n_fields=K, seed=S, n_peaks=256, gain=1.0, redraw_at_reset=True)` (planner ids): a bank of K random height fields of
     the shipped shape (128 x 128 points, 4 per metre) generated on the device before the first reset (include/mocca.h
     mocca_generate_heightfields), every env on one of them -- with `redraw_at_reset` another one in every episode; refresh_terrain(seed)
     regenerates the bank in place.  Without it the envs stand on the shipped map, as ever.
-    `privileged_scan=dict(points=[P, 2], z_above=1.0, max_drop=2.0)` (teacher-student distillation; not together with `height_scan=`): the
-    scan is attached to the handle but NOT appended to the observation row -- rows stay [obs] or [obs | depth] -- and `envs.privileged`
-    [N, obs_dim + P] holds [obs | scan], the row a teacher trained with `height_scan=` saw, refreshed by one more height-scan launch after
-    every reset and step, on the step's stream.  `attach_teacher(policy)` / `teacher_targets(mean_out, value_out)` evaluate a frozen
-    teacher on it.
-    `randomisation=randomisation.Randomisation(...)` (one handle): domain randomisation on the device (include/mocca.h
-    mocca_set_randomisation) -- per-episode motor strength and action latency and random pushes act in front of every step (one more small
-    launch), `envs.effective_action()` tells what the step read; `envs.randomisation` [N, 4] is the record of every env's plant (strength,
-    delay, steps until the next push, 0), refreshed after every reset and step.  With `obs_noise` the POLICY's row -- this object's buffer or
-    the `into=` row of the trainer's storage -- gets uniform noise added in place to its first obs_dim columns, one launch BEHIND the sensor
-    launches, which stay in their order: `envs.privileged` is refreshed first, from the clean observation.  With `privileged=True` (needs
-    `privileged_scan=`) the privileged row is [obs | scan | record] and `envs.randomisation` is its tail: a privileged critic or a teacher
-    knows the plant, the actor does not.
-    `history=history.History(steps, stride, columns, actions)` (one handle): the observation-action history (include/mocca.h mocca_history)
-    becomes the tail of the row, [obs | scan | depth | hist]: `observation_space` grows by `envs.venv.history_dim`, and reset() / step() /
-    step(into=...) / act_step() / capture_rollout fill it.  The history launch is the LAST one of a reset or step, behind the sensors and
-    behind the sensor noise, on the policy's row itself: its frames hold what the policy actually saw (noisy with `obs_noise`;
-    `envs.privileged` is not changed).  The action of a frame is what the policy output on it: reset() passes none, step(actions) the tensor it
-    handed to the launch, act_step() the policy's action output (`into["action"]` or this object's own buffer).  Without a scan or a camera
-    the observation reaches the wide row through the sensor-noise launch where there is one, else through one device copy."""
+
+    THE ROWS.  Five options shape what the policy and a teacher or privileged critic read; each needs one handle, and each costs launches
+    behind the step's own, never a torch.cat, a host copy or a synchronise:
+    `height_scan=dict(points=[P, 2], z_above=1.0, max_drop=2.0)` (perception.scan_grid builds patterns): the terrain height scan (include/
+    mocca.h mocca_height_scan), P floats; `depth_camera=perception.DepthCamera(...)`: the egocentric depth image (mocca_depth_camera),
+    width * height floats; `history=history.History(steps, stride, columns, actions)`: the observation-action history (mocca_history),
+    `envs.venv.history_dim` floats; `privileged_scan=dict(...)` (teacher-student distillation; not together with `height_scan=`): the scan
+    attached but kept OUT of the policy's row; `randomisation=randomisation.Randomisation(...)`: domain randomisation (mocca_set_randomisation)
+    -- per-episode motor strength, action latency and random pushes in front of every step (one more small launch; `envs.effective_action()`
+    tells what the step read), with `obs_noise` uniform noise on what the policy sees, and a 4-float record of every env's plant (strength,
+    delay, steps until the next push, 0).
+    The POLICY's row is [obs | scan | depth | hist], each block only where its option is given: `observation_space` has its width, and
+    reset() / step() / step(into=...) / capture_rollout return and fill it, act_step() reads it.  With more than [obs] it is a wide buffer of
+    this object's, or `into["obs"]` of the trainer's storage; the step's own observation stays in the handle's buffer.
+    The PRIVILEGED row, `envs.privileged`, is [obs | scan | record] and exists with `privileged_scan=`: the row a teacher trained with
+    `height_scan=` saw (attach_teacher / teacher_targets evaluate a frozen teacher on it), the record only with
+    `Randomisation(privileged=True)`: a privileged critic or a teacher knows the plant, the actor does not.  `envs.randomisation` [N, 4] is
+    that tail, or a buffer of its own without `privileged=True`.
+    THE ORDER behind every reset and every step, whose launch has produced the observation `o`, on the step's stream (_plan_rows states it
+    as a list, once; a captured rollout bakes it into its graph):
+      1. the privileged scan: [obs | scan] into `envs.privileged`, from the CLEAN `o`;
+      2. the plant's record into `envs.randomisation`;
+      3. the policy's row: the height scan's launch copies `o` into the row and appends the scan, the camera's appends the depth image
+         (a camera alone copies `o` itself), then the sensor noise is added IN PLACE to the row's first obs_dim columns; with no block but
+         [obs] the noise lands on `o` itself, and with a history alone the noise launch writes the noisy `o` into the row -- one device
+         copy where there is no noise;
+      4. the history, last, on the row the policy will read (noisy with `obs_noise`; `envs.privileged` is not changed): its newest frame is
+         that row, and the previous frame takes the action the policy output on it -- none after reset(), the tensor step(actions) handed
+         to the launch, act_step()'s action output (`into["action"]` or this object's own buffer).
+    Under auto-reset all of it, like the observation, belongs to the new episode's first state."""
 
     def __init__(self, env_id: str, num_envs: int, seed: int = 0, device: Optional[int] = None, sub_batches: int = 1,
                  terminal_observation: bool = False, record_slots: int = 8, eager_done: bool = False, record_events: bool = True,
@@ -228,25 +246,23 @@ class TorchVecEnv:
                  privileged_scan: Optional[dict] = None, randomisation=None, history=None, **kw):
         if randomisation is not None and randomisation.privileged and privileged_scan is None:
             raise ValueError("Randomisation(privileged=True) puts the plant's record behind [obs | scan]: that takes privileged_scan=")
-        if randomisation is not None and sub_batches > 1:
-            raise NotImplementedError("randomisation needs one handle (sub_batches=1)")
         if height_scan is not None and privileged_scan is not None:
             raise ValueError("height_scan= puts the scan into the observation row, privileged_scan= keeps it out of it: one of the two")
-        sensors = [name for name, arg in (("privileged_scan", privileged_scan), ("depth_camera", depth_camera), ("height_scan", height_scan))
-                   if arg is not None]
-        for name in sensors + (["history"] if history is not None else []):             # refused before anything touches a device
-            if terminal_observation:
+        # what lives in ONE handle's device memory -- (option, given, runs behind the step's launch) -- refused before anything touches a device
+        parted = sub_batches > 1 or len(kw.get("devices") or ()) > 1      # (what make_vec_env cuts into sub-batches or shards)
+        for name, arg, behind in (("randomisation", randomisation, False), ("privileged_scan", privileged_scan, True),
+                                  ("depth_camera", depth_camera, True), ("height_scan", height_scan, True), ("history", history, True),
+                                  ("terrain_bank", terrain_bank, False)):
+            if arg is not None and behind and terminal_observation:
                 raise NotImplementedError(f"{name} with terminal_observation=True: the sensor runs after the step's launch, when an env that "
                                           "finished already holds its next episode's first state -- the terminal state is gone, so nothing of it "
                                           "can be appended to the terminal observation")
-            if sub_batches > 1:
+            if arg is not None and parted:
                 raise NotImplementedError(f"{name} needs one handle (sub_batches=1)")
         self.venv = make_vec_env(env_id, num_envs, sub_batches=sub_batches, seed=seed, auto_reset=True,
                                  **({"device": device} if device is not None else {}), **kw)
         self.env_id, self.num_envs = env_id, int(num_envs)
         self.device = self.venv.device
-        for name in sensors + (["terrain_bank"] if terrain_bank is not None else []) + (["randomisation"] if randomisation is not None else []) + (["history"] if history is not None else []):    # (several devices are no single handle either)
-            self._one(name)
         self._terrain = None
         if terrain_bank is not None:
             from . import host_logic as H
@@ -258,34 +274,30 @@ class TorchVecEnv:
             self.venv.set_heightfield_bank(int(tb["n_fields"]), H.HEIGHT_FIELD_SCALE, rows=H.HEIGHT_FIELD_SIZE[0], cols=H.HEIGHT_FIELD_SIZE[1])
             self.refresh_terrain(int(tb.get("seed", 0)))
             self.venv.set_env_fields(None, redraw_at_reset=bool(tb.get("redraw_at_reset", True)))
-        self._scan, self._wide = 0, None
-        if height_scan is not None:
-            self.venv.set_height_scan(**height_scan)
-            self._scan = self.venv.scan_dim
-        self.privileged = None
-        if privileged_scan is not None:
-            self.venv.set_height_scan(**privileged_scan)
-            self.privileged = torch.zeros(self.num_envs, self.venv.obs_dim + self.venv.scan_dim, dtype=torch.float32, device=self.device)
-        self.randomisation, self._noisy = None, False
+        scan = height_scan if height_scan is not None else privileged_scan
+        if scan is not None:
+            self.venv.set_height_scan(**scan)
         if randomisation is not None:
             self.venv.set_randomisation(randomisation)
-            self._noisy = randomisation.obs_noise is not None
-            if randomisation.privileged:     # [obs | scan | record]: the record call writes the tail
-                self.privileged = torch.zeros(self.num_envs, self.privileged.shape[1] + _lib.RAND_WORDS, dtype=torch.float32, device=self.device)
-                self.randomisation = self.privileged[:, -_lib.RAND_WORDS:]
-            else:
-                self.randomisation = torch.zeros(self.num_envs, _lib.RAND_WORDS, dtype=torch.float32, device=self.device)
-        self._depth = 0
         if depth_camera is not None:
             self.venv.set_depth_camera(depth_camera)
-            self._depth = self.venv.depth_dim
-        self._hist = 0
         if history is not None:
             self.venv.set_history(history)
-            self._hist = self.venv.history_dim
-        if self._scan or self._depth or self._hist:
-            self._wide = torch.zeros(self.num_envs, self.venv.obs_dim + self._scan + self._depth + self._hist, dtype=torch.float32, device=self.device)
-        high = np.inf * np.ones(self.venv.obs_dim + self._scan + self._depth + self._hist, dtype=np.float32)
+        plan = self._row_plan = self._plan_rows(
+            scan=self.venv.scan_dim if height_scan is not None else 0, depth=self.venv.depth_dim if depth_camera is not None else 0,
+            hist=self.venv.history_dim if history is not None else 0, privileged_scan=self.venv.scan_dim if privileged_scan is not None else 0,
+            randomisation=randomisation)
+        width = lambda blocks: sum(w for _, w in blocks.values())
+        rows = lambda w: torch.zeros(self.num_envs, w, dtype=torch.float32, device=self.device)
+        self._wide = rows(width(plan.policy)) if len(plan.policy) > 1 else None
+        self.privileged = rows(width(plan.privileged)) if plan.privileged else None
+        self.randomisation = None
+        if "record" in plan.privileged:
+            at, w = plan.privileged["record"]
+            self.randomisation = self.privileged[:, at:at + w]
+        elif randomisation is not None:
+            self.randomisation = rows(_lib.RAND_WORDS)
+        high = np.inf * np.ones(width(plan.policy), dtype=np.float32)
         self.observation_space = gym_shim.Box(-high, high, dtype=np.float32)                      # robots.py:18-29, env_locomotion.py:58-60
         self.action_space = gym_shim.Box(-np.ones(self.venv.act_dim, np.float32), np.ones(self.venv.act_dim, np.float32), dtype=np.float32)
         # a planner env with its base controller attached (base_controller=...): the action is the 15-number plan (unbounded box,
@@ -365,51 +377,50 @@ class TorchVecEnv:
     # ---- the VecPyTorch surface ----
     def reset(self) -> torch.Tensor:
         obs = self.venv.reset()        # (the reset kernel zeroes the envs' running returns: Monitor.reset)
-        self._refresh_privileged(obs)
-        return self._noise(obs) if self._wide is None else self._row(obs, self._wide, None)
-
-    def _refresh_privileged(self, obs):
-        """privileged_scan=: the row [obs | scan] of the state the envs are in now into `self.privileged`, one launch on the step's stream;
-        randomisation=: the plant's record into `self.randomisation` (the tail of the privileged row with privileged=True), one more"""
-        if self.privileged is not None:
-            self.venv.height_scan(out=self.privileged, obs=obs)
-        if self.randomisation is not None:
-            self.venv.randomisation_record(out=self.randomisation)
+        return self._fill(obs, obs if self._wide is None else self._wide, None)
 
     def effective_action(self) -> torch.Tensor:
         """randomisation=: what the last step's kernel read in place of the action, [N, act_dim]: `VecEnv.effective_action`.  One handle only."""
         return self._one("effective_action").effective_action()
 
-    def _noise(self, row):
-        """randomisation= with obs_noise: the sensor noise onto the head of the policy's row, in place, behind every sensor launch"""
-        return self.venv.sensor_noise(row) if self._noisy else row
+    def _plan_rows(self, scan, depth, hist, privileged_scan, randomisation) -> _RowPlan:
+        """THE rows and THE order (class docstring) from the widths of the blocks (0: none) and the randomisation (None: none).  A launch
+        is called with (o, row, act): the observation the reset or step just produced, the policy's row being filled -- the wide buffer,
+        `into["obs"]`, or `o` itself where the row is [obs] -- and the action for the history's previous frame."""
+        v, d = self.venv, self.venv.obs_dim
+        noisy = randomisation is not None and randomisation.obs_noise is not None
+        record = _lib.RAND_WORDS if randomisation is not None and randomisation.privileged else 0
+        policy = _blocks(("obs", d), ("scan", scan), ("depth", depth), ("hist", hist))
+        privileged = _blocks(("obs", d), ("scan", privileged_scan), ("record", record)) if privileged_scan else {}
+        launches = []
+        if privileged:
+            launches.append(lambda o, row, act: v.height_scan(out=self.privileged, obs=o))
+        if randomisation is not None:
+            launches.append(lambda o, row, act: v.randomisation_record(out=self.randomisation))
+        if scan:
+            launches.append(lambda o, row, act: v.height_scan(out=row, obs=o))
+            if depth:
+                launches.append(lambda o, row, act, at=policy["depth"][0]: v.depth_camera(out=row[:, at:]))
+        elif depth:
+            launches.append(lambda o, row, act: v.depth_camera(out=row, obs=o))
+        elif hist:       # no sensor copies the observation: the noise launch writes the noisy head straight into the row, else one device copy
+            launches.append((lambda o, row, act: v.sensor_noise(o, out=row)) if noisy else (lambda o, row, act: row[:, :d].copy_(o)))
+            noisy = False
+        if noisy:
+            launches.append(lambda o, row, act: v.sensor_noise(row))
+        if hist:
+            launches.append(lambda o, row, act, at=policy["hist"][0]: v.history(row, act, out=row[:, at:]))
+        return _RowPlan(policy, privileged, launches)
 
-    def _row(self, obs, wide, act):
-        """the policy's wide row [obs | scan | depth | hist] into `wide`: the sensors, the sensor noise on the row's head, then -- last, on what
-        the policy will read -- the history, whose previous frame takes `act` (None: a reset)"""
-        if self._scan or self._depth:
-            self._noise(self._widen(obs, wide))
-        elif self._noisy:              # no sensor copies the observation: the noise launch writes the noisy head straight into the row
-            self.venv.sensor_noise(obs, out=wide)
-        else:
-            wide[:, :self.venv.obs_dim].copy_(obs)
-        if self._hist:
-            self.venv.history(wide, act, out=wide[:, wide.shape[1] - self._hist:])
-        return wide
-
-    def _widen(self, obs, wide):
-        """the sensors' part [obs | scan | depth] of the wide row into `wide`: one launch per sensor, the first of them copies the observation"""
-        if self._scan:
-            self.venv.height_scan(out=wide, obs=obs)
-            if self._depth:
-                self.venv.depth_camera(out=wide[:, self.venv.obs_dim + self._scan:])
-        else:
-            self.venv.depth_camera(out=wide, obs=obs)
-        return wide
+    def _fill(self, o, row, act):
+        """the row plan's launches behind a reset or a step that produced `o` -> `row`, the policy's row"""
+        for launch in self._row_plan.launches:
+            launch(o, row, act)
+        return row
 
     def _step_obs(self, actions, obs_out=None, rew_out=None, launch=None):
-        """the step's launch and, with a height scan, a depth camera or a history, the launches that write the wide row [obs | scan | depth | hist] (into
-        `obs_out` or this object's own buffer; the step's own observation stays in the handle's buffer) -> (obs, reward).  `launch`: what steps instead of step() /
+        """the step's launch and the row plan's launches behind it, which write the policy's row (into `obs_out` or this object's own buffer;
+        with a wide row the step's own observation stays in the handle's buffer) -> (obs, reward).  `launch`: what steps instead of step() /
         plan_step() (act_step: `actions` is then the policy's input row)"""
         act_launch, launch = launch, launch or self._venv_step
         if self._wide is None:
@@ -417,16 +428,14 @@ class TorchVecEnv:
                 o, r = launch(actions)[:2]
             else:
                 o, r = launch(actions, obs_out=obs_out, rew_out=rew_out)[:2]
-            self._refresh_privileged(o)
-            return self._noise(o), r
+            return self._fill(o, o, None), r
         wide = self._wide if obs_out is None else obs_out
         if wide.shape != self._wide.shape or not wide.is_contiguous():
             raise ValueError("with a height scan, a depth camera or a history the observation rows are contiguous float32 "
                              "[n_envs, obs_dim + scan_dim + depth_dim + history_dim]")
         o, r = launch(actions, rew_out=rew_out)[:2]
-        self._refresh_privileged(o)
         # the action of the frame the policy acted on: step()'s tensor, or what act_step's policy launch wrote
-        return self._row(o, wide, (actions if act_launch is None else self.last_act["action"]) if self._hist else None), r
+        return self._fill(o, wide, actions if act_launch is None else self.last_act["action"]), r
 
     def step(self, actions: torch.Tensor, into: Optional[dict] = None):
         """`into` (one handle only): {"obs": [N, obs_dim], "reward": [N, 1], "masks": [N, 1], "bad_masks": [N, 1]} -- any subset -- tensors of the

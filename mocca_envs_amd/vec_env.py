@@ -224,6 +224,11 @@ class VecEnv:
         elif then == "sync":
             self._sync()
 
+    def _rows(self, name: str, t, width: int) -> int:
+        """`t` as float32 [n_envs, >= width] rows on this device (rollout.row_view: THE rule) -> its row stride in floats; `name`: what
+        the ValueError calls it"""
+        return _ro.row_view(name, t, width, self.n_envs, self.device)
+
     def close(self):
         if getattr(self, "h", None):
             torch.cuda.synchronize(self.device)
@@ -458,11 +463,8 @@ class VecEnv:
         p = self.policy
         if p is None or not getattr(p, "asymmetric", False):
             raise _lib.MoccaError("set_critic_rows needs a policy with a privileged critic (set_policy with an asymmetric DevicePolicy)")
-        if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[0] != self.n_envs or rows.shape[1] < p.critic_in_dim \
-                or rows.dtype != torch.float32 or rows.device != self.device or rows.stride(1) != 1:
-            raise ValueError(f"the critic's rows must be a float32 [n_envs, >= {p.critic_in_dim}] tensor on the env's device with contiguous rows")
-        stride = rows.stride(0) if self.n_envs > 1 else max(rows.stride(0), rows.shape[1])
-        _lib.check(self.lib.mocca_set_critic_rows(self.h, C.c_void_p(rows.data_ptr()), int(stride)), self.h)
+        stride = self._rows("the critic's rows", rows, p.critic_in_dim)
+        _lib.check(self.lib.mocca_set_critic_rows(self.h, C.c_void_p(rows.data_ptr()), stride), self.h)
         self.critic_rows = rows
 
     def _set_policy_mirror(self, name: str, tables, *extra):
@@ -559,8 +561,7 @@ class VecEnv:
         if p is None:
             raise _lib.MoccaError("act needs a policy (set_policy)")
         n, a = self.n_envs, p.act_dim
-        if obs.dim() != 2 or obs.shape[0] != n or obs.shape[1] < p.in_dim or obs.dtype != torch.float32 or obs.device != self.device or obs.stride(1) != 1:
-            raise ValueError(f"the policy's input must be a float32 [n_envs, >= {p.in_dim}] tensor on the env's device with contiguous rows")
+        stride = self._rows("the policy's input", obs, p.in_dim)
         if eps is not None:
             if eps.shape != (n, a) or eps.dtype != torch.float32 or eps.device != self.device or not eps.is_contiguous():
                 raise ValueError(f"eps must be a contiguous float32 [n_envs, {a}] tensor on the env's device")
@@ -576,8 +577,7 @@ class VecEnv:
             t = out.get(k)
             if t is not None and (t.numel() != numel or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()):
                 raise ValueError(f"out[{k!r}] must be a contiguous float32 tensor of {numel} elements on the env's device")
-        stride = obs.stride(0) if n > 1 else max(obs.stride(0), obs.shape[1])
-        return (_ptr(obs), int(stride), _ptr(eps), int(bool(deterministic)), _ptr(out["action"]), _ptr(out.get("logp")), _ptr(out.get("value")),
+        return (_ptr(obs), stride, _ptr(eps), int(bool(deterministic)), _ptr(out["action"]), _ptr(out.get("logp")), _ptr(out.get("value")),
                 _ptr(out.get("mean"))), out
 
     def act(self, obs: torch.Tensor, eps: Optional[torch.Tensor] = None, deterministic: bool = False, out: Optional[dict] = None) -> dict:
@@ -617,11 +617,7 @@ class VecEnv:
             given["action"] = self._pol_action
         args, out = self._act_args(obs, eps, deterministic, given, False, False)
         self.last_action = out["action"]
-        obs_o, rew = self.obs if obs_out is None else obs_out, self.rew if rew_out is None else rew_out
-        if obs_out is not None or rew_out is not None:
-            if obs_o.shape != (self.n_envs, self.obs_dim) or rew.numel() != self.n_envs or obs_o.dtype != torch.float32 or rew.dtype != torch.float32 \
-                    or not obs_o.is_contiguous() or not rew.is_contiguous() or obs_o.device != self.device or rew.device != self.device:
-                raise ValueError("obs_out / rew_out must be contiguous float32 [n_envs, obs_dim] / [n_envs] tensors on the env's device")
+        obs_o, rew = (self.obs, self.rew) if obs_out is None and rew_out is None else self._step_out(obs_out, rew_out)
         _lib.check(entry(self.h, *args, C.c_void_p(obs_o.data_ptr()), C.c_void_p(rew.data_ptr()), C.c_void_p(self.done.data_ptr()),
                          C.c_void_p(self.info.data_ptr()), self._stream()), self.h)
         return obs_o, rew, self.done, self.info
@@ -830,17 +826,14 @@ class VecEnv:
         t = self.teacher
         if t is None:
             raise _lib.MoccaError("teacher_act needs a teacher (set_teacher)")
-        if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[0] < 1 or rows.shape[1] < t.in_dim or rows.dtype != torch.float32 \
-                or rows.device != self.device or rows.stride(1) != 1:
-            raise ValueError(f"the teacher's input must be a float32 [n, >= {t.in_dim}] tensor on the env's device with contiguous rows")
+        stride = _ro.row_view("the teacher's input", rows, t.in_dim, None, self.device)
         n = rows.shape[0]
         f32 = dict(dtype=torch.float32, device=self.device)
         mean = torch.empty(n, t.act_dim, **f32) if mean is None else mean
         value = torch.empty(n, **f32) if value is None else value
         _ro.stats_out("mean", mean, n * t.act_dim, self.device)
         _ro.stats_out("value", value, n, self.device)
-        stride = rows.stride(0) if n > 1 else max(rows.stride(0), rows.shape[1])
-        self._call(self.lib.mocca_teacher_act, rows, int(stride), n, mean, value)
+        self._call(self.lib.mocca_teacher_act, rows, stride, n, mean, value)
         return {"mean": mean, "value": value}
 
     # ---- the reference's env-level setters, batched (env_base.py:103-118, env_locomotion.py:76-77,224-282) ----
@@ -996,15 +989,19 @@ class VecEnv:
             actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
         if actions.shape != (self.n_envs, width):
             raise ValueError(f"{what} must be [{self.n_envs}, {width}]")
-        obs, rew = self.obs if obs_out is None else obs_out, self.rew if rew_out is None else rew_out
-        if obs_out is not None or rew_out is not None:
-            if obs.shape != (self.n_envs, self.obs_dim) or rew.numel() != self.n_envs or obs.dtype != torch.float32 or rew.dtype != torch.float32 \
-                    or not obs.is_contiguous() or not rew.is_contiguous() or obs.device != self.device or rew.device != self.device:
-                raise ValueError("obs_out / rew_out must be contiguous float32 [n_envs, obs_dim] / [n_envs] tensors on the env's device")
+        obs, rew = (self.obs, self.rew) if obs_out is None and rew_out is None else self._step_out(obs_out, rew_out)
         _lib.check(entry(self.h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
                          C.c_void_p(rew.data_ptr()), C.c_void_p(self.done.data_ptr()),
                          C.c_void_p(self.info.data_ptr()), self._stream()), self.h)
         return obs, rew, self.done, self.info
+
+    def _step_out(self, obs_out, rew_out):
+        """step() / plan_step() / act_step() / act_plan_step() with `obs_out` or `rew_out`: check them -> where the launch writes (obs, rew)"""
+        obs, rew = self.obs if obs_out is None else obs_out, self.rew if rew_out is None else rew_out
+        if obs.shape != (self.n_envs, self.obs_dim) or rew.numel() != self.n_envs or obs.dtype != torch.float32 or rew.dtype != torch.float32 \
+                or not obs.is_contiguous() or not rew.is_contiguous() or obs.device != self.device or rew.device != self.device:
+            raise ValueError("obs_out / rew_out must be contiguous float32 [n_envs, obs_dim] / [n_envs] tensors on the env's device")
+        return obs, rew
 
     def episode_masks_into(self, masks: torch.Tensor, bad_masks: torch.Tensor) -> None:
         """Point the in-kernel `masks` / `bad_masks` columns of episode_stats() at other buffers FROM THE NEXT LAUNCH ON (e.g. row t + 1 of a
@@ -1193,11 +1190,7 @@ class VecEnv:
             width += self.obs_dim
         if out is None:
             out = torch.empty(self.n_envs, width, dtype=torch.float32, device=self.device)
-        elif out.dim() != 2 or out.shape[0] != self.n_envs or out.shape[1] < width or out.dtype != torch.float32 or out.device != self.device \
-                or out.stride(1) != 1 or (self.n_envs > 1 and out.stride(0) < out.shape[1]):
-            raise ValueError(f"out must be a float32 [n_envs, >= {width}] tensor on the env's device with contiguous rows")
-        stride = out.stride(0) if self.n_envs > 1 else max(out.stride(0), width)
-        self._call(fn, out, int(stride), obs, *extra)
+        self._call(fn, out, self._rows("out", out, width), obs, *extra)
         return out if out.shape[1] == width else out[:, :width]
 
     # ---- the egocentric depth camera (include/mocca.h mocca_set_depth_camera / mocca_depth_camera) ----
@@ -1272,12 +1265,7 @@ class VecEnv:
         synchronises: into `out` (float32 [N, >= obs_dim] with contiguous rows; columns beyond obs_dim are left untouched), or IN PLACE
         without one.  The noise is keyed by the envs' step and episode counters: two calls without a step in between add the same noise."""
         out = rows if out is None else out
-        for name, t in (("rows", rows), ("out", out)):
-            if t.dim() != 2 or t.shape[0] != self.n_envs or t.shape[1] < self.obs_dim or t.dtype != torch.float32 or t.device != self.device \
-                    or t.stride(1) != 1 or (self.n_envs > 1 and t.stride(0) < self.obs_dim):
-                raise ValueError(f"{name} must be a float32 [n_envs, >= {self.obs_dim}] tensor on the env's device with contiguous rows")
-        stride = lambda t: int(t.stride(0) if self.n_envs > 1 else max(t.stride(0), self.obs_dim))
-        self._call(self.lib.mocca_sensor_noise, rows, stride(rows), out, stride(out))
+        self._call(self.lib.mocca_sensor_noise, rows, self._rows("rows", rows, self.obs_dim), out, self._rows("out", out, self.obs_dim))
         return out
 
     def randomisation_record(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1286,10 +1274,7 @@ class VecEnv:
         w = _lib.RAND_WORDS
         if out is None:
             out = torch.empty(self.n_envs, w, dtype=torch.float32, device=self.device)
-        elif out.dim() != 2 or out.shape[0] != self.n_envs or out.shape[1] < w or out.dtype != torch.float32 or out.device != self.device \
-                or out.stride(1) != 1 or (self.n_envs > 1 and out.stride(0) < w):
-            raise ValueError(f"out must be a float32 [n_envs, >= {w}] tensor on the env's device with contiguous rows")
-        self._call(self.lib.mocca_randomisation_record, out, int(out.stride(0) if self.n_envs > 1 else max(out.stride(0), w)))
+        self._call(self.lib.mocca_randomisation_record, out, self._rows("out", out, w))
         return out if out.shape[1] == w else out[:, :w]
 
     # ---- the observation-action history (include/mocca.h mocca_set_history / mocca_history; history.History) ----
@@ -1322,12 +1307,8 @@ class VecEnv:
         w, n = self.history_dim, self.n_envs
         if out is None:
             out = torch.empty(n, w, dtype=torch.float32, device=self.device)
-        for name, t, least in (("rows", rows, self.obs_dim), ("act", act, self._hist_act), ("out", out, w)):
-            if t is not None and (t.dim() != 2 or t.shape[0] != n or t.shape[1] < least or t.dtype != torch.float32 or t.device != self.device
-                                  or (t.shape[1] > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < t.shape[1])):
-                raise ValueError(f"{name} must be a float32 [n_envs, >= {least}] tensor on the env's device with contiguous rows")
-        stride = lambda t: int(t.stride(0) if n > 1 else max(t.stride(0), t.shape[1]))
-        self._call(self.lib.mocca_history, rows, stride(rows), act, 0 if act is None else stride(act), out, stride(out))
+        self._call(self.lib.mocca_history, rows, self._rows("rows", rows, self.obs_dim), act,
+                   0 if act is None else self._rows("act", act, self._hist_act), out, self._rows("out", out, w))
         return out if out.shape[1] == w else out[:, :w]
 
     def kernel_info(self) -> dict:
