@@ -1,5 +1,5 @@
 // mocca_controller.h -- layout of the planner envs' base controller as the controller kernel reads it (mocca_controller.hip), and the
-// host-side launcher.  mocca_set_base_controller (mocca_api.hip) checks the caller's plain row-major layers and has the repack kernel
+// host-side launcher.  mocca_set_base_controller (mocca_api_policy.hip) checks the caller's plain row-major layers and has the repack kernel
 // (mocca_policy.hip) build this image on the device.
 //
 // The base controller of Walker3DPlannerEnv / MikePlannerEnv (env_locomotion.py:1029-1040, :1091-1101) is an actor-critic pair of MLPs over

@@ -1,4 +1,4 @@
-// mocca_depth.h -- launcher of mocca_depth.hip (the egocentric depth camera), called by the C ABI in mocca_api.hip (include/mocca.h mocca_depth_camera).
+// mocca_depth.h -- launcher of mocca_depth.hip (the egocentric depth camera), called by the C ABI in mocca_api_sensors.hip (include/mocca.h mocca_depth_camera).
 #pragma once
 #include "mocca_rays.h"
 

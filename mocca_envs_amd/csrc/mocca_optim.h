@@ -1,7 +1,7 @@
 // mocca_optim.h -- what follows the gradient in a PPO update, as kernels (mocca_optim.hip): clip_grad_norm_ and Adam's step on the flat parameter
-// tensor of mocca_update_policy, and the epoch's shuffle.  mocca_adam_step / mocca_ppo_update (mocca_api.hip) check the caller's arguments, own
+// tensor of mocca_update_policy, and the epoch's shuffle.  mocca_adam_step / mocca_ppo_update (mocca_api_trainer.hip) check the caller's arguments, own
 // the scratch and launch them between mocca_ppo.h's four launches and the repack of mocca_policy.h.  The contract: include/mocca.h.
-// mocca_distill_update is the same loop (mocca_api.hip: update_loop) around mocca_distill_grad: same kernels, same scratch, same shuffle.
+// mocca_distill_update is the same loop (mocca_api_trainer.hip: update_loop) around mocca_distill_grad: same kernels, same scratch, same shuffle.
 //
 // Layout.  params [n_floats] f32 is mocca_update_policy's flat tensor; its first n_params floats are trainable.  grad [>= n_params] f32 in the
 // same order.  moments f32 [2][n_head]: m at 0, v at n_head (n_head: the tensor's length without mean / inv_std), caller-owned.  clock f64 [4]:

@@ -1,5 +1,5 @@
 // mocca_policy.h -- layout of a trainer's Gaussian actor-critic as the policy kernel reads it (mocca_policy.hip), and the host-side launchers.
-// mocca_set_policy (mocca_api.hip) checks the caller's shapes and sizes this image; mocca_update_policy fills it from plain row-major
+// mocca_set_policy (mocca_api_policy.hip) checks the caller's shapes and sizes this image; mocca_update_policy fills it from plain row-major
 // parameters on the device (one repack kernel); mocca_act / mocca_act_step launch the kernel.
 //
 // The policy of a SymmetricRL / ALLSTEPS / a2c-ppo-acktr trainer: a diagonal-Gaussian actor (an MLP that gives the mean, a state-independent

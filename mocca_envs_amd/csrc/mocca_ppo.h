@@ -1,7 +1,7 @@
 // mocca_ppo.h -- the body of a PPO minibatch step up to optimizer.step() as kernels (mocca_ppo.hip): evaluate_actions, the clipped
 // surrogate, the value loss and loss.backward() for the Gaussian actor-critic of mocca_policy.h, plain, mirror-symmetric, plain with the
 // mirror-symmetry loss added, or plain on mirror-duplicated rows.  mocca_ppo_grad / mocca_ppo_grad_sym / mocca_ppo_grad_mirror /
-// mocca_ppo_grad_dup (mocca_api.hip) check the caller's arguments, own the scratch and launch them.  The loss and the per-row formulas: include/mocca.h.
+// mocca_ppo_grad_dup (mocca_api_trainer.hip) check the caller's arguments, own the scratch and launch them.  The loss and the per-row formulas: include/mocca.h.
 //
 // Image.  The kernels read the policy image of mocca_policy.h and, behind it, a SECOND copy of every layer's weights but a net's first,
 // transposed: layer l's W[out][in] as the [in_pad / 16][out_pad / 16][64][4] fragment order of W^T (in and out swap roles and padding), so

@@ -1,4 +1,4 @@
-// mocca_render.h -- launchers of mocca_render.hip (link frames, scene assembly, ray caster), called by the C ABI in mocca_api.hip.
+// mocca_render.h -- launchers of mocca_render.hip (link frames, scene assembly, ray caster), called by the C ABI in mocca_api_sensors.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,5 @@
 // mocca_rollout.h -- what a PPO trainer does between collecting a rollout and learning from it, as kernels (mocca_rollout.hip), and their
-// host-side launchers.  mocca_gae / mocca_obs_stats (mocca_api.hip) check the caller's arguments, own the scratch and launch them.
+// host-side launchers.  mocca_gae / mocca_obs_stats (mocca_api_trainer.hip) check the caller's arguments, own the scratch and launch them.
 //
 // GAE (a2c-ppo-acktr's rollouts.compute_returns(use_gae, use_proper_time_limits=True) and the advantage normalisation of ppo.update).
 // Storage [T][N] / [T + 1][N] f32, contiguous.  One IEEE f32 operation per line element, in this order, never contracted into an FMA:

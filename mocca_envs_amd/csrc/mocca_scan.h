@@ -1,4 +1,4 @@
-// mocca_scan.h -- launcher of mocca_scan.hip (the terrain height scan), called by the C ABI in mocca_api.hip (include/mocca.h mocca_height_scan).
+// mocca_scan.h -- launcher of mocca_scan.hip (the terrain height scan), called by the C ABI in mocca_api_sensors.hip (include/mocca.h mocca_height_scan).
 #pragma once
 #include "mocca_rays.h"
 

@@ -53,6 +53,23 @@ def test_bad_arguments_are_errors_not_crashes(built):
     assert l.mocca_step(None, None, None, None, None, None, None) == -1
 
 
+def test_a_null_handle_is_refused_by_name(built):
+    """Every entry point that takes the handle refuses a NULL one with -1 and "<name>: NULL handle" in the thread's message (include/mocca.h:
+    the message of a failed call is available from mocca_last_error).  The exceptions keep their results: mocca_destroy(NULL) is OK,
+    mocca_episode_serial(NULL) is 0, mocca_last_error reads the message, mocca_create has no handle yet."""
+    from mocca_envs_amd import lib
+    l = lib.load()
+    assert l.mocca_destroy(None) == 0 and l.mocca_episode_serial(None) == 0
+    takes_handle = [n for n, (_, args) in lib.SYMBOLS.items()
+                    if args and args[0] is C.c_void_p and n not in ("mocca_create", "mocca_destroy", "mocca_episode_serial", "mocca_last_error")]
+    assert len(takes_handle) > 70
+    for name in takes_handle:
+        zeros = [None if t is C.c_void_p or isinstance(t, type(C.POINTER(C.c_int))) else 0 for t in lib.SYMBOLS[name][1][1:]]
+        assert getattr(l, name)(None, *zeros) == -1, name
+        msg = l.mocca_last_error(None).decode()
+        assert msg.startswith(name + ":"), (name, msg)
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():
