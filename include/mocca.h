@@ -201,7 +201,8 @@ int mocca_set_terrain(mocca_handle h, const float *terrain_dev, void *stream);
 int mocca_set_param(mocca_handle h, int param_id, double value);
 /* Per-env form for MOCCA_PARAM_CURRICULUM / _EVAL_MODE / _APPLIED_GAIN (each env of the reference owns its own
  * attributes, env_base.py:103-115): values_dev [N] f32 is COPIED into the handle; broadcast != 0 reads values_dev[0]
- * for every env.  A later scalar mocca_set_param of the same id drops the vector. */
+ * for every env.  A later scalar mocca_set_param of the same id drops the vector (MOCCA_PARAM_CURRICULUM's is refused while a
+ * curriculum is attached, mocca_set_curriculum). */
 int mocca_set_param_v(mocca_handle h, int param_id, const float *values_dev, int broadcast, void *stream);
 /* full 64-bit Philox key (MOCCA_PARAM_SEED travels through a double: exact below 2^53 only) */
 int mocca_set_seed(mocca_handle h, uint64_t seed);
@@ -1053,6 +1054,68 @@ int mocca_set_history(mocca_handle h, const int32_t *cols_host, int n_cols, int 
 int mocca_history_dim(mocca_handle h);   /* steps * (n_cols + act_dim); MOCCA_E_ARG without an attachment */
 int mocca_history(mocca_handle h, const float *rows_dev, int row_stride, const float *act_dev /* may be NULL */, int act_stride,
                   float *out_dev, int out_stride, void *stream);
+
+/* ---- per-env adaptive curriculum of the Stepper envs on the device (the reference's trainer moves ONE level for all envs from the
+ *      host, set_env_params({"curriculum": k}); here every env earns its own) ---- */
+
+/* These entry points are ADDITIVE: MOCCA_ABI_VERSION stays 8, and a handle that calls none of them launches and computes exactly what it
+ * did before.  Nothing here touches the step kernel: at every reset it already reads a per-env level from the vector of
+ * mocca_set_param_v(MOCCA_PARAM_CURRICULUM) -- terrain ranges and applied gain follow at reset, the terminal height at once -- and every step
+ * it already writes done and the info word (steps_reached).  What is added is the rule that turns an env's own episode outcomes into its
+ * own level, one small launch behind the step, so that no trainer reads episode records in the middle of a rollout.  The rule, the
+ * ownership argument and the kernel layout: mocca_envs_amd/csrc/mocca_curriculum.h.
+ *
+ * The rule.  State per env, owned by the handle: the level -- the f32 word of that vector, the single source of truth and the very word
+ * the step kernel reads --, streak (int32) and hold (int32, 0 or 1).  ONE launch; every env whose done byte is non-zero, s its info word:
+ *   1. hold != 0: hold <- 0 and NOTHING ELSE.  The auto-reset inside the step kernel runs before this launch, so when a level changes the
+ *      env's next episode already stands on terrain of the old level: a new level first shapes the episode AFTER next.  The episode in
+ *      flight at a change is neither judged nor counted.
+ *   2. L = the vector's word read as the step kernel reads it: truncated to int, clamped to 0 .. 9.
+ *   3. with totals attached: totals[L] += {1, s, success ? 1 : 0, failure ? 1 : 0} (f32 atomics on whole numbers: exact and order-free
+ *      below 2^24).
+ *   4. success, s >= promote_at: streak <- max(streak, 0) + 1; at streak >= patience: streak <- 0, and L' = L + 1 if L < max_level, else with
+ *      recycle L' = min_level + ((uint64(w) * (max_level - min_level + 1)) >> 32), else L' = L.
+ *   5. failure, s <= demote_at: streak <- min(streak, 0) - 1; at streak <= -patience: streak <- 0, L' = max(L - 1, min_level).
+ *   6. neither: streak <- 0.
+ *   7. L' != L: the vector's word <- (float)L', hold <- 1.
+ * The recycle draw: w is word 0 of Philox4x32-10 under the handle's seed key with the counter (g, 0, E, 6): g = MOCCA_PARAM_ENV_OFFSET + env,
+ * E the env's episode counter (task word MOCCA_TW_EPISODE) READ FROM THE TASK RECORD WHEN THE KERNEL RUNS.  Domain 6 in counter word 3 is new:
+ * 0 .. 3 are the envs' own draws, policy noise, the field choice and the terrain generator, 4 and 5 the randomisation's; no other draw
+ * moves.  Nothing is kept on the host: the launch can be captured in a hipGraph and a shard reproduces its envs.
+ * Each thread owns its env: no thread reads a word another thread of the launch writes; the totals are only added to, atomically.
+ *
+ * mocca_set_curriculum  attaches (cfg == NULL: detaches) the rule.  Attaching switches the level vector on: it starts from the vector where
+ *                   that is on already, else from the scalar level broadcast, clamped into [min_level, max_level]; streak and hold start
+ *                   at 0.  level_totals_dev: [10][4] f32 per level {episodes judged, sum of steps_reached, successes, failures}, caller-
+ *                   owned, zeroed by the caller when it likes, or NULL.  While attached and MOCCA_PARAM_AUTO_RESET is 1, mocca_step and
+ *                   mocca_act_step enqueue the rule's launch directly behind the step kernel on the step's stream (where info_dev is
+ *                   NULL the step writes its info words to a buffer of the handle's): policy and step stay one call, a rollout stays
+ *                   one graph, and a graph captured after attaching replays the rule.  With auto-reset off nothing is launched: done is
+ *                   sticky there, and counting episode ends is the caller's, through mocca_curriculum_apply.  While attached the scalar
+ *                   mocca_set_param(MOCCA_PARAM_CURRICULUM) is refused -- it would drop the vector --: mocca_set_param_v with broadcast
+ *                   does the same job.  mocca_set_param_v keeps working; A HOST WRITE OF LEVELS IS JUDGED AS IF THE LEVEL HAD ALWAYS
+ *                   BEEN THAT: streak and hold stay as they are.  Detaching leaves the levels in the vector and takes the scalar again.
+ *                   May allocate and synchronise; no step does.
+ * mocca_get_curriculum  level_dev / streak_dev / hold_dev: [N] int32 each or NULL; one launch on `stream`, no synchronise.
+ * mocca_curriculum_apply  the same kernel on the caller's done bytes [N] u8 and info words [N] i32: for callers with a loop of their own.
+ * Limits: STREAK, HOLD AND THE VECTOR ARE NOT PART OF THE mocca_get_state / mocca_get_task SNAPSHOT.  The planner ids are out of scope:
+ * difficulty bands of the terrain bank would need the field choice in the step kernel's reset to change.  One handle: the multi-handle
+ * wrappers of the Python layer do not offer it.
+ * Errors (MOCCA_E_ARG, with a message, before any launch; the handle is left as it was): mocca_set_curriculum on a task other than
+ * MOCCA_TASK_WALKER3D_STEPPER (the quadruped and Mike Stepper ids are that task); demote_at >= promote_at; patience outside 1 ..
+ * MOCCA_CUR_MAX_PATIENCE; levels outside 0 <= min_level <= max_level <= MOCCA_CUR_MAX_LEVEL; recycle other than 0 or 1.
+ * mocca_get_curriculum / mocca_curriculum_apply without an attachment; mocca_curriculum_apply: a NULL done_dev or info_dev. */
+#define MOCCA_CUR_MAX_LEVEL 9
+#define MOCCA_CUR_MAX_PATIENCE 64
+typedef struct mocca_curriculum {
+  int32_t promote_at, demote_at; /* an episode with steps_reached >= promote_at is a success, <= demote_at a failure; demote_at < promote_at */
+  int32_t patience;              /* that many successes (failures) in a row move the level up (down), 1 .. MOCCA_CUR_MAX_PATIENCE */
+  int32_t min_level, max_level;  /* 0 <= min_level <= max_level <= MOCCA_CUR_MAX_LEVEL */
+  int32_t recycle;               /* 1: an env promoted at max_level restarts at a level drawn uniformly from the band */
+} mocca_curriculum;
+int mocca_set_curriculum(mocca_handle h, const mocca_curriculum *cfg, float *level_totals_dev /* [10][4] or NULL, caller-owned */);
+int mocca_get_curriculum(mocca_handle h, int32_t *level_dev, int32_t *streak_dev, int32_t *hold_dev, void *stream);
+int mocca_curriculum_apply(mocca_handle h, const uint8_t *done_dev, const int32_t *info_dev, void *stream);
 
 /* registers, LDS and scratch of the step kernel as built (for DESIGN.md / bench), as the HIP runtime reports them; *sgprs = -1: the
  * runtime has no scalar-register attribute (hipFuncAttributes), the count is printed by `python -m mocca_envs_amd.build -v` */

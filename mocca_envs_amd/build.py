@@ -10,8 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libmocca_hip.so")
-SOURCES = ["mocca_api.hip", "mocca_api_terrain.hip", "mocca_api_sensors.hip", "mocca_api_policy.hip", "mocca_api_trainer.hip", "mocca_task.hip", "mocca_r32.hip", "mocca_r64.hip", "mocca_controller.hip", "mocca_render.hip", "mocca_scan.hip", "mocca_depth.hip", "mocca_policy.hip", "mocca_rollout.hip", "mocca_ppo.hip", "mocca_optim.hip", "mocca_terrain.hip", "mocca_randomise.hip", "mocca_history.hip"]   # physics kernels + the C ABI the step kernel's launch depends on; the C ABI's host-only units (terrain bank; sensors, history and randomisation; controller and policies; trainer); task-layer (INJECT) kernel instances; compact (32-row) step kernels; 64-row accuracy instance; the planner envs' base controller (MFMA); link frames and the ray caster; the terrain height scan; the egocentric depth camera; a trainer's Gaussian actor-critic (MFMA); GAE, advantage moments and running observation statistics; PPO's minibatch loss and gradient (MFMA); clip_grad_norm_, Adam's step and the epoch's shuffle; the terrain bank's random height fields; domain randomisation (perturb, sensor noise, record); the observation-action history
-DEPS = SOURCES + ["mocca_handle.h", "mocca_mlp.h", "mocca_controller.h", "mocca_policy.h", "mocca_ppo.h", "mocca_optim.h", "mocca_rollout.h", "mocca_terrain.h", "mocca_randomise.h", "mocca_history.h", "mocca_render.h", "mocca_rays.h", "mocca_scene.h", "mocca_scan.h", "mocca_depth.h", "mocca_kernels.h", "mocca_device.h", "mocca_philox.h", "topo_walker3d.h", "topo_cassie.h", "topo_walker2d.h", "topo_crab2d.h", "topo_laikago.h"]
+SOURCES = ["mocca_api.hip", "mocca_api_terrain.hip", "mocca_api_sensors.hip", "mocca_api_policy.hip", "mocca_api_trainer.hip", "mocca_api_curriculum.hip", "mocca_task.hip", "mocca_r32.hip", "mocca_r64.hip", "mocca_controller.hip", "mocca_render.hip", "mocca_scan.hip", "mocca_depth.hip", "mocca_policy.hip", "mocca_rollout.hip", "mocca_ppo.hip", "mocca_optim.hip", "mocca_terrain.hip", "mocca_randomise.hip", "mocca_history.hip", "mocca_curriculum.hip"]   # physics kernels + the C ABI the step kernel's launch depends on; the C ABI's host-only units (terrain bank; sensors, history and randomisation; controller and policies; trainer; the adaptive curriculum); task-layer (INJECT) kernel instances; compact (32-row) step kernels; 64-row accuracy instance; the planner envs' base controller (MFMA); link frames and the ray caster; the terrain height scan; the egocentric depth camera; a trainer's Gaussian actor-critic (MFMA); GAE, advantage moments and running observation statistics; PPO's minibatch loss and gradient (MFMA); clip_grad_norm_, Adam's step and the epoch's shuffle; the terrain bank's random height fields; domain randomisation (perturb, sensor noise, record); the observation-action history; the per-env adaptive curriculum
+DEPS = SOURCES + ["mocca_handle.h", "mocca_mlp.h", "mocca_controller.h", "mocca_policy.h", "mocca_ppo.h", "mocca_optim.h", "mocca_rollout.h", "mocca_terrain.h", "mocca_randomise.h", "mocca_history.h", "mocca_curriculum.h", "mocca_render.h", "mocca_rays.h", "mocca_scene.h", "mocca_scan.h", "mocca_depth.h", "mocca_kernels.h", "mocca_device.h", "mocca_philox.h", "topo_walker3d.h", "topo_cassie.h", "topo_walker2d.h", "topo_crab2d.h", "topo_laikago.h"]
 
 
 def _stale() -> bool:

@@ -1,5 +1,6 @@
 // mocca_api.hip -- kernels' entry points and the part of the C ABI of libmocca_hip.so (include/mocca.h) that the step kernel's launch depends on.
-// The host-only features are units of their own: mocca_api_terrain.hip, mocca_api_sensors.hip, mocca_api_policy.hip, mocca_api_trainer.hip.
+// The host-only features are units of their own: mocca_api_terrain.hip, mocca_api_sensors.hip, mocca_api_policy.hip, mocca_api_trainer.hip,
+// mocca_api_curriculum.hip.
 // Build: hipcc --offload-arch=gfx950 -O3 -shared -fPIC (see mocca_envs_amd/build.py).
 #include <cstdio>
 
@@ -255,6 +256,8 @@ int launch_step(const Call& c, const float* act_dev, const float* base_value, fl
   StepArgs a = make_args(h);
   a.act = act_dev; a.obs = obs_dev; a.rew = rew_dev; a.done = done_dev; a.info = info_dev;
   a.base_value = base_value;
+  const bool judge = h->cur_on && h->auto_reset;   // the adaptive curriculum's launch behind the step kernel (with auto-reset off done is sticky:
+  if (judge && !a.info) a.info = h->d_cur_info;    // counting episode ends is then the caller's, mocca_curriculum_apply); it reads the info words
   if (int rc = flush_pending(c, s)) return rc;
   if (h->rand_on) {   // strength, latency and pushes act on what the step kernel reads: one small launch in front of it, nothing without an attachment
     mocca_rand::PerturbArgs p{rand_keys(h), h->rand_cfg, act_dev, h->d_rand_eff, h->d_rand_ring, h->d_dyn, DYN_STRIDE, mocca_act_dim(h)};
@@ -284,6 +287,10 @@ int launch_step(const Call& c, const float* act_dev, const float* base_value, fl
     case INST_COMPACT: mocca_r32_launch_step(h->topo, h->task_id, h->n_envs, s, &a); break;
     case INST_WIDE: mocca_r64_launch_step(h->topo, h->task_id, h->n_envs, s, &a); break;
     default: dispatch<LaunchStep>(h->topo, h->task_id, h->n_envs, s, a);
+  }
+  if (judge) {   // the episodes that ended in this step move their envs' levels: one small launch, nothing without an attachment
+    HIP_TRY(c, hipGetLastError());
+    mocca_cur::launch_curriculum(s, curriculum_args(h, done_dev, a.info));
   }
   return c.launched();
 }
@@ -549,7 +556,10 @@ int mocca_set_param(mocca_handle h, int param_id, double value) {
   switch (param_id) {
     case MOCCA_PARAM_AUTO_RESET: h->auto_reset = value != 0; break;
     case MOCCA_PARAM_EVAL_MODE: h->eval_mode = value != 0; h->pvec_on[1] = false; break;
-    case MOCCA_PARAM_CURRICULUM: h->curriculum = (int)value < 0 ? 0 : ((int)value > 9 ? 9 : (int)value); h->pvec_on[0] = false; break;
+    case MOCCA_PARAM_CURRICULUM:
+      if (h->cur_on)
+        return c.bad("the scalar MOCCA_PARAM_CURRICULUM would drop the level vector of the attached curriculum: use mocca_set_param_v with broadcast");
+      h->curriculum = (int)value < 0 ? 0 : ((int)value > 9 ? 9 : (int)value); h->pvec_on[0] = false; break;
     case MOCCA_PARAM_APPLIED_GAIN:  // acts on the next apply_action: the task records carry the value the kernel uses; this call has no
       h->gain = (float)value; h->pvec_on[2] = false; h->gain_pending = true;   // stream, so the write is enqueued by the next call that has
       break;                                                                    // one (flush_pending), ordered on the caller's stream

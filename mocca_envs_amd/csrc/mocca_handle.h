@@ -23,6 +23,7 @@
 #include "mocca_terrain.h"
 #include "mocca_randomise.h"
 #include "mocca_history.h"
+#include "mocca_curriculum.h"
 
 #pragma GCC visibility push(hidden)   // what follows is shared by the library's units, not exported from it
 
@@ -175,6 +176,13 @@ struct mocca_ctx {
   DevBuf<int32_t> d_hist_cols;       // [n_cols] the observation columns of a frame
   DevBuf<float> d_hist_ring;         // [N][steps * stride + 1][n_cols + act_dim] the frames; NOT part of a snapshot
   DevBuf<uint32_t> d_hist_tags;      // [N][steps * stride + 1][2] (episode, step) of the frame a slot holds
+  // the per-env adaptive curriculum (mocca_curriculum.h); its levels are d_pvec[0], the words the step kernel reads
+  bool cur_on = false;               // mocca_set_curriculum: with auto_reset, launch_step runs the rule's kernel behind the step kernel
+  mocca_cur::CurConfig cur_cfg{};
+  DevBuf<int32_t> d_cur_streak;      // [N] owned by the handle; NOT part of a snapshot
+  DevBuf<int32_t> d_cur_hold;        // [N]
+  DevBuf<int32_t> d_cur_info;        // [N] the step's info words where the caller passes info_dev == NULL
+  float* cur_totals = nullptr;       // caller-owned [10][4], or null
   std::string err;
 };
 extern thread_local std::string g_err;   // the message of a call that has no handle to keep it in (mocca_api.hip)
@@ -250,6 +258,8 @@ int need_heightfield(const Call& c, const char* who, const char* when);
 mocca_rdr::HeightFieldBank heightfield_record(mocca_handle h);
 mocca_rand::RandKeys rand_keys(mocca_handle h);
 mocca_rdr::SceneArgs scene_args(mocca_handle h);
+// mocca_api_curriculum.hip: the arguments of the rule's launch on a step's done bytes and info words
+mocca_cur::CurArgs curriculum_args(mocca_handle h, const uint8_t* done_dev, const int32_t* info_dev);
 // mocca_api_policy.hip: the student's flat parameter tensor, as the optimiser calls of mocca_api_trainer.hip see it
 std::string check_n_floats(const mocca_ctx::PolicySlot& slot, size_t n_floats);
 void repack_policy(const mocca_ctx::PolicySlot& slot, const float* params_dev, size_t n_floats, hipStream_t s);

@@ -9,7 +9,7 @@
 // MOCCA_TW_EPISODE), c1 = 0 or the env's step counter T (task word MOCCA_TW_T), both read from the task record AT LAUNCH TIME -- nothing is
 // kept on the host, so every launch can be captured in a graph, and a shard reproduces the rows it owns.  Counter word 3 holds the domain:
 // 0 the envs' own draws, 1 policy noise, 2 field choice, 3 the terrain generator; this file takes 4 and 5, with a block index b in the upper
-// bits, c3 = domain + 256 b.  A uniform is u = (w >> 8) * 2^-24, a signed uniform s = 2 u - 1 (both exact in f32).
+// bits, c3 = domain + 256 b (6 is the adaptive curriculum's recycle draw, mocca_curriculum.h).  A uniform is u = (w >> 8) * 2^-24, a signed uniform s = 2 u - 1 (both exact in f32).
 //     episode parameters   (g, 0, E, 4)            strength = fmaf(u0, hi - lo, lo);  delay = delay_min + (w1 >> 8) % (delay_max - delay_min + 1);
 //                                                  phase = (w2 >> 8) % push_interval   (integers: a float product can round up to the bound)
 //     push at step T       (g, T, E, 4 + 256)      dvx = push_max * s0;  dvy = push_max * s1

@@ -27,6 +27,7 @@ DEPTH_MAX_PIXELS, DEPTH_STABILISED, DEPTH_SEE_ROBOT = 256, 1, 2   # MOCCA_DEPTH_
 HF_MAX_FIELDS, HF_MAX_PEAKS = 1024, 256   # MOCCA_HF_MAX_FIELDS, MOCCA_HF_MAX_PEAKS
 RAND_WORDS, RAND_MAX_DELAY, RAND_MAX_INTERVAL = 4, 7, 65536   # MOCCA_RAND_WORDS, MOCCA_RAND_MAX_DELAY, the bound of push_interval
 HIST_MAX_STEPS, HIST_MAX_STRIDE, HIST_MAX_DIM, HIST_MAX_ACT = 16, 8, 1024, 32   # MOCCA_HIST_MAX_STEPS, MOCCA_HIST_MAX_STRIDE, MOCCA_HIST_MAX_DIM, the bound of act_dim
+CUR_MAX_LEVEL, CUR_MAX_PATIENCE, CUR_LEVELS, CUR_TOTALS = 9, 64, 10, 4   # MOCCA_CUR_MAX_LEVEL, MOCCA_CUR_MAX_PATIENCE, the shape of the per-level totals
 RENDER_ID_NONE, RENDER_ID_GROUND, RENDER_ID_PLANK0, RENDER_ID_HEIGHTFIELD, RENDER_ID_TARGET, RENDER_ID_LINK0 = -1, 32, 33, 37, 38, 64   # MOCCA_RENDER_ID_*
 
 # every symbol include/mocca.h declares: (name, restype, argtypes)
@@ -114,6 +115,9 @@ SYMBOLS = {
     "mocca_set_history": (_i, [_vp, _vp, _i, _i, _i, _i]),
     "mocca_history_dim": (_i, [_vp]),
     "mocca_history": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    "mocca_set_curriculum": (_i, [_vp, _vp, _vp]),
+    "mocca_get_curriculum": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mocca_curriculum_apply": (_i, [_vp, _vp, _vp, _vp]),
     "mocca_is_diagnostic_build": (_i, []),
     "mocca_kernel_info": (_i, [_vp] + [C.POINTER(_i)] * 5),
     "mocca_last_error": (C.c_char_p, [_vp]),
@@ -125,6 +129,12 @@ class RandomisationConfig(C.Structure):
     """`mocca_randomisation` of include/mocca.h"""
     _fields_ = [("strength_lo", C.c_float), ("strength_hi", C.c_float), ("delay_min", C.c_int32), ("delay_max", C.c_int32),
                 ("push_interval", C.c_int32), ("push_max", C.c_float)]
+
+
+class CurriculumConfig(C.Structure):
+    """`mocca_curriculum` of include/mocca.h"""
+    _fields_ = [("promote_at", C.c_int32), ("demote_at", C.c_int32), ("patience", C.c_int32), ("min_level", C.c_int32),
+                ("max_level", C.c_int32), ("recycle", C.c_int32)]
 
 
 _lib = None

@@ -171,6 +171,8 @@ class _Parts:
     ONE_HANDLE = ("set_heightfield_bank", "generate_heightfields", "set_env_fields", "env_fields", "height_fields",
                   "set_randomisation", "effective_action", "set_sensor_noise", "sensor_noise", "randomisation_record",
                   "set_history", "history")
+    # ... and so is what acts BEHIND one handle's step on state of its own: the adaptive curriculum's streaks and holds
+    ONE_HANDLE_BEHIND_STEP = ("set_curriculum", "curriculum_levels", "curriculum_state", "curriculum_apply")
 
     def set_state(self, st) -> None:
         st = torch.as_tensor(st, dtype=torch.float32).reshape(self.n_envs, self.state_dim)
@@ -190,7 +192,7 @@ def _refusal(name: str):
     return method
 
 
-for _name in _Parts.ONE_HANDLE:
+for _name in _Parts.ONE_HANDLE + _Parts.ONE_HANDLE_BEHIND_STEP:
     setattr(_Parts, _name, _refusal(_name))
 
 

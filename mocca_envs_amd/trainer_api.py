@@ -215,7 +215,10 @@ class TorchVecEnv:
     `height_scan=dict(points=[P, 2], z_above=1.0, max_drop=2.0)` (perception.scan_grid builds patterns): the terrain height scan (include/
     mocca.h mocca_height_scan), P floats; `depth_camera=perception.DepthCamera(...)`: the egocentric depth image (mocca_depth_camera),
     width * height floats; `history=history.History(steps, stride, columns, actions)`: the observation-action history (mocca_history),
-    `envs.venv.history_dim` floats; `privileged_scan=dict(...)` (teacher-student distillation; not together with `height_scan=`): the scan
+    `envs.venv.history_dim` floats; `curriculum=curriculum.Curriculum(...)` (Stepper ids): the per-env adaptive curriculum
+    (mocca_set_curriculum) -- every env's own episodes move its own level, one small launch behind each step, also inside act_step() and a
+    captured rollout; `envs.curriculum_levels` is the int32 [N] levels on the device, `envs.curriculum_totals` the per-level counts [10, 4];
+    it adds nothing to the rows; `privileged_scan=dict(...)` (teacher-student distillation; not together with `height_scan=`): the scan
     attached but kept OUT of the policy's row; `randomisation=randomisation.Randomisation(...)`: domain randomisation (mocca_set_randomisation)
     -- per-episode motor strength, action latency and random pushes in front of every step (one more small launch; `envs.effective_action()`
     tells what the step read), with `obs_noise` uniform noise on what the policy sees, and a 4-float record of every env's plant (strength,
@@ -243,7 +246,13 @@ class TorchVecEnv:
     def __init__(self, env_id: str, num_envs: int, seed: int = 0, device: Optional[int] = None, sub_batches: int = 1,
                  terminal_observation: bool = False, record_slots: int = 8, eager_done: bool = False, record_events: bool = True,
                  height_scan: Optional[dict] = None, terrain_bank: Optional[dict] = None, depth_camera=None,
-                 privileged_scan: Optional[dict] = None, randomisation=None, history=None, **kw):
+                 privileged_scan: Optional[dict] = None, randomisation=None, history=None, curriculum=None, **kw):
+        if curriculum is not None:     # (refused before anything touches a device, like the options below)
+            from . import model as M
+            from .curriculum import STEPPER_IDS_ONLY
+            from .vec_env import TASKS
+            if TASKS.get(env_id) != M.TASK_WALKER3D_STEPPER:
+                raise ValueError(f"curriculum: {STEPPER_IDS_ONLY} ({env_id!r} is not one)")
         if randomisation is not None and randomisation.privileged and privileged_scan is None:
             raise ValueError("Randomisation(privileged=True) puts the plant's record behind [obs | scan]: that takes privileged_scan=")
         if height_scan is not None and privileged_scan is not None:
@@ -252,7 +261,7 @@ class TorchVecEnv:
         parted = sub_batches > 1 or len(kw.get("devices") or ()) > 1      # (what make_vec_env cuts into sub-batches or shards)
         for name, arg, behind in (("randomisation", randomisation, False), ("privileged_scan", privileged_scan, True),
                                   ("depth_camera", depth_camera, True), ("height_scan", height_scan, True), ("history", history, True),
-                                  ("terrain_bank", terrain_bank, False)):
+                                  ("terrain_bank", terrain_bank, False), ("curriculum", curriculum, False)):
             if arg is not None and behind and terminal_observation:
                 raise NotImplementedError(f"{name} with terminal_observation=True: the sensor runs after the step's launch, when an env that "
                                           "finished already holds its next episode's first state -- the terminal state is gone, so nothing of it "
@@ -283,6 +292,10 @@ class TorchVecEnv:
             self.venv.set_depth_camera(depth_camera)
         if history is not None:
             self.venv.set_history(history)
+        self.curriculum_totals = None                      # [10, 4] per level: episodes judged, sum of steps_reached, successes, failures; zero it when you like
+        if curriculum is not None:
+            self.curriculum_totals = self.venv.set_curriculum(curriculum)
+            self._levels = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
         plan = self._row_plan = self._plan_rows(
             scan=self.venv.scan_dim if height_scan is not None else 0, depth=self.venv.depth_dim if depth_camera is not None else 0,
             hist=self.venv.history_dim if history is not None else 0, privileged_scan=self.venv.scan_dim if privileged_scan is not None else 0,
@@ -382,6 +395,14 @@ class TorchVecEnv:
     def effective_action(self) -> torch.Tensor:
         """randomisation=: what the last step's kernel read in place of the action, [N, act_dim]: `VecEnv.effective_action`.  One handle only."""
         return self._one("effective_action").effective_action()
+
+    @property
+    def curriculum_levels(self) -> torch.Tensor:
+        """curriculum=: every env's level NOW, int32 [N] on the device -- one launch into a buffer of this object's, nothing synchronises
+        until the caller reads it (at log time, outside the collection loop)."""
+        if self.curriculum_totals is None:
+            raise _lib.MoccaError("curriculum_levels needs curriculum=Curriculum(...) at construction")
+        return self.venv.curriculum_levels(out=self._levels)
 
     def _plan_rows(self, scan, depth, hist, privileged_scan, randomisation) -> _RowPlan:
         """THE rows and THE order (class docstring) from the widths of the blocks (0: none) and the randomisation (None: none).  A launch

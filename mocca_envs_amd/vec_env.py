@@ -113,6 +113,8 @@ class VecEnv:
     randomisation = None    # set_randomisation(): the attached randomisation.Randomisation
     hist = None             # set_history(): the attached history.History, and what it resolved to on this env
     _hist_cols, _hist_act = None, 0
+    curriculum = None       # set_curriculum(): the attached curriculum.Curriculum, and its per-level totals [10, 4]
+    curriculum_totals = None
 
     def __init__(self, env_id: str = "Walker3DCustomEnv-v0", n_envs: int = 1, device: Optional[int] = None,
                  auto_reset: bool = True, seed: int = 0, model_blob: Optional[bytes] = None, env_offset: int = 0,
@@ -1310,6 +1312,59 @@ class VecEnv:
         self._call(self.lib.mocca_history, rows, self._rows("rows", rows, self.obs_dim), act,
                    0 if act is None else self._rows("act", act, self._hist_act), out, self._rows("out", out, w))
         return out if out.shape[1] == w else out[:, :w]
+
+    # ---- the per-env adaptive curriculum (include/mocca.h mocca_set_curriculum .. mocca_curriculum_apply; curriculum.Curriculum) ----
+    def set_curriculum(self, cfg, totals: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        """Attach a `curriculum.Curriculum` (None detaches; Stepper ids only): from the next step on every env's own episodes move its own
+        level, one small launch behind each step()'s / act_step()'s kernel while auto-reset is on.  The levels start from the per-env
+        levels where those are set (set_env_params with one value per env), else from the scalar level, clamped into the band.  `totals`:
+        a contiguous float32 [10, 4] tensor on the env's device, per level {episodes judged, sum of steps_reached, successes, failures},
+        which the caller zeroes when it likes; allocated here without one and returned.  While attached a scalar
+        set_env_params({"curriculum": k}) is refused: set_param_v(PARAM_CURRICULUM, [k], broadcast=True) writes every env's level.  May
+        allocate and synchronise; no step does."""
+        if cfg is None:
+            _lib.check(self.lib.mocca_set_curriculum(self.h, None, None), self.h)
+            self.curriculum, self.curriculum_totals = None, None
+            return None
+        shape = (_lib.CUR_LEVELS, _lib.CUR_TOTALS)
+        if totals is None:
+            totals = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        elif tuple(totals.shape) != shape or totals.dtype != torch.float32 or not totals.is_contiguous() or totals.device != self.device:
+            raise ValueError("set_curriculum: totals must be a contiguous float32 [10, 4] tensor on the env's device")
+        c = cfg.config()
+        self._sync()      # no launch of this handle is in flight while its buffers change
+        _lib.check(self.lib.mocca_set_curriculum(self.h, C.byref(c), C.c_void_p(totals.data_ptr())), self.h)
+        self.curriculum, self.curriculum_totals = cfg, totals
+        return totals
+
+    def _need_curriculum(self, who: str) -> None:
+        if self.curriculum is None:
+            raise _lib.MoccaError(f"{who} needs a Curriculum (set_curriculum)")
+
+    def curriculum_levels(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """every env's level: int32 [N] on the device, one launch; nothing synchronises until the caller reads it"""
+        return self.curriculum_state(level=out)["level"]
+
+    def curriculum_state(self, level: Optional[torch.Tensor] = None) -> dict:
+        """-> {"level", "streak", "hold"}: int32 [N] each on the device -- the level, the run of successes (> 0) or failures (< 0) at it,
+        and whether the episode in flight is exempt from judgement (its level changed after it was laid out).  One launch."""
+        self._need_curriculum("curriculum_state")
+        i32 = dict(dtype=torch.int32, device=self.device)
+        if level is not None and (level.shape != (self.n_envs,) or level.dtype != torch.int32 or not level.is_contiguous() or level.device != self.device):
+            raise ValueError("the levels go to a contiguous int32 [n_envs] tensor on the env's device")
+        out = {"level": torch.empty(self.n_envs, **i32) if level is None else level, "streak": torch.empty(self.n_envs, **i32),
+               "hold": torch.empty(self.n_envs, **i32)}
+        self._call(self.lib.mocca_get_curriculum, out["level"], out["streak"], out["hold"])
+        return out
+
+    def curriculum_apply(self, done: torch.Tensor, info: torch.Tensor) -> None:
+        """The rule's launch on the caller's `done` (uint8 [N]) and `info` (int32 [N]): for loops that step with auto-reset off and count
+        episode ends themselves.  With auto-reset on step() has launched it already."""
+        self._need_curriculum("curriculum_apply")
+        for t, dt, what in ((done, torch.uint8, "done"), (info, torch.int32, "info")):
+            if not isinstance(t, torch.Tensor) or t.shape != (self.n_envs,) or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"curriculum_apply: {what} must be a contiguous {dt} [n_envs] tensor on the env's device")
+        self._call(self.lib.mocca_curriculum_apply, done, info)
 
     def kernel_info(self) -> dict:
         v = [C.c_int() for _ in range(5)]

@@ -5,7 +5,7 @@ that LEARNS, and what does the step kernel cost on the workload a trained policy
 Plain PPO in the pytorch-a2c-ppo-acktr mould the reference's trainers (README.md:33-39) follow -- Gaussian MLP policy 2 x 256 tanh, separate value
 net, GAE(0.95), clipped surrogate, Adam, running observation normalisation -- with everything on the device: the step kernel writes observation /
 reward / masks / bad_masks straight into the rollout storage (`step(action, into=...)`), Monitor's statistics come from `envs.episode_totals`.
-No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it SymmetricRL's symmetric network, --mirror-loss its symmetry loss,
+No curriculum unless asked for (--curriculum K, --adaptive-curriculum ..): this is a sanity run, not SymmetricRL; --symmetric gives it SymmetricRL's symmetric network, --mirror-loss its symmetry loss,
 --mirror-dup its duplicated tuples.
 
   python tools/ppo_demo.py [--env-id Walker3DCustomEnv-v0] [--envs 4096] [--steps 32] [--iters 400] [--minutes 12] [--out gpurun_out/r06_ppo_demo]
@@ -13,7 +13,7 @@ No curriculum: this is a sanity run, not SymmetricRL; --symmetric gives it Symme
                            [--base-controller FILE] [--height-scan NX,NY] [--depth-camera W,H]
                            [--distill-from TEACHER.npz --privileged-scan NX,NY] [--privileged-critic --privileged-scan NX,NY]
                            [--rand-strength LO,HI] [--rand-latency LO,HI] [--rand-push INTERVAL,MAX] [--obs-noise SCALE] [--rand-privileged]
-                           [--history K[,S]]
+                           [--history K[,S]] [--curriculum K | --adaptive-curriculum PROMOTE,DEMOTE[,PATIENCE] [--curriculum-recycle]]
 --base-controller FILE (required for the planner ids, Walker3DPlannerEnv-v0 / MikePlannerEnv-v0): ALLSTEPS's second step.  FILE is a
 `BaseController.save_npz` file or the <out>_policy.npz of an earlier run of this script on a Stepper id (told apart by the keys; the latter
 brings its observation statistics along); it is frozen as the env's base controller and the policy trained here emits 15-number plans.
@@ -79,6 +79,13 @@ policy's row ends in the K pairs [obs | action] it read and output S, 2 S, .. K 
 that the actor can tell the plant it has from what its commands did.  Every arm works (the row is just wider; --symmetric takes the env's
 extended mirror tables); not with --mirror-loss / --mirror-dup, whose torch side mirrors with get_mirror_indices() alone.
 <out>_policy.npz records the history (`history`, a JSON string): tools/randomisation_eval.py rebuilds the env with it.
+--curriculum K (Stepper ids): every env on the terrain of level K (`set_env_params({"curriculum": K})`), fixed for the run.
+--adaptive-curriculum PROMOTE,DEMOTE[,PATIENCE] (Stepper ids; not with --curriculum): ALLSTEPS's curriculum, per env and on the device, through
+`make_vec_envs(curriculum=Curriculum(PROMOTE, DEMOTE, PATIENCE))` -- an episode that ends with steps_reached >= PROMOTE is a success, one with
+<= DEMOTE a failure, PATIENCE (default 1) of either in a row move that env one level up or down; the rule is one small launch behind every
+step (include/mocca.h mocca_set_curriculum), so the collection loop stays free of host reads.  --curriculum-recycle: an env promoted at level
+9 restarts at a level drawn from 0 .. 9.  Each logged line gains `mean_level` and `level_episodes`, the episodes judged at each level since
+the last line (`envs.curriculum_totals`, read and zeroed at log time).  <out>_policy.npz records the curriculum (`curriculum`, a JSON string).
 --verify-grad also runs the autograd path on the first minibatch of each iteration and prints the largest difference, scaled per tensor
 (--mirror-dup: on that minibatch's rows whose ratio and whose twin's ratio lie more than 1e-4 from the clip bounds, where the surrogate's
 gradient jumps and two float32 evaluations may disagree on a sample's side; the twins' ratios are spread over the bounds); with
@@ -137,6 +144,9 @@ def main(argv=None):
     ap.add_argument("--obs-noise", type=float, default=None, metavar="SCALE", help="uniform noise of this half-width on every column of the policy's observation row")
     ap.add_argument("--rand-privileged", action="store_true", help="with --privileged-critic: the plant's record joins the critic's row, [obs | scan | record]")
     ap.add_argument("--history", default=None, metavar="K[,S]", help="append the last K (observation, action) pairs, S steps apart (default 1), to the policy's row")
+    ap.add_argument("--curriculum", type=int, default=None, metavar="K", help="Stepper ids: every env on the terrain of level K, 0 .. 9")
+    ap.add_argument("--adaptive-curriculum", default=None, metavar="PROMOTE,DEMOTE[,PATIENCE]", help="Stepper ids: every env's own episodes move its own level on the device")
+    ap.add_argument("--curriculum-recycle", action="store_true", help="with --adaptive-curriculum: an env promoted at level 9 restarts at a level drawn from 0 .. 9")
     ap.add_argument("--verify-grad", action="store_true", help="with --device-grad: also run the autograd path on the first minibatch of each iteration and print the largest scaled difference")
     args = ap.parse_args(argv)
     if args.device_grad and not args.device_returns:
@@ -175,11 +185,22 @@ def main(argv=None):
         ap.error("--privileged-critic requires --privileged-scan and is not for --distill-from / --symmetric / --mirror-loss / --mirror-dup")
     if args.rand_privileged and not args.privileged_critic:
         ap.error("--rand-privileged requires --privileged-critic: the record is the tail of the critic's row")
+    if (args.curriculum is not None or args.adaptive_curriculum is not None) and "Stepper" not in args.env_id:
+        ap.error("--curriculum / --adaptive-curriculum are for the Stepper ids: the other tasks have no curriculum levels")
+    if args.curriculum is not None and (args.adaptive_curriculum is not None or not 0 <= args.curriculum <= 9):
+        ap.error("--curriculum takes a level 0 .. 9 and is not for --adaptive-curriculum, which moves the levels itself")
+    if args.curriculum_recycle and args.adaptive_curriculum is None:
+        ap.error("--curriculum-recycle requires --adaptive-curriculum")
     import torch
     import torch.nn as nn
     from mocca_envs_amd.trainer_api import make_vec_envs
     torch.manual_seed(args.seed)
     extra = {}
+    cur = None
+    if args.adaptive_curriculum is not None:
+        from mocca_envs_amd.curriculum import Curriculum
+        cur = Curriculum(*(int(v) for v in args.adaptive_curriculum.split(",")), recycle=args.curriculum_recycle)
+        extra["curriculum"] = cur
     rand = None
     if any(v is not None for v in (args.rand_strength, args.rand_latency, args.rand_push, args.obs_noise)) or args.rand_privileged:
         from mocca_envs_amd.randomisation import Randomisation
@@ -212,6 +233,8 @@ def main(argv=None):
     if args.terrain_bank:
         extra["terrain_bank"] = dict(n_fields=args.terrain_bank, seed=args.terrain_seed, gain=args.terrain_gain, redraw_at_reset=True)
     envs = make_vec_envs(args.env_id, seed=args.seed, num_processes=args.envs, record_events=False, **extra)
+    if args.curriculum is not None:
+        envs.set_env_params({"curriculum": args.curriculum})      # (before the first reset, which lays the terrain out)
     dev, N, T = envs.device, args.envs, args.steps
     od, ad = envs.observation_space.shape[0], envs.action_space.shape[0]
     if (args.depth_camera is not None or hist is not None) and od > 336:
@@ -552,6 +575,12 @@ def main(argv=None):
                 ld_sum.zero_(); ld_n = 0
             if "Stepper" in args.env_id:      # next_step_index of the running episodes (the step's info word): how far along the 20 planks the batch is
                 line["mean_next_step_index"] = float(envs.venv.info.float().mean().item())
+            if cur is not None:      # read here, at log time: the collection loop stays free of synchronisation
+                line["mean_level"] = float(envs.curriculum_levels.float().mean().item())
+                line["level_episodes"] = [int(v) for v in envs.curriculum_totals[:, 0].cpu().numpy()]
+                envs.curriculum_totals.zero_()
+            elif args.curriculum is not None:
+                line["mean_level"] = float(args.curriculum)
             log.write(json.dumps(line) + "\n"); log.flush()
             print(json.dumps(line), flush=True)
             if wall > 60.0 * args.minutes:
@@ -567,7 +596,8 @@ def main(argv=None):
              **{f"vf_{k.replace('.', '_')}": v.detach().cpu().numpy() for k, v in vf.state_dict().items()},
              env_id=np.array(args.env_id), env_steps=np.array(total_steps), **extra_stats,
              **({} if rand is None else dict(randomisation=np.array(json.dumps(rand.as_dict())))),
-             **({} if hist is None else dict(history=np.array(json.dumps(hist.as_dict())))))
+             **({} if hist is None else dict(history=np.array(json.dumps(hist.as_dict())))),
+             **({} if cur is None else dict(curriculum=np.array(json.dumps(cur.as_dict())))))
     envs.close()
 
 

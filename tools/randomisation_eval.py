@@ -4,12 +4,14 @@ sensors -- or none, the plain plant.
 
     python tools/randomisation_eval.py --policy NAME=FILE [--policy NAME=FILE ...] [--env-id Walker3DCustomEnv-v0] [--envs 1024]
                                        [--rand-strength LO,HI] [--rand-latency LO,HI] [--rand-push INTERVAL,MAX] [--obs-noise SCALE]
-                                       [--condition LABEL] [--out FILE.jsonl]
+                                       [--curriculum K[,K ...]] [--condition LABEL] [--out FILE.jsonl]
 
 Per policy every env plays ONE episode with the mean action (no action noise; the sensor noise of the condition is applied): mean return and
 mean length over the envs, one JSON line per policy, appended to --out, with the condition and the randomisation the policy's file says it
 was trained under.  A policy trained with an observation-action history (ppo_demo.py --history; its file records the `History`) plays on
-an env rebuilt with the same history: its rows are [obs | hist] again.  Reported, not gated.
+an env rebuilt with the same history: its rows are [obs | hist] again.  --curriculum K[,K ...] (Stepper ids): one cell per level, every
+env on the terrain of the fixed level K (e.g. 0,5,9 for a policy trained with ppo_demo.py --curriculum / --adaptive-curriculum); each line
+then carries `curriculum` and `mean_steps_reached`, the mean of steps_reached over the episodes.  Reported, not gated.
 """
 from __future__ import annotations
 
@@ -31,6 +33,7 @@ def main(argv=None):
     ap.add_argument("--rand-latency", default=None, metavar="LO,HI")
     ap.add_argument("--rand-push", default=None, metavar="INTERVAL,MAX")
     ap.add_argument("--obs-noise", type=float, default=None, metavar="SCALE")
+    ap.add_argument("--curriculum", default=None, metavar="K[,K ...]", help="Stepper ids: evaluate at each of these fixed curriculum levels, one line per level")
     ap.add_argument("--condition", default=None, help="a label for the lines written (default: 'randomised' with any --rand-* / --obs-noise flag, else 'plain')")
     ap.add_argument("--seed", type=int, default=12345)
     ap.add_argument("--max-steps", type=int, default=1001)
@@ -46,7 +49,10 @@ def main(argv=None):
                          push=pair(args.rand_push, (int, float), (0, 0.0)), obs_noise=args.obs_noise) if randomised else None
     condition = args.condition or ("randomised" if randomised else "plain")
     n = args.envs
-    for spec in args.policy:
+    levels = [None] if args.curriculum is None else [int(v) for v in args.curriculum.split(",")]
+    if args.curriculum is not None and ("Stepper" not in args.env_id or not all(0 <= k <= 9 for k in levels)):
+        ap.error("--curriculum takes levels 0 .. 9 of a Stepper id")
+    for spec, level in ((s, k) for s in args.policy for k in levels):
         name, path = spec.split("=", 1)
         z = np.load(path, allow_pickle=False)
         dev = torch.device("cuda", 0)
@@ -64,14 +70,17 @@ def main(argv=None):
             hist = History.from_dict(json.loads(str(z["history"])))
         envs = make_vec_envs(args.env_id, seed=args.seed, num_processes=n, record_events=False, **({} if rand is None else dict(randomisation=rand)),
                              **({} if hist is None else dict(history=hist)))
+        if level is not None:
+            envs.set_env_params({"curriculum": level})      # (before the reset, which lays the terrain out)
         obs = envs.reset()
         alive = torch.ones(n, device=dev)
-        ret, length = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        ret, length, reached = torch.zeros(n, device=dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
         with torch.no_grad():
             for t in range(args.max_steps):
                 obs, rew, _, _ = envs.step(act(obs))
                 ret += alive * rew.reshape(-1)
                 length += alive
+                reached += alive * (1.0 - envs.masks.reshape(-1)) * envs.venv.info      # the info word of the step that ends the episode
                 alive = alive * envs.masks.reshape(-1)
                 if t % 100 == 99 and float(alive.sum()) == 0.0:
                     break
@@ -80,6 +89,8 @@ def main(argv=None):
                 "evaluated_under": None if rand is None else rand.as_dict(),
                 "trained_under": json.loads(str(z["randomisation"])) if "randomisation" in z.files else None,
                 "history": None if hist is None else hist.as_dict()}
+        if level is not None:
+            line.update(curriculum=level, mean_steps_reached=float(reached.mean()))
         print(json.dumps(line), flush=True)
         if args.out:
             with open(args.out, "a") as f:
